@@ -28,6 +28,57 @@ FP64_MFMA_PEAK_TFLOPS = 78.6
 # (tools/scratch/bw_probe.hip; the guide says ~6.3), v_mfma_f64_16x16x4_f64 alone 72 TFLOP/s at 8 waves/SIMD (tools/ubench.hip)
 HBM_ACHIEVABLE_GBS = 6300.0
 FP64_MFMA_ACHIEVABLE_TFLOPS = 72.0
+DUMP_WALKERS = 16384  # --dump-outputs: per-walker arrays are cut to a fixed sample of this many walkers (configs: 24 MB at 64 electrons)
+DUMP_MAX_BYTES = 64 * 2**20
+
+
+def dump_outputs(path, arrays, walker_arrays):
+    """--dump-outputs: what the timed path handed its caller after its last step, one float64 DIR/<name>.npy per array.
+    ``walker_arrays`` (leading axis = walker) are cut to a sample of DUMP_WALKERS walkers drawn with a fixed seed, the same in
+    every run and build with the same walker count; walker_index.npy lists it.  Complex arrays add <name>_imag.npy."""
+    import numpy as np
+
+    W = len(next(iter(walker_arrays.values())))
+    idx = np.arange(W) if W <= DUMP_WALKERS else np.sort(np.random.default_rng(0).choice(W, DUMP_WALKERS, replace=False))
+    out = {}
+    for k, v in list(arrays.items()) + [(k, np.asarray(v)[idx]) for k, v in walker_arrays.items()] + [("walker_index", idx)]:
+        v = np.asarray(v)
+        out[k] = np.ascontiguousarray(v.real, dtype=np.float64)
+        if np.iscomplexobj(v):
+            out[k + "_imag"] = np.ascontiguousarray(v.imag, dtype=np.float64)
+    nbytes = sum(v.nbytes for v in out.values())
+    if nbytes > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {nbytes} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    if not os.path.isdir(path):  # a directory made here ignores itself (git), wherever the caller puts it
+        os.makedirs(path)
+        with open(os.path.join(path, ".gitignore"), "w") as f:
+            f.write("*\n")
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    print(f"[bench] --dump-outputs: {len(out)} arrays, {nbytes} bytes -> {path}", file=sys.stderr, flush=True)
+
+
+def build_or_check(ge):
+    """ge.build(), unless the tree is built and this user cannot write its build directory: build() rewrites its flag stamp on
+    every call, so it cannot run there (the parent tree of an output comparison between two builds may be read-only to whoever
+    benchmarks it).  Such a library is measured as built, after the completeness check build() ends with."""
+    stamp = os.path.join(ge.LIBDIR, "obj", "flags.txt")
+    if not os.path.exists(ge.LIB) or os.access(stamp if os.path.exists(stamp) else ge.LIBDIR, os.W_OK):
+        ge.build()
+        return
+    from pyqmc_amd import _ffi
+
+    missing = [s for s in _ffi.header_symbols() if not hasattr(_ffi.lib(), s)]
+    if missing:
+        raise SystemExit(f"{ge.LIB} lacks symbols declared in include/pyqmc_amd.h: {missing}")
+    print(f"[bench] {ge.LIBDIR} is read-only: measuring the library as built", file=sys.stderr, flush=True)
+
+
+def dump_vmc(path, dev, acc, en):
+    """--dump-outputs of the VMC modes: vmc_sweeps' results for the last timed step (acceptance; walker means of ke, ee, ei, ecp,
+    grad2, total) and the walkers it leaves on the device (coordinates, sign and log |Psi|)."""
+    sign, logv = dev.value()
+    dump_outputs(path, {"acceptance": acc[-1:], "energy": en[-1]}, {"configs": dev.configs(), "sign_psi": sign, "log_psi": logv})
 
 
 def _newest(pattern):
@@ -274,6 +325,8 @@ def c4_bench(args, torch, dist, rank, local_rank, world, red_dev, fence):
     if dist is not None:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_vmc(args.dump_outputs, dev, acc, en)
     info = rank_table(torch, dist, rank, local_rank, world)
     if rank == 0:
         print(json.dumps({
@@ -317,9 +370,9 @@ def dmc_bench(args, torch, dist, rank, local_rank, world, red_dev, fence):
     stats = {"moved": 0, "bytes": 0, "blocks": 0, "gather_s": 0.0, "exchange_s": 0.0, "state_s": 0.0}
     wrng = np.random.default_rng(4242 + rank)
 
-    def block(current):
+    def block(current, nsteps=nsb):
         nonlocal cfg, weights
-        blk, cfg, weights = dmc_propagate(wf, cfg, weights, 0.02, 10 * esig, eref, eref, nsteps=nsb, accumulators=acc, state_current=current)
+        blk, cfg, weights = dmc_propagate(wf, cfg, weights, 0.02, 10 * esig, eref, eref, nsteps=nsteps, accumulators=acc, state_current=current)
         pdist.allreduce_block([blk["energytotal"] * blk["weight"] * W, blk["weight"] * W], W, device=red_dev)
         if args.unbalance > 0:  # rehearsal: the shards' total weights pushed apart so that the comb re-assigns walkers across ranks
             weights = weights * (1.0 + args.unbalance * (rank % 2)) * np.exp(0.3 * wrng.standard_normal(len(weights)))
@@ -331,11 +384,11 @@ def dmc_bench(args, torch, dist, rank, local_rank, world, red_dev, fence):
     for i in range(max(args.warmup, 1)):
         block(i > 0)
     stats.update(moved=0, bytes=0, blocks=0, gather_s=0.0, exchange_s=0.0, state_s=0.0)
-    nblocks = max((args.steps + nsb - 1) // nsb, 1)
+    nblocks = (args.steps + nsb - 1) // nsb  # the last block is shorter when --steps is not a multiple of nsb
     fence()
     t0 = time.perf_counter()
-    for _ in range(nblocks):
-        blk = block(True)
+    for b in range(nblocks):
+        blk = block(True, min(nsb, args.steps - b * nsb))
     fence()
     elapsed = time.perf_counter() - t0
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -345,6 +398,11 @@ def dmc_bench(args, torch, dist, rank, local_rank, world, red_dev, fence):
     tbytes = torch.tensor([float(stats["bytes"])], dtype=torch.float64, device=red_dev)
     if dist is not None:
         dist.all_reduce(tbytes)
+    if args.dump_outputs and rank == 0:  # the last block's averages and the walkers, weights after its comb
+        from pyqmc_amd.energy import KEYS
+
+        dump_outputs(args.dump_outputs, {"energy": [blk["energy" + k] for k in KEYS], **{k: [blk[k]] for k in ("acceptance", "tmove_acceptance", "weight")}},
+                     {"configs": cfg.configs, "weights": weights})
     state_err = None
     if args.check_state:  # after the exchanges: the resident state (kept walkers gathered, arrivals recomputed) against a fresh recompute
         logv = dev.value()[1]
@@ -354,14 +412,16 @@ def dmc_bench(args, torch, dist, rank, local_rank, world, red_dev, fence):
         state_err = float(chk.item())
     info = rank_table(torch, dist, rank, local_rank, world)
     if rank == 0:
-        steps = nblocks * nsb
+        steps = args.steps
         print(json.dumps({
             "metric": "walker-steps/sec (DMC, diamond 2x2x2 supercell 64e- Slater-Jastrow, tstep 0.02)", "value": total * steps / elapsed,
             "unit": "walker-steps/s", "n_gpus": world, "steps": steps, "warmup": max(args.warmup, 1) * nsb, "ms_per_step": 1e3 * elapsed / steps,
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": "BASELINE config C5: diamond 2x2x2 supercell (16 atoms, 64 e-, 8 k-points, ccECP-shaped synthetic tables), DMC "
                                    "tstep 0.02 with T-moves and Ewald energies; blocks of 5 steps + block reduction + distributed stochastic comb",
-                       "walkers_per_gpu": W, "global_walkers": total, "parallelism": f"walker-sharded x{world}"},
+                       "walkers_per_gpu": W, "global_walkers": total, "parallelism": f"walker-sharded x{world}",
+                       "timed_blocks": f"{args.steps // nsb} x {nsb} steps" + (f" + 1 x {args.steps % nsb} (every block also pays the block reduction and "
+                                       f"the comb, so ms_per_step is higher than at a multiple of {nsb} steps)" if args.steps % nsb else "")},
             **info, "energy_total": float(blk["energytotal"]), "acceptance": float(blk["acceptance"]), "tmove_acceptance": float(blk["tmove_acceptance"]),
             "state_vs_recompute": state_err,
             "branching": {"blocks": stats["blocks"], "walkers_moved_per_block": stats["moved"] / max(stats["blocks"], 1),
@@ -399,7 +459,11 @@ def main():
                     "recompute (max |log Psi| difference over all ranks -> state_vs_recompute)")
     ap.add_argument("--device-buffers", action="store_true", help="--mode dmc under gloo: pack / unpack the exchanged walkers in GPU tensors and hand the "
                     "library device pointers (the RCCL code path with gloo as the transport only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what they returned for the last step to DIR/<name>.npy "
+                    "(float64; per-walker arrays of rank 0's shard as a fixed sample of at most %d walkers; at most 64 MB in all)" % DUMP_WALKERS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     for v in ("OMP_NUM_THREADS", "MKL_NUM_THREADS", "OPENBLAS_NUM_THREADS"):
         os.environ.setdefault(v, "1")
@@ -427,7 +491,7 @@ def main():
     import __graft_entry__ as ge
 
     if rank == 0:
-        ge.build()
+        build_or_check(ge)
     if dist is not None:
         dist.barrier()
     import pyqmc_amd as pa
@@ -492,6 +556,8 @@ def main():
     if not args.no_profile:
         dev.profile_enable(False)
     ecp_pts = dev.last_ecp_points()
+    if args.dump_outputs and rank == 0:  # before extra_measurements moves the walkers on
+        dump_vmc(args.dump_outputs, dev, acc, en)
 
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
     if dist is not None:

@@ -172,6 +172,25 @@ def g_ao_high_l():
          deriv2=ev.eval_gto("GTOval_sph_deriv2", pts), max_l=np.array(ev.max_l))
 
 
+def g_sph_high():
+    """G39: the reference's real solid harmonics of l = 4, 5 (numba/spherical_harmonics.py:198-378, :636-739) at 20 points — the
+    value-only routine and the value + gradient routine, block l of their output — for tools/gen_solid_harmonics.py --check."""
+    import pyqmc.wf.numba.spherical_harmonics as ref
+
+    pts = np.random.default_rng(1).standard_normal((20, 3))
+    out = {"pts": pts}
+    for l, (fv, fg) in {4: (ref.SPH4, ref.SPH4_GRAD), 5: (ref.SPH5, ref.SPH5_GRAD)}.items():
+        rows = {k: [] for k in ("val", "gval", "dx", "dy", "dz")}
+        for x, y, z in pts:
+            s, dx, dy, dz, s2 = (np.zeros((l + 1) ** 2) for _ in range(5))  # the reference fills every l' <= l; block l starts at l^2
+            fg(x, y, z, x * x, y * y, z * z, s, dx, dy, dz)
+            fv(x, y, z, x * x, y * y, z * z, s2)
+            for k, a in zip(("gval", "dx", "dy", "dz", "val"), (s, dx, dy, dz, s2)):
+                rows[k].append(a[l * l:])
+        out.update({f"l{l}_{k}": np.array(v) for k, v in rows.items()})
+    save("g39_sph_high", **out)
+
+
 # ------------------------------------------------------------------ G4 func3d
 def g_func3d():
     r = np.concatenate([np.linspace(0.05, 2.2, 40), [1.5, 1.5 - 1e-9, 1.5 + 1e-9, 7.4999, 7.5, 9.0]])
@@ -1776,6 +1795,7 @@ if __name__ == "__main__":
     g_sherman_morrison()
     g_ao()
     g_ao_high_l()
+    g_sph_high()
     g_func3d()
     g_protocol()
     g_energy()
