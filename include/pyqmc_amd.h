@@ -413,6 +413,17 @@ int pqa_philox_tapes(pqa_handle_t* h, uint64_t seed, int step, int64_t W, double
    Test entry: the CPU oracle's dmc_propagate (pyqmc/method/dmc.py:123-221) replays a device-RNG block walker by walker. */
 int pqa_philox_dmc_tapes(pqa_handle_t* h, uint64_t seed, int nsteps, int64_t W, pqa_dmc_tapes_t* out);
 
+/* ---- total spin ----------------------------------------------------------------------- */
+/* S2Accumulator.__call__ (pyqmc/observables/s2_accumulator.py): per walker S^2 = Sz(Sz+1) + N_dn - sum_{i up, j dn}
+   Psi(R^{i<->j})/Psi(R), where R^{i<->j} puts up electron i at r_j and down electron j at r_i.  The swap ratios come in closed
+   form from the resident state (orbitals of each spin at the other spin's electrons times the inverses, the Jastrow sums of
+   every electron), which the call does not modify.  s2 (W); ratios (W, N_up, N_dn) = the swap ratios, or NULL.  Fused scope:
+   real handles with a Slater factor (one or more determinants), with or without the two-body Jastrow, open or periodic at
+   Gamma; N_dn = 0 (or N_up = 0) returns Sz(Sz+1) + N_dn without a launch.  Complex / twisted handles and handles with a
+   three-body Jastrow factor are refused (<0): the swap ratios of those go through the protocol route
+   (pyqmc_amd.S2Accumulator). */
+int pqa_s2(pqa_handle_t* h, double* s2, double* ratios);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* HIP-event timing on the handle's own stream (torch.cuda.Event only sees torch's stream). */
 int pqa_timer_start(pqa_handle_t* h);

@@ -1,0 +1,101 @@
+"""Total-spin estimator — public interface of ``pyqmc/observables/s2_accumulator.py`` (``S2Accumulator``).
+
+For fixed electron counts Sz = (N_up - N_dn)/2 is sharp and S^2 = Sz(Sz+1) + S_- S_+, whose local value is
+
+    S^2_loc(R) = Sz(Sz+1) + N_dn - sum_{i up, j dn} Psi(R^{i<->j}) / Psi(R),
+
+R^{i<->j} putting up electron i at r_j and down electron j at r_i.  Two routes compute the swap ratios:
+
+* **fused** (``pqa_s2``): real wave functions living on one device handle — Slater (one or more determinants), optionally times
+  JastrowSpin, open or periodic at Gamma.  The ratios come in closed form from the resident state (pqa_s2.hip) and the state is
+  not modified.
+* **protocol**: every other wave function (complex orbitals, twisted cells, a three-body Jastrow factor, the CPU oracle's
+  objects, ...).  Per pair: up electron i is moved to r_j (``testvalue`` + ``configs.move`` + ``updateinternals``), the ratio of
+  moving down electron j to r_i is read with ``testvalue``, and i is moved back; ``wf.recompute(configs)`` at the end leaves the
+  wave function describing ``configs`` without the round-off of the unwinding moves.
+
+``last_route`` names the route of the last evaluation ("fused" or "protocol").
+"""
+
+import numpy as np
+
+from . import _ffi
+
+
+def device_s2(dev, with_ratios=False):
+    """``pqa_s2`` on a device handle: S^2 (W) of the resident walkers and, with ``with_ratios``, the swap ratios (W, N_up, N_dn)."""
+    nu, nd = dev.nelec
+    s2 = np.empty(dev.W)
+    rat = np.empty((dev.W, nu, nd)) if with_ratios else None
+    dev.call("pqa_s2", _ffi.ptr(s2), None if rat is None else _ffi.ptr(rat))
+    return (s2, rat) if with_ratios else s2
+
+
+def fused_handle(wf):
+    """The device handle ``pqa_s2`` can evaluate ``wf`` on, or None: ``wf`` must be exactly the handle's factors (a Slater
+    factor, plus the two-body Jastrow when the handle has one), real, not twisted, without a three-body factor."""
+    from .wf import JastrowSpin, MultiplyWF, Slater
+
+    factors = wf.wf_factors if isinstance(wf, MultiplyWF) else [wf]
+    kinds = [type(f) for f in factors]
+    if any(k not in (Slater, JastrowSpin) for k in kinds) or len(set(kinds)) != len(kinds) or Slater not in kinds:
+        return None
+    dev = wf.fused_device() if isinstance(wf, MultiplyWF) else getattr(wf, "_dev", None)
+    if dev is None or not hasattr(dev, "vmc_sweeps"):
+        return None
+    if not dev.has_slater or dev.cplx or dev.twisted or dev.has_j3 or dev.has_jastrow != (JastrowSpin in kinds):
+        return None
+    return dev
+
+
+class S2Accumulator:
+    """Local estimator of <S^2> (s2_accumulator.py): ``__call__`` -> {"S2": (nconf,)}, ``avg`` -> {"S2": mean}.
+
+    nelec: (n_up, n_dn); electrons 0 .. n_up-1 are spin up, the rest spin down (the Slater convention)."""
+
+    def __init__(self, nelec):
+        self.nelec = tuple(int(n) for n in nelec)
+        nu, nd = self.nelec
+        self.sz = 0.5 * (nu - nd)
+        self.last_route = None
+
+    def __call__(self, configs, wf):
+        dev = fused_handle(wf)
+        if dev is not None and tuple(dev.nelec) == self.nelec and dev.W == configs.configs.shape[0]:
+            # the handle's resident walkers are `configs` (the drivers fetch them from the device before any host accumulator)
+            self.last_route = "fused"
+            return {"S2": device_s2(dev)}
+        self.last_route = "protocol"
+        return {"S2": self._protocol(configs, wf)}
+
+    def _protocol(self, configs, wf):
+        nu, nd = self.nelec
+        nconf = configs.configs.shape[0]
+        accept = np.ones(nconf, dtype=bool)
+        orig = configs.configs.copy()
+        swap = np.zeros(nconf, dtype=wf.dtype)
+        for i in range(nu):
+            for j in range(nu, nu + nd):
+                new_i = configs.make_irreducible(i, orig[:, j].copy())
+                r1, saved = wf.testvalue(i, new_i)
+                configs.move(i, new_i, accept)
+                wf.updateinternals(i, new_i, configs, mask=accept, saved_values=saved)
+                r2, _ = wf.testvalue(j, configs.make_irreducible(j, orig[:, i].copy()))
+                swap += r1 * r2
+                back = configs.make_irreducible(i, orig[:, i].copy())
+                _, saved = wf.testvalue(i, back)
+                configs.move(i, back, accept)
+                wf.updateinternals(i, back, configs, mask=accept, saved_values=saved)
+        configs.configs[...] = orig
+        if nu and nd:
+            wf.recompute(configs)
+        return self.sz * (self.sz + 1) + nd - swap
+
+    def avg(self, configs, wf):
+        return {k: np.mean(v, axis=0) for k, v in self(configs, wf).items()}
+
+    def keys(self):
+        return self.shapes().keys()
+
+    def shapes(self):
+        return {"S2": ()}
