@@ -71,9 +71,9 @@ __device__ __forceinline__ R8Pair r8_sel(bool c, const R8Pair& a, const R8Pair& 
 // electron e left where it is / moved to its proposal.  Nothing here needs the orbitals, so the kernel runs it ahead of the AO phase, where
 // the two serial evaluations of k_sweep_res (2.3 + 2.1 us of dependent chains behind the contraction) are out of the move's critical path
 // and the registers are free.  Per lane the pairs enter the sums in the order of res_jas_m (up partner, down partner, ion): the sums are
-// the ones k_sweep_res forms.
+// the ones k_sweep_res forms.  yst: two doubles of this walker's scalars.
 template <bool NEXT>
-__device__ __forceinline__ void r8_jas_dual(const SysDev& S, int r, const double (&cx)[2], const double (&cy)[2], const double (&cz)[2],
+__device__ __forceinline__ void r8_jas_dual(const SysDev& S, int r, double* yst, const double (&cx)[2], const double (&cy)[2], const double (&cz)[2],
                                             const double* __restrict__ at_xyz, const double* __restrict__ acoef, const double* __restrict__ aq,
                                             const double* __restrict__ jt, int e, double nx, double ny, double nz, int ep, double ox, double oy,
                                             double oz, ResJ& jn, ResJ& joR, ResJ& joA) {
@@ -90,36 +90,52 @@ __device__ __forceinline__ void r8_jas_dual(const SysDev& S, int r, const double
   const double c0 = jt[3 * PQA_JQ + 10 + se], c1 = jt[3 * PQA_JQ + 11 + se];
   // ion partner(s) of this lane: atom r, and atom r + 32 of molecules with more than 32 atoms (second pass below)
   auto ion = [&](int I, double x, double y, double z) __attribute__((always_inline)) {
-    const int Ic = I < S.natom ? I : 0;
+    // (a lane without an ion — its pair is discarded — reads the record of the last ion when that ion's lane shares its 16-lane LDS group:
+    // one address, a broadcast.  Ion 0's record, read before, can share a bank with a record read in that group — ion 16's in a 24-atom
+    // system, a 2-way conflict in every ds_read2_b64 of the record)
+    const int Ic = I < S.natom ? I : (S.natom - 1 >= (I & ~15) ? S.natom - 1 : 0);
     const double* qrec = aq + ((size_t)se * S.natom + Ic) * PQA_JQP;  // (conflict-free record layout of the LDS copy, pqa_res.hpp)
     return r8_pair(S.na > 0 && I < S.natom, x - at_xyz[3 * Ic], y - at_xyz[3 * Ic + 1], z - at_xyz[3 * Ic + 2], S.rcut_a, ira, Da, qrec, acp, aca, qrec[PQA_JQ]);
   };
-  // The seven pairs of the move (three of the decided electron, four of the next one), ONE AT A TIME, the ion pairs inside (one-trip) loops:
+  // The six pairs of the move (three of the decided electron, three of the next one), ONE AT A TIME, the ion pairs inside (one-trip) loops:
   // a pair's own chains (denominator and two numerator polynomials, the cusp function) already run side by side, and every attempt to run
   // pairs side by side — two, three or all seven in one basic block — made the compiler hold their LDS operands early and spill a quarter of
   // the inverse row across this block (17-22 scratch stores and reloads per move: 19-21 us per move of two resident blocks against 17.2).
   const int nion = S.natom > 32 ? 2 : 1;
+  // The accepted case's pair of ep with e at its proposal, pair(ep at o, e at n), is pair(e at n, ep at o) of e's own evaluation in lane
+  // ip = i + 1 (na_ / nb_: same channel, same valid flag, and dx = -(o - n) exactly, so x, r and the terms u, sg are the same bits): its u
+  // and sg go through the walker's scalars yst[0..1] (lane ip writes, every lane reads: nothing is held in registers across the pairs
+  // between) instead of a seventh evaluation; the displacement o - n is formed below.
+  const bool yw = ep - (se ? S.nup : 0) == r;
   const R8Pair na_ = r8_pair(v0 && j0 != e, nx - cx[0], ny - cy[0], nz - cz[0], S.rcut_b, irb, Db, q0, bcp, bca, c0);
   r8_acc(jn, na_);
+  if (NEXT && se == 0 && yw) { yst[0] = na_.du; yst[1] = na_.sg; }
   __builtin_amdgcn_sched_barrier(0);
   const R8Pair nb_ = r8_pair(v1 && j1 != e, nx - cx[1], ny - cy[1], nz - cz[1], S.rcut_b, irb, Db, q0 + PQA_JQ, bcp, bca, c1);
   r8_acc(jn, nb_);
+  if (NEXT && se == 1 && yw) { yst[0] = nb_.du; yst[1] = nb_.sg; }
   __builtin_amdgcn_sched_barrier(0);
   for (int q = 0; q < nion; ++q) { const R8Pair nc_ = ion(r + 32 * q, nx, ny, nz); r8_acc(jn, nc_); }
   if (NEXT) {  // ---- the next electron at its current position: partner e at its old place (R) or at its proposal (A)
     __builtin_amdgcn_sched_barrier(0);
-    // the partner slot of e's spin twice: e where it is (R) and at its proposal (A; the same pair again in every lane but e's own)
+    // the partner slot of e's spin twice: e where it is (R) and at its proposal (A; the same pair again in every lane but e's own, whose
+    // terms come from lane ip above)
     const bool mine = (se ? j1 : j0) == e;
     const double px_ = mine ? nx : (se ? cx[1] : cx[0]), py_ = mine ? ny : (se ? cy[1] : cy[0]), pz_ = mine ? nz : (se ? cz[1] : cz[0]);
-    const R8Pair y = r8_pair((se ? v1 : v0) && (se ? j1 : j0) != ep, ox - px_, oy - py_, oz - pz_, S.rcut_b, irb, Db, q0 + se * PQA_JQ, bcp, bca, se ? c1 : c0);
-    __builtin_amdgcn_sched_barrier(0);
+    res_wave_sync();  // (lane ip's stores to yst before the reads)
+    const double ydu = yst[0], ysg = yst[1];
+    auto acc_y = [&](const R8Pair& own) __attribute__((always_inline)) {
+      R8Pair y;
+      y.du = mine ? ydu : own.du; y.sg = mine ? ysg : own.sg; y.dx = ox - px_; y.dy = oy - py_; y.dz = oz - pz_;
+      r8_acc(joA, y);
+    };
     const R8Pair a = r8_pair(v0 && j0 != ep, ox - cx[0], oy - cy[0], oz - cz[0], S.rcut_b, irb, Db, q0, bcp, bca, c0);
     r8_acc(joR, a);
-    if (se == 0) r8_acc(joA, y); else r8_acc(joA, a);  // (wave-uniform)
+    if (se == 0) acc_y(a); else r8_acc(joA, a);  // (wave-uniform)
     __builtin_amdgcn_sched_barrier(0);
     const R8Pair b = r8_pair(v1 && j1 != ep, ox - cx[1], oy - cy[1], oz - cz[1], S.rcut_b, irb, Db, q0 + PQA_JQ, bcp, bca, c1);
     r8_acc(joR, b);
-    if (se == 1) r8_acc(joA, y); else r8_acc(joA, b);
+    if (se == 1) acc_y(b); else r8_acc(joA, b);
     __builtin_amdgcn_sched_barrier(0);
     for (int q = 0; q < nion; ++q) { const R8Pair c = ion(r + 32 * q, ox, oy, oz); r8_acc(joR, c); r8_acc(joA, c); }
   }
@@ -313,8 +329,8 @@ static __global__ __launch_bounds__(PQA_R8_NT, 2) void k_sweep_r8(SysDev S, LwSt
           const double pox = __shfl(s ? cx[1] : cx[0], srcn, 64), poy = __shfl(s ? cy[1] : cy[0], srcn, 64), poz = __shfl(s ? cz[1] : cz[0], srcn, 64);
           ResJ jn{0.0, 0.0, 0.0, 0.0}, jr{0.0, 0.0, 0.0, 0.0}, ja{0.0, 0.0, 0.0, 0.0};
           if (S.jq_on) {
-            if (nxt) r8_jas_dual<true>(S, r, cx, cy, cz, at_xyz, acoef, aql, jt, e, npx, npy, npz, e + 1, pox, poy, poz, jn, jr, ja);
-            else r8_jas_dual<false>(S, r, cx, cy, cz, at_xyz, acoef, aql, jt, e, npx, npy, npz, e + 1, pox, poy, poz, jn, jr, ja);
+            if (nxt) r8_jas_dual<true>(S, r, ws + 28, cx, cy, cz, at_xyz, acoef, aql, jt, e, npx, npy, npz, e + 1, pox, poy, poz, jn, jr, ja);
+            else r8_jas_dual<false>(S, r, ws + 28, cx, cy, cz, at_xyz, acoef, aql, jt, e, npx, npy, npz, e + 1, pox, poy, poz, jn, jr, ja);
           } else {  // any basis, function by function: three plain evaluations (the third with e at its proposal)
             double g3[3];
             res_jas_part<false>(S, e, r, npx, npy, npz, cx, cy, cz, at_xyz, acoef, aql, jn.u, g3);

@@ -6,8 +6,11 @@
 #define PQA_R8_NT 256
 #define PQA_R8_NW 8
 #define PQA_R8_MAXQ 32   // k-steps one wave contracts at most (kt <= 4 * 32 * KW)
-#define PQA_R8_WS 32      // doubles per walker of the per-walker scalars: 0..15 as k_sweep_res; 16..19 U, grad U of the decided electron at its
-                          // proposal; 20..23 the same of the NEXT electron at its current position if the move is rejected, 24..27 if it is accepted
+#define PQA_R8_WS 34      // doubles per walker of the per-walker scalars: 0..15 as k_sweep_res; 16..19 U, grad U of the decided electron at its
+                          // proposal; 20..23 the same of the NEXT electron at its current position if the move is rejected, 24..27 if it is accepted;
+                          // 28, 29 u and sg of the accepted case's pair with the decided electron (r8_jas_dual); 30..33 unused.  34, not 32: the
+                          // AO phase reads the eight walkers' proposals in one instruction (wsc[pt * PQA_R8_WS]), which at a stride of 32 doubles
+                          // (64 banks) all sit on one bank pair, an 8-way conflict; at 34 they sit on eight (4 pt, 4 pt + 1), and rows stay 16-B aligned
 
 struct R8Tab {
   int kt;                   // tile rows: the AOs in their own order, padded to x4 (coefficient copy d_cres[s] [kt][ldc])
