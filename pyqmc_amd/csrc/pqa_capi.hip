@@ -468,34 +468,30 @@ static int create_impl(pqa_handle* h, const pqa_system_t* sys) {
   // A/B switches for the schedule variants compared in DESIGN.md sections 3-4 (all default to the measured best;
   // none of them changes results beyond summation order, tests/test_gpu_parity.py cross-checks the pairs):
   //   PQA_ORB_TP 16|32|64 point tile of k_orb (periodic: pins the automatic choice), PQA_ORB_WS 0|1 wave-specialised k_orb,
-  //   PQA_ORB_NOTAB 1 basis tables from global memory, PQA_ORB_KC5 16|32 AO rows per chunk of the periodic 5-component
-  //   launch, PQA_ORB_NOSPLIT 1 / PQA_ORB_SPLIT_MAX n chunk loop of small periodic launches on one block,
-  //   PQA_LW 0 wave-per-walker sweep | 1 lane-per-walker (default) | 2 walker-tile kernel, PQA_LW_KB k electrons per
-  //   Sherman-Morrison block (0: update every row per move; default 4), PQA_LW_GM g thread groups per walker and PQA_LW_NW
-  //   walkers per block of k_step_lw, PQA_ECP_WAVE 1 wave-per-walker ECP accumulation,
+  //   PQA_ORB_KC5 16|32 AO rows per chunk of the periodic 5-component launch, PQA_ORB_SPLIT_MAX n largest periodic launch whose
+  //   chunk loop is split over two blocks, PQA_LW 0 wave-per-walker sweep | 1 lane-per-walker (default), PQA_LW_KB k electrons per
+  //   Sherman-Morrison block (0: update every row per move; default 4), PQA_LW_GM g thread groups per walker of k_step_lw,
+  //   PQA_ECP_WAVE 1 wave-per-walker ECP accumulation,
   //   PQA_PROF_STRIDE n event brackets on every n-th orbital launch when profiling is enabled,
   //   PQA_PRE_GRID g   sub-cells per axis of the near-candidate masks of the periodic pre-pass (default 16, 8 beyond 32 atoms; 0: every candidate tested)
   //   PQA_PRE_NCUT n   at least n shell cut-off classes in the pre-pass instantiation (5 or 10 are compiled; tests)
   //   PQA_PBC_NW n words (4 image indices each) per (point, atom) image list of the periodic pre-pass (default from the cell;
-  //   1 forces the direct-test fallback: tests), PQA_WIDE_NTH 512 k_orb_wide with 512 threads in untwisted periodic cells,
-  //   PQA_TM_PRE 0 T-move ratios by the wave-per-walker loop only;
+  //   1 forces the direct-test fallback: tests), PQA_TM_PRE 0 T-move ratios by the wave-per-walker loop only;
   //   round 3 (each documented at its field above): PQA_STEP_PRE 0 k_step_lw for small shards too, PQA_DRAWS_MAX n walker count up to
   //   which a sweep's random numbers are drawn ahead, PQA_FLUSH_WB8_MAX n 8-walker flush blocks up to n walkers, PQA_ECP_LDS 0 /
   //   PQA_ECP_POINT_LW 0 first-generation ECP list passes / point kernel, PQA_ECP_ACC_WAVES 1|4 waves per walker in the
   //   wave-per-walker energy kernels, PQA_ECP_ATOM_MAJOR 0 walker-major ECP lists in periodic cells, PQA_JAS_FOLD 0 Voronoi
   //   reduction in every periodic Jastrow pair;
   //   round 4: PQA_STEP_GW 16|32|64 thread groups per walker of k_step_pre, PQA_STEP_PRE_MAX n largest shard that runs it (8192),
-  //   PQA_SPLIT 0..3 / PQA_SPLIT_MIN / PQA_SPLIT_CUS pipelined half-ensembles, PQA_JPRE 1 Jastrow sums ahead on a side stream,
   //   PQA_JAS_MERGE 0 Pade functions one by one instead of the merged rational function (jas_merge_tables),
   //   PQA_ORB_KC5 / PQA_ORB_KC1 16|32 AO rows per chunk of the periodic 5-component / value-only orbital launches.
   //   round 5: PQA_RES 0|1 resident sweep off / forced (default: by shard size, pqa_res.hip res_eligible), PQA_RES_MIN / PQA_RES_MAX walker
   //   window of the automatic choice, PQA_RES_PBC 0 periodic handles keep the launch-per-move sweep, PQA_RES_ICAP n shorter image lists in
   //   the periodic resident sweep (tests), PQA_RES_DEBUG 1 prints the tile / LDS plan, PQA_ORB_GENERAL 1 orbitals of handles beyond 64 per
-  //   spin by k_ao + k_mo_rows instead of the windowed k_orb, PQA_RES_CX 0 complex determinants keep the launch-per-move sweep, PQA_WW 0|1|3
-  //   wave-per-walker sweep in one launch off / forced with one / three waves per walker (default: one wave up to 4096 walkers), PQA_ECP_DEFER 0
+  //   spin by k_ao + k_mo_rows instead of the windowed k_orb, PQA_RES_CX 0 complex determinants keep the launch-per-move sweep, PQA_WW 0|1
+  //   wave-per-walker sweep in one launch off / forced (default: up to 4096 walkers), PQA_ECP_DEFER 0
   //   the ECP point totals are read back at every evaluation, PQA_EN_OVERLAP 0 the kinetic pass of small shards stays in line.
   if (const char* tp = getenv("PQA_ORB_TP")) h->orb_tp = atoi(tp);
-  if (const char* ns = getenv("PQA_ORB_NOSPLIT")) h->orb_nosplit = atoi(ns);
   if (const char* sm = getenv("PQA_ORB_SPLIT_MAX")) h->orb_split_max = atol(sm);
   if (const char* kc = getenv("PQA_ORB_KC5")) h->orb_kc5 = atoi(kc);
   if (const char* kc = getenv("PQA_ORB_KC1")) h->orb_kc1 = atoi(kc);
@@ -515,11 +511,8 @@ static int create_impl(pqa_handle* h, const pqa_system_t* sys) {
   if (const char* wd = getenv("PQA_ORB_WIDE")) h->orb_wide = atoi(wd);
   if (const char* wm = getenv("PQA_ORB_WIDE_MAX")) h->orb_wide_max = atol(wm);
   if (const char* kb = getenv("PQA_LW_KB")) h->lw_kb = atoi(kb);
-  if (const char* nt = getenv("PQA_ORB_NOTAB")) h->orb_notab = atoi(nt);
   if (const char* gm = getenv("PQA_LW_GM")) h->lw_gm = atoi(gm);
-  if (const char* nw = getenv("PQA_LW_NW")) { const int v = atoi(nw); h->lw_nw = (v == 16 || v == 32 || v == 64) ? v : 0; }
   if (const char* ew = getenv("PQA_ECP_WAVE")) h->ecp_wave = atoi(ew);
-  if (const char* es = getenv("PQA_ECP_SOA_T")) h->ecp_soa_t = atoi(es);
   if (const char* ep = getenv("PQA_ECP_POINT_LW")) h->ecp_point_lw = atoi(ep);
   if (const char* el = getenv("PQA_ECP_LDS")) h->ecp_lds = atoi(el);
   if (const char* jf = getenv("PQA_JAS_FOLD")) h->jas_fold_allowed = atoi(jf);
@@ -530,26 +523,13 @@ static int create_impl(pqa_handle* h, const pqa_system_t* sys) {
   if (const char* sp = getenv("PQA_STEP_PRE_MAX")) h->step_pre_max = atol(sp);
   if (const char* dm = getenv("PQA_DRAWS_MAX")) h->draws_max = atol(dm);
   if (const char* fw = getenv("PQA_FLUSH_WB8_MAX")) h->flush_wb8_max = atol(fw);
-  if (const char* sp = getenv("PQA_SPLIT")) h->split_mode = std::max(0, std::min(3, atoi(sp)));
-  if (const char* sp = getenv("PQA_SPLIT_MIN")) h->split_min = std::max(512L, atol(sp));
-  if (const char* sp = getenv("PQA_SPLIT_CUS")) h->split_cus = atoi(sp);
-  if (const char* sp = getenv("PQA_JPRE")) h->jpre = atoi(sp);
   if (const char* sp = getenv("PQA_JAS_MERGE")) h->jas_merge = atoi(sp);
-  if (const char* sp = getenv("PQA_JPRE_MIN")) h->jpre_min = std::max(64L, atol(sp));
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) h->cu_count = prop.multiProcessorCount;
-  }
   h->natom = sys->natom; h->nup = sys->nelec_up; h->ndn = sys->nelec_dn; h->N = h->nup + h->ndn;
   h->nao = sys->nao; h->nshell = sys->nshell;
   h->has_slater = sys->has_slater != 0;
   h->cplx = h->has_slater && sys->complex_orbitals != 0;
   h->twist = sys->twisted != 0;
-  // k_orb_wide: 1024 threads (64 lane groups) per 16-point tile; twisted cells need > 128 registers per thread: 512.  Untwisted
-  // periodic cells fit 128 since the lattice sums accumulate in the tile: C5 +3 % at 1024-8192 walkers over 512 threads.
-  h->wide_nth = (sys->pbc && h->twist) ? 512 : 1024;
   if (const char* e = getenv("PQA_TM_PRE")) h->tm_pre = atoi(e) != 0;
-  if (const char* e = getenv("PQA_WIDE_NTH")) { if (sys->pbc && atoi(e) == 512) h->wide_nth = 512; }
   if (h->twist && !(h->cplx && sys->pbc && sys->nL > 0)) FAIL("twisted boundary conditions need pbc, complex_orbitals and the periodic orbital tables");
   if (h->cplx && ((sys->nmo_up | sys->nmo_dn) & 1)) FAIL("complex orbitals: nmo_up / nmo_dn count the real columns [Re C | Im C] and must be even");
   h->has_j2 = sys->na > 0 || sys->nb > 0;
@@ -758,7 +738,7 @@ static int create_impl(pqa_handle* h, const pqa_system_t* sys) {
       for (int s = 0; s < 2; ++s) { T.cpad[s] = h->d_cpad[t][s]; T.ldc[s] = 16 * h->nt[s]; }
       // k_orb_wide: all shells dealt to 64 lane groups (longest processing time first), tile row of a shell = its padded row
       const int tw = h->twist ? 2 : 1;
-      const int ngrp = h->wide_nth / 16;  // lane groups of k_orb_wide (16 points per block)
+      const int ngrp = h->twist ? 32 : 64;  // lane groups of k_orb_wide (16 points per block, launch_orb_pbc: 512 / 1024 threads)
       std::vector<int> order((size_t)h->nshell), wrow((size_t)tw * h->nshell), woff(65, 0), wsh;
       auto cost = [&](int s) { return h->shell_cost[s]; };
       for (int s = 0; s < h->nshell; ++s) order[s] = s;
@@ -918,12 +898,6 @@ extern "C" void pqa_destroy(pqa_handle_t* h) {
   for (auto& pr : h->prof3_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
-  for (hipEvent_t e : h->pipe_events) (void)hipEventDestroy(e);
-  for (hipStream_t s : h->pipe_stream)
-    if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-  for (hipStream_t s : h->jas_stream)
-    if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-  if (h->b_jpre.p) (void)hipFree(h->b_jpre.p);
   if (h->pin_tot) (void)hipHostFree(h->pin_tot);
   if (h->en_stream) { (void)hipStreamSynchronize(h->en_stream); (void)hipStreamDestroy(h->en_stream); }
   if (h->draw_stream) { (void)hipStreamSynchronize(h->draw_stream); (void)hipStreamDestroy(h->draw_stream); }

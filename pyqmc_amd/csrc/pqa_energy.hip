@@ -47,7 +47,7 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
     TRY(check_launch(h, "k_kinetic_lw"));
     // the ECP kernels read walker-major coordinates; the inverse only when the wave-per-walker accumulation runs (or the
     // caller works on the walker-major state next: the DMC step's T-moves) — the thread-per-point kernel takes the planes
-    soa_T = !aos_T_needed && (!h->cplx || h->ecp_point_lw) && h->ndet == 1 && !h->has_j3 && h->ecp_wave == 0 && h->ecp_soa_t;
+    soa_T = !aos_T_needed && (!h->cplx || h->ecp_point_lw) && h->ndet == 1 && !h->has_j3 && h->ecp_wave == 0;
     if (h->necp > 0) {
       hipStream_t cur = h->stream;
       if (side.h) h->stream = side.main;  // (the ECP passes' input: in their stream)

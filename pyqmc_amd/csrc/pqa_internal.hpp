@@ -24,7 +24,6 @@
 #include "pqa_jastrow.hpp"
 #include "pqa_lw.hpp"
 #include "pqa_slater.hpp"
-#include "pqa_tile.hpp"
 #include "pqa_res.hpp"
 #include "pqa_res8_tab.hpp"
 #include "pqa_dm.hpp"
@@ -55,7 +54,6 @@ struct pqa_handle {
   int na = 0, nb = 0, necp = 0;
   bool tm_pre = true;   // T-move ratios of all candidates in one thread-per-candidate launch (PQA_TM_PRE=0: wave-per-walker loop only)
   bool aos_stale = false;  // the lane-per-walker planes hold the live state; the walker-major arrays are converted back on demand (sync_aos)
-  int wide_nth = 1024;  // threads per block of k_orb_wide (PQA_WIDE_NTH; periodic default 512)
   int pbc_maxcls = PQA_PRE_NCUT;  // most distinct shell cut-offs any atom has (picks the pre-pass instantiation)
   int pbc_nw = 2;  // words per (atom, point) of the sorted image lists k_pbc_prepass writes (4 entries each)
   bool orb_general = false;  // PQA_ORB_GENERAL=1: big open handles evaluate orbitals by k_ao + k_mo_rows instead of the windowed k_orb (A/B, tests)
@@ -106,7 +104,6 @@ struct pqa_handle {
   DevBuf b_pts, b_motmp, b_out, b_widx, b_mask, b_ao, b_flag, b_newpos, b_aux, b_accept, b_accrec, b_acccnt, b_accw, b_dwrap, b_wrap, b_epass, b_eptw[2], b_econ[2], b_eu0[2], b_tves, b_pgdet, b_pbcd0, b_pbcmask, b_pbcth, b_tmuold;
   int* d_colmap[2] = {nullptr, nullptr};  // [ndet_s][nmo_s] column of an orbital in a unique determinant, or -1
   int ecp_wave = 0;  // PQA_ECP_WAVE=1: wave-per-walker ECP accumulation (A/B)
-  int ecp_soa_t = 1;  // PQA_ECP_SOA_T=0: transpose the inverse back for the ECP point kernel (A/B)
   int ecp_point_lw = 1;  // PQA_ECP_POINT_LW=0: k_ecp_point on the planes instead of k_ecp_point_lw (A/B)
   long flush_wb8_max = 8192;  // PQA_FLUSH_WB8_MAX: walker counts up to which k_flush_lw runs with 8 walkers per block
   long draws_max = 16384;  // PQA_DRAWS_MAX: walker counts up to which a fused sweep draws its random numbers ahead (k_tile_draws)
@@ -130,11 +127,9 @@ struct pqa_handle {
   // every move.  Blocking is bitwise identical and cuts the inverse's HBM traffic ~3x; it pays since k_flush_lw stages the
   // block's update vectors in LDS (1.26 -> 0.27 ms per flush at 65536 walkers): commit + flush 15.5 -> 8.4 ms per step.
   int lw_kb = -1;
-  int lw_nw = 0;  // PQA_LW_NW: walkers per block of k_step_lw (16, 32, 64; 0 = automatic)
   int lw_gm = 0;  // thread groups of the move kernels (PQA_LW_GM; 0 = automatic)  // lane-per-walker SoA mirrors (pqa_lw.hpp)
   DevBuf b_rot, b_eunif, b_elocal, b_ecnt, b_eoff, b_epts[2], b_ewgt[2], b_epte[2], b_emo[2], b_ecp;
   int orb_tp = 0;  // 0 = automatic
-  int orb_nosplit = 0;  // PQA_ORB_NOSPLIT=1: never split the chunk loop of small periodic launches (A/B)
   long orb_split_max = 8192;  // largest periodic launch whose chunk loop is split over two blocks (PQA_ORB_SPLIT_MAX)
   // AO rows per chunk of the PERIODIC 5-component launch: 32 halves the number of (phase 1, barrier, MFMA, barrier)
   // rounds of a block's latency chain — 2x2x2 diamond supercell +4.5-10 % at every walker count, 8-atom cell +11 % at 8192
@@ -148,25 +143,6 @@ struct pqa_handle {
   long orb_wide_max = 8192;  // PQA_ORB_WIDE_MAX
   std::vector<const void*> wide_attr;  // kernels whose dynamic-LDS limit has been raised
   int orb_ws = -1;  // -1 automatic; 1 wave-specialised orbital kernel; 0 phase-alternating k_orb (PQA_ORB_WS)
-  int orb_notab = 0;  // PQA_ORB_NOTAB=1: basis tables from global memory (A/B)
-  // pipelined half-ensembles of the lane-per-walker sweep (pqa_sweep.hip): mode (PQA_SPLIT), smallest shard that is cut
-  // (PQA_SPLIT_MIN), CUs of the orbital stream in mode 3 (PQA_SPLIT_CUS, 0 = no masks)
-  // OFF by default: two free-running half-ensembles (PQA_SPLIT=1) give +3.3-3.7 % at 65536 walkers in same-box A/B runs (bit-identical;
-  // -8 % at 32768), but the kernels of the two halves then share the chip and every launch takes about twice as long for the same
-  // work — the per-kernel roofline bench.py reports from launch durations stops meaning what it says (0.40 -> 0.23 for k_orb)
-  int split_mode = 0, split_cus = 0, cu_count = 256;
-  long split_min = 65536;
-  hipStream_t pipe_stream[2] = {nullptr, nullptr};
-  // Jastrow sums of a move summed ahead on a side stream next to the orbital kernel (k_jas_pre, pqa_lw.hpp): PQA_JPRE=1 (or -1:
-  // shards of at least jpre_min walkers, PQA_JPRE_MIN), one side stream per half-ensemble, partials [2 halves of a move][G][4][W].
-  // OFF by default — measured: k_step_lw 117 -> 81 us per move, but k_orb next to k_jas_pre 122 -> 196 us (25.9 -> 27.0 ms per step
-  // at 65536 walkers; 2x2x2 periodic cell +2 %): the fp64 pipe the two share is the step's bottleneck, not idle
-  int jpre = 0;
-  long jpre_min = 32768;
-  hipStream_t jas_stream[2] = {nullptr, nullptr};
-  DevBuf b_jpre;
-  std::vector<hipEvent_t> pipe_events;
-  size_t pipe_next = 0;
   // resident sweep (pqa_res.hpp / pqa_res.hip): the whole electron sweep of 16 walkers in one block, one launch per sweep.
   // PQA_RES: -1 automatic (shards of res_min .. res_max walkers: PQA_RES_MIN / PQA_RES_MAX), 0 never, 1 whenever the system is in scope
   int res_mode = -1;
@@ -193,9 +169,8 @@ struct pqa_handle {
   bool jsx_current = false;   // ... and did: energy_dev skips its transpose of the coordinate planes
   int res_pbc = 1;  // PQA_RES_PBC=0: periodic handles keep the launch-per-move sweep (A/B)
   int res_cx = 1;   // PQA_RES_CX=0: complex determinants keep the launch-per-move sweep (A/B)
-  // wave-per-walker sweep in one launch (pqa_ww.hpp; PQA_WW): -1 by shard size (one wave per walker up to ww_max walkers), 0 off, 1 always,
-  // 3 always with three waves per walker (measured slower).  50-determinant water molecule, VMC step with energy, launches -> one
-  // launch: 0.722 -> 0.663 ms at 1 024 walkers, 0.884 -> 0.801 at 2 048, 1.428 -> 1.382 at 4 096, 2.25 -> 2.38 at 8 192
+  // wave-per-walker sweep in one launch (pqa_ww.hpp; PQA_WW): -1 by shard size (up to ww_max walkers), 0 off, 1 always.  50-determinant
+  // water molecule, VMC step with energy, launches -> one launch: 0.722 -> 0.663 ms at 1 024 walkers, 0.884 -> 0.801 at 2 048, 1.428 -> 1.382 at 4 096, 2.25 -> 2.38 at 8 192
   // ECP point totals left on the device (pqa_energy.hip: small shards on the k_ecp_accum path; PQA_ECP_DEFER=0 reads them every time)
   const double* en_d_ecp = nullptr;  // energy_dev: the ECP row(s) of its last evaluation (nullptr: no ECP)
   long* pin_tot = nullptr;  // pinned host words the scan kernels write the ECP point totals to (device-visible: hipHostMallocMapped)
@@ -217,7 +192,7 @@ struct pqa_handle {
   long orb_p_hint = 0;  // launch_orb: points the next launch is expected to work on when its P is an upper bound (0: P)
   int ww_mode = -1;
   long ww_max = 4096;
-  int lw_mode = 1;  // 1: lane-per-walker fused sweep (single determinant); 0: wave-per-walker kernels; 2: walker-tile sweep (PQA_LW)
+  int lw_mode = 1;  // 1: lane-per-walker fused sweep (single determinant); 0: wave-per-walker kernels (PQA_LW)
   // density-matrix sampling (pqa_dm.hpp): per slot the auxiliary walkers (position, orbital row, density), the kept samples
   // and the orbitals at the configurations' electrons; accumulators of the estimator in dm_val / dm_norm
   struct DmSlot { DevBuf pos, row, f, newpos, keep_pos, keep_row, keep_f, cfg; long n = 0, ncfg = 0; int nkeep = 0, spin = 0; };
@@ -351,7 +326,6 @@ int sync_aos(pqa_handle* h);
 int lw_setup(pqa_handle* h, bool lw, LwCtx& c);
 int sweep_electrons(pqa_handle* h, const MoveBuf& mb, bool lw, const LwCtx& lc);
 void launch_step_real(pqa_handle* h, const LwState& L, const MoveBuf& mb, const StepArgs& a, int rowlen);
-void launch_jas_pre(pqa_handle* h, const LwState& L, const MoveBuf& mb, const StepArgs& a, double* jnew, double* jold);
 void launch_flush_real(pqa_handle* h, const LwState& L, int s, long W, long w0, long w1, int j_lo, int j_hi, int nq, int rowlen, int n_s);
 // pqa_sweep_cx.hip
 void launch_step_cx(pqa_handle* h, const LwState& L, const MoveBuf& mb, const StepArgs& a, int rowlen);
@@ -367,9 +341,6 @@ int sweep_r8(pqa_handle* h, const MoveBuf& mb);
 // pqa_sweep_ww.hip
 bool ww_eligible(pqa_handle* h, long W);
 int sweep_ww(pqa_handle* h, const MoveBuf& mb);
-// pqa_tile.hip
-bool tile_eligible(const pqa_handle* h);
-int sweep_tile(pqa_handle* h, const MoveBuf& mb_in);
 // pqa_energy.hip
 // assemble = false: the rows of b_en are left to the caller (k_energy_finish, from b_kc and en_d_ecp)
 int energy_dev(pqa_handle* h, double threshold, const double* rot, const double* unif, uint64_t seed, uint32_t step,

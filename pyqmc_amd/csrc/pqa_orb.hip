@@ -27,7 +27,7 @@ static void launch_orb_t2(pqa_handle* h, int tabi, int spin, PointAddr pa, long 
 }
 template <int NCOMP, int KC, int TP>
 static void launch_orb_t(pqa_handle* h, int tabi, int spin, PointAddr pa, long P, double* out) {
-  if (h->nshell <= PQA_WS_MAXSH && (int)h->S.nprim <= PQA_WS_MAXP && !h->orb_notab) launch_orb_t2<NCOMP, KC, TP, true>(h, tabi, spin, pa, P, out);
+  if (h->nshell <= PQA_WS_MAXSH && (int)h->S.nprim <= PQA_WS_MAXP) launch_orb_t2<NCOMP, KC, TP, true>(h, tabi, spin, pa, P, out);
   else launch_orb_t2<NCOMP, KC, TP, false>(h, tabi, spin, pa, P, out);
 }
 

@@ -23,9 +23,10 @@ static int launch_orb_pbc(pqa_handle* h, int tabi, int spin, PointAddr pa, long 
   T.pbc_list = (const unsigned long long*)h->b_pbcmask.p;
   T.pbc_nw = NW;
   if (wide_wanted(h, tabi, P, NCOMP)) {  // small launch: one 1024-thread block per 16-point tile, the whole basis in LDS
+    // twisted cells need more than 128 registers per thread: 512 threads.  Untwisted cells fit 128 since the lattice sums accumulate
+    // in the tile: 1024 threads (64 lane groups), C5 +3 % at 1024-8192 walkers over 512 threads
     if (h->twist) TRY((launch_orb_wide<2, 512>(h, T, tabi, spin, pa, P, out)));
-    else if (h->wide_nth == 1024) TRY((launch_orb_wide<1, 1024>(h, T, tabi, spin, pa, P, out)));
-    else TRY((launch_orb_wide<1, 512>(h, T, tabi, spin, pa, P, out)));
+    else TRY((launch_orb_wide<1, 1024>(h, T, tabi, spin, pa, P, out)));
     if (h->twist) {
       const long nel = P * NCOMP * (h->nmo[spin] / 2);
       hipLaunchKernelGGL((k_row_phase<>), dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, h->stream, out, P, NCOMP, h->nmo[spin],
@@ -60,7 +61,7 @@ static int launch_orb_pbc(pqa_handle* h, int tabi, int spin, PointAddr pa, long 
     }
   }
   // small launches: split the chunk loop over two blocks per point tile (k_orb: gridDim.y), output accumulated atomically
-  const int nsplit = (P <= h->orb_split_max && T.nchunk >= 4 && !h->orb_nosplit) ? 2 : 1;
+  const int nsplit = (P <= h->orb_split_max && T.nchunk >= 4) ? 2 : 1;
   if (nsplit > 1) {
     if (h->out_sel) hipLaunchKernelGGL((k_zero_rows<>), dim3((unsigned)P, (unsigned)((NCOMP * h->nmo[spin] + 255) / 256)), dim3(256), 0, h->stream, out,
                                        NCOMP * h->nmo[spin], h->out_sel, h->out_slot_stride);
@@ -69,7 +70,7 @@ static int launch_orb_pbc(pqa_handle* h, int tabi, int spin, PointAddr pa, long 
   const dim3 grid((unsigned)((P + tp - 1) / tp), (unsigned)nsplit), block(256);
   // basis tables in LDS when they fit: besides the faster table reads, the larger LDS footprint makes the compiler
   // budget registers for 2 blocks per CU instead of 4 (128 registers + 800 B of scratch spills otherwise)
-  const bool lt = h->nshell <= PQA_WS_MAXSH && (int)h->S.nprim <= PQA_WS_MAXP && !h->orb_notab;
+  const bool lt = h->nshell <= PQA_WS_MAXSH && (int)h->S.nprim <= PQA_WS_MAXP;
 #define PQA_ORB_PBC2(NT, LT, TPV) do { if (h->twist) hipLaunchKernelGGL((k_orb<NCOMP, NT, KC, TPV, LT, 2>), grid, block, 0, h->stream, h->S, T, spin, pa, P, out); \
                                        else hipLaunchKernelGGL((k_orb<NCOMP, NT, KC, TPV, LT, 1>), grid, block, 0, h->stream, h->S, T, spin, pa, P, out); } while (0)
 #define PQA_ORB_PBC(NT, LT) do { if (tp == 64) PQA_ORB_PBC2(NT, LT, 64); else if (tp == 16) PQA_ORB_PBC2(NT, LT, 16); else PQA_ORB_PBC2(NT, LT, 32); } while (0)

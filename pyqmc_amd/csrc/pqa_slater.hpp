@@ -278,10 +278,8 @@ static __global__ __launch_bounds__(64) void k_slater_eval(SysDev S, SlaterState
 // The n x n tile is staged global -> LDS with coalesced 512-B wave accesses (row stride n+1, odd, so
 // the row-per-lane accesses below are bank-conflict free); every row is split over R = 64/n lane
 // groups so all 64 lanes work for n <= 32.  LDS: n(n+1) + 2n + 64 doubles.
-// dpart / dparts: this wave updates the passes dpart, dpart + dparts, ... of the small-determinant branch (n <= 8; the fused
-// wave-per-walker sweep deals a walker's determinants to its three waves); elsewhere every determinant (dparts 1).
 __device__ __forceinline__ void sm_update_wave(const SysDev& S, const SlaterState& st, int s, int i, long w,
-                                               const double* __restrict__ morow, double* lds, int dpart = 0, int dparts = 1) {
+                                               const double* __restrict__ morow, double* lds) {
   const int lane = threadIdx.x & 63;
   const int n = s ? S.ndn : S.nup, D = S.ndet_s[s], ld = n + 1;
   if (n <= 8) {
@@ -293,7 +291,7 @@ __device__ __forceinline__ void sm_update_wave(const SysDev& S, const SlaterStat
     const int GS = n <= 1 ? 1 : (n <= 2 ? 2 : (n <= 4 ? 4 : 8)), E = GS * GS, DP = 64 / E;
     const int g = lane / E, r = (lane & (E - 1)) / GS, c = lane & (GS - 1);
 #pragma unroll 2
-    for (int d0 = dpart * DP; d0 < D; d0 += DP * dparts) {  // (passes are independent: two in flight)
+    for (int d0 = 0; d0 < D; d0 += DP) {  // (passes are independent: two in flight)
       const int d = d0 + g;
       const bool act = d < D && r < n && c < n;
       double* Tw = st.T[s] + ((size_t)w * D + (d < D ? d : 0)) * n * n;
@@ -315,7 +313,6 @@ __device__ __forceinline__ void sm_update_wave(const SysDev& S, const SlaterStat
     }
     return;
   }
-  if (dpart != 0) return;  // (the branches below work on one determinant at a time through the wave's LDS tile: one wave does them all)
   if (n > PQA_MAXN_FAST) {
     // More than 64 electrons of this spin: the tile does not fit the staging scheme below (one lane per row, n (n + 1) doubles of
     // LDS), so the update runs on the inverse where it lies: one wave sum per row for tmp, then the rank-1 update row by row.

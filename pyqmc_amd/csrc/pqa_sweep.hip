@@ -1,14 +1,9 @@
-// pyqmc_amd C ABI implementation (host side): layout conversions, the fused VMC sweep (pqa_vmc_sweeps), the walker-tile sweep.
+// pyqmc_amd C ABI implementation (host side): layout conversions, the fused VMC sweep (pqa_vmc_sweeps).
 // See include/pyqmc_amd.h for the contract and pqa_internal.hpp for what the units share.
 #include "pqa_sweep_launch.hpp"
 
 void launch_step_real(pqa_handle* h, const LwState& L, const MoveBuf& mb, const StepArgs& a, int rowlen) {
   if (h->S.pbc) launch_step_lw<true, false>(h, L, mb, a, rowlen); else launch_step_lw<false, false>(h, L, mb, a, rowlen);
-}
-void launch_jas_pre(pqa_handle* h, const LwState& L, const MoveBuf& mb, const StepArgs& a, double* jnew, double* jold) {
-  const dim3 grid((unsigned)((a.w1 - a.w0 + a.NW - 1) / a.NW)), block((unsigned)(a.NW * a.G));
-  if (h->S.pbc) hipLaunchKernelGGL(k_jas_pre<true>, grid, block, 0, h->stream, h->S, L, mb, a, jnew, jold);
-  else hipLaunchKernelGGL(k_jas_pre<false>, grid, block, 0, h->stream, h->S, L, mb, a, jnew, jold);
 }
 void launch_flush_real(pqa_handle* h, const LwState& L, int s, long W, long w0, long w1, int j_lo, int j_hi, int nq, int rowlen, int n_s) {
   launch_flush_lw<false>(h, L, s, W, w0, w1, j_lo, j_hi, nq, rowlen, n_s);
@@ -111,49 +106,6 @@ int lw_setup(pqa_handle* h, bool lw, LwCtx& c) {
   }
   return 0;
 }
-// ---- pipelined half-ensembles (round 4) ---------------------------------------------------------------------------------
-// A move is k_orb (fp64 MFMA / VALU pipe bound, HBM idle) followed by k_step_lw (+ k_flush_lw; HBM / latency bound, the matrix
-// pipe idle), and one walker's chain is strictly serial.  Walkers are independent, so the shard is cut into two half-ensembles
-// A = [0, wm) and B = [wm, W) whose chains run side by side: while A's orbitals are evaluated, B's state is streamed, and
-// vice versa.  Every kernel takes a walker window [w0, w1) on the SAME planes (stride W) and keys its Philox streams by the
-// walker's index in the shard, so a trajectory does not depend on the cut: bit-identical to the single-stream sweep.
-//   mode 1: one stream per half, free running
-//   mode 2: one stream per half; the orbital launches of the two halves form one chain (orb A(e) -> orb B(e) -> orb A(e+1) ...),
-//           so two orbital kernels never compete for the pipe and the other half's step kernel fills the rest of the chip
-//   mode 3: one stream per kernel FAMILY (orbitals / state streaming) with the dependencies as events: the same schedule as
-//           mode 2, and the two streams can be given disjoint CU masks (PQA_SPLIT_CUS = CUs of the orbital stream)
-// PQA_SPLIT selects the mode (0: off), PQA_SPLIT_MIN the smallest shard that is cut.
-struct HalfPipe {
-  int mode = 0;
-  long wm = 0;
-  hipStream_t main = nullptr, s[2] = {nullptr, nullptr};
-  hipEvent_t orb_done[2] = {nullptr, nullptr}, step_done[2] = {nullptr, nullptr};
-};
-static int pipe_event(pqa_handle* h, hipEvent_t* ev) {  // events from a ring: a wait keeps the record it saw when it was enqueued
-  if (h->pipe_events.size() < 64) {
-    hipEvent_t e;
-    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    h->pipe_events.push_back(e);
-    *ev = e;
-    return 0;
-  }
-  *ev = h->pipe_events[h->pipe_next++ % h->pipe_events.size()];
-  return 0;
-}
-static int pipe_streams(pqa_handle* h) {
-  if (h->pipe_stream[0]) return 0;
-  const int ncu = h->split_cus;
-  for (int k = 0; k < 2; ++k) {
-    if (h->split_mode == 3 && ncu > 0 && ncu < h->cu_count) {  // family streams on disjoint CU sets: orbitals on the first ncu mask bits
-      std::vector<uint32_t> mask((h->cu_count + 31) / 32, 0u);
-      for (int c = 0; c < h->cu_count; ++c)
-        if ((c < ncu) == (k == 0)) mask[c / 32] |= 1u << (c % 32);
-      HIPCHK(hipExtStreamCreateWithCUMask(&h->pipe_stream[k], (uint32_t)mask.size(), mask.data()));
-    } else HIPCHK(hipStreamCreateWithFlags(&h->pipe_stream[k], hipStreamNonBlocking));
-  }
-  return 0;
-}
-
 // The next step's draws on the side stream, behind the sweep that has just been enqueued (the tape set of step + 1 was last read by the sweep
 // of step - 1): they run beside this step's energy pass (k_tile_draws: 64 us of Philox + Box-Muller arithmetic at 65 536 walkers, next to
 // memory- and latency-bound kernels) instead of in front of the next sweep.
@@ -211,7 +163,6 @@ static int sweep_electrons_fused(pqa_handle* h, const MoveBuf& mb_in, const LwCt
   // than 4 groups narrow the block to 32 or 16 walkers — which is also what spreads a small shard over the chip
   int G = std::min(lc.Gm, 16);
   int NW = (G <= 4) ? 64 : 256 / G;
-  if (h->lw_nw > 0 && h->lw_nw * G <= 256) NW = h->lw_nw;
   // small shards (one 16-walker block per CU at most): 32 thread groups per walker — k_step_pre<.., 32>, 512 threads, two Jastrow
   // partners per thread: (H2O)8 step 3.93 -> 3.40 ms at 4096 walkers, 3.38 -> 2.88 at 1024; 64 groups (one partner per thread, 1024
   // threads) spill at the 128-register limit: 4.47 / 3.53 ms.  PQA_STEP_GW = 16 / 32 / 64 pins it.
@@ -220,39 +171,10 @@ static int sweep_electrons_fused(pqa_handle* h, const MoveBuf& mb_in, const LwCt
     if ((gw == 32 || gw == 64) && W <= h->step_pre_max && N_ok(h) && step_pre_system_ok(h, rowlen) && KB <= gw / 4) { G = gw; NW = 16; }  // (a block row per quartet of groups)
   }
 
-  HalfPipe P;
-  P.main = h->stream;
-  P.mode = (W >= h->split_min && !(h->split_mode == 1 && h->S.pbc)) ? h->split_mode : 0;  // (free-running halves would share the periodic pre-pass scratch)
-  const int nh = P.mode ? 2 : 1;
-  P.wm = P.mode ? std::min(W, ((W / 2 + 255) / 256) * 256) : W;
-  if (P.mode) {
-    TRY(pipe_streams(h));
-    P.s[0] = h->pipe_stream[0]; P.s[1] = h->pipe_stream[1];
-    hipEvent_t fork;
-    TRY(pipe_event(h, &fork));
-    HIPCHK(hipEventRecord(fork, P.main));
-    HIPCHK(hipStreamWaitEvent(P.s[0], fork, 0));
-    HIPCHK(hipStreamWaitEvent(P.s[1], fork, 0));
-  }
-  // Jastrow sums ahead of the orbitals (k_jas_pre): on for the k_step_lw launches of large shards with a Jastrow factor
-  const bool jpre = h->has_jastrow && (h->jpre < 0 ? W >= h->jpre_min : h->jpre != 0) && !(NW < 64 && h->step_pre && W <= h->step_pre_max);
-  double* jbuf = nullptr;
-  hipEvent_t jas_done[2] = {nullptr, nullptr}, steps_done[2] = {nullptr, nullptr};
-  if (jpre) {
-    TRY(ensure(h, h->b_jpre, (size_t)2 * G * 4 * W * sizeof(double)));
-    jbuf = (double*)h->b_jpre.p;
-    for (int k = 0; k < nh; ++k)
-      if (!h->jas_stream[k]) HIPCHK(hipStreamCreateWithFlags(&h->jas_stream[k], hipStreamNonBlocking));
-  }
-  struct Guard { pqa_handle* h; hipStream_t s; ~Guard() { h->stream = s; } } guard{h, P.main};  // launches go to h->stream: restored on every exit
-  const long wlo[2] = {0, P.wm}, whi[2] = {P.wm, W};
-  // stream of a launch: half hh, family 0 = orbitals, 1 = state streaming
-  auto on = [&](int hh, int fam) { h->stream = !P.mode ? P.main : (P.mode == 3 ? P.s[fam] : P.s[hh]); };
-  auto step = [&](int hh, int e_acc, int e_prop, bool use_pre = false) {
+  auto step = [&](int e_acc, int e_prop) {
     StepArgs a{};
-    a.e_acc = e_acc; a.e_prop = e_prop; a.has_jastrow = (int)h->has_jastrow; a.G = G; a.NW = NW; a.W = W; a.w0 = wlo[hh]; a.w1 = whi[hh];
+    a.e_acc = e_acc; a.e_prop = e_prop; a.has_jastrow = (int)h->has_jastrow; a.G = G; a.NW = NW; a.W = W; a.w0 = 0; a.w1 = W;
     a.j_skip = e_prop > 0 ? e_prop - 1 : -1;
-    if (use_pre) { a.jnew = e_acc >= 0 ? jbuf : nullptr; a.jold = e_prop >= 0 ? jbuf + (size_t)G * 4 * W : nullptr; }
     if (e_acc >= 0) {
       const int s = e_acc >= h->nup, n_s = s ? h->ndn : h->nup, i_s = e_acc - (s ? h->nup : 0);
       const int q = i_s % KB;
@@ -263,16 +185,7 @@ static int sweep_electrons_fused(pqa_handle* h, const MoveBuf& mb_in, const LwCt
     }
     if (h->cplx) launch_step_cx(h, L, mb, a, rowlen); else launch_step_real(h, L, mb, a, rowlen);
   };
-  // what the state-streaming launches of half hh wait for / leave behind in modes 2 and 3
-  auto after_steps = [&](int hh) -> int {
-    if (P.mode == 3) { TRY(pipe_event(h, &P.step_done[hh])); HIPCHK(hipEventRecord(P.step_done[hh], h->stream)); }
-    return 0;
-  };
-  for (int hh = 0; hh < nh; ++hh) {
-    on(hh, 1);
-    step(hh, -1, 0);
-    TRY(after_steps(hh));
-  }
+  step(-1, 0);
   for (int e = 0; e < N; ++e) {
     const int s = e >= h->nup, n_s = s ? h->ndn : h->nup, i_s = e - (s ? h->nup : 0);
     const int q = i_s % KB, j_lo = i_s - q, j_hi = std::min(j_lo + KB, n_s);
@@ -280,80 +193,46 @@ static int sweep_electrons_fused(pqa_handle* h, const MoveBuf& mb_in, const LwCt
     const bool need_flush = block_done && (j_hi - j_lo < n_s);
     // the next electron's inverse row is current after this move's commit unless it opens a new block of the SAME spin
     const bool fuse_next = (e + 1 < N) && !(need_flush && i_s + 1 < n_s);
-    for (int hh = 0; hh < nh; ++hh) {
-      const long w0 = wlo[hh], Wn = whi[hh] - wlo[hh];
-      if (Wn <= 0) continue;
-      // ---- Jastrow sums of this move on the side stream: they need the proposal (previous step launch) and nothing of the orbitals
-      if (jpre) {
-        hipStream_t st_steps = !P.mode ? P.main : (P.mode == 3 ? P.s[1] : P.s[hh]);
-        TRY(pipe_event(h, &steps_done[hh]));
-        HIPCHK(hipEventRecord(steps_done[hh], st_steps));
-        HIPCHK(hipStreamWaitEvent(h->jas_stream[hh], steps_done[hh], 0));
-        StepArgs ja{};
-        ja.e_acc = e; ja.e_prop = (e + 1 < N) ? e + 1 : -1; ja.has_jastrow = 1; ja.G = G; ja.NW = NW; ja.W = W; ja.w0 = w0; ja.w1 = whi[hh];
-        ja.j_skip = e;
-        h->stream = h->jas_stream[hh];
-        launch_jas_pre(h, L, mb, ja, jbuf, jbuf + (size_t)G * 4 * W);
-        TRY(pipe_event(h, &jas_done[hh]));
-        HIPCHK(hipEventRecord(jas_done[hh], h->stream));
+    // ---- orbitals at the proposals: the rows go straight into the slot of electron i_s the walker is not using (accepting
+    // flips the selector)
+    TRY(launch_orb(h, s, plain_points(mb.newpos, W), W, 5, (double*)h->b_rc[s].p + (size_t)i_s * 2 * W * 5 * h->nmo[s],
+                   (const unsigned char*)h->b_sel[s].p + (size_t)i_s * W, (long)W * 5 * h->nmo[s]));
+    // ---- decide e, commit, propose e + 1
+    hipEvent_t pe1 = nullptr;
+    if (h->profile && (e % (4 * (int)h->prof_stride)) == 1) {  // sparsely sampled full (decide + propose) launches: an event pair costs ~2 us of stream time
+      if (h->prof3_used == h->prof3_events.size()) {
+        hipEvent_t a, b;
+        HIPCHK(hipEventCreate(&a));
+        HIPCHK(hipEventCreate(&b));
+        h->prof3_events.emplace_back(a, b);
       }
-      // ---- orbitals at the proposals: the rows go straight into the slot of electron i_s the walker is not using (accepting
-      // flips the selector)
-      on(hh, 0);
-      if (P.mode == 2 && P.orb_done[1 - hh]) HIPCHK(hipStreamWaitEvent(h->stream, P.orb_done[1 - hh], 0));
-      if (P.mode == 3 && P.step_done[hh]) HIPCHK(hipStreamWaitEvent(h->stream, P.step_done[hh], 0));
-      TRY(launch_orb(h, s, plain_points(mb.newpos + 3 * w0, Wn), Wn, 5, (double*)h->b_rc[s].p + ((size_t)i_s * 2 * W + w0) * 5 * h->nmo[s],
-                     (const unsigned char*)h->b_sel[s].p + (size_t)i_s * W + w0, (long)W * 5 * h->nmo[s]));
-      if (P.mode >= 2) { TRY(pipe_event(h, &P.orb_done[hh])); HIPCHK(hipEventRecord(P.orb_done[hh], h->stream)); }
-      // ---- decide e, commit, propose e + 1
-      on(hh, 1);
-      if (P.mode == 3) HIPCHK(hipStreamWaitEvent(h->stream, P.orb_done[hh], 0));
-      if (jpre) HIPCHK(hipStreamWaitEvent(h->stream, jas_done[hh], 0));
-      hipEvent_t pe1 = nullptr;
-      if (h->profile && hh == 0 && (e % (4 * (int)h->prof_stride)) == 1) {  // sparsely sampled full (decide + propose) launches: an event pair costs ~2 us of stream time
-        if (h->prof3_used == h->prof3_events.size()) {
+      if (fuse_next) {
+        HIPCHK(hipEventRecord(h->prof3_events[h->prof3_used].first, h->stream));
+        pe1 = h->prof3_events[h->prof3_used].second;
+        ++h->prof3_used;
+      }
+    }
+    step(e, fuse_next ? e + 1 : -1);
+    if (pe1) { HIPCHK(hipEventRecord(pe1, h->stream)); h->prof3_launches += 1; }
+    if (need_flush) {  // block finished: bring every other row of this spin up to date
+      const int nq = j_hi - j_lo;
+      hipEvent_t ce1 = nullptr;
+      if (h->profile && ((j_lo / std::max(KB, 1)) % 4) == 0) {  // every 4th flush of a spin
+        if (h->prof2_used == h->prof2_events.size()) {
           hipEvent_t a, b;
           HIPCHK(hipEventCreate(&a));
           HIPCHK(hipEventCreate(&b));
-          h->prof3_events.emplace_back(a, b);
+          h->prof2_events.emplace_back(a, b);
         }
-        if (fuse_next) {
-          HIPCHK(hipEventRecord(h->prof3_events[h->prof3_used].first, h->stream));
-          pe1 = h->prof3_events[h->prof3_used].second;
-          ++h->prof3_used;
-        }
+        HIPCHK(hipEventRecord(h->prof2_events[h->prof2_used].first, h->stream));
+        ce1 = h->prof2_events[h->prof2_used].second;
+        ++h->prof2_used;
       }
-      step(hh, e, fuse_next ? e + 1 : -1, jpre);
-      if (pe1) { HIPCHK(hipEventRecord(pe1, h->stream)); h->prof3_launches += 1; }
-      if (need_flush) {  // block finished: bring every other row of this spin up to date
-        const int nq = j_hi - j_lo;
-        hipEvent_t ce1 = nullptr;
-        if (h->profile && hh == 0 && ((j_lo / std::max(KB, 1)) % 4) == 0) {  // every 4th flush of a spin
-          if (h->prof2_used == h->prof2_events.size()) {
-            hipEvent_t a, b;
-            HIPCHK(hipEventCreate(&a));
-            HIPCHK(hipEventCreate(&b));
-            h->prof2_events.emplace_back(a, b);
-          }
-          HIPCHK(hipEventRecord(h->prof2_events[h->prof2_used].first, h->stream));
-          ce1 = h->prof2_events[h->prof2_used].second;
-          ++h->prof2_used;
-        }
-        if (h->cplx) launch_flush_cx(h, L, s, W, w0, whi[hh], j_lo, j_hi, nq, rowlen, n_s);
-        else launch_flush_real(h, L, s, W, w0, whi[hh], j_lo, j_hi, nq, rowlen, n_s);
-        if (ce1) { HIPCHK(hipEventRecord(ce1, h->stream)); h->prof2_launches += 1; }
-      }
-      if (!fuse_next && e + 1 < N) step(hh, -1, e + 1, jpre);
-      TRY(after_steps(hh));
+      if (h->cplx) launch_flush_cx(h, L, s, W, 0, W, j_lo, j_hi, nq, rowlen, n_s);
+      else launch_flush_real(h, L, s, W, 0, W, j_lo, j_hi, nq, rowlen, n_s);
+      if (ce1) { HIPCHK(hipEventRecord(ce1, h->stream)); h->prof2_launches += 1; }
     }
-  }
-  if (P.mode) {  // join: the caller's stream continues after both chains
-    for (int k = 0; k < 2; ++k) {
-      hipEvent_t j;
-      TRY(pipe_event(h, &j));
-      HIPCHK(hipEventRecord(j, P.s[k]));
-      HIPCHK(hipStreamWaitEvent(P.main, j, 0));
-    }
+    if (!fuse_next && e + 1 < N) step(-1, e + 1);
   }
   return 0;
 }
@@ -363,7 +242,7 @@ static int sweep_electrons_fused(pqa_handle* h, const MoveBuf& mb_in, const LwCt
 int sweep_electrons(pqa_handle* h, const MoveBuf& mb, bool lw, const LwCtx& lc) {
   if (lw) return sweep_electrons_fused(h, mb, lc);
   const long W = h->W;
-  if (ww_eligible(h, W)) return sweep_ww(h, mb);  // small shards: the whole sweep of a walker in one launch, three waves per walker (pqa_ww.hpp)
+  if (ww_eligible(h, W)) return sweep_ww(h, mb);  // small shards: the whole sweep of a walker in one launch, one wave per walker (pqa_ww.hpp)
   const size_t lds_acc = std::max(lds_sm(h), lds_det(h, 5));
   for (int e = 0; e < h->N; ++e) {
     const int s = e >= h->nup;
@@ -417,8 +296,7 @@ extern "C" int pqa_vmc_sweeps(pqa_handle_t* h, double tstep, int nsteps, const d
   if (unif) TRY(ensure(h, h->b_unif, (size_t)N * W * sizeof(double)));
   if (accept_rec) TRY(ensure(h, h->b_accrec, (size_t)N * W));
   const size_t nrot = (size_t)N * std::max(h->necp, 1);
-  const bool tile = tile_eligible(h);
-  const bool lw = !tile && h->lw_mode != 0 && h->has_slater && h->ndet == 1 && !h->has_j3 && (!h->cplx || std::max(h->nup, h->ndn) <= 32);
+  const bool lw = h->lw_mode != 0 && h->has_slater && h->ndet == 1 && !h->has_j3 && (!h->cplx || std::max(h->nup, h->ndn) <= 32);
   LwCtx lc;
   TRY(lw_setup(h, lw, lc));
   h->draw_ahead_valid = false;
@@ -439,8 +317,7 @@ extern "C" int pqa_vmc_sweeps(pqa_handle_t* h, double tstep, int nsteps, const d
     h->jsx_current = false;
     h->r8_xaos_next = energy_mean != nullptr && h->necp > 0;  // (consumed by sweep_r8 only)
     h->draws_on_device = false;
-    if (tile) TRY(sweep_tile(h, mb));
-    else TRY(sweep_electrons(h, mb, lw, lc));
+    TRY(sweep_electrons(h, mb, lw, lc));
     h->r8_xaos_next = false;
     if (h->draws_on_device && energy_mean && step + 1 < nsteps && W >= 16384 && h->draws_ahead_on) TRY(draws_ahead(h, seed, (uint32_t)(step + 1)));
     // small shards: the accepted-move count, the energy rows and their means in one launch at the end of the step (three launches of ~5 us

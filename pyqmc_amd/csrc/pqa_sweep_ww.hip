@@ -1,6 +1,6 @@
 // pyqmc_amd C ABI implementation (host side): the wave-per-walker electron sweep in one launch (pqa_ww.hpp) — eligibility, launch.
-// Its three waves run different device functions of one move side by side, so the synchronisation INSIDE those functions (PQA_WSYNC,
-// pqa_common.hpp) is the wave-level fence here: LDS operations of a wave execute in order, the fence keeps the compiler from moving them.
+// A block is one wave, so the synchronisation INSIDE the device functions it calls (PQA_WSYNC, pqa_common.hpp) is the wave-level fence
+// here: LDS operations of a wave execute in order, the fence keeps the compiler from moving them.
 #define PQA_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 #define PQA_SYNC_NS pqa_sync_wave
 #include "pqa_internal.hpp"
@@ -28,13 +28,11 @@ int sweep_ww(pqa_handle* h, const MoveBuf& mb) {
   const long W = h->W;
   int lmax = 0;
   for (int l : h->shell_l) lmax = std::max(lmax, l);
-  const int nwv = h->ww_mode == 3 ? 3 : 1;  // PQA_WW=3: three waves per walker
-  const dim3 grid((unsigned)W), block(64 * nwv);
+  const dim3 grid((unsigned)W), block(64);
   const size_t lds = ww_lds(h);
   const int xoff = (int)ww_xoff(h);
-#define PQA_WW_LAUNCH(LM, NW) hipLaunchKernelGGL((k_sweep_ww<LM, NW>), grid, block, lds, h->stream, h->S, h->st, h->js, mb, (int)h->has_slater, (int)h->has_jastrow, xoff, (int)ww_cstage(h), W)
-  if (nwv == 3) { if (lmax <= 2) PQA_WW_LAUNCH(2, 3); else if (lmax <= 3) PQA_WW_LAUNCH(3, 3); else PQA_WW_LAUNCH(5, 3); }
-  else { if (lmax <= 2) PQA_WW_LAUNCH(2, 1); else if (lmax <= 3) PQA_WW_LAUNCH(3, 1); else PQA_WW_LAUNCH(5, 1); }
+#define PQA_WW_LAUNCH(LM) hipLaunchKernelGGL((k_sweep_ww<LM>), grid, block, lds, h->stream, h->S, h->st, h->js, mb, (int)h->has_slater, (int)h->has_jastrow, xoff, (int)ww_cstage(h), W)
+  if (lmax <= 2) PQA_WW_LAUNCH(2); else if (lmax <= 3) PQA_WW_LAUNCH(3); else PQA_WW_LAUNCH(5);
 #undef PQA_WW_LAUNCH
   return check_launch(h, "k_sweep_ww");
 }

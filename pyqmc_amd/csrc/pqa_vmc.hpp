@@ -47,6 +47,23 @@ __device__ __forceinline__ void limdrift_dmc(double& gx, double& gy, double& gz,
   gx *= te; gy *= te; gz *= te;
 }
 
+// A sweep's random numbers, drawn ahead of it from the same Philox streams the sweep kernels draw from themselves (so every
+// path makes the same decisions): gauss [N][W][3] standard normals, unif [N][W].  Read by the resident sweeps and by the
+// launch-per-move sweep of small shards, which keeps Box-Muller (sincos, log) out of its per-move chain.
+template <int PQA_UNIT = 0>  // (a template so that only the units that launch it compile it)
+static __global__ __launch_bounds__(256) void k_tile_draws(uint64_t seed, uint32_t step, int N, long W, double* __restrict__ gauss, double* __restrict__ unif) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)N * W) return;
+  const int e = (int)(idx / W);
+  const long w = idx - (long)e * W;
+  double z0, z1, z2, z3;
+  normal2(philox(seed, (uint32_t)w, (uint32_t)e, PQA_STREAM_GAUSS_A, step), z0, z1);
+  normal2(philox(seed, (uint32_t)w, (uint32_t)e, PQA_STREAM_GAUSS_B, step), z2, z3);
+  gauss[3 * idx] = z0; gauss[3 * idx + 1] = z1; gauss[3 * idx + 2] = z2;
+  const Philox p = philox(seed, (uint32_t)w, (uint32_t)e, PQA_STREAM_ACCEPT, step);
+  unif[idx] = u01(p.c[0], p.c[1]);
+}
+
 // Slater part of a move: gradient of log|Psi_S| (real part for complex orbitals: the drift uses np.real(grad),
 // mc.py:118,126) and |ratio|^2, sanitised like gradient_value (slater.py:414-417).  CX: complex determinants.
 template <bool CX>

@@ -11,18 +11,12 @@
 //            the block's LDS copy of the coefficient matrix) and the Slater ratios; the Jastrow terms at the proposal
 //   phase D  Metropolis test (mc.py:124-132, dmc.py:57-70); accepted: the determinants' Sherman-Morrison updates (slater.py:88-94),
 //            cache row, coordinate
-// NWV = 1 (default for small shards): one wave per walker runs the parts one after the other — the launches' chains without the 3 N launches,
-// their drain / fill and the separate orbital kernel: C4 step 0.884 -> 0.801 ms at 2 048 walkers (2.32 -> 2.56 M walker-steps/s).
-// NWV = 3 (PQA_WW=3): the three parts of phases A and C on three waves side by side, the determinant updates dealt to the waves.  MEASURED
-// (tools/scratch/ww1_clk.py, profiles/r05_ww_one_launch.txt): a move takes 23 us in a block that has the CU to itself (phase A 7.4, proposal 1,
-// phase C 10.7 of which the orbital row 6.2 before the LDS copy of the coefficients, decision + commit 4) — but 6 144 waves at 168 registers
-// are two rounds of 12 waves per CU, and with every SIMD holding three waves the same move takes ~37 us: 575 us per sweep against 431 us of the
-// launches.  The three chains of a move are not latency alone — two waves per SIMD already keep the fp64 pipe about half busy — so splitting
-// them over waves buys less than the registers and barriers cost.  Kept as the measured answer to the round-4 review's "fuse k_propose ->
-// k_accept -> next k_propose into one persistent launch".
+// One wave per walker runs the parts one after the other — the launches' chains without the 3 N launches, their drain / fill and the
+// separate orbital kernel: C4 step 0.884 -> 0.801 ms at 2 048 walkers (2.32 -> 2.56 M walker-steps/s).  Three waves per walker, the parts of
+// phases A and C side by side, measured slower (575 us per sweep against 431 us of the launches) and were removed.
 // The device functions are the ones k_propose / k_accept call, in the same order of operations — the same numbers except for the orbital
 // row, whose contraction is a sequential sum here and an MFMA tile sum in the orbital kernels (relative differences of 1e-16).
-// Scope: open boundary conditions, real orbitals, l <= 5.  Requires PQA_WSYNC to be the wave-level fence (pqa_sweep_ww.hip).
+// Scope: open boundary conditions, real orbitals, l <= 5.  PQA_WSYNC is the wave-level fence here (pqa_sweep_ww.hip).
 #pragma once
 #include "pqa_ao.hpp"
 #include "pqa_vmc.hpp"
@@ -67,16 +61,14 @@ __device__ __forceinline__ void ww_orb_point(const SysDev& S, int s, double x, d
   PQA_WSYNC();
 }
 
-// grid = W blocks of 192 threads.  Dynamic LDS: [0, xoff) the scratch of the Slater functions and (from S.j3_off) of the three-body
+// grid = W blocks of 64 threads.  Dynamic LDS: [0, xoff) the scratch of the Slater functions and (from S.j3_off) of the three-body
 // Jastrow term, then PQA_WW_XCH exchange doubles, the orbital row [5][max nmo] and the AO values [5][nao].
-// NWV = 3: the three roles on three waves; NWV = 1: one wave per walker runs them one after the other (the launches' chains without the
-// launches: the orbital row from the block itself, no drain / fill between the parts of a move)
-template <int LMAX, int NWV>
-static __global__ __launch_bounds__(64 * NWV, NWV == 3 ? 3 : 2) void k_sweep_ww(SysDev S, SlaterState st, JastrowState js, MoveBuf mb, int has_slater,
-                                                                  int has_jastrow, int xoff, int cstage, long W) {
+template <int LMAX>
+static __global__ __launch_bounds__(64, 2) void k_sweep_ww(SysDev S, SlaterState st, JastrowState js, MoveBuf mb, int has_slater,
+                                                         int has_jastrow, int xoff, int cstage, long W) {
   extern __shared__ double lds[];
   const long w = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tid = threadIdx.x, lane = tid & 63;
   // exchange area: [0..4] / [16..20] Slater terms (gx, gy, gz, val2, sign) at the current position / at the proposal, [5..8] / [21..24]
   // one/two-body Jastrow (U, g), [9..12] / [25..28] three-body, [13..15] the scaled gaussians
   double* xch = lds + xoff;
@@ -86,8 +78,8 @@ static __global__ __launch_bounds__(64 * NWV, NWV == 3 ? 3 : 2) void k_sweep_ww(
   double* cl = aov + 5 * (size_t)S.nao;  // cstage: the coefficient matrices of both spins [nao][nmo_up], [nao][nmo_dn]
   if (cstage) {
     const int n0 = S.nao * S.nmo[0], n1 = S.nao * S.nmo[1];
-    for (int k = tid; k < n0; k += 64 * NWV) cl[k] = S.mo[0][k];
-    for (int k = tid; k < n1; k += 64 * NWV) cl[n0 + k] = S.mo[1][k];
+    for (int k = tid; k < n0; k += 64) cl[k] = S.mo[0][k];
+    for (int k = tid; k < n1; k += 64) cl[n0 + k] = S.mo[1][k];
     __syncthreads();
   }
   const int N = S.nelec;
@@ -101,10 +93,10 @@ static __global__ __launch_bounds__(64 * NWV, NWV == 3 ? 3 : 2) void k_sweep_ww(
     const double ex = xw[3 * e], ey = xw[3 * e + 1], ez = xw[3 * e + 2];
     double dgx = 0.0, dgy = 0.0, dgz = 0.0, U0 = 0.0, z0 = 0.0, z1 = 0.0, z2 = 0.0, nx = ex, ny = ey, nz = ez;
 #pragma unroll 1
-    for (int ph = 0; ph < 2; ++ph) {  // phase A (current position), phase C (proposal): the three parts side by side
+    for (int ph = 0; ph < 2; ++ph) {  // phase A (current position), phase C (proposal): the three parts one after the other
       double* xo = xch + 16 * ph;
       PQA_W1CLK(ph ? 3 : 0);
-      if (wv == 0) {  // (NWV 1: the only wave)
+      {
         double gx = 0.0, gy = 0.0, gz = 0.0, v2 = 1.0, sgn = 1.0;
         if (has_slater) {
           const double* r_ = st.cache[s] + ((size_t)w * n + i) * 5 * nmo;
@@ -127,18 +119,13 @@ static __global__ __launch_bounds__(64 * NWV, NWV == 3 ? 3 : 2) void k_sweep_ww(
           }
         }
       }
-      if (NWV == 1) {
+      {
         double U = 0.0, g[3] = {0.0, 0.0, 0.0}, lp;
         if (has_jastrow) jas_eval<1, false>(S, xw, e, nx, ny, nz, U, g, lp, 1, nullptr);
         if (lane == 0) { xo[5] = U; xo[6] = g[0]; xo[7] = g[1]; xo[8] = g[2]; }
         U = 0.0; g[0] = g[1] = g[2] = 0.0;
         if (has_j3) jas_eval<1, false>(S, xw, e, nx, ny, nz, U, g, lp, 2, lds + S.j3_off);
         if (lane == 0) { xo[9] = U; xo[10] = g[0]; xo[11] = g[1]; xo[12] = g[2]; }
-      } else if (wv != 0) {
-        double U = 0.0, g[3] = {0.0, 0.0, 0.0}, lp;
-        if (wv == 1) { if (has_jastrow) jas_eval<1, false>(S, xw, e, nx, ny, nz, U, g, lp, 1, nullptr); }
-        else if (has_j3) jas_eval<1, false>(S, xw, e, nx, ny, nz, U, g, lp, 2, lds + S.j3_off);
-        if (lane == 0) { double* o = xo + (wv == 1 ? 5 : 9); o[0] = U; o[1] = g[0]; o[2] = g[1]; o[3] = g[2]; }
       }
       PQA_W1CLK(ph ? 4 : 1);
       __syncthreads();
@@ -200,11 +187,11 @@ static __global__ __launch_bounds__(64 * NWV, NWV == 3 ? 3 : 2) void k_sweep_ww(
     }
     if (acc) {
       if (has_slater) {
-        sm_update_wave(S, st, s, i, w, row, lds, wv, NWV);
+        sm_update_wave(S, st, s, i, w, row, lds);
         double* c = st.cache[s] + ((size_t)w * n + i) * 5 * nmo;
-        for (int k = tid; k < 5 * nmo; k += 64 * NWV) c[k] = row[k];
+        for (int k = tid; k < 5 * nmo; k += 64) c[k] = row[k];
       }
-      if (tid == (NWV == 3 ? 64 : 0)) { xg[3 * e] = nx; xg[3 * e + 1] = ny; xg[3 * e + 2] = nz; }
+      if (tid == 0) { xg[3 * e] = nx; xg[3 * e + 1] = ny; xg[3 * e + 2] = nz; }
     }
     PQA_W1CLK(6);
     __syncthreads();  // (the coordinate, the inverses and the exchange area before the next electron)

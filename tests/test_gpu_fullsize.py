@@ -560,11 +560,10 @@ def test_resident_sweep_against_the_launch_per_move_sweep(cfg, W, monkeypatch):
             assert note(f"{cfg}_{W}_resident_vs_launches_{k}", np.max(np.abs(a[k] - b[k]) / np.maximum(1.0, np.abs(b[k])))) < 1e-10
 
 
-@pytest.mark.parametrize("cfg,W,ww_mode", [("C4", 2048, "1"), ("C4", 77, "1"), ("C4", 300, "3")])
+@pytest.mark.parametrize("cfg,W,ww_mode", [("C4", 2048, "1"), ("C4", 77, "1"), ("C4", 300, "1")])
 def test_one_launch_wave_per_walker_sweep_against_the_launches(cfg, W, ww_mode, monkeypatch):
-    """The wave-per-walker sweep in one launch (k_sweep_ww; PQA_WW=1: one wave per walker, =3: three waves per walker — Slater terms, two-body
-    Jastrow, three-body Jastrow side by side, the determinants' Sherman-Morrison updates dealt to the waves; the proposal's orbital row
-    evaluated by the block itself)
+    """The wave-per-walker sweep in one launch (k_sweep_ww, PQA_WW=1: one wave per walker runs Slater terms, two-body Jastrow, three-body
+    Jastrow and the determinants' Sherman-Morrison updates one after the other; the proposal's orbital row evaluated by the block itself)
     against k_propose -> orbital kernel -> k_accept per move, on the 50-determinant water molecule with a three-body Jastrow factor: the
     same Philox streams and the same device functions, only the orbital row's contraction sums in another order.  Every Metropolis decision
     equal; walkers, log-values, energies and the DMC step's statistics equal to rounding; the updated state equal to a fresh recompute."""

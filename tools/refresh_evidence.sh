@@ -50,9 +50,7 @@ python $R/tools/prof_stats.py /tmp/pd/d_results.db $O/c4_2048_kernel_stats.csv
 for w in 1024 2048 4096 8192 16384 32768; do echo -n "{\"walkers\": $w, \"line\": \"" >> $O/small_shards.txt; python $R/tools/scratch/lib_bench.py $R/pyqmc_amd/lib/libpyqmc_amd.so $w 2>/dev/null | tr -d '\n' >> $O/small_shards.txt; echo "\"}" >> $O/small_shards.txt; done
 rm -rf /tmp/pd; rocprofv3 --kernel-trace --stats -d /tmp/pd -o d -- python $R/tools/scratch/lib_bench.py $R/pyqmc_amd/lib/libpyqmc_amd.so 4096 > /dev/null 2>&1 < /dev/null
 python $R/tools/prof_stats.py /tmp/pd/d_results.db $O/m_4096_kernel_stats.csv
-# round 4: the pipelined half-ensemble sweep (A/B per mode + which kernels really overlap), the 2-rank same-GPU DMC rehearsal
-python $R/tools/split_ab.py --walkers $W --steps 10 1 2 3 > $O/split_ab.jsonl 2>> $O/bench.err < /dev/null
-for m in 0 1 2; do rm -rf /tmp/tr$m; rocprofv3 --kernel-trace --output-format csv -d /tmp/tr$m -o t -- python $R/tools/split_ab.py --walkers $W --steps 3 $m > /dev/null 2>&1 < /dev/null; echo "== PQA_SPLIT=$m (first block: mode 0 reference run, second: the mode)"; python $R/tools/trace_overlap.py $(find /tmp/tr$m -name "*kernel_trace.csv" | head -1) 0.25; done > $O/split_overlap.txt 2>&1
+# round 4: the 2-rank same-GPU DMC rehearsal
 (cd $R && python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --mode dmc --backend gloo --same-gpu --device-buffers --unbalance 0.5 --steps 20 --warmup 1 > $O/bench_dmc_2rank_same_gpu.json 2>> $O/bench.err < /dev/null)
 python $R/tools/cpu_config_baseline.py c2 c3 c4 c5 big > $O/cpu_config_baseline.jsonl 2>> $O/bench.err
 # round 5: handles beyond 64 electrons per spin, the protocol route, the resident sweep against the launch-per-move sweep, the LDS-DMA probe
@@ -66,7 +64,7 @@ timeout 120 $R/tools/scratch/bin/dma_probe > $O/dma_probe.txt 2>&1
 # round 5, later sessions: the periodic / complex resident sweep and the one-launch wave-per-walker sweep against the launches they replace, the
 # ECP point totals left on the device against the read-back
 for c in c3 c5; do for w in 4096 8192 16384; do for r in 1 0; do echo -n "{\"PQA_RES\": $r, \"line\": " >> $O/resident_pbc_ab.txt; PQA_RES=$r python $R/tools/config_bench.py $c --walkers $w --steps 8 2>/dev/null | tail -1 | tr -d '\n' >> $O/resident_pbc_ab.txt; echo "}" >> $O/resident_pbc_ab.txt; done; done; done
-for w in 1024 2048 4096; do for m in "PQA_WW=0 PQA_ECP_DEFER=0 PQA_EN_OVERLAP=0" "PQA_WW=0" "PQA_WW=3" "PQA_WW=1 PQA_ECP_DEFER=0" "PQA_WW=1"; do echo -n "{\"env\": \"$m\", \"line\": " >> $O/c4_one_launch_ab.txt; env $m python $R/tools/config_bench.py c4 --walkers $w --steps 20 2>/dev/null | tail -1 | tr -d '\n' >> $O/c4_one_launch_ab.txt; echo "}" >> $O/c4_one_launch_ab.txt; done; done
+for w in 1024 2048 4096; do for m in "PQA_WW=0 PQA_ECP_DEFER=0 PQA_EN_OVERLAP=0" "PQA_WW=0" "PQA_WW=1 PQA_ECP_DEFER=0" "PQA_WW=1"; do echo -n "{\"env\": \"$m\", \"line\": " >> $O/c4_one_launch_ab.txt; env $m python $R/tools/config_bench.py c4 --walkers $w --steps 20 2>/dev/null | tail -1 | tr -d '\n' >> $O/c4_one_launch_ab.txt; echo "}" >> $O/c4_one_launch_ab.txt; done; done
 for d in 0 1; do echo -n "{\"PQA_ECP_DEFER\": $d, \"line\": " >> $O/c4_one_launch_ab.txt; PQA_ECP_DEFER=$d python $R/tools/config_bench.py c2 --walkers 4096 --steps 40 2>/dev/null | tail -1 | tr -d '\n' >> $O/c4_one_launch_ab.txt; echo "}" >> $O/c4_one_launch_ab.txt; done
 # round 6: the second-generation resident sweep (k_sweep_r8) against k_sweep_res and the launch-per-move sweep, its phase stamps (timing build
 # libpqa_RCLK.so, in-tree: python -c "import __graft_entry__ as g, os; g.build(extra_flags=['-DPQA_RES_CLK'], lib=os.path.join(g.LIBDIR, 'libpqa_RCLK.so'))"),
