@@ -13,11 +13,6 @@
 #include "pqa_common.hpp"
 #include "pqa_sph_high.hpp"
 
-#define PQA_STR_(x) #x
-#define PQA_UNROLL_N(n) _Pragma(PQA_STR_(unroll n))  // (a macro inside '#pragma unroll' does not survive -save-temps builds)
-#ifndef PQA_PRIM_UNROLL
-#define PQA_PRIM_UNROLL 1
-#endif
 // exp of a non-positive argument (the Gaussians' -alpha r^2): round(x log2 e) and a two-term Cody-Waite reduction, a degree-11
 // polynomial on |r| <= ln 2 / 2 (near-minimax fit of (e^r - 1 - r) / r^2, so e^0 = 1 exactly), ldexp.  20 instructions where the
 // library routine takes 24 (it also serves positive arguments: two compare-and-select pairs for overflow / underflow); max error
@@ -58,17 +53,10 @@ __device__ __forceinline__ void exp_neg3(double x0, double x1, double x2, double
 #undef PQA_E3
   e0 = ldexp(p0, (int)k0); e1 = ldexp(p1, (int)k1); e2 = ldexp(p2, (int)k2);
 }
-#ifndef PQA_EXP_NEG
-#define PQA_EXP_NEG 1  // 0: library exp (A/B: k_orb<5> 129.2 -> 127.3 us, k_orb<1> 821 -> 790, periodic k_orb_wide 193 -> 187)
-#endif
-#if PQA_EXP_NEG
-#define PQA_EXP(x) exp_neg(x)
-#else
-#define PQA_EXP(x) exp(x)
-#endif
+// exp_neg in the primitive sums, against the library exp: k_orb<5> 129.2 -> 127.3 us, k_orb<1> 821 -> 790, periodic k_orb_wide 193 -> 187.
 // Primitive screening: skip a primitive with alpha r^2 > PQA_PRIM_CUT (it contributes < 2e-22 of its coefficient).  The test
 // is per lane and the exp sequence is only saved when EVERY lane of the wave skips.
-//  * open systems (-DPQA_PRIM_SCREEN=1, off): the 64 points of a wave are 64 different walkers, some lane is nearly always
+//  * open systems (not screened): the 64 points of a wave are 64 different walkers, some lane is nearly always
 //    close, and the compare + branch cost more than the rare skip saves (round 2, tools/scratch/ab_screen.sh: k_orb<5>
 //    136.7 -> 141.4 us per 65536 points).  Round 3 tried it on the values-only launches with the ECP points listed atom by atom
 //    (every tile within a few bohr of one atom, so distant atoms' tight primitives drop out for the whole wave): 826 -> 968 us
@@ -77,9 +65,6 @@ __device__ __forceinline__ void exp_neg3(double x0, double x1, double x2, double
 //  * periodic cells (always on, SCREEN template argument): every lane walks the images of an atom NEAREST FIRST, so from the
 //    second image on all lanes sit at r^2 >~ (half the cell)^2 and the tight primitives of a contracted shell drop out for
 //    the whole wave.
-#ifndef PQA_PRIM_SCREEN
-#define PQA_PRIM_SCREEN 0
-#endif
 #define PQA_PRIM_CUT 50.0
 
 // p-th point lives at base + (p / group) * group_stride + (p % group) * 3
@@ -185,15 +170,11 @@ __device__ __forceinline__ void shell_eval(int l, double x, double y, double z, 
                                            const double* __restrict__ pcoef, int np, Sink&& sink) {
   const double r2 = x * x + y * y + z * z;
   double R = 0.0, dRs = 0.0, lapR = 0.0;
-  PQA_UNROLL_N(PQA_PRIM_UNROLL)
+#pragma unroll 1
   for (int p = 0; p < np; ++p) {
     const double a = pexp[p];
-    if ((SCREEN || PQA_PRIM_SCREEN) && a * r2 > PQA_PRIM_CUT) continue;
-#ifdef PQA_ABL_NOEXP  // ablation builds only (tools/scratch/abl_pbc.sh): wrong values, kernel timing only
-    const double t = pcoef[p] * (1.0 - 1e-3 * a * r2);
-#else
-    const double t = pcoef[p] * PQA_EXP(-a * r2);
-#endif
+    if (SCREEN && a * r2 > PQA_PRIM_CUT) continue;
+    const double t = pcoef[p] * exp_neg(-a * r2);
     R += t;
     if (NCOMP > 1) dRs += a * t;
     if (NCOMP == 5) lapR += t * (2.0 * a) * (2.0 * a * r2 - 3.0);
@@ -373,7 +354,7 @@ __device__ __forceinline__ void pbc_ctx_update(const SysDev& S, PbcCtx& c, int i
 // the image phase) and hands them to sink(m, ...) and sink_im(m, ...).  Untwisted: sink only.
 // ls(j, lx, ly, lz, ph): lattice vector (and, twisted, the (cos, sin) phase) of image j — from the kernel's LDS copy where it has one:
 // the image walk alone (list decode, a per-lane gather of the vector, r^2, the range test) was a third of k_orb<5> and two thirds
-// of k_orb<1> in a periodic cell with the vectors gathered from global memory (compile-time ablation, tools/scratch/abl_pbc.sh).
+// of k_orb<1> in a periodic cell with the vectors gathered from global memory (measured with a compile-time ablation build).
 template <int NCOMP, bool TW = false, int LMAX = 3, class Sink, class SinkIm, class LsGet>
 __device__ __forceinline__ void shell_eval_pbc(const SysDev& S, const PbcCtx& c, int sh, int l, const double* __restrict__ pexp,
                                                const double* __restrict__ pcoef, int np, Sink&& sink, SinkIm&& sink_im, bool& accumulate,
@@ -382,14 +363,12 @@ __device__ __forceinline__ void shell_eval_pbc(const SysDev& S, const PbcCtx& c,
   // sinks to add instead of store): 7 x NCOMP running sums in registers — twice that for a twisted cell — were 70 / 140 of
   // the kernel's ~255 registers, pinned it at 2 (twisted: 1) waves per SIMD and spilled.
   accumulate = false;
-#ifndef PQA_ABL_NOZERO
 #pragma unroll
   for (int m = 0; m < 2 * LMAX + 1; ++m)
     if (m < 2 * l + 1) {
       sink(m, 0.0, 0.0, 0.0, 0.0, 0.0);
       if (TW) sink_im(m, 0.0, 0.0, 0.0, 0.0, 0.0);
     }
-#endif
   accumulate = true;
   const int nimg = S.pb->num_Ls[c.ia];
   const double scut = S.pb->shell_cut[sh];
@@ -411,11 +390,7 @@ __device__ __forceinline__ void shell_eval_pbc(const SysDev& S, const PbcCtx& c,
   // wave sit anywhere in the cell: iterating over image indices in lock-step would make every lane wait for the union of
   // all lanes' images).  Iterations = max over lanes of the number of images inside the shell's range.
   {
-#ifdef PQA_ABL_NOWALK
-    bool alive = false;
-#else
     bool alive = !c.ovf;
-#endif
     unsigned long long cur = 0ull;
     int k = 0;
     while (__any(alive)) {
@@ -429,11 +404,7 @@ __device__ __forceinline__ void shell_eval_pbc(const SysDev& S, const PbcCtx& c,
           double lx, ly, lz, cj = 1.0, sj = 0.0;
           ls(j, lx, ly, lz, cj, sj);
           const double xj = c.x0 - lx, yj = c.y0 - ly, zj = c.z0 - lz;
-#ifdef PQA_ABL_NOADD
-          if (xj * xj + yj * yj + zj * zj <= scut) { if (xj == 1.2345e300) add(xj, yj, zj, j, cj, sj); }
-#else
           if (xj * xj + yj * yj + zj * zj <= scut) add(xj, yj, zj, j, cj, sj);
-#endif
           else alive = false;  // sorted by distance: nothing further can be inside
         }
       }
@@ -901,11 +872,7 @@ static __global__ __launch_bounds__(256) void k_orb(SysDev S, ChunkTab T, int sp
           bq[ks][u] = (ut < NT) ? crow[(long)ks * 4 * ldc + 16 * ut] : 0.0;
         }
     }
-#ifdef PQA_ABL_NOP1
-    const int s_end = 0;
-#else
     const int s_end = cw_off[ch * G + grp + 1];
-#endif
     for (int si = cw_off[ch * G + grp]; si < s_end; ++si) {
       const int sh = cw_shell[si];
       int l_, np_, q0, kb, ia_ = 0, rt_ = -1, rn_ = 0;
@@ -983,11 +950,7 @@ static __global__ __launch_bounds__(256) void k_orb(SysDev S, ChunkTab T, int sp
         for (int c = 0; c < NCOMP; ++c) {
           const double a = tile[c][k][col];
 #pragma unroll
-#ifdef PQA_ABL_NOMFMA
-          for (int u = 0; u < NU; ++u) acc[u][c][0] += a * bq[ks][u];
-#else
           for (int u = 0; u < NU; ++u) acc[u][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bq[ks][u], acc[u][c], 0, 0, 0);
-#endif
         }
       }
     }
@@ -1166,12 +1129,6 @@ static __global__ __launch_bounds__(512) void k_orb_ws(SysDev S, ChunkTab T, int
 // (up to ~150 KB: one block per CU), and after a single barrier the waves contract (component, orbital tile) pairs over the
 // full K with v_mfma_f64_16x16x4_f64.  Same shell routines, same coefficient layout (the chunk table's padded row order), so
 // rows are identical to k_orb's up to the MFMA accumulation order (one K loop instead of per-chunk partial sums).
-#ifdef PQA_WIDE_CLK  // timing build only (tools/scratch/wide_clk.py): 100 MHz stamps of the phases of the first blocks
-static __device__ unsigned long long pqa_wide_clk[1024 * 8];
-#define PQA_CLK(k) do { if (blockIdx.x < 1024 && threadIdx.x == 0) pqa_wide_clk[blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
-#else
-#define PQA_CLK(k) do { } while (0)
-#endif
 struct WideTab {
   const int* off;     // [65] shells of lane group g: shell[off[g] .. off[g+1]); 64 groups (1024 threads) or 32 (512 threads)
   const int* shell;
@@ -1188,7 +1145,6 @@ __host__ __device__ inline size_t wide_lds_bytes(int ncomp, int rows_pad, int ns
 template <int NCOMP, int NT, int PBC, int NTH>
 static __global__ __launch_bounds__(NTH) void k_orb_wide(SysDev S, ChunkTab T, WideTab Wt, int spin, PointAddr pa, long P, double* __restrict__ out) {
   extern __shared__ double wl[];
-  PQA_CLK(0);
   const int K = Wt.rows_pad;
   double* tile = wl;                                  // [NCOMP][K][16]
   double* sh_xyz = tile + (size_t)NCOMP * K * 16;     // [nshell][3]
@@ -1224,7 +1180,6 @@ static __global__ __launch_bounds__(NTH) void k_orb_wide(SysDev S, ChunkTab T, W
   for (int p = tid; p < S.nprim; p += NTH) { pr_exp[p] = S.prim_exp[p]; pr_coef[p] = S.prim_coef[p]; }
   for (int k = tid; k < NCOMP * K * 16; k += NTH) tile[k] = 0.0;  // (the K padding rows stay zero)
   __syncthreads();
-  PQA_CLK(1);
   const int pl = tid & 15, grp = tid >> 4;
   const long p0 = (long)blockIdx.x * 16;
   const long pmine = (p0 + pl < P) ? p0 + pl : P - 1;
@@ -1272,12 +1227,7 @@ static __global__ __launch_bounds__(NTH) void k_orb_wide(SysDev S, ChunkTab T, W
       } else shell_eval_pbc<NCOMP, false>(S, ctx, sh, l_, pe, pc, np_, to_tile, to_tile, accum, ls_get);
     } else shell_eval<NCOMP>(l_, x, y, z, pe, pc, np_, to_tile);
   }
-  PQA_CLK(2);
-#ifdef PQA_WIDE_CLK
-  if (blockIdx.x < 1024 && threadIdx.x == NTH - 64) pqa_wide_clk[blockIdx.x * 8 + 6] = wall_clock64();  // (last wave's phase 1)
-#endif
   __syncthreads();
-  PQA_CLK(3);
   // contraction: wave <-> (component c, orbital tile ut); D[point][orbital] += A[point][k] B[k][orbital], B straight from L2
   const double* __restrict__ C = T.cpad[spin];
   const int ldc = T.ldc[spin], nmo = S.nmo[spin];
@@ -1302,7 +1252,6 @@ static __global__ __launch_bounds__(NTH) void k_orb_wide(SysDev S, ChunkTab T, W
       for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc, 0, 0, 0);
     }
     for (; ks < K / 4; ++ks) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a_[(size_t)ks * 64], b_[(size_t)ks * 4 * ldc], acc, 0, 0, 0);
-    PQA_CLK(4);
     const int j = 16 * ut + i16;
     if (j < nmo) {
 #pragma unroll
@@ -1310,5 +1259,4 @@ static __global__ __launch_bounds__(NTH) void k_orb_wide(SysDev S, ChunkTab T, W
         if (orow[r]) orow[r][c * nmo + j] = acc[r];
     }
   }
-  PQA_CLK(5);
 }

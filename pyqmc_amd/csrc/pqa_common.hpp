@@ -5,9 +5,7 @@
 
 #define PQA_WAVE 64
 #define PQA_MAXBAS 16     // max two-body Jastrow basis functions per kind (hot kernels loop to na / nb; only the protocol kernels' register arrays have this length)
-#ifndef PQA_MAXBAS3
 #define PQA_MAXBAS3 8     // max three-body basis functions per kind (fully unrolled register arrays in jas3_eval)
-#endif
 #define PQA_JQ 24         // doubles per merged-numerator record (N1[4], N2[7], N3[10], padding)
 #define PQA_MAXN 128      // max electrons / orbitals per spin (real orbitals; up to 64 on every fast path, above: the two-slot wave kernels)
 #define PQA_MAXN_FAST 64  // one lane per column: LDS-staged determinant tile, lane-per-walker planes, four 16-column MFMA tiles

@@ -21,9 +21,7 @@
 #include "pqa_energy.hpp"
 #include "pqa_lw.hpp"
 
-#ifndef PQA_ECP_WB
 #define PQA_ECP_WB 4  // walkers (waves) per block of the list-building passes
-#endif
 
 struct EcpTab {  // same member names as the SysDev tables: ecp_radial_t works on either
   const int* ecp_chan_off;

@@ -83,9 +83,7 @@ static __global__ __launch_bounds__(256) void k_cache_from_rc(const double* __re
 // Contribution of the pairs j = j0, j0+dj, ... and ions I = j0, j0+dj, ... to U_e, grad U_e, (bare) lap U_e
 // of electron e of walker w at (rx,ry,rz); MODE 2 also returns that share of the Coulomb sums
 // ee = sum_{j>e} 1/r, ei = -sum Z/r.  (j0,dj) = (0,1) gives the full sums.
-#ifndef PQA_JAS_PF
 #define PQA_JAS_PF 4
-#endif
 #define PQA_JAS_NF 4  // basis functions per kind whose tables the fast path keeps in scalar registers
 // FAST (nb, na <= PQA_JAS_NF, the reference's default Jastrow has 4 + 4): the function tables (kind, parameter, cusp constant,
 // the two coefficient columns electron e can meet) are read ONCE into scalar registers.  Indexed by the loop variable they
@@ -339,7 +337,6 @@ __device__ __forceinline__ void lw_move_sums(const SysDev& S, const LwState& L, 
   const int s = e >= S.nup, i = e - s * S.nup, n = s ? S.ndn : S.nup, nmo = S.nmo[s];
   constexpr int CF = CX ? 2 : 1;
   double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;  // q: imaginary parts (CX)
-#ifndef PQA_MP_NOSLATER
   {
     const double* Ti = L.Tt[s] + (size_t)i * n * CF * W + w;
     const int* occ = S.det_occ[s];
@@ -404,11 +401,8 @@ __device__ __forceinline__ void lw_move_sums(const SysDev& S, const LwState& L, 
       }
     }
   }
-#endif
   double U = 0.0, gg[3] = {0.0, 0.0, 0.0};
-#ifndef PQA_MP_NOJAS
   lw_jastrow_part<PBC, UJ>(S, L, e, has_jastrow, px, py, pz, W, w, g, G, jskip, U, gg);
-#endif
   if (CX) {  // rows: Re r0, Im r0, Re r1, Im r1, ..., then U, grad U
     p[0] = r0; p[1] = q0; p[2] = r1; p[3] = q1; p[4] = r2; p[5] = q2; p[6] = r3; p[7] = q3;
     p[PQA_LW_PART_ROWS(CX) - 4] = U; p[PQA_LW_PART_ROWS(CX) - 3] = gg[0]; p[PQA_LW_PART_ROWS(CX) - 2] = gg[1]; p[PQA_LW_PART_ROWS(CX) - 1] = gg[2];
@@ -443,9 +437,7 @@ __device__ __forceinline__ void lw_slater_terms(const double (&v)[PR], double& g
 // in LDS once and shared by the row groups — read per row from global memory they were 4x the traffic of the inverse
 // itself (1.26 ms per flush at 65 536 walkers).  A row's arithmetic and its order are unchanged (bitwise identical).
 // 16 consecutive walkers are 128 contiguous bytes of every (row, column) plane: two full cache lines per access.
-#ifndef PQA_FLUSH_WB
 #define PQA_FLUSH_WB 16
-#endif
 // PQA_ROWDOT — the order of a row's dot product V . T[j] in EVERY lane-per-walker kernel that updates rows (k_flush_lw, the commit
 // halves of k_step_lw and k_step_pre): four partial sums over the quarters [q NMAX/4, (q + 1) NMAX/4) of the row's NMAX-padded
 // columns, each in ascending k, combined as ((p0 + p1) + p2) + p3 (complex rows: quarters of the complex columns, real and imaginary
@@ -562,16 +554,8 @@ struct StepArgs {
 // Block = NW walkers x G groups, <= 256 threads.  WIDE: NW = 64, a wave is one group (g wave-uniform: table look-ups stay scalar
 // loads).  Otherwise NW = 16 or 32 and a wave holds 4 or 2 groups of the same walkers: small shards then spread over 4x / 2x
 // as many blocks — with 64 walkers per block 4096 walkers are 64 blocks on 64 of the 256 CUs, each issuing all 16 groups' work.
-#ifndef PQA_STEP_MINW
-#define PQA_STEP_MINW 0  // > 0: minimum waves per SIMD the register allocation of k_step_lw must allow (A/B: tools/scratch/r3_ab_simple.sh)
-#endif
-#if PQA_STEP_MINW > 0
-#define PQA_STEP_BOUNDS __launch_bounds__(256, PQA_STEP_MINW)
-#else
-#define PQA_STEP_BOUNDS __launch_bounds__(256)
-#endif
 template <bool PBC, bool CX, int NMAX, bool WIDE>
-static __global__ PQA_STEP_BOUNDS void k_step_lw(SysDev S, LwState L, MoveBuf mb, StepArgs a) {
+static __global__ __launch_bounds__(256) void k_step_lw(SysDev S, LwState L, MoveBuf mb, StepArgs a) {
   extern __shared__ double sh[];
   constexpr int PR = PQA_LW_PART_ROWS(CX), JU = CX ? 8 : 4, CF = CX ? 2 : 1;
   const int NW = WIDE ? 64 : a.NW;
@@ -706,7 +690,6 @@ static __global__ PQA_STEP_BOUNDS void k_step_lw(SysDev S, LwState L, MoveBuf mb
     // ---- rows of the electron block (k_flush_lw brings the others up to date when the block ends).  Rejected walkers take
     // part in the loads and stores (writing back what they read): a cache line holds 8 walkers, so it is fetched and written
     // whenever one of them accepted anyway, and with every lane storing the wave writes whole lines.
-#ifndef PQA_ST_NOCOMMIT
     if (__any(acc)) {
       double* T = L.Tt[s] + w;
       for (int j = a.j_lo + g; j < a.j_hi; j += G) {
@@ -756,7 +739,6 @@ static __global__ PQA_STEP_BOUNDS void k_step_lw(SysDev S, LwState L, MoveBuf mb
         }
       }
     }
-#endif
     __syncthreads();  // inverse rows, coordinate: visible to the other groups of this walker block
   }
   if (a.e_prop >= 0) {
@@ -818,15 +800,12 @@ static __global__ PQA_STEP_BOUNDS void k_step_lw(SysDev S, LwState L, MoveBuf mb
 // half through LDS instead of a store / barrier / load.  Registers are no object here (one wave per SIMD).
 // Every sum is formed from the same operands in the same order as in k_step_lw / lw_move_sums / jas_eval_lane_t<.., FAST>; the
 // compiler contracts multiply-adds differently in the two inlining contexts, so a group's Jastrow gradient sum can differ in its
-// last bit: same decisions, walkers equal to ~1e-14 after a sweep (measured with the -DPQA_PRE_DBG builds, which swap single
-// parts back to the k_step_lw routines; tests/test_gpu_fullsize.py::test_prefetching_step_kernel_against_the_general_one).
+// last bit: same decisions, walkers equal to ~1e-14 after a sweep (measured with builds that swapped single parts back to the
+// k_step_lw routines; tests/test_gpu_fullsize.py::test_prefetching_step_kernel_against_the_general_one).
 // Scope (the host falls back to k_step_lw otherwise): real orbitals, ground-state occupation lists, Jastrow tables of at most
 // PQA_JAS_NF functions per kind, G >= 8 groups with N <= PQA_PRE_NP G electrons, natom <= PQA_PRE_NA G ions, and a
 // Sherman-Morrison block of at most G rows.
 #define PQA_PRE_NP 8
-#ifndef PQA_PRE_DBG
-#define PQA_PRE_DBG 0  // bisecting aid: 1 / 2 decide / propose sums by lw_move_sums, 4 / 8 only their Jastrow part by jas_eval_lane
-#endif
 #define PQA_PRE_NA 4
 struct JasTabs {  // wave-uniform function tables (scalar registers)
   int bk[PQA_JAS_NF], ak[PQA_JAS_NF];
@@ -896,18 +875,11 @@ __device__ __forceinline__ void jas_pre(const SysDev& S, const JasTabs& J, int e
 // GW = 32 / 64 (round 4): 16 walkers x GW groups = 512 / 1024 threads — two / ONE partner electron and ion per thread, so the two
 // Jastrow pair loops that made up most of the ~3000-instruction dependent chain of a launch become one or two pair evaluations;
 // the groups' partial sums are totalled by eight threads per walker (one per row of the sums, group order) instead of by every thread.
-#ifdef PQA_PRE_CLK  // timing build only (tools/scratch/pre_clk.py): 100 MHz stamps of the phases of the first 256 blocks of the LAST launch
-static __device__ unsigned long long pqa_pre_clk[256 * 16];
-#define PQA_PCLK(k) do { if (blockIdx.x < 256 && threadIdx.x == 0) pqa_pre_clk[blockIdx.x * 16 + (k)] = wall_clock64(); } while (0)
-#else
-#define PQA_PCLK(k) do { } while (0)
-#endif
 template <bool PBC, int NMAX, int GW = 16>
 static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(SysDev S, LwState L, MoveBuf mb, StepArgs a) {
   extern __shared__ double sh[];
   constexpr int PR = 8, JU = 4, NF = PQA_JAS_NF;
   constexpr int NS = GW == 16 ? (NMAX + 7) / 8 : (NMAX + GW - 1) / GW, NP = GW == 16 ? PQA_PRE_NP : 64 / GW, NA = GW == 16 ? PQA_PRE_NA : 64 / GW;
-  PQA_PCLK(0);
   const int NW = a.NW, G = a.G;
   const int lane = (int)threadIdx.x % NW, g = (int)threadIdx.x / NW;
   const long W = a.W;
@@ -1018,7 +990,6 @@ static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(Sy
       for (int u = 0; u < NS; ++u) rv2[c][u] = (jb2 + u < je2) ? row2[c * nmo2 + jb2 + u] : 0.0;
   }
   bool acc = false;
-  PQA_PCLK(1);
   if (has_a) {
     const int e = ea;
     {
@@ -1026,29 +997,13 @@ static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(Sy
 #pragma unroll
       for (int u = 0; u < NS; ++u)
         if (jb + u < je) { const double t = tinv[u]; r0 += rv[0][u] * t; r1 += rv[1][u] * t; r2 += rv[2][u] * t; r3 += rv[3][u] * t; }
-#ifdef PQA_PRE_CLK
-      if (blockIdx.x < 256 && threadIdx.x == 0) pqa_pre_clk[blockIdx.x * 16 + 2] = wall_clock64() + (r0 == 1.2345e300 ? 1 : 0);  // the Slater sums (= every load of the first two round trips) done
-#endif
       double U, gg[3];
       jas_pre<PBC, NP, NA>(S, J, e, npx, npy, npz, a.has_jastrow, g, G, pcx, pcy, pcz, atx, aty, atz, bcA0, bcA1, acA, U, gg);
-#ifdef PQA_PRE_CLK
-      if (blockIdx.x < 256 && threadIdx.x == 0) pqa_pre_clk[blockIdx.x * 16 + 3] = wall_clock64() + (U == 1.2345e300 ? 1 : 0);  // this thread's Jastrow pairs done
-#endif
-#if PQA_PRE_DBG & 1
-      double p[PR];
-      lw_move_sums<PBC, false>(S, L, e, a.has_jastrow, npx, npy, npz, lw_row(L, s, i, cur ^ 1, w, W, nmo), W, w, g, G, p);
-#elif PQA_PRE_DBG & 4
-      double lp_, ee_, ei_;
-      jas_eval_lane<1, PBC>(S, L.xt, W, w, e, npx, npy, npz, a.has_jastrow, g, G, U, gg, lp_, ee_, ei_);
       const double p[PR] = {r0, r1, r2, r3, U, gg[0], gg[1], gg[2]};
-#else
-      const double p[PR] = {r0, r1, r2, r3, U, gg[0], gg[1], gg[2]};
-#endif
 #pragma unroll
       for (int c = 0; c < PR; ++c) shP[(c * G + g) * NW + lane] = p[c];
     }
     __syncthreads();
-    PQA_PCLK(4);
     double v[PR];
     if (GW > 16) {
       if (g < PR) {
@@ -1057,7 +1012,6 @@ static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(Sy
         shTot[g * NW + lane] = tsum;
       }
       __syncthreads();
-      PQA_PCLK(5);
 #pragma unroll
       for (int c = 0; c < PR; ++c) v[c] = shTot[c * NW + lane];
     } else {
@@ -1099,9 +1053,6 @@ static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(Sy
       u = u01(ph.c[0], ph.c[1]);
     }
     acc = ratio > u;
-#ifdef PQA_PRE_CLK
-    if (blockIdx.x < 256 && threadIdx.x == 0) pqa_pre_clk[blockIdx.x * 16 + 6] = wall_clock64() + (acc ? 0 : 0);  // decided
-#endif
     if (lead) {
       if (mb.dmc) {
         const double rx = a0 + d0, ry = a1 + d1, rz = a2 + d2;
@@ -1110,9 +1061,7 @@ static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(Sy
         if (acc) mb.r2_acc[w] += r2;
       }
       a.act[w] = acc;
-#if !(PQA_PRE_DBG & 32)
       if (mb.accept_rec) mb.accept_rec[(size_t)e * W + w] = acc;
-#endif
       if (acc) {
         mb.acc_w[w] += 1;
         L.sel[s][(size_t)i * W + w] = (uint8_t)(cur ^ 1);
@@ -1143,7 +1092,6 @@ static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(Sy
       }
     }
     __syncthreads();
-    PQA_PCLK(7);
     // ---- the block rows
     if (QUART) {
       // quarter sums of V . T[jrow] -> LDS (the partial-sum planes are free: every group has read its totals), then every thread of
@@ -1156,9 +1104,6 @@ static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(Sy
       }
       shP[g * NW + lane] = pq;
       __syncthreads();
-#ifdef PQA_PRE_CLK
-      if (blockIdx.x < 256 && threadIdx.x == 0) pqa_pre_clk[blockIdx.x * 16 + 12] = wall_clock64();
-#endif
       if (has_row) {
         double* Tj = L.Tt[s] + (size_t)jrow * n * W + w;
         const bool any = __any(acc);  // k_step_lw stores nothing where no lane of the wave accepted
@@ -1174,15 +1119,11 @@ static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(Sy
 #pragma unroll
           for (int u = 0; u < TBN; ++u)
             if (kq0 + u < n) tb[u] = acc ? tb[u] - shR[(kq0 + u) * NW + lane] * tmp : tb[u];
-#ifdef PQA_PRE_CLK
-          if (blockIdx.x < 256 && threadIdx.x == 0) pqa_pre_clk[blockIdx.x * 16 + 13] = wall_clock64() + (tb[0] == 1.2345e300 ? 1 : 0);
-#endif
           if (live && any) {
 #pragma unroll
             for (int u = 0; u < TBN; ++u)
               if (kq0 + u < n) Tj[(size_t)(kq0 + u) * W] = tb[u];
           }
-          PQA_PCLK(14);
           if (handoff && jrow == i2) {
 #pragma unroll
             for (int u = 0; u < TBN; ++u)
@@ -1221,20 +1162,10 @@ static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(Sy
       }
     }
     __syncthreads();
-    PQA_PCLK(8);
     // the accepted proposal replaces the electron's coordinate in the register copy
-#if PQA_PRE_DBG & 16
-#pragma unroll
-    for (int m = 0; m < NP; ++m) {
-      const int j = g + m * G;
-      const double* xj = L.xt + (size_t)(j < S.nelec ? j : 0) * 3 * W + w;
-      pcx[m] = xj[0]; pcy[m] = xj[W]; pcz[m] = xj[2 * W];
-    }
-#else
 #pragma unroll
     for (int m = 0; m < NP; ++m)
       if (acc && g + m * G == e) { pcx[m] = npx; pcy[m] = npy; pcz[m] = npz; }
-#endif
   }
   if (has_p) {
     // ---- drift at the current position, proposal r' = r + sqrt(tau) z + tau limdrift(grad)   (mc.py:117-121)
@@ -1250,29 +1181,11 @@ static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(Sy
         if (jb2 + u < je2) { const double t = tinv2[u]; r0 += rv2[0][u] * t; r1 += rv2[1][u] * t; r2 += rv2[2][u] * t; r3 += rv2[3][u] * t; }
       double U, gg[3];
       jas_pre<PBC, NP, NA>(S, J, e, xe2[0], xe2[1], xe2[2], a.has_jastrow, g, G, pcx, pcy, pcz, atx, aty, atz, bcP0, bcP1, acP, U, gg);
-#if PQA_PRE_DBG & 32
-      {
-        double U2, g2[3], lp_, ee_, ei_;
-        jas_eval_lane<1, PBC>(S, L.xt, W, w, e, xe2[0], xe2[1], xe2[2], a.has_jastrow, g, G, U2, g2, lp_, ee_, ei_);
-        const int code = (U != U2 ? 1 : 0) | (gg[0] != g2[0] ? 2 : 0) | (gg[1] != g2[1] ? 4 : 0) | (gg[2] != g2[2] ? 8 : 0);
-        shV[g * NW + lane] = (double)(code ? (code | (g << 4)) : 0);
-      }
-#endif
-#if PQA_PRE_DBG & 2
-      double p[PR];
-      lw_move_sums<PBC, false>(S, L, e, a.has_jastrow, xe2[0], xe2[1], xe2[2], lw_row(L, s2, i2, cur2, w, W, nmo2), W, w, g, G, p);
-#elif PQA_PRE_DBG & 8
-      double lp_, ee_, ei_;
-      jas_eval_lane<1, PBC>(S, L.xt, W, w, e, xe2[0], xe2[1], xe2[2], a.has_jastrow, g, G, U, gg, lp_, ee_, ei_);
       const double p[PR] = {r0, r1, r2, r3, U, gg[0], gg[1], gg[2]};
-#else
-      const double p[PR] = {r0, r1, r2, r3, U, gg[0], gg[1], gg[2]};
-#endif
 #pragma unroll
       for (int c = 0; c < PR; ++c) shP[(c * G + g) * NW + lane] = p[c];
     }
     __syncthreads();
-    PQA_PCLK(9);
     if (GW > 16) {
       if (g < PR) {
         double tsum = 0.0;
@@ -1281,7 +1194,6 @@ static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(Sy
       }
       __syncthreads();
     }
-    PQA_PCLK(10);
     if (!lead) return;
     double v[PR];
     if (GW > 16) {
@@ -1316,52 +1228,39 @@ static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(Sy
     if (mb.dwrap) fold_cell(S, np_[0], np_[1], np_[2], mb.dwrap + 3 * w);  // make_irreducible, mc.py:121
     double* ao = L.auxt + w;
     ao[0] = z0; ao[W] = z1; ao[2 * W] = z2; ao[3 * W] = gx; ao[4 * W] = gy; ao[5 * W] = gz; ao[6 * W] = v[JU];
-    PQA_PCLK(11);
   }
 }
 
 // ---------------------------------------------------------------- kinetic + Coulomb
 // thread = (walker, electron), walker fastest.  part [5][N][W]: ke_e, grad2_e, ee_e, ei_e, U_e (Jastrow exponent of electron e)
-// block = (64 walkers, PQA_KIN_EB electrons): one wave per electron, so the electron index — and with it the spin, the orbital
-// occupation list and every Jastrow table address — must stay wave-uniform (scalar loads): threadIdx.y goes through
-// readfirstlane.  (As a plain per-lane value it turned the occupation look-up of the inner loop into a dependent vector load:
-// 2.0 -> 3.3 ms per evaluation.)  Every electron's thread walks ALL coordinates of its walker for the Jastrow and Coulomb sums,
-// so the 64 electron-waves of a walker group pull the group's coordinates through the fabric 64 times (the counters show
+// block = 64 walkers of one electron, so the electron index — and with it the spin, the orbital occupation list and every
+// Jastrow table address — is wave-uniform (scalar loads).  (As a per-lane value it turned the occupation look-up of the inner
+// loop into a dependent vector load: 2.0 -> 3.3 ms per evaluation.)  Every electron's thread walks ALL coordinates of its
+// walker for the Jastrow and Coulomb sums, so the 64 electron-waves of a walker group pull the group's coordinates through the fabric 64 times (the counters show
 // 195 KB per walker against 96 KB of inverse + cache rows; the re-reads hit the Infinity Cache).
 // Where the time goes at 65 536 walkers (round 6, tools/scratch/row_probe.hip + kernel variants): the row cache alone streams at 5.0 (a lane per
 // row) to 5.8 TB/s (a quad per line), the inverse planes alone at 5.8 TB/s — 1.1 ms for both — but read in the same kernel, even by different
 // blocks, the two streams take 1.5-1.9 ms (tile-blocked inverse: 1.55): the mix, not either pattern, costs the bandwidth.  The coordinate walk
-// of the Jastrow / Coulomb sums (96 KB per wave out of L2) adds 0.28 ms on top although its arithmetic is 0.07 ms.  PQA_KIN_V: 1 = a lane
-// streams its own row (1.86 ms), 3 = quad-cooperative lines in the QUAD instantiation (1.79 ms, default; shards below 16 384 walkers take the
-// other one: 163 against 121 registers, and 4 096 walkers are one round of waves only at four per SIMD — 195 vs 231 us for C5), 4 = V1 with
-// half a component requested ahead (1.84 ms).
-#ifndef PQA_KIN_EB
-#define PQA_KIN_EB 1
-#endif
-#ifndef PQA_KIN_V
-#define PQA_KIN_V 3
-#endif
-// PQA_KIN_C0 = 1 (default): the quad-cooperative instantiation does not read the VALUE block of the cached rows.  The reference divides the
+// of the Jastrow / Coulomb sums (96 KB per wave out of L2) adds 0.28 ms on top although its arithmetic is 0.07 ms.  Row reads measured: a lane
+// streams its own row (1.86 ms), quad-cooperative lines in the QUAD instantiation (1.79 ms, kept; shards below 16 384 walkers take the
+// other one: 163 against 121 registers, and 4 096 walkers are one round of waves only at four per SIMD — 195 vs 231 us for C5), a lane's own
+// row with half a component requested ahead (1.84 ms, removed).
+// The quad-cooperative instantiation does not read the VALUE block of the cached rows.  The reference divides the
 // derivative sums by sum_j phi_j(r_i) T_ji (slater.py gradient_laplacian: ratios[1:] / ratios[0]) — at the electron's own position that is row i of
 // the Slater matrix times column i of its inverse: 1, up to the rounding the inverse has accumulated since the last recompute.  Taking it as 1
 // saves a fifth of the row traffic (1.78 -> 1.68 ms at 65 536 walkers); measured on (H2O)8, 16 384 walkers, 40 sweeps without a recompute, the
 // steps' kinetic-energy means agree with the dividing build to the last bit or one ulp (<= 4e-16 relative; tools/scratch/c0_check.py).
-// -DPQA_KIN_C0=0 restores the division.
-#ifndef PQA_KIN_C0
-#define PQA_KIN_C0 1
-#endif
 template <bool PBC, bool CX = false, bool QUAD = false>  // QUAD: quad-cooperative row reads (large shards; real determinants, W % 4 == 0)
-static __global__ __launch_bounds__(64 * PQA_KIN_EB) void k_kinetic_lw(SysDev S, LwState L, int has_jastrow, long W, double* __restrict__ part) {
-  // Block b -> (walker group, electron block): the electron blocks of ONE walker group sit 8 apart in the linear block order, so
+static __global__ __launch_bounds__(64) void k_kinetic_lw(SysDev S, LwState L, int has_jastrow, long W, double* __restrict__ part) {
+  // Block b -> (walker group, electron): the electron blocks of ONE walker group sit 8 apart in the linear block order, so
   // they land on the same XCD (blocks go to the XCDs round-robin) and run at about the same time: the group's coordinates, which
   // every one of them walks, come out of that XCD's L2 after the first.  (With the electron on grid.y the 64 blocks of a group were
   // 1 024 blocks apart and every one fetched the coordinates again: 195 KB per walker through the fabric against 98 KB of rows and
   // inverses, at 6.2 TB/s — the kernel was bound by re-reads.)
-  const int neb_ = (S.nelec + PQA_KIN_EB - 1) / PQA_KIN_EB;
-  const long chunk = (long)blockIdx.x / (8 * neb_);
-  const int rem = (int)((long)blockIdx.x % (8 * neb_));
+  const long chunk = (long)blockIdx.x / (8 * S.nelec);
+  const int rem = (int)((long)blockIdx.x % (8 * S.nelec));
   const long w = (chunk * 8 + (rem & 7)) * 64 + threadIdx.x;
-  const int e = (rem >> 3) * PQA_KIN_EB + (PQA_KIN_EB > 1 ? __builtin_amdgcn_readfirstlane((int)threadIdx.y) : 0);
+  const int e = rem >> 3;
   if (w >= W || e >= S.nelec) return;
   const int s = e >= S.nup, i = e - s * S.nup, n = s ? S.ndn : S.nup, nmo = S.nmo[s];
   constexpr int CF = CX ? 2 : 1;
@@ -1375,14 +1274,13 @@ static __global__ __launch_bounds__(64 * PQA_KIN_EB) void k_kinetic_lw(SysDev S,
       // ground-state occupation: whole 64-byte lines of the lane's own row, two adjacent 32-byte loads each, used up at once
       // (walking 4 slots of all five components first left every line half used until the next round: 320 lines per wave in
       // flight, more than L1 keeps with 16 waves per CU — the kernel took 3.5 ms instead of 1.9)
-#if PQA_KIN_V == 3 || PQA_KIN_V == 1
       // Quad-cooperative rows: the four lanes of a quad (walkers wq .. wq + 3) read the row of each of the four walkers together, 16 bytes per
       // lane = one whole 64-byte line per quad and instruction, 16 lines per wave-instruction.  (A lane streaming its own row touches a line of
       // its own per load: 64 lines per instruction, and the address path — one line per cycle and CU — not HBM set the kernel's time: 3.7 TB/s.)
       // Lane q of the quad holds orbital slots j + 2q, j + 2q + 1 of each 8-slot line, so it takes those two slots of the inverse row of ALL four
       // walkers (two 32-byte loads of T[slot][wq .. wq + 3]) and accumulates its share of all four walkers' sums; the quad adds the shares at the
       // end (DPP) and lane q keeps walker wq + q's.
-      if (QUAD && PQA_KIN_V == 3 && n <= 32 && (W & 3) == 0) {
+      if (QUAD && n <= 32 && (W & 3) == 0) {
         const int q = (int)threadIdx.x & 3;
         const long wq = w - q;
         const uint32_t s4 = *reinterpret_cast<const uint32_t*>(L.sel[s] + (size_t)i * W + wq);
@@ -1399,19 +1297,19 @@ static __global__ __launch_bounds__(64 * PQA_KIN_EB) void k_kinetic_lw(SysDev S,
           const double4 ta = *reinterpret_cast<const double4*>(Tq + (size_t)j * W), tb = *reinterpret_cast<const double4*>(Tq + (size_t)(j + 1) * W);
           double2 v[20];
 #pragma unroll
-          for (int c = PQA_KIN_C0; c < 5; ++c)
+          for (int c = 1; c < 5; ++c)
 #pragma unroll
             for (int t = 0; t < 4; ++t) v[c * 4 + t] = *reinterpret_cast<const double2*>(rq[t] + c * nmo + j);
           __builtin_amdgcn_sched_barrier(0);
           const double t0[4] = {ta.x, ta.y, ta.z, ta.w}, t1[4] = {tb.x, tb.y, tb.z, tb.w};
 #pragma unroll
-          for (int c = PQA_KIN_C0; c < 5; ++c)
+          for (int c = 1; c < 5; ++c)
 #pragma unroll
             for (int t = 0; t < 4; ++t) { p[t][c] += v[c * 4 + t].x * t0[t]; p[t][c] += v[c * 4 + t].y * t1[t]; }
           __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
-        for (int c = PQA_KIN_C0; c < 5; ++c) {
+        for (int c = 1; c < 5; ++c) {
           double mine = 0.0;
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
@@ -1422,43 +1320,8 @@ static __global__ __launch_bounds__(64 * PQA_KIN_EB) void k_kinetic_lw(SysDev S,
           }
           r[c] = mine;
         }
-        if (PQA_KIN_C0) r[0] = 1.0;
+        r[0] = 1.0;
       } else
-#endif
-#if PQA_KIN_V == 4
-      // component-major, a whole component (n doubles = n / 8 lines of the lane's own row) requested before the previous component's products:
-      // 256 bytes per lane in flight all the time (the compiler's own schedule of V == 1 waits for every line before it asks for the next:
-      // one 64-byte line per lane in flight, 3.7 TB/s)
-      if (n <= 32) {
-        double t[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) t[u] = (u < n) ? Ti[(size_t)u * W] : 0.0;
-        // half a component (16 slots = 128 bytes) per buffer: request the next half, then use the previous one
-        double4 A[4], B[4];
-#define PQA_KIN_SB __builtin_amdgcn_sched_barrier(0);
-#define PQA_KIN_LOAD(BUF, H) _Pragma("unroll") for (int k = 0; k < 4; ++k) BUF[k] = *reinterpret_cast<const double4*>(row + ((H) >> 1) * nmo + ((((H) & 1) * 16 + 4 * k) < n ? ((H) & 1) * 16 + 4 * k : 0));  /* (slots >= n: t = 0) */
-#define PQA_KIN_DOT(BUF, H)                                                                                       \
-  _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                                                 \
-    const int j_ = ((H) & 1) * 16 + 4 * k;                                                                        \
-    r[(H) >> 1] += BUF[k].x * t[j_]; r[(H) >> 1] += BUF[k].y * t[j_ + 1]; r[(H) >> 1] += BUF[k].z * t[j_ + 2]; r[(H) >> 1] += BUF[k].w * t[j_ + 3]; \
-  }
-        PQA_KIN_LOAD(A, 0)
-        PQA_KIN_LOAD(B, 1)
-        PQA_KIN_SB PQA_KIN_DOT(A, 0) PQA_KIN_SB PQA_KIN_LOAD(A, 2)
-        PQA_KIN_SB PQA_KIN_DOT(B, 1) PQA_KIN_SB PQA_KIN_LOAD(B, 3)
-        PQA_KIN_SB PQA_KIN_DOT(A, 2) PQA_KIN_SB PQA_KIN_LOAD(A, 4)
-        PQA_KIN_SB PQA_KIN_DOT(B, 3) PQA_KIN_SB PQA_KIN_LOAD(B, 5)
-        PQA_KIN_SB PQA_KIN_DOT(A, 4) PQA_KIN_SB PQA_KIN_LOAD(A, 6)
-        PQA_KIN_SB PQA_KIN_DOT(B, 5) PQA_KIN_SB PQA_KIN_LOAD(B, 7)
-        PQA_KIN_SB PQA_KIN_DOT(A, 6) PQA_KIN_SB PQA_KIN_LOAD(A, 8)
-        PQA_KIN_SB PQA_KIN_DOT(B, 7) PQA_KIN_SB PQA_KIN_LOAD(B, 9)
-        PQA_KIN_SB PQA_KIN_DOT(A, 8)
-        PQA_KIN_DOT(B, 9)
-#undef PQA_KIN_LOAD
-#undef PQA_KIN_DOT
-#undef PQA_KIN_SB
-      } else
-#elif PQA_KIN_V == 1 || PQA_KIN_V == 3  // component-major: the lane streams its row front to back (adjacent lines back to back), inverse row in registers
       if (n <= 32) {
         double t[32];
 #pragma unroll
@@ -1473,20 +1336,6 @@ static __global__ __launch_bounds__(64 * PQA_KIN_EB) void k_kinetic_lw(SysDev S,
               r[c] += hi.x * t[j + 4]; r[c] += hi.y * t[j + 5]; r[c] += hi.z * t[j + 6]; r[c] += hi.w * t[j + 7];
             }
       } else
-#elif PQA_KIN_V == 2  // component-major, the inverse row re-read per component (coalesced, cache hits)
-      if (true) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c)
-          for (int j = 0; j < n; j += 8) {
-            double t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = Ti[(size_t)(j + u) * W];
-            const double4 lo = *reinterpret_cast<const double4*>(row + c * nmo + j), hi = *reinterpret_cast<const double4*>(row + c * nmo + j + 4);
-            r[c] += lo.x * t[0]; r[c] += lo.y * t[1]; r[c] += lo.z * t[2]; r[c] += lo.w * t[3];
-            r[c] += hi.x * t[4]; r[c] += hi.y * t[5]; r[c] += hi.z * t[6]; r[c] += hi.w * t[7];
-          }
-      } else
-#endif
       for (int j = 0; j < n; j += 8) {
         double t[8];
 #pragma unroll

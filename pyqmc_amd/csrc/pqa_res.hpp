@@ -239,9 +239,6 @@ __device__ __forceinline__ void res_jas_part(const SysDev& S, int e, int r, doub
 // at a harmless distance and discarded by a select), so the compiler interleaves the eight pairs res_jas_dual_m evaluates.
 // K <= 4 Pade functions through the KD = 4 polynomials (records and denominators are zero padded); a basis without cusp function
 // passes cusp parameter and coefficient 0.
-#ifndef PQA_RES_JCHAIN
-#define PQA_RES_JCHAIN 2
-#endif
 // Minimal image of a Jastrow pair from the block's LDS copy of the cell: where every Jastrow cut-off is at most the inradius of the
 // cell-centred parallelepiped (PbcDev::jas_fold, flag at pbt[29]) the fold IS the minimal image inside the cut-off (min_image_j);
 // otherwise the general reduction on the global tables.
@@ -301,9 +298,7 @@ __device__ __forceinline__ void res_jas_m(const SysDev& S, int r, const double (
                         jt + (se + q) * PQA_JQ, bcp, bca, jt[3 * PQA_JQ + 10 + se + q], j);
     }
   }
-#if PQA_RES_JCHAIN < 3
   __builtin_amdgcn_sched_barrier(0);  // (three pairs interleaved need more registers than the kernel has to spare)
-#endif
   {
     double Da[5];
 #pragma unroll
@@ -397,27 +392,13 @@ __device__ __forceinline__ void res_image_masks(const double* __restrict__ pbt, 
   if (outside) { m0 = 0ull; m1 = 0ull; }
 }
 
-#ifdef PQA_RES_CLK  // timing build only: 100 MHz stamps of thread 0 of the first blocks, last move of the sweep
-static __device__ unsigned long long pqa_res_clk[64 * 16];
-static __device__ unsigned long long pqa_res_clk3[64 * 8];
-static __device__ unsigned long long pqa_res_clk2[64 * 16];  // thread 0's AO phase: cycles in [0] list header + zeroing, [1] fold, [2] walk + evaluation, [3] shells, [4] images evaluated
-#define PQA_RCLK2(k, v) do { if (blockIdx.x < 64 && threadIdx.x == 0) pqa_res_clk2[blockIdx.x * 16 + (k)] = (v); } while (0)
-#define PQA_RCLK(k) do { if (blockIdx.x < 64 && threadIdx.x == 0) pqa_res_clk[blockIdx.x * 16 + (k)] = wall_clock64(); } while (0)
-#else
-#define PQA_RCLK(k) do { } while (0)
-#define PQA_RCLK2(k, v) do { } while (0)
-#endif
-
 // grid = ceil((w_hi - w_lo) / 16) blocks of 512 threads; dynamic LDS = RT.region doubles + res_lds_fixed(...).
 // mb.gauss [N][W][3] and mb.unif [N][W] must be set (the caller draws them ahead from the Philox streams when there is no tape).
 // Register budget: 256 per thread (two waves per SIMD).  What is carried across the orbital phase is the inverse row (64), the
 // two coordinates (12) and a few indices; everything a proposal hands to its decision waits in LDS (wsc), the accumulators live
 // only across the MFMA loop, and the loads a decision / the next proposal need are issued after the AO phase.
-#ifndef PQA_RES_LB
-#define PQA_RES_LB PQA_RES_NT
-#endif
 template <bool DMC, int LMAX, bool PBC = false, bool CX = false>
-static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwState L, MoveBuf mb, ChunkTab T, ResTab RT, int has_jastrow,
+static __global__ __launch_bounds__(PQA_RES_NT) void k_sweep_res(SysDev S, LwState L, MoveBuf mb, ChunkTab T, ResTab RT, int has_jastrow,
                                                                   long W, long w_lo, long w_hi) {
   extern __shared__ double lds[];
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // (wave-uniform: scalar)
@@ -604,7 +585,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
       };
       if (i < 0) prefetch();
       if (i >= 0) {
-        PQA_RCLK(0);
         res_block_sync();  // proposals of all 16 walkers are in wsc; the previous move's reads of the region are done
         // ================= orbital rows at the 16 proposals
         // (opaque copies: the addresses of the unrolled contraction below depend on them, so the compiler cannot hoist the ~100
@@ -626,9 +606,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
             // K padding they land on still contract to zero) and every thread writes its entries at its own offsets — class by class, inside a
             // class slice by slice.  One thread per pair was 11 of the move's 50 us in the 8-atom cell (8 of 32 lane groups busy).
             unsigned long long* pcnt = reinterpret_cast<unsigned long long*>(region);  // [natom][16][NS], 8-bit fields
-#ifdef PQA_RES_CLK
-            const unsigned long long tA = clock64(); unsigned long long tB = tA, tC = tA, tD = tA, tE = tA;
-#endif
             const int a = grp % S.natom, q = grp / S.natom;
             const bool on = q < NS;
             unsigned long long k0 = 0ull, k1 = 0ull;
@@ -644,9 +621,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
               unsigned long long m0 = 0ull, m1 = 0ull;
               const int ncl = at_int[3 * a + 1];
               res_image_masks(pbt, pbi, c, a, at_int[3 * a], at_int[3 * a + 2], m0, m1);
-#ifdef PQA_RES_CLK
-              asm volatile("" : "+v"(m0), "+v"(m1)); tB = clock64();
-#endif
               double cut_r[PQA_RES_NCUT];
 #pragma unroll
               for (int k = 0; k < PQA_RES_NCUT; ++k) cut_r[k] = at_cut[a * (1 + PQA_RES_NCUT) + 1 + k];
@@ -674,13 +648,7 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
               }
               pcnt[((size_t)a * 16 + pl) * NS + q] = cnt;
             }
-#ifdef PQA_RES_CLK
-            tC = clock64();
-#endif
             res_block_sync();
-#ifdef PQA_RES_CLK
-            tD = clock64();
-#endif
             if (on) {
               const unsigned long long* pc = pcnt + ((size_t)a * 16 + pl) * NS;
               int n = 0;
@@ -731,10 +699,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
               }
               if (q == 0) imgn[a * 16 + pl] = (unsigned char)n;
             }
-#ifdef PQA_RES_CLK
-            tE = clock64();
-            PQA_RCLK2(5, tB - tA); PQA_RCLK2(6, tC - tB); PQA_RCLK2(7, tD - tC); PQA_RCLK2(8, tE - tD);
-#endif
           } else
           for (int a = grp; a < S.natom; a += 32) {
             const ResPair c = res_pair_base(pbt, pbi, a, ppx, ppy, ppz, at_xyz[3 * a], at_xyz[3 * a + 1], at_xyz[3 * a + 2]);
@@ -803,10 +767,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
             imgn[a * 16 + pl] = (unsigned char)n;
           }
           res_block_sync();
-          PQA_RCLK(14);
-#ifdef PQA_RES_CLK
-          if (blockIdx.x < 64 && threadIdx.x == 0) { int c255 = 0, tot = 0; for (int q = 0; q < S.natom * 16; ++q) { c255 += imgn[q] == 255; tot += imgn[q] == 255 ? 0 : imgn[q]; } pqa_res_clk[blockIdx.x * 16 + 15] = ((unsigned long long)c255 << 32) | (unsigned)tot; }
-#endif
         }
         for (int ps = 0; ps < RT.npass; ++ps) {
           const int row_base = RT.pass_row0[ps], nks = (RT.pass_row0[ps + 1] - row_base) >> 2;
@@ -814,14 +774,7 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
           {
             const int po1 = (PBC && CX && RT.twist) ? 16 : 0;
             const double px = wsc[pl * PQA_RES_WS + po1], py = wsc[pl * PQA_RES_WS + po1 + 1], pz = wsc[pl * PQA_RES_WS + po1 + 2];
-#ifndef PQA_RES_ABL_NOAO
-#ifdef PQA_RES_CLK
-            unsigned long long c_a = 0, c_b = 0, c_c = 0, n_sh = 0, n_im = 0;
-#endif
             for (int it = goff[ps * 32 + grp]; it < goff[ps * 32 + grp + 1]; ++it) {
-#ifdef PQA_RES_CLK
-              const unsigned long long t_0 = clock64();
-#endif
               const int sh = glist[it];
               const int l_ = sh_meta[5 * sh], np_ = sh_meta[5 * sh + 1], q0 = sh_meta[5 * sh + 2], krow = sh_meta[5 * sh + 3] - row_base;
               if (PBC) {
@@ -876,15 +829,9 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
                                                 }
                                               });
                   };
-#ifdef PQA_RES_CLK
-                  const unsigned long long t_1 = clock64();
-#endif
                   double x0, y0, z0, f0_, f1_, f2_;
                   res_fold(pbt, px - at_xyz[3 * a_], py - at_xyz[3 * a_ + 1], pz - at_xyz[3 * a_ + 2], x0, y0, z0, f0_, f1_, f2_);
                   const double scut = sh_cut[sh];
-#ifdef PQA_RES_CLK
-                  const unsigned long long t_2 = clock64();
-#endif
                   const unsigned char* lst = imgl + ((size_t)a_ * 16 + pl) * RT.icap;
                   if (nim == 254) {  // (rare: same images in index order, found again from the masks)
                     const ResPair c2 = res_pair_base(pbt, pbi, a_, px, py, pz, at_xyz[3 * a_], at_xyz[3 * a_ + 1], at_xyz[3 * a_ + 2]);
@@ -909,13 +856,7 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
                     const double xj = x0 - LsL[3 * j], yj = y0 - LsL[3 * j + 1], zj = z0 - LsL[3 * j + 2];
                     if (xj * xj + yj * yj + zj * zj > scut) break;  // (class-ordered list: nothing further is inside this shell's cut-off)
                     add_image(xj, yj, zj, j);
-#ifdef PQA_RES_CLK
-                    ++n_im;
-#endif
                   }
-#ifdef PQA_RES_CLK
-                  { const unsigned long long t_3 = clock64(); c_a += t_1 - t_0; c_b += t_2 - t_1; c_c += t_3 - t_2; ++n_sh; }
-#endif
                   continue;
                 }
               } else
@@ -926,11 +867,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
                                     tl[(size_t)4 * KT * 16] = lp;
                                   });
             }
-#endif
-#ifdef PQA_RES_CLK
-            if (PBC) { PQA_RCLK2(0, c_a); PQA_RCLK2(1, c_b); PQA_RCLK2(2, c_c); PQA_RCLK2(3, n_sh); PQA_RCLK2(4, n_im); }
-            if (PBC && blockIdx.x < 64 && (threadIdx.x & 63) == 0) pqa_res_clk3[blockIdx.x * 8 + (threadIdx.x >> 6)] = c_a + c_b + c_c;  // per wave: its phase 1
-#endif
           }
           // B operand of this wave's k-steps (L2-resident coefficient rows): a ring of four, the first three requested behind the AO
           // phase — in flight while the waves meet at the barrier — and k-step q + 3 while k-step q is contracted (all of them at
@@ -940,12 +876,10 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
 #pragma unroll
           for (int q = 0; q < 3; ++q) bq[q] = (kwv + q * KW < nks) ? cb[(size_t)(kwv + q * KW) * 4 * ldc] : 0.0;
           bq[3] = 0.0;
-          PQA_RCLK(1);
           res_block_sync();
           d4 acc[5];
 #pragma unroll
           for (int c = 0; c < 5; ++c) acc[c] = (d4){0.0, 0.0, 0.0, 0.0};
-#ifndef PQA_RES_ABL_NOMFMA
           {
             const double* a_ = region + (size_t)kq * 16 + i16;
 #pragma unroll 1
@@ -966,9 +900,7 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
               }
             }
           }
-#endif
           if (ps == RT.npass - 1) prefetch();
-          PQA_RCLK(2);
           // K-partials of this wave: lane holds D[point = kq + 4 rr][orbital = 16 u + i16].  One pass: they take the tile's place
           // (every wave has to be done reading it); several passes: own memory behind the tile, accumulated pass by pass by the
           // same lane
@@ -989,14 +921,12 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
           }
         }
         res_block_sync();
-        PQA_RCLK(3);
         // ---- this walker's rows: the KW partials added in a fixed order (thread r: orbital r, five components)
         if (r < 16 * nt) {
           if (KW == 4) res_combine<4>(part + (size_t)wl * PS + r, PS, 16 * nt, rn + r);
           else res_combine<8>(part + (size_t)wl * PS + r, PS, 16 * nt, rn + r);
         }
         res_wave_sync();
-        PQA_RCLK(7);
         // Slater sums at the proposal: ratio and gradient rows against T[i] (zero beyond n)
         if (CX) {
           if (RT.twist) {  // wrap phase of the folded proposal (orbitals.py:203-213; k_row_phase): every orbital row times exp(i theta)
@@ -1023,7 +953,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
         p0 = rn[oc] * te; p1 = rn[32 + oc] * te; p2 = rn[64 + oc] * te; p3 = rn[96 + oc] * te;
         p0 = res_sum32(p0); p1 = res_sum32(p1); p2 = res_sum32(p2); p3 = res_sum32(p3);
         }
-        PQA_RCLK(8);
       }
       const bool have_dec = i >= 0, have_prop = i + 1 < n;
       bool accd = false;
@@ -1038,7 +967,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
         } else { hx = finite_or(p1 / p0, 0.0); hy = finite_or(p2 / p0, 0.0); hz = finite_or(p3 / p0, 0.0); }
         const double val = finite_or(dr, 1.0);
         double val2 = CX ? finite_or(m2, 1.0) : val * val;
-#ifndef PQA_RES_ABL_NOJAS
         if (has_jastrow) {
           ResJ jn{0.0, 0.0, 0.0, 0.0};
           if (S.jq_on) res_jas_m<PBC>(S, r, cx, cy, cz, at_xyz, acoef, aql, jt, e, npx, npy, npz, jn, pbt);
@@ -1052,8 +980,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
           const double ej = exp(jn.u - ws[9]);
           val2 *= ej * ej;
         }
-#endif
-        PQA_RCLK(9);
         {
           const double z0 = ws[3], z1 = ws[4], z2 = ws[5], d0 = ws[6], d1 = ws[7], d2 = ws[8];
           const double fwd = z0 * z0 + z1 * z1 + z2 * z2;
@@ -1076,12 +1002,10 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
           }
         }
         if (live && r == 0 && mb.accept_rec) mb.accept_rec[(size_t)e * W + wg] = accd;
-        PQA_RCLK(4);
         if (accd) {
           // Sherman-Morrison on the register rows (slater.py:88-94): R = T_old[i] / ratio, T[j] -= R (V . T[j]), T[i] = R;
           // the row's dot product in the PQA_ROWDOT order of the lane-per-walker kernels.  Eight columns at a time (the
           // scheduling fences keep the compiler from requesting all 64 LDS operands at once)
-#ifndef PQA_RES_ABL_NOSM
           if (CX) {
             // complex rows: 16 (re, im) columns; the row's dot product V . T[r] in the PQA_ROWDOT order of the complex lane-per-walker
             // kernels (quarters of the complex columns), R = T_old[i] / ratio
@@ -1143,8 +1067,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
             __builtin_amdgcn_sched_barrier(0);
           }
           }
-#endif
-          PQA_RCLK(13);
           // sign and log of the determinant (per walker, in LDS; lane 0): the ratios' magnitudes as a running product, its
           // logarithm taken when it leaves [1e-60, 1e60] and at the end of the spin's sweep (log of a product = sum of logs to
           // rounding; one log per move was ~1 us)
@@ -1178,7 +1100,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
             if (live) sels[(size_t)i * W + wg] = (uint8_t)selr;
           }
         }
-        PQA_RCLK(5);
       }
       // ================= propose electron i + 1 (mc.py:117-121): drift at its current position
       if (have_prop) {
@@ -1189,7 +1110,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
           for (int k = 0; k < 32; ++k) rowE[wl * 32 + k] = t[k];
         }
         res_wave_sync();
-        PQA_RCLK(10);
         double gx, gy, gz;
         if (CX) {
           const double tr = r < n ? rowE[wl * 32 + 2 * r] : 0.0, ti = r < n ? rowE[wl * 32 + 2 * r + 1] : 0.0;
@@ -1208,8 +1128,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
         const int src = (lane & 32) | ip;
         const double pox = __shfl(s ? cx[1] : cx[0], src, 64), poy = __shfl(s ? cy[1] : cy[0], src, 64), poz = __shfl(s ? cz[1] : cz[0], src, 64);
         double U0 = 0.0;
-        PQA_RCLK(11);
-#ifndef PQA_RES_ABL_NOJAS
         if (has_jastrow) {
           ResJ jo{0.0, 0.0, 0.0, 0.0};
           if (S.jq_on) res_jas_m<PBC>(S, r, cx, cy, cz, at_xyz, acoef, aql, jt, ep, pox, poy, poz, jo, pbt);
@@ -1221,8 +1139,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
           jo.u = res_sum32(jo.u); jo.x = res_sum32(jo.x); jo.y = res_sum32(jo.y); jo.z = res_sum32(jo.z);
           U0 = jo.u; gx += jo.x; gy += jo.y; gz += jo.z;
         }
-#endif
-        PQA_RCLK(12);
         if (DMC) limdrift_dmc(gx, gy, gz, mb.tstep); else limdrift3(gx, gy, gz);
         const double sq = jt[3 * PQA_JQ + 15], df = DMC ? 1.0 : mb.tstep;
         const double z0 = g0 * sq, z1 = g1 * sq, z2 = g2 * sq;
@@ -1254,7 +1170,6 @@ static __global__ __launch_bounds__(PQA_RES_LB) void k_sweep_res(SysDev S, LwSta
           ws[3] = z0; ws[4] = z1; ws[5] = z2; ws[6] = gx; ws[7] = gy; ws[8] = gz; ws[9] = U0;
         }
         res_wave_sync();
-        PQA_RCLK(6);
       }
     }
     // ---- this spin's state back to the planes

@@ -190,7 +190,7 @@ int sweep_r8(pqa_handle* h, const MoveBuf& mb) {
   return check_launch(h, "k_sweep_r8");
 }
 
-#ifdef PQA_RES_CLK  // timing build only (tools/scratch/res_clk.py --r8)
+#ifdef PQA_RES_CLK  // timing build only (tools/scratch/res_clk.py)
 extern "C" int pqa_debug_r8_clk(unsigned long long* dst, int n) {
   return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(pqa_res_clk), (size_t)n * sizeof(unsigned long long));
 }

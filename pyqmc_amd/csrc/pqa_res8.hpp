@@ -162,20 +162,22 @@ __device__ __forceinline__ void r8_combine(const double* __restrict__ pb, int PS
   }
 }
 
-#ifndef PQA_R8_UNIT0
-#define PQA_R8_UNIT0 1  // the value sum at an electron's own position taken as 1 (see the next-proposal drift below)
-#endif
 // grid = ceil((w_hi - w_lo) / 8) blocks of 256 threads, two per CU (256 registers per thread, dynamic LDS <= 80 KB).
+#ifdef PQA_RES_CLK  // timing build only (tools/scratch/res_clk.py): 100 MHz stamps of thread 0 of the first blocks
+static __device__ unsigned long long pqa_res_clk[64 * 16];
+static __device__ unsigned long long pqa_res_clk2[64 * 16];
+#define PQA_RCLK2(k, v) do { if (blockIdx.x < 64 && threadIdx.x == 0) pqa_res_clk2[blockIdx.x * 16 + (k)] = (v); } while (0)
+#define PQA_RCLK(k) do { if (blockIdx.x < 64 && threadIdx.x == 0) pqa_res_clk[blockIdx.x * 16 + (k)] = wall_clock64(); } while (0)
+#else
+#define PQA_RCLK(k) do { } while (0)
+#define PQA_RCLK2(k, v) do { } while (0)
+#endif
 // timing builds: the phase stamps of a move in the MIDDLE of the second spin's sweep (the last move has no next electron: half the Jastrow
 // work, no prefetch)
 #define PQA_R8CLK(k) do { if (s == 1 && i == 16) PQA_RCLK(k); } while (0)
 // (timing builds) wall-clock stamps of a block's prologue / epilogue: 0 tables in LDS, 1 + 4 s: spin s rows loaded, 2 + 4 s: its moves done,
 // 3 + 4 s: its state stored, 4 + 4 s: past the spin's closing barrier
-#ifdef PQA_RES_CLK
 #define PQA_R8T(k) PQA_RCLK2(k, wall_clock64())
-#else
-#define PQA_R8T(k) do { } while (0)
-#endif
 template <bool DMC, int LMAX>
 static __global__ __launch_bounds__(PQA_R8_NT, 2) void k_sweep_r8(SysDev S, LwState L, MoveBuf mb, ChunkTab T, R8Tab RT, int has_jastrow,
                                                                   long W, long w_lo, long w_hi) {
@@ -312,7 +314,7 @@ static __global__ __launch_bounds__(PQA_R8_NT, 2) void k_sweep_r8(SysDev S, LwSt
         if (i + 1 < n) {
           const int slot = __shfl(selr, (lane & 32) | (i + 1), 64);
           const double* row = rcs + (((size_t)(i + 1) * 2 + slot) * W + wg) * 5 * nmo;
-          if (r < n) { if (!PQA_R8_UNIT0) ro[0] = row[oc]; ro[1] = row[nmo + oc]; ro[2] = row[2 * nmo + oc]; ro[3] = row[3 * nmo + oc]; }
+          if (r < n) { ro[1] = row[nmo + oc]; ro[2] = row[2 * nmo + oc]; ro[3] = row[3 * nmo + oc]; }
           const double* zt = mb.gauss + ((size_t)(e + 1) * W + wg) * 3;
           g0 = zt[0]; g1 = zt[1]; g2 = zt[2];
         }
@@ -588,17 +590,10 @@ static __global__ __launch_bounds__(PQA_R8_NT, 2) void k_sweep_r8(SysDev S, LwSt
           const double te = rowE[wl * 32 + r];
           double q1 = ro[1] * te, q2 = ro[2] * te, q3 = ro[3] * te;
           q1 = res_sum32(q1); q2 = res_sum32(q2); q3 = res_sum32(q3);
-          if (PQA_R8_UNIT0) {
-            // The reference divides the gradient sums by the value sum (slater.py gradient: ratios[1:] / ratios[0]), which at the electron's own
-            // position is row e of the Slater matrix times column e of its inverse: 1 up to the rounding of the inverse.  Taken as 1: one load,
-            // one 32-lane sum and a division less per move (-DPQA_R8_UNIT0=0 restores them; the drift changes by that rounding, ~1e-13 relative).
-            gx = finite_or(q1, 0.0); gy = finite_or(q2, 0.0); gz = finite_or(q3, 0.0);
-          } else {
-            double q0 = ro[0] * te;
-            q0 = res_sum32(q0);
-            const double iq0 = 1.0 / q0;
-            gx = finite_or(q1 * iq0, 0.0); gy = finite_or(q2 * iq0, 0.0); gz = finite_or(q3 * iq0, 0.0);
-          }
+          // The reference divides the gradient sums by the value sum (slater.py gradient: ratios[1:] / ratios[0]), which at the electron's own
+          // position is row e of the Slater matrix times column e of its inverse: 1 up to the rounding of the inverse.  Taken as 1: one load,
+          // one 32-lane sum and a division less per move (the drift changes by that rounding, ~1e-13 relative).
+          gx = finite_or(q1, 0.0); gy = finite_or(q2, 0.0); gz = finite_or(q3, 0.0);
         }
         const int src = (lane & 32) | ip;
         const double pox = __shfl(s ? cx[1] : cx[0], src, 64), poy = __shfl(s ? cy[1] : cy[0], src, 64), poz = __shfl(s ? cz[1] : cz[0], src, 64);

@@ -36,9 +36,3 @@ int sweep_ww(pqa_handle* h, const MoveBuf& mb) {
 #undef PQA_WW_LAUNCH
   return check_launch(h, "k_sweep_ww");
 }
-
-#ifdef PQA_WW_CLK  // timing build only
-extern "C" int pqa_debug_ww1_clk(unsigned long long* dst, int n) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(pqa_ww1_clk), (size_t)n * sizeof(unsigned long long));
-}
-#endif

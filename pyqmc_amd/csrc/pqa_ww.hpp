@@ -3,7 +3,7 @@
 // Wave functions outside the lane-per-walker kernels' scope (multi-determinant expansions, three-body Jastrow factors) move an electron
 // with k_propose -> orbital kernel -> k_accept (pqa_vmc.hpp): three launches per move, each a single wave per walker running one dependent
 // chain after the other — for the 50-determinant water molecule of BASELINE config C4 (2 048 walkers, 8 electrons) 21 + 6 + 27 us per move
-// of which the chains are 14 and 22 (tools/scratch/ww_clk.py: Slater terms 4.6, two-body Jastrow 3.4, three-body 5.9; at the proposal 4.1,
+// of which the chains are 14 and 22 (phase stamps of a timing build: Slater terms 4.6, two-body Jastrow 3.4, three-body 5.9; at the proposal 4.1,
 // 9.3 + decision, commit 7.6).  Here a block owns the walker for the whole sweep:
 //   phase A  Slater drift at the current position (cached orbital row), one/two-body Jastrow, three-body Jastrow
 //   phase B  the proposal (mc.py:117-121, dmc.py:46-52)
@@ -21,12 +21,6 @@
 #include "pqa_ao.hpp"
 #include "pqa_vmc.hpp"
 
-#ifdef PQA_WW_CLK  // timing build only (tools/scratch/ww1_clk.py): 100 MHz stamps of lane 0 of each wave of the first 256 blocks, last move
-static __device__ unsigned long long pqa_ww1_clk[256 * 3 * 8];
-#define PQA_W1CLK(k) do { if (blockIdx.x < 256 && (threadIdx.x & 63) == 0) pqa_ww1_clk[(blockIdx.x * 3 + (threadIdx.x >> 6)) * 8 + (k)] = wall_clock64(); } while (0)
-#else
-#define PQA_W1CLK(k) do { } while (0)
-#endif
 #define PQA_WW_XCH 32  // doubles of the exchange area in front of the orbital row
 
 // Orbital row [5][nmo] of spin s at one point by one wave.  aov: [5][nao] LDS scratch.
@@ -95,12 +89,11 @@ static __global__ __launch_bounds__(64, 2) void k_sweep_ww(SysDev S, SlaterState
 #pragma unroll 1
     for (int ph = 0; ph < 2; ++ph) {  // phase A (current position), phase C (proposal): the three parts one after the other
       double* xo = xch + 16 * ph;
-      PQA_W1CLK(ph ? 3 : 0);
       {
         double gx = 0.0, gy = 0.0, gz = 0.0, v2 = 1.0, sgn = 1.0;
         if (has_slater) {
           const double* r_ = st.cache[s] + ((size_t)w * n + i) * 5 * nmo;
-          if (ph) { ww_orb_point<LMAX>(S, s, nx, ny, nz, aov, row, cstage ? cl + (s ? S.nao * S.nmo[0] : 0) : S.mo[s]); r_ = row; PQA_W1CLK(7); }
+          if (ph) { ww_orb_point<LMAX>(S, s, nx, ny, nz, aov, row, cstage ? cl + (s ? S.nao * S.nmo[0] : 0) : S.mo[s]); r_ = row; }
           slater_move_terms<false>(S, st, s, i, w, r_, lds, gx, gy, gz, v2, &sgn);
         }
         if (lane == 0) {
@@ -127,9 +120,7 @@ static __global__ __launch_bounds__(64, 2) void k_sweep_ww(SysDev S, SlaterState
         if (has_j3) jas_eval<1, false>(S, xw, e, nx, ny, nz, U, g, lp, 2, lds + S.j3_off);
         if (lane == 0) { xo[9] = U; xo[10] = g[0]; xo[11] = g[1]; xo[12] = g[2]; }
       }
-      PQA_W1CLK(ph ? 4 : 1);
       __syncthreads();
-      PQA_W1CLK(ph ? 5 : 2);
       if (ph == 0) {
         // ---- phase B: the proposal (every thread; k_propose's arithmetic: the three-body terms join the two-body ones, the sum the Slater part)
         double j0 = xch[6], j1 = xch[7], j2 = xch[8];
@@ -193,7 +184,6 @@ static __global__ __launch_bounds__(64, 2) void k_sweep_ww(SysDev S, SlaterState
       }
       if (tid == 0) { xg[3 * e] = nx; xg[3 * e + 1] = ny; xg[3 * e + 2] = nz; }
     }
-    PQA_W1CLK(6);
     __syncthreads();  // (the coordinate, the inverses and the exchange area before the next electron)
   }
 }
