@@ -424,6 +424,17 @@ int pqa_philox_dmc_tapes(pqa_handle_t* h, uint64_t seed, int nsteps, int64_t W, 
    (pyqmc_amd.S2Accumulator). */
 int pqa_s2(pqa_handle_t* h, double* s2, double* ratios);
 
+/* ---- symmetry operators ------------------------------------------------------------------ */
+/* SymmetryAccumulator / SymmetryAccumulatorPBC.__call__ (pyqmc/observables/accumulators.py:237-283, :286-341): per operator o
+   and walker w the ratio Psi(S_o R)/Psi(R), where S_o R moves every electron to x' = (x - origin_o) @ S_o + origin_o (row
+   vectors: the reference's einsum("ijk,kl->ijl", x, S)) and, in a periodic cell, folds it back into the cell (enforce_pbc).
+   ops (nop,3,3) row-major; origins (nop,3), or NULL for the origin 0; ratio (nop, W).  Read-only on the resident state (after
+   the layout sync): inverses, determinants, Jastrow sums, coordinates and wrap stay as they were.  Fused scope: real handles
+   with a Slater factor (one or more determinants), with or without the two-body Jastrow, open or periodic at Gamma.  Complex /
+   twisted handles and handles with a three-body Jastrow factor are refused (<0): those go through the protocol route
+   (pyqmc_amd.SymmetryAccumulator). */
+int pqa_symmetry(pqa_handle_t* h, int nop, const double* ops, const double* origins, double* ratio);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* HIP-event timing on the handle's own stream (torch.cuda.Event only sees torch's stream). */
 int pqa_timer_start(pqa_handle_t* h);

@@ -16,6 +16,7 @@ from .vmc import vmc, vmc_worker  # noqa: F401
 from .wf import DeviceWF, JastrowSpin, MultiplyWF, Slater, ThreeBodyJastrow, generate_wf  # noqa: F401
 from . import obdm  # noqa: F401
 from .s2 import S2Accumulator  # noqa: F401
+from .symmetry import SymmetryAccumulator, SymmetryAccumulatorPBC  # noqa: F401
 from .accumulators import LinearTransform, PGradTransform, StochasticReconfiguration  # noqa: F401
 from .obdm import OBDMAccumulator  # noqa: F401
 from .tbdm import TBDMAccumulator  # noqa: F401

@@ -118,6 +118,10 @@ struct pqa_handle {
   long wrap_W = 0;
   DevBuf b_gauss, b_unif, b_kc, b_en, b_means, b_sign, b_log, b_ju;
   DevBuf b_s2phi[2], b_s2out;  // pqa_s2 (pqa_s2.hip): orbitals of each spin at the other spin's electrons (a walker chunk), outputs
+  // pqa_symmetry (pqa_symmetry.hip), per walker chunk: transformed coordinates, orbitals of each spin at its transformed electrons,
+  // determinant ratios (sign, log) of each spin; the ratios of every operator.  sym_attr: k_sym_det's dynamic-LDS limit raised (n > 90)
+  DevBuf b_symx, b_symphi[2], b_symdet[2], b_symout;
+  bool sym_attr = false;
   DevBuf b_tpos, b_twgt, b_tlive, b_trat;
   DevBuf b_tmcnt, b_tmoff, b_tmpass, b_tmamp, b_tmacc, b_tmidx, b_tmapos, b_tmu, b_tmtile, b_tmaoff, b_tmptw, b_tmmarks, b_dmcw, b_dmcold, b_dmcr2, b_dmcout;
   int tm_P = 0;
