@@ -10,6 +10,10 @@ EnergyAccumulator evaluation (mc.py:142-148), all device-resident (pqa_vmc_sweep
 Walkers shard across ranks with no data-path collective; the only exchange is the
 per-block all-reduce of the energy sums (RCCL), which is inside the timed region.
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, settling, warm-up, the timed steps, --dump-outputs and the result
+line (with the roofline objects priced from the timed steps' own launches).  --full adds what takes runs of its own: the
+sweep-only and walker-count grid (`extra`) and the CPU baseline (`cpu_baseline`, `speedup_vs_cpu_*`), both at N = 1.
 """
 
 import argparse
@@ -446,10 +450,12 @@ def main():
     ap.add_argument("--tstep", type=float, default=0.3)
     ap.add_argument("--settle", type=int, default=30, help="untimed settling steps before the warm-up steps (clock ramp of a fresh process)")
     ap.add_argument("--mode", default="vmc", choices=["vmc", "dmc", "c4"], help="vmc: the headline metric (default); dmc: config C5 with branching; c4: config C4 (multi-determinant VMC)")
-    ap.add_argument("--cpu-walkers", type=int, default=256, help="walkers per CPU-baseline process")
-    ap.add_argument("--cpu-procs", type=int, default=0, help="CPU-baseline processes (0 = physical cores of one socket)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the sweep-only and walker-count grid measurements (extra)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline also measure the sweep-only and walker-count grid (extra) and the "
+                    "CPU baseline (N = 1 only); a plain run skips both")
+    ap.add_argument("--cpu-walkers", type=int, default=256, help="walkers per CPU-baseline process (--full)")
+    ap.add_argument("--cpu-procs", type=int, default=0, help="CPU-baseline processes (--full; 0 = physical cores of one socket)")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the sweep-only and walker-count grid measurements (extra)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket the orbital kernel with HIP events")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for control-flow tests)")
     ap.add_argument("--same-gpu", action="store_true", help="TEST ONLY: all ranks use GPU 0 (needs --backend gloo)")
@@ -699,9 +705,9 @@ def main():
                                 "formula": "N (F_ao(5) + 2*5*M*n + 16 n + 2 F_j2 + acc*4 n^2) + N (10 n + 1.3 F_j2) + ecp_points (F_ao(1) + 2 M n + 2 n + F_j2/2); "
                                            "bytes: launches per step x calibrated counter bytes per launch (resident sweep: k_sweep_r8 1, k_tile_draws 1, k_orb<1> 2, kinetic, ECP passes; "
                                            "launch-per-move sweep: k_step_lw 77, k_flush_lw 14, k_orb 64 + 2, kinetic, ECP passes)"}
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             out["extra"] = extra_measurements(pa, wf, dev, mol, W, args)
-        if not args.no_cpu_baseline and world == 1:  # reported at N = 1 only (the other ranks would just wait)
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N = 1 only (the other ranks would just wait)
             out["cpu_baseline"] = cpu_baseline(args.cpu_walkers, args.tstep, max_procs=args.cpu_procs)
             out["speedup_vs_cpu_measured"] = value / out["cpu_baseline"]["value"]
             out["speedup_vs_cpu_socket_extrapolated"] = value / out["cpu_baseline"]["socket_extrapolated"]

@@ -430,6 +430,26 @@ def test_two_gpu_dmc_bench_over_rccl():
     assert note("two_gpu_dmc_state_vs_recompute", line["state_vs_recompute"]) <= 1e-9
 
 
+def test_plain_bench_line_leaves_the_full_measurements_out():
+    """A plain ``bench.py`` run prints the headline line with its roofline (priced from the timed launches) and nothing that
+    takes runs of its own: the sweep-only / walker-count grid and the CPU baseline come with ``--full`` only."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    cmd = [sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "1", "--walkers", "4096", "--steps", "2", "--warmup", "1", "--settle", "2"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=helpers.ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "roofline_step"):
+        assert k in line, k
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["config"]["walkers_per_gpu"] == 4096
+    assert abs(line["value"] - 4096 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-9
+    for k in ("extra", "cpu_baseline", "speedup_vs_cpu_measured", "speedup_vs_cpu_socket_extrapolated"):
+        assert k not in line, k
+
+
 def test_energy_statistics_against_the_oracle():
     """(Oracle-generated fixture g29: the expected mean and error bar come from the pinned CPU oracle, not from the reference itself.)
     north_star: "energies within 1 mHa statistical error of reference" — as a test that can fail.  Trial function: H2O with

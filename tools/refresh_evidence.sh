@@ -15,7 +15,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python $R/tools/pmc_summary.py /tmp/pm_FETCH_SIZE/t_results.db /tmp/pm_WRITE_SIZE/t_results.db /tmp/pc_FETCH_SIZE/t_results.db /tmp/pc_WRITE_SIZE/t_results.db $W $O/pmc_summary.json > $O/pmc_summary.txt 2>&1
 cp $O/pmc_summary.json $R/profiles/r06_pmc_summary.json  # (this box's copy: bench.py reads its `traffic` fields from it)
-python $R/bench.py --walkers $W > $O/bench.json 2> $O/bench.err < /dev/null
+python $R/bench.py --walkers $W --full > $O/bench.json 2> $O/bench.err < /dev/null
 python $R/bench.py --mode dmc --steps 20 --warmup 2 > $O/bench_dmc.json 2>> $O/bench.err < /dev/null
 python $R/bench.py --mode c4 --steps 20 --warmup 2 > $O/bench_c4.json 2>> $O/bench.err < /dev/null
 rocprofv3 --kernel-trace --stats -d /tmp/pb -o b -- python $R/bench.py --walkers $W --steps 10 --warmup 2 --no-cpu-baseline --no-extra > /dev/null 2>&1 < /dev/null
