@@ -435,6 +435,18 @@ int pqa_s2(pqa_handle_t* h, double* s2, double* ratios);
    (pyqmc_amd.SymmetryAccumulator). */
 int pqa_symmetry(pqa_handle_t* h, int nop, const double* ops, const double* origins, double* ratio);
 
+/* ---- structure factor --------------------------------------------------------------- */
+/* SqAccumulator (pyqmc/observables/accumulators.py:191-234): per walker w and wave vector q
+     sq[w][q]     = |sum_j       exp(i q.r_j)|^2 / N,
+     spinsq[w][q] = |sum_j s_j * exp(i q.r_j)|^2 / N      (s_j = +1 for the nelec_up first electrons, -1 for the rest),
+   periodic points folded into the cell first (twisted handles keep unfolded coordinates).  nqv vectors q (nqv,3) Cartesian.
+   With qn (nqv,3) and recip (3x3, rows b_a): q = sum_a qn[.][a] b_a, and every phase comes from a power recurrence of the three
+   base phases exp(i b_a.r) (the q grids of SqAccumulator); with qn = NULL (recip ignored) one sincos per (q, electron).  The
+   caller asserts that q and qn @ recip agree.  mean = 0: sq, spinsq (W, nqv); mean = 1: walker means (nqv), reduced on the
+   device in a fixed order (no atomics: two calls give the same bits).  Every handle kind; read-only on the resident state
+   (coordinates are read in place from whichever layout holds them: no layout sync, no change to anything a sweep reads). */
+int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, const double* recip, int mean, double* sq, double* spinsq);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* HIP-event timing on the handle's own stream (torch.cuda.Event only sees torch's stream). */
 int pqa_timer_start(pqa_handle_t* h);

@@ -17,6 +17,7 @@ from .wf import DeviceWF, JastrowSpin, MultiplyWF, Slater, ThreeBodyJastrow, gen
 from . import obdm  # noqa: F401
 from .s2 import S2Accumulator  # noqa: F401
 from .symmetry import SymmetryAccumulator, SymmetryAccumulatorPBC  # noqa: F401
+from .sq import SqAccumulator  # noqa: F401
 from .accumulators import LinearTransform, PGradTransform, StochasticReconfiguration  # noqa: F401
 from .obdm import OBDMAccumulator  # noqa: F401
 from .tbdm import TBDMAccumulator  # noqa: F401

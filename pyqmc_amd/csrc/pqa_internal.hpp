@@ -122,6 +122,10 @@ struct pqa_handle {
   // determinant ratios (sign, log) of each spin; the ratios of every operator.  sym_attr: k_sym_det's dynamic-LDS limit raised (n > 90)
   DevBuf b_symx, b_symphi[2], b_symdet[2], b_symout;
   bool sym_attr = false;
+  // pqa_sq (pqa_sq.hip): q vectors and their integer coordinates, per-walker values of a walker chunk, the mean mode's row partials and
+  // running sums.  sq_attr: k_sq<true>'s dynamic-LDS limit raised (phase tables above 64 KiB per walker)
+  DevBuf b_sqq, b_sqout, b_sqpart, b_sqacc;
+  bool sq_attr = false;
   DevBuf b_tpos, b_twgt, b_tlive, b_trat;
   DevBuf b_tmcnt, b_tmoff, b_tmpass, b_tmamp, b_tmacc, b_tmidx, b_tmapos, b_tmu, b_tmtile, b_tmaoff, b_tmptw, b_tmmarks, b_dmcw, b_dmcold, b_dmcr2, b_dmcout;
   int tm_P = 0;

@@ -35,6 +35,19 @@ def positive_gpoints(gmax, recvec, alpha, cellvolume):
     return gpoints[big], gweight[big], np.ascontiguousarray(gpts.T[big], dtype=np.int32)
 
 
+def generate_positive_gpoints(gmax, recvec):
+    """The half-space grid of ``generate_positive_gpoints`` (ewald.py:380-388) without the weight filter: the x > 0 block
+    (gmax, 2 gmax+1, 2 gmax+1), then x = 0, y > 0, then x = y = 0, z > 0, in that order; gmax (2 gmax+1)^2 + gmax (2 gmax+1) + gmax
+    points.  Returns the Cartesian vectors (n, 3) and their integer coordinates (n, 3) in the basis of the rows of
+    2 pi recvec."""
+    blocks = [np.mgrid[1 : gmax + 1, -gmax : gmax + 1, -gmax : gmax + 1].reshape(3, -1),
+              np.mgrid[0:1, 1 : gmax + 1, -gmax : gmax + 1].reshape(3, -1),
+              np.mgrid[0:1, 0:1, 1 : gmax + 1].reshape(3, -1)]
+    gpts = np.concatenate(blocks, axis=1)
+    gpoints = np.einsum("ji,jk->ik", gpts, np.asarray(recvec) * 2 * np.pi)
+    return gpoints, np.ascontiguousarray(gpts.T, dtype=np.int32)
+
+
 def ewald_tables(cell, ewald_gmax=200, nlatvec=1):
     if nlatvec != 1:
         raise NotImplementedError("the device real-space sum runs over the 27 cells of nlatvec = 1 (the reference's default)")
