@@ -447,6 +447,21 @@ int pqa_symmetry(pqa_handle_t* h, int nop, const double* ops, const double* orig
    (coordinates are read in place from whichever layout holds them: no layout sync, no change to anything a sweep reads). */
 int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, const double* recip, int mean, double* sq, double* spinsq);
 
+/* ---- correlated evaluation of parameter sets (line minimisation) ---------------------------------- */
+/* correlated_compute_worker (pyqmc/method/linemin.py:378-409): the resident walkers evaluated at K sets of the two-body Jastrow
+   coefficients acoeff (K, natom, na, 2) and bcoeff (K, nb, 3).  Row k equals, within rounding, what this sequence gives on the same
+   handle: upload set k's acoeff / bcoeff; pqa_wf_recompute -> logpsi[k] (W); pqa_energy(threshold, rot, unif, seed) -> en[k]
+   (6, W), with the same draws for every k (the reference resets numpy's random state before every set, linemin.py:394-397).
+   The Jastrow factor is linear in its coefficients, so the Slater part is evaluated once per call (a Slater-only energy pass:
+   Coulomb / Ewald, local ECP channel, ECP points with their Slater-weighted values) and each set only contracts basis-resolved
+   Jastrow rows (per electron grad / laplacian, per ECP point B(q) - B(r_e)) with its coefficients; logpsi[k] = log|Psi| + U_k - U
+   from the basis sums the handle keeps.  The handle's coefficients, walkers, inverses and basis sums are not written; as
+   pqa_energy it syncs a lane-per-walker layout back and drops saved gradient_value rows, as pqa_wf_value it refreshes stale basis
+   sums.  Real single-determinant Slater x two-body Jastrow handles with the semi-local ECP integrator, open or periodic; anything
+   else is refused. */
+int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, const double* bcoeff, double threshold, const double* rot,
+                   const double* unif, uint64_t seed, double* logpsi, double* en);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* HIP-event timing on the handle's own stream (torch.cuda.Event only sees torch's stream). */
 int pqa_timer_start(pqa_handle_t* h);

@@ -18,7 +18,9 @@ from . import obdm  # noqa: F401
 from .s2 import S2Accumulator  # noqa: F401
 from .symmetry import SymmetryAccumulator, SymmetryAccumulatorPBC  # noqa: F401
 from .sq import SqAccumulator  # noqa: F401
-from .accumulators import LinearTransform, PGradTransform, StochasticReconfiguration  # noqa: F401
+from .accumulators import LinearTransform, PGradTransform, StochasticReconfiguration, gradient_generator  # noqa: F401
+from . import sample_many  # noqa: F401
+from .linemin import line_minimization  # noqa: F401
 from .obdm import OBDMAccumulator  # noqa: F401
 from .tbdm import TBDMAccumulator  # noqa: F401
 

@@ -168,3 +168,12 @@ class StochasticReconfiguration:
 
 
 PGradTransform = StochasticReconfiguration
+
+
+def gradient_generator(mol, wf, to_opt=None, nodal_cutoff=1e-3, eps=1e-3, inverse_strategy="regularized_inverse", **ewald_kwargs):
+    """The gradient object of line minimisation (``observables/accumulators.py:27-42``): an ``EnergyAccumulator`` and the
+    ``LinearTransform`` of ``to_opt`` in a ``StochasticReconfiguration``."""
+    from .energy import EnergyAccumulator
+
+    return StochasticReconfiguration(EnergyAccumulator(mol, **ewald_kwargs), LinearTransform(wf.parameters, to_opt),
+                                     nodal_cutoff=nodal_cutoff, eps=eps, inverse_strategy=inverse_strategy)

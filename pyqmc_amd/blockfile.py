@@ -67,8 +67,20 @@ class BlockFile:
             configs.wrap = np.array(st["wrap"])
         return np.array(st["weights"]) if "weights" in st else None
 
+    def load_parameters(self):
+        """{key: array} of the ``wf/<key>`` parameters an optimisation file holds (``opt_hdf``); {} for a vmc / dmc file."""
+        if self.backend == "h5py":
+            with h5py.File(self.path, "r") as f:
+                if "wf" in f and not isinstance(f["wf"], h5py.Dataset):
+                    return {k: f["wf"][k][()] for k in f["wf"]}
+                return {k[3:]: f[k][()] for k in f if k.startswith("wf/")}  # (stores that keep the group's members as flat names)
+        with np.load(self.path + ".state.npz") as z:
+            return {k[3:]: z[k] for k in z.files if k.startswith("wf/")}
+
     # ---------------------------------------------------------------- writing
-    def append(self, block, attrs, configs, weights=None):
+    def append(self, block, attrs, configs, weights=None, parameters=None):
+        """One record.  ``parameters`` ({key: array}, optional): wave-function parameters kept as ``wf/<key>`` and overwritten
+        by every record (the optimisation file of linemin.py:23-38); without them the file is exactly a vmc / dmc block file."""
         state = {"configs": np.asarray(configs.configs)}
         if hasattr(configs, "wrap"):
             state["wrap"] = np.asarray(configs.wrap)
@@ -90,6 +102,10 @@ class BlockFile:
                     if k not in f:
                         f.create_dataset(k, v.shape, maxshape=(None,) + v.shape[1:], chunks=True, dtype=v.dtype)
                     f[k][...] = v
+                for k, v in (parameters or {}).items():
+                    if "wf/" + k not in f:
+                        f.create_dataset("wf/" + k, data=np.asarray(v))
+                    f["wf/" + k][...] = np.asarray(v)
             return
         if self._nblocks is None:
             idx = self._block_index()
@@ -98,7 +114,7 @@ class BlockFile:
         # walkers first, record second: a crash in between leaves walkers one block AHEAD of the record (that block's averages
         # are lost), never a record whose walkers are one block behind
         tmp = self.path + ".state.tmp.npz"
-        np.savez(tmp, **state)
+        np.savez(tmp, **state, **{"wf/" + k: np.asarray(v) for k, v in (parameters or {}).items()})
         os.replace(tmp, self.path + ".state.npz")
         with zipfile.ZipFile(self.path + ".blocks.npz", "a", zipfile.ZIP_STORED) as z:
             for k, v in block.items():
@@ -124,7 +140,7 @@ class BlockFile:
             with h5py.File(self.path, "r") as f:
                 return {k: f[k][()] for k in STATE_KEYS if k in f}
         with np.load(self.path + ".state.npz") as z:
-            return {k: z[k] for k in z.files}
+            return {k: z[k] for k in z.files if not k.startswith("wf/")}
 
     def attrs(self):
         if self.backend == "h5py":
@@ -141,7 +157,7 @@ class BlockFile:
         """{dataset name: (nblocks, ...) array} — exactly the per-block datasets of the HDF5 layout."""
         if self.backend == "h5py":
             with h5py.File(self.path, "r") as f:
-                return {k: f[k][()] for k in f if with_state or k not in STATE_KEYS}
+                return {k: f[k][()] for k in f if (with_state or k not in STATE_KEYS) and not k.startswith("wf/") and isinstance(f[k], h5py.Dataset)}
         cols = {}
         with zipfile.ZipFile(self.path + ".blocks.npz") as z:
             for n in sorted(z.namelist()):

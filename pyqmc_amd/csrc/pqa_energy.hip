@@ -187,6 +187,7 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
     }
     }
     h->last_ecp_points = defer ? -1 : tot[0] + tot[1];
+    h->ecp_last_tot[0] = defer ? -1 : tot[0]; h->ecp_last_tot[1] = defer ? -1 : tot[1]; h->ecp_last_nseg = B.nseg;
     h->last_ecp_dev[0] = defer ? cnt_dev[0] : nullptr; h->last_ecp_dev[1] = defer ? cnt_dev[1] : nullptr;
     for (int s = 0; s < 2; ++s) {
       const size_t n = (size_t)std::max<long>(tot[s], 1);

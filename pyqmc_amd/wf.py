@@ -271,6 +271,21 @@ class DeviceWF:
         out[5] += 1j * a[6]
         return np.moveaxis(out, 0, axis)
 
+    def correlated(self, acoeff, bcoeff, threshold=10.0, rot=None, unif=None, seed=0):
+        """``pqa_correlated``: the resident walkers at K sets of two-body Jastrow coefficients, acoeff (K, natom, na, 2) and
+        bcoeff (K, nb, 3), every set with the same energy draws -> (logpsi (K, W), energy rows (K, 6, W)).  The handle keeps its
+        own coefficients and state."""
+        a, b = _ffi.f64(acoeff), _ffi.f64(bcoeff)
+        K = a.shape[0]
+        if a.shape != (K, self.natom, self.na, 2) or b.shape != (K, self.nb, 3):
+            raise ValueError(f"acoeff (K, {self.natom}, {self.na}, 2) and bcoeff (K, {self.nb}, 3) expected, got {a.shape}, {b.shape}")
+        logpsi, en = np.empty((K, self.W)), np.empty((K, 6, self.W))
+        rot = None if rot is None else _ffi.f64(rot)
+        unif = None if unif is None else _ffi.f64(unif)
+        self.call("pqa_correlated", int(K), _ffi.ptr(a), _ffi.ptr(b), float(threshold), _ffi.ptr(rot), _ffi.ptr(unif), int(seed),
+                  _ffi.ptr(logpsi), _ffi.ptr(en))
+        return logpsi, en
+
     def vmc_sweeps(self, tstep, nsteps, gauss=None, unif=None, threshold=10.0, ecp_rot=None, ecp_unif=None, seed=0,
                    energy=True, record=False):
         acc = np.empty(nsteps)
@@ -1131,3 +1146,34 @@ def generate_wf(mol, mf, determinants=None, jastrow_kws=None, device=0, tol=None
     if jastrow3:
         return MultiplyWF(sl, ja, ThreeBodyJastrow(mol, a3, b3, _dev=dev))
     return MultiplyWF(sl, ja)
+
+
+def default_to_opt(wf, optimize_orbitals=False, optimize_zeros=True, epsilon=1e-8):
+    """The ``to_opt`` dictionary the reference's ``wftools.generate_wf`` returns beside a wave function (wftools.py:50-61, :147-151),
+    for a wave function built by ``generate_wf`` (whose own return value stays the wave function alone):
+    ``wf1det_coeff`` true except the largest coefficient when there is more than one determinant (else all false);
+    ``wf1mo_coeff_alpha`` / ``wf1mo_coeff_beta`` with ``optimize_orbitals``: all true, or with ``optimize_zeros=False`` false where
+    |c| < ``epsilon`` (generate_slater's arguments and defaults, wftools.py:27-35, :55-58); ``wf2acoeff`` all true except the cusp
+    entries ``[:, 0, :]`` when the basis starts with an ion cusp; ``wf2bcoeff`` all true except row 0 (the electron-electron cusp);
+    ``wf3ccoeff`` all true when there is a three-body factor."""
+    sl, ja = wf.wf_factors[0], wf.wf_factors[1]
+    det = np.asarray(sl.parameters["det_coeff"])
+    to_opt = {"wf1det_coeff": np.zeros(det.shape, dtype=bool)}
+    if det.size > 1:
+        to_opt["wf1det_coeff"][:] = True
+        to_opt["wf1det_coeff"][np.argmax(np.abs(det))] = False
+    if optimize_orbitals:
+        for k in ("mo_coeff_alpha", "mo_coeff_beta"):
+            to_opt["wf1" + k] = np.ones(np.shape(sl.parameters[k]), dtype=bool)
+            if not optimize_zeros:
+                to_opt["wf1" + k][np.abs(np.asarray(sl.parameters[k])) < epsilon] = False
+    a = np.ones(np.shape(ja.parameters["acoeff"]), dtype=bool)
+    abasis = ja._dev._ctor.get("a_basis") or []
+    if len(abasis) and isinstance(abasis[0], func3d.CutoffCuspFunction):
+        a[:, 0, :] = False  # (cusp conditions)
+    b = np.ones(np.shape(ja.parameters["bcoeff"]), dtype=bool)
+    b[0, [0, 1, 2]] = False
+    to_opt["wf2acoeff"], to_opt["wf2bcoeff"] = a, b
+    if len(wf.wf_factors) > 2:
+        to_opt["wf3ccoeff"] = np.ones(np.shape(wf.wf_factors[2].parameters["ccoeff"]), dtype=bool)
+    return to_opt
