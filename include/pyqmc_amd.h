@@ -462,6 +462,23 @@ int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, const doubl
 int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, const double* bcoeff, double threshold, const double* rot,
                    const double* unif, uint64_t seed, double* logpsi, double* en);
 
+/* ---- mixture sampling of several wave functions (excited states) ------------------------------------------------------------------ */
+/* sample_overlap_worker (pyqmc/method/sample_many.py:130-186) without its accumulator: nsteps Metropolis sweeps of the walkers resident
+   on the K handles hs[0..K-1] with the distribution sum_k |Psi_k|^2, all on the device.  Every electron move does what the protocol
+   route (MultiplyWF.gradient / gradient_value / value / updateinternals per handle) does: the proposal x + gauss + tstep limdrift(mean_k
+   grad_k), the acceptance t_prob sum_k |ratio_k|^2 w_k / sum_k w_k with w_k = exp(2 (log|Psi_k| - log|Psi_0|)) against unif, and the
+   Sherman-Morrison + Jastrow updates of all K handles under the one accept mask; a handle whose determinants of the moved spin had
+   vanished (slater.py:269-275) has its Slater state rebuilt from the moved walkers instead.  gauss (nsteps*N, W, 3) already scaled by
+   sqrt(tstep) and unif (nsteps*N, W) are the reference's draws in its order.  After each sweep n, overlap[n] (K, K) is the walker mean
+   of psi_i psi_j / rho (compute_weights, :42-55); weights (K, K, W) or NULL receives the last sweep's per-walker values; acc_ratio or
+   NULL the accepted fraction of all moves.  Scope: real Slater x two-body Jastrow handles (pqa_wf_eval's), any number of
+   determinants, open boundaries, one device, equal W, N and nelec_up, distinct handles, K <= 8; anything else is refused and the
+   caller takes the protocol route.  All K handles' work runs on hs[0]'s stream.  Afterwards every handle holds the state the
+   protocol route would leave (walkers, inverses, determinants, Jastrow sums); saved gradient_value rows are dropped.  Errors are
+   reported on hs[0]. */
+int pqa_overlap_sweeps(pqa_handle_t* const* hs, int K, double tstep, int nsteps, const double* gauss, const double* unif,
+                       double* overlap, double* weights, double* acc_ratio);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* HIP-event timing on the handle's own stream (torch.cuda.Event only sees torch's stream). */
 int pqa_timer_start(pqa_handle_t* h);

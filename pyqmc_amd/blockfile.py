@@ -72,7 +72,10 @@ class BlockFile:
         if self.backend == "h5py":
             with h5py.File(self.path, "r") as f:
                 if "wf" in f and not isinstance(f["wf"], h5py.Dataset):
-                    return {k: f["wf"][k][()] for k in f["wf"]}
+                    out = {}
+                    # (nested groups too: "wf/<state>/<key>" of an ensemble optimisation file)
+                    f["wf"].visititems(lambda k, obj: out.__setitem__(k, obj[()]) if isinstance(obj, h5py.Dataset) else None)
+                    return out
                 return {k[3:]: f[k][()] for k in f if k.startswith("wf/")}  # (stores that keep the group's members as flat names)
         with np.load(self.path + ".state.npz") as z:
             return {k[3:]: z[k] for k in z.files if k.startswith("wf/")}
@@ -157,12 +160,23 @@ class BlockFile:
         """{dataset name: (nblocks, ...) array} — exactly the per-block datasets of the HDF5 layout."""
         if self.backend == "h5py":
             with h5py.File(self.path, "r") as f:
-                return {k: f[k][()] for k in f if (with_state or k not in STATE_KEYS) and not k.startswith("wf/") and isinstance(f[k], h5py.Dataset)}
+                out = {}
+
+                def take(k, obj):
+                    if (with_state or k not in STATE_KEYS) and not k.startswith("wf/") and isinstance(obj, h5py.Dataset):
+                        out[k] = obj[()]
+
+                if hasattr(f, "visititems"):  # datasets inside groups too ("weighted/total" of a sample_overlap file)
+                    f.visititems(take)
+                else:
+                    for k in f:
+                        take(k, f[k])
+                return out
         cols = {}
         with zipfile.ZipFile(self.path + ".blocks.npz") as z:
             for n in sorted(z.namelist()):
-                if not n.startswith("__attrs__/"):
-                    cols.setdefault(n.split("/")[0], []).append(np.load(io.BytesIO(z.read(n))))
+                if not n.startswith("__attrs__/"):  # member <dataset>/<block>.npy; a dataset name may hold a group ("weighted/total")
+                    cols.setdefault(n.rsplit("/", 1)[0], []).append(np.load(io.BytesIO(z.read(n))))
         out = {k: np.stack(v) for k, v in cols.items()}
         if with_state:
             out.update(self._state())

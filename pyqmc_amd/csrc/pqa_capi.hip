@@ -899,6 +899,8 @@ extern "C" void pqa_destroy(pqa_handle_t* h) {
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->pin_tot) (void)hipHostFree(h->pin_tot);
+  if (h->b_ovl.p) (void)hipFree(h->b_ovl.p);
+  if (h->pin_ovl) (void)hipHostFree(h->pin_ovl);
   if (h->en_stream) { (void)hipStreamSynchronize(h->en_stream); (void)hipStreamDestroy(h->en_stream); }
   if (h->draw_stream) { (void)hipStreamSynchronize(h->draw_stream); (void)hipStreamDestroy(h->draw_stream); }
   for (hipEvent_t e : h->draw_ev) if (e) (void)hipEventDestroy(e);
@@ -1135,7 +1137,7 @@ static int ensure_walkers(pqa_handle* h, long W) {
   return 0;
 }
 
-static int jas_refresh(pqa_handle* h) {
+int jas_refresh(pqa_handle* h) {
   if (h->has_j2 && h->jas_stale && h->W > 0) {
     hipLaunchKernelGGL((k_jastrow_recompute<>), dim3((unsigned)h->W), dim3(64), 0, h->stream, h->S, h->js);
     TRY(check_launch(h, "k_jastrow_recompute"));
@@ -1145,7 +1147,7 @@ static int jas_refresh(pqa_handle* h) {
 }
 
 
-static int slater_rebuild(pqa_handle* h) {  // cache + inverse + determinants from js.x
+int slater_rebuild(pqa_handle* h) {  // cache + inverse + determinants from js.x
   const int nel[2] = {h->nup, h->ndn};
   for (int s = 0; s < 2; ++s) {
     if (nel[s] == 0) {  // an empty spin channel (fully polarised system): the determinant of the 0 x 0 matrix is 1
@@ -1184,7 +1186,7 @@ static int slater_rebuild(pqa_handle* h) {  // cache + inverse + determinants fr
   return 0;
 }
 
-static int slater_value_dev(pqa_handle* h) {
+int slater_value_dev(pqa_handle* h) {
   if (h->cplx) hipLaunchKernelGGL((k_slater_value_c<>), dim3((unsigned)h->W), dim3(64), 0, h->stream, h->S, h->st, (double*)h->b_sign.p, (double*)h->b_log.p);
   else hipLaunchKernelGGL((k_slater_value<>), dim3((unsigned)h->W), dim3(64), 0, h->stream, h->S, h->st, (double*)h->b_sign.p, (double*)h->b_log.p);
   return check_launch(h, "k_slater_value");

@@ -126,6 +126,10 @@ struct pqa_handle {
   // running sums.  sq_attr: k_sq<true>'s dynamic-LDS limit raised (phase tables above 64 KiB per walker)
   DevBuf b_sqq, b_sqout, b_sqpart, b_sqacc;
   bool sq_attr = false;
+  // pqa_overlap_sweeps (pqa_overlap.hip), on the first handle of the call: one sweep's tapes, the old-position drift, acceptance counts,
+  // the (K, K, W) weights and the per-sweep overlaps; pinned words the vanished-determinant flags of all K handles come back in
+  DevBuf b_ovl;
+  int* pin_ovl = nullptr;
   DevBuf b_tpos, b_twgt, b_tlive, b_trat;
   DevBuf b_tmcnt, b_tmoff, b_tmpass, b_tmamp, b_tmacc, b_tmidx, b_tmapos, b_tmu, b_tmtile, b_tmaoff, b_tmptw, b_tmmarks, b_dmcw, b_dmcold, b_dmcr2, b_dmcout;
   int tm_P = 0;
@@ -357,3 +361,7 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
                bool soa_current = false, bool aos_T_needed = true, bool assemble = true);
 // pqa_dmcsteps.hip
 int scan_ints(pqa_handle* h, const int* c, long* o, long n, long Wm, long* marks);
+// pqa_capi.hip
+int jas_refresh(pqa_handle* h);       // basis sums a fused sweep left stale, recomputed
+int slater_rebuild(pqa_handle* h);    // orbital cache, inverses and determinants of both spins from js.x
+int slater_value_dev(pqa_handle* h);  // sign / log of the Slater factor -> b_sign / b_log

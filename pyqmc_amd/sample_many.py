@@ -1,14 +1,25 @@
 """Sampling the mixture of several wave functions — ``pyqmc/method/sample_many.py``.
 
 ``sample_overlap_worker`` moves the walkers by Metropolis with the distribution proportional to ``sum_i |Psi_i|^2`` over the
-wave functions ``wfs`` (deep copies of one device wave function, each on a handle of its own), through the protocol entry points
-(``gradient``, ``gradient_value``, ``updateinternals`` with ``saved_values``).  Its draws are ``np.random.normal`` and
-``np.random.rand`` in the reference's order, so a test can replay them.  Line minimisation (``pyqmc_amd.linemin``) calls it with
-``energy=None``, the only value in scope here: the weighted energies need the reference's ``EnergyAccumulatorMultipleWF``, which
-this package does not have.
+wave functions ``wfs`` (deep copies of one device wave function, each on a handle of its own).  Two routes give the same walk:
+
+* ``"fused"``: ``pqa_overlap_sweeps`` runs the sweeps of all K handles on the device (real Slater x two-body Jastrow handles, any
+  number of determinants, open boundaries, one device, distinct handles, K <= 8);
+* ``"protocol"``: the reference's loop over the protocol entry points (``gradient``, ``gradient_value``, ``value``,
+  ``updateinternals`` with ``saved_values``) for everything else.
+
+Both draw ``np.random.normal`` and ``np.random.rand`` in the reference's order, so seeded runs agree and a test can replay the draws.
+``energy`` is a multiple-wave-function accumulator (``avg(configs, wfs, weights)``, e.g. ``EnergyAccumulatorMultipleWF``) or None;
+the route the last worker call took is in ``last_route``.
 """
 
+import ctypes as C
+
 import numpy as np
+
+from . import _ffi
+
+last_route = None  # "fused" or "protocol": the route of the last sample_overlap_worker call
 
 
 def limdrift(g, cutoff=1):
@@ -19,10 +30,10 @@ def limdrift(g, cutoff=1):
     return g
 
 
-def _no_energy(energy):
-    if energy is not None:
-        raise NotImplementedError("sample_overlap with an energy accumulator needs EnergyAccumulatorMultipleWF, which pyqmc_amd does not "
-                                  "provide: pass energy=None")
+def _check_energy(energy):
+    if energy is not None and not getattr(energy, "multiple_wf", False):
+        raise NotImplementedError("sample_overlap needs an accumulator over several wave functions (avg(configs, wfs, weights)): wrap "
+                                  "a single-wave-function accumulator in EnergyAccumulatorMultipleWF or AdaptSingleAccumulator")
 
 
 def compute_weights(wfs):
@@ -48,10 +59,75 @@ def rolling_average(block, data, nsteps):
         block[k] += it / nsteps
 
 
-def sample_overlap_worker(wfs, configs, tstep, nsteps, energy):
-    r"""``nsteps`` Metropolis sweeps with the distribution :math:`\propto \sum_i |\Psi_i|^2` (sample_many.py:137-195).
-    Returns (weighted block, unweighted block, configs)."""
-    _no_energy(energy)
+def fused_handles(wfs, configs):
+    """The device handles of ``wfs`` when the fused route can take them, else None (see the module docstring)."""
+    if len(wfs) < 1 or len(wfs) > 8 or hasattr(configs, "wrap") or np.ndim(configs.configs) != 3:
+        return None
+    devs = []
+    for wf in wfs:
+        d = wf._product_device() if hasattr(wf, "_product_device") else None
+        if d is None or d.pbc or getattr(d, "twisted", False):
+            return None
+        devs.append(d)
+    if len({id(d) for d in devs}) != len(devs) or len({d.device for d in devs}) != 1:
+        return None
+    return devs
+
+
+def _route(wfs, configs, route):
+    if route not in (None, "fused", "protocol"):
+        raise ValueError(f"route must be None, 'fused' or 'protocol', not {route!r}")
+    devs = None if route == "protocol" else fused_handles(wfs, configs)
+    if route == "fused" and devs is None:
+        raise ValueError("route='fused' needs real Slater x two-body Jastrow wave functions on distinct handles of one device, open "
+                         "boundaries and at most 8 wave functions")
+    return devs
+
+
+def overlap_sweeps(devs, tstep, gauss, unif, weights=False):
+    """``pqa_overlap_sweeps`` on the handles ``devs`` with the tapes gauss (nsteps*N, W, 3) and unif (nsteps*N, W) -> (overlap
+    (nsteps, K, K), weights (K, K, W) of the last sweep or None, acceptance)."""
+    K, W, N = len(devs), devs[0].W, devs[0].N
+    nsteps = gauss.shape[0] // N
+    gauss, unif = _ffi.f64(gauss), _ffi.f64(unif)
+    ovl = np.empty((nsteps, K, K))
+    wts = np.empty((K, K, W)) if weights else None
+    acc = C.c_double()
+    hs = (C.c_void_p * K)(*[d._h.value for d in devs])
+    rc = _ffi.lib().pqa_overlap_sweeps(hs, K, float(tstep), int(nsteps), _ffi.ptr(gauss), _ffi.ptr(unif), _ffi.ptr(ovl),
+                                       None if wts is None else _ffi.ptr(wts), C.byref(acc))
+    for d in devs:
+        d._zero = [None, None]  # (the determinants changed)
+    _ffi.check(devs[0]._h, rc)
+    return ovl, wts, acc.value
+
+
+def _worker_fused(devs, wfs, configs, tstep, nsteps, energy):
+    for wf in wfs:
+        wf.recompute(configs)
+        wf.wf_factors[0]._saved = None
+    weighted_block = {}
+    unweighted_block = {"acceptance": 0.0}
+    nconf, nelec = configs.configs.shape[:2]
+    per_call = 1 if energy is not None else nsteps  # an accumulator may draw from np.random between sweeps: tapes per sweep then
+    for n0 in range(0, nsteps, max(per_call, 1)):
+        m = min(per_call, nsteps - n0)
+        gauss, unif = np.empty((m * nelec, nconf, 3)), np.empty((m * nelec, nconf))
+        for i in range(m * nelec):
+            gauss[i] = np.random.normal(scale=np.sqrt(tstep), size=(nconf, 3))
+            unif[i] = np.random.rand(nconf)
+        overlap, weights, _ = overlap_sweeps(devs, tstep, gauss, unif, weights=energy is not None)
+        if energy is not None:
+            configs.configs[...] = devs[0].configs()
+        for j in range(m):
+            rolling_average(unweighted_block, {"overlap": overlap[j]}, nsteps)
+            if energy is not None:
+                rolling_average(weighted_block, energy.avg(configs, wfs, weights), nsteps)
+    configs.configs[...] = devs[0].configs()
+    return weighted_block, unweighted_block, configs
+
+
+def _worker_protocol(wfs, configs, tstep, nsteps, energy):
     for wf in wfs:
         wf.recompute(configs)
     weighted_block = {}
@@ -80,20 +156,68 @@ def sample_overlap_worker(wfs, configs, tstep, nsteps, energy):
                 wf.updateinternals(e, newcoorde, configs, mask=accept, saved_values=saved)
         weights = compute_weights(wfs)
         rolling_average(unweighted_block, {"overlap": np.mean(weights, axis=-1)}, nsteps)
+        if energy is not None:
+            rolling_average(weighted_block, energy.avg(configs, wfs, weights), nsteps)
     return weighted_block, unweighted_block, configs
 
 
-def sample_overlap(wfs, configs, energy, nsteps=10, nblocks=10, tstep=0.5, hdf_file=None, client=None, npartitions=None):
-    """``nblocks`` blocks of ``sample_overlap_worker`` (sample_many.py:80-105, :205-223) -> (weighted, unweighted, configs), the
-    block dictionaries inverted to ``{quantity: array over blocks}``.  No block file and no parallel client here."""
-    _no_energy(energy)
+def sample_overlap_worker(wfs, configs, tstep, nsteps, energy, route=None):
+    r"""``nsteps`` Metropolis sweeps with the distribution :math:`\propto \sum_i |\Psi_i|^2` (sample_many.py:130-186).
+    Returns (weighted block, unweighted block, configs).  ``route``: None (fused when every handle is eligible), "fused" (an error
+    if one is not) or "protocol"."""
+    global last_route
+    _check_energy(energy)
+    devs = _route(wfs, configs, route)
+    last_route = "protocol" if devs is None else "fused"
+    if devs is None:
+        return _worker_protocol(wfs, configs, tstep, nsteps, energy)
+    return _worker_fused(devs, wfs, configs, tstep, nsteps, energy)
+
+
+def hdf_save(hdf_file, weighted, unweighted, attr, configs):
+    """sample_many.py:27-39 through ``BlockFile``: one record per block, its datasets in the groups ``weighted`` and ``unweighted``
+    (``weighted/total``, ``unweighted/overlap``, ...), the walkers overwritten."""
+    if hdf_file is not None:
+        from .blockfile import BlockFile
+
+        rec = {f"{label}/{k}": v for label, data in (("weighted", weighted), ("unweighted", unweighted)) for k, v in data.items()}
+        BlockFile(hdf_file).append(rec, attr, configs)
+
+
+def sample_overlap(wfs, configs, energy, nsteps=10, nblocks=10, tstep=0.5, hdf_file=None, client=None, npartitions=None, route=None):
+    """``nblocks`` blocks of ``sample_overlap_worker`` (sample_many.py:63-88, :189-213) -> (weighted, unweighted, configs), the
+    block dictionaries inverted to ``{quantity: array over blocks}``.  ``hdf_file``: every block appended through ``BlockFile``; an
+    existing file gives the starting walkers (the reference's restart).  No parallel client here."""
+    _check_energy(energy)
     if client is not None or npartitions is not None:
         raise NotImplementedError("pyqmc_amd.sample_overlap runs on one device: client / npartitions must be None")
     if hdf_file is not None:
-        raise NotImplementedError("pyqmc_amd.sample_overlap writes no block file: hdf_file must be None")
+        from .blockfile import BlockFile
+
+        store = BlockFile(hdf_file)
+        if store.exists():
+            store.load_walkers(configs)
     weighted, unweighted = [], []
     for _ in range(nblocks):
-        w, u, configs = sample_overlap_worker(wfs, configs, tstep, nsteps, energy)
+        w, u, configs = sample_overlap_worker(wfs, configs, tstep, nsteps, energy, route=route)
         weighted.append(w)
         unweighted.append(u)
+        hdf_save(hdf_file, w, u, dict(tstep=tstep), configs)
     return invert_list_of_dicts(weighted), invert_list_of_dicts(unweighted), configs
+
+
+def normalize(weighted, unweighted):
+    """Averages and standard errors over blocks (sample_many.py:216-235): the unweighted quantities as they are, the weighted ones
+    divided by sqrt(N_i N_j) with N the diagonal of the mean overlap."""
+    import scipy.stats
+
+    avg, error = {}, {}
+    for k, it in unweighted.items():
+        avg[k] = np.mean(it, axis=0)
+        error[k] = scipy.stats.sem(it, axis=0)
+    N = np.abs(avg["overlap"].diagonal())
+    Nij = np.sqrt(np.outer(N, N))
+    for k, it in weighted.items():
+        avg[k] = np.mean(it, axis=0) / Nij
+        error[k] = scipy.stats.sem(it, axis=0) / Nij
+    return avg, error
