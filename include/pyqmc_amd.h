@@ -462,6 +462,19 @@ int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, const doubl
 int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, const double* bcoeff, double threshold, const double* rot,
                    const double* unif, uint64_t seed, double* logpsi, double* en);
 
+/* ---- variance of the local energy at parameter sets (variance optimisation) ------------------------------------------------------ */
+/* optvariance.py:44-54 on the resident walkers, for K sets of two-body Jastrow coefficients acoeff (K,natom,na,2),
+   bcoeff (K,nb,3).  eoff (W) = Enref total - Enref ke per walker.  For set k:
+     ke[k][w]  kinetic energy with set k (NULL: not written),
+     var[k]    population variance (ddof 0) over w of eoff[w] + ke[k][w],
+     dvar[k]   (P) d var[k] / d c, acoeff entries then bcoeff entries in their array order (NULL: not computed).
+   Only the kinetic energy is evaluated (the Jastrow rows of pqa_correlated, no Coulomb, no ECP); ke agrees with pqa_correlated's ke
+   row.  The walker reductions run on the device in a fixed order (two calls give the same bits).  The handle's coefficients,
+   walkers, inverses and basis sums are not written (a lane-per-walker layout is synced back, as pqa_energy does).  Real
+   single-determinant Slater x two-body Jastrow handles, open or periodic, with or without ECP; anything else is refused. */
+int pqa_variance(pqa_handle_t* h, int K, const double* acoeff, const double* bcoeff, const double* eoff, double* ke, double* var,
+                 double* dvar);
+
 /* ---- mixture sampling of several wave functions (excited states) ------------------------------------------------------------------ */
 /* sample_overlap_worker (pyqmc/method/sample_many.py:130-186) without its accumulator: nsteps Metropolis sweeps of the walkers resident
    on the K handles hs[0..K-1] with the distribution sum_k |Psi_k|^2, all on the device.  Every electron move does what the protocol

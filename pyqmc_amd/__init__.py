@@ -21,6 +21,7 @@ from .sq import SqAccumulator  # noqa: F401
 from .accumulators import LinearTransform, PGradTransform, StochasticReconfiguration, gradient_generator  # noqa: F401
 from . import sample_many  # noqa: F401
 from .linemin import line_minimization  # noqa: F401
+from .optvariance import optvariance  # noqa: F401
 from .accumulators_multiwf import AdaptSingleAccumulator, EnergyAccumulatorMultipleWF  # noqa: F401
 from .ensemble import StochasticReconfigurationWfbyWf, optimize_ensemble  # noqa: F401
 from .obdm import OBDMAccumulator  # noqa: F401

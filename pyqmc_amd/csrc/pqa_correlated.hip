@@ -13,6 +13,7 @@
 //                   ecp_k = local + sum_q s_q exp(dU_k(q)),  total_k = ke_k + ee + ei + ecp_k + ii.
 // The handle's coefficients are never changed.  Outputs are written per walker chunk of at most 256 MiB.
 #include "pqa_internal.hpp"
+#include "pqa_jrows.hpp"
 
 namespace {
 
@@ -53,12 +54,10 @@ struct CorrArgs {
 
 template <bool PBC>
 __device__ __forceinline__ double dist(const SysDev& S, double dx, double dy, double dz, double (&d)[3]) {
-  if (PBC) min_image_j(S, dx, dy, dz);
-  d[0] = dx; d[1] = dy; d[2] = dz;
-  return sqrt(dx * dx + dy * dy + dz * dz);
+  return jrow_dist<PBC>(S, dx, dy, dz, d);
 }
 
-// One wave per walker (grid.x), lanes = parameter sets kb + lane (grid.y: chunks of 64 sets).  LDS: rows R[4][P].
+// One wave per walker (grid.x), lanes = parameter sets kb + lane (grid.y: chunks of 64 sets).  LDS: rows R[4][P] (jas_rows).
 template <bool PBC>
 __global__ __launch_bounds__(64) void k_corr_energy(SysDev S, SlaterState st, JastrowState js, CorrArgs A) {
   extern __shared__ double R[];
@@ -75,45 +74,7 @@ __global__ __launch_bounds__(64) void k_corr_energy(SysDev S, SlaterState st, Ja
     double r[5];
     slater_ratios<5>(S, st, s, i, w, st.cache[s] + ((size_t)w * n + i) * 5 * nmo, r, nullptr);
     const double G0 = r[1] / r[0], G1 = r[2] / r[0], G2 = r[3] / r[0], L = r[4] / r[0];
-    const double ex = xw[3 * e], ey = xw[3 * e + 1], ez = xw[3 * e + 2];
-    for (int p = lane; p < 4 * P; p += 64) R[p] = 0.0;
-    __syncthreads();
-    // one-body rows: a lane owns an atom, so its entries (atom, k, spin of e) are written by it alone
-    for (int I = lane; I < S.natom; I += 64) {
-      double d[3];
-      const double rr = dist<PBC>(S, ex - S.atom_xyz[3 * I], ey - S.atom_xyz[3 * I + 1], ez - S.atom_xyz[3 * I + 2], d);
-      if (rr < S.rcut_a) {
-        const RadShared sh = rad_shared<2>(rr, ira);
-        for (int a = 0; a < S.na; ++a) {
-          double v, gf, lpl;
-          rad_fn<2>(S.a_kind[a], S.a_param[a], S.a_aux[a], S.rcut_a, sh, v, gf, lpl);
-          const int p = (I * S.na + a) * 2 + s;
-          R[p] = gf * d[0]; R[P + p] = gf * d[1]; R[2 * P + p] = gf * d[2]; R[3 * P + p] = lpl;
-        }
-      }
-    }
-    // two-body rows: columns s (same spin pair: 2s) and s + 1 of basis function l, summed over the other electrons
-    for (int l = 0; l < S.nb; ++l) {
-      double acc[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
-      for (int j = lane; j < N; j += 64) {
-        if (j == e) continue;
-        double d[3];
-        const double rr = dist<PBC>(S, ex - xw[3 * j], ey - xw[3 * j + 1], ez - xw[3 * j + 2], d);
-        if (rr < S.rcut_b) {
-          const RadShared sh = rad_shared<2>(rr, irb);
-          double v, gf, lpl;
-          rad_fn<2>(S.b_kind[l], S.b_param[l], S.b_aux[l], S.rcut_b, sh, v, gf, lpl);
-          const int c = j >= S.nup;
-          acc[c][0] += gf * d[0]; acc[c][1] += gf * d[1]; acc[c][2] += gf * d[2]; acc[c][3] += lpl;
-        }
-      }
-      for (int c = 0; c < 2; ++c)
-        for (int m = 0; m < 4; ++m) {
-          const double t = wave_sum(acc[c][m]);
-          if (lane == 0) R[m * P + Pa + l * 3 + s + c] = t;
-        }
-    }
-    __syncthreads();
+    jas_rows<PBC>(S, xw, e, s, xw[3 * e], xw[3 * e + 1], xw[3 * e + 2], P, Pa, ira, irb, R);
     if (act) {
       double gx = 0.0, gy = 0.0, gz = 0.0, lp = 0.0;
       for (int q = 0; q < S.natom * S.na; ++q) {

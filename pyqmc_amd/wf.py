@@ -286,6 +286,23 @@ class DeviceWF:
                   _ffi.ptr(logpsi), _ffi.ptr(en))
         return logpsi, en
 
+    def variance(self, acoeff, bcoeff, eoff, grad=False, ke=False):
+        """``pqa_variance``: population variance over the resident walkers of ``eoff + ke_k`` at K sets of two-body Jastrow
+        coefficients, acoeff (K, natom, na, 2) and bcoeff (K, nb, 3), with ``eoff`` (W) the fixed part of the local energy ->
+        (var (K,), dvar (K, P) or None, ke (K, W) or None).  ``grad``: d var / dc, acoeff entries then bcoeff entries; ``ke``: the
+        kinetic energies.  The handle keeps its own coefficients and state."""
+        a, b, e = _ffi.f64(acoeff), _ffi.f64(bcoeff), _ffi.f64(eoff)
+        K = a.shape[0]
+        if a.shape != (K, self.natom, self.na, 2) or b.shape != (K, self.nb, 3):
+            raise ValueError(f"acoeff (K, {self.natom}, {self.na}, 2) and bcoeff (K, {self.nb}, 3) expected, got {a.shape}, {b.shape}")
+        if e.shape != (self.W,):
+            raise ValueError(f"eoff ({self.W},) expected, got {e.shape}")
+        var = np.empty(K)
+        dvar = np.empty((K, a[0].size + b[0].size)) if grad else None
+        kin = np.empty((K, self.W)) if ke else None
+        self.call("pqa_variance", int(K), _ffi.ptr(a), _ffi.ptr(b), _ffi.ptr(e), _ffi.ptr(kin), _ffi.ptr(var), _ffi.ptr(dvar))
+        return var, dvar, kin
+
     def vmc_sweeps(self, tstep, nsteps, gauss=None, unif=None, threshold=10.0, ecp_rot=None, ecp_unif=None, seed=0,
                    energy=True, record=False):
         acc = np.empty(nsteps)
