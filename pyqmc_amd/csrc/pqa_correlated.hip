@@ -7,17 +7,14 @@
 //                   the ECP point lists with their Slater-weighted values s_q = (D(e -> q) / D) w_q (b_econ), the same draws for all
 //                   sets; the log values from the basis sums the handle keeps (k_corr_u);
 //   per walker      k_corr_energy: per electron grad D / D and lap D / D (from the orbital-row cache), the basis-resolved Jastrow rows
-//                   (grad_e B_p, lap_e B_p) in LDS, and for every ECP point the row B_p(q) - B_p(r_e); each row is contracted with the
-//                   (P x K) coefficient matrix, one set per lane, and combined per set:
+//                   (grad_e B_p, lap_e B_p) in LDS, and for every ECP point the row B_p(q) - B_p(r_e) (jas_rows / jas_diff_rows,
+//                   pqa_estim.hpp); each row is contracted with the (P x K) coefficient matrix, one set per lane, and combined per set:
 //                   ke_k = -1/2 sum_e [lap D/D + 2 grad D/D . grad U_k + lap U_k + |grad U_k|^2],  grad2_k = sum_e |grad D/D + grad U_k|^2,
 //                   ecp_k = local + sum_q s_q exp(dU_k(q)),  total_k = ke_k + ee + ei + ecp_k + ii.
 // The handle's coefficients are never changed.  Outputs are written per walker chunk of at most 256 MiB.
-#include "pqa_internal.hpp"
-#include "pqa_jrows.hpp"
+#include "pqa_estim.hpp"
 
 namespace {
-
-constexpr size_t kCorrScratchBytes = size_t(256) << 20;
 
 // U[k][w] = sum_i bvalues[w][i] c_b[k][i] + sum_i avalues[w][i] c_a[k][i] for k < K1: one wave per walker, the summation order of
 // jas_value_wave (k_jastrow_value), so the row of the handle's own coefficients reproduces its Jastrow value bit for bit.
@@ -52,12 +49,7 @@ struct CorrArgs {
   double* out;              // [K][6][Wc]
 };
 
-template <bool PBC>
-__device__ __forceinline__ double dist(const SysDev& S, double dx, double dy, double dz, double (&d)[3]) {
-  return jrow_dist<PBC>(S, dx, dy, dz, d);
-}
-
-// One wave per walker (grid.x), lanes = parameter sets kb + lane (grid.y: chunks of 64 sets).  LDS: rows R[4][P] (jas_rows).
+// One wave per walker (grid.x), lanes = parameter sets kb + lane (grid.y: chunks of 64 sets).  LDS: rows R[4][P] (ke_electron).
 template <bool PBC>
 __global__ __launch_bounds__(64) void k_corr_energy(SysDev S, SlaterState st, JastrowState js, CorrArgs A) {
   extern __shared__ double R[];
@@ -69,32 +61,11 @@ __global__ __launch_bounds__(64) void k_corr_energy(SysDev S, SlaterState st, Ja
   const double* xw = js.x + (size_t)w * N * 3;
   const double irb = 1.0 / S.rcut_b, ira = 1.0 / S.rcut_a;
   double ke = 0.0, g2 = 0.0;
-  for (int e = 0; e < N; ++e) {
-    const int s = e >= S.nup, i = e - s * S.nup, n = s ? S.ndn : S.nup, nmo = S.nmo[s];
-    double r[5];
-    slater_ratios<5>(S, st, s, i, w, st.cache[s] + ((size_t)w * n + i) * 5 * nmo, r, nullptr);
-    const double G0 = r[1] / r[0], G1 = r[2] / r[0], G2 = r[3] / r[0], L = r[4] / r[0];
-    jas_rows<PBC>(S, xw, e, s, xw[3 * e], xw[3 * e + 1], xw[3 * e + 2], P, Pa, ira, irb, R);
-    if (act) {
-      double gx = 0.0, gy = 0.0, gz = 0.0, lp = 0.0;
-      for (int q = 0; q < S.natom * S.na; ++q) {
-        const int p = 2 * q + s;
-        const double c = A.ct[(size_t)p * A.K + k];
-        gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
-      }
-      for (int q = 0; q < 2 * S.nb; ++q) {
-        const int p = Pa + (q >> 1) * 3 + s + (q & 1);
-        const double c = A.ct[(size_t)p * A.K + k];
-        gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
-      }
-      const double lj = lp + gx * gx + gy * gy + gz * gz;
-      const double lap = L + lj + 2.0 * (G0 * gx + G1 * gy + G2 * gz);
+  for (int e = 0; e < N; ++e)
+    ke_electron<PBC>(S, st, xw, w, e, P, Pa, ira, irb, R, A.ct, A.K, k, act, [&](double lap, double tx, double ty, double tz) {
       ke += -0.5 * lap;
-      const double tx = G0 + gx, ty = G1 + gy, tz = G2 + gz;
       g2 += tx * tx + ty * ty + tz * tz;
-    }
-    __syncthreads();
-  }
+    });
   // ECP: every point of the walker in k_ecp_sum's order (spin up then down, segment by segment); row B_p(q) - B_p(r_e)
   double tot = 0.0;
   if (A.has_ecp) {
@@ -105,39 +76,7 @@ __global__ __launch_bounds__(64) void k_corr_energy(SysDev S, SlaterState st, Ja
         for (long pt = o[0]; pt < o[1]; ++pt) {
           const int e = A.pte[sp][pt], s = e >= S.nup;
           const double qx = A.pts[sp][3 * pt], qy = A.pts[sp][3 * pt + 1], qz = A.pts[sp][3 * pt + 2];
-          const double ex = xw[3 * e], ey = xw[3 * e + 1], ez = xw[3 * e + 2];
-          for (int p = lane; p < P; p += 64) R[p] = 0.0;
-          __syncthreads();
-          for (int I = lane; I < S.natom; I += 64) {
-            double d[3];
-            const double rn = dist<PBC>(S, qx - S.atom_xyz[3 * I], qy - S.atom_xyz[3 * I + 1], qz - S.atom_xyz[3 * I + 2], d);
-            const double ro = dist<PBC>(S, ex - S.atom_xyz[3 * I], ey - S.atom_xyz[3 * I + 1], ez - S.atom_xyz[3 * I + 2], d);
-            const RadShared shn = rad_shared<0>(rn, ira), sho = rad_shared<0>(ro, ira);
-            for (int a = 0; a < S.na; ++a) {
-              double vn = 0.0, vo = 0.0, gf, lpl;
-              if (rn < S.rcut_a) rad_fn<0>(S.a_kind[a], S.a_param[a], S.a_aux[a], S.rcut_a, shn, vn, gf, lpl);
-              if (ro < S.rcut_a) rad_fn<0>(S.a_kind[a], S.a_param[a], S.a_aux[a], S.rcut_a, sho, vo, gf, lpl);
-              R[(I * S.na + a) * 2 + s] = vn - vo;
-            }
-          }
-          for (int l = 0; l < S.nb; ++l) {
-            double acc[2] = {0.0, 0.0};
-            for (int j = lane; j < N; j += 64) {
-              if (j == e) continue;
-              double d[3];
-              const double rn = dist<PBC>(S, qx - xw[3 * j], qy - xw[3 * j + 1], qz - xw[3 * j + 2], d);
-              const double ro = dist<PBC>(S, ex - xw[3 * j], ey - xw[3 * j + 1], ez - xw[3 * j + 2], d);
-              double vn = 0.0, vo = 0.0, gf, lpl;
-              if (rn < S.rcut_b) rad_fn<0>(S.b_kind[l], S.b_param[l], S.b_aux[l], S.rcut_b, rad_shared<0>(rn, irb), vn, gf, lpl);
-              if (ro < S.rcut_b) rad_fn<0>(S.b_kind[l], S.b_param[l], S.b_aux[l], S.rcut_b, rad_shared<0>(ro, irb), vo, gf, lpl);
-              acc[j >= S.nup] += vn - vo;
-            }
-            for (int c = 0; c < 2; ++c) {
-              const double t = wave_sum(acc[c]);
-              if (lane == 0) R[Pa + l * 3 + s + c] = t;
-            }
-          }
-          __syncthreads();
+          jas_diff_rows<PBC>(S, xw, e, s, qx, qy, qz, P, Pa, ira, irb, R);
           if (act) {
             double du = 0.0;
             for (int q = 0; q < S.natom * S.na; ++q) { const int p = 2 * q + s; du += A.ct[(size_t)p * A.K + k] * R[p]; }
@@ -162,12 +101,10 @@ extern "C" int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, cons
   if (h->W == 0) FAIL("state not initialised (call pqa_wf_recompute)");
   if (K < 1) FAIL("pqa_correlated: K must be at least 1");
   if (!acoeff || !bcoeff || !logpsi || !en) FAIL("pqa_correlated: acoeff, bcoeff, logpsi and en must not be NULL");
-  if (!h->has_slater || !h->has_j2 || h->has_j3 || h->cplx || h->ndet != 1)
-    FAIL("pqa_correlated: needs a real single-determinant Slater x two-body Jastrow handle (others: set, recompute and evaluate per set)");
+  TRY(linear_jastrow_scope(h, "pqa_correlated"));
   if (h->ecpb_on || h->ecp_wave) FAIL("pqa_correlated: needs the semi-local ECP integrator's thread-per-point pass (evaluate per set)");
   const long W = h->W;
   const int Pa = h->natom * h->na * 2, Pb = h->nb * 3, P = Pa + Pb, K1 = K + 1;
-  if ((size_t)4 * P * sizeof(double) > 64 * 1024) FAIL("pqa_correlated: more Jastrow coefficients than one LDS row block holds");
   // log|Psi| at the handle's own coefficients (as pqa_wf_value: refreshes the basis sums a fused sweep left stale)
   std::vector<double> lg0((size_t)W);
   TRY(pqa_wf_value(h, nullptr, lg0.data()));
@@ -177,11 +114,7 @@ extern "C" int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, cons
   if (Pb) HIPCHK(hipMemcpy(cb.data(), bcoeff, (size_t)K * Pb * sizeof(double), hipMemcpyDefault));
   if (Pa) HIPCHK(hipMemcpy(ca.data() + (size_t)K * Pa, h->d_acoeff, Pa * sizeof(double), hipMemcpyDeviceToHost));
   if (Pb) HIPCHK(hipMemcpy(cb.data() + (size_t)K * Pb, h->d_bcoeff, Pb * sizeof(double), hipMemcpyDeviceToHost));
-  std::vector<double> ct((size_t)P * K);  // [P][K]: acoeff entries, then bcoeff entries
-  for (int k = 0; k < K; ++k) {
-    for (int p = 0; p < Pa; ++p) ct[(size_t)p * K + k] = ca[(size_t)k * Pa + p];
-    for (int p = 0; p < Pb; ++p) ct[(size_t)(Pa + p) * K + k] = cb[(size_t)k * Pb + p];
-  }
+  const std::vector<double> ct = pack_coef_sets(ca.data(), cb.data(), K, Pa, Pb);
   // the Slater-only energy pass, once: the Jastrow switched off and the ECP totals read on the host (restored on every exit)
   struct Flags {
     pqa_handle* h; bool has_jastrow, has_j2; int defer;
@@ -196,7 +129,7 @@ extern "C" int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, cons
   if (has_ecp && (h->ecp_last_tot[0] < 0 || h->ecp_last_tot[1] < 0)) FAIL("pqa_correlated: ECP point totals were left on the device");
   // device scratch (b_out is sized by every user on entry): coefficient rows for k_corr_u, U, the [P][K] matrix, a chunk of outputs
   const size_t nca = (size_t)K1 * std::max(Pa, 1), ncb = (size_t)K1 * std::max(Pb, 1), nu = (size_t)K1 * W, nct = (size_t)P * K;
-  const long Wc = std::max<long>(1, std::min<long>(W, (long)(kCorrScratchBytes / ((size_t)K * 6 * sizeof(double)))));
+  const long Wc = walker_chunk(W, (size_t)K * 6 * sizeof(double));
   TRY(ensure(h, h->b_out, (nca + ncb + nu + nct + (size_t)K * 6 * Wc) * sizeof(double)));
   double* d_ca = (double*)h->b_out.p;
   double* d_cb = d_ca + nca;

@@ -1,0 +1,240 @@
+// Code shared by the fused estimator units (pqa_s2, pqa_symmetry, pqa_sq, pqa_correlated, pqa_overlap, pqa_variance); no other
+// unit includes it.
+//
+// Basis-resolved two-body Jastrow rows: U = sum_p c_p B_p(R) is linear in the coefficients (acoeff entries (atom, k, spin), then
+// bcoeff entries (k, pair)), and so are grad_e U, lap_e U and U(e -> q) - U(e).  jas_rows writes R[m * P + p] = grad_e B_p
+// (m = 0, 1, 2) and lap_e B_p (m = 3) for electron e, jas_diff_rows R[p] = B_p(e -> q) - B_p(e), and a caller contracts them with
+// whichever coefficient set it needs.
+#pragma once
+#include "pqa_internal.hpp"
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// device
+
+template <bool PBC>
+__device__ __forceinline__ double jrow_dist(const SysDev& S, double dx, double dy, double dz, double (&d)[3]) {
+  if (PBC) min_image_j(S, dx, dy, dz);
+  d[0] = dx; d[1] = dy; d[2] = dz;
+  return sqrt(dx * dx + dy * dy + dz * dz);
+}
+
+// Values of the one-body (TWO = false) or two-body (TWO = true) Jastrow basis functions at distance r (irc: 1 / cutoff): f(l, v) for
+// every basis function l in index order, nothing outside the cutoff.
+template <bool TWO, class F>
+__device__ __forceinline__ void jas_basis(const SysDev& S, double r, double irc, F&& f) {
+  const double rc = TWO ? S.rcut_b : S.rcut_a;
+  if (r < rc) {
+    const RadShared sh = rad_shared<0>(r, irc);
+    const int n = TWO ? S.nb : S.na;
+    for (int l = 0; l < n; ++l) {
+      double v, gf, lp;
+      if (TWO) rad_fn<0>(S.b_kind[l], S.b_param[l], S.b_aux[l], rc, sh, v, gf, lp);
+      else rad_fn<0>(S.a_kind[l], S.a_param[l], S.a_aux[l], rc, sh, v, gf, lp);
+      f(l, v);
+    }
+  }
+}
+
+// Rows of electron e (spin s, position ex, ey, ez) of the walker whose coordinates are xw into the LDS block R[4][P].  One wave per
+// walker calls it; the rows are complete for every lane on return.  ira / irb: 1 / rcut_a, 1 / rcut_b.
+template <bool PBC>
+__device__ __forceinline__ void jas_rows(const SysDev& S, const double* xw, int e, int s, double ex, double ey, double ez,
+                                         int P, int Pa, double ira, double irb, double* R) {
+  const int lane = threadIdx.x, N = S.nelec;
+  for (int p = lane; p < 4 * P; p += 64) R[p] = 0.0;
+  __syncthreads();
+  // one-body rows: a lane owns an atom, so its entries (atom, k, spin of e) are written by it alone
+  for (int I = lane; I < S.natom; I += 64) {
+    double d[3];
+    const double rr = jrow_dist<PBC>(S, ex - S.atom_xyz[3 * I], ey - S.atom_xyz[3 * I + 1], ez - S.atom_xyz[3 * I + 2], d);
+    if (rr < S.rcut_a) {
+      const RadShared sh = rad_shared<2>(rr, ira);
+      for (int a = 0; a < S.na; ++a) {
+        double v, gf, lpl;
+        rad_fn<2>(S.a_kind[a], S.a_param[a], S.a_aux[a], S.rcut_a, sh, v, gf, lpl);
+        const int p = (I * S.na + a) * 2 + s;
+        R[p] = gf * d[0]; R[P + p] = gf * d[1]; R[2 * P + p] = gf * d[2]; R[3 * P + p] = lpl;
+      }
+    }
+  }
+  // two-body rows: columns s (same spin pair: 2s) and s + 1 of basis function l, summed over the other electrons
+  for (int l = 0; l < S.nb; ++l) {
+    double acc[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+    for (int j = lane; j < N; j += 64) {
+      if (j == e) continue;
+      double d[3];
+      const double rr = jrow_dist<PBC>(S, ex - xw[3 * j], ey - xw[3 * j + 1], ez - xw[3 * j + 2], d);
+      if (rr < S.rcut_b) {
+        const RadShared sh = rad_shared<2>(rr, irb);
+        double v, gf, lpl;
+        rad_fn<2>(S.b_kind[l], S.b_param[l], S.b_aux[l], S.rcut_b, sh, v, gf, lpl);
+        const int c = j >= S.nup;
+        acc[c][0] += gf * d[0]; acc[c][1] += gf * d[1]; acc[c][2] += gf * d[2]; acc[c][3] += lpl;
+      }
+    }
+    for (int c = 0; c < 2; ++c)
+      for (int m = 0; m < 4; ++m) {
+        const double t = wave_sum(acc[c][m]);
+        if (lane == 0) R[m * P + Pa + l * 3 + s + c] = t;
+      }
+  }
+  __syncthreads();
+}
+
+// Value-only rows R[p] = B_p(q) - B_p(r_e) of moving electron e (spin s) of the walker whose coordinates are xw to q (qx, qy, qz),
+// into the first P doubles of R.  One wave per walker calls it; the rows are complete for every lane on return.
+template <bool PBC>
+__device__ __forceinline__ void jas_diff_rows(const SysDev& S, const double* xw, int e, int s, double qx, double qy, double qz,
+                                              int P, int Pa, double ira, double irb, double* R) {
+  const int lane = threadIdx.x, N = S.nelec;
+  const double ex = xw[3 * e], ey = xw[3 * e + 1], ez = xw[3 * e + 2];
+  for (int p = lane; p < P; p += 64) R[p] = 0.0;
+  __syncthreads();
+  for (int I = lane; I < S.natom; I += 64) {
+    double d[3];
+    const double rn = jrow_dist<PBC>(S, qx - S.atom_xyz[3 * I], qy - S.atom_xyz[3 * I + 1], qz - S.atom_xyz[3 * I + 2], d);
+    const double ro = jrow_dist<PBC>(S, ex - S.atom_xyz[3 * I], ey - S.atom_xyz[3 * I + 1], ez - S.atom_xyz[3 * I + 2], d);
+    const RadShared shn = rad_shared<0>(rn, ira), sho = rad_shared<0>(ro, ira);
+    for (int a = 0; a < S.na; ++a) {
+      double vn = 0.0, vo = 0.0, gf, lpl;
+      if (rn < S.rcut_a) rad_fn<0>(S.a_kind[a], S.a_param[a], S.a_aux[a], S.rcut_a, shn, vn, gf, lpl);
+      if (ro < S.rcut_a) rad_fn<0>(S.a_kind[a], S.a_param[a], S.a_aux[a], S.rcut_a, sho, vo, gf, lpl);
+      R[(I * S.na + a) * 2 + s] = vn - vo;
+    }
+  }
+  for (int l = 0; l < S.nb; ++l) {
+    double acc[2] = {0.0, 0.0};
+    for (int j = lane; j < N; j += 64) {
+      if (j == e) continue;
+      double d[3];
+      const double rn = jrow_dist<PBC>(S, qx - xw[3 * j], qy - xw[3 * j + 1], qz - xw[3 * j + 2], d);
+      const double ro = jrow_dist<PBC>(S, ex - xw[3 * j], ey - xw[3 * j + 1], ez - xw[3 * j + 2], d);
+      double vn = 0.0, vo = 0.0, gf, lpl;
+      if (rn < S.rcut_b) rad_fn<0>(S.b_kind[l], S.b_param[l], S.b_aux[l], S.rcut_b, rad_shared<0>(rn, irb), vn, gf, lpl);
+      if (ro < S.rcut_b) rad_fn<0>(S.b_kind[l], S.b_param[l], S.b_aux[l], S.rcut_b, rad_shared<0>(ro, irb), vo, gf, lpl);
+      acc[j >= S.nup] += vn - vo;
+    }
+    for (int c = 0; c < 2; ++c) {
+      const double t = wave_sum(acc[c]);
+      if (lane == 0) R[Pa + l * 3 + s + c] = t;
+    }
+  }
+  __syncthreads();
+}
+
+// Kinetic terms of electron e of walker w (one wave per walker; LDS R[4][P] for jas_rows).  G = grad D / D and L = lap D / D come
+// from the orbital-row cache; on the lanes with act the rows are contracted with set k of ct [P][K] to g = grad_e U_k,
+// lp = lap_e U_k, and f(lap, tx, ty, tz) receives lap = L + lp + |g|^2 + 2 G . g (the electron's lap Psi / Psi) and t = G + g.
+// k_corr_energy and k_var_ke both form their kinetic energy here, so they hold the same bits.
+template <bool PBC, class F>
+__device__ __forceinline__ void ke_electron(const SysDev& S, const SlaterState& st, const double* xw, long w, int e, int P, int Pa,
+                                            double ira, double irb, double* R, const double* ct, int K, int k, bool act, F&& f) {
+  const int s = e >= S.nup, i = e - s * S.nup, n = s ? S.ndn : S.nup, nmo = S.nmo[s];
+  double r[5];
+  slater_ratios<5>(S, st, s, i, w, st.cache[s] + ((size_t)w * n + i) * 5 * nmo, r, nullptr);
+  const double G0 = r[1] / r[0], G1 = r[2] / r[0], G2 = r[3] / r[0], L = r[4] / r[0];
+  jas_rows<PBC>(S, xw, e, s, xw[3 * e], xw[3 * e + 1], xw[3 * e + 2], P, Pa, ira, irb, R);
+  if (act) {
+    double gx = 0.0, gy = 0.0, gz = 0.0, lp = 0.0;
+    for (int q = 0; q < S.natom * S.na; ++q) {
+      const int p = 2 * q + s;
+      const double c = ct[(size_t)p * K + k];
+      gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
+    }
+    for (int q = 0; q < 2 * S.nb; ++q) {
+      const int p = Pa + (q >> 1) * 3 + s + (q & 1);
+      const double c = ct[(size_t)p * K + k];
+      gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
+    }
+    const double lj = lp + gx * gx + gy * gy + gz * gz;
+    const double lap = L + lj + 2.0 * (G0 * gx + G1 * gy + G2 * gz);
+    f(lap, G0 + gx, G1 + gy, G2 + gz);
+  }
+  __syncthreads();
+}
+
+// One 16 x 16 tile of a product C = A B over k < n on v_mfma_f64_16x16x4_f64.  Lane (i16, kq) = (lane & 15, lane >> 4) supplies
+// a(k) = A[row i16][k] and b(k) = B[k][col i16] for its k = k0 + kq < n (zero beyond n; the row / column bounds are the
+// callbacks'); C[row kq + 4 r][col i16] lands in element r of the result.
+template <class FA, class FB>
+__device__ __forceinline__ d4 mfma_tile(int n, int kq, FA&& a, FB&& b) {
+  d4 c = {0.0, 0.0, 0.0, 0.0};
+  for (int k0 = 0; k0 < n; k0 += 4) {
+    const int k = k0 + kq;
+    const bool kin = k < n;
+    c = __builtin_amdgcn_mfma_f64_16x16x4f64(a(k, kin), b(k, kin), c, 0, 0, 0);
+  }
+  return c;
+}
+
+// Fixed-order sum over the 256 threads of a block (sh: 256 doubles of LDS); every thread gets the total.
+__device__ __forceinline__ double block_sum256(double v, double* sh) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) sh[t] += sh[t + o];
+    __syncthreads();
+  }
+  const double r = sh[0];
+  __syncthreads();
+  return r;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// host
+
+// Per-walker scratch of an estimator is allocated for a walker chunk of at most this many bytes.
+constexpr size_t kChunkScratchBytes = size_t(256) << 20;
+
+inline long walker_chunk(long W, size_t bytes_per_walker) {  // walkers per chunk
+  return std::max<long>(1, std::min<long>(W, (long)(kChunkScratchBytes / std::max<size_t>(bytes_per_walker, 1))));
+}
+
+// The periodic orbital launcher times its tile sizes on large launches and keeps the choice; an estimator's launches are not to
+// change the choices the handle's sweeps made themselves, so the tuning is restored on every exit.
+struct TpTuneGuard {
+  pqa_handle* h;
+  decltype(pqa_handle::tp_tune) saved;
+  explicit TpTuneGuard(pqa_handle* h_) : h(h_) { memcpy(saved, h->tp_tune, sizeof(h->tp_tune)); }
+  ~TpTuneGuard() { memcpy(h->tp_tune, saved, sizeof(h->tp_tune)); }
+};
+
+// Scope of the read-only estimators (pqa_s2, pqa_symmetry): a real, untwisted Slater handle without a three-body factor.
+inline int readonly_scope(pqa_handle* h, const char* fn) {
+  const char* why = !h->has_slater             ? "the handle has no Slater factor"
+                    : (h->cplx || h->twist)     ? "complex orbitals / twisted cell"
+                    : h->has_j3                 ? "three-body Jastrow factor"
+                                                : nullptr;
+  if (why) FAIL(std::string(fn) + ": " + why + " (outside the fused scope: use the protocol route)");
+  return 0;
+}
+
+// Scope of the linear-Jastrow units (pqa_correlated, pqa_variance): a real single-determinant Slater x two-body Jastrow handle whose
+// row block R[4][P] fits the LDS.
+inline int linear_jastrow_scope(pqa_handle* h, const char* fn) {
+  if (!h->has_slater || !h->has_j2 || h->has_j3 || h->cplx || h->ndet != 1)
+    FAIL(std::string(fn) + ": needs a real single-determinant Slater x two-body Jastrow handle (others: set, recompute and evaluate per set)");
+  const int P = h->natom * h->na * 2 + h->nb * 3;
+  if ((size_t)4 * P * sizeof(double) > 64 * 1024) FAIL(std::string(fn) + ": more Jastrow coefficients than one LDS row block holds");
+  return 0;
+}
+
+// The [P][K] coefficient matrix of K sets, acoeff ca [K][Pa] and bcoeff cb [K][Pb]: acoeff entries, then bcoeff entries.
+inline std::vector<double> pack_coef_sets(const double* ca, const double* cb, int K, int Pa, int Pb) {
+  const int P = Pa + Pb;
+  std::vector<double> ct((size_t)P * K);
+  for (int k = 0; k < K; ++k) {
+    for (int p = 0; p < Pa; ++p) ct[(size_t)p * K + k] = ca[(size_t)k * Pa + p];
+    for (int p = 0; p < Pb; ++p) ct[(size_t)(Pa + p) * K + k] = cb[(size_t)k * Pb + p];
+  }
+  return ct;
+}
+
+// Raises kernel fn's dynamic-LDS limit to the 160 KiB of a CU, once per handle.
+inline int raise_lds_limit(pqa_handle* h, const void* fn) {
+  if (std::find(h->wide_attr.begin(), h->wide_attr.end(), fn) != h->wide_attr.end()) return 0;
+  HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  h->wide_attr.push_back(fn);
+  return 0;
+}

@@ -117,15 +117,16 @@ struct pqa_handle {
   int ecp_nchan = 0, ecp_nterm = 0;
   long wrap_W = 0;
   DevBuf b_gauss, b_unif, b_kc, b_en, b_means, b_sign, b_log, b_ju;
-  DevBuf b_s2phi[2], b_s2out;  // pqa_s2 (pqa_s2.hip): orbitals of each spin at the other spin's electrons (a walker chunk), outputs
-  // pqa_symmetry (pqa_symmetry.hip), per walker chunk: transformed coordinates, orbitals of each spin at its transformed electrons,
-  // determinant ratios (sign, log) of each spin; the ratios of every operator.  sym_attr: k_sym_det's dynamic-LDS limit raised (n > 90)
-  DevBuf b_symx, b_symphi[2], b_symdet[2], b_symout;
-  bool sym_attr = false;
+  // value-only orbitals of each spin at a walker chunk of points: pqa_s2 (at the other spin's electrons), pqa_symmetry (at the
+  // spin's transformed electrons)
+  DevBuf b_orbphi[2];
+  DevBuf b_s2out;  // pqa_s2 (pqa_s2.hip): outputs
+  // pqa_symmetry (pqa_symmetry.hip), per walker chunk: transformed coordinates, determinant ratios (sign, log) of each spin; the
+  // ratios of every operator
+  DevBuf b_symx, b_symdet[2], b_symout;
   // pqa_sq (pqa_sq.hip): q vectors and their integer coordinates, per-walker values of a walker chunk, the mean mode's row partials and
-  // running sums.  sq_attr: k_sq<true>'s dynamic-LDS limit raised (phase tables above 64 KiB per walker)
+  // running sums
   DevBuf b_sqq, b_sqout, b_sqpart, b_sqacc;
-  bool sq_attr = false;
   // pqa_overlap_sweeps (pqa_overlap.hip), on the first handle of the call: one sweep's tapes, the old-position drift, acceptance counts,
   // the (K, K, W) weights and the per-sweep overlaps; pinned words the vanished-determinant flags of all K handles come back in
   DevBuf b_ovl;

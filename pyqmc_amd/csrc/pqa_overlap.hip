@@ -14,8 +14,8 @@
 //              had vanished instead gets k_jastrow_update and a rebuild of its Slater state from the moved walkers (the protocol's
 //              fallback: Slater.recompute(configs) then the Jastrow update)
 // After each sweep: every handle's value, then k_ovl_weights (compute_weights, sample_many.py:42-55: psi_i psi_j / rho per walker)
-// and k_ovl_mean (the walker mean, a fixed-order tree).
-#include "pqa_internal.hpp"
+// and k_ovl_mean (the walker mean, a fixed-order tree: block_sum256).
+#include "pqa_estim.hpp"
 
 // the reference's arithmetic, operation by operation: no fused multiply-adds in this unit's own kernels
 #pragma clang fp contract(off)
@@ -142,13 +142,8 @@ __global__ __launch_bounds__(256) void k_ovl_mean(const double* __restrict__ wts
   const double* row = wts + (size_t)blockIdx.x * W;
   double a = 0.0;
   for (long w = threadIdx.x; w < W; w += 256) a += row[w];
-  part[threadIdx.x] = a;
-  __syncthreads();
-  for (int n = 128; n > 0; n >>= 1) {
-    if ((int)threadIdx.x < n) part[threadIdx.x] += part[threadIdx.x + n];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = part[0] / (double)W;
+  a = block_sum256(a, part);
+  if (threadIdx.x == 0) out[blockIdx.x] = a / (double)W;
 }
 
 // every handle runs on the first handle's stream for the call's duration (launch_orb and the helpers launch on h->stream)

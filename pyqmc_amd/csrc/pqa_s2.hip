@@ -14,7 +14,7 @@
 //
 // Work per walker: one value-only orbital pass per spin at the OTHER spin's electrons (launch_orb, chunked over walkers), the
 // two rho products per 16x16 tile of (i, j) on v_mfma_f64_16x16x4_f64, O(N^2) Jastrow pairs, one wave reduction.
-#include "pqa_internal.hpp"
+#include "pqa_estim.hpp"
 
 namespace {
 
@@ -43,31 +43,19 @@ __global__ __launch_bounds__(64) void k_s2(SysDev S, SlaterState st, JastrowStat
         if (k == e) continue;
         double dx = ex - xs[3 * k], dy = ey - xs[3 * k + 1], dz = ez - xs[3 * k + 2];
         if (PBC) min_image_j(S, dx, dy, dz);
-        const double r = sqrt(dx * dx + dy * dy + dz * dz);
-        if (r < S.rcut_b) {
-          const RadShared sh = rad_shared<0>(r, irb);
-          const int c = k >= nu;  // channel column of an up electron at x: 0 uu / 1 ud; of a down one: 1 ud / 2 dd
-          for (int l = 0; l < S.nb; ++l) {
-            double v, gf, lp;
-            rad_fn<0>(S.b_kind[l], S.b_param[l], S.b_aux[l], S.rcut_b, sh, v, gf, lp);
-            u += S.bcoeff[l * 3 + c] * v;
-            d += S.bcoeff[l * 3 + 1 + c] * v;
-          }
-        }
+        const int c = k >= nu;  // channel column of an up electron at x: 0 uu / 1 ud; of a down one: 1 ud / 2 dd
+        jas_basis<true>(S, sqrt(dx * dx + dy * dy + dz * dz), irb, [&](int l, double v) {
+          u += S.bcoeff[l * 3 + c] * v;
+          d += S.bcoeff[l * 3 + 1 + c] * v;
+        });
       }
       for (int I = 0; I < S.natom; ++I) {
         double dx = ex - S.atom_xyz[3 * I], dy = ey - S.atom_xyz[3 * I + 1], dz = ez - S.atom_xyz[3 * I + 2];
         if (PBC) min_image_j(S, dx, dy, dz);
-        const double r = sqrt(dx * dx + dy * dy + dz * dz);
-        if (r < S.rcut_a) {
-          const RadShared sh = rad_shared<0>(r, ira);
-          for (int k = 0; k < S.na; ++k) {
-            double v, gf, lp;
-            rad_fn<0>(S.a_kind[k], S.a_param[k], S.a_aux[k], S.rcut_a, sh, v, gf, lp);
-            u += S.acoeff[(I * S.na + k) * 2] * v;
-            d += S.acoeff[(I * S.na + k) * 2 + 1] * v;
-          }
-        }
+        jas_basis<false>(S, sqrt(dx * dx + dy * dy + dz * dz), ira, [&](int k, double v) {
+          u += S.acoeff[(I * S.na + k) * 2] * v;
+          d += S.acoeff[(I * S.na + k) * 2 + 1] * v;
+        });
       }
       gu[e] = u;
       gd[e] = d;
@@ -101,24 +89,13 @@ __global__ __launch_bounds__(64) void k_s2(SysDev S, SlaterState st, JastrowStat
         const double wD = D > 1 ? det_weight(S, st, w, Dd, ref) : 1.0;
         const double* Ta = Tu + (size_t)a * nu * nu;
         const int* oa = S.det_occ[0] + (size_t)a * nu;
-        d4 cu = {0.0, 0.0, 0.0, 0.0};
-        for (int k0 = 0; k0 < nu; k0 += 4) {  // rho_up(i, j) = sum_k T_up[i][k] phi_up_{occ[k]}(r_j)
-          const int k = k0 + kq;
-          const bool kin = k < nu;
-          const double av = (ia < nu && kin) ? Ta[(size_t)ia * nu + k] : 0.0;
-          const double bv = (ja < nd && kin) ? Pu[(size_t)ja * nmu + oa[k]] : 0.0;
-          cu = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, cu, 0, 0, 0);
-        }
+        // rho_up(i, j) = sum_k T_up[i][k] phi_up_{occ[k]}(r_j),  rho_dn(j, i) = sum_k phi_dn_{occ[k]}(r_i) T_dn[j][k]
+        const d4 cu = mfma_tile(nu, kq, [&](int k, bool kin) { return (ia < nu && kin) ? Ta[(size_t)ia * nu + k] : 0.0; },
+                                [&](int k, bool kin) { return (ja < nd && kin) ? Pu[(size_t)ja * nmu + oa[k]] : 0.0; });
         const double* Tb = Td + (size_t)b * nd * nd;
         const int* ob = S.det_occ[1] + (size_t)b * nd;
-        d4 cd = {0.0, 0.0, 0.0, 0.0};
-        for (int k0 = 0; k0 < nd; k0 += 4) {  // rho_dn(j, i) = sum_k phi_dn_{occ[k]}(r_i) T_dn[j][k]
-          const int k = k0 + kq;
-          const bool kin = k < nd;
-          const double av = (ia < nu && kin) ? Pd[(size_t)ia * nmd + ob[k]] : 0.0;
-          const double bv = (ja < nd && kin) ? Tb[(size_t)ja * nd + k] : 0.0;
-          cd = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, cd, 0, 0, 0);
-        }
+        const d4 cd = mfma_tile(nd, kq, [&](int k, bool kin) { return (ia < nu && kin) ? Pd[(size_t)ia * nmd + ob[k]] : 0.0; },
+                                [&](int k, bool kin) { return (ja < nd && kin) ? Tb[(size_t)ja * nd + k] : 0.0; });
 #pragma unroll
         for (int r = 0; r < 4; ++r) num[r] += wD * cu[r] * cd[r];
       }
@@ -132,15 +109,9 @@ __global__ __launch_bounds__(64) void k_s2(SysDev S, SlaterState st, JastrowStat
           double dj = gu[je] - gu[i] + gd[i] - gd[je];
           double dx = xs[3 * i] - xs[3 * je], dy = xs[3 * i + 1] - xs[3 * je + 1], dz = xs[3 * i + 2] - xs[3 * je + 2];
           if (PBC) min_image_j(S, dx, dy, dz);
-          const double rij = sqrt(dx * dx + dy * dy + dz * dz);
-          if (rij < S.rcut_b) {
-            const RadShared sh = rad_shared<0>(rij, 1.0 / S.rcut_b);
-            for (int l = 0; l < S.nb; ++l) {
-              double v, gf, lp;
-              rad_fn<0>(S.b_kind[l], S.b_param[l], S.b_aux[l], S.rcut_b, sh, v, gf, lp);
-              dj -= (S.bcoeff[l * 3] + S.bcoeff[l * 3 + 2] - 2.0 * S.bcoeff[l * 3 + 1]) * v;
-            }
-          }
+          jas_basis<true>(S, sqrt(dx * dx + dy * dy + dz * dz), 1.0 / S.rcut_b, [&](int l, double v) {
+            dj -= (S.bcoeff[l * 3] + S.bcoeff[l * 3 + 2] - 2.0 * S.bcoeff[l * 3 + 1]) * v;
+          });
           ratio *= exp(dj);
         }
         tot += ratio;
@@ -152,15 +123,6 @@ __global__ __launch_bounds__(64) void k_s2(SysDev S, SlaterState st, JastrowStat
   if (lane == 0) s2[w] = base - tot;
 }
 
-// scratch of the orbital values: at most this many bytes, the walkers taken in chunks that fit
-constexpr size_t kS2ScratchBytes = size_t(256) << 20;
-
-long s2_chunk(const pqa_handle* h) {  // walkers per chunk
-
-  const size_t per = (size_t)(h->ndn * h->nmo[0] + h->nup * h->nmo[1]) * sizeof(double);
-  return std::max<long>(1, std::min<long>(h->W, (long)(kS2ScratchBytes / std::max<size_t>(per, 1))));
-}
-
 }  // namespace
 
 extern "C" int pqa_s2(pqa_handle_t* h, double* s2, double* ratios) {
@@ -168,9 +130,7 @@ extern "C" int pqa_s2(pqa_handle_t* h, double* s2, double* ratios) {
   HIPCHK(hipSetDevice(h->device));
   if (h->W == 0) FAIL("pqa_s2: state not initialised (call recompute)");
   if (!s2) FAIL("pqa_s2: s2 is NULL");
-  if (!h->has_slater) FAIL("pqa_s2: the handle has no Slater factor (outside the fused scope: use the protocol route)");
-  if (h->cplx || h->twist) FAIL("pqa_s2: complex orbitals / twisted cell (outside the fused scope: use the protocol route)");
-  if (h->has_j3) FAIL("pqa_s2: three-body Jastrow factor (outside the fused scope: use the protocol route)");
+  TRY(readonly_scope(h, "pqa_s2"));
   const long W = h->W;
   const int nu = h->nup, nd = h->ndn, N = h->N;
   const double sz = 0.5 * (nu - nd), base = sz * (sz + 1.0) + nd;
@@ -179,19 +139,16 @@ extern "C" int pqa_s2(pqa_handle_t* h, double* s2, double* ratios) {
     HIPCHK(hipMemcpy(s2, v.data(), (size_t)W * sizeof(double), hipMemcpyDefault));
     return 0;
   }
-  const long Wc = s2_chunk(h);
-  DevBuf& bu = h->b_s2phi[0];
-  DevBuf& bd = h->b_s2phi[1];
+  const long Wc = walker_chunk(W, (size_t)(nd * h->nmo[0] + nu * h->nmo[1]) * sizeof(double));  // (orbital scratch)
+  DevBuf& bu = h->b_orbphi[0];
+  DevBuf& bd = h->b_orbphi[1];
   TRY(ensure(h, bu, (size_t)Wc * nd * h->nmo[0] * sizeof(double)));
   TRY(ensure(h, bd, (size_t)Wc * nu * h->nmo[1] * sizeof(double)));
   const size_t nrat = ratios ? (size_t)W * nu * nd : 0;
   TRY(ensure(h, h->b_s2out, ((size_t)W + nrat) * sizeof(double)));
   double* d_s2 = (double*)h->b_s2out.p;
   double* d_rat = ratios ? d_s2 + W : nullptr;
-  // the periodic orbital launcher times its tile sizes on large launches and keeps the choice: the handle's sweeps are to see
-  // the choices they made themselves
-  pqa_handle::TpTune tune_saved[2][48];
-  memcpy(tune_saved, h->tp_tune, sizeof tune_saved);
+  TpTuneGuard tune(h);
   const size_t lds = (size_t)5 * N * sizeof(double);
   int rc = 0;
   for (long w0 = 0; w0 < W && !rc; w0 += Wc) {
@@ -210,7 +167,6 @@ extern "C" int pqa_s2(pqa_handle_t* h, double* s2, double* ratios) {
                          (const double*)bd.p, w0, (int)h->has_j2, base, d_s2, d_rat);
     rc = check_launch(h, "k_s2");
   }
-  memcpy(h->tp_tune, tune_saved, sizeof tune_saved);
   if (rc) return rc;
   if (ratios) HIPCHK(hipMemcpyAsync(ratios, d_rat, nrat * sizeof(double), hipMemcpyDefault, h->stream));
   return copy_out(h, s2, d_s2, (size_t)W * sizeof(double));

@@ -21,11 +21,10 @@
 // Per-walker mode copies each chunk out.  Mean mode sums every chunk on the device in a fixed order (k_sq_rows: column sums over
 // fixed row slices; k_sq_fold: the slices in order, plus the previous chunks' running sum) and divides by W at the last chunk:
 // no atomics, so two calls give the same bits.
-#include "pqa_internal.hpp"
+#include "pqa_estim.hpp"
 
 namespace {
 
-constexpr size_t kSqScratchBytes = size_t(256) << 20;  // per-walker values of one walker chunk: at most this many bytes
 constexpr size_t kSqLdsBlock = 40 << 10;              // LDS per block WB is sized for (four blocks of four waves per CU)
 constexpr size_t kSqLdsMax = 160 << 10;               // LDS per CU: a larger phase table takes the direct path
 constexpr int kSqThreads = 256;
@@ -165,7 +164,7 @@ extern "C" int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, 
   if (rec)
     for (int k = 0; k < 9; ++k) A.recip[k] = recip[k];
 
-  const long Wc = std::max<long>(1, std::min<long>(W, (long)(kSqScratchBytes / ((size_t)2 * Q * sizeof(double)))));
+  const long Wc = walker_chunk(W, (size_t)2 * Q * sizeof(double));  // (the per-walker values of a chunk)
   // walkers per block: as many as fit kSqLdsBlock (at most 64), fewer while a chunk would give fewer than 2048 blocks
   int wbs = 6;
   while (wbs > 0 && ((size_t)1 << wbs) * tab > kSqLdsBlock) --wbs;
@@ -173,11 +172,7 @@ extern "C" int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, 
   A.wbs = wbs;
   const int WB = 1 << wbs;
   const size_t lds = (size_t)WB * tab;
-  if (lds > 64 * 1024 && !h->sq_attr) {
-    HIPCHK(hipFuncSetAttribute((const void*)k_sq<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSqLdsMax));
-    HIPCHK(hipFuncSetAttribute((const void*)k_sq<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSqLdsMax));
-    h->sq_attr = true;
-  }
+  if (lds > 64 * 1024) TRY(raise_lds_limit(h, rec ? (const void*)k_sq<true> : (const void*)k_sq<false>));
 
   TRY(ensure(h, h->b_sqq, (size_t)Q * 3 * (sizeof(double) + sizeof(int))));
   double* d_q = (double*)h->b_sqq.p;

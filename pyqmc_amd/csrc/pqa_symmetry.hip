@@ -18,7 +18,7 @@
 // Work per operator and walker chunk (orbital scratch <= 256 MiB): k_sym_xform writes the transformed coordinates, one value-only
 // orbital pass per spin at that spin's transformed electrons (launch_orb), k_sym_det per (walker, spin, unique determinant),
 // k_sym_comb per walker.
-#include "pqa_internal.hpp"
+#include "pqa_estim.hpp"
 
 namespace {
 
@@ -54,19 +54,14 @@ __global__ __launch_bounds__(64) void k_sym_det(SysDev S, SlaterState st, int s,
   const double* Ta = st.T[s] + ((size_t)w * D + a) * n * n;
   const int* occ = S.det_occ[s] + (size_t)a * n;
   const double* P = phi + (size_t)wl * n * nmo;
-  // MFMA operands as in k_s2: lane (i16, kq) holds A[row i16][k kq] and B[k kq][col i16]; D[row kq + 4 r][col i16] lands in acc[r]
+  // MFMA tiles (mfma_tile): lane (i16, kq) supplies A[row i16][k] and B[k][col i16]; C[row kq + 4 r][col i16] lands in c[r]
   const int i16 = lane & 15, kq = lane >> 4;
   for (int i0 = 0; i0 < n; i0 += 16) {
     for (int j0 = 0; j0 < n; j0 += 16) {
       const int ia = i0 + i16, ja = j0 + i16;
-      d4 c = {0.0, 0.0, 0.0, 0.0};
-      for (int k0 = 0; k0 < n; k0 += 4) {  // B[i][j] = sum_k T[i][k] phi_{occ[k]}(r'_j)
-        const int k = k0 + kq;
-        const bool kin = k < n;
-        const double av = (ia < n && kin) ? Ta[(size_t)ia * n + k] : 0.0;
-        const double bv = (ja < n && kin) ? P[(size_t)ja * nmo + occ[k]] : 0.0;
-        c = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, c, 0, 0, 0);
-      }
+      // B[i][j] = sum_k T[i][k] phi_{occ[k]}(r'_j)
+      const d4 c = mfma_tile(n, kq, [&](int k, bool kin) { return (ia < n && kin) ? Ta[(size_t)ia * n + k] : 0.0; },
+                             [&](int k, bool kin) { return (ja < n && kin) ? P[(size_t)ja * nmo + occ[k]] : 0.0; });
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = i0 + kq + 4 * r;
@@ -144,15 +139,7 @@ __device__ double jas_total_part(const SysDev& S, const double* xs, int lane) {
     for (int I = 0; I < S.natom; ++I) {
       double dx = xs[3 * e] - S.atom_xyz[3 * I], dy = xs[3 * e + 1] - S.atom_xyz[3 * I + 1], dz = xs[3 * e + 2] - S.atom_xyz[3 * I + 2];
       if (PBC) min_image_j(S, dx, dy, dz);
-      const double r = sqrt(dx * dx + dy * dy + dz * dz);
-      if (r < S.rcut_a) {
-        const RadShared sh = rad_shared<0>(r, ira);
-        for (int k = 0; k < S.na; ++k) {
-          double v, gf, lp;
-          rad_fn<0>(S.a_kind[k], S.a_param[k], S.a_aux[k], S.rcut_a, sh, v, gf, lp);
-          u += S.acoeff[(I * S.na + k) * 2 + sp] * v;
-        }
-      }
+      jas_basis<false>(S, sqrt(dx * dx + dy * dy + dz * dz), ira, [&](int k, double v) { u += S.acoeff[(I * S.na + k) * 2 + sp] * v; });
     }
   }
   // pair p -> (i, j), i < j, rows in order: row i starts at st(i) = i (2N - i - 1) / 2
@@ -166,6 +153,7 @@ __device__ double jas_total_part(const SysDev& S, const double* xs, int lane) {
     const int j = (int)(p - (long)i * (2 * N - i - 1) / 2) + i + 1;
     double dx = xs[3 * i] - xs[3 * j], dy = xs[3 * i + 1] - xs[3 * j + 1], dz = xs[3 * i + 2] - xs[3 * j + 2];
     if (PBC) min_image_j(S, dx, dy, dz);
+    // (written out, not through jas_basis: there the compiler contracts min_image_j's periodic projections in another order)
     const double r = sqrt(dx * dx + dy * dy + dz * dz);
     if (r < S.rcut_b) {
       const int c = (i >= nu) + (j >= nu);  // 0 up-up, 1 up-down, 2 down-down
@@ -227,18 +215,6 @@ __global__ __launch_bounds__(64) void k_sym_comb(SysDev S, SlaterState st, Jastr
   if (lane == 0) out[wl] = (ref2 > -INFINITY) ? num / den * exp(ref2 - ref + du) : 0.0;
 }
 
-// scratch of the transformed coordinates, the orbital values and the determinant ratios: at most this many bytes per walker chunk
-constexpr size_t kSymScratchBytes = size_t(256) << 20;
-
-size_t sym_per_walker(const pqa_handle* h) {
-  return ((size_t)3 * h->N + (size_t)h->nup * h->nmo[0] + (size_t)h->ndn * h->nmo[1] + 2 * (size_t)(h->ndet_s[0] + h->ndet_s[1])) *
-         sizeof(double);
-}
-
-long sym_chunk(const pqa_handle* h) {  // walkers per chunk
-  return std::max<long>(1, std::min<long>(h->W, (long)(kSymScratchBytes / std::max<size_t>(sym_per_walker(h), 1))));
-}
-
 }  // namespace
 
 extern "C" int pqa_symmetry(pqa_handle_t* h, int nop, const double* ops, const double* origins, double* ratio) {
@@ -247,33 +223,27 @@ extern "C" int pqa_symmetry(pqa_handle_t* h, int nop, const double* ops, const d
   if (h->W == 0) FAIL("pqa_symmetry: state not initialised (call recompute)");
   if (nop < 0) FAIL("pqa_symmetry: negative operator count");
   if (nop > 0 && (!ops || !ratio)) FAIL("pqa_symmetry: ops / ratio is NULL");
-  if (!h->has_slater) FAIL("pqa_symmetry: the handle has no Slater factor (outside the fused scope: use the protocol route)");
-  if (h->cplx || h->twist) FAIL("pqa_symmetry: complex orbitals / twisted cell (outside the fused scope: use the protocol route)");
-  if (h->has_j3) FAIL("pqa_symmetry: three-body Jastrow factor (outside the fused scope: use the protocol route)");
+  TRY(readonly_scope(h, "pqa_symmetry"));
   if (nop == 0) return 0;
   const long W = h->W;
   const int nu = h->nup, nd = h->ndn, N = h->N;
   const int nel[2] = {nu, nd};
-  const long Wc = sym_chunk(h);
+  // scratch per walker: transformed coordinates, orbital values, determinant ratios
+  const long Wc = walker_chunk(W, ((size_t)3 * N + (size_t)nu * h->nmo[0] + (size_t)nd * h->nmo[1] +
+                                   2 * (size_t)(h->ndet_s[0] + h->ndet_s[1])) * sizeof(double));
   TRY(ensure(h, h->b_symx, (size_t)Wc * N * 3 * sizeof(double)));
   for (int s = 0; s < 2; ++s) {
-    TRY(ensure(h, h->b_symphi[s], (size_t)Wc * std::max(nel[s] * h->nmo[s], 1) * sizeof(double)));
+    TRY(ensure(h, h->b_orbphi[s], (size_t)Wc * std::max(nel[s] * h->nmo[s], 1) * sizeof(double)));
     TRY(ensure(h, h->b_symdet[s], (size_t)2 * Wc * h->ndet_s[s] * sizeof(double)));
   }
   TRY(ensure(h, h->b_symout, (size_t)nop * W * sizeof(double)));
   for (int s = 0; s < 2; ++s) {
     const size_t lds = (size_t)nel[s] * (nel[s] + 1) * sizeof(double);
-    if (lds > 64 * 1024 && !h->sym_attr) {  // (91 electrons of a spin and more: 128 x 129 doubles = 129 KiB of the 160 KiB per CU)
-      HIPCHK(hipFuncSetAttribute((const void*)k_sym_det, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      h->sym_attr = true;
-    }
+    if (lds > 64 * 1024) TRY(raise_lds_limit(h, (const void*)k_sym_det));  // (91 electrons of a spin and more: 128 x 129 doubles = 129 KiB)
   }
   const double* xs = (const double*)h->b_symx.p;
   double* d_out = (double*)h->b_symout.p;
-  // the periodic orbital launcher times its tile sizes on large launches and keeps the choice: the handle's sweeps are to see
-  // the choices they made themselves
-  pqa_handle::TpTune tune_saved[2][48];
-  memcpy(tune_saved, h->tp_tune, sizeof tune_saved);
+  TpTuneGuard tune(h);
   int rc = 0;
   for (int o = 0; o < nop && !rc; ++o) {
     SymOp op;
@@ -292,10 +262,10 @@ extern "C" int pqa_symmetry(pqa_handle_t* h, int nop, const double* ops, const d
         rl[s] = rs[s] + (size_t)wc * h->ndet_s[s];
         if (nel[s] == 0) continue;
         PointAddr pa{xs + 3 * (s ? nu : 0), nel[s], 3L * N};  // the transformed spin-s electrons of the chunk's walkers
-        rc = launch_orb(h, s, pa, wc * nel[s], 1, (double*)h->b_symphi[s].p);
+        rc = launch_orb(h, s, pa, wc * nel[s], 1, (double*)h->b_orbphi[s].p);
         if (rc) break;
         hipLaunchKernelGGL(k_sym_det, dim3((unsigned)(wc * h->ndet_s[s])), dim3(64), (size_t)nel[s] * (nel[s] + 1) * sizeof(double),
-                           h->stream, h->S, h->st, s, (const double*)h->b_symphi[s].p, w0, rs[s], rl[s]);
+                           h->stream, h->S, h->st, s, (const double*)h->b_orbphi[s].p, w0, rs[s], rl[s]);
         rc = check_launch(h, "k_sym_det");
       }
       if (rc) break;
@@ -310,7 +280,6 @@ extern "C" int pqa_symmetry(pqa_handle_t* h, int nop, const double* ops, const d
       rc = check_launch(h, "k_sym_comb");
     }
   }
-  memcpy(h->tp_tune, tune_saved, sizeof tune_saved);
   if (rc) return rc;
   return copy_out(h, ratio, d_out, (size_t)nop * W * sizeof(double));
 }

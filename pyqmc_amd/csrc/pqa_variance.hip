@@ -6,19 +6,17 @@
 //   ke_k          = -1/2 sum_e [lap D/D + 2 grad D/D . grad_e U_k + lap_e U_k + |grad_e U_k|^2]   (k_corr_energy's contraction),
 //   d ke_k / dc_p = -1/2 sum_e [lap_e B_p + 2 t_e . grad_e B_p],
 //   var_k = 1/W sum_w (E_w - Ebar)^2,  dvar_k = 2/W sum_w (E_w - Ebar) d ke_k[w] / dc,  E_w = eoff_w + ke_k[w].
-// k_var_ke runs one wave per walker over the electrons with the rows of pqa_jrows.hpp (grad D / D, lap D / D from the orbital-row
-// cache; no Coulomb, no ECP).  Without the gradient the lanes are sets, as in k_corr_energy.  With it a block is one set: every lane
-// forms that set's contraction in the same order (the same ke bits) and owns the coefficients p = lane + 64 j, accumulated over the
-// electrons in registers.  The per-walker derivatives are written per walker chunk of at most 256 MiB; each chunk is reduced about
-// its own mean m_c (A_c = sum_w d_w, B_c = sum_w (E_w - m_c) d_w) and the chunks are combined as sum_c B_c + (m_c - Ebar) A_c, so no
-// two large sums are subtracted (E_w ~ -100 Ha, var ~ 1 Ha^2).  Every walker reduction is a fixed-order tree: no atomics, and two
-// calls give the same bits.  The handle is only read.
-#include "pqa_internal.hpp"
-#include "pqa_jrows.hpp"
+// k_var_ke runs one wave per walker over the electrons with k_corr_energy's per-electron terms (ke_electron, pqa_estim.hpp: grad D / D
+// and lap D / D from the orbital-row cache, the Jastrow rows; no Coulomb, no ECP), so both kernels form the same ke bits.  Without
+// the gradient the lanes are sets, as in k_corr_energy.  With it a block is one set: every lane forms that set's contraction and
+// owns the coefficients p = lane + 64 j, accumulated over the electrons in registers.  The per-walker derivatives are written per
+// walker chunk of at most 256 MiB; each chunk is reduced about its own mean m_c (A_c = sum_w d_w, B_c = sum_w (E_w - m_c) d_w) and
+// the chunks are combined as sum_c B_c + (m_c - Ebar) A_c, so no two large sums are subtracted (E_w ~ -100 Ha, var ~ 1 Ha^2).
+// Every walker reduction is a fixed-order tree (block_sum256): no atomics, and two calls give the same bits.  The handle is only read.
+#include "pqa_estim.hpp"
 
 namespace {
 
-constexpr size_t kVarScratchBytes = size_t(256) << 20;
 constexpr int kVarWB = 256;  // walkers per partial sum of k_var_dpart
 
 struct VarArgs {
@@ -46,38 +44,17 @@ __global__ __launch_bounds__(64) void k_var_ke(SysDev S, SlaterState st, Jastrow
   double dk[NR];
 #pragma unroll
   for (int j = 0; j < NR; ++j) dk[j] = 0.0;
-  for (int e = 0; e < N; ++e) {
-    const int s = e >= S.nup, i = e - s * S.nup, n = s ? S.ndn : S.nup, nmo = S.nmo[s];
-    double r[5];
-    slater_ratios<5>(S, st, s, i, w, st.cache[s] + ((size_t)w * n + i) * 5 * nmo, r, nullptr);
-    const double G0 = r[1] / r[0], G1 = r[2] / r[0], G2 = r[3] / r[0], L = r[4] / r[0];
-    jas_rows<PBC>(S, xw, e, s, xw[3 * e], xw[3 * e + 1], xw[3 * e + 2], P, Pa, ira, irb, R);
-    if (act) {
-      double gx = 0.0, gy = 0.0, gz = 0.0, lp = 0.0;
-      for (int q = 0; q < S.natom * S.na; ++q) {
-        const int p = 2 * q + s;
-        const double c = A.ct[(size_t)p * A.K + k];
-        gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
-      }
-      for (int q = 0; q < 2 * S.nb; ++q) {
-        const int p = Pa + (q >> 1) * 3 + s + (q & 1);
-        const double c = A.ct[(size_t)p * A.K + k];
-        gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
-      }
-      const double lj = lp + gx * gx + gy * gy + gz * gz;
-      const double lap = L + lj + 2.0 * (G0 * gx + G1 * gy + G2 * gz);
+  for (int e = 0; e < N; ++e)
+    ke_electron<PBC>(S, st, xw, w, e, P, Pa, ira, irb, R, A.ct, A.K, k, act, [&](double lap, double tx, double ty, double tz) {
       ke += -0.5 * lap;
       if (NS > 0) {
-        const double tx = G0 + gx, ty = G1 + gy, tz = G2 + gz;
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
           const int p = lane + 64 * j;
           if (p < P) dk[j] += -0.5 * (R[3 * P + p] + 2.0 * (tx * R[p] + ty * R[P + p] + tz * R[2 * P + p]));
         }
       }
-    }
-    __syncthreads();
-  }
+    });
   if (!act) return;
   if (NS == 0 || lane == 0) A.ke[(size_t)k * A.W + w] = ke;
   if (NS > 0) {
@@ -88,20 +65,6 @@ __global__ __launch_bounds__(64) void k_var_ke(SysDev S, SlaterState st, Jastrow
       if (p < P) d[p] = dk[j];
     }
   }
-}
-
-// Fixed-order sum over the 256 threads of a block (sh: 256 doubles of LDS); every thread gets the total.
-__device__ __forceinline__ double block_sum256(double v, double* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) sh[t] += sh[t + o];
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
 }
 
 // mean[k] = 1/n sum_{w0 <= w < w0 + n} (eoff[w] + ke[k][w]): one block per set.
@@ -204,11 +167,9 @@ extern "C" int pqa_variance(pqa_handle_t* h, int K, const double* acoeff, const 
   if (h->W == 0) FAIL("state not initialised (call pqa_wf_recompute)");
   if (K < 1) FAIL("pqa_variance: K must be at least 1");
   if (!acoeff || !bcoeff || !eoff || !var) FAIL("pqa_variance: acoeff, bcoeff, eoff and var must not be NULL");
-  if (!h->has_slater || !h->has_j2 || h->has_j3 || h->cplx || h->ndet != 1)
-    FAIL("pqa_variance: needs a real single-determinant Slater x two-body Jastrow handle (others: set, recompute and evaluate per set)");
+  TRY(linear_jastrow_scope(h, "pqa_variance"));
   const long W = h->W;
   const int Pa = h->natom * h->na * 2, Pb = h->nb * 3, P = Pa + Pb;
-  if ((size_t)4 * P * sizeof(double) > 64 * 1024) FAIL("pqa_variance: more Jastrow coefficients than one LDS row block holds");
   const bool grad = dvar != nullptr;
   const int ns = !grad ? 0 : P <= 256 ? 4 : P <= 512 ? 8 : P <= 1024 ? 16 : 32;
   TRY(sync_aos(h));  // (the walker-major coordinates and orbital rows the kernel reads)
@@ -216,13 +177,9 @@ extern "C" int pqa_variance(pqa_handle_t* h, int K, const double* acoeff, const 
   HIPCHK(hipStreamSynchronize(h->stream));
   if (Pa) HIPCHK(hipMemcpy(ca.data(), acoeff, ca.size() * sizeof(double), hipMemcpyDefault));
   if (Pb) HIPCHK(hipMemcpy(cb.data(), bcoeff, cb.size() * sizeof(double), hipMemcpyDefault));
-  std::vector<double> ct((size_t)P * K);  // [P][K]: acoeff entries, then bcoeff entries
-  for (int k = 0; k < K; ++k) {
-    for (int p = 0; p < Pa; ++p) ct[(size_t)p * K + k] = ca[(size_t)k * Pa + p];
-    for (int p = 0; p < Pb; ++p) ct[(size_t)(Pa + p) * K + k] = cb[(size_t)k * Pb + p];
-  }
+  const std::vector<double> ct = pack_coef_sets(ca.data(), cb.data(), K, Pa, Pb);
   // walker chunks: only the per-walker derivatives [K][Wc][P] scale with them
-  const long Wc = grad ? std::max<long>(1, std::min<long>(W, (long)(kVarScratchBytes / ((size_t)K * P * sizeof(double))))) : W;
+  const long Wc = grad ? walker_chunk(W, (size_t)K * P * sizeof(double)) : W;
   const int nc = (int)((W + Wc - 1) / Wc), nwb = (int)((Wc + kVarWB - 1) / kVarWB);
   // device scratch (b_out is sized by every user on entry): [P][K], eoff, ke [K][W], mean [K], var [K], chunk means [nc][K];
   // with the gradient: derivatives [K][Wc][P], partials [K][nwb][2][P], chunk sums [nc][K][2][P], dvar [K][P]

@@ -29,6 +29,7 @@ import numpy as np
 
 from . import sample_many as sm
 from .energy import EnergyAccumulator
+from .wf import linear_jastrow_device
 
 
 def opt_hdf(hdf_file, data, attr, configs, parameters):
@@ -218,25 +219,12 @@ def correlated_compute(wf, configs, params, pgrad_acc, client=None, npartitions=
     return correlated_compute_worker(wf, configs, params, pgrad_acc, ref_wfs)
 
 
-_FUSED_KEYS = {"wf2acoeff", "wf2bcoeff"}
-
-
 def correlated_route(wf, pgrad_acc):
     """``"fused"`` when ``pqa_correlated`` covers this wave function, accumulator and parameter selection, else ``"protocol"``."""
-    from .wf import JastrowSpin, Slater
-
-    f = getattr(wf, "wf_factors", None)
-    if f is None or len(f) != 2 or type(f[0]) is not Slater or type(f[1]) is not JastrowSpin:
-        return "protocol"
-    dev = wf.fused_device()
-    if dev is None or dev.cplx or dev.ndet != 1 or dev.has_j3:
-        return "protocol"
     enacc = getattr(pgrad_acc, "enacc", None)
     if type(enacc) is not EnergyAccumulator or not enacc.use_old_ecp:
         return "protocol"
-    if not set(pgrad_acc.transform.to_opt) <= _FUSED_KEYS:
-        return "protocol"
-    return "fused"
+    return "protocol" if linear_jastrow_device(wf, pgrad_acc.transform.to_opt) is None else "fused"
 
 
 def _weights(psi, ref_wfs):

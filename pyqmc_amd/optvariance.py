@@ -26,7 +26,7 @@ agrees for one or two keys).
 
 import numpy as np
 
-_FUSED_KEYS = {"wf2acoeff", "wf2bcoeff"}
+from .wf import linear_jastrow_device
 
 
 def _keys(wf, params):
@@ -35,18 +35,8 @@ def _keys(wf, params):
 
 def optvariance_route(wf, params=None):
     """``"fused"`` when ``pqa_variance`` covers this wave function and parameter selection, else ``"protocol"``."""
-    from .wf import JastrowSpin, Slater
-
-    f = getattr(wf, "wf_factors", None)
-    if f is None or len(f) != 2 or type(f[0]) is not Slater or type(f[1]) is not JastrowSpin:
-        return "protocol"
-    dev = wf.fused_device()
-    if dev is None or dev.cplx or dev.ndet != 1 or dev.has_j3:
-        return "protocol"
     keys = _keys(wf, params)
-    if not keys or not set(keys) <= _FUSED_KEYS:
-        return "protocol"
-    return "fused"
+    return "fused" if keys and linear_jastrow_device(wf, keys) is not None else "protocol"
 
 
 def flatten(wf, params):

@@ -20,6 +20,7 @@ R^{i<->j} putting up electron i at r_j and down electron j at r_i.  Two routes c
 import numpy as np
 
 from . import _ffi
+from .wf import readonly_device as fused_handle  # (the fused-route predicate, kept under its name here)
 
 
 def device_s2(dev, with_ratios=False):
@@ -29,23 +30,6 @@ def device_s2(dev, with_ratios=False):
     rat = np.empty((dev.W, nu, nd)) if with_ratios else None
     dev.call("pqa_s2", _ffi.ptr(s2), None if rat is None else _ffi.ptr(rat))
     return (s2, rat) if with_ratios else s2
-
-
-def fused_handle(wf):
-    """The device handle ``pqa_s2`` can evaluate ``wf`` on, or None: ``wf`` must be exactly the handle's factors (a Slater
-    factor, plus the two-body Jastrow when the handle has one), real, not twisted, without a three-body factor."""
-    from .wf import JastrowSpin, MultiplyWF, Slater
-
-    factors = wf.wf_factors if isinstance(wf, MultiplyWF) else [wf]
-    kinds = [type(f) for f in factors]
-    if any(k not in (Slater, JastrowSpin) for k in kinds) or len(set(kinds)) != len(kinds) or Slater not in kinds:
-        return None
-    dev = wf.fused_device() if isinstance(wf, MultiplyWF) else getattr(wf, "_dev", None)
-    if dev is None or not hasattr(dev, "vmc_sweeps"):
-        return None
-    if not dev.has_slater or dev.cplx or dev.twisted or dev.has_j3 or dev.has_jastrow != (JastrowSpin in kinds):
-        return None
-    return dev
 
 
 class S2Accumulator:

@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _ffi
 from .configs import enforce_pbc
-from .s2 import fused_handle
+from .wf import readonly_device
 
 
 def device_symmetry(dev, ops, origins=None):
@@ -51,7 +51,7 @@ class SymmetryAccumulator:
         return None
 
     def __call__(self, configs, wf):
-        dev = fused_handle(wf)
+        dev = readonly_device(wf)
         names = list(self.symmetry_operators)
         if dev is not None and dev.W == configs.configs.shape[0]:
             # the handle's resident walkers are `configs` (the drivers fetch them from the device before any host accumulator)

@@ -271,14 +271,19 @@ class DeviceWF:
         out[5] += 1j * a[6]
         return np.moveaxis(out, 0, axis)
 
-    def correlated(self, acoeff, bcoeff, threshold=10.0, rot=None, unif=None, seed=0):
-        """``pqa_correlated``: the resident walkers at K sets of two-body Jastrow coefficients, acoeff (K, natom, na, 2) and
-        bcoeff (K, nb, 3), every set with the same energy draws -> (logpsi (K, W), energy rows (K, 6, W)).  The handle keeps its
-        own coefficients and state."""
+    def _coef_sets(self, acoeff, bcoeff):
+        """K sets of two-body Jastrow coefficients, acoeff (K, natom, na, 2) and bcoeff (K, nb, 3), as float64 -> (a, b, K)."""
         a, b = _ffi.f64(acoeff), _ffi.f64(bcoeff)
         K = a.shape[0]
         if a.shape != (K, self.natom, self.na, 2) or b.shape != (K, self.nb, 3):
             raise ValueError(f"acoeff (K, {self.natom}, {self.na}, 2) and bcoeff (K, {self.nb}, 3) expected, got {a.shape}, {b.shape}")
+        return a, b, K
+
+    def correlated(self, acoeff, bcoeff, threshold=10.0, rot=None, unif=None, seed=0):
+        """``pqa_correlated``: the resident walkers at K sets of two-body Jastrow coefficients, acoeff (K, natom, na, 2) and
+        bcoeff (K, nb, 3), every set with the same energy draws -> (logpsi (K, W), energy rows (K, 6, W)).  The handle keeps its
+        own coefficients and state."""
+        a, b, K = self._coef_sets(acoeff, bcoeff)
         logpsi, en = np.empty((K, self.W)), np.empty((K, 6, self.W))
         rot = None if rot is None else _ffi.f64(rot)
         unif = None if unif is None else _ffi.f64(unif)
@@ -291,10 +296,8 @@ class DeviceWF:
         coefficients, acoeff (K, natom, na, 2) and bcoeff (K, nb, 3), with ``eoff`` (W) the fixed part of the local energy ->
         (var (K,), dvar (K, P) or None, ke (K, W) or None).  ``grad``: d var / dc, acoeff entries then bcoeff entries; ``ke``: the
         kinetic energies.  The handle keeps its own coefficients and state."""
-        a, b, e = _ffi.f64(acoeff), _ffi.f64(bcoeff), _ffi.f64(eoff)
-        K = a.shape[0]
-        if a.shape != (K, self.natom, self.na, 2) or b.shape != (K, self.nb, 3):
-            raise ValueError(f"acoeff (K, {self.natom}, {self.na}, 2) and bcoeff (K, {self.nb}, 3) expected, got {a.shape}, {b.shape}")
+        a, b, K = self._coef_sets(acoeff, bcoeff)
+        e = _ffi.f64(eoff)
         if e.shape != (self.W,):
             raise ValueError(f"eoff ({self.W},) expected, got {e.shape}")
         var = np.empty(K)
@@ -1087,6 +1090,38 @@ class MultiplyWF:
             for j in range(i + 1, len(g)):
                 cross += np.sum(g[i] * g[j], axis=0)
         return np.sum(g, axis=0), np.sum(l, axis=0) + 2 * cross
+
+
+def readonly_device(wf):
+    """The device handle the read-only fused estimators (``pqa_s2``, ``pqa_symmetry``) can evaluate ``wf`` on, or None: ``wf`` must
+    be exactly the handle's factors (a Slater factor, plus the two-body Jastrow when the handle has one), real, not twisted, without
+    a three-body factor."""
+    factors = wf.wf_factors if isinstance(wf, MultiplyWF) else [wf]
+    kinds = [type(f) for f in factors]
+    if any(k not in (Slater, JastrowSpin) for k in kinds) or len(set(kinds)) != len(kinds) or Slater not in kinds:
+        return None
+    dev = wf.fused_device() if isinstance(wf, MultiplyWF) else getattr(wf, "_dev", None)
+    if dev is None or not hasattr(dev, "vmc_sweeps"):
+        return None
+    if not dev.has_slater or dev.cplx or dev.twisted or dev.has_j3 or dev.has_jastrow != (JastrowSpin in kinds):
+        return None
+    return dev
+
+
+LINEAR_JASTROW_KEYS = {"wf2acoeff", "wf2bcoeff"}  # the parameters the linear-Jastrow entry points vary
+
+
+def linear_jastrow_device(wf, keys):
+    """The device handle the linear-Jastrow entry points (``pqa_correlated``, ``pqa_variance``) can evaluate ``wf`` on while the
+    parameters ``keys`` vary, or None: ``wf`` must be Slater x JastrowSpin on one handle, real, with one determinant and no three-body
+    factor, and ``keys`` within ``LINEAR_JASTROW_KEYS``."""
+    f = getattr(wf, "wf_factors", None)
+    if f is None or len(f) != 2 or type(f[0]) is not Slater or type(f[1]) is not JastrowSpin:
+        return None
+    dev = wf.fused_device()
+    if dev is None or dev.cplx or dev.ndet != 1 or dev.has_j3:
+        return None
+    return dev if set(keys) <= LINEAR_JASTROW_KEYS else None
 
 
 def _ion_cusp_list(mol, ion_cusp):
