@@ -465,71 +465,54 @@ static int create_impl(pqa_handle* h, const pqa_system_t* sys) {
   HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   HIPCHK(hipEventCreate(&h->ev0));
   HIPCHK(hipEventCreate(&h->ev1));
-  // A/B switches for the schedule variants compared in DESIGN.md sections 3-4 (all default to the measured best;
-  // none of them changes results beyond summation order, tests/test_gpu_parity.py cross-checks the pairs):
-  //   PQA_ORB_TP 16|32|64 point tile of k_orb (periodic: pins the automatic choice), PQA_ORB_WS 0|1 wave-specialised k_orb,
-  //   PQA_ORB_KC5 16|32 AO rows per chunk of the periodic 5-component launch, PQA_ORB_SPLIT_MAX n largest periodic launch whose
-  //   chunk loop is split over two blocks, PQA_LW 0 wave-per-walker sweep | 1 lane-per-walker (default), PQA_LW_KB k electrons per
-  //   Sherman-Morrison block (0: update every row per move; default 4), PQA_LW_GM g thread groups per walker of k_step_lw,
-  //   PQA_ECP_WAVE 1 wave-per-walker ECP accumulation,
-  //   PQA_PROF_STRIDE n event brackets on every n-th orbital launch when profiling is enabled,
-  //   PQA_PRE_GRID g   sub-cells per axis of the near-candidate masks of the periodic pre-pass (default 16, 8 beyond 32 atoms; 0: every candidate tested)
-  //   PQA_PRE_NCUT n   at least n shell cut-off classes in the pre-pass instantiation (5 or 10 are compiled; tests)
-  //   PQA_PBC_NW n words (4 image indices each) per (point, atom) image list of the periodic pre-pass (default from the cell;
-  //   1 forces the direct-test fallback: tests), PQA_TM_PRE 0 T-move ratios by the wave-per-walker loop only;
-  //   round 3 (each documented at its field above): PQA_STEP_PRE 0 k_step_lw for small shards too, PQA_DRAWS_MAX n walker count up to
-  //   which a sweep's random numbers are drawn ahead, PQA_FLUSH_WB8_MAX n 8-walker flush blocks up to n walkers, PQA_ECP_LDS 0 /
-  //   PQA_ECP_POINT_LW 0 first-generation ECP list passes / point kernel, PQA_ECP_ACC_WAVES 1|4 waves per walker in the
-  //   wave-per-walker energy kernels, PQA_ECP_ATOM_MAJOR 0 walker-major ECP lists in periodic cells, PQA_JAS_FOLD 0 Voronoi
-  //   reduction in every periodic Jastrow pair;
-  //   round 4: PQA_STEP_GW 16|32|64 thread groups per walker of k_step_pre, PQA_STEP_PRE_MAX n largest shard that runs it (8192),
-  //   PQA_JAS_MERGE 0 Pade functions one by one instead of the merged rational function (jas_merge_tables),
-  //   PQA_ORB_KC5 / PQA_ORB_KC1 16|32 AO rows per chunk of the periodic 5-component / value-only orbital launches.
-  //   round 5: PQA_RES 0|1 resident sweep off / forced (default: by shard size, pqa_res.hip res_eligible), PQA_RES_MIN / PQA_RES_MAX walker
-  //   window of the automatic choice, PQA_RES_PBC 0 periodic handles keep the launch-per-move sweep, PQA_RES_ICAP n shorter image lists in
-  //   the periodic resident sweep (tests), PQA_RES_DEBUG 1 prints the tile / LDS plan, PQA_ORB_GENERAL 1 orbitals of handles beyond 64 per
-  //   spin by k_ao + k_mo_rows instead of the windowed k_orb, PQA_RES_CX 0 complex determinants keep the launch-per-move sweep, PQA_WW 0|1
-  //   wave-per-walker sweep in one launch off / forced (default: up to 4096 walkers), PQA_ECP_DEFER 0
-  //   the ECP point totals are read back at every evaluation, PQA_EN_OVERLAP 0 the kinetic pass of small shards stays in line.
+  // Environment switches.  Each pins one of two routes that the handle otherwise picks from the system and the shard size, so that
+  // a test can compare them (results agree up to summation order, bitwise where the test says so).  Read here unless noted;
+  // the last column names the tests/test_gpu_*.py files that set the switch:
+  //   PQA_RES 0|1           resident sweeps off / forced (default: res_eligible, r8_eligible)               fullsize, parity, pbc
+  //   PQA_R8 0|1            k_sweep_r8 off / forced for open-boundary real handles                          fullsize, parity
+  //   PQA_WW 0|1            one-launch wave-per-walker sweep off / forced (default: up to ww_max walkers)   fullsize
+  //   PQA_LW 0              wave-per-walker kernels instead of the lane-per-walker fused sweep              parity, pbc
+  //   PQA_LW_KB k           electrons per Sherman-Morrison block (0: every row on every move)               parity; bench.py reads it
+  //   PQA_LW_GM g           thread groups per walker of the move kernels (0: automatic)                     jastrow_merge
+  //   PQA_STEP_PRE 0        k_step_lw for small shards too, instead of k_step_pre                           parity, fullsize, jastrow_merge
+  //   PQA_ECP_LDS 0         first-generation ECP list passes (k_ecp_count / k_ecp_fill)                     parity
+  //   PQA_ECP_POINT_LW 0    k_ecp_point on the planes instead of k_ecp_point_lw                             parity, pbc
+  //   PQA_ECP_WAVE 1        wave-per-walker ECP accumulation                                                parity
+  //   PQA_ECP_ACC_WAVES 1|4 waves per walker of k_ecp_accum / k_kinetic_coulomb                             parity
+  //   PQA_ECP_DEFER 0       ECP point totals read back at every evaluation                                  parity
+  //   PQA_ORB_TP 16|32|64   point tile of k_orb (periodic: pins the automatic choice)                       pbc
+  //   PQA_ORB_WS 0|1        phase-alternating / wave-specialised k_orb                                      parity
+  //   PQA_ORB_GENERAL 1     orbitals beyond 64 per spin by k_ao + k_mo_rows instead of the windowed k_orb   parity
+  //   PQA_JAS_MERGE 0       Pade functions one by one instead of the merged rational function               jastrow_merge
+  //   PQA_JAS_FOLD 0        Voronoi reduction in every periodic Jastrow pair                                pbc
+  //   PQA_RADTAB 0          primitive sums instead of radial tables (build_radial_tables)                   parity
+  //   PQA_PRE_GRID g        sub-cells per axis of the pre-pass candidate masks (0: all tested; near_masks)  pbc
+  //   PQA_PRE_NCUT n        at least n shell cut-off classes in the pre-pass instantiation (below)          pbc
+  //   PQA_PBC_NW n          words per (point, atom) pre-pass image list (below; 1: direct tests)            pbc
+  //   PQA_RES_ICAP n        shorter image lists in the periodic resident sweep (pqa_res.hip)                fullsize
+  // Diagnostics: PQA_RES_DEBUG 1|2 prints the resident sweeps' tile / LDS plans (pqa_res.hip, pqa_res8.hip) and the radial-table
+  // fit error; PQA_R8_STAGGER and PQA_R8_ABL set fields of k_sweep_r8's table (pqa_res8.hip; PQA_R8_ABL: timing builds only).
   if (const char* tp = getenv("PQA_ORB_TP")) h->orb_tp = atoi(tp);
-  if (const char* sm = getenv("PQA_ORB_SPLIT_MAX")) h->orb_split_max = atol(sm);
-  if (const char* kc = getenv("PQA_ORB_KC5")) h->orb_kc5 = atoi(kc);
-  if (const char* kc = getenv("PQA_ORB_KC1")) h->orb_kc1 = atoi(kc);
-  if (const char* ps = getenv("PQA_PROF_STRIDE")) h->prof_stride = (unsigned)std::max(1, atoi(ps));
   if (const char* lw = getenv("PQA_LW")) h->lw_mode = atoi(lw);
   if (const char* rs = getenv("PQA_RES")) h->res_mode = atoi(rs);
   if (const char* rs = getenv("PQA_R8")) h->r8_mode = atoi(rs);
-  if (const char* rs = getenv("PQA_RES_PBC")) h->res_pbc = atoi(rs);
-  if (const char* rs = getenv("PQA_RES_CX")) h->res_cx = atoi(rs);
   if (const char* rs = getenv("PQA_WW")) h->ww_mode = atoi(rs);
   if (const char* rs = getenv("PQA_ECP_DEFER")) h->ecp_defer = atoi(rs);
-  if (const char* rs = getenv("PQA_EN_OVERLAP")) h->en_overlap = atoi(rs);
-  if (const char* rs = getenv("PQA_DRAWS_AHEAD")) h->draws_ahead_on = atoi(rs) != 0;
-  if (const char* rs = getenv("PQA_RES_MIN")) h->res_min = atol(rs);
-  if (const char* rs = getenv("PQA_RES_MAX")) h->res_max = atol(rs);
   if (const char* ws = getenv("PQA_ORB_WS")) h->orb_ws = atoi(ws);
-  if (const char* wd = getenv("PQA_ORB_WIDE")) h->orb_wide = atoi(wd);
-  if (const char* wm = getenv("PQA_ORB_WIDE_MAX")) h->orb_wide_max = atol(wm);
   if (const char* kb = getenv("PQA_LW_KB")) h->lw_kb = atoi(kb);
   if (const char* gm = getenv("PQA_LW_GM")) h->lw_gm = atoi(gm);
   if (const char* ew = getenv("PQA_ECP_WAVE")) h->ecp_wave = atoi(ew);
   if (const char* ep = getenv("PQA_ECP_POINT_LW")) h->ecp_point_lw = atoi(ep);
   if (const char* el = getenv("PQA_ECP_LDS")) h->ecp_lds = atoi(el);
   if (const char* jf = getenv("PQA_JAS_FOLD")) h->jas_fold_allowed = atoi(jf);
-  if (const char* am = getenv("PQA_ECP_ATOM_MAJOR")) h->ecp_atom_major = atoi(am);
   if (const char* ea = getenv("PQA_ECP_ACC_WAVES")) h->ecp_acc_waves = atoi(ea);
   if (const char* sp = getenv("PQA_STEP_PRE")) h->step_pre = atoi(sp);
-  if (const char* sp = getenv("PQA_STEP_GW")) h->step_gw = atoi(sp);
-  if (const char* sp = getenv("PQA_STEP_PRE_MAX")) h->step_pre_max = atol(sp);
-  if (const char* dm = getenv("PQA_DRAWS_MAX")) h->draws_max = atol(dm);
-  if (const char* fw = getenv("PQA_FLUSH_WB8_MAX")) h->flush_wb8_max = atol(fw);
   if (const char* sp = getenv("PQA_JAS_MERGE")) h->jas_merge = atoi(sp);
   h->natom = sys->natom; h->nup = sys->nelec_up; h->ndn = sys->nelec_dn; h->N = h->nup + h->ndn;
   h->nao = sys->nao; h->nshell = sys->nshell;
   h->has_slater = sys->has_slater != 0;
   h->cplx = h->has_slater && sys->complex_orbitals != 0;
   h->twist = sys->twisted != 0;
-  if (const char* e = getenv("PQA_TM_PRE")) h->tm_pre = atoi(e) != 0;
   if (h->twist && !(h->cplx && sys->pbc && sys->nL > 0)) FAIL("twisted boundary conditions need pbc, complex_orbitals and the periodic orbital tables");
   if (h->cplx && ((sys->nmo_up | sys->nmo_dn) & 1)) FAIL("complex orbitals: nmo_up / nmo_dn count the real columns [Re C | Im C] and must be even");
   h->has_j2 = sys->na > 0 || sys->nb > 0;

@@ -70,7 +70,7 @@ extern "C" int pqa_dmc_steps(pqa_handle_t* h, double tstep, int nsteps, double b
     if (tp) TRY(ensure(h, h->b_tmu, (size_t)(2 + necp) * NW * sizeof(double)));
     TRY(ensure(h, h->b_rot, nrot * 9 * sizeof(double)));
   }
-  const bool lw = h->lw_mode != 0 && h->has_slater && h->ndet == 1 && !h->has_j3 && (!h->cplx || std::max(h->nup, h->ndn) <= 32);
+  const bool lw = lw_eligible(h);
   LwCtx lc;
   TRY(lw_setup(h, lw, lc));
   const dim3 gw256((unsigned)((W + 255) / 256));
@@ -137,7 +137,7 @@ extern "C" int pqa_dmc_steps(pqa_handle_t* h, double tstep, int nsteps, double b
             TRY(launch_orb(h, s, plain_points(B.pts + 3 * base_s[s], cnt_s[s]), cnt_s[s], 1, (double*)h->b_emo[s].p));
           }
         // ratios of all candidates against the state before the first T-move: one thread per candidate (k_tm_ratio)
-        const bool pre = h->ndet == 1 && !h->has_j3 && !h->cplx && h->tm_pre;
+        const bool pre = h->ndet == 1 && !h->has_j3 && !h->cplx;
         // U_e of every electron at its current position: from the second step of a call on, the energy evaluation that closed the
         // previous step left exactly that ([N][W], k_kinetic_lw) — the walkers have not moved since
         const double* d_uold = nullptr;

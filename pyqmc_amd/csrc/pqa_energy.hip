@@ -29,7 +29,7 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
   if (soa_current) {
     // shards whose ECP passes read their point totals back: the host waits for the counting passes while the kinetic pass runs beside them on
     // the side stream, and has the rest of the evaluation enqueued before the device gets there (the read-back was an idle gap of ~50 us)
-    if (h->necp > 0 && h->ecpb_on == 0 && h->en_overlap && (W <= 16384 || h->en_overlap > 1) && !will_defer) TRY(side_begin());  // (PQA_EN_OVERLAP=2: at every size, A/B)
+    if (h->necp > 0 && h->ecpb_on == 0 && W <= 16384 && !will_defer) TRY(side_begin());
     const dim3 gk((unsigned)((((W + 63) / 64 + 7) / 8) * 8 * h->N)), bk(64);  // see k_kinetic_lw
     const bool kin_quad = W >= 16384 && (W & 3) == 0;  // quad-cooperative row reads (k_kinetic_lw): large shards
     if (h->cplx) {
@@ -64,7 +64,7 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
   } else {
     // small shards with ECPs: the kinetic / Coulomb pass on a side stream beside the ECP passes — both are a few thousand latency-bound waves
     // (50-determinant water molecule, 2 048 walkers: 125 us and 245 us one after the other)
-    if (h->necp > 0 && h->en_overlap && W * h->N <= 32768) TRY(side_begin());
+    if (h->necp > 0 && W * h->N <= 32768) TRY(side_begin());
     {  // four waves per walker while the launch is too small to fill the chip with one
       const bool kc4 = h->ecp_acc_waves == 4 || (h->ecp_acc_waves == 0 && W * h->N <= 32768);
       const size_t st_ = (size_t)(h->cplx ? 2 : 1) * lds_det(h, 5);
@@ -117,7 +117,7 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
     const bool ecp_t = h->ecp_lds && h->necp <= 64 && (long)h->necp * ((h->N + 63) / 64) <= 64 && tab_b <= 32768;
     // (atom-major lists where the orbital kernel gains from them: periodic cells, whose per-lane image walks then have similar
     // lengths within a tile — 2x2x2 diamond VMC +3 % at 32768 walkers; open systems gain nothing and pay a longer scan and sum)
-    const long nseg = (!batched && ecp_t && h->ecp_atom_major && h->S.pbc) ? h->necp : 1, nsw = nseg * W;
+    const long nseg = (!batched && ecp_t && h->S.pbc) ? h->necp : 1, nsw = nseg * W;
     B.nseg = (int)nseg;
     TRY(ensure(h, h->b_ecnt, 2 * nsw * sizeof(int)));
     TRY(ensure(h, h->b_eoff, 2 * (nsw + 1) * sizeof(long)));

@@ -52,7 +52,6 @@ struct pqa_handle {
   int natom = 0, nup = 0, ndn = 0, N = 0, nao = 0, nshell = 0;
   int nmo[2] = {0, 0}, nt[2] = {1, 1}, ndet = 1, ndet_s[2] = {1, 1};
   int na = 0, nb = 0, necp = 0;
-  bool tm_pre = true;   // T-move ratios of all candidates in one thread-per-candidate launch (PQA_TM_PRE=0: wave-per-walker loop only)
   bool aos_stale = false;  // the lane-per-walker planes hold the live state; the walker-major arrays are converted back on demand (sync_aos)
   int pbc_maxcls = PQA_PRE_NCUT;  // most distinct shell cut-offs any atom has (picks the pre-pass instantiation)
   int pbc_nw = 2;  // words per (atom, point) of the sorted image lists k_pbc_prepass writes (4 entries each)
@@ -105,14 +104,9 @@ struct pqa_handle {
   int* d_colmap[2] = {nullptr, nullptr};  // [ndet_s][nmo_s] column of an orbital in a unique determinant, or -1
   int ecp_wave = 0;  // PQA_ECP_WAVE=1: wave-per-walker ECP accumulation (A/B)
   int ecp_point_lw = 1;  // PQA_ECP_POINT_LW=0: k_ecp_point on the planes instead of k_ecp_point_lw (A/B)
-  long flush_wb8_max = 8192;  // PQA_FLUSH_WB8_MAX: walker counts up to which k_flush_lw runs with 8 walkers per block
-  long draws_max = 16384;  // PQA_DRAWS_MAX: walker counts up to which a fused sweep draws its random numbers ahead (k_tile_draws)
-  long step_pre_max = 8192;  // PQA_STEP_PRE_MAX: largest shard (walkers) that runs k_step_pre (8192: 5.90 -> 5.57 ms per (H2O)8 step since the quartet commit; 16384 loses)
-  int step_gw = 0;       // PQA_STEP_GW: thread groups per walker of k_step_pre for shards <= 4096 walkers (0 automatic: 64; 16 / 32 / 64)
   int step_pre = 1;      // PQA_STEP_PRE=0: k_step_lw for small shards too (A/B, bitwise check)
   int ecp_acc_waves = 0; // PQA_ECP_ACC_WAVES: 1 / 4 waves per walker in k_ecp_accum / k_kinetic_coulomb (0: 4 while walkers x electrons <= 32768)
   int jas_fold_allowed = 1;  // PQA_JAS_FOLD=0: Voronoi reduction in every periodic Jastrow pair (A/B, bitwise check)
-  int ecp_atom_major = 1;  // PQA_ECP_ATOM_MAJOR=0: walker-major ECP point lists in periodic cells too (A/B)
   int ecp_lds = 1;       // PQA_ECP_LDS=0: first-generation k_ecp_count / k_ecp_fill (A/B)
   int ecp_nchan = 0, ecp_nterm = 0;
   long wrap_W = 0;
@@ -143,23 +137,14 @@ struct pqa_handle {
   int lw_gm = 0;  // thread groups of the move kernels (PQA_LW_GM; 0 = automatic)  // lane-per-walker SoA mirrors (pqa_lw.hpp)
   DevBuf b_rot, b_eunif, b_elocal, b_ecnt, b_eoff, b_epts[2], b_ewgt[2], b_epte[2], b_emo[2], b_ecp;
   int orb_tp = 0;  // 0 = automatic
-  long orb_split_max = 8192;  // largest periodic launch whose chunk loop is split over two blocks (PQA_ORB_SPLIT_MAX)
-  // AO rows per chunk of the PERIODIC 5-component launch: 32 halves the number of (phase 1, barrier, MFMA, barrier)
-  // rounds of a block's latency chain — 2x2x2 diamond supercell +4.5-10 % at every walker count, 8-atom cell +11 % at 8192
-  // walkers, -4 % at 32768 (PQA_ORB_KC5=16 restores the 16-row chunks; the open-system kernel keeps 16: 0.36 vs 0.29 of peak)
-  int orb_kc5 = 0;  // 0: by launch size (launch_orb_pbc_any); PQA_ORB_KC5 16|32 pins it
-  int orb_kc1 = 16;  // AO rows per chunk of the periodic value-only launch (PQA_ORB_KC1 16|32)
   struct TpTune { float ms[2] = {1e30f, 1e30f}; int n[2] = {0, 0}; int choice = 0; };  // periodic k_orb: [0] 32-point, [1] 64-point tiles
   TpTune tp_tune[2][48];  // per chunk table (5 / 1 components) and log2 bucket of the point count
   WideTab wide[2]{};  // lane-group shell lists of the whole-K small-launch kernel (k_orb_wide), per chunk table (64 groups; periodic: 32)
-  int orb_wide = -1;  // PQA_ORB_WIDE: -1 automatic (5-component launches of <= orb_wide_max points), 0 never, 1 whenever the tile fits LDS
-  long orb_wide_max = 8192;  // PQA_ORB_WIDE_MAX
   std::vector<const void*> wide_attr;  // kernels whose dynamic-LDS limit has been raised
   int orb_ws = -1;  // -1 automatic; 1 wave-specialised orbital kernel; 0 phase-alternating k_orb (PQA_ORB_WS)
   // resident sweep (pqa_res.hpp / pqa_res.hip): the whole electron sweep of 16 walkers in one block, one launch per sweep.
-  // PQA_RES: -1 automatic (shards of res_min .. res_max walkers: PQA_RES_MIN / PQA_RES_MAX), 0 never, 1 whenever the system is in scope
+  // PQA_RES: -1 automatic (by shard size, res_eligible), 0 never, 1 whenever the system is in scope
   int res_mode = -1;
-  long res_min = 1, res_max = 1L << 40;
   bool res_ready = false, res_ok = false;
   // dense mode: the tile holds the AOs in their own order (rows padded to x4 only) with its own coefficient copy d_cres[s] [rows4][ldc] —
   // for bases whose chunk-padded rows do not fit one LDS tile (the 2x2x2 diamond cell: 208 AOs, 224 padded rows)
@@ -180,8 +165,6 @@ struct pqa_handle {
   double r8_util = 0.0;
   bool r8_xaos_next = false;  // the next k_sweep_r8 launch also writes the walker-major coordinates (js.x)
   bool jsx_current = false;   // ... and did: energy_dev skips its transpose of the coordinate planes
-  int res_pbc = 1;  // PQA_RES_PBC=0: periodic handles keep the launch-per-move sweep (A/B)
-  int res_cx = 1;   // PQA_RES_CX=0: complex determinants keep the launch-per-move sweep (A/B)
   // wave-per-walker sweep in one launch (pqa_ww.hpp; PQA_WW): -1 by shard size (up to ww_max walkers), 0 off, 1 always.  50-determinant
   // water molecule, VMC step with energy, launches -> one launch: 0.722 -> 0.663 ms at 1 024 walkers, 0.884 -> 0.801 at 2 048, 1.428 -> 1.382 at 4 096, 2.25 -> 2.38 at 8 192
   // ECP point totals left on the device (pqa_energy.hip: small shards on the k_ecp_accum path; PQA_ECP_DEFER=0 reads them every time)
@@ -190,12 +173,11 @@ struct pqa_handle {
   int ecp_last_nseg = 1;           // ... and the segments per walker of those lists (EcpBuf::nseg)
   long* pin_tot = nullptr;  // pinned host words the scan kernels write the ECP point totals to (device-visible: hipHostMallocMapped)
   int ecp_defer = 1;
-  int en_overlap = 1;  // kinetic / Coulomb pass of small wave-per-walker shards on a side stream beside the ECP passes (PQA_EN_OVERLAP=0: in line)
   // the NEXT step's sweep draws (k_tile_draws) generated beside the energy pass of the current step: second tape set, its stream and events
   DevBuf b_gauss_b, b_unif_b;
   hipStream_t draw_stream = nullptr;
   hipEvent_t draw_ev[2] = {nullptr, nullptr};
-  bool draw_ahead_valid = false, draws_on_device = false, draws_ahead_on = true;  // (PQA_DRAWS_AHEAD=0: A/B)  // draws_on_device: the last sweep took its draws from k_tile_draws
+  bool draw_ahead_valid = false, draws_on_device = false;  // draws_on_device: the last sweep took its draws from k_tile_draws
   uint32_t draw_ahead_step = 0;
   uint64_t draw_ahead_seed = 0;
   long draw_ahead_W = 0;
@@ -233,11 +215,12 @@ struct pqa_handle {
   long prof2_launches = 0;
   double prof2_ms = 0.0;
   size_t prof_used = 0;
-  unsigned prof_tick = 0, prof2_tick = 0;  // the event pairs bracket every 4th eligible launch (PQA_PROF_STRIDE)
-  unsigned prof_stride = 4;
+  unsigned prof_tick = 0;  // the event pairs bracket every prof_stride-th eligible launch
   long prof_launches = 0;
   double prof_ms = 0.0, prof_pc = 0.0;
 };
+// profiling: event pairs bracket a 1-in-prof_stride sample of the eligible launches (an event pair costs ~2 us of stream time)
+static constexpr unsigned prof_stride = 4;
 
 #define HIPCHK(call)                                                                                     \
   do {                                                                                                   \
@@ -324,6 +307,10 @@ static inline size_t lds_det(const pqa_handle* h, int ncomp) {
 struct LwCtx {
   int Gm = 1, KB = 1, nmax = 1;
 };
+// the lane-per-walker fused sweep (pqa_lw.hpp) covers the handle: one determinant, no three-body Jastrow, complex ones up to 32 per spin
+static inline bool lw_eligible(const pqa_handle* h) {
+  return h->lw_mode != 0 && h->has_slater && h->ndet == 1 && !h->has_j3 && (!h->cplx || std::max(h->nup, h->ndn) <= 32);
+}
 
 // ---- functions defined in one unit and called from others
 // pqa_orb.hip: out[p][ncomp][nmo_spin]; out_sel / slot_stride: two-slot output (ChunkTab::out_sel), else plain rows
@@ -351,7 +338,7 @@ int sweep_res(pqa_handle* h, const MoveBuf& mb);
 int res_refresh_coeff(pqa_handle* h, int s, const double* mo_host);  // (pqa_res.hip: dense coefficient copy follows set_mo)
 // pqa_res8.hip
 static inline int res_rows_alloc(int rows4) { return rows4 + 96; }  // rows of the dense coefficient copies d_cres: zero beyond the basis (k_sweep_r8 contracts six k-steps per trip in every wave)
-bool r8_eligible(pqa_handle* h, long W);
+bool r8_eligible(pqa_handle* h);
 int sweep_r8(pqa_handle* h, const MoveBuf& mb);
 // pqa_sweep_ww.hip
 bool ww_eligible(pqa_handle* h, long W);

@@ -45,7 +45,7 @@ static int launch_orb_impl(pqa_handle* h, int spin, PointAddr pa, long P, int nc
   hipEvent_t e0 = nullptr, e1 = nullptr;
   // account the dominant (move) launches only, and only a 1-in-prof_stride sample of them: an event pair costs ~2 us of
   // stream time, 512 pairs per step were 1.2 ms of a 27 ms step
-  const bool prof = h->profile && ncomp == 5 && (h->prof_tick++ % h->prof_stride) == 0;
+  const bool prof = h->profile && ncomp == 5 && (h->prof_tick++ % prof_stride) == 0;
   if (prof) {
     if (h->prof_used == h->prof_events.size()) {
       hipEvent_t a, b;

@@ -12,9 +12,8 @@ static inline ChunkTab tabx(const pqa_handle* h, int tabi) {  // the chunk table
 }
 // whole-K kernel for small 5-component launches (k_orb_wide, pqa_ao.hpp)
 static inline bool wide_wanted(const pqa_handle* h, int tabi, long P, int ncomp) {
-  if (ncomp != 5 || h->orb_wide == 0 || h->wide[tabi].rows_pad <= 0) return false;
+  if (ncomp != 5 || h->wide[tabi].rows_pad <= 0) return false;
   if (wide_lds_bytes(5, h->wide[tabi].rows_pad, h->nshell, (int)h->S.nprim, (h->S.pbc && h->S.nL <= PQA_LS_MAX) ? 5 * h->S.nL : 0) > (size_t)160 * 1024 - 256) return false;
-  if (h->orb_wide == 1) return true;
   // measured (tools/scratch/ab_wide*.sh, 1 MI355X): (H2O)8 step 6.65 -> 4.73 ms at 1024 walkers, 7.64 -> 5.86 at 4096, 9.08 -> 7.84
   // at 8192, even at 16384, slower at 32768 (one 1024-thread block per CU cannot overlap AO and MFMA phases of different
   // tiles); periodic cells (512 threads, two lane-group chains per point like the K-split k_orb): 2x2x2 diamond +5 / +8 / +2.5 %
@@ -23,8 +22,9 @@ static inline bool wide_wanted(const pqa_handle* h, int tabi, long P, int ncomp)
   // walkers, 708k -> 756k at 8192; untwisted 8-atom cell even
   // ... and with the image walk / accumulation as they are now it wins up to 32768 points (C3 +18 % at 24576 walkers, +7 % at
   // 16384 and 32768; C5 +6 % at 12288, +1-2 % at 16384 and 32768): periodic threshold 4 x orb_wide_max
-  if (h->S.pbc) return (h->twist || h->nshell >= 64) && P <= 4 * h->orb_wide_max;
-  return P <= h->orb_wide_max + h->orb_wide_max / 2;
+  constexpr long orb_wide_max = 8192;
+  if (h->S.pbc) return (h->twist || h->nshell >= 64) && P <= 4 * orb_wide_max;
+  return P <= orb_wide_max + orb_wide_max / 2;
 }
 template <int PBCV, int NTH>
 static int launch_orb_wide(pqa_handle* h, const ChunkTab& T, int tabi, int spin, PointAddr pa, long P, double* out) {

@@ -61,7 +61,8 @@ static int launch_orb_pbc(pqa_handle* h, int tabi, int spin, PointAddr pa, long 
     }
   }
   // small launches: split the chunk loop over two blocks per point tile (k_orb: gridDim.y), output accumulated atomically
-  const int nsplit = (P <= h->orb_split_max && T.nchunk >= 4) ? 2 : 1;
+  constexpr long orb_split_max = 8192;  // largest launch (points) whose chunk loop is split
+  const int nsplit = (P <= orb_split_max && T.nchunk >= 4) ? 2 : 1;
   if (nsplit > 1) {
     if (h->out_sel) hipLaunchKernelGGL((k_zero_rows<>), dim3((unsigned)P, (unsigned)((NCOMP * h->nmo[spin] + 255) / 256)), dim3(256), 0, h->stream, out,
                                        NCOMP * h->nmo[spin], h->out_sel, h->out_slot_stride);
@@ -131,16 +132,17 @@ int launch_orb_general(pqa_handle* h, int ncomp, int spin, PointAddr pa, long P,
 int launch_orb_pbc_any(pqa_handle* h, int ncomp, int spin, PointAddr pa, long P, double* out) {
   if (h->pbc_high_l || h->big) return launch_orb_general(h, ncomp, spin, pa, P, out);
   if (ncomp == 5) {
-    // AO rows per chunk of the 5-component launch.  Automatic (PQA_ORB_KC5 unset): 16 for launches of at least 16384 points, 32 below —
+    // AO rows per chunk of the 5-component launch: 32 halves the number of (phase 1, barrier, MFMA, barrier) rounds of a block's latency
+    // chain — 2x2x2 diamond supercell +4.5-10 % at every walker count, 8-atom cell +11 % at 8192 walkers, -4 % at 32768 (the open-system
+    // kernel keeps 16: 0.36 vs 0.29 of peak).  16 for launches of at least 16384 points, 32 below —
     // measured at the end of round 4: whole-ensemble launches (recompute, the DMC step's refresh of accepted T-moves: 131 k points per
     // spin at 4096 walkers) run ~2x faster with 16-row chunks (C5 DMC 33.5 -> 31.4 ms per step at 16384 walkers, 62.8 -> 58.0 at 32768,
     // 10.5 -> 10.05 at 4096; 8-atom cubic cell VMC 12.7 -> 11.9 at 32768), 8192-point move launches of that cell lose 16 % with them.
-    const int kc = (h->orb_kc5 == 16 || h->orb_kc5 == 32) ? h->orb_kc5 : (P >= 16384 ? 16 : 32);
-    return (kc == 32) ? launch_orb_pbc<5, 32>(h, 1, spin, pa, P, out) : launch_orb_pbc<5, 16>(h, 0, spin, pa, P, out);
+    return (P >= 16384) ? launch_orb_pbc<5, 16>(h, 0, spin, pa, P, out) : launch_orb_pbc<5, 32>(h, 1, spin, pa, P, out);
   }
   // value-only launches (ECP quadrature points, T-move candidates): 16-row chunks on the 5-component launch's chunk table
   // (C5 DMC 10.1 -> 9.8 ms per step at 4096 walkers, 31.2 -> 30.3 at 16384; C3 6.62 -> 6.47 at 8192; 2x2x2 VMC + 1.5-2 %; the 8-atom
-  // cubic cell loses 1 %); PQA_ORB_KC1=32 restores the 32-row chunks
-  if (ncomp == 1) return (h->orb_kc1 == 32) ? launch_orb_pbc<1, 32>(h, 1, spin, pa, P, out) : launch_orb_pbc<1, 16>(h, 0, spin, pa, P, out);
+  // cubic cell loses 1 %)
+  if (ncomp == 1) return launch_orb_pbc<1, 16>(h, 0, spin, pa, P, out);
   FAIL("orbital kernel supports ncomp 1 or 5");
 }

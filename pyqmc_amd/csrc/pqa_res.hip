@@ -31,9 +31,9 @@ static int res_setup(pqa_handle* h) {
   if (h->res_mode == 0) return 0;
   if (!h->has_slater || h->ndet != 1 || h->has_j3) return 0;
   // complex determinants: periodic cells (twisted or not), 16 electrons and 16 orbitals per spin — a row of the inverse is 32 doubles
-  if (h->cplx && (!h->S.pbc || h->nup > 16 || h->ndn > 16 || h->res_cx == 0)) return 0;
+  if (h->cplx && (!h->S.pbc || h->nup > 16 || h->ndn > 16)) return 0;
   if (h->twist && !h->cplx) return 0;
-  if (h->S.pbc && (h->S.nL <= 0 || h->pbc_high_l || h->res_pbc == 0 || !h->pbc_lists_ok)) return 0;  // periodic: lattice-summed orbitals, l <= 3 (PQA_RES_PBC=0 keeps the launches)
+  if (h->S.pbc && (h->S.nL <= 0 || h->pbc_high_l || !h->pbc_lists_ok)) return 0;  // periodic: lattice-summed orbitals, l <= 3
   if (h->nup > 32 || h->ndn > 32 || h->nmo[0] > 32 || h->nmo[1] > 32 || h->N > 64 || h->N < 1 || h->natom > 64) return 0;
   int lmax = 0;
   for (int l : h->shell_l) lmax = std::max(lmax, l);
@@ -216,7 +216,6 @@ bool res_eligible(pqa_handle* h, long W) {
   // automatic: measured against the launch-per-move sweep (gpurun_out/res_scan.jsonl, round 5; sweep only): (H2O)8 1.66x at 512
   // walkers, 1.88x at 4096, 1.38x at 16384, 1.06x at 32768, 1.02x at 49152, 0.97x at 65536; H2O (8 electrons: a walker's 32 lanes
   // are mostly idle) 1.2x up to 4096 walkers, 0.49x at 16384.  One round of blocks (16 walkers per CU) always wins.
-  if (W < h->res_min || W > h->res_max) return false;
   // periodic cells (lattice-summed AO phase in the block, round 5; 2x2x2 diamond cell, sweep alone, launches -> resident): 4.10 -> 2.71 ms at
   // 2048 walkers, 4.43 -> 2.74 at 4096, 7.56 -> 5.48 at 8192, 12.5 -> 10.9 at 16384, 17.2 -> 16.4 at 24576, even at 32768
   // (after the image lists were dealt to several threads per pair and the lattice sums went to ds_add_f64: DMC step 13.6 -> 12.1 ms at 4096,

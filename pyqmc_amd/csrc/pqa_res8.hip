@@ -147,14 +147,13 @@ static int r8_setup(pqa_handle* h) {
   return 0;
 }
 
-bool r8_eligible(pqa_handle* h, long W) {
+bool r8_eligible(pqa_handle* h) {
   if (h->res_mode == 0) return false;  // PQA_RES=0: the launch-per-move sweep
   if (!h->r8_ready) {
     if (r8_setup(h) != 0) { h->r8_ok = false; h->err.clear(); }
   }
   if (!h->r8_ok) return false;
   if (h->r8_mode > 0) return true;
-  if (W < h->res_min || W > h->res_max) return false;
   return h->r8_util >= 0.5 && std::max(h->nup, h->ndn) >= 16;
 }
 

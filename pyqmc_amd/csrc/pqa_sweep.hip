@@ -134,9 +134,10 @@ static int sweep_electrons_fused(pqa_handle* h, const MoveBuf& mb_in, const LwCt
   MoveBuf mb = mb_in;
   // the resident sweep (pqa_res.hpp: one launch per sweep, state on chip) where the system is in its scope; it reads both tapes
   const bool tapes_ok = (mb.gauss != nullptr) == (mb.unif != nullptr);
-  const bool r8 = tapes_ok && r8_eligible(h, W);  // (second generation, open-boundary real handles: pqa_res8.hpp)
+  const bool r8 = tapes_ok && r8_eligible(h);  // (second generation, open-boundary real handles: pqa_res8.hpp)
   const bool res = r8 || (tapes_ok && res_eligible(h, W));
-  if (!mb.gauss && !mb.unif && (res || W <= h->draws_max)) {
+  constexpr long draws_max = 16384;  // walker counts up to which a fused sweep draws its random numbers ahead (k_tile_draws)
+  if (!mb.gauss && !mb.unif && (res || W <= draws_max)) {
     // small shards: the sweep's normals and uniforms drawn ahead by one launch from the same Philox streams (k_tile_draws) — in
     // k_step_lw the lead group's Box-Muller pairs are ~600 dependent instructions of every move's chain with one wave per SIMD
     const size_t NW = (size_t)h->N * W;
@@ -165,11 +166,8 @@ static int sweep_electrons_fused(pqa_handle* h, const MoveBuf& mb_in, const LwCt
   int NW = (G <= 4) ? 64 : 256 / G;
   // small shards (one 16-walker block per CU at most): 32 thread groups per walker — k_step_pre<.., 32>, 512 threads, two Jastrow
   // partners per thread: (H2O)8 step 3.93 -> 3.40 ms at 4096 walkers, 3.38 -> 2.88 at 1024; 64 groups (one partner per thread, 1024
-  // threads) spill at the 128-register limit: 4.47 / 3.53 ms.  PQA_STEP_GW = 16 / 32 / 64 pins it.
-  {
-    const int gw = h->step_gw ? h->step_gw : 32;
-    if ((gw == 32 || gw == 64) && W <= h->step_pre_max && N_ok(h) && step_pre_system_ok(h, rowlen) && KB <= gw / 4) { G = gw; NW = 16; }  // (a block row per quartet of groups)
-  }
+  // threads) spill at the 128-register limit: 4.47 / 3.53 ms.
+  if (W <= step_pre_max && N_ok(h) && step_pre_system_ok(h, rowlen) && KB <= 32 / 4) { G = 32; NW = 16; }  // (a block row per quartet of groups)
 
   auto step = [&](int e_acc, int e_prop) {
     StepArgs a{};
@@ -199,7 +197,7 @@ static int sweep_electrons_fused(pqa_handle* h, const MoveBuf& mb_in, const LwCt
                    (const unsigned char*)h->b_sel[s].p + (size_t)i_s * W, (long)W * 5 * h->nmo[s]));
     // ---- decide e, commit, propose e + 1
     hipEvent_t pe1 = nullptr;
-    if (h->profile && (e % (4 * (int)h->prof_stride)) == 1) {  // sparsely sampled full (decide + propose) launches: an event pair costs ~2 us of stream time
+    if (h->profile && (e % (4 * (int)prof_stride)) == 1) {  // sparsely sampled full (decide + propose) launches: an event pair costs ~2 us of stream time
       if (h->prof3_used == h->prof3_events.size()) {
         hipEvent_t a, b;
         HIPCHK(hipEventCreate(&a));
@@ -296,7 +294,7 @@ extern "C" int pqa_vmc_sweeps(pqa_handle_t* h, double tstep, int nsteps, const d
   if (unif) TRY(ensure(h, h->b_unif, (size_t)N * W * sizeof(double)));
   if (accept_rec) TRY(ensure(h, h->b_accrec, (size_t)N * W));
   const size_t nrot = (size_t)N * std::max(h->necp, 1);
-  const bool lw = h->lw_mode != 0 && h->has_slater && h->ndet == 1 && !h->has_j3 && (!h->cplx || std::max(h->nup, h->ndn) <= 32);
+  const bool lw = lw_eligible(h);
   LwCtx lc;
   TRY(lw_setup(h, lw, lc));
   h->draw_ahead_valid = false;
@@ -319,7 +317,7 @@ extern "C" int pqa_vmc_sweeps(pqa_handle_t* h, double tstep, int nsteps, const d
     h->draws_on_device = false;
     TRY(sweep_electrons(h, mb, lw, lc));
     h->r8_xaos_next = false;
-    if (h->draws_on_device && energy_mean && step + 1 < nsteps && W >= 16384 && h->draws_ahead_on) TRY(draws_ahead(h, seed, (uint32_t)(step + 1)));
+    if (h->draws_on_device && energy_mean && step + 1 < nsteps && W >= 16384) TRY(draws_ahead(h, seed, (uint32_t)(step + 1)));
     // small shards: the accepted-move count, the energy rows and their means in one launch at the end of the step (three launches of ~5 us
     // otherwise — 2 % of the 50-determinant molecule's step at 2 048 walkers)
     const bool finish1 = energy_mean && W <= 16384;

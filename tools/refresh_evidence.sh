@@ -64,7 +64,7 @@ timeout 120 $R/tools/scratch/bin/dma_probe > $O/dma_probe.txt 2>&1
 # round 5, later sessions: the periodic / complex resident sweep and the one-launch wave-per-walker sweep against the launches they replace, the
 # ECP point totals left on the device against the read-back
 for c in c3 c5; do for w in 4096 8192 16384; do for r in 1 0; do echo -n "{\"PQA_RES\": $r, \"line\": " >> $O/resident_pbc_ab.txt; PQA_RES=$r python $R/tools/config_bench.py $c --walkers $w --steps 8 2>/dev/null | tail -1 | tr -d '\n' >> $O/resident_pbc_ab.txt; echo "}" >> $O/resident_pbc_ab.txt; done; done; done
-for w in 1024 2048 4096; do for m in "PQA_WW=0 PQA_ECP_DEFER=0 PQA_EN_OVERLAP=0" "PQA_WW=0" "PQA_WW=1 PQA_ECP_DEFER=0" "PQA_WW=1"; do echo -n "{\"env\": \"$m\", \"line\": " >> $O/c4_one_launch_ab.txt; env $m python $R/tools/config_bench.py c4 --walkers $w --steps 20 2>/dev/null | tail -1 | tr -d '\n' >> $O/c4_one_launch_ab.txt; echo "}" >> $O/c4_one_launch_ab.txt; done; done
+for w in 1024 2048 4096; do for m in "PQA_WW=0 PQA_ECP_DEFER=0" "PQA_WW=0" "PQA_WW=1 PQA_ECP_DEFER=0" "PQA_WW=1"; do echo -n "{\"env\": \"$m\", \"line\": " >> $O/c4_one_launch_ab.txt; env $m python $R/tools/config_bench.py c4 --walkers $w --steps 20 2>/dev/null | tail -1 | tr -d '\n' >> $O/c4_one_launch_ab.txt; echo "}" >> $O/c4_one_launch_ab.txt; done; done
 for d in 0 1; do echo -n "{\"PQA_ECP_DEFER\": $d, \"line\": " >> $O/c4_one_launch_ab.txt; PQA_ECP_DEFER=$d python $R/tools/config_bench.py c2 --walkers 4096 --steps 40 2>/dev/null | tail -1 | tr -d '\n' >> $O/c4_one_launch_ab.txt; echo "}" >> $O/c4_one_launch_ab.txt; done
 # round 6: the second-generation resident sweep (k_sweep_r8) against k_sweep_res and the launch-per-move sweep, its phase stamps (timing build
 # libpqa_RCLK.so, in-tree: python -c "import __graft_entry__ as g, os; g.build(extra_flags=['-DPQA_RES_CLK'], lib=os.path.join(g.LIBDIR, 'libpqa_RCLK.so'))"),
