@@ -447,6 +447,46 @@ int pqa_symmetry(pqa_handle_t* h, int nop, const double* ops, const double* orig
    (coordinates are read in place from whichever layout holds them: no layout sync, no change to anything a sweep reads). */
 int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, const double* recip, int mean, double* sq, double* spinsq);
 
+/* ---- slab (2D) Ewald energy ------------------------------------------------------------------------ */
+/* Ewald (pyqmc/observables/ewald2d.py; Yeh and Berkowitz, J. Chem. Phys. 111, 3155): Coulomb energy of a cell that is periodic along
+   its first two lattice vectors and open along the third, of the resident walkers.  Per pair with minimal-image displacement
+   d = (dx, dy, z) (all three lattice vectors, as the handle's other pair terms):
+     real    sum_L erfc(alpha |d + L|) / |d + L|                       over the nlat in-plane displacements lat,
+     recip   2 sum_k cos(k.d) (pi / (A k)) [e^{kz} erfc(k / 2 alpha + alpha z) + e^{-kz} erfc(k / 2 alpha - alpha z)],
+     charge  -(2 pi / A) [z erf(alpha z) + exp(-alpha^2 z^2) / (alpha sqrt(pi))],
+   the reciprocal weight in a scaled form that cannot overflow (pqa_ewald2d.hip).  Electron-electron pairs carry charge 1 and
+   ee adds nelec * self_const; electron-ion pairs carry -q_I (the atom axis is contracted in all three terms; the reference's
+   real-space contraction runs over the electron axis).  The ion-ion term is position independent and stays with the
+   caller.  The tables (pyqmc_amd.ewald2d.ewald2d_tables):
+     alpha, area        partition parameter, area of the in-plane cell
+     self_const         -alpha / sqrt(pi) + sum_k gweight_k - sqrt(pi) / (A alpha)
+     nk, kn, knorm, kpref, recip
+                        k_j = kn[j][0] recip[0] + kn[j][1] recip[1] (recip: the two in-plane reciprocal rows, 2 x 3), |k_j| = knorm[j] > 0,
+                        kpref[j] = (pi / (A knorm[j])) exp(-(knorm[j] / 2 alpha)^2)
+     nlat, lat          in-plane real-space displacements (nlat, 3), nlat >= 1: (2 nlatvec + 1)^2 of them for any nlatvec
+     nion, ion_xyz, ion_charge
+                        ions (nion, 3) / (nion); nion = 0: the handle's atoms and charges
+     walker_chunk       walkers per scratch chunk; 0: the estimator units' own bound
+   mean = 0: ee, ei (W) per walker; mean = 1: the walker means (one double each), reduced on the device in a fixed order that does
+   not depend on the chunk size (no atomics: two calls give the same bits).  Every handle kind with pbc != 0 (coordinates are
+   folded into the cell first: twisted handles keep unfolded ones); open-boundary handles are refused (<0).  Read-only on the
+   resident state: the coordinates are read in place from whichever layout holds them. */
+typedef struct {
+  double alpha, area, self_const;
+  int32_t nk;
+  const int32_t* kn;
+  const double* knorm;
+  const double* kpref;
+  double recip[6];
+  int32_t nlat;
+  const double* lat;
+  int32_t nion;
+  const double* ion_xyz;
+  const double* ion_charge;
+  int64_t walker_chunk;
+} pqa_ewald2d_t;
+int pqa_ewald2d(pqa_handle_t* h, const pqa_ewald2d_t* tab, int mean, double* ee, double* ei);
+
 /* ---- correlated evaluation of parameter sets (line minimisation) ---------------------------------- */
 /* correlated_compute_worker (pyqmc/method/linemin.py:378-409): the resident walkers evaluated at K sets of the two-body Jastrow
    coefficients acoeff (K, natom, na, 2) and bcoeff (K, nb, 3).  Row k equals, within rounding, what this sequence gives on the same

@@ -54,6 +54,15 @@ class SystemStruct(C.Structure):
     ]
 
 
+class Ewald2dTab(C.Structure):
+    """pqa_ewald2d_t (include/pyqmc_amd.h)."""
+
+    _fields_ = [("alpha", C.c_double), ("area", C.c_double), ("self_const", C.c_double),
+                ("nk", C.c_int32), ("kn", C.c_void_p), ("knorm", C.c_void_p), ("kpref", C.c_void_p), ("recip", C.c_double * 6),
+                ("nlat", C.c_int32), ("lat", C.c_void_p), ("nion", C.c_int32), ("ion_xyz", C.c_void_p), ("ion_charge", C.c_void_p),
+                ("walker_chunk", C.c_int64)]
+
+
 _H = C.c_void_p
 _PROTOTYPES = {
     "pqa_create": (C.c_int, [C.POINTER(SystemStruct), C.c_int, C.POINTER(_H)]),
@@ -109,6 +118,7 @@ _PROTOTYPES = {
     "pqa_s2": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
     "pqa_symmetry": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pqa_sq": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "pqa_ewald2d": (C.c_int, [_H, C.POINTER(Ewald2dTab), C.c_int, C.c_void_p, C.c_void_p]),
     "pqa_correlated": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                  C.c_void_p]),
     "pqa_variance": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -121,6 +121,8 @@ struct pqa_handle {
   // pqa_sq (pqa_sq.hip): q vectors and their integer coordinates, per-walker values of a walker chunk, the mean mode's row partials and
   // running sums
   DevBuf b_sqq, b_sqout, b_sqpart, b_sqacc;
+  // pqa_ewald2d (pqa_ewald2d.hip): the call's tables, per-walker values of a walker chunk, the mean mode's partial sums
+  DevBuf b_e2tab, b_e2out, b_e2acc;
   // pqa_overlap_sweeps (pqa_overlap.hip), on the first handle of the call: one sweep's tapes, the old-position drift, acceptance counts,
   // the (K, K, W) weights and the per-sweep overlaps; pinned words the vanished-determinant flags of all K handles come back in
   DevBuf b_ovl;

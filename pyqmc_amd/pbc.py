@@ -57,7 +57,7 @@ def get_supercell(cell, S):
     scale = abs(int(round(np.linalg.det(S))))
     ne = (cell.nelec[0] * scale, cell.nelec[1] * scale)
     sup = Cell(names, xyz, S @ cell.lattice_vectors(), nelec=ne, basis=cell._basis, ecp=cell._ecp,
-               charges=np.repeat(cell.atom_charges(), scale))
+               charges=np.repeat(cell.atom_charges(), scale), dimension=getattr(cell, "dimension", 3))
     sup.original_cell, sup.S, sup.scale = cell, S, scale
     return sup
 

@@ -120,10 +120,10 @@ class Cell(Mol):
     bohr).  ``hasattr(cell, "a")`` is what switches the reference to ``PeriodicConfigs``/Ewald
     (``mc.py:69``, ``accumulators.py:52``, ``wftools.py:82-83``)."""
 
-    def __init__(self, symbols, coords_bohr, a, **kw):
+    def __init__(self, symbols, coords_bohr, a, dimension=3, **kw):
         super().__init__(symbols, coords_bohr, **kw)
         self.a = np.asarray(a, dtype=float).reshape(3, 3)
-        self.dimension = 3
+        self.dimension = int(dimension)  # 2: a slab, periodic along the first two lattice vectors (pyqmc_amd.ewald2d)
 
     def lattice_vectors(self):
         return self.a

@@ -24,7 +24,7 @@ for k in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
     rows.append([g("name"), g("vgpr_count"), g("agpr_count"), g("sgpr_count"), g("group_segment_fixed_size"), g("private_segment_fixed_size")])
 names = subprocess.run(["c++filt"], input="\n".join(r[0] for r in rows), capture_output=True, text=True).stdout.split("\n")
 for r, n in zip(rows, names):
-    n = re.sub(r"^void ", "", n)
+    n = re.sub(r"^void ", "", n).replace("(anonymous namespace)::", "")  # (the estimator units keep their kernels in one)
     n = re.sub(r"\(.*$", "", n)
     if len(sys.argv) > 1 and not any(s in n for s in sys.argv[1:]):
         continue
