@@ -393,6 +393,22 @@ int pqa_obdm_accumulate(pqa_handle_t* h, int slot, int k, int64_t nconf, int nel
    twice; ijkl (4,ntuple) int32.  Accumulates value (nconf,ntuple), norm_a (nconf,norb_a), norm_b (nconf,norb_b). */
 int pqa_tbdm_accumulate(pqa_handle_t* h, int k, int64_t nconf, int nea, int neb, const int32_t* assign_a, const int32_t* assign_b,
                         const double* ratio, int ratio_complex, const int32_t* ijkl, int ntuple, int first);
+/* One sweep of the two-body estimator with the pair ratios formed on the device (tbdm.py:232-246) instead of handed in: wf holds
+   the wave function with the configurations as its resident walkers (wf's W = nconf), ev the estimator's orbitals as above.  For
+   walker w the auxiliary points r1 = kept sample k of slot 0, walker assign_a[w], and r2 = the same of slot 1 with assign_b[w], are
+   read on the device (periodic handles keep them unfolded: the orbital kernel folds, the Jastrow distances are minimal images);
+   ratio[w][a][b] = Psi(r_a -> r1, r_b -> r2)/Psi for a over the whole spin block spin_a and b over spin_b of wf, in closed form from
+   wf's resident state (pqa_tbdm.hip: single-move rows v = phi . inverse, a 2 x 2 determinant of them for equal spins, the
+   determinant-weighted sum for several determinants, times exp of the two-body Jastrow difference), 0 for a pair naming one
+   electron twice.  wf's state is not modified.  The ratios of a walker chunk (walker_chunk walkers; 0: the estimator units' own
+   bound) are contracted on ev's stream by the kernel of pqa_tbdm_accumulate, after which ev holds exactly what that call
+   accumulates (pqa_dm_fetch reads it); ratio (W,nea,neb) host receives the ratios, or NULL: nothing but the two assignments
+   crosses the bus.  ijkl = NULL with ntuple = 0: ratios only, nothing is accumulated and pqa_dm_points is not needed.
+   Fused scope: wf real and untwisted with a Slater factor (one or more determinants), with or without the two-body Jastrow, no
+   three-body factor, open or periodic at Gamma; ev real, on the same device.  Everything else is refused (<0): those pair ratios go
+   through the protocol route (pyqmc_amd.TBDMAccumulator: testvalue, updateinternals, testvalue_many). */
+int pqa_tbdm_sweep(pqa_handle_t* wf, pqa_handle_t* ev, int k, int spin_a, int spin_b, const int32_t* assign_a, const int32_t* assign_b,
+                   const int32_t* ijkl, int ntuple, int first, int64_t walker_chunk, double* ratio);
 /* Read an accumulator times `scale`: which = 0 value (ncol = entries per configuration, doubled when complex), 1 norm /
    norm_a, 2 norm_b (ncol = orbitals).  mean = 0: (nconf,ncol); mean != 0: (ncol,) averaged over the configurations on
    the device (the accumulators' avg(), obdm.py:195-197). */

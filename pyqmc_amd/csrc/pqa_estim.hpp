@@ -1,4 +1,4 @@
-// Code shared by the fused estimator units (pqa_s2, pqa_symmetry, pqa_sq, pqa_correlated, pqa_overlap, pqa_variance); no other
+// Code shared by the fused estimator units (pqa_s2, pqa_symmetry, pqa_sq, pqa_correlated, pqa_overlap, pqa_variance, pqa_tbdm); no other
 // unit includes it.
 //
 // Basis-resolved two-body Jastrow rows: U = sum_p c_p B_p(R) is linear in the coefficients (acoeff entries (atom, k, spin), then
@@ -200,7 +200,7 @@ struct TpTuneGuard {
   ~TpTuneGuard() { memcpy(h->tp_tune, saved, sizeof(h->tp_tune)); }
 };
 
-// Scope of the read-only estimators (pqa_s2, pqa_symmetry): a real, untwisted Slater handle without a three-body factor.
+// Scope of the read-only estimators (pqa_s2, pqa_symmetry, pqa_tbdm_sweep): a real, untwisted Slater handle without a three-body factor.
 inline int readonly_scope(pqa_handle* h, const char* fn) {
   const char* why = !h->has_slater             ? "the handle has no Slater factor"
                     : (h->cplx || h->twist)     ? "complex orbitals / twisted cell"

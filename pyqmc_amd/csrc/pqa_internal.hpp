@@ -115,6 +115,7 @@ struct pqa_handle {
   // spin's transformed electrons)
   DevBuf b_orbphi[2];
   DevBuf b_s2out;  // pqa_s2 (pqa_s2.hip): outputs
+  DevBuf b_tbpts;  // pqa_tbdm_sweep (pqa_tbdm.hip): the auxiliary points of a walker chunk, gathered from the evaluator handle
   // pqa_symmetry (pqa_symmetry.hip), per walker chunk: transformed coordinates, determinant ratios (sign, log) of each spin; the
   // ratios of every operator
   DevBuf b_symx, b_symdet[2], b_symout;
@@ -355,3 +356,5 @@ int scan_ints(pqa_handle* h, const int* c, long* o, long n, long Wm, long* marks
 int jas_refresh(pqa_handle* h);       // basis sums a fused sweep left stale, recomputed
 int slater_rebuild(pqa_handle* h);    // orbital cache, inverses and determinants of both spins from js.x
 int slater_value_dev(pqa_handle* h);  // sign / log of the Slater factor -> b_sign / b_log
+// accumulators of the density-matrix estimators: shapes recorded on the first sweep, checked on the others; buffers sized
+int dm_prepare(pqa_handle* h, long nconf, long nval, int cx, int first, long nnorm_a, long nnorm_b);

@@ -11,23 +11,63 @@ DOI:10.1063/1.4793531; tbdm.py:188-283).  On the device handle of an ``obdm.Orbi
   matrix products per configuration — and ``value[(i,j,k,l)] = M[i][k] conj(phi_j(r1')) conj(phi_l(r2')) / (f1 f2)``.
   The reference builds a (configurations x pairs x index tuples) tensor instead.
 
-The pair ratios come from the wave function's protocol: ``testvalue`` + ``updateinternals`` move electron a to r1'
-(Sherman-Morrison on the device), ``testvalue_many`` gives the ratios of all partners b at once (``k_testvalue_many``),
-and a second ``updateinternals`` moves a back.  ``numpy.random`` is consumed in the reference's order.
+Two routes give the pair ratios:
+
+* **fused** (``pqa_tbdm_sweep``): real wave functions living on one device handle whose resident walkers are the configurations —
+  Slater (one or more determinants), optionally times JastrowSpin, open or periodic at Gamma — with a real evaluator on the same
+  device.  The ratios come in closed form from the resident state (pqa_tbdm.hip), which is not modified, for a walker chunk at a
+  time, and ``k_tbdm_acc`` consumes them on the device: only the two assignments cross the bus.
+* **protocol**: every other wave function.  ``testvalue`` + ``updateinternals`` move electron a to r1' (Sherman-Morrison on the
+  device), ``testvalue_many`` gives the ratios of all partners b at once (``k_testvalue_many``), and a second ``updateinternals``
+  moves a back.
+
+``last_route`` names the route of the last evaluation.  ``numpy.random`` is consumed in the reference's order on both routes (the
+ratios draw nothing).
 """
 
 import numpy as np
 
 from . import _ffi
 from .obdm import AuxiliaryWalkers, OrbitalEvaluator
+from .wf import readonly_device
+
+ROUTES = (None, "fused", "protocol")
+
+
+def device_tbdm_sweep(dev, ev, k, spins, assign_a, assign_b, ijkl=None, first=True, walker_chunk=0, with_ratios=False):
+    """``pqa_tbdm_sweep``: the pair ratios of wave-function handle ``dev`` at kept sample ``k`` of the two resident walks of the
+    evaluator ``ev`` (an ``OrbitalEvaluator``), contracted into ``ev``'s accumulators for the index tuples ``ijkl`` (4, M) (None:
+    ratios only).  Returns the ratios (W, nea, neb) with ``with_ratios``, else None."""
+    a, b = (np.ascontiguousarray(x, dtype=np.int32) for x in (assign_a, assign_b))
+    if a.shape != (dev.W,) or b.shape != (dev.W,):
+        raise ValueError(f"assignments ({dev.W},) expected, got {a.shape} and {b.shape}")
+    R = np.empty((dev.W, dev.nelec[spins[0]], dev.nelec[spins[1]])) if with_ratios else None
+    if ijkl is not None:
+        ijkl = np.ascontiguousarray(ijkl, dtype=np.int32)
+    dev.call("pqa_tbdm_sweep", ev.dev._h, int(k), int(spins[0]), int(spins[1]), _ffi.ptr(a), _ffi.ptr(b), _ffi.ptr(ijkl),
+             0 if ijkl is None else ijkl.shape[1], int(first), int(walker_chunk), _ffi.ptr(R))
+    return R
+
+
+def device_pair_ratios(dev, ev, k, spins, assign_a, assign_b, walker_chunk=0):
+    """R (W, nea, neb) = Psi(r_a -> r1', r_b -> r2') / Psi of ``dev``'s resident walkers, r1' / r2' the auxiliary walkers
+    ``assign_a`` / ``assign_b`` of kept sample ``k`` in slots 0 / 1 of the evaluator ``ev``; nothing is accumulated."""
+    return device_tbdm_sweep(dev, ev, k, spins, assign_a, assign_b, walker_chunk=walker_chunk, with_ratios=True)
 
 
 class TBDMAccumulator:
     """Keys ``value`` (M,), ``norm_a`` (norb_a,), ``norm_b`` (norb_b,) per configuration for the M index tuples ``ijkl``
-    (default: the whole sector).  ``orb_coeff`` (2, nao, norb): orbital basis per spin; ``spin`` = (s1, s2)."""
+    (default: the whole sector).  ``orb_coeff`` (2, nao, norb): orbital basis per spin; ``spin`` = (s1, s2).
+
+    ``route``: None takes the fused route whenever the wave function and the evaluator are in its scope and the protocol route
+    otherwise; "fused" raises outside the scope; "protocol" always moves the electrons.  ``walker_chunk``: walkers per scratch chunk
+    of the fused route (0: the library's bound)."""
 
     def __init__(self, mol, orb_coeff, spin, nsweeps=4, tstep=0.50, warmup=200, naux=None, ijkl=None, kpts=None,
-                 eval_gto_precision=None, device=0):
+                 eval_gto_precision=None, device=0, route=None, walker_chunk=0):
+        if route not in ROUTES:
+            raise ValueError(f"route must be one of {ROUTES}")
+        self._route, self._walker_chunk, self.last_route = route, int(walker_chunk), None
         self.orbitals = OrbitalEvaluator(mol, orb_coeff, kpts=kpts, eval_gto_precision=eval_gto_precision, device=device)
         self._mol, self.dtype = self.orbitals.mol, self.orbitals.mo_dtype
         self._tstep, self._nsweeps, self._warmup, self._naux, self._spin_sector = tstep, nsweeps, warmup, naux, tuple(spin)
@@ -55,8 +95,23 @@ class TBDMAccumulator:
             wf.updateinternals(a, configs.electron(a), configs)  # and back: the state ends where it started
         return R
 
+    def _fused_device(self, configs, wf):
+        """The handle the fused route evaluates ``wf`` on, or None: a read-only-scope wave function whose resident walkers are the
+        configurations, whole non-empty spin blocks, a real evaluator on the same device."""
+        if self._route == "protocol":
+            return None
+        dev, ev = readonly_device(wf), self.orbitals.dev
+        ok = (dev is not None and dev.W == configs.configs.shape[0] and tuple(dev.nelec) == tuple(self._mol.nelec)
+              and min(len(e) for e in self._electrons) > 0 and not ev.cplx and not ev.twisted and ev.device == dev.device)
+        if not ok and self._route == "fused":
+            raise ValueError("route='fused' needs a real Slater (x two-body Jastrow) wave function on one device handle whose resident "
+                             "walkers are the configurations, and a real orbital evaluator on the same device")
+        return dev if ok else None
+
     def _sample(self, configs, wf):
         ev, nconf = self.orbitals, configs.configs.shape[0]
+        dev = self._fused_device(configs, wf)
+        self.last_route = "protocol" if dev is None else "fused"
         if self._walkers is None:
             naux = nconf if self._naux is None else self._naux
             self._walkers = [AuxiliaryWalkers(ev, 0), AuxiliaryWalkers(ev, 1)]
@@ -71,7 +126,9 @@ class TBDMAccumulator:
         for s in (0, 1):
             ev.points(s, s, x[:, self._electrons[s]])
         cplx = False
-        for sw in range(self._nsweeps):
+        for sw in range(self._nsweeps if dev is not None else 0):  # the ratios stay on the device
+            device_tbdm_sweep(dev, ev, sw, self._spin_sector, pick[0][sw], pick[1][sw], self._ijkl, sw == 0, self._walker_chunk)
+        for sw in range(self._nsweeps if dev is None else 0):
             there = [ev.container(kept[s][sw][pick[s][sw]]).electron(0) for s in (0, 1)]
             R = np.ascontiguousarray(self._pair_ratios(configs, wf, *there))
             rc = np.iscomplexobj(R)

@@ -1,0 +1,134 @@
+"""Two-body density matrix timing, fused route against protocol route: one JSON line per configuration, appended to
+profiles/tbdm_bench.jsonl with --record.
+
+    python tools/tbdm_bench.py [--configs C2,M4096,M,MD50,K222] [--reps 7] [--routes fused,protocol] [--protocol-budget-s 90] [--record]
+
+Per configuration and route: wall-clock milliseconds per ``TBDMAccumulator.__call__`` (nsweeps = 4, 8 orbitals per spin, sector
+(up, down)) — the auxiliary walks, the orbitals at the electrons, the four sweeps and the fetch of the result, which ends with a
+stream synchronisation.  Two warm-up calls (the first also warms the walks up), then ``reps`` timed calls: median, minimum, maximum
+and spread = (max - min) / median.  The protocol route at more than 4 096 walkers runs only when 16 x its 4 096-walker time fits
+--protocol-budget-s; otherwise the record says that it was left out for time.  The library is used as built (no build on import).
+The kernel split comes from a ``rocprofv3 --kernel-trace --stats`` run of this tool with --routes fused --reps 3.
+"""
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.environ.get("TBDM_BENCH_TREE", ROOT))  # (another checkout of the package: the parent commit's protocol route)
+
+HBM_BYTES_PER_S = 8.0e12  # MI355X HBM3E peak
+F64_VECTOR_FLOPS = 78.6e12  # MI355X fp64 vector peak
+NORB, NSWEEPS = 8, 4
+
+
+def build(name):
+    """(mol, wf, walkers, TBDMAccumulator keyword arguments)"""
+    from pyqmc_amd import systems
+    from tests import helpers
+
+    def open_orbitals(mol):
+        C = np.asarray(systems.random_mf(mol, seed=5, nvirt=NORB).mo_coeff)
+        return dict(orb_coeff=[C[0][:, :NORB], C[1][:, :NORB]])
+
+    if name in ("M", "M4096"):
+        mol = systems.water_cluster()
+        return mol, helpers.gpu_wf(mol, systems.random_mf(mol)), 65536 if name == "M" else 4096, open_orbitals(mol)
+    if name == "C2":
+        mol = systems.water()
+        return mol, helpers.gpu_wf(mol, systems.random_mf(mol)), 4096, open_orbitals(mol)
+    if name == "MD50":
+        mol = systems.water()
+        mf = systems.random_mf(mol, nvirt=6)
+        return mol, helpers.gpu_wf(mol, mf, systems.random_determinants(mol, mf, 50)), 2048, open_orbitals(mol)
+    if name == "K222":  # diamond, 2 x 2 x 2 primitive cells: 8 k-points, one orbital of each
+        sup, wf = helpers.gpu_pbc_wf("k222")
+        _, kmf = helpers.pbc_slater_case("k222")
+        kpts = np.asarray(kmf.kpts)
+        per_k = NORB // len(kpts)
+        return sup, wf, 4096, dict(orb_coeff=[np.asarray(kmf.mo_coeff[0][k])[:, :per_k] for k in range(len(kpts))], kpts=kpts)
+    raise KeyError(name)
+
+
+def shapes_model(dev, W):
+    """(bytes, flops) of the fused route's own kernels for one sweep, from the shapes: inverses, coordinates and the two orbital rows
+    read, the ratios written by k_tbdm_pairs and read back by k_tbdm_acc; the inverse products, the Jastrow pairs (~60 flops per basis
+    function and pair) and the combination.  The orbital pass is the orbital kernel's own roofline and is counted in neither."""
+    nu, nd = dev.nelec
+    N = nu + nd
+    nds, nb = dev.ndet_s, 4
+    by = W * 8 * (nds[0] * nu * nu + nds[1] * nd * nd + 3 * N + 2 * max(dev.nmo) + 2 * nu * nd)
+    fl = W * (2 * (nds[0] * nu * nu + nds[1] * nd * nd) + 60 * nb * (2 * N * N + nu * nd) + 4 * dev.ndet * nu * nd)
+    return by, fl
+
+
+def time_route(pa, mol, wf, configs, kw, route, reps):
+    extra = {} if route is None else {"route": route}  # (route None: a tree without the keyword, the parent commit)
+    acc = pa.TBDMAccumulator(mol, spin=(0, 1), nsweeps=NSWEEPS, warmup=20, **kw, **extra)
+    np.random.seed(11)
+    ms = []
+    for r in range(reps + 2):
+        t0 = time.perf_counter()
+        acc(configs, wf)
+        if r >= 2:
+            ms.append((time.perf_counter() - t0) * 1e3)
+    med = float(np.median(ms))
+    return {"ms": med, "min_ms": float(min(ms)), "max_ms": float(max(ms)), "spread": float((max(ms) - min(ms)) / med), "reps": reps,
+            "route_taken": getattr(acc, "last_route", "protocol")}
+
+
+def run(name, reps, routes, budget_s, small_protocol_ms):
+    import pyqmc_amd as pa
+
+    mol, wf, W, kw = build(name)
+    dev = wf.fused_device()
+    configs = pa.initial_guess(mol, W, rng=np.random.default_rng(1))
+    if hasattr(mol, "a"):
+        from pyqmc_amd.configs import PeriodicConfigs
+
+        configs = PeriodicConfigs(configs.configs, mol.lattice_vectors())
+    wf.recompute(configs)
+    rec = {"config": name, "walkers": W, "nelec": list(dev.nelec), "ndet": dev.ndet, "nsweeps": NSWEEPS, "norb": NORB, "sector": [0, 1]}
+    if "fused" in routes:
+        rec["fused"] = time_route(pa, mol, wf, configs, kw, "fused", reps)
+        by, fl = shapes_model(dev, W)
+        rec["model_bytes_per_sweep"], rec["model_flops_per_sweep"] = by, fl
+        rec["model_floor_ms_per_call"] = NSWEEPS * max(by / HBM_BYTES_PER_S, fl / F64_VECTOR_FLOPS) * 1e3
+    for route in [r for r in routes if r != "fused"]:
+        key = "protocol" if route == "protocol" else "parent"
+        if W > 4096 and small_protocol_ms is not None and small_protocol_ms * (W / 4096) * (min(reps, 2) + 2) * 1e-3 > budget_s:
+            rec[key] = {"skipped": "time", "projected_ms_per_call": small_protocol_ms * W / 4096}
+            continue
+        rec[key] = time_route(pa, mol, wf, configs, kw, "protocol" if route == "protocol" else None, reps if W <= 4096 else min(reps, 2))
+    if "fused" in rec and "ms" in rec.get("protocol", {}):
+        rec["speedup"] = rec["protocol"]["ms"] / rec["fused"]["ms"]
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="C2,M4096,M,MD50,K222")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--routes", default="fused,protocol", help="fused, protocol, parent (a tree without the route keyword: TBDM_BENCH_TREE)")
+    ap.add_argument("--protocol-budget-s", type=float, default=90.0)
+    ap.add_argument("--record", action="store_true", help="append the lines to profiles/tbdm_bench.jsonl")
+    a = ap.parse_args()
+    small = None
+    for name in a.configs.split(","):
+        rec = run(name, a.reps, a.routes.split(","), a.protocol_budget_s, small)
+        if name == "M4096":
+            small = (rec.get("protocol") or rec.get("parent") or {}).get("ms")
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if a.record:
+            with open(os.path.join(ROOT, "profiles", "tbdm_bench.jsonl"), "a") as f:
+                f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
