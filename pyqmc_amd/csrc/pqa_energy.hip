@@ -17,8 +17,8 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
                           (W * (long)h->N * h->necp * std::max(h->S.ecp_naip_max, 1)) * (long)(64 + 8 * std::max(h->nmo[0], h->nmo[1])) <= (long)256 << 20;
   auto side_begin = [&]() -> int {  // the kinetic / Coulomb pass goes to the side stream; the caller's stream carries on with the ECP passes
     if (!h->en_stream) {
-      HIPCHK(hipStreamCreateWithFlags(&h->en_stream, hipStreamNonBlocking));
-      for (hipEvent_t& e : h->en_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      TRY(new_stream(h, &h->en_stream));
+      for (hipEvent_t& e : h->en_ev) TRY(new_event(h, &e, hipEventDisableTiming));
     }
     HIPCHK(hipEventRecord(h->en_ev[0], h->stream));
     HIPCHK(hipStreamWaitEvent(h->en_stream, h->en_ev[0], 0));
@@ -152,7 +152,7 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
     else hipLaunchKernelGGL(k_ecp_count<false>, dim3((unsigned)W), dim3(64), 0, h->stream, h->S, h->js, B, W);
     // device-wide scans of the two spins' point counts (the one-block k_scan2 took 0.26 ms at 65536 walkers; small shards: one launch)
     // (both totals land in the handle's pinned, device-visible host words: one stream synchronisation is the whole read-back)
-    if (!h->pin_tot) HIPCHK(hipHostMalloc((void**)&h->pin_tot, 4 * sizeof(long), hipHostMallocMapped));
+    if (!h->pin_tot) TRY(new_pinned(h, &h->pin_tot, 4, hipHostMallocMapped));
     if (nsw <= 16384) hipLaunchKernelGGL((k_scan_small2<>), dim3(1), dim3(1024), 0, h->stream, (const int*)B.cnt, B.off, (const int*)B.cnt + nsw, B.off + (nsw + 1), nsw, h->pin_tot);
     else {
       TRY(ensure(h, h->b_tmmarks, 4 * sizeof(long)));

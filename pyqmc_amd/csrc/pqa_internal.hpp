@@ -1,6 +1,9 @@
-// Host-side internals shared by the translation units of libpyqmc_amd.so (pqa_capi.hip, pqa_orb.hip, pqa_sweep.hip,
-// pqa_energy.hip, pqa_dmcsteps.hip): the handle, the error macros, buffer helpers and the functions one unit calls in another.
-// The device code lives in the kernel headers; every kernel has internal linkage, so a unit only compiles what it launches.
+// Host-side internals shared by every translation unit of libpyqmc_amd.so (the UNITS of __graft_entry__.py): the handle, the
+// error macros, the helpers through which the handle allocates and records what it owns, and the functions one unit calls in
+// another.  pqa_create.hip builds and destroys the handle, pqa_capi.hip holds the protocol entry points and the walker state,
+// pqa_orb*.hip / pqa_sweep*.hip / pqa_res*.hip / pqa_energy.hip / pqa_dmcsteps.hip the fused paths, the remaining units one
+// estimator each.  The device code lives in the kernel headers; every kernel has internal linkage, so a unit only compiles what
+// it launches.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,11 +32,17 @@
 #include "pqa_dm.hpp"
 #include "pqa_vmc.hpp"
 
-
-
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+};
+
+// launch profiler: a pool of event pairs around sampled launches (prof_acquire), their elapsed time summed on demand (prof_drain)
+struct ProfSet {
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+  size_t used = 0;
+  long launches = 0;
+  double ms = 0.0;
 };
 
 struct ChunkHost {
@@ -47,7 +56,13 @@ struct pqa_handle {
   int device = 0;
   hipStream_t stream = nullptr;
   std::string err;
-  std::vector<void*> owned;  // table allocations freed at destroy
+  // What the handle allocates it records here (ensure, upload_table, new_event, new_stream, new_pinned below), and pqa_destroy
+  // frees the records: nothing is freed by name.  streams[0] is `stream`.
+  std::vector<void*> owned;   // table allocations
+  std::vector<DevBuf*> bufs;  // the DevBuf fields that hold an allocation
+  std::vector<hipEvent_t> events;
+  std::vector<hipStream_t> streams;
+  std::vector<void*> pinned;
   // host copies needed after create
   int natom = 0, nup = 0, ndn = 0, N = 0, nao = 0, nshell = 0;
   int nmo[2] = {0, 0}, nt[2] = {1, 1}, ndet = 1, ndet_s[2] = {1, 1};
@@ -128,6 +143,9 @@ struct pqa_handle {
   // the (K, K, W) weights and the per-sweep overlaps; pinned words the vanished-determinant flags of all K handles come back in
   DevBuf b_ovl;
   int* pin_ovl = nullptr;
+  hipEvent_t ovl_ev = nullptr;                  // pqa_overlap_sweeps: the flags of an electron move have reached pin_ovl
+  hipEvent_t tb_ev[2] = {nullptr, nullptr};     // pqa_tbdm_sweep: a chunk's ratios produced / consumed
+  hipEvent_t tune_ev[2] = {nullptr, nullptr};   // periodic k_orb: timing of the tile-size trials (tp_tune)
   DevBuf b_tpos, b_twgt, b_tlive, b_trat;
   DevBuf b_tmcnt, b_tmoff, b_tmpass, b_tmamp, b_tmacc, b_tmidx, b_tmapos, b_tmu, b_tmtile, b_tmaoff, b_tmptw, b_tmmarks, b_dmcw, b_dmcold, b_dmcr2, b_dmcout;
   int tm_P = 0;
@@ -208,19 +226,11 @@ struct pqa_handle {
   // measurement
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool profile = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof2_events;  // Sherman-Morrison commit launches of the fused sweep
-  size_t prof2_used = 0;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof3_events;  // partial-sum launches (k_move_part_lw) of the fused sweep
-  size_t prof3_used = 0;
-  long prof3_launches = 0;
-  double prof3_ms = 0.0;
-  long prof2_launches = 0;
-  double prof2_ms = 0.0;
-  size_t prof_used = 0;
-  unsigned prof_tick = 0;  // the event pairs bracket every prof_stride-th eligible launch
-  long prof_launches = 0;
-  double prof_ms = 0.0, prof_pc = 0.0;
+  ProfSet prof_orb;     // orbital launches (launch_orb) and the resident sweeps' launches
+  ProfSet prof_commit;  // Sherman-Morrison commit launches of the fused sweep
+  ProfSet prof_part;    // partial-sum launches (k_move_part_lw) of the fused sweep
+  unsigned prof_tick = 0;  // the orbital set's event pairs bracket every prof_stride-th eligible launch
+  double prof_pc = 0.0;    // point-components of the orbital set's launches
 };
 // profiling: event pairs bracket a 1-in-prof_stride sample of the eligible launches (an event pair costs ~2 us of stream time)
 static constexpr unsigned prof_stride = 4;
@@ -246,7 +256,6 @@ static constexpr unsigned prof_stride = 4;
     if (rc_) return rc_; \
   } while (0)
 
-
 static inline int ensure(pqa_handle* h, DevBuf& b, size_t bytes) {
   if (bytes <= b.cap && b.p) return 0;
   // A buffer that has to GROW holds data-dependent sizes (ECP / T-move point lists: ~38 points per walker +- sqrt(N)
@@ -260,6 +269,7 @@ static inline int ensure(pqa_handle* h, DevBuf& b, size_t bytes) {
   size_t want = std::max<size_t>(regrow ? bytes + bytes / 4 : bytes, 256);
   HIPCHK(hipMalloc(&b.p, want));
   b.cap = want;
+  if (!regrow) h->bufs.push_back(&b);  // (std::swap of two recorded buffers keeps both records valid: pqa_resample)
   return 0;
 }
 
@@ -273,6 +283,50 @@ static int upload_table(pqa_handle* h, const T* src, size_t n, T** dst) {
   if (src) HIPCHK(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
   else HIPCHK(hipMemset(p, 0, n * sizeof(T)));
   *dst = (T*)p;
+  return 0;
+}
+
+// event / non-blocking stream / pinned host words of the handle, recorded for pqa_destroy
+static inline int new_event(pqa_handle* h, hipEvent_t* e, unsigned flags = hipEventDefault) {
+  HIPCHK(hipEventCreateWithFlags(e, flags));
+  h->events.push_back(*e);
+  return 0;
+}
+static inline int new_stream(pqa_handle* h, hipStream_t* s) {
+  HIPCHK(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+  h->streams.push_back(*s);
+  return 0;
+}
+template <class T>
+static int new_pinned(pqa_handle* h, T** p, size_t n, unsigned flags) {
+  HIPCHK(hipHostMalloc((void**)p, n * sizeof(T), flags));
+  h->pinned.push_back(*p);
+  return 0;
+}
+
+// The next event pair of a profiler set, created if the pool has none left.  take = false only makes sure the pair exists.
+static inline int prof_acquire(pqa_handle* h, ProfSet& p, hipEvent_t& e0, hipEvent_t& e1, bool take = true) {
+  if (p.used == p.ev.size()) {
+    hipEvent_t a, b;
+    TRY(new_event(h, &a));
+    TRY(new_event(h, &b));
+    p.ev.emplace_back(a, b);
+  }
+  if (take) {
+    e0 = p.ev[p.used].first;
+    e1 = p.ev[p.used].second;
+    ++p.used;
+  }
+  return 0;
+}
+// elapsed time of the pairs used since the last drain, added to the set's total (the stream has been synchronised)
+static inline int prof_drain(pqa_handle* h, ProfSet& p) {
+  for (size_t i = 0; i < p.used; ++i) {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, p.ev[i].first, p.ev[i].second));
+    p.ms += ms;
+  }
+  p.used = 0;
   return 0;
 }
 
@@ -352,6 +406,11 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
                bool soa_current = false, bool aos_T_needed = true, bool assemble = true);
 // pqa_dmcsteps.hip
 int scan_ints(pqa_handle* h, const int* c, long* o, long n, long Wm, long* marks);
+// pqa_create.hip
+int set_mo(pqa_handle* h, int s, const double* mo_host);  // orbital coefficients of a spin: d_mo, the padded copies, the resident sweep's
+int set_c3(pqa_handle* h, const double* c);               // three-body coefficients, symmetrised
+int jas_merge_tables(pqa_handle* h);                      // merged Pade numerators, after every change of acoeff / bcoeff
+int ecp_quadrature_offset(int naip);                      // first row of a quadrature rule in d_quad (-1: no such rule)
 // pqa_capi.hip
 int jas_refresh(pqa_handle* h);       // basis sums a fused sweep left stale, recomputed
 int slater_rebuild(pqa_handle* h);    // orbital cache, inverses and determinants of both spins from js.x

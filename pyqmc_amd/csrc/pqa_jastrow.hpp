@@ -91,7 +91,7 @@ __device__ __forceinline__ void rad_fn(int kind, double par, double aux, double 
 // (c0, t5, q of RadShared; rad_fn's formulas summed over k).  ONE reciprocal and 3K .. 6K - 3 multiply-adds per pair instead of K
 // reciprocals with two Newton steps each: the lane-per-walker pair loops are instruction bound and the reciprocals were a third of
 // them.  The numerator polynomials depend on the coefficient set (spin channel; atom and spin) and are tabulated by the host
-// whenever coefficients change (pqa_capi.hip: jas_merge_tables, long-double products rounded once).  All beta_k > -1 and
+// whenever coefficients change (pqa_create.hip: jas_merge_tables, long-double products rounded once).  All beta_k > -1 and
 // 0 <= p <= 1: D has no zero, its coefficients are positive for the usual positive beta; the numerators carry the same
 // cancellation between functions as the function-by-function sums, so the results agree to rounding (a few 1e-16 of the sum of
 // magnitudes: tests/test_gpu_jastrow_merge.py).  KD = 3: K <= 3 (zero-padded), KD = 4: K = 4.

@@ -47,15 +47,7 @@ static int launch_orb_impl(pqa_handle* h, int spin, PointAddr pa, long P, int nc
   // stream time, 512 pairs per step were 1.2 ms of a 27 ms step
   const bool prof = h->profile && ncomp == 5 && (h->prof_tick++ % prof_stride) == 0;
   if (prof) {
-    if (h->prof_used == h->prof_events.size()) {
-      hipEvent_t a, b;
-      HIPCHK(hipEventCreate(&a));
-      HIPCHK(hipEventCreate(&b));
-      h->prof_events.emplace_back(a, b);
-    }
-    e0 = h->prof_events[h->prof_used].first;
-    e1 = h->prof_events[h->prof_used].second;
-    ++h->prof_used;
+    TRY(prof_acquire(h, h->prof_orb, e0, e1));
     HIPCHK(hipEventRecord(e0, h->stream));
   }
   // 64-point tiles need >= ~4 blocks per CU to overlap their exp and MFMA phases across blocks; below
@@ -93,7 +85,7 @@ static int launch_orb_impl(pqa_handle* h, int spin, PointAddr pa, long P, int nc
   TRY(check_launch(h, "k_orb"));
   if (prof) {
     HIPCHK(hipEventRecord(e1, h->stream));
-    h->prof_launches += 1;
+    h->prof_orb.launches += 1;
     h->prof_pc += (double)P * ncomp;
   }
   return 0;

@@ -55,8 +55,9 @@ static int launch_orb_pbc(pqa_handle* h, int tabi, int spin, PointAddr pa, long 
     else {
       tune_slot = tune->n[0] <= tune->n[1] ? 0 : 1;  // alternate; best of two samples each
       tp = tune_slot ? 64 : 32;
-      HIPCHK(hipEventCreate(&te0));
-      HIPCHK(hipEventCreate(&te1));
+      if (!h->tune_ev[0])
+        for (hipEvent_t& e : h->tune_ev) TRY(new_event(h, &e));
+      te0 = h->tune_ev[0]; te1 = h->tune_ev[1];
       HIPCHK(hipEventRecord(te0, h->stream));
     }
   }
@@ -86,8 +87,6 @@ static int launch_orb_pbc(pqa_handle* h, int tabi, int spin, PointAddr pa, long 
     HIPCHK(hipEventSynchronize(te1));
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, te0, te1));
-    HIPCHK(hipEventDestroy(te0));
-    HIPCHK(hipEventDestroy(te1));
     tune->ms[tune_slot] = std::min(tune->ms[tune_slot], ms);
     if (++tune->n[tune_slot] >= 2 && tune->n[1 - tune_slot] >= 2) tune->choice = tune->ms[1] < tune->ms[0] ? 64 : 32;
   }

@@ -160,13 +160,6 @@ struct StreamShare {
   }
 };
 
-struct EventGuard {
-  hipEvent_t ev = nullptr;
-  ~EventGuard() {
-    if (ev) (void)hipEventDestroy(ev);
-  }
-};
-
 int values_dev(pqa_handle* h) {  // pqa_wf_value's two parts, left on the device: b_sign / b_log (Slater), b_ju (Jastrow)
   TRY(slater_value_dev(h));
   hipLaunchKernelGGL((k_jastrow_value<>), dim3((unsigned)h->W), dim3(64), 0, h->stream, h->S, h->js, (double*)h->b_ju.p);
@@ -253,9 +246,8 @@ extern "C" int pqa_overlap_sweeps(pqa_handle_t* const* hs, int K, double tstep, 
   double* d_acc = d_grad + 3 * (size_t)W;
   double* d_w = d_acc + W;
   double* d_o = d_w + nw;
-  if (!h->pin_ovl) HIPCHK(hipHostMalloc((void**)&h->pin_ovl, kMaxK * sizeof(int), hipHostMallocDefault));
-  EventGuard evg;
-  HIPCHK(hipEventCreateWithFlags(&evg.ev, hipEventDisableTiming));
+  if (!h->pin_ovl) TRY(new_pinned(h, &h->pin_ovl, kMaxK, hipHostMallocDefault));
+  if (!h->ovl_ev) TRY(new_event(h, &h->ovl_ev, hipEventDisableTiming));
   hipStream_t st = h->stream;
   HIPCHK(hipMemsetAsync(d_acc, 0, (size_t)W * sizeof(double), st));
   const unsigned gb = (unsigned)((W + 255) / 256);
@@ -273,7 +265,7 @@ extern "C" int pqa_overlap_sweeps(pqa_handle_t* const* hs, int K, double tstep, 
                            (int*)g->b_flag.p);
         HIPCHK(hipMemcpyAsync(h->pin_ovl + k, g->b_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
       }
-      HIPCHK(hipEventRecord(evg.ev, st));
+      HIPCHK(hipEventRecord(h->ovl_ev, st));
       hipLaunchKernelGGL(k_ovl_gather, dim3(gb), dim3(256), 0, st, P, K, N, e, W);
       TRY(check_launch(h, "k_has_zero / k_ovl_gather"));
       for (int k = 0; k < K; ++k) {
@@ -290,7 +282,7 @@ extern "C" int pqa_overlap_sweeps(pqa_handle_t* const* hs, int K, double tstep, 
       hipLaunchKernelGGL(k_ovl_decide, dim3(gb), dim3(256), 0, st, P, K, W, tstep, (const double*)(d_g + (size_t)e * W * 3),
                          (const double*)(d_u + (size_t)e * W), (const double*)d_grad, d_acc);
       TRY(check_launch(h, "k_ovl_decide"));
-      HIPCHK(hipEventSynchronize(evg.ev));  // (the proposal and decision stay queued while the host reads the flags)
+      HIPCHK(hipEventSynchronize(h->ovl_ev));  // (the proposal and decision stay queued while the host reads the flags)
       for (int k = 0; k < K; ++k) {
         pqa_handle* g = hs[k];
         const int nmo = g->nmo[s];

@@ -238,16 +238,10 @@ int sweep_res(pqa_handle* h, const MoveBuf& mb) {
   const dim3 grid((unsigned)((W + PQA_RES_NW - 1) / PQA_RES_NW)), block(PQA_RES_NT);
   hipEvent_t e1 = nullptr;
   if (h->profile) {  // every launch is bracketed (one launch per sweep)
-    if (h->prof_used == h->prof_events.size()) {
-      hipEvent_t a, b;
-      HIPCHK(hipEventCreate(&a));
-      HIPCHK(hipEventCreate(&b));
-      h->prof_events.emplace_back(a, b);
-    }
-    HIPCHK(hipEventRecord(h->prof_events[h->prof_used].first, h->stream));
-    e1 = h->prof_events[h->prof_used].second;
-    ++h->prof_used;
-    h->prof_launches += 1;
+    hipEvent_t e0 = nullptr;
+    TRY(prof_acquire(h, h->prof_orb, e0, e1));
+    HIPCHK(hipEventRecord(e0, h->stream));
+    h->prof_orb.launches += 1;
     h->prof_pc += (double)W * h->N * 5;  // point-components of this launch (as launch_orb counts them)
   }
 #define PQA_RES_LAUNCH(D, LM) hipLaunchKernelGGL((k_sweep_res<D, LM>), grid, block, h->res_lds, h->stream, h->S, L, mb, Tc, h->res_tab, (int)h->has_jastrow, W, 0L, W)

@@ -113,8 +113,8 @@ int draws_ahead(pqa_handle* h, uint64_t seed, uint32_t next_step) {
   const long W = h->W;
   const size_t NW = (size_t)h->N * W;
   if (!h->draw_stream) {
-    HIPCHK(hipStreamCreateWithFlags(&h->draw_stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : h->draw_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    TRY(new_stream(h, &h->draw_stream));
+    for (hipEvent_t& e : h->draw_ev) TRY(new_event(h, &e, hipEventDisableTiming));
   }
   DevBuf& bg = (next_step & 1) ? h->b_gauss_b : h->b_gauss;
   DevBuf& bu = (next_step & 1) ? h->b_unif_b : h->b_unif;
@@ -198,37 +198,23 @@ static int sweep_electrons_fused(pqa_handle* h, const MoveBuf& mb_in, const LwCt
     // ---- decide e, commit, propose e + 1
     hipEvent_t pe1 = nullptr;
     if (h->profile && (e % (4 * (int)prof_stride)) == 1) {  // sparsely sampled full (decide + propose) launches: an event pair costs ~2 us of stream time
-      if (h->prof3_used == h->prof3_events.size()) {
-        hipEvent_t a, b;
-        HIPCHK(hipEventCreate(&a));
-        HIPCHK(hipEventCreate(&b));
-        h->prof3_events.emplace_back(a, b);
-      }
-      if (fuse_next) {
-        HIPCHK(hipEventRecord(h->prof3_events[h->prof3_used].first, h->stream));
-        pe1 = h->prof3_events[h->prof3_used].second;
-        ++h->prof3_used;
-      }
+      hipEvent_t pe0 = nullptr;
+      TRY(prof_acquire(h, h->prof_part, pe0, pe1, fuse_next));  // (without fuse_next the pair is only created)
+      if (fuse_next) HIPCHK(hipEventRecord(pe0, h->stream));
     }
     step(e, fuse_next ? e + 1 : -1);
-    if (pe1) { HIPCHK(hipEventRecord(pe1, h->stream)); h->prof3_launches += 1; }
+    if (pe1) { HIPCHK(hipEventRecord(pe1, h->stream)); h->prof_part.launches += 1; }
     if (need_flush) {  // block finished: bring every other row of this spin up to date
       const int nq = j_hi - j_lo;
       hipEvent_t ce1 = nullptr;
       if (h->profile && ((j_lo / std::max(KB, 1)) % 4) == 0) {  // every 4th flush of a spin
-        if (h->prof2_used == h->prof2_events.size()) {
-          hipEvent_t a, b;
-          HIPCHK(hipEventCreate(&a));
-          HIPCHK(hipEventCreate(&b));
-          h->prof2_events.emplace_back(a, b);
-        }
-        HIPCHK(hipEventRecord(h->prof2_events[h->prof2_used].first, h->stream));
-        ce1 = h->prof2_events[h->prof2_used].second;
-        ++h->prof2_used;
+        hipEvent_t ce0 = nullptr;
+        TRY(prof_acquire(h, h->prof_commit, ce0, ce1));
+        HIPCHK(hipEventRecord(ce0, h->stream));
       }
       if (h->cplx) launch_flush_cx(h, L, s, W, 0, W, j_lo, j_hi, nq, rowlen, n_s);
       else launch_flush_real(h, L, s, W, 0, W, j_lo, j_hi, nq, rowlen, n_s);
-      if (ce1) { HIPCHK(hipEventRecord(ce1, h->stream)); h->prof2_launches += 1; }
+      if (ce1) { HIPCHK(hipEventRecord(ce1, h->stream)); h->prof_commit.launches += 1; }
     }
     if (!fuse_next && e + 1 < N) step(-1, e + 1);
   }

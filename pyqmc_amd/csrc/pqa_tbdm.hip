@@ -186,14 +186,6 @@ __global__ __launch_bounds__(64) void k_tbdm_pairs(SysDev S, SlaterState st, Jas
   }
 }
 
-struct EventPair {
-  hipEvent_t produced = nullptr, consumed = nullptr;
-  ~EventPair() {
-    if (produced) (void)hipEventDestroy(produced);
-    if (consumed) (void)hipEventDestroy(consumed);
-  }
-};
-
 }  // namespace
 
 extern "C" int pqa_tbdm_sweep(pqa_handle_t* h, pqa_handle_t* ev, int k, int spin_a, int spin_b, const int32_t* assign_a,
@@ -250,11 +242,11 @@ extern "C" int pqa_tbdm_sweep(pqa_handle_t* h, pqa_handle_t* ev, int k, int spin
                       (same ? 0 : (size_t)h->ndet_s[spin_b] * neb)) * sizeof(double);
   if (lds > 160 * 1024) FAIL("pqa_tbdm_sweep: more determinants than one LDS block holds (use the protocol route)");
   if (lds > 64 * 1024) TRY(raise_lds_limit(h, h->S.pbc ? (const void*)k_tbdm_pairs<true> : (const void*)k_tbdm_pairs<false>));
-  EventPair evp;
-  HIPCHK(hipEventCreateWithFlags(&evp.produced, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&evp.consumed, hipEventDisableTiming));
+  if (!h->tb_ev[0])
+    for (hipEvent_t& e : h->tb_ev) TRY(new_event(h, &e, hipEventDisableTiming));
+  const hipEvent_t produced = h->tb_ev[0], consumed = h->tb_ev[1];
   // the evaluator's queued work (walks, points, the uploads above) is done before the producer reads its arrays
-  HIPCHK(hipEventRecord(evp.consumed, ev->stream));
+  HIPCHK(hipEventRecord(consumed, ev->stream));
   TpTuneGuard tune(h);
   double* d_pts = (double*)h->b_tbpts.p;
   double* d_R = (double*)ev->dm_ratio.p;
@@ -262,7 +254,7 @@ extern "C" int pqa_tbdm_sweep(pqa_handle_t* h, pqa_handle_t* ev, int k, int spin
   const int* d_ab = (const int*)ev->dm_assign[1].p;
   for (long w0 = 0; w0 < W; w0 += Wc) {
     const long wc = std::min(Wc, W - w0);
-    HIPCHK(hipStreamWaitEvent(h->stream, evp.consumed, 0));  // (the previous chunk's ratios have been contracted)
+    HIPCHK(hipStreamWaitEvent(h->stream, consumed, 0));  // (the previous chunk's ratios have been contracted)
     hipLaunchKernelGGL(k_tbdm_gather, dim3((unsigned)((2 * wc + 255) / 256)), dim3(256), 0, h->stream,
                        (const double*)da.keep_pos.p + (size_t)k * da.n * 3, (const double*)db.keep_pos.p + (size_t)k * db.n * 3, d_aa, d_ab, w0,
                        wc, d_pts);
@@ -283,8 +275,8 @@ extern "C" int pqa_tbdm_sweep(pqa_handle_t* h, pqa_handle_t* ev, int k, int spin
     TRY(check_launch(h, "k_tbdm_pairs"));
     if (ratio)
       HIPCHK(hipMemcpyAsync(ratio + (size_t)w0 * nea * neb, d_R, (size_t)wc * nea * neb * sizeof(double), hipMemcpyDefault, h->stream));
-    HIPCHK(hipEventRecord(evp.produced, h->stream));
-    HIPCHK(hipStreamWaitEvent(ev->stream, evp.produced, 0));
+    HIPCHK(hipEventRecord(produced, h->stream));
+    HIPCHK(hipStreamWaitEvent(ev->stream, produced, 0));
     if (accumulate) {
       hipLaunchKernelGGL((k_tbdm_acc<>), dim3((unsigned)wc), dim3(256), lds_acc, ev->stream,
                          (const double*)da.keep_row.p + (size_t)k * da.n * na, (const double*)da.keep_f.p + (size_t)k * da.n,
@@ -294,7 +286,7 @@ extern "C" int pqa_tbdm_sweep(pqa_handle_t* h, pqa_handle_t* ev, int k, int spin
                          (double*)ev->dm_norm[0].p + (size_t)w0 * na, (double*)ev->dm_norm[1].p + (size_t)w0 * nb);
       TRY(on_ev(check_launch(ev, "k_tbdm_acc")));
     }
-    HIPCHK(hipEventRecord(evp.consumed, ev->stream));
+    HIPCHK(hipEventRecord(consumed, ev->stream));
   }
   if (ratio) HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's array is complete on return)
   return 0;

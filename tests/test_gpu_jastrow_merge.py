@@ -1,5 +1,5 @@
 """The merged evaluation of a Jastrow basis' PolyPade functions (csrc/pqa_jastrow.hpp: pade_merged — one rational function of p
-per pair, numerator tables from pqa_capi.hip: jas_merge_tables) against the function-by-function route it replaces on the
+per pair, numerator tables from pqa_create.hip: jas_merge_tables) against the function-by-function route it replaces on the
 lane-per-walker kernels (PQA_JAS_MERGE=0): jastrowspin.py:296-385 with func3d.py:25-49 summed in a different order, so the two
 agree to rounding.  Both are pinned to the oracle elsewhere (tests/test_gpu_parity.py, test_gpu_fullsize.py)."""
 

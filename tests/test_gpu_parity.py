@@ -1040,6 +1040,60 @@ def test_device_resample_is_a_gather_of_the_state(kind):
         a.fused_device().resample(np.full(W, W))
 
 
+def _resample_gathers(a, b, cfg, stale, tag):
+    """The gather checks of the test above for wave function `a` (a second instance `b` recomputes): `stale` = after two fused
+    sweeps that leave the Jastrow sums stale, else straight after recompute, when pqa_resample gathers avalues / bvalues too."""
+    W = cfg.configs.shape[0]
+    idx = np.random.default_rng(32).integers(0, W, W)
+    idx[:5] = [7, 7, 7, 0, W - 1]
+    a.recompute(cfg)
+    if stale:
+        a.fused_device().vmc_sweeps(0.3, 2, seed=4, energy=False)
+    x_old, (s_old, l_old) = a.fused_device().configs(), a.value()
+    a.fused_device().resample(idx)
+    assert np.array_equal(a.fused_device().configs(), x_old[idx])
+    s_new, l_new = a.value()
+    assert np.array_equal(s_new, s_old[idx]) and np.array_equal(l_new, l_old[idx])
+    cfg_b = cfg.copy()
+    cfg_b.resample(idx)
+    cfg_b.configs[...] = x_old[idx]
+    sb, lb = b.recompute(cfg_b)
+    assert note(f"resample_{tag}_phase", np.max(np.abs(sb - s_new))) < 1e-9
+    assert note(f"resample_{tag}_log", np.max(np.abs(lb - l_new))) < 1e-9
+    e = 5
+    ep = cfg_b.electron(e)
+    ga, la = a.gradient_laplacian(e, ep)
+    gb, lb_ = b.gradient_laplacian(e, ep)
+    assert relerr(ga, gb) < 1e-8 and relerr(la, lb_) < 1e-8
+
+
+def test_device_resample_gathers_current_jastrow_sums():
+    """pqa_resample straight after recompute: the Jastrow sums are current, so avalues / bvalues are gathered with the rest."""
+    import pyqmc_amd as pa
+
+    mol = systems.water()
+    a, b = (helpers.gpu_wf(mol, systems.random_mf(mol)) for _ in range(2))
+    _resample_gathers(a, b, pa.initial_guess(mol, 96, rng=np.random.default_rng(31)), False, "sj_current")
+
+
+@pytest.mark.parametrize("stale", [True, False], ids=["stale", "current"])
+def test_device_resample_complex_periodic(stale):
+    """pqa_resample of a complex periodic handle (3x1x1 diamond cell, 12 complex orbitals per spin: inverse and determinant
+    phase rows of two doubles per entry), with the Jastrow sums stale and current."""
+    import pyqmc_amd as pa
+
+    sup, mf = helpers.pbc_complex_case()
+
+    def build():
+        wf = pa.generate_wf(sup, mf)
+        wf.parameters["wf2acoeff"], wf.parameters["wf2bcoeff"] = helpers.pbc_jastrow_coeffs(sup)
+        return wf
+
+    a, b = build(), build()
+    assert a.fused_device().cplx
+    _resample_gathers(a, b, pa.initial_guess(sup, 96, rng=np.random.default_rng(31)), stale, f"cplx_{'stale' if stale else 'current'}")
+
+
 def test_rundmc_device_branching_statistics():
     """rundmc with branching on the device (state gathered, recompute every 10 blocks) against the reference schedule
     (recompute after every branch): same population dynamics within the statistical error."""
