@@ -203,6 +203,26 @@ int pqa_j3_eval(pqa_handle_t* h, int e, const double* pts, int64_t nrow, int npt
    coordinates when the handle has no two-body factor to do it */
 int pqa_j3_update(pqa_handle_t* h, int e, const double* epos, const uint8_t* mask);
 
+/* ---- Gaussian-process Jastrow factor (GPSJastrow, gps2.py) ----------------------------- */
+/* The factor keeps a state of its own on the handle: its own copy of the walkers and its own walker count, independent of the
+   Slater / Jastrow state, which these calls neither read nor write.  Any handle serves, also one created without a Slater and
+   without a Jastrow factor; it supplies the electron count and the cell (minimal image in periodic handles).
+   Support points xsupport (nsup, 2, 3), weights alpha (nsup), width f.  Call it again to change any of them: the stored
+   Gaussians are NOT rebuilt (gps2.py rebuilds them in recompute only); a different nsup invalidates the state. */
+int pqa_gps_set(pqa_handle_t* h, int nsup, const double* xsupport, const double* alpha, double f);
+/* recompute :21-34 / value :40-43 -> log Psi (W) */
+int pqa_gps_recompute(pqa_handle_t* h, const double* configs, int64_t W, double* logval);
+int pqa_gps_value(pqa_handle_t* h, double* logval);
+/* testvalue :76-93 (mode 0), gradient_value :95-108 (mode 1), gradient_laplacian :123-136 (mode 2); argument and output layout
+   as pqa_jastrow_eval.  nrow = 0 returns at once. */
+int pqa_gps_eval(pqa_handle_t* h, int e, const double* pts, int64_t nrow, int npt, const int32_t* widx, int mode, double* out);
+/* updateinternals :68-74: epos (W, 3), mask (W) or NULL.  The sums over the electrons of the touched walkers are formed afresh. */
+int pqa_gps_update(pqa_handle_t* h, int e, const double* epos, const uint8_t* mask);
+/* pgradient :139-173: d_alpha (W, nsup), d_xsupport (W, nsup, 2, 3), d_f (W) */
+int pqa_gps_pgradient(pqa_handle_t* h, double* d_alpha, double* d_xsupport, double* d_f);
+/* test access: e_cs (W, nsup, N, 2) and the unit's walkers (W, N, 3); either may be NULL */
+int pqa_gps_get_state(pqa_handle_t* h, double* e_cs, double* configs);
+
 /* ---- fused device-resident path --------------------------------------------------------- */
 /* MultiplyWF.recompute (multiplywf.py:81-88) for all factors of the handle; also fills the
    per-electron orbital cache used by the fused sweep/energy. */

@@ -94,6 +94,13 @@ _PROTOTYPES = {
     "pqa_j3_value": (C.c_int, [_H, C.c_void_p]),
     "pqa_j3_eval": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "pqa_j3_update": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p]),
+    "pqa_gps_set": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_double]),
+    "pqa_gps_recompute": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pqa_gps_value": (C.c_int, [_H, C.c_void_p]),
+    "pqa_gps_eval": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "pqa_gps_update": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p]),
+    "pqa_gps_pgradient": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pqa_gps_get_state": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
     "pqa_wf_recompute": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "pqa_wf_value": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
     "pqa_get_configs": (C.c_int, [_H, C.c_void_p]),

@@ -139,6 +139,13 @@ struct pqa_handle {
   DevBuf b_sqq, b_sqout, b_sqpart, b_sqacc;
   // pqa_ewald2d (pqa_ewald2d.hip): the call's tables, per-walker values of a walker chunk, the mean mode's partial sums
   DevBuf b_e2tab, b_e2out, b_e2acc;
+  // Gaussian-process Jastrow factor (pqa_gps.hip), a state of its own beside the walker state above: support points (nsup, 2, 3)
+  // followed by alpha (nsup); the unit's own walkers (gps_W, N, 3), e [gps_W][N][2 nsup] and S [gps_W][2 nsup]; per-call inputs
+  // (points / new positions; walker indices / mask) and outputs.  gps_nsup == 0: pqa_gps_set has not run; gps_W == 0: no recompute yet
+  DevBuf b_gps_par, b_gps_x, b_gps_e, b_gps_s, b_gps_in, b_gps_idx, b_gps_out;
+  int gps_nsup = 0;
+  double gps_f = 0.0;
+  long gps_W = 0;
   // pqa_overlap_sweeps (pqa_overlap.hip), on the first handle of the call: one sweep's tapes, the old-position drift, acceptance counts,
   // the (K, K, W) weights and the per-sweep overlaps; pinned words the vanished-determinant flags of all K handles come back in
   DevBuf b_ovl;

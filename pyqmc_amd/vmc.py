@@ -23,6 +23,11 @@ import numpy as np
 from .energy import KEYS, EnergyAccumulator
 
 
+class NotOnOneDeviceError(TypeError, NotImplementedError):
+    """``vmc_worker`` was handed a wave function that does not live on one device handle: the wrong kind of object for this
+    driver (TypeError, as it always raised) and a route this driver does not implement (NotImplementedError)."""
+
+
 def device_of(wf):
     """The device handle a wave function lives on: the shared one of a ``MultiplyWF``, or a bare factor's own
     (``Slater`` / ``JastrowSpin`` / ``ThreeBodyJastrow`` built by ``generate_wf`` / ``generate_jastrow``); None otherwise."""
@@ -84,7 +89,7 @@ def vmc_worker(wf, configs, tstep, nsteps, accumulators, tapes=None, seed=None, 
     (open systems only: periodic containers also carry the block's wrap counters)."""
     dev = device_of(wf)
     if dev is None:
-        raise TypeError("pyqmc_amd.vmc_worker drives a wave function that lives on one device handle (generate_wf); for anything else "
+        raise NotOnOneDeviceError("pyqmc_amd.vmc_worker drives a wave function that lives on one device handle (generate_wf); for anything else "
                         "run the reference's own pyqmc.method.mc.vmc_worker over the protocol objects (INTEGRATION.md)")
     if not all(isinstance(a, EnergyAccumulator) for a in accumulators.values()):
         return _vmc_worker_host_accumulators(dev, wf, configs, tstep, nsteps, accumulators, tapes or {}, seed, state_current)
