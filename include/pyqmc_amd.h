@@ -223,6 +223,34 @@ int pqa_gps_pgradient(pqa_handle_t* h, double* d_alpha, double* d_xsupport, doub
 /* test access: e_cs (W, nsup, N, 2) and the unit's walkers (W, N, 3); either may be NULL */
 int pqa_gps_get_state(pqa_handle_t* h, double* e_cs, double* configs);
 
+/* ---- AO-pair (geminal) Jastrow factor (GeminalJastrow, geminaljastrow.py) -------------------------- */
+/* log Psi = sum_{i>j} a_i^T G a_j with a_i the AO values at electron i and G = triu(gcoeff) + triu(gcoeff)^T.  As the GPS factor
+   it keeps a state of its own on the handle (its walkers, their AO values and the sums over the electrons), independent of the
+   Slater / Jastrow state, which these calls neither read nor write.  The handle must carry basis tables (created with orbital
+   coefficients, which the factor ignores) and real AOs: open systems and periodic cells at the Gamma point; twisted and complex
+   handles are refused.
+   gcoeff (n) in numpy.triu_indices(nao) order; n must be nao (nao + 1) / 2 (:81-84).  The stored AO values are not touched. */
+int pqa_geminal_set(pqa_handle_t* h, const double* gcoeff, int64_t n);
+/* recompute :70-88 / value :102-118 -> log Psi (W) */
+int pqa_geminal_recompute(pqa_handle_t* h, const double* configs, int64_t W, double* logval);
+int pqa_geminal_value(pqa_handle_t* h, double* logval);
+/* testvalue :206-236 (mode 0), gradient_value :155-160 (mode 1), gradient_laplacian :173-188 (mode 2); argument and output layout
+   as pqa_jastrow_eval.  nrow = 0 returns at once.  keep_saved (mode 1, widx NULL): the AO values at pts are kept for the
+   pqa_geminal_update of the same electron that follows. */
+int pqa_geminal_eval(pqa_handle_t* h, int e, const double* pts, int64_t nrow, int npt, const int32_t* widx, int mode, int keep_saved,
+                     double* out);
+/* testvalue_many :238-256: electrons es (ne) each moved to the one point pts (nrow, 3) of its row -> out (nrow, ne) */
+int pqa_geminal_testvalue_many(pqa_handle_t* h, const int32_t* es, int ne, const double* pts, int64_t nrow, const int32_t* widx,
+                               double* out);
+/* updateinternals :90-100: epos (W, 3), mask (W) or NULL.  The sums over the electrons of the touched walkers are formed afresh.
+   use_saved: take the AO values the last evaluation kept (it must have been mode 1 with keep_saved for this electron) instead of
+   evaluating them at epos; both routes give bitwise the same state. */
+int pqa_geminal_update(pqa_handle_t* h, int e, const double* epos, const uint8_t* mask, int use_saved);
+/* pgradient :190-204: d_gcoeff (W, nao (nao + 1) / 2) */
+int pqa_geminal_pgradient(pqa_handle_t* h, double* d_gcoeff);
+/* test access: ao_val (W, N, nao) and the unit's walkers (W, N, 3); either may be NULL */
+int pqa_geminal_get_state(pqa_handle_t* h, double* ao_val, double* configs);
+
 /* ---- fused device-resident path --------------------------------------------------------- */
 /* MultiplyWF.recompute (multiplywf.py:81-88) for all factors of the handle; also fills the
    per-electron orbital cache used by the fused sweep/energy. */

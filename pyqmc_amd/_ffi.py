@@ -101,6 +101,14 @@ _PROTOTYPES = {
     "pqa_gps_update": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p]),
     "pqa_gps_pgradient": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pqa_gps_get_state": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "pqa_geminal_set": (C.c_int, [_H, C.c_void_p, C.c_int64]),
+    "pqa_geminal_recompute": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pqa_geminal_value": (C.c_int, [_H, C.c_void_p]),
+    "pqa_geminal_eval": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "pqa_geminal_testvalue_many": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "pqa_geminal_update": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "pqa_geminal_pgradient": (C.c_int, [_H, C.c_void_p]),
+    "pqa_geminal_get_state": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
     "pqa_wf_recompute": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "pqa_wf_value": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
     "pqa_get_configs": (C.c_int, [_H, C.c_void_p]),

@@ -146,6 +146,14 @@ struct pqa_handle {
   int gps_nsup = 0;
   double gps_f = 0.0;
   long gps_W = 0;
+  // AO-pair (geminal) Jastrow factor (pqa_geminal.hip), a state of its own as the one above: the symmetric G (nao, nao); the unit's
+  // own walkers (gem_W, N, 3), their AO values A [gem_W][N][nao] and sums T [gem_W][nao]; the value plane a mode-1 evaluation kept
+  // for the update that follows it; per-call scratch: AO planes, the rows h = (T - a_e) G, inputs (points / positions / gcoeff),
+  // walker and electron indices or the mask, outputs.  gem_set: pqa_geminal_set has run; gem_W == 0: no recompute yet
+  DevBuf b_gem_g, b_gem_x, b_gem_a, b_gem_t, b_gem_saved, b_gem_ao, b_gem_h, b_gem_in, b_gem_idx, b_gem_out;
+  bool gem_set = false, gem_saved_valid = false;
+  int gem_saved_e = -1;
+  long gem_W = 0;
   // pqa_overlap_sweeps (pqa_overlap.hip), on the first handle of the call: one sweep's tapes, the old-position drift, acceptance counts,
   // the (K, K, W) weights and the per-sweep overlaps; pinned words the vanished-determinant flags of all K handles come back in
   DevBuf b_ovl;
