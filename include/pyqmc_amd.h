@@ -596,6 +596,37 @@ int pqa_variance(pqa_handle_t* h, int K, const double* acoeff, const double* bco
 int pqa_overlap_sweeps(pqa_handle_t* const* hs, int K, double tstep, int nsteps, const double* gauss, const double* unif,
                        double* overlap, double* weights, double* acc_ratio);
 
+/* ---- superposition of several wave functions (AddWF) ------------------------------------------------------------------------------- */
+/* Psi = sum_k coeffs[k] Psi_k (pyqmc/wf/addwf.py) over the walkers resident on the K handles hs[0..K-1], which hold the same walkers.
+   With w_k = coeffs[k] Psi_k / Psi per walker (sum_k w_k = 1), formed as c_k sign_k exp(log|Psi_k| - max_j log|Psi_j|) over their sum
+   (the maximum is the walker's own, not the ensemble's as in the reference: no 0 / 0 when walkers differ by hundreds in log|Psi|).
+   Scope of all three, pqa_overlap_sweeps': real Slater x two-body Jastrow handles (pqa_wf_eval's), any number of determinants, open
+   boundaries, one device, equal W, N and nelec_up, distinct handles, K <= 8, real coeffs; anything else is refused and the caller takes
+   the protocol route.  All K handles' work runs on hs[0]'s stream; saved gradient_value rows are dropped; errors are reported on hs[0].
+
+   pqa_add_weights: sign (W) and logabs (W) of Psi and w (K, W); any of the three may be NULL.  Each handle's own value stays on the
+   device.
+
+   pqa_add_sweeps: nsteps sweeps of vmc_worker (pyqmc/method/mc.py:112-137) over |Psi|^2, all on the device.  Every electron move does what
+   the protocol route (AddWF.gradient_value twice, updateinternals with saved_values) does: with v_k = Psi_k(R') / Psi_k(R) the drift
+   sum_k rho_k grad_k, rho_k = w_k v_k / sum_j w_j v_j, under MultiplyWF.gradient_value's non-finite rules per handle; the proposal
+   x + gauss + tstep limdrift(drift); the acceptance t_prob |sum_k w_k v_k|^2 against unif; the Sherman-Morrison + Jastrow updates of all K
+   handles under the one accept mask, a handle whose determinants of the moved spin had vanished (slater.py:269-275) having its Slater
+   state rebuilt from the moved walkers instead.  gauss (nsteps*N, W, 3) already scaled by sqrt(tstep) and unif (nsteps*N, W) are the
+   reference's draws in its order.  acc (nsteps) or NULL receives each sweep's accepted fraction.  Afterwards every handle holds the state
+   the protocol route would leave (walkers, inverses, determinants, Jastrow sums).
+
+   pqa_add_energy: out (6, W) = ke, ee, ei, ecp, grad2, total of Psi (the rows of pqa_energy).  Every handle runs its own energy pass
+   (pqa_energy's; semi-local ECP integrator only) with the SAME rot / unif, or the same seed where they are NULL: E_L = sum_k w_k E_L,k
+   holds only for one set of ECP rotations and mask draws.  ke = sum_k w_k ke_k, ecp = sum_k w_k ecp_k, ee and ei are hs[0]'s, total =
+   ke + ee + ei + ecp + the ion-ion energy; grad2 = sum_e |sum_k w_k grad_e Psi_k / Psi_k|^2 from an electron loop at the current
+   positions.  The handles' rows and the combination stay on the device; only out comes back.  The walker state is not written. */
+int pqa_add_weights(pqa_handle_t* const* hs, int K, const double* coeffs, double* sign, double* logabs, double* w);
+int pqa_add_sweeps(pqa_handle_t* const* hs, int K, const double* coeffs, double tstep, int nsteps, const double* gauss,
+                   const double* unif, double* acc);
+int pqa_add_energy(pqa_handle_t* const* hs, int K, const double* coeffs, double threshold, const double* rot, const double* unif,
+                   uint64_t seed, double* out);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* HIP-event timing on the handle's own stream (torch.cuda.Event only sees torch's stream). */
 int pqa_timer_start(pqa_handle_t* h);

@@ -30,6 +30,7 @@ from .obdm import OBDMAccumulator  # noqa: F401
 from .tbdm import TBDMAccumulator  # noqa: F401
 from .gps import GPSJastrow  # noqa: F401
 from .geminal import GeminalJastrow  # noqa: F401
+from .addwf import AddWF  # noqa: F401
 
 __version__ = "0.1.0"
 from . import chkfile, hdf5lite  # noqa: F401,E402  (PySCF checkpoint ingest without an HDF5 library)

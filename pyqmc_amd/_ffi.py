@@ -139,6 +139,9 @@ _PROTOTYPES = {
                                  C.c_void_p]),
     "pqa_variance": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pqa_overlap_sweeps": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pqa_add_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pqa_add_sweeps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pqa_add_energy": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "pqa_philox_tapes": (C.c_int, [_H, C.c_uint64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "pqa_philox_dmc_tapes": (C.c_int, [_H, C.c_uint64, C.c_int, C.c_int64, C.c_void_p]),
     "pqa_timer_start": (C.c_int, [_H]),

@@ -158,7 +158,10 @@ struct pqa_handle {
   // the (K, K, W) weights and the per-sweep overlaps; pinned words the vanished-determinant flags of all K handles come back in
   DevBuf b_ovl;
   int* pin_ovl = nullptr;
-  hipEvent_t ovl_ev = nullptr;                  // pqa_overlap_sweeps: the flags of an electron move have reached pin_ovl
+  hipEvent_t ovl_ev = nullptr;                  // pqa_overlap_sweeps / pqa_add_sweeps: the flags of an electron move have reached pin_ovl
+  // pqa_add_* (pqa_add.hip), on the first handle of the call: one sweep's tapes, the (K, W) weights, the old-position drift, acceptance
+  // counts and per-sweep fractions; or the weights and the six combined energy rows
+  DevBuf b_add;
   hipEvent_t tb_ev[2] = {nullptr, nullptr};     // pqa_tbdm_sweep: a chunk's ratios produced / consumed
   hipEvent_t tune_ev[2] = {nullptr, nullptr};   // periodic k_orb: timing of the tile-size trials (tp_tune)
   DevBuf b_tpos, b_twgt, b_tlive, b_trat;

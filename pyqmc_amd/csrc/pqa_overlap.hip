@@ -15,44 +15,11 @@
 //              fallback: Slater.recompute(configs) then the Jastrow update)
 // After each sweep: every handle's value, then k_ovl_weights (compute_weights, sample_many.py:42-55: psi_i psi_j / rho per walker)
 // and k_ovl_mean (the walker mean, a fixed-order tree: block_sum256).
-#include "pqa_estim.hpp"
+#include "pqa_multi.hpp"
 
-// the reference's arithmetic, operation by operation: no fused multiply-adds in this unit's own kernels
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)  // (as pqa_multi.hpp: this unit's own kernels too)
 
 namespace {
-
-constexpr int kMaxK = 8;
-
-struct OvlPtrs {
-  const double* x[kMaxK];     // js.x (W, N, 3) of every handle
-  double* pts[kMaxK];         // b_pts: e's current position (W, 3)
-  const double* out[kMaxK];   // b_out: the nine rows of pqa_wf_eval (9, W)
-  double* newpos[kMaxK];      // b_newpos (W, 3)
-  uint8_t* mask[kMaxK];       // b_mask (W)
-  const double* sign[kMaxK];  // b_sign (W): Slater sign
-  const double* lg[kMaxK];    // b_log (W): Slater log
-  const double* ju[kMaxK];    // b_ju (W): Jastrow log
-};
-
-__device__ __forceinline__ double nan_to_num(double v) {
-  if (v != v) return 0.0;
-  if (v > DBL_MAX) return DBL_MAX;
-  if (v < -DBL_MAX) return -DBL_MAX;
-  return v;
-}
-
-__device__ __forceinline__ void limdrift1(double (&g)[3]) {  // mc.limdrift, cutoff 1
-  const double tot = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-  if (tot > 1.0) for (int d = 0; d < 3; ++d) g[d] = g[d] / tot;
-}
-
-__global__ __launch_bounds__(256) void k_ovl_gather(OvlPtrs P, int K, int N, int e, long W) {
-  const long w = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= W) return;
-  for (int k = 0; k < K; ++k)
-    for (int d = 0; d < 3; ++d) P.pts[k][3 * w + d] = P.x[k][((size_t)w * N + e) * 3 + d];
-}
 
 // grad (W, 3) kept for the decision; new positions into every handle's b_newpos
 __global__ __launch_bounds__(256) void k_ovl_propose(OvlPtrs P, int K, long W, double tstep, const double* __restrict__ gauss,
@@ -146,96 +113,22 @@ __global__ __launch_bounds__(256) void k_ovl_mean(const double* __restrict__ wts
   if (threadIdx.x == 0) out[blockIdx.x] = a / (double)W;
 }
 
-// every handle runs on the first handle's stream for the call's duration (launch_orb and the helpers launch on h->stream)
-struct StreamShare {
-  pqa_handle* const* hs;
-  int K;
-  hipStream_t own[kMaxK];
-  StreamShare(pqa_handle* const* hs_, int K_) : hs(hs_), K(K_) {
-    for (int k = 0; k < K; ++k) own[k] = hs[k]->stream;
-    for (int k = 1; k < K; ++k) hs[k]->stream = hs[0]->stream;
-  }
-  ~StreamShare() {
-    for (int k = 1; k < K; ++k) hs[k]->stream = own[k];
-  }
-};
-
-int values_dev(pqa_handle* h) {  // pqa_wf_value's two parts, left on the device: b_sign / b_log (Slater), b_ju (Jastrow)
-  TRY(slater_value_dev(h));
-  hipLaunchKernelGGL((k_jastrow_value<>), dim3((unsigned)h->W), dim3(64), 0, h->stream, h->S, h->js, (double*)h->b_ju.p);
-  return check_launch(h, "k_jastrow_value");
-}
-
-int rows_at(pqa_handle* h, int e, const double* pts) {  // pqa_wf_eval's chain (jmode 1) at pts (W, 3) -> b_out (9, W), orbital rows in b_motmp
-  const int s = e >= h->nup;
-  const long W = h->W;
-  TRY(launch_orb(h, s, plain_points(pts, W), W, 5, (double*)h->b_motmp.p));
-  hipLaunchKernelGGL(k_slater_eval<5>, dim3((unsigned)W), dim3(64), lds_det(h, 5), h->stream, h->S, h->st, e, (const double*)h->b_motmp.p, W, 1,
-                     (const int*)nullptr, (double*)h->b_out.p);
-  hipLaunchKernelGGL((k_jastrow_eval<>), dim3((unsigned)W), dim3(64), lds_j3(h), h->stream, h->S, h->js, e, pts, W, 1, (const int*)nullptr, 1, 1,
-                     (double*)h->b_out.p + (size_t)5 * W);
-  return check_launch(h, "k_slater_eval / k_jastrow_eval");
-}
-
 }  // namespace
 
 extern "C" int pqa_overlap_sweeps(pqa_handle_t* const* hs, int K, double tstep, int nsteps, const double* gauss, const double* unif,
                                   double* overlap, double* weights, double* acc_ratio) {
   if (!hs || K < 1 || !hs[0]) return -2;
   pqa_handle* h = hs[0];  // (errors are reported on the first handle)
-  if (K > kMaxK) FAIL("pqa_overlap_sweeps: at most 8 wave functions");
   if (nsteps < 0) FAIL("pqa_overlap_sweeps: nsteps must not be negative");
   if (!gauss || !unif || !overlap) FAIL("pqa_overlap_sweeps: gauss, unif and overlap must not be NULL");
-  for (int k = 0; k < K; ++k) {
-    pqa_handle* g = hs[k];
-    if (!g) FAIL("pqa_overlap_sweeps: a NULL handle");
-    for (int j = 0; j < k; ++j)
-      if (hs[j] == g) FAIL("pqa_overlap_sweeps: the same handle twice");
-    if (!g->has_slater || !g->has_j2 || g->has_j3 || g->cplx)
-      FAIL("pqa_overlap_sweeps: every handle must be a real Slater x two-body-Jastrow product (others: the protocol route)");
-    if (g->S.pbc || g->twist) FAIL("pqa_overlap_sweeps: open boundary conditions only (periodic handles: the protocol route)");
-    if (g->W == 0) FAIL("pqa_overlap_sweeps: walkers not resident (call pqa_wf_recompute on every handle)");
-    if (g->device != h->device) FAIL("pqa_overlap_sweeps: all handles must be on one device");
-    if (g->W != h->W || g->N != h->N || g->nup != h->nup) FAIL("pqa_overlap_sweeps: all handles must have the same walkers and electrons");
-  }
+  TRY(multi_validate(hs, K, "pqa_overlap_sweeps"));
   HIPCHK(hipSetDevice(h->device));
   const long W = h->W;
   const int N = h->N;
-  for (int k = 0; k < K; ++k) {
-    pqa_handle* g = hs[k];
-    g->dmc_old_valid = false;  // (as pqa_wf_update)
-    TRY(sync_aos(g));
-    int rc = jas_refresh(g);
-    if (rc) { h->err = g->err; return rc; }
-    g->saved_valid = false;
-  }
-  // every handle's queued work done before its stream is shared
-  for (int k = 1; k < K; ++k) {
-    hipError_t e = hipStreamSynchronize(hs[k]->stream);
-    if (e != hipSuccess) FAIL(std::string("pqa_overlap_sweeps: ") + hipGetErrorString(e));
-  }
+  TRY(multi_begin(hs, K, "pqa_overlap_sweeps"));
   StreamShare share(hs, K);
   OvlPtrs P{};
-  for (int k = 0; k < K; ++k) {
-    pqa_handle* g = hs[k];
-    const int nmo = std::max(g->nmo[0], g->nmo[1]);
-    int rc = 0;
-    if (!rc) rc = ensure(g, g->b_pts, (size_t)W * 3 * sizeof(double));
-    if (!rc) rc = ensure(g, g->b_motmp, (size_t)W * 5 * nmo * sizeof(double));
-    if (!rc) rc = ensure(g, g->b_out, (size_t)9 * W * sizeof(double));
-    if (!rc) rc = ensure(g, g->b_newpos, (size_t)W * 3 * sizeof(double));
-    if (!rc) rc = ensure(g, g->b_mask, (size_t)W);
-    if (!rc) rc = ensure(g, g->b_flag, sizeof(int));
-    if (rc) { h->err = g->err; return rc; }
-    P.x[k] = g->js.x;
-    P.pts[k] = (double*)g->b_pts.p;
-    P.out[k] = (const double*)g->b_out.p;
-    P.newpos[k] = (double*)g->b_newpos.p;
-    P.mask[k] = (uint8_t*)g->b_mask.p;
-    P.sign[k] = (const double*)g->b_sign.p;
-    P.lg[k] = (const double*)g->b_log.p;
-    P.ju[k] = (const double*)g->b_ju.p;
-  }
+  TRY(multi_buffers(hs, K, P));
   // scratch on the first handle: one sweep's tapes (N W 3 + N W), the old drift (3 W), acceptance counts (W), weights (K K W),
   // per-sweep overlaps (nsteps K K)
   const size_t ng = (size_t)N * W * 3, nu = (size_t)N * W, nw = (size_t)K * K * W, no = (size_t)std::max(nsteps, 1) * K * K;
@@ -246,8 +139,6 @@ extern "C" int pqa_overlap_sweeps(pqa_handle_t* const* hs, int K, double tstep, 
   double* d_acc = d_grad + 3 * (size_t)W;
   double* d_w = d_acc + W;
   double* d_o = d_w + nw;
-  if (!h->pin_ovl) TRY(new_pinned(h, &h->pin_ovl, kMaxK, hipHostMallocDefault));
-  if (!h->ovl_ev) TRY(new_event(h, &h->ovl_ev, hipEventDisableTiming));
   hipStream_t st = h->stream;
   HIPCHK(hipMemsetAsync(d_acc, 0, (size_t)W * sizeof(double), st));
   const unsigned gb = (unsigned)((W + 255) / 256);
@@ -256,16 +147,7 @@ extern "C" int pqa_overlap_sweeps(pqa_handle_t* const* hs, int K, double tstep, 
     TRY(copy_in(h, d_u, unif + (size_t)n * nu, nu * sizeof(double)));
     for (int e = 0; e < N; ++e) {
       const int s = e >= h->nup;
-      // slater.py:269-275 tests the spin's determinants before its update; nothing below changes them before that point
-      for (int k = 0; k < K; ++k) {
-        pqa_handle* g = hs[k];
-        HIPCHK(hipMemsetAsync(g->b_flag.p, 0, sizeof(int), st));
-        const long count = W * g->ndet_s[s];
-        hipLaunchKernelGGL((k_has_zero<>), dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (const double*)g->st.dlog[s], count,
-                           (int*)g->b_flag.p);
-        HIPCHK(hipMemcpyAsync(h->pin_ovl + k, g->b_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-      }
-      HIPCHK(hipEventRecord(h->ovl_ev, st));
+      TRY(multi_flags(hs, K, s));
       hipLaunchKernelGGL(k_ovl_gather, dim3(gb), dim3(256), 0, st, P, K, N, e, W);
       TRY(check_launch(h, "k_has_zero / k_ovl_gather"));
       for (int k = 0; k < K; ++k) {
@@ -282,19 +164,7 @@ extern "C" int pqa_overlap_sweeps(pqa_handle_t* const* hs, int K, double tstep, 
       hipLaunchKernelGGL(k_ovl_decide, dim3(gb), dim3(256), 0, st, P, K, W, tstep, (const double*)(d_g + (size_t)e * W * 3),
                          (const double*)(d_u + (size_t)e * W), (const double*)d_grad, d_acc);
       TRY(check_launch(h, "k_ovl_decide"));
-      HIPCHK(hipEventSynchronize(h->ovl_ev));  // (the proposal and decision stay queued while the host reads the flags)
-      for (int k = 0; k < K; ++k) {
-        pqa_handle* g = hs[k];
-        const int nmo = g->nmo[s];
-        const bool zero = h->pin_ovl[k] != 0;
-        const uint8_t* dm = (const uint8_t*)g->b_mask.p;
-        if (!zero)
-          hipLaunchKernelGGL((k_sm_update<>), dim3((unsigned)W), dim3(64), lds_sm(g), st, g->S, g->st, e, (const double*)g->b_motmp.p, 5 * nmo, dm, 1);
-        hipLaunchKernelGGL((k_jastrow_update<>), dim3((unsigned)W), dim3(64), 0, st, g->S, g->js, e, (const double*)g->b_newpos.p, dm);
-        int rc = check_launch(g, "k_sm_update / k_jastrow_update");
-        if (!rc && zero) rc = slater_rebuild(g);  // (the protocol's fallback: the Slater state rebuilt from the moved walkers)
-        if (rc) { h->err = g->err; return rc; }
-      }
+      TRY(multi_update(hs, K, e, s));
     }
     for (int k = 0; k < K; ++k) {
       int rc = values_dev(hs[k]);

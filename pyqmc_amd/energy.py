@@ -57,7 +57,39 @@ class EnergyAccumulator:
         if dev.pbc:
             dev.set_ewald(**self._ewald_kws)
 
+    def _call_add(self, configs, wf, rot, unif):
+        """A superposition (``AddWF``) in the fused scope: ``pqa_add_energy`` over its components' handles, every handle bound to
+        this accumulator and given the same ECP draws (E_L = sum_k w_k E_L,k holds only then).  There is no protocol route for the
+        energy, so ``wf.route`` plays no part here and ``wf.last_route`` is left alone.  ``check_configs`` compares the first handle's
+        walkers with ``configs`` (one transfer, as for a single handle); the library checks that all handles hold as many."""
+        from .addwf import add_energy
+
+        if not self.use_old_ecp:
+            raise NotImplementedError("EnergyAccumulator(use_old_ecp=False) does not take an AddWF: the batched ECP integrator is not "
+                                      "part of pqa_add_energy")
+        devs, why = wf.scope()
+        if devs is None:
+            raise TypeError(f"pyqmc_amd.EnergyAccumulator takes an AddWF only in the fused scope: {why}")
+        if self.check_configs and not (devs[0].W == len(configs.configs) and np.array_equal(devs[0].configs(), configs.configs)):
+            raise ValueError("walkers on the device differ from `configs`: call wf.recompute(configs) "
+                             "(or keep wf.updateinternals in step with configs.move) first")
+        for d in devs:
+            self.bind(d)
+        self._calls += 1
+        if rot is not None and unif is not None:
+            key = 0  # every draw is replayed: the device streams are not used
+        else:
+            key = int(np.random.randint(0, 2**31 - 1)) if self.seed is None else self.seed + self._calls
+        for c in wf.wf_components:
+            c.wf_factors[0]._saved = None  # (the saved rows of a gradient_value call are overwritten)
+        out = add_energy(devs, wf._real_coeffs(), self.threshold, rot=rot, unif=unif, seed=key)
+        return {k: out[i] for i, k in enumerate(KEYS)}
+
     def __call__(self, configs, wf, rot=None, unif=None):
+        from .addwf import AddWF
+
+        if isinstance(wf, AddWF):
+            return self._call_add(configs, wf, rot, unif)
         dev = self._device(wf)
         if getattr(dev, "twisted", False):  # twisted handles hold unfolded coordinates (include/pyqmc_amd.h)
             same = np.allclose(dev.configs(), configs.configs + configs.wrap @ configs.lvecs, rtol=0, atol=1e-9)
@@ -86,7 +118,10 @@ class EnergyAccumulator:
         (W,P,3) candidate positions) over all ECP atoms' quadrature points.  ``rot`` (necp,3,3) / ``unif`` (necp,W)
         replay the reference's draws; by default they are drawn from ``numpy.random`` like the reference does."""
         from . import _ffi
+        from .addwf import AddWF
 
+        if isinstance(wf, AddWF):
+            raise NotImplementedError("T-moves with an AddWF are not implemented")
         if not self.use_old_ecp:  # accumulators.py:84-86
             return self.ecp.nonlocal_tmoves(configs, wf, e, tau, rot=rot, unif=unif)
         dev = self._device(wf)

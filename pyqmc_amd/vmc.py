@@ -11,6 +11,9 @@ other accumulator (density matrices, parameter gradients, ...) is called on the 
 device sweep, on the walkers fetched from the device, and talks to the wave function through the
 protocol entry points as it would in the reference.
 
+An ``AddWF`` whose components are in the fused scope (``pyqmc_amd/addwf.py``) is moved by ``pqa_add_sweeps``, one call per sweep, with
+host-drawn tapes; its accumulators run on the fetched walkers after every sweep.
+
 The reference's own per-electron Python loop (``mc.py:115-137``) is NOT restated here: an unmodified
 ``pyqmc.method.mc.vmc_worker`` runs over these wave-function objects as they are,
 and the parity tests drive the protocol entry points through ``tests/helpers.protocol_vmc_worker``.
@@ -78,6 +81,52 @@ def _vmc_worker_host_accumulators(dev, wf, configs, tstep, nsteps, accumulators,
     return block_avg, configs
 
 
+def _vmc_worker_add(wf, devs, configs, tstep, nsteps, accumulators, tapes, seed):
+    """A superposition (``AddWF``) on the fused route: every sweep is one ``pqa_add_sweeps`` call with tapes drawn on the host in the
+    reference's order (per electron ``np.random.normal`` then ``np.random.rand``, mc.py:119-131), so a seeded run equals the protocol
+    route; then the accumulators on the fetched walkers (``EnergyAccumulator`` through ``pqa_add_energy``).  ``seed``: the draws of
+    the sweeps come from ``np.random.RandomState(seed)`` instead of numpy's global generator.  ``tapes``: ``gauss`` (nsteps, N, W, 3)
+    unit normals and ``unif`` (nsteps, N, W) replace the draws; ``ecp_rot`` / ``ecp_unif`` (nsteps, ...) go to the energy.
+    ``state_current`` / ``fetch_configs`` of ``vmc_worker`` play no part: every block recomputes all K handles and every sweep fetches
+    the walkers, also with no accumulator (where one call could run all ``nsteps``; kept to one call form)."""
+    from .addwf import add_sweeps
+
+    rng = np.random if seed is None else np.random.RandomState(seed)
+    wf.recompute(configs)
+    for c in wf.wf_components:
+        c.wf_factors[0]._saved = None
+    wf.last_route = "fused"
+    nconf, nelec = configs.configs.shape[:2]
+    coeffs = wf._real_coeffs()
+    block_avg = {}
+    t_move = t_acc = 0.0
+    acc = 0.0
+    for step in range(nsteps):
+        t0 = time.perf_counter()
+        if "gauss" in tapes:
+            gauss, unif = np.sqrt(tstep) * np.asarray(tapes["gauss"][step]), np.asarray(tapes["unif"][step])
+        else:
+            gauss, unif = np.empty((nelec, nconf, 3)), np.empty((nelec, nconf))
+            for e in range(nelec):
+                gauss[e] = rng.normal(scale=np.sqrt(tstep), size=(nconf, 3))
+                unif[e] = rng.rand(nconf)
+        acc = add_sweeps(devs, coeffs, tstep, gauss, unif)[-1]
+        configs.configs[...] = devs[0].configs()
+        t1 = time.perf_counter()
+        for k, accumulator in accumulators.items():
+            if isinstance(accumulator, EnergyAccumulator) and "ecp_rot" in tapes:
+                dat = {m: np.mean(v, axis=0) for m, v in accumulator(configs, wf, rot=tapes["ecp_rot"][step], unif=tapes["ecp_unif"][step]).items()}
+            else:
+                dat = accumulator.avg(configs, wf)
+            for m, res in dat.items():
+                block_avg[k + m] = block_avg.get(k + m, 0.0) + res / nsteps
+        t_move, t_acc = t_move + (t1 - t0), t_acc + (time.perf_counter() - t1)
+    block_avg["acceptance"] = acc
+    block_avg["move time"] = t_move / max(nsteps, 1)
+    block_avg["accumulator time"] = t_acc / max(nsteps, 1)
+    return block_avg, configs
+
+
 def vmc_worker(wf, configs, tstep, nsteps, accumulators, tapes=None, seed=None, state_current=False, fetch_configs=True):
     """One block of ``nsteps`` sweeps (mc.py:102-153): returns (block averages, configs).
 
@@ -87,6 +136,12 @@ def vmc_worker(wf, configs, tstep, nsteps, accumulators, tapes=None, seed=None, 
     that knows the device already holds the state of ``configs`` (it ran the previous block and touched nothing since) passes
     ``state_current=True``; one that does not need the walkers on the host after this block passes ``fetch_configs=False``
     (open systems only: periodic containers also carry the block's wrap counters)."""
+    from .addwf import AddWF
+
+    if isinstance(wf, AddWF):  # a superposition in the fused scope: K handles, one device (pqa_add_sweeps)
+        devs = wf.fused_devices() if not hasattr(configs, "wrap") else None
+        if devs is not None:
+            return _vmc_worker_add(wf, devs, configs, tstep, nsteps, accumulators, tapes or {}, seed)
     dev = device_of(wf)
     if dev is None:
         raise NotOnOneDeviceError("pyqmc_amd.vmc_worker drives a wave function that lives on one device handle (generate_wf); for anything else "
