@@ -419,20 +419,25 @@ static __global__ __launch_bounds__(PQA_R8_NT, 2) void k_sweep_r8(SysDev S, LwSt
         bq[5] = 0.0;
         PQA_R8CLK(1);
         res_block_sync();
-        d4 acc[3];
+        d4 acc[2];
+        double lap[2] = {0.0, 0.0};
 #pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] = (d4){0.0, 0.0, 0.0, 0.0};
+        for (int c = 0; c < 2; ++c) acc[c] = (d4){0.0, 0.0, 0.0, 0.0};
         {
-          // A operand: row m = 8 h + p of MFMA j is component 2 j + h of point p (j = 2: component 4 in both halves, the upper one unused);
-          // the next k-step's three operands are read while this one's MFMAs run, the B operand five steps ahead
+          // A operand: row m = 8 h + p of 16x16x4 MFMA j is component 2 j + h of point p.  Component 4 (the Laplacian) would fill half of a
+          // third one; it goes through two v_mfma_f64_4x4x4_4b_f64 instead (half the pipe time of one 16x16x4): four independent 4x4x4
+          // products each, block (lane >> 2) & 3 = orbitals 16 u + 4 block .. + 3, of points 0..3 (lap[0]) and 4..7 (lap[1]).  That form
+          // takes A[i][k] from lane i + 4 block + 16 k and B[k][j] from lane j + 4 block + 16 k: B is the register the 16x16x4 form uses,
+          // A is the Laplacian plane at point (lane & 3) + 4 g in every block (a broadcast read).
+          // The next k-step's four operands are read while this one's MFMAs run, the B operand five steps ahead
           const int h8 = i16 >> 3, p8 = i16 & 7;
           const double* a0 = region + (size_t)h8 * csv + kq * 8 + p8;
           const double* a1 = region + (size_t)(2 + h8) * csv + kq * 8 + p8;
-          const double* a2 = region + (size_t)4 * csv + kq * 8 + p8;
-          double xa[2][3];
+          const double* a2 = region + (size_t)4 * csv + kq * 8 + (i16 & 3);
+          double xa[2][4];
           {
             const int ka = min(kwv, nks - 1) * 32;
-            xa[0][0] = a0[ka]; xa[0][1] = a1[ka]; xa[0][2] = a2[ka];
+            xa[0][0] = a0[ka]; xa[0][1] = a1[ka]; xa[0][2] = a2[ka]; xa[0][3] = a2[ka + 4];
           }
 #pragma unroll 1
           for (int q6 = 0; q6 < nq && PQA_R8_ON(2); q6 += 6) {
@@ -441,11 +446,12 @@ static __global__ __launch_bounds__(PQA_R8_NT, 2) void k_sweep_r8(SysDev S, LwSt
               const int q = q6 + qq;
               bq[(qq + 5) % 6] = cb[(size_t)min(q + 5, nq - 1) * bstep];
               const int ka = min(kwv + (q + 1) * KW, nks - 1) * 32;
-              xa[(qq + 1) & 1][0] = a0[ka]; xa[(qq + 1) & 1][1] = a1[ka]; xa[(qq + 1) & 1][2] = a2[ka];
+              xa[(qq + 1) & 1][0] = a0[ka]; xa[(qq + 1) & 1][1] = a1[ka]; xa[(qq + 1) & 1][2] = a2[ka]; xa[(qq + 1) & 1][3] = a2[ka + 4];
               if (q < nq) {  // (wave-uniform; the loads above stay unconditional so that the compiler can count them)
                 acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[qq & 1][0], bq[qq], acc[0], 0, 0, 0);
                 acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[qq & 1][1], bq[qq], acc[1], 0, 0, 0);
-                acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[qq & 1][2], bq[qq], acc[2], 0, 0, 0);
+                lap[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(xa[qq & 1][2], bq[qq], lap[0], 0, 0, 0);
+                lap[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(xa[qq & 1][3], bq[qq], lap[1], 0, 0, 0);
               }
             }
           }
@@ -454,15 +460,15 @@ static __global__ __launch_bounds__(PQA_R8_NT, 2) void k_sweep_r8(SysDev S, LwSt
         PQA_R8CLK(2);
         res_block_sync();  // every wave is done reading the tile: the K-partials take its place
         {
-          // lane holds D[m = kq + 4 rr][orbital = 16 u + i16]: rr 0, 1 -> component 2 j of points kq, kq + 4; rr 2, 3 -> component 2 j + 1
+          // lane holds D[m = kq + 4 rr][orbital = 16 u + i16]: rr 0, 1 -> component 2 j of points kq, kq + 4; rr 2, 3 -> component 2 j + 1;
+          // the 4x4x4 form leaves D[i][j] of a block in lane j + 4 block + 16 i: lap[g] is component 4 of point kq + 4 g at the same orbital
           double* pw = part + ((size_t)kw * PQA_R8_NW + kq) * PS + 16 * u + i16;
 #pragma unroll
-          for (int j = 0; j < 3; ++j)
+          for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-              const int c = 2 * j + (rr >> 1);
-              if (c < 5) pw[(size_t)4 * (rr & 1) * PS + c * 16 * nt] = acc[j][rr];
-            }
+            for (int rr = 0; rr < 4; ++rr) pw[(size_t)4 * (rr & 1) * PS + (2 * j + (rr >> 1)) * 16 * nt] = acc[j][rr];
+#pragma unroll
+          for (int g = 0; g < 2; ++g) pw[(size_t)4 * g * PS + 4 * 16 * nt] = lap[g];
         }
         res_block_sync();
         PQA_R8CLK(3);
