@@ -566,6 +566,27 @@ int pqa_ewald2d(pqa_handle_t* h, const pqa_ewald2d_t* tab, int mean, double* ee,
 int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, const double* bcoeff, double threshold, const double* rot,
                    const double* unif, uint64_t seed, double* logpsi, double* en);
 
+/* ---- stochastic-reconfiguration moments from the resident state ----------------------------------- */
+/* StochasticReconfiguration.avg (stochastic_reconfiguration.py:49-118) on the resident walkers, without the walkers or the
+   derivative arrays crossing the bus.  Column i of the serialised derivative matrix dp (W, P) is entry pos[i] (flat C-order index)
+   of the parameter src[i] names: 0 det_coeff (ndet), 1 acoeff (natom, na, 2), 2 bcoeff (nb, 3), 3 ccoeff (natom, na3, na3, nb3, 3);
+   src and pos are host arrays of P entries.  The energy pass is pqa_energy's (threshold, rot, unif, seed as there: the per-walker
+   energies are the same bits).  With the weights w (W, host or device; NULL: 1 / W; normalised by their sum) and the Pathak-Wagner
+   weight f of grad2 at nodal_cutoff (x = 1 / (grad2 cutoff^2); f = x (9 - 15 x + 7 x^2) where x < 1, else 1):
+     en_mean (6)         sum_w w E_k for ke, ee, ei, ecp, grad2, total,
+     moments (P + 2, P)  row-major: rows 0 .. P-1 dpidpj = sum_w dp_i (w f dp_j), row P dpH = sum_w E (w f dp_j) with E the total
+                         energy, row P + 1 dppsi = sum_w (w f dp_j),
+     en_walker (W, 6)    the per-walker energies, or NULL: nothing of size W leaves the device.
+   The product runs on the fp64 matrix cores over walker chunks of at most 256 MiB of gathered columns; the walker sums have a fixed
+   order (two calls give the same bits) and dpidpj is exactly symmetric.  The walkers, inverses, determinants and coefficients are
+   not written; as pqa_energy the call syncs a lane-per-walker layout back and drops saved gradient_value rows, as pqa_wf_value it
+   refreshes stale basis sums.  Real handles (open or periodic, one or more determinants, with or without the three-body factor,
+   either ECP integrator); complex / twisted handles, a column of a factor the handle lacks, and moments beyond 256 MiB are refused
+   (<0): those go through the protocol route.  Orbital coefficients are not a source. */
+int pqa_sr_moments(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff, const double* weights,
+                   double threshold, const double* rot, const double* unif, uint64_t seed, double* en_mean, double* moments,
+                   double* en_walker);
+
 /* ---- variance of the local energy at parameter sets (variance optimisation) ------------------------------------------------------ */
 /* optvariance.py:44-54 on the resident walkers, for K sets of two-body Jastrow coefficients acoeff (K,natom,na,2),
    bcoeff (K,nb,3).  eoff (W) = Enref total - Enref ke per walker.  For set k:

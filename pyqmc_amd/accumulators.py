@@ -10,6 +10,8 @@ Public names, argument meaning and returned keys are those of the reference's ``
   ``k_gram_mfma``): with ``A = [dp | E | 1]`` (nconf, p+2) and ``B = w f dp`` (nconf, p),
   ``A^T B = [[dpidpj], [dpH], [dppsi]]``.  The per-walker derivatives come from ``wf.pgradient()`` (``k_pgrad_det``,
   ``k_pgrad_mo``, ``k_j3_pgrad``).
+* On the device route (``sr_route``) ``avg`` takes energy means and moments from ONE call on the resident state (``pqa_sr_moments``):
+  neither the walkers nor the derivative arrays come to the host.
 """
 
 import numpy as np
@@ -103,17 +105,87 @@ def device_gram(wf):
     return gram
 
 
+SR_SOURCES = {"wf1det_coeff": 0, "wf2acoeff": 1, "wf2bcoeff": 2, "wf3ccoeff": 3}  # parameter -> source code of pqa_sr_moments
+
+
+def sr_columns(transform):
+    """``(src, pos)`` of ``pqa_sr_moments`` for a ``LinearTransform`` whose keys are all in ``SR_SOURCES``: column i of the serialised
+    derivative matrix is flat entry ``pos[i]`` of the parameter ``src[i]`` names (key after key, selected entries in C order)."""
+    src = [np.full(len(p), SR_SOURCES[k], dtype=np.int32) for k, p in transform._pos.items()]
+    pos = [np.asarray(p, dtype=np.int32) for p in transform._pos.values()]
+    return (np.concatenate(src), np.concatenate(pos)) if src else (np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))
+
+
+def _sr_device(wf):
+    """(device handle, None) when ``wf`` is ``generate_wf``'s product on one real handle, else (None, reason)."""
+    from . import wf as pwf
+
+    if not isinstance(wf, pwf.MultiplyWF):
+        return None, f"{type(wf).__name__} is not a pyqmc_amd.MultiplyWF on one device handle"
+    kinds = [type(f) for f in wf.wf_factors]
+    if kinds not in ([pwf.Slater, pwf.JastrowSpin], [pwf.Slater, pwf.JastrowSpin, pwf.ThreeBodyJastrow]):
+        return None, "factors other than Slater x JastrowSpin [x ThreeBodyJastrow]: " + ", ".join(k.__name__ for k in kinds)
+    dev = wf.fused_device()
+    if dev is None or not hasattr(dev, "sr_moments"):
+        return None, "the factors do not share one device handle"
+    if dev.cplx or dev.twisted:
+        return None, "complex orbitals / twisted cell"
+    return dev, None
+
+
+def sr_route(wf, sr):
+    """``("device", reason)`` when ``sr.avg`` can take its moments from the resident state (``pqa_sr_moments``), else
+    ``("protocol", reason)``.  The device route needs: ``wf`` on one real device handle (``generate_wf``'s Slater x two-body Jastrow,
+    with or without the three-body factor); ``sr.enacc`` a ``pyqmc_amd.EnergyAccumulator`` itself (not a subclass or a stand-in);
+    ``sr.transform`` a ``LinearTransform`` whose optimised keys are all among ``SR_SOURCES``; no injected ``gram``."""
+    from .energy import EnergyAccumulator
+
+    dev, why = _sr_device(wf)
+    if dev is None:
+        return "protocol", why
+    if type(sr.enacc) is not EnergyAccumulator:
+        return "protocol", f"the energy object is a {type(sr.enacc).__name__}, not a pyqmc_amd.EnergyAccumulator"
+    if sr._gram is not None:
+        return "protocol", "an injected gram"
+    if type(sr.transform) is not LinearTransform:
+        return "protocol", f"the transform is a {type(sr.transform).__name__}, not a pyqmc_amd.LinearTransform"
+    other = [k for k in sr.transform.to_opt if k not in SR_SOURCES]
+    if other:
+        return "protocol", "parameters without a device source: " + ", ".join(other)
+    if sr.transform.nparams == 0:
+        return "protocol", "no parameter is optimised"
+    return "device", "one real device handle, device energy, every parameter has a device source"
+
+
 class StochasticReconfiguration:
     """Energy plus the moments ``dpH = <E f dp>``, ``dppsi = <f dp>``, ``dpidpj = <dp (f dp)^T>`` of the logarithmic
     parameter derivatives (``stochastic_reconfiguration.py:49-118``) and the SR step from their averages (:120-176).
 
     ``gram``: callable ``(A, B) -> A^T B``; default: the device product of the wave function's own handle (tests of the
-    host logic inject a NumPy one)."""
+    host logic inject a NumPy one).
 
-    def __init__(self, enacc, transform, nodal_cutoff=1e-3, eps=1e-1, inverse_strategy="pseudo_inverse", verbose=False, gram=None):
+    ``route``: where ``avg`` forms its averages.  ``"protocol"``: derivatives through ``wf.pgradient()``, energies through the energy
+    object, one product (``pqa_gram``).  ``"device"``: one ``pqa_sr_moments`` call on the resident state; ``NotImplementedError`` with
+    the reason when ``sr_route`` says the case is out of its scope.  None (default): the device route when in scope, else the protocol
+    route.  ``last_route`` records what the last evaluation took."""
+
+    def __init__(self, enacc, transform, nodal_cutoff=1e-3, eps=1e-1, inverse_strategy="pseudo_inverse", verbose=False, gram=None,
+                 route=None):
+        if route not in (None, "device", "protocol"):
+            raise ValueError(f"route must be None, 'device' or 'protocol', got {route!r}")
         self.enacc, self.transform = enacc, transform
         self.nodal_cutoff, self.eps, self.inverse_strategy, self.verbose = nodal_cutoff, eps, inverse_strategy, verbose
         self._gram = gram
+        self.route, self.last_route = route, None
+
+    def resolve_route(self, wf):
+        """The route ``avg`` takes for ``wf``: ``"device"`` or ``"protocol"`` (see ``route``)."""
+        if self.route == "protocol":
+            return "protocol"
+        r, why = sr_route(wf, self)
+        if self.route == "device" and r != "device":
+            raise NotImplementedError(f"StochasticReconfiguration(route='device'): {why}")
+        return r
 
     def _derivatives(self, configs, wf, cutoff):
         dp = self.transform.serialize_gradients(wf.pgradient())
@@ -121,13 +193,42 @@ class StochasticReconfiguration:
         return dp, en, dp * nodal_regularization(en["grad2"], cutoff)[1][:, None]
 
     def __call__(self, configs, wf):
+        self.last_route = "protocol"
         dp, d, fdp = self._derivatives(configs, wf, self.nodal_cutoff)
         d["dpH"] = d["total"][:, None] * fdp
         d["dppsi"] = fdp
         d["dpidpj"] = dp[:, :, None] * fdp[:, None, :]
         return d
 
+    def avg_resident(self, wf, weights=None):
+        """``avg`` on the device route for the walkers resident behind ``wf``, without comparing them with a host container: binds
+        the energy object, advances its call count and derives the key of the energy draws as ``EnergyAccumulator.__call__`` does,
+        then one ``pqa_sr_moments`` call."""
+        from .energy import KEYS
+
+        dev, why = _sr_device(wf)
+        if dev is None:
+            raise NotImplementedError(f"StochasticReconfiguration.avg_resident: {why}")
+        enacc = self.enacc
+        enacc.bind(dev)
+        enacc._calls += 1
+        key = int(np.random.randint(0, 2**31 - 1)) if enacc.seed is None else enacc.seed + enacc._calls
+        src, pos = sr_columns(self.transform)
+        # the reference regularises with the default cut-off in avg (:105)
+        en, m = dev.sr_moments(src, pos, 1e-3, weights=weights, threshold=enacc.threshold, seed=key)
+        self.last_route = "device"
+        d = {k: en[i] for i, k in enumerate(KEYS)}
+        d["dpidpj"], d["dpH"], d["dppsi"] = m[:-2], m[-2], m[-1]
+        return d
+
     def avg(self, configs, wf, weights=None):
+        if self.resolve_route(wf) == "device":
+            dev = _sr_device(wf)[0]
+            if self.enacc.check_configs and not (dev.W == len(configs.configs) and np.array_equal(dev.configs(), configs.configs)):
+                raise ValueError("walkers on the device differ from `configs`: call wf.recompute(configs) "
+                                 "(or keep wf.updateinternals in step with configs.move) first")
+            return self.avg_resident(wf, weights)
+        self.last_route = "protocol"
         dp, en, fdp = self._derivatives(configs, wf, 1e-3)  # the reference regularises with the default cut-off here (:105)
         nconf = configs.configs.shape[0]
         w = np.full(nconf, 1.0 / nconf) if weights is None else np.asarray(weights, dtype=float) / np.sum(weights)
@@ -170,10 +271,13 @@ class StochasticReconfiguration:
 PGradTransform = StochasticReconfiguration
 
 
-def gradient_generator(mol, wf, to_opt=None, nodal_cutoff=1e-3, eps=1e-3, inverse_strategy="regularized_inverse", **ewald_kwargs):
+def gradient_generator(mol, wf, to_opt=None, nodal_cutoff=1e-3, eps=1e-3, inverse_strategy="regularized_inverse", route=None, **ewald_kwargs):
     """The gradient object of line minimisation (``observables/accumulators.py:27-42``): an ``EnergyAccumulator`` and the
-    ``LinearTransform`` of ``to_opt`` in a ``StochasticReconfiguration``."""
+    ``LinearTransform`` of ``to_opt`` in a ``StochasticReconfiguration``.  ``route``: see ``StochasticReconfiguration``;
+    ``"device"`` is checked against ``wf`` here already."""
     from .energy import EnergyAccumulator
 
-    return StochasticReconfiguration(EnergyAccumulator(mol, **ewald_kwargs), LinearTransform(wf.parameters, to_opt),
-                                     nodal_cutoff=nodal_cutoff, eps=eps, inverse_strategy=inverse_strategy)
+    sr = StochasticReconfiguration(EnergyAccumulator(mol, **ewald_kwargs), LinearTransform(wf.parameters, to_opt),
+                                   nodal_cutoff=nodal_cutoff, eps=eps, inverse_strategy=inverse_strategy, route=route)
+    sr.resolve_route(wf)  # (route="device" out of scope: NotImplementedError now, not at the first block)
+    return sr

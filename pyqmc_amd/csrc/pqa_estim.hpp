@@ -1,5 +1,5 @@
-// Code shared by the fused estimator units (pqa_s2, pqa_symmetry, pqa_sq, pqa_correlated, pqa_overlap, pqa_variance, pqa_tbdm); no other
-// unit includes it.
+// Code shared by the fused estimator units (pqa_s2, pqa_symmetry, pqa_sq, pqa_correlated, pqa_overlap, pqa_variance, pqa_tbdm, pqa_sr); no
+// other unit includes it.
 //
 // Basis-resolved two-body Jastrow rows: U = sum_p c_p B_p(R) is linear in the coefficients (acoeff entries (atom, k, spin), then
 // bcoeff entries (k, pair)), and so are grad_e U, lap_e U and U(e -> q) - U(e).  jas_rows writes R[m * P + p] = grad_e B_p

@@ -162,6 +162,9 @@ struct pqa_handle {
   // pqa_add_* (pqa_add.hip), on the first handle of the call: one sweep's tapes, the (K, W) weights, the old-position drift, acceptance
   // counts and per-sweep fractions; or the weights and the six combined energy rows
   DevBuf b_add;
+  // pqa_sr_moments (pqa_sr.hip): the running moments, energy means, weights, a walker chunk's gathered matrix and scales, the slices'
+  // partial tiles, the column description
+  DevBuf b_sr;
   hipEvent_t tb_ev[2] = {nullptr, nullptr};     // pqa_tbdm_sweep: a chunk's ratios produced / consumed
   hipEvent_t tune_ev[2] = {nullptr, nullptr};   // periodic k_orb: timing of the tile-size trials (tp_tune)
   DevBuf b_tpos, b_twgt, b_tlive, b_trat;

@@ -1,0 +1,249 @@
+// Stochastic-reconfiguration moments of the resident walkers (StochasticReconfiguration.avg, stochastic_reconfiguration.py:49-118).
+//
+// The protocol route brings the walkers and every factor's (W x parameters) derivative arrays to the host, gathers the optimised
+// columns there and uploads [dp | E | 1] and w f dp again for one product (pqa_gram).  Everything the estimator needs is on the handle
+// already, so this call leaves it there:
+//   energy_dev       the energy pass of pqa_energy (same draws, same per-walker rows in b_en);
+//   sources          det_coeff: k_pgrad_det (b_pgdet); acoeff / bcoeff: the basis sums the handle keeps (refreshed where a fused sweep
+//                    left them stale); ccoeff: k_j3_pgrad (b_out) - only those the column description names;
+//   k_sr_gather      per walker chunk of at most 256 MiB: the compact row-major A = [dp | E | 1] (Wc, P + 2) and the scale
+//                    s_w = w_w f_w (w: the normalised weight, f: the Pathak-Wagner weight from grad2);
+//   k_sr_syrk        A^T diag(s) A[:, :P] on v_mfma_f64_16x16x4_f64, walkers as the k dimension.  A block of four waves owns a 32 x 32
+//                    tile (one 16 x 16 tile per wave) and a slice of the walkers; 16 walkers of both column panels are staged in LDS per
+//                    step, the right-hand panel scaled by s as it is loaded (w f dp never exists in memory).  dpidpj is symmetric: of
+//                    its tiles only those on or above the diagonal are computed;
+//   k_sr_reduce      the slices' partial tiles summed in slice order (the same bits on every call), the lower triangle mirrored from
+//                    the upper one (dpidpj is exactly symmetric), added to the running moments of the chunks before;
+//   k_sr_means       the six weighted energy means, a fixed-order tree.
+// Only the (P + 2) x P moments and the six means leave the device (and the (W, 6) per-walker energies when the caller asks for them).
+#include "pqa_estim.hpp"
+
+namespace {
+
+constexpr int kSrKB = 16;      // walkers staged per step of k_sr_syrk
+constexpr int kSrLd = 48;      // doubles per staged row: 32 columns + 16 of padding, so rows kq and kq + 1 of an operand read land in
+                               // different halves of the 64 LDS banks (no conflict within a half-wave's ds_read_b64)
+
+struct SrSources {
+  const double* base[4];  // det_coeff, acoeff, bcoeff, ccoeff derivatives, walker-major
+  long stride[4];         // doubles per walker of each
+};
+
+// Pathak-Wagner weight (accumulators.nodal_regularization)
+__device__ __forceinline__ double sr_nodal_f(double grad2, double cutoff) {
+  const double x = 1.0 / (grad2 * (cutoff * cutoff));
+  return x < 1.0 ? x * (9.0 + x * (-15.0 + 7.0 * x)) : 1.0;
+}
+
+// sum of the W weights: one block, a fixed-order tree
+__global__ __launch_bounds__(256) void k_sr_wsum(const double* __restrict__ wts, long W, double* __restrict__ out) {
+  __shared__ double part[256];
+  double a = 0.0;
+  for (long w = threadIdx.x; w < W; w += 256) a += wts[w];
+  a = block_sum256(a, part);
+  if (threadIdx.x == 0) out[0] = a;
+}
+
+// normalised weight of walker w (wts == nullptr: 1 / W)
+__device__ __forceinline__ double sr_weight(const double* wts, const double* wsum, long W, long w) {
+  return wts ? wts[w] / wsum[0] : 1.0 / (double)W;
+}
+
+// out[k] = sum_w w_w en[k][w] for the six energy rows: one block per row, a fixed-order tree
+__global__ __launch_bounds__(256) void k_sr_means(const double* __restrict__ en /*[6][W]*/, const double* __restrict__ wts,
+                                                  const double* __restrict__ wsum, long W, double* __restrict__ out) {
+  __shared__ double part[256];
+  const double* row = en + (size_t)blockIdx.x * W;
+  double a = 0.0;
+  for (long w = threadIdx.x; w < W; w += 256) a += sr_weight(wts, wsum, W, w) * row[w];
+  a = block_sum256(a, part);
+  if (threadIdx.x == 0) out[blockIdx.x] = a;
+}
+
+// One thread per (walker of the chunk, column of A): A[w][i] = derivative column i (i < P), the local energy (P), 1 (P + 1); the
+// thread of column 0 also writes the walker's scale.
+__global__ __launch_bounds__(256) void k_sr_gather(SrSources S, const int* __restrict__ src, const int* __restrict__ pos, int P,
+                                                   const double* __restrict__ en /*[6][W]*/, const double* __restrict__ wts,
+                                                   const double* __restrict__ wsum, double cutoff, long W, long w0, long Wc,
+                                                   double* __restrict__ A /*[Wc][P + 2]*/, double* __restrict__ scale /*[Wc]*/) {
+  const int lda = P + 2;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= Wc * lda) return;
+  const long bw = idx / lda, w = w0 + bw;
+  const int i = (int)(idx - bw * lda);
+  double v;
+  if (i < P) {
+    const int s = src[i];
+    v = S.base[s][(size_t)w * S.stride[s] + pos[i]];
+  } else
+    v = i == P ? en[5 * W + w] : 1.0;
+  A[idx] = v;
+  if (i == 0) scale[bw] = sr_weight(wts, wsum, W, w) * sr_nodal_f(en[4 * W + w], cutoff);
+}
+
+// part[sl] (P + 2, P) += tile (32 bi .., 32 bj ..) of A^T diag(s) A[:, :P] over the walkers of slice sl.  grid = (column blocks,
+// row blocks, slices), block = 256: wave (wi, wj) = (wave >> 1, wave & 1) owns the 16 x 16 tile (2 bi + wi, 2 bj + wj).  Blocks strictly
+// below the diagonal are skipped unless they hold a row >= P (the dpH / dppsi rows); a wave's tile below the diagonal is not stored.
+__global__ __launch_bounds__(256) void k_sr_syrk(const double* __restrict__ A, const double* __restrict__ scale, long Wc, int P, long per,
+                                                 double* __restrict__ part) {
+  __shared__ double La[kSrKB * kSrLd], Lb[kSrKB * kSrLd];
+  const int bj = blockIdx.x, bi = blockIdx.y, sl = blockIdx.z;
+  if (bi > bj && bi * 32 + 31 < P) return;
+  const int lda = P + 2;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, i16 = lane & 15, kq = lane >> 4, wi = wave >> 1, wj = wave & 1;
+  const long k_lo = (long)sl * per, k_hi = k_lo + per < Wc ? k_lo + per : Wc;
+  // staging: element e = t + 256 q of the two 16 x 32 panels: panel e >> 9, row (e >> 5) & 15, column e & 31
+  const int c = t & 31, r0 = t >> 5;  // q advances the row by 8; q >= 2: the right-hand panel
+  const int ca = bi * 32 + c, cb = bj * 32 + c;
+  const bool ain = ca < lda, bin = cb < P;
+  double v[4];
+  auto fetch = [&](long k0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const long row = k0 + r0 + 8 * (q & 1);
+      const bool rin = row < k_hi;
+      if (q < 2) v[q] = (rin && ain) ? A[(size_t)row * lda + ca] : 0.0;
+      else v[q] = (rin && bin) ? A[(size_t)row * lda + cb] * scale[row] : 0.0;
+    }
+  };
+  d4 acc = {0.0, 0.0, 0.0, 0.0};
+  if (k_lo < k_hi) fetch(k_lo);
+  for (long k0 = k_lo; k0 < k_hi; k0 += kSrKB) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) (q < 2 ? La : Lb)[(r0 + 8 * (q & 1)) * kSrLd + c] = v[q];
+    __syncthreads();
+    if (k0 + kSrKB < k_hi) fetch(k0 + kSrKB);  // (the next step's loads fly while this one multiplies)
+#pragma unroll
+    for (int kk = 0; kk < kSrKB / 4; ++kk) {
+      const int row = kk * 4 + kq;
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(La[row * kSrLd + wi * 16 + i16], Lb[row * kSrLd + wj * 16 + i16], acc, 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  const int ti = 2 * bi + wi, tj = 2 * bj + wj;
+  if (ti > tj && ti * 16 + 15 < P) return;
+  // lane holds D[row = kq + 4 r][col = i16]
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int p = ti * 16 + kq + 4 * r, q = tj * 16 + i16;
+    if (p < lda && q < P) part[((size_t)sl * lda + p) * P + q] = acc[r];
+  }
+}
+
+// mom (P + 2, P) = (first ? 0 : mom) + sum over the slices in slice order; element (i, j) of the symmetric block is read at
+// (min, max): the tiles below the diagonal were never written.
+__global__ __launch_bounds__(256) void k_sr_reduce(const double* __restrict__ part, int P, int nslice, int first, double* __restrict__ mom) {
+  const long n = (long)(P + 2) * P;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n) return;
+  const int i = (int)(idx / P), j = (int)(idx - (long)i * P);
+  const long from = (i < P && j < i) ? (long)j * P + i : idx;
+  double s = 0.0;
+  for (int sl = 0; sl < nslice; ++sl) s += part[(size_t)sl * n + from];
+  mom[idx] = first ? s : mom[idx] + s;
+}
+
+}  // namespace
+
+extern "C" int pqa_sr_moments(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff, const double* weights,
+                              double threshold, const double* rot, const double* unif, uint64_t seed, double* en_mean, double* moments,
+                              double* en_walker) {
+  // argument checks first: they need nothing but the handle's host-side sizes
+  if (P < 1) FAIL("pqa_sr_moments: P must be at least 1");
+  if (!src || !pos || !en_mean || !moments) FAIL("pqa_sr_moments: src, pos, en_mean and moments must not be NULL");
+  if (!(nodal_cutoff > 0.0)) FAIL("pqa_sr_moments: nodal_cutoff must be positive");
+  if (h->cplx) FAIL("pqa_sr_moments: complex orbitals / twisted cell (outside the device scope: use the protocol route)");
+  const long size[4] = {h->has_slater ? (long)h->ndet : 0, h->has_j2 ? (long)h->natom * h->na * 2 : 0, h->has_j2 ? (long)h->nb * 3 : 0,
+                        h->has_j3 ? (long)h->natom * h->na3 * h->na3 * h->nb3 * 3 : 0};
+  bool need[4] = {false, false, false, false};
+  for (int i = 0; i < P; ++i) {
+    if (src[i] < 0 || src[i] > 3) FAIL("pqa_sr_moments: src must be 0 (det_coeff), 1 (acoeff), 2 (bcoeff) or 3 (ccoeff)");
+    if (pos[i] < 0 || pos[i] >= size[src[i]]) FAIL("pqa_sr_moments: pos outside the parameter src names (or the handle has no such factor)");
+    need[src[i]] = true;
+  }
+  const size_t nmom = (size_t)(P + 2) * P;
+  if (nmom * sizeof(double) > kChunkScratchBytes) FAIL("pqa_sr_moments: the (P + 2) x P moments exceed the 256 MiB scratch limit (use the protocol route)");
+  if (h->W == 0) FAIL("state not initialised (call pqa_wf_recompute)");
+  TRY(sync_aos(h));
+  HIPCHK(hipSetDevice(h->device));
+  const long W = h->W;
+  h->saved_valid = false;  // (as pqa_energy: the saved orbital rows of a gradient_value call are overwritten)
+  TRY(energy_dev(h, threshold, rot, unif, seed, 0u));
+  const double* d_en = (const double*)h->b_en.p;
+  // derivative sources
+  SrSources S{};
+  if (need[0]) {
+    TRY(slater_value_dev(h));  // sign / log of the determinant expansion -> b_sign, b_log
+    TRY(ensure(h, h->b_pgdet, (size_t)W * h->ndet * sizeof(double)));
+    hipLaunchKernelGGL((k_pgrad_det<>), dim3((unsigned)((W * h->ndet + 255) / 256)), dim3(256), 0, h->stream, h->S, h->st,
+                       (const double*)h->b_sign.p, (const double*)h->b_log.p, W, (double*)h->b_pgdet.p);
+    TRY(check_launch(h, "k_pgrad_det"));
+    S.base[0] = (const double*)h->b_pgdet.p; S.stride[0] = size[0];
+  }
+  if (need[1] || need[2]) {
+    TRY(jas_refresh(h));
+    S.base[1] = h->js.avalues; S.stride[1] = size[1];
+    S.base[2] = h->js.bvalues; S.stride[2] = size[2];
+  }
+  if (need[3]) {
+    const size_t lds = ((size_t)h->N * h->natom * h->na3 + (size_t)h->N * (h->N - 1) / 2 * h->nb3) * sizeof(double);
+    if (lds > 150 * 1024) FAIL("three-body parameter gradient: the a/b value tables of one walker do not fit LDS");
+    TRY(ensure(h, h->b_out, (size_t)W * size[3] * sizeof(double)));
+    if (lds > 64 * 1024) TRY(raise_lds_limit(h, reinterpret_cast<const void*>(k_j3_pgrad<>)));
+    hipLaunchKernelGGL((k_j3_pgrad<>), dim3((unsigned)W), dim3(64), lds, h->stream, h->S, h->js, (double*)h->b_out.p);
+    TRY(check_launch(h, "k_j3_pgrad"));
+    S.base[3] = (const double*)h->b_out.p; S.stride[3] = size[3];
+  }
+  // scratch: [moments | means (6) | weight sum (1) | weights (W) | per-walker energies (W, 6) | scale (Wc) | A (Wc, P + 2) |
+  // partials (nslice, P + 2, P) | src, pos]
+  const int lda = P + 2;
+  const long Wc = walker_chunk(W, (size_t)lda * sizeof(double));
+  const int nbi = (lda + 31) / 32, nbj = (P + 31) / 32;
+  long nslice = std::min<long>(std::max<long>(1, 1024 / ((long)nbi * nbj)), std::max<long>(1, Wc / 64));
+  nslice = std::max<long>(1, std::min<long>(nslice, (long)(kChunkScratchBytes / (nmom * sizeof(double)))));
+  const size_t nw = weights ? (size_t)W : 0, nenw = en_walker ? (size_t)6 * W : 0;
+  const size_t ndbl = nmom + 6 + 1 + nw + nenw + (size_t)Wc + (size_t)Wc * lda + (size_t)nslice * nmom;
+  TRY(ensure(h, h->b_sr, ndbl * sizeof(double) + (size_t)2 * P * sizeof(int)));
+  double* d_mom = (double*)h->b_sr.p;
+  double* d_mean = d_mom + nmom;
+  double* d_wsum = d_mean + 6;
+  double* d_wts = d_wsum + 1;
+  double* d_enw = d_wts + nw;
+  double* d_scale = d_enw + nenw;
+  double* d_A = d_scale + Wc;
+  double* d_part = d_A + (size_t)Wc * lda;
+  int* d_src = (int*)(d_part + (size_t)nslice * nmom);
+  int* d_pos = d_src + P;
+  TRY(copy_in(h, d_src, src, (size_t)P * sizeof(int)));
+  TRY(copy_in(h, d_pos, pos, (size_t)P * sizeof(int)));
+  const double* wts = nullptr;
+  if (weights) {
+    TRY(copy_in(h, d_wts, weights, (size_t)W * sizeof(double)));
+    hipLaunchKernelGGL(k_sr_wsum, dim3(1), dim3(256), 0, h->stream, (const double*)d_wts, W, d_wsum);
+    TRY(check_launch(h, "k_sr_wsum"));
+    wts = d_wts;
+  }
+  hipLaunchKernelGGL(k_sr_means, dim3(6), dim3(256), 0, h->stream, d_en, wts, (const double*)d_wsum, W, d_mean);
+  TRY(check_launch(h, "k_sr_means"));
+  for (long w0 = 0; w0 < W; w0 += Wc) {
+    const long wc = std::min(Wc, W - w0);
+    const long ns = std::min<long>(nslice, std::max<long>(1, wc / 64));
+    const long per = ((wc + ns - 1) / ns + kSrKB - 1) / kSrKB * kSrKB;  // walkers per slice, whole staging steps
+    hipLaunchKernelGGL(k_sr_gather, dim3((unsigned)((wc * lda + 255) / 256)), dim3(256), 0, h->stream, S, (const int*)d_src,
+                       (const int*)d_pos, P, d_en, wts, (const double*)d_wsum, nodal_cutoff, W, w0, wc, d_A, d_scale);
+    TRY(check_launch(h, "k_sr_gather"));
+    hipLaunchKernelGGL(k_sr_syrk, dim3((unsigned)nbj, (unsigned)nbi, (unsigned)ns), dim3(256), 0, h->stream, (const double*)d_A,
+                       (const double*)d_scale, wc, P, per, d_part);
+    TRY(check_launch(h, "k_sr_syrk"));
+    hipLaunchKernelGGL(k_sr_reduce, dim3((unsigned)((nmom + 255) / 256)), dim3(256), 0, h->stream, (const double*)d_part, P, (int)ns,
+                       (int)(w0 == 0), d_mom);
+    TRY(check_launch(h, "k_sr_reduce"));
+  }
+  TRY(copy_in(h, moments, d_mom, nmom * sizeof(double)));
+  if (en_walker) {
+    transpose(h, d_en, d_enw, 6, W);  // rows (6, W) -> (W, 6)
+    TRY(check_launch(h, "k_transpose"));
+    TRY(copy_in(h, en_walker, d_enw, (size_t)6 * W * sizeof(double)));
+  }
+  return copy_out(h, en_mean, d_mean, 6 * sizeof(double));
+}

@@ -31,11 +31,11 @@ class StochasticReconfigurationWfbyWf:
 
     multiple_wf = True
 
-    def __init__(self, enacc, transform, eps=1e-3):
+    def __init__(self, enacc, transform, eps=1e-3, route=None):
         self.enacc = enacc
         self.transform = transform
         self.eps = eps
-        self._onewf = StochasticReconfiguration(enacc, transform, eps)
+        self._onewf = StochasticReconfiguration(enacc, transform, eps, route=route)  # route: of the single-state accumulator's avg
 
     def onewf(self):
         return self._onewf

@@ -9,7 +9,9 @@ Philox stream seeded from ``numpy.random`` (or from explicit tapes for trajector
 tests).  With ``EnergyAccumulator``s only, the energy evaluation is fused into the same call; any
 other accumulator (density matrices, parameter gradients, ...) is called on the host after every
 device sweep, on the walkers fetched from the device, and talks to the wave function through the
-protocol entry points as it would in the reference.
+protocol entry points as it would in the reference.  The exception: ``StochasticReconfiguration``
+accumulators on their device route (``accumulators.sr_route``) take their averages from the resident
+state after every sweep (``pqa_sr_moments``), and the walkers stay on the device until the block ends.
 
 An ``AddWF`` whose components are in the fused scope (``pyqmc_amd/addwf.py``) is moved by ``pqa_add_sweeps``, one call per sweep, with
 host-drawn tapes; its accumulators run on the fetched walkers after every sweep.
@@ -73,6 +75,39 @@ def _vmc_worker_host_accumulators(dev, wf, configs, tstep, nsteps, accumulators,
         t1 = time.perf_counter()
         for k, accumulator in accumulators.items():
             for m, res in accumulator.avg(configs, wf).items():
+                block_avg[k + m] = block_avg.get(k + m, 0.0) + res / nsteps
+        t_move, t_acc, acc_sum = t_move + (t1 - t0), t_acc + (time.perf_counter() - t1), acc[-1]
+    block_avg["acceptance"] = acc_sum
+    block_avg["move time"] = t_move / nsteps
+    block_avg["accumulator time"] = t_acc / nsteps
+    return block_avg, configs
+
+
+def _vmc_worker_resident_accumulators(dev, wf, configs, tstep, nsteps, accumulators, tapes, seed, state_current):
+    """Device sweeps, device accumulators: every accumulator is a ``StochasticReconfiguration`` on its device route, so after every
+    sweep (one ``pqa_vmc_sweeps`` call, keyed as in ``_vmc_worker_host_accumulators``) each ``avg_resident(wf)`` takes its averages
+    from the state the sweep left (``pqa_sr_moments``), in dictionary order; the ``np.random`` draws come in the same order as on
+    the host-accumulator path.  Open systems fetch the walkers once, after the last sweep; periodic containers carry the wrap counters
+    of every sweep call and are fetched after each."""
+    if seed is None:
+        seed = int(np.random.randint(0, 2**31 - 1))
+    if not state_current:
+        wf.recompute(configs)
+    block_avg = {}
+    t_move = t_acc = 0.0
+    acc_sum = 0.0
+    for step in range(nsteps):
+        t0 = time.perf_counter()
+        g, u = tapes.get("gauss"), tapes.get("unif")
+        acc, _, rec = dev.vmc_sweeps(tstep, 1, gauss=None if g is None else g[step : step + 1], unif=None if u is None else u[step : step + 1],
+                                     seed=seed * nsteps + step, energy=False, record="record" in tapes)
+        if "record" in tapes:
+            tapes["record"].append(rec)
+        if dev.pbc or step == nsteps - 1:
+            _fetch(dev, configs)
+        t1 = time.perf_counter()
+        for k, accumulator in accumulators.items():
+            for m, res in accumulator.avg_resident(wf).items():
                 block_avg[k + m] = block_avg.get(k + m, 0.0) + res / nsteps
         t_move, t_acc, acc_sum = t_move + (t1 - t0), t_acc + (time.perf_counter() - t1), acc[-1]
     block_avg["acceptance"] = acc_sum
@@ -147,6 +182,11 @@ def vmc_worker(wf, configs, tstep, nsteps, accumulators, tapes=None, seed=None, 
         raise NotOnOneDeviceError("pyqmc_amd.vmc_worker drives a wave function that lives on one device handle (generate_wf); for anything else "
                         "run the reference's own pyqmc.method.mc.vmc_worker over the protocol objects (INTEGRATION.md)")
     if not all(isinstance(a, EnergyAccumulator) for a in accumulators.values()):
+        from .accumulators import StochasticReconfiguration
+
+        srs = [a for a in accumulators.values() if type(a) is StochasticReconfiguration]
+        if nsteps > 0 and len(srs) == len(accumulators) and all([a.resolve_route(wf) == "device" for a in srs]):
+            return _vmc_worker_resident_accumulators(dev, wf, configs, tstep, nsteps, accumulators, tapes or {}, seed, state_current)
         return _vmc_worker_host_accumulators(dev, wf, configs, tstep, nsteps, accumulators, tapes or {}, seed, state_current)
     tapes = tapes or {}
     if seed is None:

@@ -291,6 +291,26 @@ class DeviceWF:
                   _ffi.ptr(logpsi), _ffi.ptr(en))
         return logpsi, en
 
+    def sr_moments(self, src, pos, nodal_cutoff, weights=None, threshold=10.0, rot=None, unif=None, seed=0, per_walker=False):
+        """``pqa_sr_moments``: the moments of ``StochasticReconfiguration.avg`` from the resident state.  Column i of the serialised
+        derivative matrix is flat entry ``pos[i]`` of the parameter ``src[i]`` (0 det_coeff, 1 acoeff, 2 bcoeff, 3 ccoeff);
+        ``weights`` (W) are normalised by their sum (None: 1 / W); ``threshold`` / ``rot`` / ``unif`` / ``seed`` as in ``energy``.
+        Returns (en_mean (6), moments (P + 2, P): rows dpidpj, dpH, dppsi[, en_walker (W, 6) with ``per_walker``])."""
+        src, pos = np.ascontiguousarray(src, dtype=np.int32), np.ascontiguousarray(pos, dtype=np.int32)
+        P = len(src)
+        if src.shape != (P,) or pos.shape != (P,):
+            raise ValueError(f"src and pos must be one-dimensional and equally long, got {src.shape}, {pos.shape}")
+        w = None if weights is None else _ffi.f64(weights)
+        if w is not None and w.shape != (self.W,):
+            raise ValueError(f"weights ({self.W},) expected, got {w.shape}")
+        rot = None if rot is None else _ffi.f64(rot)
+        unif = None if unif is None else _ffi.f64(unif)
+        en_mean, moments = np.empty(6), np.empty((P + 2, P))
+        en_walker = np.empty((self.W, 6)) if per_walker else None
+        self.call("pqa_sr_moments", int(P), _ffi.ptr(src), _ffi.ptr(pos), float(nodal_cutoff), _ffi.ptr(w), float(threshold), _ffi.ptr(rot),
+                  _ffi.ptr(unif), int(seed), _ffi.ptr(en_mean), _ffi.ptr(moments), _ffi.ptr(en_walker))
+        return (en_mean, moments, en_walker) if per_walker else (en_mean, moments)
+
     def variance(self, acoeff, bcoeff, eoff, grad=False, ke=False):
         """``pqa_variance``: population variance over the resident walkers of ``eoff + ke_k`` at K sets of two-body Jastrow
         coefficients, acoeff (K, natom, na, 2) and bcoeff (K, nb, 3), with ``eoff`` (W) the fixed part of the local energy ->

@@ -1,0 +1,88 @@
+"""Gradient-VMC timings on one MI355X -> profiles/sr_bench.jsonl (one JSON line per case).
+
+    python tools/sr_bench.py [--walkers 16384 65536] [--sweeps 10] [--reps 2] [--out profiles/sr_bench.jsonl]
+
+One vmc_worker block of `sweeps` sweeps for the (H2O)8 cluster with the gradient accumulator of line minimisation
+(gradient_generator, default_to_opt), on the device route (pqa_sr_moments on the resident state) and on the protocol route
+(walkers and derivative arrays through the host, pqa_gram), alternately in one process.  Each route gets a warm-up block first; the
+block averages of the two routes from the same walkers, sweep keys and energy keys are checked equal (1e-9) before anything is
+timed.  Wall clock of the whole block (both routes end with the walkers on the host), the best of `reps`.
+"""
+
+import argparse
+import copy
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+import pyqmc_amd as pa  # noqa: E402
+from pyqmc_amd import systems  # noqa: E402
+from pyqmc_amd import wf as pwf  # noqa: E402
+from pyqmc_amd.accumulators import gradient_generator  # noqa: E402
+
+ROUTES = ("device", "protocol")
+
+
+def case(W, sweeps, reps):
+    mol = systems.water_cluster()
+    wf = pa.generate_wf(mol, systems.random_mf(mol))
+    rng = np.random.default_rng(11)  # (a non-trivial Jastrow: small random coefficients, the electron-electron cusp row kept)
+    ja = wf.wf_factors[1].parameters
+    wf.parameters["wf2acoeff"] = 0.05 * rng.standard_normal(np.shape(ja["acoeff"]))
+    wf.parameters["wf2bcoeff"] = np.concatenate([np.asarray(ja["bcoeff"])[:1], 0.05 * rng.standard_normal((np.shape(ja["bcoeff"])[0] - 1, 3))])
+    start = pa.initial_guess(mol, W, rng=np.random.default_rng(2))
+    sr = {r: gradient_generator(mol, wf, pwf.default_to_opt(wf), route=r) for r in ROUTES}
+
+    def block(route, nsteps, seed):
+        sr[route].enacc.seed, sr[route].enacc._calls = 1000 * seed, 0
+        t0 = time.perf_counter()
+        blk, _ = pa.vmc_worker(wf, copy.deepcopy(start), 0.3, nsteps, {"pgrad": sr[route]}, seed=seed)
+        dt = time.perf_counter() - t0
+        assert sr[route].last_route == route
+        return blk, dt
+
+    warm = {r: block(r, 2, 1)[0] for r in ROUTES}  # (warm-up, and the check that the routes agree)
+    worst = 0.0
+    for k, v in warm["protocol"].items():
+        if "time" not in k:
+            worst = max(worst, float(np.max(np.abs(warm["device"][k] - v)) / max(np.max(np.abs(v)), 1e-300)))
+    assert worst < 1e-9, worst
+    best = {r: (np.inf, None) for r in ROUTES}
+    for rep in range(reps):
+        for r in ROUTES:
+            blk, dt = block(r, sweeps, 2 + rep)
+            if dt < best[r][0]:
+                best[r] = (dt, blk)
+    row = {"what": "gradient VMC block (vmc_worker, gradient_generator)", "system": "(H2O)8", "walkers": W, "sweeps": sweeps,
+           "nparams": int(sr["device"].transform.nparams), "routes_max_relerr": worst}
+    for r in ROUTES:
+        dt, blk = best[r]
+        row.update({f"seconds_{r}": dt, f"move_ms_per_sweep_{r}": 1e3 * float(blk["move time"]),
+                    f"accumulator_ms_per_sweep_{r}": 1e3 * float(blk["accumulator time"])})
+    row["speedup"] = row["seconds_protocol"] / row["seconds_device"]
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--walkers", type=int, nargs="+", default=[16384, 65536])
+    ap.add_argument("--sweeps", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sr_bench.jsonl"))
+    a = ap.parse_args()
+    rows = [case(W, a.sweeps, a.reps) for W in a.walkers]
+    if a.out:
+        with open(a.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
