@@ -457,6 +457,29 @@ int pqa_tbdm_accumulate(pqa_handle_t* h, int k, int64_t nconf, int nea, int neb,
    through the protocol route (pyqmc_amd.TBDMAccumulator: testvalue, updateinternals, testvalue_many). */
 int pqa_tbdm_sweep(pqa_handle_t* wf, pqa_handle_t* ev, int k, int spin_a, int spin_b, const int32_t* assign_a, const int32_t* assign_b,
                    const int32_t* ijkl, int ntuple, int first, int64_t walker_chunk, double* ratio);
+/* The whole one-body estimator of one evaluation (obdm.py:139-193) with the ratios formed on the device: wf holds the wave function
+   with the configurations as its resident walkers (wf's W = nconf), ev the estimator's orbitals, whose `slot` holds the last
+   nsweeps (or more) samples of a pqa_dm_walk.  es (ne) host: the listed electrons, any order, either spin, none twice.  Their
+   coordinates are gathered from wf's resident walkers on the device and ev's orbitals are evaluated there into the slot (what
+   pqa_dm_points does from a host array).  Sweep s = 0 .. nsweeps-1 uses kept sample s: walker w takes the auxiliary walker
+   assign[s][w] (assign (nsweeps,W) host), or, with assign = NULL, floor(u naux) with u from Philox keyed by (seed; walker, sweep);
+   assign_out (nsweeps,W) host receives the assignments used (may be NULL).  ratio[s][w][e] = Psi(r_e -> r')/Psi in closed form from
+   wf's resident state (pqa_obdm.hip: the single-move rows v = phi . inverse, the determinant-weighted sum for several determinants,
+   times exp of the two-body Jastrow difference); ratio (nsweeps,W,ne) host receives them, or NULL.  wf's state is not modified.
+   mean = 0: ev's per-walker accumulators end as nsweeps pqa_obdm_accumulate calls leave them (first != 0 starts them, otherwise the
+   sweeps are added; pqa_dm_fetch reads them).  mean != 0 (first must be set): value_mean (norb,norb) and norm_mean (norb) host
+   receive the means over walkers and sweeps, value_mean = sum_s B_s^T T_s / (W nsweeps) on the fp64 matrix cores with the walkers
+   as the k dimension; no per-walker (norb,norb) array exists in this mode.  walker_chunk: walkers per scratch chunk (0: the
+   estimator units' own bound; the mean mode takes whole 64-walker slices).  Every sum has a fixed order that does not depend on
+   the chunk.  Fused scope: wf real and untwisted with a Slater factor (one or more determinants), with or without the two-body
+   Jastrow, no three-body factor, open or periodic at Gamma; ev real, on the same device; ne >= 1.  Everything else is refused (<0):
+   those go through the protocol route (pyqmc_amd.OBDMAccumulator: testvalue_many, pqa_obdm_accumulate). */
+int pqa_obdm_sweeps(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
+                    uint64_t seed, int mean, int first, int64_t walker_chunk, double* ratio, int32_t* assign_out, double* value_mean,
+                    double* norm_mean);
+/* Device bytes ev holds for pqa_obdm_sweeps: scratch = the mean mode's panels, partial tiles and sums plus a walker chunk's ratios;
+   per_walker = the per-walker accumulators (value, norms), which the mean mode never allocates. */
+int pqa_obdm_bytes(pqa_handle_t* ev, int64_t* scratch, int64_t* per_walker);
 /* Read an accumulator times `scale`: which = 0 value (ncol = entries per configuration, doubled when complex), 1 norm /
    norm_a, 2 norm_b (ncol = orbitals).  mean = 0: (nconf,ncol); mean != 0: (ncol,) averaged over the configurations on
    the device (the accumulators' avg(), obdm.py:195-197). */

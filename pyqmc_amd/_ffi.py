@@ -129,6 +129,9 @@ _PROTOTYPES = {
     "pqa_tbdm_accumulate": (C.c_int, [_H, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                       C.c_int, C.c_int]),
     "pqa_tbdm_sweep": (C.c_int, [_H, _H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    "pqa_obdm_sweeps": (C.c_int, [_H, _H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pqa_obdm_bytes": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pqa_dm_fetch": (C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]),
     "pqa_gram": (C.c_int, [_H, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pqa_s2": (C.c_int, [_H, C.c_void_p, C.c_void_p]),

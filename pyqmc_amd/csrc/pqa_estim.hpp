@@ -1,4 +1,4 @@
-// Code shared by the fused estimator units (pqa_s2, pqa_symmetry, pqa_sq, pqa_correlated, pqa_overlap, pqa_variance, pqa_tbdm, pqa_sr); no
+// Code shared by the fused estimator units (pqa_s2, pqa_symmetry, pqa_sq, pqa_correlated, pqa_overlap, pqa_variance, pqa_tbdm, pqa_sr, pqa_obdm); no
 // other unit includes it.
 //
 // Basis-resolved two-body Jastrow rows: U = sum_p c_p B_p(R) is linear in the coefficients (acoeff entries (atom, k, spin), then

@@ -165,7 +165,10 @@ struct pqa_handle {
   // pqa_sr_moments (pqa_sr.hip): the running moments, energy means, weights, a walker chunk's gathered matrix and scales, the slices'
   // partial tiles, the column description
   DevBuf b_sr;
-  hipEvent_t tb_ev[2] = {nullptr, nullptr};     // pqa_tbdm_sweep: a chunk's ratios produced / consumed
+  // pqa_obdm_sweeps (pqa_obdm.hip), on the evaluator's handle in the mean mode: a walker chunk's panels T, B and norm terms, the slices'
+  // partial tiles, the running sums and their scaled copy
+  DevBuf b_obdm;
+  hipEvent_t tb_ev[2] = {nullptr, nullptr};     // pqa_tbdm_sweep / pqa_obdm_sweeps: a chunk's ratios produced / consumed
   hipEvent_t tune_ev[2] = {nullptr, nullptr};   // periodic k_orb: timing of the tile-size trials (tp_tune)
   DevBuf b_tpos, b_twgt, b_tlive, b_trat;
   DevBuf b_tmcnt, b_tmoff, b_tmpass, b_tmamp, b_tmacc, b_tmidx, b_tmapos, b_tmu, b_tmtile, b_tmaoff, b_tmptw, b_tmmarks, b_dmcw, b_dmcold, b_dmcr2, b_dmcout;

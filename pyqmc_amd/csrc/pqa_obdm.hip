@@ -1,0 +1,386 @@
+// One-body density matrix (OBDMAccumulator, pyqmc/observables/obdm.py:139-193) from the resident state: every auxiliary sweep of one
+// evaluation in one call, read-only on the wave function's handle, contracted on the orbital evaluator's handle without a trip
+// through the host.
+//
+// For walker w and sweep s let r' be the auxiliary walker assign[s][w] of kept sample s of the evaluator's slot, F = f(r') / norb,
+// and e run over the listed electrons es:
+//
+//   b[w][i]    = phi_i(r') / F                                                   (the slot's kept rows and densities)
+//   R[w][e]    = Psi(r_e -> r') / Psi = (sum_D w_D v_D(r')[e] / sum_D w_D) exp(A_e(r'))
+//   v_D(q)[e]  = sum_k phi^s_{occ_D[k]}(q) T^s_D[e][k]                           (the single-move ratio; T the electron-major inverse)
+//   A_e(q)     = U(e -> q) - U                                                   (two-body Jastrow factor, as k_tbdm_pairs forms it)
+//   t[w][j]    = sum_e R[w][e] phi_j(r_e)
+//   value[w]  += b[w] (x) t[w],   norm[w][i] += phi_i(r')^2 / F
+//
+// The estimator is a rank-one update per walker and sweep, so its walker mean is a thin product, value_mean = B^T T / W with the
+// (W, norb) panels B and T: k_obdm_mean runs it on v_mfma_f64_16x16x4_f64 with the walkers as the k dimension, and no per-walker
+// (norb, norb) matrix exists in that mode.  The per-walker mode hands the ratios to k_obdm_acc (pqa_dm.hpp) on the device, after
+// which the evaluator holds exactly what pqa_obdm_accumulate leaves.
+//
+// Every sum has a fixed order that does not depend on the walker chunk: a slice of the mean product is kSlice consecutive walkers
+// counted from walker 0 (chunks hold whole slices), a slice's partial tile is one MFMA chain, and k_obdm_reduce adds the partial tiles
+// to the running sums one after the other in slice order, sweep after sweep.
+#include "pqa_estim.hpp"
+
+namespace {
+
+constexpr int kSlice = 64;  // walkers per slice of the mean product: 16 k-steps of the 16x16x4 MFMA
+constexpr uint32_t kStreamAssign = 0x4f42u;  // Philox counter word of the assignment draws
+
+// xe[(w ne + t)][3] = coordinates of listed electron es[t] of resident walker w
+__global__ __launch_bounds__(256) void k_obdm_epts(const double* __restrict__ x, const int* __restrict__ es, int ne, int N, long W,
+                                                   double* __restrict__ xe) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= W * ne) return;
+  const long w = i / ne;
+  const int t = (int)(i - w * ne);
+  const double* p = x + ((size_t)w * N + es[t]) * 3;
+  xe[3 * i] = p[0]; xe[3 * i + 1] = p[1]; xe[3 * i + 2] = p[2];
+}
+
+// pts[wl][3] = pos[assign[w0 + wl]] for the wc walkers of a chunk.  draw: the assignment is drawn here, floor(u naux) with u from
+// Philox keyed by (seed; walker, sweep), and stored.
+__global__ __launch_bounds__(256) void k_obdm_gather(const double* __restrict__ pos, int* __restrict__ assign, long w0, long wc, int draw,
+                                                     uint64_t seed, uint32_t sweep, long naux, double* __restrict__ pts) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= wc) return;
+  const long w = w0 + i;
+  int a;
+  if (draw) {
+    const Philox ph = philox(seed, (uint32_t)w, sweep, PQA_STREAM_ACCEPT, kStreamAssign);
+    const long k = (long)(u01(ph.c[0], ph.c[1]) * (double)naux);
+    a = (int)(k < naux ? k : naux - 1);
+    assign[w] = a;
+  } else a = assign[w];
+  const double* p = pos + 3 * (size_t)a;
+  pts[3 * i] = p[0]; pts[3 * i + 1] = p[1]; pts[3 * i + 2] = p[2];
+}
+
+// v[d n + i] = sum_k phi[occ_d[k]] T_d[i][k] for every unique determinant d of spin s and electron i (k_tbdm_pairs' product with
+// one right-hand side): GS = 2^m >= min(n, 64) lanes share a row of the inverse, a butterfly over the group adds the partial sums.
+__device__ __forceinline__ void inverse_rows(const SysDev& S, const SlaterState& st, int s, long w, const double* __restrict__ phi, double* v) {
+  const int lane = threadIdx.x, n = s ? S.ndn : S.nup, D = S.ndet_s[s];
+  int GS = 1;
+  while (GS < n && GS < 64) GS <<= 1;
+  const int per = 64 / GS, g = lane / GS, j = lane & (GS - 1);
+  const double* Tw = st.T[s] + (size_t)w * D * n * n;
+  for (int r0 = 0; r0 < D * n; r0 += per) {
+    const int r = r0 + g;
+    const bool act = r < D * n;
+    double p = 0.0;
+    if (act) {
+      const int* occ = S.det_occ[s] + (size_t)(r / n) * n;
+      for (int k = j; k < n; k += GS) p += phi[occ[k]] * Tw[(size_t)r * n + k];
+    }
+    for (int off = 1; off < GS; off <<= 1) p += __shfl_xor(p, off, 64);
+    if (act && j == 0) v[r] = p;
+  }
+}
+
+template <bool PBC>
+__device__ __forceinline__ double pair_u(const SysDev& S, double dx, double dy, double dz, int col, double irb) {
+  if (PBC) min_image_j(S, dx, dy, dz);
+  double u = 0.0;
+  jas_basis<true>(S, sqrt(dx * dx + dy * dy + dz * dz), irb, [&](int l, double v) { u += S.bcoeff[l * 3 + col] * v; });
+  return u;
+}
+template <bool PBC>
+__device__ __forceinline__ double ion_u(const SysDev& S, double qx, double qy, double qz, int spin, double ira) {
+  double u = 0.0;
+  for (int I = 0; I < S.natom; ++I) {
+    double dx = qx - S.atom_xyz[3 * I], dy = qy - S.atom_xyz[3 * I + 1], dz = qz - S.atom_xyz[3 * I + 2];
+    if (PBC) min_image_j(S, dx, dy, dz);
+    jas_basis<false>(S, sqrt(dx * dx + dy * dy + dz * dz), ira, [&](int k, double v) { u += S.acoeff[(I * S.na + k) * 2 + spin] * v; });
+  }
+  return u;
+}
+
+// One wave per walker of the chunk.  phi_up / phi_dn [wc][nmo_s]: the wave function's orbitals at the walkers' r' (a spin without a
+// listed electron: not read); pts [wc][3]; es [ne]; cfg [W][ne][norb]: the evaluator's orbitals at the listed electrons; rows / f: the
+// kept sample's orbital rows [naux][norb] and densities; assign [W].  Outputs (each may be NULL): R [wc][ne], the panels T, B, Nn
+// [wc][norb] (t, b and the norm term of the walker).
+// Dynamic LDS (doubles): 3 N coordinates, 2 ne (Jastrow differences, ratios), ndet weights (several determinants), the v tables
+// ndet_up nup + ndet_dn ndn.
+template <bool PBC>
+__global__ __launch_bounds__(64) void k_obdm_rt(SysDev S, SlaterState st, JastrowState js, const double* __restrict__ phi_up,
+                                                const double* __restrict__ phi_dn, const double* __restrict__ pts,
+                                                const int* __restrict__ es, int ne, long w0, int jas, int spins,
+                                                const double* __restrict__ cfg, const double* __restrict__ rows,
+                                                const double* __restrict__ f, const int* __restrict__ assign, int norb,
+                                                double* __restrict__ R, double* __restrict__ T, double* __restrict__ B,
+                                                double* __restrict__ Nn) {
+  extern __shared__ double lds[];
+  const int N = S.nelec, lane = threadIdx.x, D = S.ndet;
+  const long wl = blockIdx.x, w = w0 + wl;
+  double* xs = lds;                     // [N][3]
+  double* A = lds + 3 * N;              // [ne]
+  double* Rl = A + ne;                  // [ne]
+  double* wd = Rl + ne;                 // [D] (D > 1)
+  double* vu = wd + (D > 1 ? D : 0);    // [ndet_up][nup]
+  double* vd = vu + (size_t)S.ndet_s[0] * S.nup;  // [ndet_dn][ndn]
+  const double* xw = js.x + (size_t)w * N * 3;
+  for (int q = lane; q < 3 * N; q += 64) xs[q] = xw[q];
+  const double qx = pts[3 * wl], qy = pts[3 * wl + 1], qz = pts[3 * wl + 2];
+  __syncthreads();
+  if (jas) {
+    const double irb = 1.0 / S.rcut_b, ira = 1.0 / S.rcut_a;
+    for (int t = lane; t < ne; t += 64) {  // a lane owns a listed electron
+      const int e = es[t], se = e >= S.nup;
+      const double ex = xs[3 * e], ey = xs[3 * e + 1], ez = xs[3 * e + 2];
+      double un = 0.0, uo = 0.0;
+      for (int j = 0; j < N; ++j) {
+        if (j == e) continue;
+        const int col = se + (j >= S.nup);
+        const double jx = xs[3 * j], jy = xs[3 * j + 1], jz = xs[3 * j + 2];
+        un += pair_u<PBC>(S, qx - jx, qy - jy, qz - jz, col, irb);
+        uo += pair_u<PBC>(S, ex - jx, ey - jy, ez - jz, col, irb);
+      }
+      un += ion_u<PBC>(S, qx, qy, qz, se, ira);
+      uo += ion_u<PBC>(S, ex, ey, ez, se, ira);
+      A[t] = un - uo;
+    }
+  }
+  double den = 1.0;
+  if (D > 1) {  // determinant weights relative to the largest |determinant|
+    const double ref = det_ref(S, st, w);
+    double t = 0.0;
+    for (int Dd = lane; Dd < D; Dd += 64) {
+      const double x = det_weight(S, st, w, Dd, ref);
+      wd[Dd] = x;
+      t += x;
+    }
+    den = wave_sum(t);
+  }
+  if (spins & 1) inverse_rows(S, st, 0, w, phi_up + (size_t)wl * S.nmo[0], vu);
+  if (spins & 2) inverse_rows(S, st, 1, w, phi_dn + (size_t)wl * S.nmo[1], vd);
+  __syncthreads();
+  for (int t = lane; t < ne; t += 64) {
+    const int e = es[t], s = e >= S.nup, i = e - s * S.nup, n = s ? S.ndn : S.nup;
+    const double* v = s ? vd : vu;
+    double ratio;
+    if (D > 1) {
+      ratio = 0.0;
+      for (int Dd = 0; Dd < D; ++Dd) ratio += wd[Dd] * v[(size_t)S.det_map[s * D + Dd] * n + i];
+      ratio /= den;
+    } else ratio = v[i];
+    if (jas) ratio *= exp(A[t]);
+    Rl[t] = ratio;
+    if (R) R[(size_t)wl * ne + t] = ratio;
+  }
+  if (!T) return;
+  __syncthreads();
+  const int a = assign[w];
+  const double* brow = rows + (size_t)a * norb;
+  const double F = f[a] / norb;
+  const double* cw = cfg + (size_t)w * ne * norb;
+  for (int j = lane; j < norb; j += 64) {
+    double s = 0.0;
+    for (int t = 0; t < ne; ++t) s += Rl[t] * cw[(size_t)t * norb + j];
+    const double b = brow[j];
+    T[(size_t)wl * norb + j] = s;
+    B[(size_t)wl * norb + j] = b / F;
+    Nn[(size_t)wl * norb + j] = (b * b) / F;
+  }
+}
+
+// Partial tiles of B^T T and partial column sums of Nn for the slices of a chunk: one wave per 16 x 16 tile (p0, q0) and slice of
+// kSlice walkers.  part [slice][P P + P]: the tile's entries, and from the waves of the q0 = 0 tiles the norm columns p0 .. p0 + 15
+// summed walker after walker.
+__global__ __launch_bounds__(64) void k_obdm_mean(const double* __restrict__ B, const double* __restrict__ T, const double* __restrict__ Nn,
+                                                  long wc, int P, double* __restrict__ part) {
+  const int lane = threadIdx.x, i16 = lane & 15, kq = lane >> 4;
+  const int p0 = blockIdx.x * 16, q0 = blockIdx.y * 16;
+  const long sl = blockIdx.z, n_lo = sl * kSlice, n_hi = (n_lo + kSlice < wc) ? n_lo + kSlice : wc;
+  double* out = part + (size_t)sl * ((size_t)P * P + P);
+  const bool pin = p0 + i16 < P, qin = q0 + i16 < P;
+  d4 acc = {0.0, 0.0, 0.0, 0.0};
+  for (long r = n_lo; r < n_hi; r += 4) {
+    const long rr = r + kq;
+    const double a = (pin && rr < n_hi) ? B[rr * P + p0 + i16] : 0.0;
+    const double b = (qin && rr < n_hi) ? T[rr * P + q0 + i16] : 0.0;
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {  // lane holds D[row = kq + 4 r][col = i16]
+    const int p = p0 + kq + 4 * r, q = q0 + i16;
+    if (p < P && q < P) out[(size_t)p * P + q] = acc[r];
+  }
+  if (q0 == 0 && kq == 0 && pin) {
+    double s = 0.0;
+    for (long r = n_lo; r < n_hi; ++r) s += Nn[r * P + p0 + i16];
+    out[(size_t)P * P + p0 + i16] = s;
+  }
+}
+
+// sums[i] (+)= part[0][i] + part[1][i] + ... one after the other (start != 0: from zero)
+__global__ __launch_bounds__(256) void k_obdm_reduce(const double* __restrict__ part, long n, long nslice, int start, double* __restrict__ sums) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double s = start ? 0.0 : sums[i];
+  for (long sl = 0; sl < nslice; ++sl) s += part[(size_t)sl * n + i];
+  sums[i] = s;
+}
+
+}  // namespace
+
+extern "C" int pqa_obdm_sweeps(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
+                               uint64_t seed, int mean, int first, int64_t chunk, double* ratio, int32_t* assign_out, double* value_mean,
+                               double* norm_mean) {
+  if (!h) return -2;
+  if (!ev) FAIL("pqa_obdm_sweeps: the orbital evaluator's handle is NULL");
+  TRY(sync_aos(h));
+  HIPCHK(hipSetDevice(h->device));
+  if (h->W == 0) FAIL("pqa_obdm_sweeps: state not initialised (call recompute)");
+  TRY(readonly_scope(h, "pqa_obdm_sweeps"));
+  if (ev == h) FAIL("pqa_obdm_sweeps: the wave function and the orbital evaluator must be two handles");
+  if (ev->cplx || ev->twist) FAIL("pqa_obdm_sweeps: complex orbital evaluator (outside the fused scope: use the protocol route)");
+  if (ev->device != h->device) FAIL("pqa_obdm_sweeps: the two handles are on different devices (use the protocol route)");
+  if (slot < 0 || slot > 1) FAIL("pqa_obdm_sweeps: slot must be 0 or 1");
+  if (!es || ne < 1) FAIL("pqa_obdm_sweeps: no electron listed (use the protocol route)");
+  const long W = h->W;
+  const int N = h->N;
+  int spins = 0;
+  {
+    std::vector<char> seen((size_t)N, 0);
+    for (int t = 0; t < ne; ++t) {
+      if (es[t] < 0 || es[t] >= N) FAIL("pqa_obdm_sweeps: electron index out of range (use the protocol route)");
+      if (seen[es[t]]) FAIL("pqa_obdm_sweeps: an electron is listed twice (use the protocol route)");
+      seen[es[t]] = 1;
+      spins |= es[t] >= h->nup ? 2 : 1;
+    }
+  }
+  auto& d = ev->dm[slot];
+  if (nsweeps < 1 || nsweeps > d.nkeep) FAIL("pqa_obdm_sweeps: more sweeps than pqa_dm_walk kept samples (use the protocol route)");
+  if (d.n <= 0) FAIL("pqa_obdm_sweeps: no auxiliary walkers (call pqa_dm_walk)");
+  if (mean && (!value_mean || !norm_mean)) FAIL("pqa_obdm_sweeps: the mean mode needs value_mean and norm_mean");
+  if (!mean && !first && ev->dm_nconf != W)
+    FAIL("pqa_obdm_sweeps: the wave function holds another number of walkers than the accumulators were started with (use the protocol route)");
+  if (mean && !first) FAIL("pqa_obdm_sweeps: the mean mode starts its sums in every call (first must be set)");
+  if (assign)
+    for (size_t i = 0; i < (size_t)nsweeps * W; ++i)
+      if (assign[i] < 0 || assign[i] >= d.n) FAIL("pqa_obdm_sweeps: assignment outside the auxiliary walkers");
+  auto on_ev = [&](int rc) {  // (errors are reported on the wave function's handle)
+    if (rc) h->err = ev->err;
+    return rc;
+  };
+  const int norb = ev->nmo[d.spin];
+  if (norb <= 0) FAIL("pqa_obdm_sweeps: the evaluator has no orbitals of the walk's spin");
+  const int D = h->ndet;
+  const size_t lds = ((size_t)3 * N + 2 * (size_t)ne + (D > 1 ? D : 0) + (size_t)h->ndet_s[0] * h->nup + (size_t)h->ndet_s[1] * h->ndn) * sizeof(double);
+  if (lds > 160 * 1024) FAIL("pqa_obdm_sweeps: more determinants than one LDS block holds (use the protocol route)");
+  if (lds > 64 * 1024) TRY(raise_lds_limit(h, h->S.pbc ? (const void*)k_obdm_rt<true> : (const void*)k_obdm_rt<false>));
+  // scratch per walker: the point, the orbital rows of the spins present, and the ratios (per-walker mode) or the three panels and
+  // the walker's share of a slice's partial tile (mean mode)
+  const int nm0 = (spins & 1) ? h->nmo[0] : 0, nm1 = (spins & 2) ? h->nmo[1] : 0;
+  const size_t npart = (size_t)norb * norb + norb;  // doubles of a slice's partials, and of the running sums
+  const bool need_R = !mean || ratio;
+  const size_t per_walker = (3 + (size_t)nm0 + nm1 + (need_R ? ne : 0) + (mean ? 3 * (size_t)norb + (npart + kSlice - 1) / kSlice : 0)) * sizeof(double);
+  long Wc = chunk > 0 ? std::min<long>(W, chunk) : walker_chunk(W, per_walker);
+  if (mean && Wc < W) Wc = std::max<long>(kSlice, Wc - Wc % kSlice);  // (whole slices: the slices do not depend on the chunk)
+  const long nsl_max = (std::min(Wc, W) + kSlice - 1) / kSlice;
+  TRY(on_ev(ensure(ev, ev->dm_assign[0], (size_t)nsweeps * W * sizeof(int))));
+  if (assign) TRY(on_ev(copy_in(ev, ev->dm_assign[0].p, assign, (size_t)nsweeps * W * sizeof(int))));
+  TRY(on_ev(ensure(ev, ev->b_pts, (size_t)W * ne * 3 * sizeof(double))));
+  TRY(on_ev(ensure(ev, d.cfg, (size_t)W * ne * norb * sizeof(double))));
+  if (need_R) TRY(on_ev(ensure(ev, ev->dm_ratio, (size_t)Wc * ne * sizeof(double))));
+  if (mean) TRY(on_ev(ensure(ev, ev->b_obdm, ((size_t)3 * Wc * norb + (size_t)(nsl_max + 2) * npart) * sizeof(double))));
+  else TRY(on_ev(dm_prepare(ev, W, (long)norb * norb, 0, first, norb, 0)));
+  TRY(ensure(h, h->b_tves, (size_t)ne * sizeof(int)));
+  TRY(ensure(h, h->b_tbpts, (size_t)3 * Wc * sizeof(double)));
+  if (nm0) TRY(ensure(h, h->b_orbphi[0], (size_t)Wc * nm0 * sizeof(double)));
+  if (nm1) TRY(ensure(h, h->b_orbphi[1], (size_t)Wc * nm1 * sizeof(double)));
+  if (!h->tb_ev[0])
+    for (hipEvent_t& e : h->tb_ev) TRY(new_event(h, &e, hipEventDisableTiming));
+  const hipEvent_t produced = h->tb_ev[0], consumed = h->tb_ev[1];
+  TpTuneGuard tune(h), tune_ev(ev);
+  ev->saved_valid = false;
+  d.ncfg = W * ne;
+  const int* d_es = (const int*)h->b_tves.p;
+  int* d_assign = (int*)ev->dm_assign[0].p;
+  double* d_pts = (double*)h->b_tbpts.p;
+  double* d_R = need_R ? (double*)ev->dm_ratio.p : nullptr;
+  double *d_T = nullptr, *d_B = nullptr, *d_N = nullptr, *d_part = nullptr, *d_sums = nullptr, *d_out = nullptr;
+  if (mean) {
+    d_T = (double*)ev->b_obdm.p;
+    d_B = d_T + (size_t)Wc * norb;
+    d_N = d_B + (size_t)Wc * norb;
+    d_part = d_N + (size_t)Wc * norb;
+    d_sums = d_part + (size_t)nsl_max * npart;
+    d_out = d_sums + npart;
+  }
+  // the listed electrons' coordinates, gathered from the resident walkers on the wave function's stream (after the evaluator's
+  // queued work, which may still read b_pts), and the evaluator's orbitals there on its own stream
+  HIPCHK(hipEventRecord(consumed, ev->stream));
+  HIPCHK(hipStreamWaitEvent(h->stream, consumed, 0));
+  TRY(copy_in(h, h->b_tves.p, es, (size_t)ne * sizeof(int)));
+  hipLaunchKernelGGL(k_obdm_epts, dim3((unsigned)((W * ne + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->js.x, d_es, ne, N, W,
+                     (double*)ev->b_pts.p);
+  TRY(check_launch(h, "k_obdm_epts"));
+  HIPCHK(hipEventRecord(produced, h->stream));
+  HIPCHK(hipStreamWaitEvent(ev->stream, produced, 0));
+  TRY(on_ev(launch_orb(ev, d.spin, plain_points((const double*)ev->b_pts.p, W * ne), W * ne, 1, (double*)d.cfg.p)));
+  HIPCHK(hipEventRecord(consumed, ev->stream));
+  for (int s = 0; s < nsweeps; ++s) {
+    const double* keep_pos = (const double*)d.keep_pos.p + (size_t)s * d.n * 3;
+    const double* keep_row = (const double*)d.keep_row.p + (size_t)s * d.n * norb;
+    const double* keep_f = (const double*)d.keep_f.p + (size_t)s * d.n;
+    int* asg = d_assign + (size_t)s * W;
+    for (long w0 = 0; w0 < W; w0 += Wc) {
+      const long wc = std::min(Wc, W - w0);
+      HIPCHK(hipStreamWaitEvent(h->stream, consumed, 0));  // (the previous chunk's ratios / panels have been contracted)
+      hipLaunchKernelGGL(k_obdm_gather, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, h->stream, keep_pos, asg, w0, wc, assign ? 0 : 1,
+                         seed, (uint32_t)s, d.n, d_pts);
+      TRY(check_launch(h, "k_obdm_gather"));
+      if (nm0) TRY(launch_orb(h, 0, plain_points(d_pts, wc), wc, 1, (double*)h->b_orbphi[0].p));
+      if (nm1) TRY(launch_orb(h, 1, plain_points(d_pts, wc), wc, 1, (double*)h->b_orbphi[1].p));
+      if (h->S.pbc)
+        hipLaunchKernelGGL((k_obdm_rt<true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
+                           (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, (const double*)d.cfg.p,
+                           keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_B, d_N);
+      else
+        hipLaunchKernelGGL((k_obdm_rt<false>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
+                           (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, (const double*)d.cfg.p,
+                           keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_B, d_N);
+      TRY(check_launch(h, "k_obdm_rt"));
+      if (ratio)
+        HIPCHK(hipMemcpyAsync(ratio + ((size_t)s * W + w0) * ne, d_R, (size_t)wc * ne * sizeof(double), hipMemcpyDefault, h->stream));
+      HIPCHK(hipEventRecord(produced, h->stream));
+      HIPCHK(hipStreamWaitEvent(ev->stream, produced, 0));
+      if (mean) {
+        const long nsl = (wc + kSlice - 1) / kSlice;
+        const unsigned tiles = (unsigned)((norb + 15) / 16);
+        hipLaunchKernelGGL(k_obdm_mean, dim3(tiles, tiles, (unsigned)nsl), dim3(64), 0, ev->stream, (const double*)d_B, (const double*)d_T,
+                           (const double*)d_N, wc, norb, d_part);
+        hipLaunchKernelGGL(k_obdm_reduce, dim3((unsigned)((npart + 255) / 256)), dim3(256), 0, ev->stream, (const double*)d_part, (long)npart,
+                           nsl, (int)(s == 0 && w0 == 0), d_sums);
+        TRY(on_ev(check_launch(ev, "k_obdm_mean")));
+      } else {
+        hipLaunchKernelGGL((k_obdm_acc<>), dim3((unsigned)wc), dim3(256), (size_t)2 * norb * sizeof(double), ev->stream, keep_row, keep_f,
+                           (const int*)asg + w0, (const double*)d.cfg.p + (size_t)w0 * ne * norb, (const double*)d_R, 0, 0, ne, norb,
+                           (int)(first && s == 0), (double*)ev->dm_val.p + (size_t)w0 * norb * norb, (double*)ev->dm_norm[0].p + (size_t)w0 * norb);
+        TRY(on_ev(check_launch(ev, "k_obdm_acc")));
+      }
+      HIPCHK(hipEventRecord(consumed, ev->stream));
+    }
+  }
+  if (ratio) HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's array is complete on return)
+  if (mean) {
+    hipLaunchKernelGGL((k_scale_copy<>), dim3((unsigned)((npart + 255) / 256)), dim3(256), 0, ev->stream, (const double*)d_sums, (long)npart,
+                       1.0 / ((double)W * nsweeps), d_out);
+    TRY(on_ev(check_launch(ev, "k_scale_copy")));
+    HIPCHK(hipMemcpyAsync(value_mean, d_out, (size_t)norb * norb * sizeof(double), hipMemcpyDefault, ev->stream));
+    HIPCHK(hipMemcpyAsync(norm_mean, d_out + (size_t)norb * norb, (size_t)norb * sizeof(double), hipMemcpyDefault, ev->stream));
+  }
+  if (assign_out) HIPCHK(hipMemcpyAsync(assign_out, d_assign, (size_t)nsweeps * W * sizeof(int), hipMemcpyDefault, ev->stream));
+  if (mean || assign_out) HIPCHK(hipStreamSynchronize(ev->stream));
+  return 0;
+}
+
+// Bytes the evaluator holds for the fused one-body estimator: scratch = the mean mode's panels, partial tiles and sums plus the
+// ratios of a walker chunk; per_walker = the per-walker accumulators (value and norms) the mean mode never allocates.
+extern "C" int pqa_obdm_bytes(pqa_handle_t* ev, int64_t* scratch, int64_t* per_walker) {
+  if (!ev) return -2;
+  if (scratch) *scratch = (int64_t)(ev->b_obdm.cap + ev->dm_ratio.cap);
+  if (per_walker) *per_walker = (int64_t)(ev->dm_val.cap + ev->dm_norm[0].cap + ev->dm_norm[1].cap);
+  return 0;
+}

@@ -112,6 +112,18 @@ class EnergyAccumulator:
     def avg(self, configs, wf):
         return {k: np.mean(v, axis=0) for k, v in self(configs, wf).items()}
 
+    def avg_resident(self, wf):
+        """``avg`` for the walkers resident behind ``wf``, without a host container to compare them with: binds the handle, advances
+        the call count and derives the key of the energy draws as ``__call__`` does, then the means of ``dev.energy``."""
+        dev = self._device(wf)
+        self.bind(dev)
+        self._calls += 1
+        key = int(np.random.randint(0, 2**31 - 1)) if self.seed is None else self.seed + self._calls
+        out = dev.energy(self.threshold, seed=key)
+        if np.iscomplexobj(out):
+            return {k: np.mean(out[i] if k in ("ecp", "total") else out[i].real.copy(), axis=0) for i, k in enumerate(KEYS)}
+        return {k: np.mean(out[i], axis=0) for i, k in enumerate(KEYS)}
+
     def nonlocal_tmoves(self, configs, wf, e, tau, rot=None, unif=None):
         """``EnergyAccumulator.nonlocal_tmoves`` (accumulators.py:80-86) -> ``eval_ecp.compute_tmoves``
         (eval_ecp.py:43-80): dict with ``ratio`` (W,P), ``weight`` (W,P) and ``configs`` (an electron object with

@@ -13,6 +13,19 @@ device handle that holds ``orb_coeff`` as its orbitals (``OrbitalEvaluator``):
 
 The host only draws random numbers — from ``numpy.random`` in the reference's order, so that a seeded run reproduces the
 reference draw for draw — and moves the small per-sweep arrays (positions, assignments, ratios).
+
+Two routes give the ratios (``route``, as in ``TBDMAccumulator``):
+
+* **protocol**: the four steps above, sweep by sweep through ``wf.testvalue_many`` — every wave function.
+* **fused** (``pqa_obdm_sweeps``, ``csrc/pqa_obdm.hip``): real wave functions living on one device handle whose resident walkers are
+  the configurations — Slater (one or more determinants), optionally times JastrowSpin, open or periodic at Gamma — with a real
+  evaluator on the same device.  The electrons' coordinates are read from the resident walkers, the ratios of all sweeps come in
+  closed form from the resident state, and the estimator is contracted on the device in the same call: per configuration
+  (``__call__``) or, for ``avg`` / ``avg_resident``, as the walker mean ``B^T T / W`` on the fp64 matrix cores without a
+  per-configuration matrix.  With ``rng="numpy"`` the draws are those of the protocol route; ``rng="device"`` draws the walk and the
+  assignments from the device's Philox streams, keyed by one ``numpy.random`` integer per evaluation.
+
+``last_route`` names the route of the last evaluation.
 """
 
 import numpy as np
@@ -21,7 +34,9 @@ from . import _ffi
 from . import pbc as _pbc
 from .configs import OpenConfigs, PeriodicConfigs
 from .systems import initial_guess
-from .wf import DeviceWF
+from .wf import DeviceWF, readonly_device
+
+ROUTES = (None, "fused", "protocol")
 
 
 class _OneElectronView:
@@ -96,6 +111,14 @@ class OrbitalEvaluator:
                       int(nkeep), _ffi.ptr(keep), _ffi.ptr(acc))
         return acc, keep
 
+    def walk_device(self, slot, spin, x, nsamples, seed, tstep, nkeep):
+        """``pqa_dm_walk`` on the device's own Philox streams keyed by ``seed`` (no tapes): as ``walk`` without the decisions."""
+        n = len(x)
+        keep = np.empty((nkeep, n, 3))
+        self.dev.call("pqa_dm_walk", int(slot), int(spin), n, int(nsamples), float(tstep), _ffi.ptr(x), None, None, int(seed), int(nkeep),
+                      _ffi.ptr(keep), None)
+        return None, keep
+
     def points(self, slot, spin, x):
         x = _ffi.f64(x).reshape(-1, 3)
         self.dev.call("pqa_dm_points", int(slot), int(spin), _ffi.ptr(x), len(x))
@@ -125,6 +148,8 @@ class AuxiliaryWalkers:
     device handle.  ``start`` places them like the reference (``initial_guess`` electrons re-read one by one,
     obdm.py:121-124); ``advance`` runs the walk and keeps the last ``keep`` samples on the device."""
 
+    tape_bytes = 256 << 20  # most host memory the tapes of one ``pqa_dm_walk`` call take
+
     def __init__(self, orbitals, slot):
         self.orbitals, self.slot, self.x = orbitals, slot, None
 
@@ -132,9 +157,27 @@ class AuxiliaryWalkers:
         seed = initial_guess(self.orbitals.mol, int(naux / electrons_per_config) + 1, rng=np.random)
         self.x = np.ascontiguousarray(self.orbitals.true_positions(seed).reshape(-1, 3)[:naux])
 
-    def advance(self, spin, nsamples, tstep, keep=0):
-        gauss, unif = draw_walk_tapes(len(self.x), nsamples)
-        return self.orbitals.walk(self.slot, spin, self.x, gauss, unif, tstep, keep)
+    def advance(self, spin, nsamples, tstep, keep=0, seed=None):
+        """``nsamples`` steps of the walk; returns (decisions (nsamples, n), positions of the last ``keep`` samples).  The tapes are
+        drawn and walked in groups of samples that stay within ``tape_bytes`` (the last group holds the kept samples): the draw
+        order and the positions are those of one call, since a call starts from the positions its predecessor returned.
+        ``seed``: the device's Philox streams instead of tapes (no decisions are returned)."""
+        if seed is not None:
+            return self.orbitals.walk_device(self.slot, spin, self.x, nsamples, seed, tstep, keep)
+        n = len(self.x)
+        group = max(1, int(self.tape_bytes // (32 * n)))  # a sample's tapes: 3 normals and 1 uniform per walker
+        sizes, left = [], nsamples
+        while left > max(group, keep):
+            take = min(group, left - keep) if keep else group
+            sizes.append(take)
+            left -= take
+        sizes.append(left)
+        acc, kept = [], None
+        for i, ns in enumerate(sizes):
+            gauss, unif = draw_walk_tapes(n, ns)
+            a, kept = self.orbitals.walk(self.slot, spin, self.x, gauss, unif, tstep, keep if i == len(sizes) - 1 else 0)
+            acc.append(a)
+        return (acc[0] if len(acc) == 1 else np.concatenate(acc)), kept
 
     @property
     def configs(self):
@@ -156,15 +199,55 @@ def sample_onebody(configs, orbitals, nsamples=1, tstep=0.5, spin=0):
     return acc, snaps, [orbitals.mos(k, spin) for k in kept]
 
 
+def device_obdm_sweeps(dev, ev, electrons, nsweeps, assign=None, seed=0, mean=False, first=True, walker_chunk=0, with_ratios=False):
+    """``pqa_obdm_sweeps``: the one-body estimator of wave-function handle ``dev`` over the first ``nsweeps`` kept samples of slot 0
+    of the evaluator ``ev`` (an ``OrbitalEvaluator``) for the listed ``electrons``.  ``assign`` (nsweeps, W): the auxiliary walker of
+    every configuration, or None: drawn on the device from ``seed``.  Returns a dict: ``assign`` (the assignments used), ``ratio``
+    (nsweeps, W, nelec) with ``with_ratios``, and with ``mean`` the walker means ``value`` (norb, norb) and ``norm`` (norb,) already
+    divided by ``nsweeps``; without ``mean`` the evaluator's per-configuration accumulators hold the sums (``ev.fetch``)."""
+    es = np.ascontiguousarray(np.asarray(electrons).ravel(), dtype=np.int32)
+    W, norb = dev.W, ev.norb
+    out = {}
+    if assign is not None:
+        assign = np.ascontiguousarray(assign, dtype=np.int32)
+        if assign.shape != (nsweeps, W):
+            raise ValueError(f"assignments ({nsweeps}, {W}) expected, got {assign.shape}")
+        out["assign"] = assign
+    else:
+        out["assign"] = np.empty((nsweeps, W), dtype=np.int32)
+    if with_ratios:
+        out["ratio"] = np.empty((nsweeps, W, len(es)))
+    if mean:
+        out["value"], out["norm"] = np.empty((norb, norb)), np.empty(norb)
+    dev.call("pqa_obdm_sweeps", ev.dev._h, 0, _ffi.ptr(es), len(es), int(nsweeps), _ffi.ptr(assign), int(seed), int(mean), int(first),
+             int(walker_chunk), _ffi.ptr(out.get("ratio")), None if assign is not None else _ffi.ptr(out["assign"]), _ffi.ptr(out.get("value")),
+             _ffi.ptr(out.get("norm")))
+    return out
+
+
 class OBDMAccumulator:
     """Keys ``value`` (norb,norb), ``norm`` (norb,) per configuration (obdm.py:26-213).
 
     ``spin`` 0/1 restricts the moved electrons to the up/down ones, ``electrons`` to an explicit list; ``naux`` auxiliary
     walkers (default: one per configuration), ``nsweeps`` auxiliary samples per evaluation, ``warmup`` samples before the
-    first."""
+    first.
+
+    ``route``: None takes the fused route whenever the wave function and the evaluator are in its scope and the protocol route
+    otherwise; "fused" raises outside the scope; "protocol" always goes through ``wf.testvalue_many``.  ``rng``: "numpy" draws the
+    walk and the assignments from ``numpy.random`` in the reference's order on both routes; "device" (fused route only) draws one
+    ``numpy.random`` integer per evaluation and leaves the rest to the device's Philox streams.  ``walker_chunk``: walkers per
+    scratch chunk of the fused route (0: the library's bound).  ``last_route`` names the route of the last evaluation."""
 
     def __init__(self, mol, orb_coeff, nsweeps=5, tstep=0.50, warmup=10000, naux=None, spin=None, electrons=None, kpts=None,
-                 eval_gto_precision=None, device=0):
+                 eval_gto_precision=None, device=0, route=None, rng="numpy", walker_chunk=0):
+        if route not in ROUTES:
+            raise ValueError(f"route must be one of {ROUTES}")
+        if rng not in ("numpy", "device"):
+            raise ValueError("rng must be 'numpy' or 'device'")
+        if rng == "device" and route == "protocol":
+            raise ValueError("rng='device' draws inside pqa_obdm_sweeps: it needs the fused route")
+        self._route, self._rng, self._walker_chunk, self.last_route = route, rng, int(walker_chunk), None
+        self.last_assign = None  # (nsweeps, nconf) assignments of the last fused evaluation
         nup, ntot = mol.nelec[0], int(np.sum(mol.nelec))
         if spin is not None:
             if spin not in (0, 1):
@@ -182,13 +265,45 @@ class OBDMAccumulator:
     def _extra_config(self):
         return None if self._walkers is None else self._walkers.configs
 
-    def _sample(self, configs, wf):
-        """Runs one evaluation on the device; returns whether the accumulated value is complex."""
-        ev, nconf = self.orbitals, configs.configs.shape[0]
+    def _out_of_scope(self, wf, nconf=None):
+        """Why the fused route cannot take ``wf`` (and ``nconf`` configurations), or None when it can."""
+        dev, ev = readonly_device(wf), self.orbitals.dev
+        es = np.asarray(self._electrons).ravel()
+        if dev is None:
+            return "the wave function is not a real Slater (x two-body Jastrow) product on one device handle"
+        if ev.cplx or ev.twisted:
+            return "the orbital evaluator is complex"
+        if ev.device != dev.device:
+            return "the wave function and the evaluator are on different devices"
+        if tuple(dev.nelec) != tuple(self._mol.nelec):
+            return "the wave function has other electron numbers than the accumulator's system"
+        if len(es) < 1:
+            return "no electron is listed"
+        if es.min() < 0 or es.max() >= dev.N or len(np.unique(es)) != len(es):
+            return "the electron list repeats an electron or names one the wave function does not have"
+        if nconf is not None and dev.W != nconf:
+            return "the wave function's resident walkers are not the configurations"
+        return None
+
+    def resolve_route(self, wf, nconf=None):
+        """The route an evaluation takes for ``wf``: "fused" or "protocol" (see ``route``)."""
+        if self._route == "protocol":
+            return "protocol"
+        why = self._out_of_scope(wf, nconf)
+        if why is not None and (self._route == "fused" or self._rng == "device"):
+            raise ValueError(f"OBDMAccumulator(route='fused'): {why} (outside the fused scope: use the protocol route)")
+        return "protocol" if why is not None else "fused"
+
+    def _start(self, nconf, seed=None):
         if self._walkers is None:
-            self._walkers = AuxiliaryWalkers(ev, 0)
+            self._walkers = AuxiliaryWalkers(self.orbitals, 0)
             self._walkers.start(nconf if self._naux is None else self._naux, self.nelec)
-            self._walkers.advance(0, self._warmup, self._tstep)
+            self._walkers.advance(0, self._warmup, self._tstep, seed=None if seed is None else seed + 1)
+
+    def _sample(self, configs, wf):
+        """Runs one evaluation on the device, protocol route; returns whether the accumulated value is complex."""
+        ev, nconf = self.orbitals, configs.configs.shape[0]
+        self._start(nconf)
         naux = len(self._walkers.x)
         pick = np.random.randint(0, naux, size=(self._nsweeps, nconf)).astype(np.int32)  # drawn before the walk (obdm.py:150)
         _, kept = self._walkers.advance(0, self._nsweeps, self._tstep, keep=self._nsweeps)
@@ -205,8 +320,35 @@ class OBDMAccumulator:
         self._walkers.x = np.ascontiguousarray(kept[-1][pick[-1]])
         return cplx
 
+    def _sample_fused(self, dev, mean, with_ratios=False):
+        """One evaluation on the fused route: the walk, then ONE ``pqa_obdm_sweeps`` call on the walkers resident behind ``dev``.
+        Returns (value_mean, norm_mean) of the mean mode (else None, the evaluator's accumulators hold the result) and the ratios
+        (nsweeps, W, nelec) when asked for."""
+        ev, nconf, nsw = self.orbitals, dev.W, self._nsweeps
+        seed = int(np.random.randint(0, 2**31 - 1)) if self._rng == "device" else None
+        self._start(nconf, seed)
+        naux = len(self._walkers.x)
+        pick = None
+        if seed is None:
+            pick = np.random.randint(0, naux, size=(nsw, nconf)).astype(np.int32)  # drawn before the walk (obdm.py:150)
+        _, kept = self._walkers.advance(0, nsw, self._tstep, keep=nsw, seed=seed)
+        out = device_obdm_sweeps(dev, ev, self._electrons, nsw, assign=pick, seed=0 if seed is None else seed, mean=mean,
+                                 walker_chunk=self._walker_chunk, with_ratios=with_ratios)
+        vm, nm, ratio, used = out.get("value"), out.get("norm"), out.get("ratio"), out["assign"]
+        self.last_assign = used
+        self._walkers.x = np.ascontiguousarray(kept[-1][self.last_assign[-1]])  # the reference's resampling step, as in _sample
+        return (vm, nm), ratio
+
     def _result(self, configs, wf, mean):
-        cplx, nconf, scale = self._sample(configs, wf), configs.configs.shape[0], 1.0 / self._nsweeps
+        nconf, scale = configs.configs.shape[0], 1.0 / self._nsweeps
+        self.last_route = self.resolve_route(wf, nconf)
+        if self.last_route == "fused":
+            (vm, nm), _ = self._sample_fused(readonly_device(wf), mean)
+            if mean:
+                return {"value": vm, "norm": nm}
+            cplx = False
+        else:
+            cplx = self._sample(configs, wf)
         return {"value": self.orbitals.fetch(0, nconf, (self.norb, self.norb), scale, mean, cplx),
                 "norm": self.orbitals.fetch(1, nconf, (self.norb,), scale, mean)}
 
@@ -216,6 +358,14 @@ class OBDMAccumulator:
     def avg(self, configs, wf):
         """Mean over the configurations, reduced on the device (obdm.py:195-197)."""
         return self._result(configs, wf, True)
+
+    def avg_resident(self, wf):
+        """``avg`` on the fused route for the walkers resident behind ``wf``, without a host container."""
+        if self.resolve_route(wf) != "fused":
+            raise ValueError("OBDMAccumulator.avg_resident needs the fused route")
+        self.last_route = "fused"
+        (vm, nm), _ = self._sample_fused(readonly_device(wf), True)
+        return {"value": vm, "norm": nm}
 
     def evaluate_orbitals(self, configs):
         return self.orbitals.mos(self.orbitals.true_positions(configs))

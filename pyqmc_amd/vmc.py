@@ -11,7 +11,8 @@ other accumulator (density matrices, parameter gradients, ...) is called on the 
 device sweep, on the walkers fetched from the device, and talks to the wave function through the
 protocol entry points as it would in the reference.  The exception: ``StochasticReconfiguration``
 accumulators on their device route (``accumulators.sr_route``) take their averages from the resident
-state after every sweep (``pqa_sr_moments``), and the walkers stay on the device until the block ends.
+state after every sweep (``pqa_sr_moments``), and so do ``OBDMAccumulator``s on their fused route (``pqa_obdm_sweeps``) and the plain
+``EnergyAccumulator``s beside them: the walkers stay on the device until the block ends.
 
 An ``AddWF`` whose components are in the fused scope (``pyqmc_amd/addwf.py``) is moved by ``pqa_add_sweeps``, one call per sweep, with
 host-drawn tapes; its accumulators run on the fetched walkers after every sweep.
@@ -84,10 +85,11 @@ def _vmc_worker_host_accumulators(dev, wf, configs, tstep, nsteps, accumulators,
 
 
 def _vmc_worker_resident_accumulators(dev, wf, configs, tstep, nsteps, accumulators, tapes, seed, state_current):
-    """Device sweeps, device accumulators: every accumulator is a ``StochasticReconfiguration`` on its device route, so after every
-    sweep (one ``pqa_vmc_sweeps`` call, keyed as in ``_vmc_worker_host_accumulators``) each ``avg_resident(wf)`` takes its averages
-    from the state the sweep left (``pqa_sr_moments``), in dictionary order; the ``np.random`` draws come in the same order as on
-    the host-accumulator path.  Open systems fetch the walkers once, after the last sweep; periodic containers carry the wrap counters
+    """Device sweeps, device accumulators: every accumulator is a ``StochasticReconfiguration`` on its device route, an
+    ``OBDMAccumulator`` on its fused route or a plain ``EnergyAccumulator``, so after every sweep (one ``pqa_vmc_sweeps`` call, keyed
+    as in ``_vmc_worker_host_accumulators``) each ``avg_resident(wf)`` takes its averages from the state the sweep left
+    (``pqa_sr_moments``, ``pqa_obdm_sweeps``, ``pqa_energy``), in dictionary order; the ``np.random`` draws come in the same order as
+    on the host-accumulator path.  Open systems fetch the walkers once, after the last sweep; periodic containers carry the wrap counters
     of every sweep call and are fetched after each."""
     if seed is None:
         seed = int(np.random.randint(0, 2**31 - 1))
@@ -184,8 +186,16 @@ def vmc_worker(wf, configs, tstep, nsteps, accumulators, tapes=None, seed=None, 
     if not all(isinstance(a, EnergyAccumulator) for a in accumulators.values()):
         from .accumulators import StochasticReconfiguration
 
-        srs = [a for a in accumulators.values() if type(a) is StochasticReconfiguration]
-        if nsteps > 0 and len(srs) == len(accumulators) and all([a.resolve_route(wf) == "device" for a in srs]):
+        from .obdm import OBDMAccumulator
+
+        def resident(a):  # the accumulator takes its averages from the resident state (avg_resident)
+            if type(a) is StochasticReconfiguration:
+                return a.resolve_route(wf) == "device"
+            if type(a) is OBDMAccumulator:
+                return a.resolve_route(wf) == "fused"
+            return type(a) is EnergyAccumulator
+
+        if nsteps > 0 and all([resident(a) for a in accumulators.values()]):
             return _vmc_worker_resident_accumulators(dev, wf, configs, tstep, nsteps, accumulators, tapes or {}, seed, state_current)
         return _vmc_worker_host_accumulators(dev, wf, configs, tstep, nsteps, accumulators, tapes or {}, seed, state_current)
     tapes = tapes or {}
