@@ -58,8 +58,11 @@ def compute_S(e_trial, e_est, branchcut, v2, tau, eloc, nelec):
 
 
 def dmc_propagate(mol, wf, configs, weights, tstep, branchcut_start, e_trial, e_est, nsteps, tape, threshold=10.0,
-                  record=None):
-    """dmc.py:123-221 with the EnergyAccumulator as the only accumulator.  Returns (df, configs, weights)."""
+                  record=None, margins=None):
+    """dmc.py:123-221 with the EnergyAccumulator as the only accumulator.  Returns (df, configs, weights).
+    ``record`` (optional list) receives ("t" | "d", electron, accept mask) per T-move / drift-diffusion move, ``margins`` (optional list)
+    the same entries with how far each test was from flipping: ``ratio - u`` of a drift-diffusion move, ``acceptance - u`` of a
+    selected T-move (inf where none was selected)."""
     W, N = configs.configs.shape[:2]
     has_ecp = bool(mol._ecp)
     necp = len(oenergy.ecp_atoms(mol))
@@ -85,13 +88,16 @@ def dmc_propagate(mol, wf, configs, weights, tstep, branchcut_start, e_trial, e_
                 ratio, weight, pos = compute_tmoves(mol, configs, wf, e, threshold, tstep, tape)
                 sel_u = np.array([tape.rand1() for _ in range(W)])
                 newpos, chosen, acc = select_tmoves(ratio, weight, pos, configs.configs[:, e, :], sel_u)
-                accept = chosen & (acc > tape.rand(W))
+                u_t = tape.rand(W)
+                accept = chosen & (acc > u_t)
                 ep = configs.make_irreducible(e, newpos)
                 configs.move(e, ep, accept)
                 wf.updateinternals(e, ep, configs, mask=accept)
                 tm_acc += accept / N
                 if record is not None:
                     record.append(("t", e, accept.copy()))
+                if margins is not None:
+                    margins.append(("t", e, np.where(chosen, acc - u_t, np.inf)))
         for e in range(N):
             grad = limdrift(np.real(wf.gradient(e, configs.electron(e)).T), tstep)
             gauss = tape.normal(W) * np.sqrt(tstep)
@@ -103,7 +109,8 @@ def dmc_propagate(mol, wf, configs, weights, tstep, branchcut_start, e_trial, e_
             ratio = np.abs(wfratio) ** 2 * np.exp(1 / (2 * tstep) * (fwd - bwd))
             if not np.iscomplexobj(wfratio):
                 ratio = ratio * np.sign(wfratio)  # fixed node only for real wave functions (dmc.py:64-66)
-            accept = ratio > tape.rand(W)
+            u_d = tape.rand(W)
+            accept = ratio > u_d
             r2 = np.sum((gauss + grad) ** 2, axis=1)
             configs.move(e, ep, accept)
             wf.updateinternals(e, ep, configs, mask=accept, saved_values=saved)
@@ -112,6 +119,8 @@ def dmc_propagate(mol, wf, configs, weights, tstep, branchcut_start, e_trial, e_
             prob_acc += accept / N
             if record is not None:
                 record.append(("d", e, accept.copy()))
+            if margins is not None:
+                margins.append(("d", e, ratio - u_d))
         eloc_old, v2_old = eloc.copy(), v2.copy()
         en = energy()
         eloc, v2 = en["total"].real, en["grad2"]

@@ -1248,8 +1248,11 @@ static __global__ __launch_bounds__(GW == 16 ? 256 : 16 * GW) void k_step_pre(Sy
 // The quad-cooperative instantiation does not read the VALUE block of the cached rows.  The reference divides the
 // derivative sums by sum_j phi_j(r_i) T_ji (slater.py gradient_laplacian: ratios[1:] / ratios[0]) — at the electron's own position that is row i of
 // the Slater matrix times column i of its inverse: 1, up to the rounding the inverse has accumulated since the last recompute.  Taking it as 1
-// saves a fifth of the row traffic (1.78 -> 1.68 ms at 65 536 walkers); measured on (H2O)8, 16 384 walkers, 40 sweeps without a recompute, the
-// steps' kinetic-energy means agree with the dividing build to the last bit or one ulp (<= 4e-16 relative; tools/scratch/c0_check.py).
+// saves a fifth of the row traffic (1.78 -> 1.68 ms at 65 536 walkers).  What it drops is, to first order, sum_e (q_e - 1) s_e with
+// s_e = -1/2 (ls_e + 2 gs_e.gj_e) for ke and 2 gs_e.(gs_e + gj_e) for grad2 (tests/test_conditioning_cpu.py proves the formula on the oracle).
+// Measured on (H2O)8 with cond(D) ~ 1e7, 16 384 walkers, 6 sweeps without a recompute (max |q_e - 1| = 4.7e-8): the fused walker means differ
+// from the dividing standalone pass by 1.2e-11 (ke) and 5.3e-10 (grad2), inside B = mean_w sum_e |q_we - 1| |s_we| = 2.2e-9 and 1.9e-8
+// (tests/test_gpu_conditioning.py); with well-conditioned orbitals they agree to one ulp.
 template <bool PBC, bool CX = false, bool QUAD = false>  // QUAD: quad-cooperative row reads (large shards; real determinants, W % 4 == 0)
 static __global__ __launch_bounds__(64) void k_kinetic_lw(SysDev S, LwState L, int has_jastrow, long W, double* __restrict__ part) {
   // Block b -> (walker group, electron): the electron blocks of ONE walker group sit 8 apart in the linear block order, so

@@ -39,10 +39,10 @@ def oracle_wf(mol, mf, determinants=None, seed=11):
     return owf.MultiplyWF(sl, ja)
 
 
-def gpu_wf(mol, mf, determinants=None, seed=11):
+def gpu_wf(mol, mf, determinants=None, seed=11, jastrow_kws=None):
     import pyqmc_amd as pa
 
-    wf = pa.generate_wf(mol, mf, determinants=determinants)
+    wf = pa.generate_wf(mol, mf, determinants=determinants, jastrow_kws=jastrow_kws)
     a, b = jastrow_params(mol, seed)
     wf.parameters["wf2acoeff"] = a
     wf.parameters["wf2bcoeff"] = b
