@@ -155,7 +155,9 @@ def compute_tmoves(mol, configs, wf, e, threshold, tau, tape):
         r[d["mask"]] = d["ratio"]
         ratios.append(r)
         weights.append(w)
-        poss.append(d["epos"])
+        # the reference's candidates are the FOLDED points (eval_ecp.py:113 make_irreducible; propose_tmoves takes their coordinates alone,
+        # dmc.py:100): a T-move across the cell boundary does not advance the wrap counters
+        poss.append(np.asarray(configs.make_irreducible(e, d["epos"], d["mask"]).configs))
     return np.concatenate(ratios, axis=1), np.concatenate(weights, axis=1), np.concatenate(poss, axis=1)
 
 

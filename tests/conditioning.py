@@ -7,8 +7,13 @@ T (the inverse, [orbital j, electron e]), log|Psi|, and q_e = sum_j phi_j(r_e) T
 the reference divides its derivative sums by and two device kernels take as 1 (k_sweep_r8's next-proposal drift, the quad-cooperative
 k_kinetic_lw).  All three are judged against an inverse / determinant of the Slater matrix that the ORACLE evaluates at the judged
 state's own coordinates: two float64 trajectories differ by ~1e-9 bohr, and cond(D) times that is more than what is measured.
+
+Cases: open-boundary real single determinants (CASES), periodic cells with real, complex and twisted orbitals (PBC_CASES), multi-determinant
+expansions with two- and three-body Jastrow factors (MD_CASES).  ``Case`` builds both sides of any of them; the truth functions take real
+and complex matrices and every unique determinant of a spin.
 """
 
+import ast
 import copy
 import functools
 import os
@@ -20,6 +25,7 @@ from pyqmc_amd import systems
 from pyqmc_amd.configs import OpenConfigs
 
 LD = np.longdouble
+CLD = np.clongdouble
 TSTEP = 0.3
 FIXTURE = "g50_conditioning"
 
@@ -32,13 +38,46 @@ CASES = {
 }
 # max cond(D) over the final walkers, measured with the oracle (asserted within a decade by test_conditioning_cpu.py)
 COND = {"water-1e-5": 3e6, "water-1e-7": 3e8, "general-1e-5": 2e7, "cluster-1e-5": 9e6}
+
+# Periodic, complex and twisted single-determinant cases: name -> (builder, eps, walkers, sweeps, forced sweeps, tape seed).  Their
+# oracle side (1.3 .. 15 s a sweep) is the committed fixture g51.
+PBC_FIXTURE = "g51_conditioning_pbc"
+PBC_CASES = {
+    "gamma-1e-5": ("gamma", 1e-5, 13, 100, (5, 50), 3),  # diamond primitive cell at Gamma: 4 real orbitals per spin
+    # the same cell twisted: complex rows with the wrap phase.  Tape seed 6: with 3, 4, 5, 7 the smallest forced ratio is 1.5e-3 .. 6.7e-3,
+    # not below 1e-3 (the modulus of a complex function has no nodal surface to land next to)
+    "twist-1e-5": ("twist", 1e-5, 13, 100, (5, 50), 6),
+    # 3x1x1, 3 k-points, complex coefficients: 12 per spin.  Tape seed 5: seeds 3, 4, 6, 7 give 1.6e-3 .. 3.7e-3
+    "cx311-1e-5": ("cx311", 1e-5, 13, 30, (3, 15), 5),
+    "k222-1e-5": ("k222", 1e-5, 13, 12, (3,), 3),        # 2x2x2, 8 k-points (C5 shape): 32 real per spin, two orbital tiles
+    # The resident sweep takes a cell only with at most 128 lattice-sum candidates: the primitive cells above have 249 and 3x1x1 has 183,
+    # so of those four only k222 (79) runs k_sweep_res.  The conventional cell (81 candidates, 4 k-points, 16 per spin) does, real at
+    # Gamma-compatible k-points and complex with the twist of config C3 — the shapes that put k_sweep_res<PBC> (one orbital tile) and
+    # k_sweep_res<PBC, CX> (16 complex per spin, the most it takes) under these tests.
+    "cubic-1e-5": ("fcc2cubic", 1e-5, 13, 20, (3, 10), 3),
+    "c3-1e-5": ("c3", 1e-5, 13, 20, (3, 10), 3),
+}
+RES_ELIGIBLE = ("k222-1e-5", "cubic-1e-5", "c3-1e-5")
+# Multi-determinant H2O (4 + 4, 6 virtual orbitals): name -> (determinant list, three-body Jastrow, eps, walkers, sweeps, forced, seed)
+MD_CASES = {
+    "multidet-all-1e-5": ("all", False, 1e-5, 13, 100, (5, 50), 3),
+    "c4-mixed-1e-5": ("mixed", True, 1e-5, 13, 100, (5, 50), 3),
+}
+COND.update({"gamma-1e-5": 2.5e6, "twist-1e-5": 1e6, "cx311-1e-5": 3e6, "k222-1e-5": 6e6, "cubic-1e-5": 3e6, "c3-1e-5": 3e6, "multidet-all-1e-5": 4e7, "c4-mixed-1e-5": 4e7})
 LIVE = ("water-1e-5", "water-1e-7", "general-1e-5")  # the cluster's oracle side (~9 s a run) is the committed fixture
+LIVE_ALL = LIVE + tuple(MD_CASES)
+ALL_CASES = tuple(CASES) + tuple(PBC_CASES) + tuple(MD_CASES)
+# "all-ill": every determinant keeps orbitals 0 and 1 of both spins (excitations out of 2 and 3 only): all scale with eps alike and
+# every inverse is ill-conditioned.  "mixed" is the list of the fixture g8_protocol_h2o_multidet: determinants that drop orbital 0 or 1
+# are well-conditioned and ~1e5 times larger than those that keep both — the log shift of the determinant weights at work.
+DETS_ALL_ILL = [(1.0, [[0, 1, 2, 3], [0, 1, 2, 3]]), (-0.35, [[0, 1, 2, 4], [0, 1, 2, 3]]), (0.3, [[0, 1, 2, 3], [0, 1, 3, 5]]),
+                (-0.25, [[0, 1, 3, 6], [0, 1, 2, 7]]), (0.2, [[0, 1, 4, 8], [0, 1, 2, 3]]), (0.15, [[0, 1, 2, 4], [0, 1, 5, 9]])]
 
 
-def near_degenerate_mf(mol, eps):
+def near_degenerate_mf(mol, eps, nvirt=0):
     """``systems.random_mf`` with occupied orbital 1 of each spin replaced by orbital 0 + eps * (a unit vector): columns 0 and 1 of every
     walker's Slater matrix are parallel up to eps, cond(D) ~ O(10) / eps wherever the walker is."""
-    mf = systems.random_mf(mol)
+    mf = systems.random_mf(mol, nvirt=nvirt)
     mo = np.array(mf.mo_coeff, dtype=float)
     g = np.random.default_rng(5)
     for s in (0, 1):
@@ -48,6 +87,41 @@ def near_degenerate_mf(mol, eps):
     return systems.MeanField(mo, np.array(mf.mo_occ))
 
 
+def near_degenerate_kmf(sup, eps, **random_kmf_kws):
+    """``pbc.random_kmf`` with, at k-point 0 of each spin, occupied column 1 replaced by column 0 + eps * (a unit vector, complex where
+    the coefficients are): two columns of every walker's Slater matrix are parallel up to eps.  The rest of the mean field is unchanged."""
+    from pyqmc_amd import pbc
+
+    mf = pbc.random_kmf(sup, **random_kmf_kws)
+    g = np.random.default_rng(5)
+    mo = [[np.array(m) for m in mf.mo_coeff[s]] for s in (0, 1)]
+    for s in (0, 1):
+        c = mo[s][0]
+        d = g.standard_normal(c.shape[0])
+        if np.iscomplexobj(c):
+            d = d + 1j * g.standard_normal(c.shape[0])
+        d /= np.linalg.norm(d)
+        c[:, 1] = c[:, 0] + eps * d
+    return pbc.KMeanField(mf.kpts, mo, mf.mo_occ)
+
+
+def permuted_kmf(mf, seed):
+    """``permuted_mf`` for a k-point mean field: the columns of every k-point's block in another order."""
+    from pyqmc_amd import pbc
+
+    r = np.random.default_rng(seed)
+    mo = [[np.asarray(m)[:, r.permutation(np.asarray(m).shape[1])] for m in mf.mo_coeff[s]] for s in (0, 1)]
+    return pbc.KMeanField(mf.kpts, mo, mf.mo_occ)
+
+
+def permuted_determinants(dets, nelec, seed):
+    """The same expansion (up to one global sign) with the occupied columns of EVERY determinant in another order: one permutation of
+    the positions per spin, applied to each occupation list alike, so every determinant changes by the same sign."""
+    r = np.random.default_rng(seed)
+    pos = [r.permutation(n) for n in nelec]
+    return [(c, [[occ[s][i] for i in pos[s]] for s in (0, 1)]) for c, occ in dets]
+
+
 def permuted_mf(mf, seed):
     """The same determinant (up to its sign) with the occupied columns in another order: every sum over orbitals runs in another order."""
     r = np.random.default_rng(seed)
@@ -55,13 +129,13 @@ def permuted_mf(mf, seed):
     return systems.MeanField(np.stack([mo[s][:, r.permutation(mo.shape[2])] for s in (0, 1)]), np.array(mf.mo_occ))
 
 
-def tapes(mol, W, nsteps, forced=()):
+def tapes(mol, W, nsteps, forced=(), seed=3):
     """-> (start configs, gauss (nsteps,N,W,3), unif (nsteps,N,W), tstep).  Sweeps in ``forced`` have uniforms 0: every proposal is
-    accepted whatever its ratio, which is how walkers land next to nodes."""
+    accepted whatever its ratio, which is how walkers land next to nodes.  A cell gives ``PeriodicConfigs`` starts."""
     import pyqmc_amd as pa
 
     N = int(np.sum(mol.nelec))
-    r = np.random.default_rng(3)
+    r = np.random.default_rng(seed)
     gauss = r.standard_normal((nsteps, N, W, 3))
     unif = r.random((nsteps, N, W))
     for k in forced:
@@ -70,15 +144,19 @@ def tapes(mol, W, nsteps, forced=()):
 
 
 def refined_inverse(D):
-    """(..., n, n) float64 -> longdouble inverse: ``np.linalg.inv`` refined by Newton-Schulz steps X <- X (2 I - D X) in longdouble until
-    max |D X - I| < 1e-16 or the residual stops falling.  (A residual EVALUATED in longdouble cannot fall below ~ eps_ld * |D| |X| ~ 1e-19 *
-    cond(D), which is above 1e-16 for cond(D) > 1e3; the iteration has converged when it reaches that floor.  What counts is the
+    """(..., n, n) float64 or complex128 -> longdouble (clongdouble) inverse: ``np.linalg.inv`` refined by Newton-Schulz steps
+    X <- X (2 I - D X) in longdouble until max |D X - I| < 1e-16 or the residual stops falling.  (A residual EVALUATED in longdouble
+    cannot fall below ~ eps_ld * |D| |X| ~ 1e-19 * cond(D), which is above 1e-16 for cond(D) > 1e3; the iteration has converged when it
+    reaches that floor.  What counts is the
     forward error, which test_conditioning_cpu.py measures against 50-digit arithmetic: < 1e-11 relative at cond 3e8, 1e-13 at 3e6 —
     three orders below the chain errors judged with it.  float64 ``inv`` alone is off by cond * 1e-16 and would not do.)"""
-    D = np.asarray(D, dtype=float)
-    Dl = D.astype(LD)
-    X = np.linalg.inv(D).astype(LD)
-    I2 = 2 * np.eye(D.shape[-1], dtype=LD)
+    D = np.asarray(D)
+    cx = np.iscomplexobj(D)
+    D = D.astype(complex if cx else float)
+    ld = CLD if cx else LD
+    Dl = D.astype(ld)
+    X = np.linalg.inv(D).astype(ld)
+    I2 = 2 * np.eye(D.shape[-1], dtype=ld)
     last = np.inf
     for _ in range(30):
         P = Dl @ X
@@ -90,12 +168,16 @@ def refined_inverse(D):
     return X
 
 
-def logabsdet(D):
-    """(W, n, n) float64 -> (W,) log |det D| by Gaussian elimination with partial pivoting in longdouble (float64 slogdet is off by
-    cond * 1e-16, the size of what it would be compared with)."""
-    A = np.array(D, dtype=LD)
-    W, n, _ = A.shape
+def slogdet_ld(D):
+    """(..., n, n) float64 or complex128 -> (phase (...,), log |det D| (...,)) by Gaussian elimination with partial pivoting in
+    longdouble (float64 slogdet is off by cond * 1e-16, the size of what it would be compared with).  phase: +-1, or a unit complex."""
+    D = np.asarray(D)
+    cx = np.iscomplexobj(D)
+    lead, n = D.shape[:-2], D.shape[-1]
+    A = np.array(D, dtype=CLD if cx else LD).reshape((-1, n, n))
+    W = A.shape[0]
     out = np.zeros(W, dtype=LD)
+    ph = np.ones(W, dtype=CLD if cx else LD)
     ar = np.arange(W)
     for k in range(n):
         p = k + np.argmax(np.abs(A[:, k:, k]), axis=1)
@@ -104,54 +186,101 @@ def logabsdet(D):
         A[:, k] = rows
         piv = A[:, k, k]
         out += np.log(np.abs(piv))
+        ph = ph * np.where(p != k, -1, 1) * (piv / np.abs(piv))
         if k + 1 < n:
             f = A[:, k + 1:, k] / piv[:, None]
             A[:, k + 1:, k:] -= f[:, :, None] * A[:, k, None, k:]
+    return ph.reshape(lead), out.reshape(lead)
+
+
+def logabsdet(D):
+    """(..., n, n) -> (...,) log |det D| in longdouble (``slogdet_ld``)."""
+    return slogdet_ld(D)[1]
+
+
+def _coords_of(coords):
+    return np.asarray(coords.configs if hasattr(coords, "configs") else coords, dtype=float)
+
+
+def chain_errors(slater_matrix_fn, inverse, logdet, coords, phase=None, det_map=None, det_coeff=None):
+    """The errors a chain of updates has left in one state (the device's or the oracle's), per walker.
+
+    slater_matrix_fn(coords, s) -> (W, n_s, n_s) [electron, orbital], or (W, D_s, n_s, n_s) with every unique determinant of spin s: the
+    oracle's Slater matrices at ``coords``, real or complex; inverse: per spin (W, n_s, n_s) or (W, D_s, n_s, n_s) [orbital, electron];
+    logdet: (W,) the state's log |Psi| less a freshly evaluated Jastrow exponent; coords: (W, N, 3) or a configs object (a periodic
+    one carries the wrap counters the rows of a twisted cell need), the judged state's own; phase: (W,) the state's sign or phase of Psi;
+    det_map (2, ndet) and det_coeff (ndet,): the expansion Psi = sum_D c_D det_up[det_map[0, D]] det_dn[det_map[1, D]] (default: the
+    product of determinant 0 of each spin).
+    -> {"inv": (W,) max over spins AND unique determinants of max |T - X| / max |X| against ``refined_inverse``,
+        "log": (W,) |logdet - fresh| with fresh = log |sum_D ...| formed from the longdouble log-determinants,
+        "phase": (W,) |arg(phase / fresh phase)| (only with ``phase``),
+        "q0m1": (W, N) q_e - 1 with q_e = sum_j D_ej T_je (of the unique determinant where it is largest),
+        "cond": (W,) max over spins and determinants of cond(D), "cond_min": (W,) the min}."""
+    W = _coords_of(coords).shape[0]
+    inv_err, cond, cond_min, q = np.zeros(W), np.zeros(W), np.full(W, np.inf), []
+    ph, lg = [np.ones((W, 1), dtype=LD)] * 2, [np.zeros((W, 1), dtype=LD)] * 2
+    for s in (0, 1):
+        D = np.asarray(slater_matrix_fn(coords, s))
+        if D.shape[-1] == 0:
+            continue
+        D = D.astype(complex if np.iscomplexobj(D) else float)
+        T = np.asarray(inverse[s])
+        if D.ndim == 3:
+            D, T = D[:, None], T[:, None]
+        ld = CLD if np.iscomplexobj(D) else LD
+        X = refined_inverse(D)
+        T = T.astype(complex if ld is CLD else float).astype(ld)
+        err = np.max(np.abs(T - X), axis=(2, 3)) / np.max(np.abs(X), axis=(2, 3))
+        inv_err = np.maximum(inv_err, err.astype(float).max(axis=1))
+        c = np.linalg.cond(D)
+        cond, cond_min = np.maximum(cond, c.max(axis=1)), np.minimum(cond_min, c.min(axis=1))
+        ph[s], lg[s] = slogdet_ld(D)
+        qs = np.einsum("wdej,wdje->wde", D.astype(ld), T) - 1
+        worst = np.argmax(np.abs(qs), axis=1)[:, None]
+        q.append(np.take_along_axis(qs, worst, axis=1)[:, 0].astype(complex if ld is CLD else float))
+    if det_map is None:
+        det_map, det_coeff = np.zeros((2, 1), dtype=int), np.ones(1)
+    lsum = lg[0][:, det_map[0]] + lg[1][:, det_map[1]]  # (W, ndet)
+    ref = lsum.max(axis=1)
+    tot = np.sum(np.asarray(det_coeff, dtype=LD)[None, :] * ph[0][:, det_map[0]] * ph[1][:, det_map[1]] * np.exp(lsum - ref[:, None]), axis=1)
+    fresh = np.log(np.abs(tot)) + ref
+    out = {"inv": inv_err, "log": np.abs((np.asarray(np.real(logdet), dtype=LD) - fresh).astype(float)), "q0m1": np.concatenate(q, axis=1),
+           "cond": cond, "cond_min": cond_min}
+    if phase is not None:
+        out["phase"] = np.abs(np.angle((np.asarray(phase) / (tot / np.abs(tot))).astype(complex)))
     return out
 
 
-def chain_errors(slater_matrix_fn, inverse, logdet, coords):
-    """The errors a chain of updates has left in one state (the device's or the oracle's), per walker.
-
-    slater_matrix_fn(coords, s) -> (W, n_s, n_s) [electron, orbital]: the oracle's Slater matrix of spin s at ``coords``;
-    inverse: per spin (W, n_s, n_s) [orbital, electron]; logdet: (W,) the state's log |det up| + log |det dn| (its log |Psi| less a
-    freshly evaluated Jastrow exponent); coords: (W, N, 3), the judged state's own.
-    -> {"inv": (W,) max over spins of max |T - X| / max |X| against ``refined_inverse``, "log": (W,) |logdet - fresh|,
-        "q0m1": (W, N) q_e - 1 with q_e = sum_j D_ej T_je, "cond": (W,) max over spins of cond(D)}."""
-    coords = np.asarray(coords, dtype=float)
-    W = coords.shape[0]
-    inv_err, cond, fresh, q = np.zeros(W), np.zeros(W), np.zeros(W, dtype=LD), []
-    for s in (0, 1):
-        D = np.asarray(slater_matrix_fn(coords, s), dtype=float)
-        if D.shape[1] == 0:
-            continue
-        X = refined_inverse(D)
-        T = np.asarray(inverse[s], dtype=float).astype(LD)
-        err = np.max(np.abs(T - X), axis=(1, 2)) / np.max(np.abs(X), axis=(1, 2))
-        inv_err = np.maximum(inv_err, err.astype(float))
-        cond = np.maximum(cond, np.linalg.cond(D))
-        fresh += logabsdet(D)
-        q.append((np.einsum("wej,wje->we", D.astype(LD), T) - 1).astype(float))
-    return {"inv": inv_err, "log": np.abs((np.asarray(logdet, dtype=LD) - fresh).astype(float)), "q0m1": np.concatenate(q, axis=1),
-            "cond": cond}
-
-
 def summary(err):
-    """The three figures the tests bound: max over walkers (and electrons) of each chain error."""
-    return {"inv": float(err["inv"].max()), "log": float(err["log"].max()), "q0m1": float(np.abs(err["q0m1"]).max())}
+    """The figures the tests bound: max over walkers (and electrons) of each chain error."""
+    out = {"inv": float(err["inv"].max()), "log": float(err["log"].max()), "q0m1": float(np.abs(err["q0m1"]).max())}
+    if "phase" in err:
+        out["phase"] = float(err["phase"].max())
+    return out
 
 
 # ---------------------------------------------------------------- oracle side
-def oracle_slater_matrix(owf):
+def oracle_slater_matrices(owf):
+    """-> fn(configs, s) -> (W, D_s, n_s, n_s): every unique determinant's Slater matrix of spin s, evaluated on the configs OBJECT — for
+    a periodic one at ``sl._r``: folded coordinates AND wrap counters (a twisted row evaluated at the folded position alone lacks its
+    phase e^{ik.L.wrap}: a relative "error" of order 1 on a correct state)."""
     sl = owf.wf_factors[0]
     nup, ndn = sl._nelec
 
-    def fn(x, s):
+    def fn(cfg, s):
         b, e = nup * s, nup + ndn * s
-        _, mo = sl._mo(np.asarray(x)[:, b:e].reshape(-1, 3), s, 1)
-        return mo[0].reshape(len(x), e - b, -1)[:, :, sl._det_occup[s][0]]
+        x = sl._r(cfg)
+        _, mo = sl._mo(x[:, b:e].reshape(-1, 3), s, 1)
+        mo = mo[0].reshape(len(x), e - b, -1)
+        return np.stack([mo[:, :, occ] for occ in sl._det_occup[s]], axis=1)
 
     return fn
+
+
+def oracle_slater_matrix(owf):
+    """-> fn(x, s) -> (W, n_s, n_s): determinant 0 of spin s at the open-boundary coordinates x."""
+    fn = oracle_slater_matrices(owf)
+    return lambda x, s: fn(OpenConfigs(np.array(x)), s)[:, 0]
 
 
 def fresh_jastrow(mol, mf, x):
@@ -174,6 +303,104 @@ def oracle_state(owf):
 def device_state(wf, dev):
     """(inverse per spin, log|Psi|) of the device's resident state."""
     return [wf.wf_factors[0]._get_state(s)[0][:, 0] for s in (0, 1)], dev.value()[1]
+
+
+def oracle_state_all(owf):
+    """(inverse per spin with every unique determinant (W, D_s, n, n), sign or phase of Psi, log|Psi|) of the oracle's current state."""
+    ph, lg = owf.value()
+    return [owf.wf_factors[0]._inverse[s] for s in (0, 1)], ph, lg
+
+
+def device_state_all(wf, dev):
+    """The same of the device's resident state."""
+    ph, lg = dev.value()
+    return [wf.wf_factors[0]._get_state(s)[0] for s in (0, 1)], ph, lg
+
+
+class Case:
+    """The inputs of one case, of any kind: system, mean field, determinant list, tapes, and the builders of both sides."""
+
+    def __init__(self, name):
+        from pyqmc_amd import pbc
+
+        self.name, self.dets, self.three, self.seed, self.periodic = name, None, False, 3, name in PBC_CASES
+        if name in CASES:
+            make, eps, self.W, self.ns, self.forced = CASES[name]
+            self.mol = make()
+            self.mf = near_degenerate_mf(self.mol, eps)
+        elif name in MD_CASES:
+            which, self.three, eps, self.W, self.ns, self.forced, self.seed = MD_CASES[name]
+            self.mol = systems.water()
+            self.mf = near_degenerate_mf(self.mol, eps, nvirt=6)
+            self.dets = DETS_ALL_ILL if which == "all" else ast.literal_eval(str(helpers.golden("g8_protocol_h2o_multidet")["det_json"]))
+        else:
+            kind, eps, self.W, self.ns, self.forced, self.seed = PBC_CASES[name]
+            if kind == "twist":
+                S, twist = helpers.TWIST_CASES["prim"]
+                kws = {"complex_coeff": True, "twist": twist}
+            elif kind == "c3":
+                S, kws = helpers.PBC_SLATER_CASES["fcc2cubic"], {"complex_coeff": True, "twist": helpers.TWIST_CASES["prim"][1]}
+            elif kind == "cx311":
+                S, kws = np.diag([3.0, 1.0, 1.0]), {"complex_coeff": True}
+            else:
+                S, kws = helpers.PBC_SLATER_CASES[kind], {}
+            self.mol = pbc.get_supercell(systems.diamond_primitive(), S)
+            self.mf = near_degenerate_kmf(self.mol, eps, **kws)
+        self.complex = self.periodic and PBC_CASES[name][0] in ("twist", "cx311", "c3")
+
+    def oracle_wf(self, mf=None, dets=None):
+        mf, dets = self.mf if mf is None else mf, self.dets if dets is None else dets
+        if self.periodic:
+            return helpers.oracle_pbc_wf(None, case=(self.mol, mf))[1]
+        return (helpers.oracle_wf3 if self.three else helpers.oracle_wf)(self.mol, mf, dets)
+
+    def gpu_wf(self):
+        if self.periodic:
+            return helpers.gpu_pbc_wf(None, case=(self.mol, self.mf))[1]
+        if self.three:
+            return helpers.gpu_wf3(self.mol, self.mf, self.dets)
+        return helpers.gpu_wf(self.mol, self.mf, self.dets, jastrow_kws={"ion_cusp": False})
+
+    def configs(self, x, wrap=None):
+        if not self.periodic:
+            return OpenConfigs(np.array(x))
+        from pyqmc_amd.configs import PeriodicConfigs
+
+        return PeriodicConfigs(np.array(x), self.mol.lattice_vectors(), wrap=None if wrap is None else np.array(wrap))
+
+    def tapes(self, nsteps=None, forced=None):
+        return tapes(self.mol, self.W, self.ns if nsteps is None else nsteps, self.forced if forced is None else forced, seed=self.seed)
+
+    def permuted(self, seed):
+        """(mean field, determinant list) of the same wave function with every sum over orbitals in another order."""
+        if self.periodic:
+            return permuted_kmf(self.mf, seed), None
+        if self.dets is None:
+            return permuted_mf(self.mf, seed), None
+        return self.mf, permuted_determinants(self.dets, self.mol.nelec, seed)
+
+    def judge(self, inverse, phase, logpsi, cfg, mf=None, dets=None):
+        """``chain_errors`` of a state (inverse per spin, sign or phase and log of Psi) at its own configs, against a freshly built oracle
+        wave function: Slater matrices on the configs object, the Jastrow exponent (both factors with a three-body one) evaluated anew."""
+        owf = self.oracle_wf(mf, dets)
+        sl = owf.wf_factors[0]
+        jast = sum(f.recompute(cfg.copy())[1] for f in owf.wf_factors[1:])
+        multi = self.dets is not None
+        return chain_errors(oracle_slater_matrices(owf), inverse, logpsi - jast, cfg, phase=phase if self.complex else None,
+                            det_map=sl._det_map if multi else None, det_coeff=sl.parameters["det_coeff"] if multi else None)
+
+    def fresh_kinetic(self, cfg):
+        """(ke, grad2) rows of a freshly recomputed oracle state at cfg."""
+        from oracle import energy as oen
+
+        owf = self.oracle_wf()
+        owf.recompute(cfg.copy())
+        return oen.kinetic(cfg.copy(), owf)
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    return Case(name)
 
 
 def kinetic_rows(owf, x):
@@ -220,39 +447,43 @@ def rel_rows(a, b):
 
 
 def case_inputs(name):
-    make, eps, W, nsteps, forced = CASES[name]
-    mol = make()
-    return mol, near_degenerate_mf(mol, eps), W, nsteps, forced
+    c = case(name)
+    return c.mol, c.mf, c.W, c.ns, c.forced
 
 
-def oracle_run(name, mf=None, nsteps=None, with_energy=False):
-    """One oracle chain of case ``name`` (optionally with another mean field of the same wave function, or cut short).
-    -> dict: decisions (nsteps, N, W), margins (same shape, ratio - u), x (final coordinates), chain-error summary ``inv`` / ``log`` /
-    ``q0m1`` / ``cond``, ``ke_upd_vs_fresh`` / ``grad2_upd_vs_fresh`` (rel_rows of the updated state's kinetic rows against a fresh
-    state's at the same coordinates), and with ``with_energy`` the block means ``block_ke`` / ``block_grad2`` of vmc_worker."""
+def oracle_run(name, mf=None, nsteps=None, with_energy=False, dets=None):
+    """One oracle chain of case ``name`` (optionally with another mean field / determinant list of the same wave function, or cut short).
+    -> dict: decisions (nsteps, N, W), margins (same shape, ratio - u), x (final coordinates; folded, with ``wrap``, for a cell),
+    ``psi_phase`` (complex cases), chain-error summary ``inv`` / ``log`` / ``q0m1`` (/ ``phase``), ``cond`` / ``cond_min`` (largest and
+    smallest over walkers and unique determinants), ``ke_upd_vs_fresh`` / ``grad2_upd_vs_fresh`` (rel_rows of the updated state's kinetic
+    rows against a fresh state's at the same coordinates), and with ``with_energy`` the block means ``block_ke`` / ``block_grad2``."""
     from oracle import energy as oen, vmc as ovmc
 
-    mol, mf0, W, ns, forced = case_inputs(name)
-    mf = mf0 if mf is None else mf
-    start, gauss, unif, tstep = tapes(mol, W, ns, forced)
-    ns = ns if nsteps is None else nsteps
-    owf = helpers.oracle_wf(mol, mf)
+    c = case(name)
+    mf, dets = c.mf if mf is None else mf, c.dets if dets is None else dets
+    ns = c.ns if nsteps is None else nsteps
+    start, gauss, unif, tstep = c.tapes()
+    owf = c.oracle_wf(mf, dets)
     N = gauss.shape[1]
     record, margins = [], []
-    emol = copy.copy(mol)
+    emol = copy.copy(c.mol)
     emol._ecp = {}  # only the kinetic rows of vmc_worker's energies are used: spare the oracle its ECP pass
     blk, cfg = ovmc.vmc_worker(emol, owf, start, tstep, gauss[:ns], unif[:ns], with_energy=with_energy, record=record, margins=margins)
     x = np.array(cfg.configs)
-    inv, logpsi = oracle_state(owf)
-    err = chain_errors(oracle_slater_matrix(owf), inv, logpsi - fresh_jastrow(mol, mf, x), x)
-    out = {"decisions": np.asarray(record).reshape(ns, N, W), "margins": np.asarray(margins).reshape(ns, N, W), "x": x,
-           "cond": float(err["cond"].max()), **summary(err)}
+    inv, ph, logpsi = oracle_state_all(owf)
+    err = c.judge(inv, ph, logpsi, cfg, mf, dets)
+    out = {"decisions": np.asarray(record).reshape(ns, N, c.W), "margins": np.asarray(margins).reshape(ns, N, c.W), "x": x,
+           "cond": float(err["cond"].max()), "cond_min": float(err["cond_min"].min()), **summary(err)}
+    if c.periodic:
+        out["wrap"] = np.array(cfg.wrap)
+    if c.complex:
+        out["psi_phase"] = np.array(ph)
     ke_u, g2_u = oen.kinetic(cfg, owf)
-    fresh = helpers.oracle_wf(mol, mf)
-    fresh.recompute(OpenConfigs(x.copy()))
-    ke_f, g2_f = oen.kinetic(OpenConfigs(x.copy()), fresh)
+    fresh = c.oracle_wf(mf, dets)
+    fresh.recompute(cfg.copy())
+    ke_f, g2_f = oen.kinetic(cfg.copy(), fresh)
     out["ke_upd_vs_fresh"], out["grad2_upd_vs_fresh"] = rel_rows(ke_u, ke_f), rel_rows(g2_u, g2_f)
-    out["owf"] = owf
+    out["owf"], out["cfg"] = owf, cfg
     if with_energy:
         out["block_ke"], out["block_grad2"] = float(blk["energyke"]), float(blk["energygrad2"])
     return out
@@ -260,6 +491,8 @@ def oracle_run(name, mf=None, nsteps=None, with_energy=False):
 
 FIXTURE_KEYS = ("decisions", "x", "inv", "log", "q0m1", "cond", "ke_upd_vs_fresh", "grad2_upd_vs_fresh", "min_margin", "forced_min_ratio",
                 "spread_x", "spread_inv", "spread_log", "spread_q0m1")
+PBC_KEYS = FIXTURE_KEYS + ("wrap", "cond_min")     # every periodic case of g51, as "<case>/<key>"
+COMPLEX_KEYS = ("psi_phase", "phase", "spread_phase")  # and the complex ones
 
 
 def unforced_min_margin(run, forced):
@@ -269,30 +502,45 @@ def unforced_min_margin(run, forced):
     return float(m[keep].min())
 
 
-def compute_case(name):
-    """The whole oracle side of a case: the run, a second run with the occupied columns permuted (what two float64 evaluations of one
-    chain differ by), and the precondition figures.  The cluster's is stored by golden/make_golden_conditioning.py."""
-    mol, mf, W, ns, forced = case_inputs(name)
-    a = oracle_run(name, with_energy=name in LIVE)
-    b = oracle_run(name, mf=permuted_mf(mf, 1), with_energy=name in LIVE)
-    out = {k: a[k] for k in a if k not in ("margins", "owf")}
+def permuted_run(name, seed=1, **kw):
+    mf, dets = case(name).permuted(seed)
+    return oracle_run(name, mf=mf, dets=dets, **kw)
+
+
+def combine_runs(name, a, b):
+    """The oracle side of a case from its run ``a`` and the run ``b`` with the occupied columns permuted (what two float64 evaluations of
+    one chain differ by), with the precondition figures."""
+    forced = case(name).forced
+    out = {k: a[k] for k in a if k not in ("margins", "owf", "cfg")}
     out["min_margin"] = unforced_min_margin(a, forced)
     out["forced_min_ratio"] = float(min(a["margins"][k].min() for k in forced))  # (u = 0: the margin is the ratio)
     out["decisions_equal_permuted"] = bool(np.array_equal(a["decisions"], b["decisions"]))
     out["spread_x"] = float(np.max(np.abs(a["x"] - b["x"])))
-    for k in ("inv", "log", "q0m1"):
+    for k in ("inv", "log", "q0m1") + (("phase",) if "phase" in a else ()):
         out["spread_" + k] = b[k] / a[k]
-    if name in LIVE:
+    if "block_ke" in a:
         out["spread_block_ke"] = abs(a["block_ke"] - b["block_ke"])
         out["spread_block_grad2"] = abs(a["block_grad2"] - b["block_grad2"])
     return out
 
 
+def compute_case(name):
+    """The whole oracle side of a case.  The cluster's and the periodic cases' are stored by golden/make_golden_conditioning.py."""
+    return combine_runs(name, oracle_run(name, with_energy=name in LIVE), permuted_run(name, with_energy=name in LIVE))
+
+
 @functools.lru_cache(maxsize=None)
 def oracle_case(name):
-    """The oracle side of a case, computed once per process (water cases) or read from the fixture (cluster)."""
-    if name in LIVE:
+    """The oracle side of a case, computed once per process (molecular cases) or read from a fixture (cluster: g50; periodic: g51)."""
+    if name in LIVE_ALL:
         return compute_case(name)
+    if name in PBC_CASES:
+        g = helpers.golden(PBC_FIXTURE)
+        keys = PBC_KEYS + (COMPLEX_KEYS if case(name).complex else ())
+        out = {k: (g[f"{name}/{k}"] if g[f"{name}/{k}"].ndim else g[f"{name}/{k}"].item()) for k in keys}
+        out["decisions"] = out["decisions"].astype(bool)
+        out["decisions_equal_permuted"] = bool(g[f"{name}/decisions_equal_permuted"])
+        return out
     g = np.load(os.path.join(helpers.GOLDEN, FIXTURE + ".npz"), allow_pickle=False)
     out = {k: (g[k] if g[k].ndim else g[k].item()) for k in FIXTURE_KEYS}
     out["decisions"] = out["decisions"].astype(bool)
@@ -305,25 +553,107 @@ DMC_TSTEP, DMC_STEPS, DMC_SEED = 0.02, 30, 77
 DMC_ETRIAL, DMC_BRANCHCUT = -5.0, 50.0  # fixed inputs of both sides (the local energies of this trial function scatter around it: weights stay O(1))
 
 
-def oracle_dmc(mol, mf, x0, device_tapes, tmoves=True):
-    """``oracle.dmc.dmc_propagate`` on the draws of a device-RNG DMC block (``DeviceWF.philox_dmc_tapes``), from coordinates x0 with unit
-    weights.  -> dict: per-walker ``min_margin`` (smallest |margin| of any of its tests), ``accepted`` (steps, 2) counts of accepted
-    drift-diffusion moves / T-moves per step, x, weights, the chain-error summary and cond."""
+# The periodic DMC chains: case -> (fixture prefix, steps, e_trial); host tapes from PBC_DMC_TAPE_SEED.  gamma-1e-5 runs the launch-per-move
+# sweep only (its handle refuses the resident one); cubic-1e-5 runs both, its resident sweep being k_sweep_res<DMC, PBC>.  e_trial from the
+# oracle's local energies of the 13 start walkers: gamma median -3.1, mean -6.6 with the one outlier (a walker next to a node, 3e3) cut at
+# the branch cut; cubic median -16.0 (a step of its oracle chain takes 15 s of CPU: 12 steps).  The local energies of these random trial functions scatter by tens of hartree, so the weights are O(1) only in the
+# median (gamma: 0.63, with single walkers at 5e-4 and 3.1), not for every walker; the device's weights are compared relatively.
+PBC_DMC_TAPE_SEED = 78
+PBC_DMC = {"gamma-1e-5": ("dmc", DMC_STEPS, -5.0), "cubic-1e-5": ("dmc_cubic", 12, -16.0)}
+PBC_DMC_KEYS = ("min_margin", "accepted", "x", "wrap", "weights", "cond", "inv", "log", "q0m1", "spread_x", "spread_weights", "wrap_first")
+PBC_DMC_FIRST = 2  # "wrap_first": the wrap counters after this many steps (1 for cubic), which the CPU test reproduces live
+
+
+def host_dmc_tapes(seed, nsteps, N, necp, W, tmoves=True):
+    """A seeded dictionary of the arrays ``DeviceWF.dmc_steps(tapes=...)`` takes (the layout of ``philox_dmc_tapes``): both sides of a DMC
+    chain can then run without the other."""
+    r = np.random.default_rng(seed)
+
+    def rots(*shape):
+        q = r.standard_normal(shape + (4,))
+        w, x, y, z = np.moveaxis(q / np.linalg.norm(q, axis=-1, keepdims=True), -1, 0)
+        return np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], axis=-1),
+                         np.stack([2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)], axis=-1),
+                         np.stack([2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], axis=-1)], axis=-2)
+
+    t = {"gauss": r.standard_normal((nsteps, N, W, 3)), "unif": r.random((nsteps, N, W))}
+    if necp:
+        t["ecp_rot"], t["ecp_unif"] = rots(nsteps + 1, N, necp), r.random((nsteps + 1, N, necp, W))
+        if tmoves:
+            t["tm_rot"], t["tm_unif"] = rots(nsteps, N, necp), r.random((nsteps, N, necp, W))
+            t["tm_u1"], t["tm_u2"] = r.random((nsteps, N, W)), r.random((nsteps, N, W))
+    return t
+
+
+def _oracle_dmc(mol, owf, cfg0, device_tapes, e_trial, judge, tmoves=True):
     from oracle import dmc as odmc, energy as oen
 
-    W, N = x0.shape[:2]
-    owf = helpers.oracle_wf(mol, mf)
+    W, N = cfg0.configs.shape[:2]
     tape = helpers.DeviceDmcTape(device_tapes, N, len(oen.ecp_atoms(mol)), tmoves)
     nsteps = device_tapes["gauss"].shape[0]
     record, margins = [], []
-    _, cfg, wts = odmc.dmc_propagate(mol, owf, OpenConfigs(np.array(x0)), np.ones(W), DMC_TSTEP, DMC_BRANCHCUT, DMC_ETRIAL, DMC_ETRIAL,
+    _, cfg, wts = odmc.dmc_propagate(mol, owf, cfg0, np.ones(W), DMC_TSTEP, DMC_BRANCHCUT, e_trial, e_trial,
                                      nsteps, tape, record=record, margins=margins)
     x = np.array(cfg.configs)
-    inv, logpsi = oracle_state(owf)
-    err = chain_errors(oracle_slater_matrix(owf), inv, logpsi - fresh_jastrow(mol, mf, x), x)
+    err = judge(owf, cfg)
     per_step = len(record) // nsteps
     acc = np.zeros((nsteps, 2, W))
     for k, (kind, _, a) in enumerate(record):
         acc[k // per_step, 0 if kind == "d" else 1] += a
-    return {"min_margin": np.min([np.abs(m) for _, _, m in margins], axis=0), "accepted": acc, "x": x, "weights": np.asarray(wts),
-            "cond": float(err["cond"].max()), **summary(err)}
+    out = {"min_margin": np.min([np.abs(m) for _, _, m in margins], axis=0), "accepted": acc, "x": x, "weights": np.asarray(wts),
+           "cond": float(err["cond"].max()), **summary(err)}
+    if hasattr(cfg, "wrap"):
+        out["wrap"] = np.array(cfg.wrap)
+    return out
+
+
+def oracle_dmc(mol, mf, x0, device_tapes, tmoves=True):
+    """``oracle.dmc.dmc_propagate`` on the draws of a device-RNG DMC block (``DeviceWF.philox_dmc_tapes``), from coordinates x0 with unit
+    weights.  -> dict: per-walker ``min_margin`` (smallest |margin| of any of its tests), ``accepted`` (steps, 2) counts of accepted
+    drift-diffusion moves / T-moves per step, x, weights, the chain-error summary and cond."""
+
+    def judge(owf, cfg):
+        x = np.array(cfg.configs)
+        inv, logpsi = oracle_state(owf)
+        return chain_errors(oracle_slater_matrix(owf), inv, logpsi - fresh_jastrow(mol, mf, x), x)
+
+    return _oracle_dmc(mol, helpers.oracle_wf(mol, mf), OpenConfigs(np.array(x0)), device_tapes, DMC_ETRIAL, judge, tmoves)
+
+
+def pbc_dmc_tapes(name):
+    from oracle import energy as oen
+
+    c = case(name)
+    return host_dmc_tapes(PBC_DMC_TAPE_SEED, PBC_DMC[name][1], int(np.sum(c.mol.nelec)), len(oen.ecp_atoms(c.mol)), c.W)
+
+
+def pbc_dmc_first(name):
+    return PBC_DMC_FIRST if name == "gamma-1e-5" else 1
+
+
+def oracle_pbc_dmc(name, permuted=False, nsteps=None):
+    """The oracle side of a periodic DMC chain: ``dmc_propagate`` over PeriodicConfigs (T-moves folded into the cell, Ewald energies) on
+    the host tapes, from the case's start walkers; ``permuted``: with the occupied columns in another order."""
+    c = case(name)
+    mf = c.permuted(1)[0] if permuted else c.mf
+    t = pbc_dmc_tapes(name)
+    if nsteps is not None:
+        t = {k: v[:nsteps + 1 if k.startswith("ecp_") else nsteps] for k, v in t.items()}
+    start, *_ = c.tapes(1, ())
+    return _oracle_dmc(c.mol, c.oracle_wf(mf), start, t, PBC_DMC[name][2], lambda owf, cfg: c.judge(*oracle_state_all(owf), cfg, mf))
+
+
+def combine_dmc(a, b, first):
+    """The fixture entries of a chain from its run ``a``, the permuted-column run ``b`` and the cut-short run ``first``."""
+    out = dict(a)
+    good = a["min_margin"] >= 1e-7
+    out["spread_x"] = float(np.max(np.abs(b["x"] - a["x"])[good]))
+    out["spread_weights"] = float(np.max(np.abs(b["weights"] / a["weights"] - 1)[good]))
+    out["wrap_first"] = first["wrap"]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_pbc_dmc_case(name):
+    g, p = helpers.golden(PBC_FIXTURE), PBC_DMC[name][0]
+    return {k: (g[f"{p}/{k}"] if g[f"{p}/{k}"].ndim else g[f"{p}/{k}"].item()) for k in PBC_DMC_KEYS}

@@ -373,12 +373,19 @@ def unfold_ao(sup, kpts, ao_super):
     return out
 
 
-def oracle_pbc_wf(tag, Ls=None):
-    """Oracle Slater x Jastrow for a PBC_SLATER_CASES entry, parameters as make_golden.ref_pbc_wf."""
+def _pbc_case(tag, case):
+    if case is not None:
+        return case
+    return big_cell_case() if tag == "big" else (big_complex_case() if tag == "big_complex" else pbc_slater_case(tag))
+
+
+def oracle_pbc_wf(tag, Ls=None, case=None):
+    """Oracle Slater x Jastrow for a PBC_SLATER_CASES entry (or for ``case`` = (supercell, k-point mean field)), parameters as
+    make_golden.ref_pbc_wf."""
     from oracle import jastrow_basis, wf as owf
     from pyqmc_amd import pbc
 
-    sup, mf = big_cell_case() if tag == "big" else (big_complex_case() if tag == "big_complex" else pbc_slater_case(tag))
+    sup, mf = _pbc_case(tag, case)
     if Ls is None:
         Ls = pbc.lattice_points_within(sup.original_cell.lattice_vectors(), 30.0)
     sl = owf.Slater.periodic(sup, mf.kpts, mf.mo_coeff, Ls)
@@ -389,10 +396,10 @@ def oracle_pbc_wf(tag, Ls=None):
     return sup, owf.MultiplyWF(sl, ja)
 
 
-def gpu_pbc_wf(tag, **kw):
+def gpu_pbc_wf(tag, case=None, **kw):
     import pyqmc_amd as pa
 
-    sup, mf = big_cell_case() if tag == "big" else (big_complex_case() if tag == "big_complex" else pbc_slater_case(tag))
+    sup, mf = _pbc_case(tag, case)
     wf = pa.generate_wf(sup, mf, **kw)
     a, b = pbc_jastrow_coeffs(sup)
     wf.parameters["wf2acoeff"], wf.parameters["wf2bcoeff"] = a, b

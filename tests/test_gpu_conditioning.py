@@ -10,6 +10,14 @@ from the fixture g50 for the cluster), never anything the device produced; test_
 Measured on an MI355X (every figure is printed, and written to $PQA_TEST_REPORT_DIR/parity_report_conditioning.json where that is set;
 DESIGN.md section 33 has the table): largest
 device / oracle ratio 5.3 through k_sweep_r8, 4.7 through k_sweep_res, 7.6 through the launch-per-move sweep, 3.1 in the DMC chains.
+
+(e) - (g) and the last two cases of (d): the same for periodic cells (real, complex, twisted: launch-per-move sweep, wave-per-walker
+launches, k_sweep_res<PBC> and <PBC, CX> on the cells that sweep takes), for multi-determinant handles with two- and three-body Jastrow
+factors (k_sweep_ww and the k_propose / k_accept launches; every unique determinant's inverse is judged) and for periodic DMC chains on
+host tapes (launch-per-move sweep and k_sweep_res<DMC, PBC>); their oracle side is the fixture g51 or runs live.  Largest device / oracle ratio: 4.5 through k_sweep_res<PBC[, CX]>, 6.3
+through the periodic launch-per-move sweep, 4.5 through the wave-per-walker launches, 6.3 through k_sweep_ww, 3.9 through k_propose /
+k_accept, 4.4 in the periodic DMC chains (2.5 through k_sweep_res<DMC, PBC>).  Which sweep ran is asserted from the profiler's bracket
+counts (_sweep_launches) or the resident sweep's set-up report.
 """
 
 import json
@@ -268,33 +276,261 @@ def test_quad_kinetic_pass_within_its_first_order_bound():
             "grad2": note("quad_standalone_grad2_rows_over_oracle", cond.rel_rows(rows[4][:NQ], g2_f) / cond.rel_rows(g2_u, g2_o))})
 
 
+# ---------------------------------------------------------------- (e) periodic, complex and twisted sweeps
+PBC_PATHS = {"res": {"PQA_RES": "1"},                            # k_sweep_res<.., PBC> / <.., PBC, CX>
+             "launches": {"PQA_RES": "0"},                       # k_step_lw<PBC, CX, ..>, blocked update and k_flush_lw
+             "ww-launches": {"PQA_RES": "0", "PQA_LW": "0"}}     # wave per walker: k_propose<CX> / k_accept<CX>
+
+
+def _pbc_handle(c, path, monkeypatch):
+    for k in ("PQA_RES", "PQA_R8", "PQA_LW", "PQA_WW"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in PBC_PATHS[path].items():
+        monkeypatch.setenv(k, v)  # read when the handle is created
+    monkeypatch.setenv("PQA_RES_DEBUG", "1")
+    wf = c.gpu_wf()
+    return wf, wf.fused_device()
+
+
+def _assert_res_ran(capfd):
+    """PQA_RES_DEBUG makes res_setup report its tables once it has accepted the system: with PQA_RES=1 the sweep then is k_sweep_res."""
+    out, err = capfd.readouterr()
+    print(out, end="")
+    assert "[pqa_res]" in err
+
+
+def _sweep_launches(dev):
+    """(bracketed orbital launches at proposals, bracketed k_step_lw launches) of the sweeps since ``profile_enable`` — which sweep ran:
+    k_sweep_ww launches no orbital kernel at all (0, 0); k_propose -> orbitals -> k_accept one per move, of which every 4th is bracketed
+    (> 0, 0); the lane-per-walker launch-per-move sweep also brackets a sample of its k_step_lw launches (> 0, > 0); a resident sweep
+    brackets its one launch per sweep (sweeps, 0).  (test_gpu_pbc.py::test_event_brackets_do_not_change_the_sweep: the brackets leave
+    the numbers alone.)"""
+    dev.sync()
+    n_orb, n_part = dev.profile_query()[0], dev.profile_query_part()[0]
+    dev.profile_enable(False)
+    return n_orb, n_part
+
+
+def _device_configs(c, dev, start):
+    """The device's walkers as the container of their kind: for a cell folded coordinates and wrap counters (start wraps plus the
+    sweeps' wrap deltas), fetched as the VMC driver does."""
+    if not c.periodic:
+        return c.configs(dev.configs())
+    from pyqmc_amd.vmc import _fetch
+
+    cfg = start.copy()
+    _fetch(dev, cfg)
+    return cfg
+
+
+def _chain_ratios(c, o, tag, wf, dev, cfg, rows, nrows=None):
+    """The device's chain errors and kinetic rows over the oracle's own, noted; -> {key: ratio}."""
+    inv, phase, logpsi = cond.device_state_all(wf, dev)
+    err = c.judge(inv, phase, logpsi, cfg)
+    dev_err = cond.summary(err)
+    note(f"{tag}_cond", err["cond"].max())
+    note(f"{tag}_cond_min", err["cond_min"].min())
+    r = {}
+    for k in dev_err:
+        note(f"{tag}_{k}", dev_err[k])
+        r[k] = note(f"{tag}_{k}_over_oracle", dev_err[k] / o[k])
+    r["x"] = note(f"{tag}_x_over_oracle_spread", float(np.max(np.abs(cfg.configs - o["x"]))) / o["spread_x"])
+    n = c.W if nrows is None else nrows
+    sub = c.configs(cfg.configs[:n], cfg.wrap[:n]) if c.periodic else c.configs(cfg.configs[:n])
+    ke_f, g2_f = c.fresh_kinetic(sub)
+    r["ke"] = note(f"{tag}_ke_rows_over_oracle", cond.rel_rows(rows[0][:n], ke_f) / o["ke_upd_vs_fresh"])
+    r["grad2"] = note(f"{tag}_grad2_rows_over_oracle", cond.rel_rows(rows[4][:n], g2_f) / o["grad2_upd_vs_fresh"])
+    return r
+
+
+def _pbc_params():
+    """Every periodic case through the launch-per-move sweep; the two primitive cells also through the wave-per-walker launches; the
+    resident sweep on the cells it takes (res_setup refuses more than 128 lattice-sum candidates: the primitive cells have 249, 3x1x1
+    has 183 — with PQA_RES=1 those handles run the launch-per-move sweep again)."""
+    return [(n, p) for n in cond.PBC_CASES for p in PBC_PATHS
+            if (p == "launches" or (p == "res" and n in cond.RES_ELIGIBLE) or (p == "ww-launches" and n in ("gamma-1e-5", "twist-1e-5")))]
+
+
+@pytest.mark.parametrize("name,path", _pbc_params())
+def test_periodic_chain_on_tapes_against_the_oracle(name, path, monkeypatch, capfd):
+    """The periodic cases of tests/conditioning.py (diamond at Gamma and twisted: 100 sweeps; 3x1x1 with complex coefficients: 30; 2x2x2:
+    12; the conventional cell, real and twisted: 20; no recompute, forced sweeps) through the launch-per-move sweep (k_step_lw, blocked
+    update, k_flush_lw), the resident sweep k_sweep_res<PBC> (2x2x2: two orbital tiles; conventional cell: one) and k_sweep_res<PBC, CX>
+    (twisted conventional cell) and, for the two primitive cells, the wave-per-walker launches (k_propose / k_accept), on the oracle's tapes.
+    Every decision is the oracle's (fixture g51; its unforced |ratio - u| is > 1e-5 everywhere) and so is every wrap counter.  In units of
+    the oracle's own figure for the same chain, each <= 8: the inverse of both spins against a refined inverse of the oracle's Slater
+    matrix on the device's PeriodicConfigs (coordinates and wraps), log|Psi| and, for complex cases, the phase of Psi against fresh ones,
+    max |q_e - 1|; the folded coordinates in units of what two float64 oracle runs differ by; the per-walker ke and grad2 rows of the
+    standalone energy pass against the oracle on a fresh state at the device's configs (k222: the first 4 walkers), in units of the
+    oracle's updated-against-fresh difference."""
+    c, o = cond.case(name), cond.oracle_case(name)
+    wf, dev = _pbc_handle(c, path, monkeypatch)
+    dev.set_ewald(10, 1)
+    start, gauss, unif, tstep = c.tapes()
+    wf.recompute(start)
+    dev.profile_enable(True)
+    acc, en, rec = dev.vmc_sweeps(tstep, c.ns, gauss=gauss, unif=unif, energy=False, record=True)
+    n_orb, n_part = _sweep_launches(dev)
+    rows = np.real(dev.energy(10.0, seed=9))
+    tag = f"{name}_{path}"
+    note(f"{tag}_bracketed_orbital_launches", n_orb), note(f"{tag}_bracketed_step_lw_launches", n_part)
+    if path == "res":
+        _assert_res_ran(capfd)
+        assert (n_orb, n_part) == (c.ns, 0)
+    elif path == "launches":
+        assert n_orb > c.ns and n_part > 0  # k_orb per move, k_step_lw
+    else:
+        assert n_orb > c.ns and n_part == 0  # PQA_LW=0 took effect: k_propose / k_accept around the orbital launches
+    assert dev.pbc and bool(dev.cplx) == c.complex
+    for k, v in o.items():
+        if isinstance(v, float):
+            note(f"{name}_oracle_{k}", v)  # the yardsticks themselves
+    same = rec == o["decisions"]
+    note(f"{tag}_decisions_equal", same.mean())
+    assert same.all(), (int((~same).sum()), np.argwhere(~same)[:4].tolist())
+    cfg = _device_configs(c, dev, start)
+    wraps = cfg.wrap == o["wrap"]
+    note(f"{tag}_wraps_equal", wraps.mean())
+    r = _chain_ratios(c, o, tag, wf, dev, cfg, rows, nrows=4 if name == "k222-1e-5" else None)
+    assert wraps.all(), np.argwhere(~wraps)[:4].tolist()
+    _check(r)
+
+
+# ---------------------------------------------------------------- (f) multi-determinant and three-body handles
+@pytest.mark.parametrize("ww", ["1", "0"])
+@pytest.mark.parametrize("name", list(cond.MD_CASES))
+def test_multidet_chain_on_tapes_against_the_oracle(name, ww, monkeypatch):
+    """The multi-determinant cases (H2O with 6 'all-ill' determinants and a two-body Jastrow; with the 'mixed' list of g8 and two- plus
+    three-body Jastrow factors; 100 sweeps, forced sweeps 5 and 50) through the fused wave-per-walker sweep k_sweep_ww (PQA_WW=1) and the
+    k_propose -> orbitals -> k_accept launches (PQA_WW=0), on the oracle's tapes against the oracle run live.  Every decision is the
+    oracle's.  In units of the oracle's own figures, each <= 8: the inverse of EVERY unique determinant of both spins (the largest error
+    counts), log|Psi| against the long-double log-determinants, the coefficients and freshly evaluated Jastrow exponents, max |q_e - 1|,
+    the coordinates, the ke and grad2 rows.  c4-mixed: the resident three-body exponent equals a fresh one to 1e-12 relative — that
+    factor keeps no partial sums, nothing may drift."""
+    c, o = cond.case(name), cond.oracle_case(name)
+    for k in ("PQA_RES", "PQA_R8", "PQA_LW"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("PQA_WW", ww)
+    wf = c.gpu_wf()
+    dev = wf.fused_device()
+    assert max(dev.ndet_s) > 1  # a wave-per-walker handle (which of its two sweeps ran: _sweep_launches below)
+    start, gauss, unif, tstep = c.tapes()
+    wf.recompute(start)
+    dev.profile_enable(True)
+    acc, en, rec = dev.vmc_sweeps(tstep, c.ns, gauss=gauss, unif=unif, energy=False, record=True)
+    n_orb, n_part = _sweep_launches(dev)
+    rows = np.real(dev.energy(10.0, seed=9))
+    tag = f"{name}_ww{ww}"
+    note(f"{tag}_bracketed_orbital_launches", n_orb)
+    assert n_part == 0
+    assert n_orb == 0 if ww == "1" else n_orb > c.ns  # k_sweep_ww did run (no orbital launch) / the launches did (one per move)
+    for k, v in o.items():
+        if isinstance(v, float):
+            note(f"{name}_oracle_{k}", v)
+    same = rec == o["decisions"]
+    note(f"{tag}_decisions_equal", same.mean())
+    assert same.all(), (int((~same).sum()), np.argwhere(~same)[:4].tolist())
+    cfg = _device_configs(c, dev, start)
+    r = _chain_ratios(c, o, tag, wf, dev, cfg, rows)
+    if c.three:
+        j3 = wf.wf_factors[2]
+        u_res = j3.value()[1]
+        u_fresh = j3.recompute(cfg)[1]  # (last: this replaces the factor's resident state)
+        drift = note(f"{tag}_j3_exponent_resident_vs_fresh", helpers.relerr(u_res, u_fresh))
+        assert drift <= 1e-12
+    _check(r)
+
+
+# ---------------------------------------------------------------- (g) the periodic DMC instantiation
+@pytest.mark.parametrize("name,path", [("gamma-1e-5", "launches"), ("cubic-1e-5", "launches"), ("cubic-1e-5", "res")])
+def test_periodic_dmc_chain_against_the_oracle(name, path, monkeypatch, capfd):
+    """DMC chains at tstep 0.02 on 13 walkers: gamma-1e-5, 30 steps, through the launch-per-move sweep (the primitive cell's handle
+    refuses the resident one); cubic-1e-5, 12 steps (384 moves and 384 T-move proposals per walker), through the launch-per-move sweep
+    and through k_sweep_res<DMC, PBC>.  T-move candidates folded into the cell, wrap counters, Ewald energies in the weights.  Unlike the
+    open case the draws are HOST tapes (conditioning.host_dmc_tapes), so the oracle side (oracle.dmc.dmc_propagate over PeriodicConfigs,
+    twice, occupied columns permuted) is the committed fixture g51.  The conditions of test_dmc_chain_against_the_oracle: a walker is
+    excused only where the oracle itself had |margin| < 1e-7, at most one of the 13; the oracle alone shows rejections and T-moves;
+    per-step accepted counts exact; coordinates, wrap counters, weights and chain errors within 8 x the oracle's own."""
+    import pyqmc_amd as pa
+
+    c, o = cond.case(name), cond.oracle_pbc_dmc_case(name)
+    _, nsteps, e_trial = cond.PBC_DMC[name]
+    wf, dev = _pbc_handle(c, path, monkeypatch)
+    pa.EnergyAccumulator(c.mol).bind(dev)  # the Ewald tables and quadrature rule of the oracle's defaults
+    start, *_ = c.tapes(1, ())
+    wf.recompute(start)
+    w = np.ones(c.W)
+    avg, acc = dev.dmc_steps(cond.DMC_TSTEP, nsteps, w, cond.DMC_BRANCHCUT, e_trial, e_trial, tapes=cond.pbc_dmc_tapes(name))
+    if path == "res":
+        _assert_res_ran(capfd)
+    good = o["min_margin"] >= 1e-7
+    tag = f"pbc_dmc_{name}_{path}"
+    note(f"{tag}_walkers_excused", (~good).sum())
+    note(f"{tag}_oracle_min_margin", o["min_margin"].min())
+    assert (~good).sum() <= 1
+    N, W = start.configs.shape[1], c.W
+    assert o["accepted"][:, 0].sum() < 0.999 * nsteps * N * W and o["accepted"][:, 1].sum() >= 1  # rejections and T-moves do occur
+    if good.all():
+        assert np.array_equal(np.rint(acc * W * N), o["accepted"].sum(axis=2)), (acc * W * N, o["accepted"].sum(axis=2))
+    cfg = _device_configs(c, dev, start)
+    x = cfg.configs
+    assert np.max(np.abs(x - o["x"])[good]) < 1e-6  # every decision and T-move the oracle's
+    wraps = (cfg.wrap == o["wrap"])[good]
+    note(f"{tag}_wraps_equal", wraps.mean())
+    r = {}
+    r["x"] = note(f"{tag}_x_over_oracle_spread", float(np.max(np.abs(x - o["x"])[good])) / o["spread_x"])
+    r["weights"] = note(f"{tag}_weights_over_oracle_spread", float(np.max(np.abs(w / o["weights"] - 1)[good])) / o["spread_weights"])
+    err = c.judge(*cond.device_state_all(wf, dev), cfg)
+    dev_err = {"inv": float(err["inv"][good].max()), "log": float(err["log"][good].max()), "q0m1": float(np.abs(err["q0m1"][good]).max())}
+    note(f"{tag}_cond", err["cond"].max())
+    for k in ("inv", "log", "q0m1"):
+        note(f"{tag}_{k}", dev_err[k])
+        r[k] = note(f"{tag}_{k}_over_oracle", dev_err[k] / o[k])
+    assert wraps.all()
+    _check(r)
+
+
 # ---------------------------------------------------------------- (d) walker independence
-@pytest.mark.parametrize("path", ["r8", "res16"])
+@pytest.mark.parametrize("path", ["r8", "res16", "k222-res", "c3-res"])
 def test_walkers_that_share_a_block_are_independent(path, monkeypatch, capfd):
     """The resident sweeps run 8 (k_sweep_r8) or 16 (k_sweep_res) walkers per block through shared LDS tiles and cross-lane sums.  The 13
     walkers of water-1e-5, 3 sweeps on tapes, once as they are and once with walkers and tapes permuted: every walker meets other
     block-mates and another slot, the partly filled block included.  Per walker, after un-permuting, bit for bit: decisions, coordinates,
     log|Psi|, the inverse of both spins, the rows of the standalone energy pass.  (The walker means are sums in another order and are
-    not compared.)"""
-    mol, mf, W, _, _ = cond.case_inputs("water-1e-5")
-    start, gauss, unif, tstep = cond.tapes(mol, W, 3, (1,))
+    not compared.)  'k222-res' / 'c3-res': the same for k222-1e-5 and c3-1e-5 through k_sweep_res<PBC> and <PBC, CX> (image lists and
+    lattice sums in shared LDS), with the wrap deltas and the phase of Psi — the cells the resident sweep takes; the primitive cells'
+    handles refuse it.  (k_sweep_ww runs one wave per walker with no shared tile.)"""
+    name, path = (path.split("-")[0] + "-1e-5", "res") if "-" in path else ("water-1e-5", path)
+    c = cond.case(name)
+    W = c.W
+    start, gauss, unif, tstep = c.tapes(3, (1,))
     perm = np.random.default_rng(1).permutation(W)
     assert not np.array_equal(perm // 8, np.arange(W) // 8)
     outs = []
     for order in (np.arange(W), perm):
-        wf, dev = _handle(mol, mf, path, monkeypatch, capfd)
-        wf.recompute(OpenConfigs(start.configs[order].copy()))
+        if c.periodic:
+            wf, dev = _pbc_handle(c, path, monkeypatch)
+            dev.set_ewald(10, 1)
+            wf.recompute(c.configs(start.configs[order], start.wrap[order]))
+        else:
+            wf, dev = _handle(c.mol, c.mf, path, monkeypatch, capfd)
+            wf.recompute(OpenConfigs(start.configs[order].copy()))
         _, _, rec = dev.vmc_sweeps(tstep, 3, gauss=gauss[:, :, order].copy(), unif=unif[:, :, order].copy(), energy=False, record=True)
-        inv, logpsi = cond.device_state(wf, dev)
-        got = {"rec": np.moveaxis(rec, 2, 0), "x": dev.configs(), "logpsi": logpsi, "inv_up": inv[0], "inv_dn": inv[1],
+        inv, phase, logpsi = cond.device_state_all(wf, dev)
+        got = {"rec": np.moveaxis(rec, 2, 0), "x": dev.configs(), "logpsi": logpsi, "inv_up": inv[0][:, 0], "inv_dn": inv[1][:, 0],
                "rows": np.real(dev.energy(10.0, seed=9))[[0, 1, 2, 4]].T}  # ke, ee, ei, grad2 (the ECP row draws its grid per walker index)
+        if c.periodic:
+            got["wrap_delta"], got["phase"] = dev.wrap_delta(), phase
         back = np.argsort(order)
         outs.append({k: v[back] for k, v in got.items()})
     if path == "r8":
         _assert_r8_ran(capfd)
+    if c.periodic:
+        _assert_res_ran(capfd)
     a, b = outs
     assert 0.1 < a["rec"].mean() < 1.0
+    tag = path if not c.periodic else name.split("-")[0] + "_" + path
     for k in a:
         diff = a[k] != b[k]
-        note(f"independence_{path}_{k}_unequal", diff.sum())
+        note(f"independence_{tag}_{k}_unequal", diff.sum())
         assert not diff.any(), (k, np.argwhere(diff)[:4].tolist())
