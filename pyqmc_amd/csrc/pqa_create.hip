@@ -393,7 +393,7 @@ int set_mo(pqa_handle* h, int s, const double* mo_host) {
   if (h->nmo[s] == 0 || !mo_host) return 0;  // an empty spin channel (fully polarised systems): nothing to upload
   HIPCHK(hipMemcpy(h->d_mo[s], mo_host, (size_t)h->nao * std::max(h->nmo[s], 1) * sizeof(double), hipMemcpyHostToDevice));
   for (int t = 0; t < 2; ++t) TRY(upload_cpad(h, t, s, mo_host));
-  TRY(res_refresh_coeff(h, s, mo_host));  // (the resident sweep's dense coefficient copy, if it keeps one)
+  TRY(cres_upload(h, s, mo_host));  // (the resident sweep's dense coefficient copy, if it keeps one)
   return 0;
 }
 
@@ -473,9 +473,9 @@ static int create_switches(pqa_handle* h, const pqa_system_t* sys) {
   // Environment switches.  Each pins one of two routes that the handle otherwise picks from the system and the shard size, so that
   // a test can compare them (results agree up to summation order, bitwise where the test says so).  Read here unless noted;
   // the last column names the tests/test_gpu_*.py files that set the switch:
-  //   PQA_RES 0|1           resident sweeps off / forced (default: res_eligible, r8_eligible)               fullsize, parity, pbc
+  //   PQA_RES 0|1           resident sweeps off / forced (default: res_plan, r8_plan)                     fullsize, parity, pbc
   //   PQA_R8 0|1            k_sweep_r8 off / forced for open-boundary real handles                          fullsize, parity
-  //   PQA_WW 0|1            one-launch wave-per-walker sweep off / forced (default: up to ww_max walkers)   fullsize
+  //   PQA_WW 0|1            one-launch wave-per-walker sweep off / forced (default: up to ww.max walkers)   fullsize
   //   PQA_LW 0              wave-per-walker kernels instead of the lane-per-walker fused sweep              parity, pbc
   //   PQA_LW_KB k           electrons per Sherman-Morrison block (0: every row on every move)               parity; bench.py reads it
   //   PQA_LW_GM g           thread groups per walker of the move kernels (0: automatic)                     jastrow_merge
@@ -495,15 +495,16 @@ static int create_switches(pqa_handle* h, const pqa_system_t* sys) {
   //   PQA_PRE_NCUT n        at least n shell cut-off classes in the pre-pass instantiation (below)          pbc
   //   PQA_PBC_NW n          words per (point, atom) pre-pass image list (below; 1: direct tests)            pbc
   //   PQA_RES_ICAP n        shorter image lists in the periodic resident sweep (pqa_res.hip)                fullsize
-  // Diagnostics: PQA_RES_DEBUG 1|2 prints the resident sweeps' tile / LDS plans (pqa_res.hip, pqa_res8.hip) and the radial-table
-  // fit error; PQA_R8_STAGGER and PQA_R8_ABL set fields of k_sweep_r8's table (pqa_res8.hip; PQA_R8_ABL: timing builds only).
+  // Diagnostics: PQA_RES_DEBUG 1|2 prints the resident sweeps' tile / LDS plans (pqa_res.hip, pqa_res8.hip), the radial-table fit
+  // error and, whenever a handle's sweep takes another route than its last one, "[pqa] sweep route: <kernel>" (sweep_electrons); PQA_R8_STAGGER and PQA_R8_ABL set fields of k_sweep_r8's table (pqa_res8.hip; PQA_R8_ABL: timing builds only).
   const struct { const char* name; int* field; } sw[] = {
-      {"PQA_ORB_TP", &h->orb_tp}, {"PQA_LW", &h->lw_mode}, {"PQA_RES", &h->res_mode}, {"PQA_R8", &h->r8_mode}, {"PQA_WW", &h->ww_mode},
-      {"PQA_ECP_DEFER", &h->ecp_defer}, {"PQA_ORB_WS", &h->orb_ws}, {"PQA_LW_KB", &h->lw_kb}, {"PQA_LW_GM", &h->lw_gm},
+      {"PQA_ORB_TP", &h->orb_tp}, {"PQA_LW", &h->lw.mode}, {"PQA_RES", &h->res.mode}, {"PQA_R8", &h->r8.mode}, {"PQA_WW", &h->ww.mode},
+      {"PQA_ECP_DEFER", &h->ecp_defer}, {"PQA_ORB_WS", &h->orb_ws}, {"PQA_LW_KB", &h->lw.kb}, {"PQA_LW_GM", &h->lw.gm},
       {"PQA_ECP_WAVE", &h->ecp_wave}, {"PQA_ECP_POINT_LW", &h->ecp_point_lw}, {"PQA_ECP_LDS", &h->ecp_lds}, {"PQA_JAS_FOLD", &h->jas_fold_allowed},
-      {"PQA_ECP_ACC_WAVES", &h->ecp_acc_waves}, {"PQA_STEP_PRE", &h->step_pre}, {"PQA_JAS_MERGE", &h->jas_merge}};
+      {"PQA_ECP_ACC_WAVES", &h->ecp_acc_waves}, {"PQA_STEP_PRE", &h->lw.step_pre}, {"PQA_JAS_MERGE", &h->jas_merge}};
   for (const auto& w : sw)
     if (const char* e = getenv(w.name)) *w.field = atoi(e);
+  h->route.debug = getenv("PQA_RES_DEBUG") != nullptr;
   h->natom = sys->natom; h->nup = sys->nelec_up; h->ndn = sys->nelec_dn; h->N = h->nup + h->ndn;
   h->nao = sys->nao; h->nshell = sys->nshell;
   h->has_slater = sys->has_slater != 0;
@@ -524,7 +525,7 @@ static int create_switches(pqa_handle* h, const pqa_system_t* sys) {
   h->big = h->nup > PQA_MAXN_FAST || h->ndn > PQA_MAXN_FAST || (sys->has_slater && (sys->nmo_up > PQA_MAXN_FAST || sys->nmo_dn > PQA_MAXN_FAST));
   if (h->big && h->twist) FAIL("twisted cells: at most 64 electrons and 64 orbitals per spin channel (the general orbital path evaluates real AOs)");
   if (h->big && h->cplx && !(sys->pbc && sys->nL > 0)) FAIL("complex orbitals beyond 64 per spin: periodic handles only");
-  if (h->big) h->lw_mode = 0;
+  if (h->big) h->lw.mode = 0;
   if (const char* e = getenv("PQA_ORB_GENERAL")) h->orb_general = atoi(e) != 0;
   return 0;
 }
@@ -576,6 +577,7 @@ static int create_orbital_tables(pqa_handle* h, const pqa_system_t* sys, PbcDev&
       h->pbc_high_l = true;  // the general (thread-per-point) orbital path, pqa_orb_pbc.hip
     }
     h->shell_l.push_back(sys->shell_l[s]);
+    h->lmax = std::max(h->lmax, sys->shell_l[s]);
     h->shell_np.push_back(sys->shell_prim_off[s + 1] - sys->shell_prim_off[s]);
     h->shell_ao.push_back(sys->shell_ao_off[s]);
   }

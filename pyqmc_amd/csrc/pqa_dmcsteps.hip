@@ -187,7 +187,7 @@ extern "C" int pqa_dmc_steps(pqa_handle_t* h, double tstep, int nsteps, double b
       mb.gauss = (const double*)h->b_gauss.p; mb.unif = (const double*)h->b_unif.p;
     }
     if (lw && tmoves) TRY(lw_from_aos(h, false));  // the T-moves worked on the AoS coordinates and inverses
-    TRY(sweep_electrons(h, mb, lw, lc));
+    TRY(sweep_electrons(h, mb, lc));
     hipLaunchKernelGGL((k_sum_reset_int<>), dim3(1), dim3(1024), 0, h->stream, (int*)h->b_accw.p, W, (int*)h->b_acccnt.p + 2 * step);
     TRY(check_launch(h, "k_propose/k_accept (dmc)"));
     TRY(energy_dev(h, threshold, (tp && necp) ? tp->ecp_rot + (size_t)(step + 1) * nrot * 9 : nullptr,

@@ -52,6 +52,9 @@ struct ChunkHost {
   int rows_pad = 0;
 };
 
+// which kernels a sweep over the electrons runs (sweep_route, pqa_sweep.hip)
+enum class SweepRoute { none = -1, r8, res, lw, ww, ww_launches };
+
 struct pqa_handle {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -88,6 +91,7 @@ struct pqa_handle {
   EwaldDev ew{};  // periodic Coulomb tables (pqa_set_ewald)
   bool ew_set = false;
   std::vector<int> shell_l, shell_np, shell_ao;
+  int lmax = 0;  // highest l of the basis (picks the LMAX instantiation of the sweeps)
   std::vector<int> rt_shells;  // [nshell][2] host copy of SysDev::shell_rt (radial tables of the contracted shells)
   double rt_err = 0.0;         // largest table error found at create, relative to sum |c| a^k
   std::vector<int> shell_cost;  // phase-1 cost model of a shell (shell_costs): balances the lane groups of the orbital kernels
@@ -119,7 +123,6 @@ struct pqa_handle {
   int* d_colmap[2] = {nullptr, nullptr};  // [ndet_s][nmo_s] column of an orbital in a unique determinant, or -1
   int ecp_wave = 0;  // PQA_ECP_WAVE=1: wave-per-walker ECP accumulation (A/B)
   int ecp_point_lw = 1;  // PQA_ECP_POINT_LW=0: k_ecp_point on the planes instead of k_ecp_point_lw (A/B)
-  int step_pre = 1;      // PQA_STEP_PRE=0: k_step_lw for small shards too (A/B, bitwise check)
   int ecp_acc_waves = 0; // PQA_ECP_ACC_WAVES: 1 / 4 waves per walker in k_ecp_accum / k_kinetic_coulomb (0: 4 while walkers x electrons <= 32768)
   int jas_fold_allowed = 1;  // PQA_JAS_FOLD=0: Voronoi reduction in every periodic Jastrow pair (A/B, bitwise check)
   int ecp_lds = 1;       // PQA_ECP_LDS=0: first-generation k_ecp_count / k_ecp_fill (A/B)
@@ -174,12 +177,14 @@ struct pqa_handle {
   DevBuf b_tmcnt, b_tmoff, b_tmpass, b_tmamp, b_tmacc, b_tmidx, b_tmapos, b_tmu, b_tmtile, b_tmaoff, b_tmptw, b_tmmarks, b_dmcw, b_dmcold, b_dmcr2, b_dmcout;
   int tm_P = 0;
   int *d_ptk = nullptr, *d_pti = nullptr;
-  DevBuf b_xt, b_Tt[2], b_rc[2], b_sel[2], b_auxt, b_kpart, b_rbuf, b_vbuf, b_act;
-  // electrons per Sherman-Morrison block (PQA_LW_KB): -1 automatic (4 for >= 16 electrons per spin), 0 = update every row on
-  // every move.  Blocking is bitwise identical and cuts the inverse's HBM traffic ~3x; it pays since k_flush_lw stages the
-  // block's update vectors in LDS (1.26 -> 0.27 ms per flush at 65536 walkers): commit + flush 15.5 -> 8.4 ms per step.
-  int lw_kb = -1;
-  int lw_gm = 0;  // thread groups of the move kernels (PQA_LW_GM; 0 = automatic)  // lane-per-walker SoA mirrors (pqa_lw.hpp)
+  DevBuf b_xt, b_Tt[2], b_rc[2], b_sel[2], b_auxt, b_kpart, b_rbuf, b_vbuf, b_act;  // lane-per-walker SoA mirrors (pqa_lw.hpp)
+  // launch-per-move sweep on those planes (k_step_lw / k_step_pre, pqa_lw.hpp).  mode (PQA_LW): 1 lane-per-walker fused sweeps for
+  // single-determinant handles, 0 the wave-per-walker kernels.  kb (PQA_LW_KB), electrons per Sherman-Morrison block: -1 automatic (4 for
+  // >= 16 electrons per spin), 0 = update every row on every move.  Blocking is bitwise identical and cuts the inverse's HBM traffic ~3x;
+  // it pays since k_flush_lw stages the block's update vectors in LDS (1.26 -> 0.27 ms per flush at 65536 walkers): commit + flush
+  // 15.5 -> 8.4 ms per step.  gm (PQA_LW_GM): thread groups of the move kernels, 0 = automatic.  step_pre (PQA_STEP_PRE): 0 = k_step_lw
+  // for small shards too (A/B, bitwise check)
+  struct { int mode = 1, kb = -1, gm = 0, step_pre = 1; } lw;
   DevBuf b_rot, b_eunif, b_elocal, b_ecnt, b_eoff, b_epts[2], b_ewgt[2], b_epte[2], b_emo[2], b_ecp;
   int orb_tp = 0;  // 0 = automatic
   struct TpTune { float ms[2] = {1e30f, 1e30f}; int n[2] = {0, 0}; int choice = 0; };  // periodic k_orb: [0] 32-point, [1] 64-point tiles
@@ -187,31 +192,26 @@ struct pqa_handle {
   WideTab wide[2]{};  // lane-group shell lists of the whole-K small-launch kernel (k_orb_wide), per chunk table (64 groups; periodic: 32)
   std::vector<const void*> wide_attr;  // kernels whose dynamic-LDS limit has been raised
   int orb_ws = -1;  // -1 automatic; 1 wave-specialised orbital kernel; 0 phase-alternating k_orb (PQA_ORB_WS)
+  // The route of the last sweep that PQA_RES_DEBUG reported (sweep_route, pqa_sweep.hip; debug: the variable was set at create)
+  struct { bool debug = false; SweepRoute reported = SweepRoute::none; } route;
   // resident sweep (pqa_res.hpp / pqa_res.hip): the whole electron sweep of 16 walkers in one block, one launch per sweep.
-  // PQA_RES: -1 automatic (by shard size, res_eligible), 0 never, 1 whenever the system is in scope
-  int res_mode = -1;
-  bool res_ready = false, res_ok = false;
-  // dense mode: the tile holds the AOs in their own order (rows padded to x4 only) with its own coefficient copy d_cres[s] [rows4][ldc] —
-  // for bases whose chunk-padded rows do not fit one LDS tile (the 2x2x2 diamond cell: 208 AOs, 224 padded rows)
-  bool res_dense = false;
-  int res_rows4 = 0;
+  // mode (PQA_RES): -1 automatic (by shard size, res_plan), 0 never, 1 whenever the system is in scope.  ready / ok: res_setup has run /
+  // accepted the system.  dense: the tile holds the AOs in their own order (rows padded to x4 only, res_rows4) and the contraction
+  // reads d_cres — for bases whose chunk-padded rows do not fit one LDS tile (the 2x2x2 diamond cell: 208 AOs, 224 padded rows)
+  struct { int mode = -1; bool ready = false, ok = false, dense = false; ResTab tab{}; size_t lds = 0; } res;
+  // dense coefficient copy [res_rows_alloc(res_rows4)][ldc] of each spin in AO order, for k_sweep_res's dense mode and k_sweep_r8
+  // (cres_upload: allocated by the first setup that needs it, refreshed by set_mo)
   double* d_cres[2] = {nullptr, nullptr};
-  ResTab res_tab{};
-  size_t res_lds = 0;
-  int res_lmax = 0;
   int pbc_mincls = 0;
   bool pbc_lists_ok = false;
   // second generation of the resident sweep for open-boundary real handles (pqa_res8.hpp / pqa_res8.hip): 8 walkers per 256-thread block, two
-  // blocks per CU, wave-uniform AO phase.  PQA_R8: -1 automatic (r8_eligible), 0 never (k_sweep_res / the launches), 1 whenever in scope
-  int r8_mode = -1;
-  bool r8_ready = false, r8_ok = false;
-  R8Tab r8_tab{};
-  size_t r8_lds = 0;
-  double r8_util = 0.0;
-  bool r8_xaos_next = false;  // the next k_sweep_r8 launch also writes the walker-major coordinates (js.x)
-  bool jsx_current = false;   // ... and did: energy_dev skips its transpose of the coordinate planes
-  // wave-per-walker sweep in one launch (pqa_ww.hpp; PQA_WW): -1 by shard size (up to ww_max walkers), 0 off, 1 always.  50-determinant
+  // blocks per CU, wave-uniform AO phase.  mode (PQA_R8): -1 automatic (r8_plan), 0 never (k_sweep_res / the launches), 1 whenever in
+  // scope.  util: filled atom slots of the work items.  xaos_next: the next k_sweep_r8 launch also writes the walker-major coordinates
+  // (js.x); jsx_current: ... and did: energy_dev skips its transpose of the coordinate planes
+  struct { int mode = -1; bool ready = false, ok = false; R8Tab tab{}; size_t lds = 0; double util = 0.0; bool xaos_next = false, jsx_current = false; } r8;
+  // wave-per-walker sweep in one launch (pqa_ww.hpp).  mode (PQA_WW): -1 by shard size (up to max walkers), 0 off, 1 always.  50-determinant
   // water molecule, VMC step with energy, launches -> one launch: 0.722 -> 0.663 ms at 1 024 walkers, 0.884 -> 0.801 at 2 048, 1.428 -> 1.382 at 4 096, 2.25 -> 2.38 at 8 192
+  struct { int mode = -1; long max = 4096; } ww;
   // ECP point totals left on the device (pqa_energy.hip: small shards on the k_ecp_accum path; PQA_ECP_DEFER=0 reads them every time)
   const double* en_d_ecp = nullptr;  // energy_dev: the ECP row(s) of its last evaluation (nullptr: no ECP)
   long ecp_last_tot[2] = {0, 0};  // energy_dev: points of each spin's list in its last evaluation (-1: totals left on the device)
@@ -219,22 +219,22 @@ struct pqa_handle {
   long* pin_tot = nullptr;  // pinned host words the scan kernels write the ECP point totals to (device-visible: hipHostMallocMapped)
   int ecp_defer = 1;
   // the NEXT step's sweep draws (k_tile_draws) generated beside the energy pass of the current step: second tape set, its stream and events
-  DevBuf b_gauss_b, b_unif_b;
-  hipStream_t draw_stream = nullptr;
-  hipEvent_t draw_ev[2] = {nullptr, nullptr};
-  bool draw_ahead_valid = false, draws_on_device = false;  // draws_on_device: the last sweep took its draws from k_tile_draws
-  uint32_t draw_ahead_step = 0;
-  uint64_t draw_ahead_seed = 0;
-  long draw_ahead_W = 0;
+  // (ahead_*: the step, seed and walker count the set was drawn for; on_device: the last sweep took its draws from k_tile_draws)
+  struct {
+    DevBuf b_gauss_b, b_unif_b;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool ahead_valid = false, on_device = false;
+    uint32_t ahead_step = 0;
+    uint64_t ahead_seed = 0;
+    long ahead_W = 0;
+  } draw;
   hipStream_t en_stream = nullptr;
   hipEvent_t en_ev[3] = {nullptr, nullptr, nullptr};
   bool ecp_hint_valid = false;
   long ecp_hint[2] = {0, 0}, ecp_evals = 0;
   const long* last_ecp_dev[2] = {nullptr, nullptr};
   long orb_p_hint = 0;  // launch_orb: points the next launch is expected to work on when its P is an upper bound (0: P)
-  int ww_mode = -1;
-  long ww_max = 4096;
-  int lw_mode = 1;  // 1: lane-per-walker fused sweep (single determinant); 0: wave-per-walker kernels (PQA_LW)
   // density-matrix sampling (pqa_dm.hpp): per slot the auxiliary walkers (position, orbital row, density), the kept samples
   // and the orbitals at the configurations' electrons; accumulators of the estimator in dm_val / dm_norm
   struct DmSlot { DevBuf pos, row, f, newpos, keep_pos, keep_row, keep_f, cfg; long n = 0, ncfg = 0; int nkeep = 0, spin = 0; };
@@ -390,7 +390,7 @@ struct LwCtx {
 };
 // the lane-per-walker fused sweep (pqa_lw.hpp) covers the handle: one determinant, no three-body Jastrow, complex ones up to 32 per spin
 static inline bool lw_eligible(const pqa_handle* h) {
-  return h->lw_mode != 0 && h->has_slater && h->ndet == 1 && !h->has_j3 && (!h->cplx || std::max(h->nup, h->ndn) <= 32);
+  return h->lw.mode != 0 && h->has_slater && h->ndet == 1 && !h->has_j3 && (!h->cplx || std::max(h->nup, h->ndn) <= 32);
 }
 
 // ---- functions defined in one unit and called from others
@@ -407,19 +407,24 @@ int lw_from_aos(pqa_handle* h, bool with_cache = true);
 int lw_to_aos(pqa_handle* h, bool with_cache);
 int sync_aos(pqa_handle* h);
 int lw_setup(pqa_handle* h, bool lw, LwCtx& c);
-int sweep_electrons(pqa_handle* h, const MoveBuf& mb, bool lw, const LwCtx& lc);
+int sweep_electrons(pqa_handle* h, const MoveBuf& mb, const LwCtx& lc);
 void launch_step_real(pqa_handle* h, const LwState& L, const MoveBuf& mb, const StepArgs& a, int rowlen);
 void launch_flush_real(pqa_handle* h, const LwState& L, int s, long W, long w0, long w1, int j_lo, int j_hi, int nq, int rowlen, int n_s);
 // pqa_sweep_cx.hip
 void launch_step_cx(pqa_handle* h, const LwState& L, const MoveBuf& mb, const StepArgs& a, int rowlen);
 void launch_flush_cx(pqa_handle* h, const LwState& L, int s, long W, long w0, long w1, int j_lo, int j_hi, int nq, int rowlen, int n_s);
-// pqa_res.hip
-bool res_eligible(pqa_handle* h, long W);
-int sweep_res(pqa_handle* h, const MoveBuf& mb);
-int res_refresh_coeff(pqa_handle* h, int s, const double* mo_host);  // (pqa_res.hip: dense coefficient copy follows set_mo)
-// pqa_res8.hip
+// the one-launch sweeps.  *_plan: whether the sweep takes this handle (and shard size) — the setup runs on first use, once per handle; out of
+// scope leaves *use false and returns 0, a device error returns its code with h->err set
+static inline int res_rows4(const pqa_handle* h) { return ((h->twist ? 2 : 1) * h->nao + 3) & ~3; }  // rows of a dense tile: the AOs (twisted: real, then imaginary parts) padded to x4
 static inline int res_rows_alloc(int rows4) { return rows4 + 96; }  // rows of the dense coefficient copies d_cres: zero beyond the basis (k_sweep_r8 contracts six k-steps per trip in every wave)
-bool r8_eligible(pqa_handle* h);
+// pqa_res.hip
+int res_plan(pqa_handle* h, long W, bool* use);
+int sweep_res(pqa_handle* h, const MoveBuf& mb);
+int cres_upload(pqa_handle* h, int s, const double* mo_host);  // d_cres[s]: refreshed from set_mo's mo_host, or (nullptr) made from d_mo[s]
+int unique_primitives(pqa_handle* h, std::vector<double>& pe_u, std::vector<double>& pc_u, std::vector<int>& q0_u);
+int sweep_launch_begin(pqa_handle* h, const MoveBuf& mb, hipEvent_t* e1);  // tapes check and profiling bracket of a one-launch sweep
+// pqa_res8.hip
+int r8_plan(pqa_handle* h, bool* use);
 int sweep_r8(pqa_handle* h, const MoveBuf& mb);
 // pqa_sweep_ww.hip
 bool ww_eligible(pqa_handle* h, long W);

@@ -1,15 +1,34 @@
 // pyqmc_amd C ABI implementation (host side): the resident electron sweep (pqa_res.hpp) — tables, eligibility, launch.
-// Called by sweep_electrons_fused (pqa_sweep.hip) in place of the per-move launches of the lane-per-walker sweep.
+// Chosen by sweep_route (pqa_sweep.hip) in place of the per-move launches of the lane-per-walker sweep.
 #include "pqa_internal.hpp"
 
-// Passes over the padded coefficient rows of the 16-row chunk table (h->chunks[0]: the coefficient matrices cpad[0] are shared
-// with k_orb), shell lists per (pass, lane group), LDS budget.  Once per handle; leaves res_ok = false when the system is outside
-// the kernel's scope.
-// dense coefficient copy [rows4][ldc] of spin s in AO order (rows beyond nao and columns beyond nmo zero)
-int res_refresh_coeff(pqa_handle* h, int s, const double* mo_host) {
-  if (!h->d_cres[s] || h->nmo[s] == 0) return 0;
+// Every instantiation of the kernel, [plain | PBC | PBC + CX][LMAX 2 | 3; the complex row 3 | 2][DMC]: the table drives the dynamic-LDS
+// attribute (res_setup) and the launch (res_kernel, sweep_res).  (s, p, d shells: 25 running sums of a shell's lattice sum in registers;
+// with f shells 35.)  The complex row lists LMAX 3 first because the compiler emits the kernels in the order the unit names them: this is
+// the order it always has, and the unit's device code stays what it was byte for byte.
+using ResKernel = void (*)(SysDev, LwState, MoveBuf, ChunkTab, ResTab, int, long, long, long);
+static const ResKernel res_kernels[3][2][2] = {
+    {{k_sweep_res<false, 2>, k_sweep_res<true, 2>}, {k_sweep_res<false, 3>, k_sweep_res<true, 3>}},
+    {{k_sweep_res<false, 2, true>, k_sweep_res<true, 2, true>}, {k_sweep_res<false, 3, true>, k_sweep_res<true, 3, true>}},
+    {{k_sweep_res<false, 3, true, true>, k_sweep_res<true, 3, true, true>}, {k_sweep_res<false, 2, true, true>, k_sweep_res<true, 2, true, true>}}};
+static ResKernel res_kernel(const pqa_handle* h, bool dmc) {
+  const int variant = h->cplx ? 2 : (h->S.pbc ? 1 : 0);
+  return res_kernels[variant][(h->lmax > 2) != (variant == 2)][dmc];
+}
+
+// Dense coefficient copy d_cres[s] [res_rows_alloc(rows4)][ldc] of spin s in AO order (rows beyond nao and columns beyond nmo zero).
+// mo_host: set_mo's new coefficients — refreshes the copy if a setup has made one; nullptr (the setups): allocated on first use and
+// filled from d_mo[s].
+int cres_upload(pqa_handle* h, int s, const double* mo_host) {
+  if (h->nmo[s] == 0 || (mo_host && !h->d_cres[s])) return 0;
   const int ldc = 16 * h->nt[s], nmo = h->nmo[s];
-  std::vector<double> pad((size_t)res_rows_alloc(h->res_rows4) * ldc, 0.0);  // (zero rows behind the basis: k_sweep_r8's K split)
+  std::vector<double> pad((size_t)res_rows_alloc(res_rows4(h)) * ldc, 0.0), mo;  // (zero rows behind the basis: k_sweep_r8's K split)
+  if (!mo_host) {
+    mo.resize((size_t)h->nao * nmo);
+    HIPCHK(hipMemcpy(mo.data(), h->d_mo[s], mo.size() * sizeof(double), hipMemcpyDeviceToHost));
+    mo_host = mo.data();
+    if (!h->d_cres[s]) TRY(upload_table<double>(h, nullptr, pad.size(), &h->d_cres[s]));
+  }
   for (int a = 0; a < h->nao; ++a)
     for (int j = 0; j < nmo; ++j) pad[(size_t)a * ldc + j] = mo_host[(size_t)a * nmo + j];
   if (h->twist) {  // rows nao .. 2 nao: the imaginary AO parts, (i AO_im)(C_re + i C_im) = AO_im (-C_im + i C_re), columns [re | im] (upload_cpad)
@@ -25,42 +44,46 @@ int res_refresh_coeff(pqa_handle* h, int s, const double* mo_host) {
   return 0;
 }
 
+// Primitives: shells with the same (exponent, coefficient) sequence — the same shell of every atom of a species — share one LDS copy.
+// pe_u / pc_u: the distinct sequences; q0_u[shell]: where the shell's sequence starts in them.
+int unique_primitives(pqa_handle* h, std::vector<double>& pe_u, std::vector<double>& pc_u, std::vector<int>& q0_u) {
+  std::vector<double> pe((size_t)h->S.nprim), pc((size_t)h->S.nprim);
+  std::vector<int> po((size_t)h->nshell + 1);
+  HIPCHK(hipMemcpy(pe.data(), h->S.prim_exp, pe.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(pc.data(), h->S.prim_coef, pc.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(po.data(), h->S.shell_prim_off, po.size() * sizeof(int), hipMemcpyDeviceToHost));
+  q0_u.assign((size_t)h->nshell, 0);
+  for (int sh = 0; sh < h->nshell; ++sh) {
+    const int n = po[sh + 1] - po[sh];
+    int found = -1;
+    for (int prev = 0; prev < sh && found < 0; ++prev)
+      if (po[prev + 1] - po[prev] == n && std::equal(pe.begin() + po[sh], pe.begin() + po[sh + 1], pe.begin() + po[prev]) &&
+          std::equal(pc.begin() + po[sh], pc.begin() + po[sh + 1], pc.begin() + po[prev])) found = q0_u[prev];
+    if (found < 0) { found = (int)pe_u.size(); pe_u.insert(pe_u.end(), pe.begin() + po[sh], pe.begin() + po[sh + 1]); pc_u.insert(pc_u.end(), pc.begin() + po[sh], pc.begin() + po[sh + 1]); }
+    q0_u[sh] = found;
+  }
+  return 0;
+}
+
+// Passes over the padded coefficient rows of the 16-row chunk table (h->chunks[0]: the coefficient matrices cpad[0] are shared
+// with k_orb), shell lists per (pass, lane group), LDS budget.  Once per handle (res_plan); returns 0 and leaves res.ok = false when the system is
+// outside the kernel's scope, an error code (h->err set) when the device refuses a copy, an allocation or the LDS attribute.
 static int res_setup(pqa_handle* h) {
-  h->res_ready = true;
-  h->res_ok = false;
-  if (h->res_mode == 0) return 0;
+  h->res.ok = false;
+  if (h->res.mode == 0) return 0;
   if (!h->has_slater || h->ndet != 1 || h->has_j3) return 0;
   // complex determinants: periodic cells (twisted or not), 16 electrons and 16 orbitals per spin — a row of the inverse is 32 doubles
   if (h->cplx && (!h->S.pbc || h->nup > 16 || h->ndn > 16)) return 0;
   if (h->twist && !h->cplx) return 0;
   if (h->S.pbc && (h->S.nL <= 0 || h->pbc_high_l || !h->pbc_lists_ok)) return 0;  // periodic: lattice-summed orbitals, l <= 3
   if (h->nup > 32 || h->ndn > 32 || h->nmo[0] > 32 || h->nmo[1] > 32 || h->N > 64 || h->N < 1 || h->natom > 64) return 0;
-  int lmax = 0;
-  for (int l : h->shell_l) lmax = std::max(lmax, l);
-  if (lmax > 3) return 0;
-  h->res_lmax = lmax;
+  if (h->lmax > 3) return 0;
   const ChunkHost& c = h->chunks[0];
   const int nch = (int)c.nk.size();
   if (nch == 0) return 0;
-  // primitives: shells with the same (exponent, coefficient) sequence — the same shell of every atom of a species — share one LDS copy
   std::vector<double> pe_u, pc_u;
-  std::vector<int> q0_u((size_t)h->nshell, 0);
-  {
-    std::vector<double> pe((size_t)h->S.nprim), pc((size_t)h->S.nprim);
-    std::vector<int> po((size_t)h->nshell + 1);
-    HIPCHK(hipMemcpy(pe.data(), h->S.prim_exp, pe.size() * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(pc.data(), h->S.prim_coef, pc.size() * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(po.data(), h->S.shell_prim_off, po.size() * sizeof(int), hipMemcpyDeviceToHost));
-    for (int sh = 0; sh < h->nshell; ++sh) {
-      const int n = po[sh + 1] - po[sh];
-      int found = -1;
-      for (int prev = 0; prev < sh && found < 0; ++prev)
-        if (po[prev + 1] - po[prev] == n && std::equal(pe.begin() + po[sh], pe.begin() + po[sh + 1], pe.begin() + po[prev]) &&
-            std::equal(pc.begin() + po[sh], pc.begin() + po[sh + 1], pc.begin() + po[prev])) found = q0_u[prev];
-      if (found < 0) { found = (int)pe_u.size(); pe_u.insert(pe_u.end(), pe.begin() + po[sh], pe.begin() + po[sh + 1]); pc_u.insert(pc_u.end(), pc.begin() + po[sh], pc.begin() + po[sh + 1]); }
-      q0_u[sh] = found;
-    }
-  }
+  std::vector<int> q0_u;
+  TRY(unique_primitives(h, pe_u, pc_u, q0_u));
   const int nprim_u = (int)pe_u.size();
   int rows_cap = 1 << 30;
   size_t part_rn = 0;
@@ -96,7 +119,7 @@ static int res_setup(pqa_handle* h) {
   const bool one = !h->twist && rows_all <= rows_cap && (size_t)80 * rows_all <= avail;
   // dense mode: the chunk padding (16-row chunks: 224 rows for the 208 AOs of the 2x2x2 diamond cell) is what keeps the basis out of one
   // tile, and the AOs in their own order (padded to x4) fit
-  const int rows4 = ((h->twist ? 2 : 1) * h->nao + 3) & ~3;
+  const int rows4 = res_rows4(h);
   const size_t fixed1 = res_lds_fixed(h->nshell, nprim_u, h->natom, h->na, h->nshell, 1);
   bool dense = false;
   if (!one && rows4 <= rows_cap) {
@@ -111,17 +134,9 @@ static int res_setup(pqa_handle* h) {
   const int kt_cap = (one || dense) ? (dense ? rows4 : rows_all) : std::min(rows_cap, (int)(((avail - part_rn) / 80) & ~(size_t)3));
   if (kt_cap < 20) return 0;
   ResTab RT{};
-  h->res_dense = dense;
-  h->res_rows4 = rows4;
-  if (dense) {
-    for (int s = 0; s < 2; ++s) {
-      if (h->nmo[s] == 0) continue;
-      std::vector<double> mo((size_t)h->nao * h->nmo[s]);
-      HIPCHK(hipMemcpy(mo.data(), h->d_mo[s], mo.size() * sizeof(double), hipMemcpyDeviceToHost));
-      if (!h->d_cres[s]) TRY(upload_table<double>(h, nullptr, (size_t)res_rows_alloc(rows4) * 16 * h->nt[s], &h->d_cres[s]));
-      TRY(res_refresh_coeff(h, s, mo.data()));
-    }
-  }
+  h->res.dense = dense;
+  if (dense)
+    for (int s = 0; s < 2; ++s) TRY(cres_upload(h, s, nullptr));
   int ch = 0, kt = 0;
   std::vector<int> pass_of_chunk((size_t)nch, 0);
   if (dense) {
@@ -175,25 +190,16 @@ static int res_setup(pqa_handle* h) {
   TRY(upload_table(h, pe_u.data(), pe_u.size(), &tmp_d)); RT.prim_exp_u = tmp_d;
   TRY(upload_table(h, pc_u.data(), pc_u.size(), &tmp_d)); RT.prim_coef_u = tmp_d;
   RT.nprim_u = nprim_u;
-  h->res_lds = (size_t)RT.region * sizeof(double) + res_lds_fixed(h->nshell, nprim_u, h->natom, h->na, RT.nlist, RT.npass);
-  h->res_lds = (h->res_lds + 7) & ~(size_t)7;
-  RT.pbc_off = (int)h->res_lds; RT.icap = icap;
+  h->res.lds = (size_t)RT.region * sizeof(double) + res_lds_fixed(h->nshell, nprim_u, h->natom, h->na, RT.nlist, RT.npass);
+  h->res.lds = (h->res.lds + 7) & ~(size_t)7;
+  RT.pbc_off = (int)h->res.lds; RT.icap = icap;
   RT.twist = h->twist ? 1 : 0; RT.im_off = h->nao;
   if (const char* e = getenv("PQA_RES_ICAP")) RT.icap = std::max(1, std::min(icap, atoi(e)));  // (tests: short lists, the pairs that overflow walk the masks)
-  h->res_lds += pbc_b;
-  if (h->res_lds > 160 * 1024) return 0;
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_res<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_res<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_res<false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_res<true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_res<false, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_res<true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_res<false, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_res<true, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_res<false, 3, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_res<true, 3, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_res<false, 2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_res<true, 2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  h->res.lds += pbc_b;
+  if (h->res.lds > 160 * 1024) return 0;
+  for (const auto& variant : res_kernels)
+    for (const auto& lm : variant)
+      for (ResKernel k : lm) HIPCHK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   if (const char* dbg = getenv("PQA_RES_DEBUG"); dbg && atoi(dbg) > 1) {  // the lane groups' shell lists with the cost model's figures
     for (int g = 0; g < PQA_RES_G * RT.npass; ++g) {
       fprintf(stderr, "[pqa_res] group %2d:", g);
@@ -201,18 +207,13 @@ static int res_setup(pqa_handle* h) {
       fprintf(stderr, "\n");
     }
   }
-  if (getenv("PQA_RES_DEBUG")) fprintf(stderr, "[pqa_res] passes %d, tile rows %d (padded basis %d), LDS %zu B, image-list capacity %d\n", RT.npass, RT.kt, c.rows_pad, h->res_lds, RT.icap);
-  h->res_tab = RT;
-  h->res_ok = true;
+  if (getenv("PQA_RES_DEBUG")) fprintf(stderr, "[pqa_res] passes %d, tile rows %d (padded basis %d), LDS %zu B, image-list capacity %d\n", RT.npass, RT.kt, c.rows_pad, h->res.lds, RT.icap);
+  h->res.tab = RT;
+  h->res.ok = true;
   return 0;
 }
 
-bool res_eligible(pqa_handle* h, long W) {
-  if (!h->res_ready) {
-    if (res_setup(h) != 0) { h->res_ok = false; h->err.clear(); }
-  }
-  if (!h->res_ok) return false;
-  if (h->res_mode > 0) return true;
+static bool res_auto(const pqa_handle* h, long W) {
   // automatic: measured against the launch-per-move sweep (gpurun_out/res_scan.jsonl, round 5; sweep only): (H2O)8 1.66x at 512
   // walkers, 1.88x at 4096, 1.38x at 16384, 1.06x at 32768, 1.02x at 49152, 0.97x at 65536; H2O (8 electrons: a walker's 32 lanes
   // are mostly idle) 1.2x up to 4096 walkers, 0.49x at 16384.  One round of blocks (16 walkers per CU) always wins.
@@ -227,39 +228,37 @@ bool res_eligible(pqa_handle* h, long W) {
   if (h->S.pbc) return W <= 32768;
   return W <= 4096 || (std::max(h->nup, h->ndn) >= 16 && W <= 49152);
 }
+int res_plan(pqa_handle* h, long W, bool* use) {
+  *use = false;
+  if (!h->res.ready) { TRY(res_setup(h)); h->res.ready = true; }  // (a setup that failed is tried, and fails, again)
+  *use = h->res.ok && (h->res.mode > 0 || res_auto(h, W));
+  return 0;
+}
+
+// What a one-launch sweep does in front of its launch: both tapes are there; under the profiler the launch is bracketed (one launch per
+// sweep: every one) — *e1 is the closing event the caller records behind the launch, nullptr without the profiler.
+int sweep_launch_begin(pqa_handle* h, const MoveBuf& mb, hipEvent_t* e1) {
+  *e1 = nullptr;
+  if (!mb.gauss || !mb.unif) FAIL("resident sweep: the random-number tapes are missing");
+  if (!h->profile) return 0;
+  hipEvent_t e0 = nullptr;
+  TRY(prof_acquire(h, h->prof_orb, e0, *e1));
+  HIPCHK(hipEventRecord(e0, h->stream));
+  h->prof_orb.launches += 1;
+  h->prof_pc += (double)h->W * h->N * 5;  // point-components of this launch (as launch_orb counts them)
+  return 0;
+}
 
 // One sweep over all electrons of walkers [0, W): a single launch.  mb carries both tapes (the caller drew them if there were none).
 int sweep_res(pqa_handle* h, const MoveBuf& mb) {
-  if (!mb.gauss || !mb.unif) FAIL("resident sweep: the random-number tapes are missing");
+  hipEvent_t e1 = nullptr;
+  TRY(sweep_launch_begin(h, mb, &e1));
   const long W = h->W;
   const LwState L = lw_state(h);
   ChunkTab Tc = h->tab[0];
-  if (h->res_dense) { Tc.cpad[0] = h->d_cres[0]; Tc.cpad[1] = h->d_cres[1]; }
+  if (h->res.dense) { Tc.cpad[0] = h->d_cres[0]; Tc.cpad[1] = h->d_cres[1]; }
   const dim3 grid((unsigned)((W + PQA_RES_NW - 1) / PQA_RES_NW)), block(PQA_RES_NT);
-  hipEvent_t e1 = nullptr;
-  if (h->profile) {  // every launch is bracketed (one launch per sweep)
-    hipEvent_t e0 = nullptr;
-    TRY(prof_acquire(h, h->prof_orb, e0, e1));
-    HIPCHK(hipEventRecord(e0, h->stream));
-    h->prof_orb.launches += 1;
-    h->prof_pc += (double)W * h->N * 5;  // point-components of this launch (as launch_orb counts them)
-  }
-#define PQA_RES_LAUNCH(D, LM) hipLaunchKernelGGL((k_sweep_res<D, LM>), grid, block, h->res_lds, h->stream, h->S, L, mb, Tc, h->res_tab, (int)h->has_jastrow, W, 0L, W)
-#define PQA_RES_LAUNCH_P(D, LM) hipLaunchKernelGGL((k_sweep_res<D, LM, true>), grid, block, h->res_lds, h->stream, h->S, L, mb, Tc, h->res_tab, (int)h->has_jastrow, W, 0L, W)
-#define PQA_RES_LAUNCH_C(D, LM) hipLaunchKernelGGL((k_sweep_res<D, LM, true, true>), grid, block, h->res_lds, h->stream, h->S, L, mb, Tc, h->res_tab, (int)h->has_jastrow, W, 0L, W)
-  if (h->cplx) {
-    if (mb.dmc) { if (h->res_lmax <= 2) PQA_RES_LAUNCH_C(true, 2); else PQA_RES_LAUNCH_C(true, 3); }
-    else { if (h->res_lmax <= 2) PQA_RES_LAUNCH_C(false, 2); else PQA_RES_LAUNCH_C(false, 3); }
-  } else
-#undef PQA_RES_LAUNCH_C
-  if (h->S.pbc) {  // (s, p, d shells: 25 running sums of a shell's lattice sum in registers; with f shells 35)
-    if (mb.dmc) { if (h->res_lmax <= 2) PQA_RES_LAUNCH_P(true, 2); else PQA_RES_LAUNCH_P(true, 3); }
-    else { if (h->res_lmax <= 2) PQA_RES_LAUNCH_P(false, 2); else PQA_RES_LAUNCH_P(false, 3); }
-  } else
-#undef PQA_RES_LAUNCH_P
-  if (mb.dmc) { if (h->res_lmax <= 2) PQA_RES_LAUNCH(true, 2); else PQA_RES_LAUNCH(true, 3); }
-  else { if (h->res_lmax <= 2) PQA_RES_LAUNCH(false, 2); else PQA_RES_LAUNCH(false, 3); }
-#undef PQA_RES_LAUNCH
+  hipLaunchKernelGGL(res_kernel(h, mb.dmc != 0), grid, block, h->res.lds, h->stream, h->S, L, mb, Tc, h->res.tab, (int)h->has_jastrow, W, 0L, W);
   if (e1) HIPCHK(hipEventRecord(e1, h->stream));
   return check_launch(h, "k_sweep_res");
 }

@@ -1,43 +1,30 @@
 // pyqmc_amd C ABI implementation (host side): the second-generation resident sweep (pqa_res8.hpp) — work items of the wave-uniform AO
-// phase, eligibility, launch.  Called by sweep_electrons_fused (pqa_sweep.hip) ahead of k_sweep_res and the launch-per-move sweep.
+// phase, eligibility, launch.  sweep_route (pqa_sweep.hip) asks r8_plan ahead of k_sweep_res and the launch-per-move sweep.
 #include "pqa_internal.hpp"
 #include "pqa_res8.hpp"
+
+// Every instantiation of the kernel, [LMAX 2 | 3][DMC]: the table drives the dynamic-LDS attribute (r8_setup) and the launch (sweep_r8).
+using R8Kernel = void (*)(SysDev, LwState, MoveBuf, ChunkTab, R8Tab, int, long, long, long);
+static const R8Kernel r8_kernels[2][2] = {{k_sweep_r8<false, 2>, k_sweep_r8<true, 2>}, {k_sweep_r8<false, 3>, k_sweep_r8<true, 3>}};
 
 // Once per handle.  Work item = one shell type (same l and the same exponent / coefficient sequence: the same shell of every atom of a
 // species) on up to eight atoms; items go to the four waves by descending cost (longest processing time first).  The tile holds the AOs in
 // their own order (rows padded to x4) and the contraction reads the dense coefficient copy d_cres (shared with k_sweep_res's dense mode;
-// res_refresh_coeff keeps it current after set_mo).
+// cres_upload makes it and keeps it current after set_mo).  Returns 0 and leaves r8.ok = false when the system is outside the kernel's
+// scope, an error code (h->err set) when the device refuses a copy, an allocation or the LDS attribute.
 static int r8_setup(pqa_handle* h) {
-  h->r8_ready = true;
-  h->r8_ok = false;
-  if (h->r8_mode == 0) return 0;
+  h->r8.ok = false;
+  if (h->r8.mode == 0) return 0;
   if (!h->has_slater || h->ndet != 1 || h->has_j3 || h->cplx || h->twist || h->S.pbc || h->big) return 0;
   if (h->nup > 32 || h->ndn > 32 || h->nmo[0] > 32 || h->nmo[1] > 32 || h->N > 64 || h->N < 1 || h->natom > 64) return 0;
-  int lmax = 0;
-  for (int l : h->shell_l) lmax = std::max(lmax, l);
-  if (lmax > 3) return 0;
+  if (h->lmax > 3) return 0;
   for (int s = 0; s < 2; ++s)
     if ((s ? h->ndn : h->nup) > 0 && (h->nt[s] < 1 || h->nt[s] > 2)) return 0;
-  // deduplicated primitives (as res_setup) and the shells' atoms
+  // deduplicated primitives and the shells' atoms
   std::vector<double> pe_u, pc_u;
-  std::vector<int> q0_u((size_t)h->nshell, 0), sat((size_t)h->nshell, 0);
-  {
-    std::vector<double> pe((size_t)h->S.nprim), pc((size_t)h->S.nprim);
-    std::vector<int> po((size_t)h->nshell + 1);
-    HIPCHK(hipMemcpy(pe.data(), h->S.prim_exp, pe.size() * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(pc.data(), h->S.prim_coef, pc.size() * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(po.data(), h->S.shell_prim_off, po.size() * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(sat.data(), h->S.shell_atom, sat.size() * sizeof(int), hipMemcpyDeviceToHost));
-    for (int sh = 0; sh < h->nshell; ++sh) {
-      const int n = po[sh + 1] - po[sh];
-      int found = -1;
-      for (int prev = 0; prev < sh && found < 0; ++prev)
-        if (po[prev + 1] - po[prev] == n && std::equal(pe.begin() + po[sh], pe.begin() + po[sh + 1], pe.begin() + po[prev]) &&
-            std::equal(pc.begin() + po[sh], pc.begin() + po[sh + 1], pc.begin() + po[prev])) found = q0_u[prev];
-      if (found < 0) { found = (int)pe_u.size(); pe_u.insert(pe_u.end(), pe.begin() + po[sh], pe.begin() + po[sh + 1]); pc_u.insert(pc_u.end(), pc.begin() + po[sh], pc.begin() + po[sh + 1]); }
-      q0_u[sh] = found;
-    }
-  }
+  std::vector<int> q0_u, sat((size_t)h->nshell, 0);
+  TRY(unique_primitives(h, pe_u, pc_u, q0_u));
+  HIPCHK(hipMemcpy(sat.data(), h->S.shell_atom, sat.size() * sizeof(int), hipMemcpyDeviceToHost));
   struct Item { int l, np, q0, cost; std::vector<int> shells; };
   std::vector<Item> items;
   {
@@ -58,7 +45,7 @@ static int r8_setup(pqa_handle* h) {
   if (nitem == 0) return 0;
   double used = 0.0;
   for (const Item& it : items) used += (double)it.shells.size();
-  h->r8_util = used / (8.0 * nitem);
+  h->r8.util = used / (8.0 * nitem);
   std::vector<int> order((size_t)nitem);
   for (int k = 0; k < nitem; ++k) order[k] = k;
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return items[a].cost > items[b].cost; });
@@ -92,7 +79,7 @@ static int r8_setup(pqa_handle* h) {
   }
   RT.wave_off[4] = pos;
   RT.nitem = nitem;
-  const int rows4 = (h->nao + 3) & ~3;
+  const int rows4 = res_rows4(h);
   RT.kt = rows4;
   RT.cstride = 8 * rows4;
   while (RT.cstride % 32 != 16) RT.cstride += 8;  // planes c, c + 1 start 128 B apart mod 256: the two halves of an A operand on different banks
@@ -106,18 +93,11 @@ static int r8_setup(pqa_handle* h) {
   RT.jstage = (int)part_rn;
   RT.region = (int)std::max((size_t)5 * RT.cstride, part_rn + (size_t)PQA_R8_NW * 12 * 33);
   RT.nprim_u = (int)pe_u.size();
-  h->r8_lds = (size_t)RT.region * sizeof(double) + r8_lds_fixed(RT.nprim_u, h->natom, h->na, nitem);
-  h->r8_lds = (h->r8_lds + 15) & ~(size_t)15;
-  if (h->r8_lds > 80 * 1024) return 0;  // two blocks per CU
-  // dense coefficient copy
-  h->res_rows4 = rows4;
-  for (int s = 0; s < 2; ++s) {
-    if (h->nmo[s] == 0 || h->d_cres[s]) continue;
-    std::vector<double> mo((size_t)h->nao * h->nmo[s]);
-    HIPCHK(hipMemcpy(mo.data(), h->d_mo[s], mo.size() * sizeof(double), hipMemcpyDeviceToHost));
-    TRY(upload_table<double>(h, nullptr, (size_t)res_rows_alloc(rows4) * 16 * h->nt[s], &h->d_cres[s]));
-    TRY(res_refresh_coeff(h, s, mo.data()));
-  }
+  h->r8.lds = (size_t)RT.region * sizeof(double) + r8_lds_fixed(RT.nprim_u, h->natom, h->na, nitem);
+  h->r8.lds = (h->r8.lds + 15) & ~(size_t)15;
+  if (h->r8.lds > 80 * 1024) return 0;  // two blocks per CU
+  for (int s = 0; s < 2; ++s)
+    if (!h->d_cres[s]) TRY(cres_upload(h, s, nullptr));  // dense coefficient copy
   int* tmp_i = nullptr;
   TRY(upload_table(h, hdr.data(), hdr.size(), &tmp_i)); RT.item_hdr = tmp_i;
   TRY(upload_table(h, lane.data(), lane.size(), &tmp_i)); RT.item_lane = tmp_i;
@@ -125,15 +105,13 @@ static int r8_setup(pqa_handle* h) {
   TRY(upload_table(h, ixyz.data(), ixyz.size(), &tmp_d)); RT.item_xyz = tmp_d;
   TRY(upload_table(h, pe_u.data(), pe_u.size(), &tmp_d)); RT.prim_exp_u = tmp_d;
   TRY(upload_table(h, pc_u.data(), pc_u.size(), &tmp_d)); RT.prim_coef_u = tmp_d;
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_r8<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_r8<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_r8<false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_sweep_r8<true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+  for (const auto& lm : r8_kernels)
+    for (R8Kernel k : lm) HIPCHK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
   if (getenv("PQA_RES_DEBUG")) {
-    fprintf(stderr, "[pqa_res8] %d items (slot use %.2f), tile rows %d, plane stride %d, LDS %zu B, wave loads %ld %ld %ld %ld\n", nitem, h->r8_util,
-            RT.kt, RT.cstride, h->r8_lds, load[0], load[1], load[2], load[3]);
+    fprintf(stderr, "[pqa_res8] %d items (slot use %.2f), tile rows %d, plane stride %d, LDS %zu B, wave loads %ld %ld %ld %ld\n", nitem, h->r8.util,
+            RT.kt, RT.cstride, h->r8.lds, load[0], load[1], load[2], load[3]);
     int nb = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_sweep_r8<false, 2>, PQA_R8_NT, h->r8_lds);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)r8_kernels[0][0], PQA_R8_NT, h->r8.lds);
     fprintf(stderr, "[pqa_res8] resident blocks per CU (k_sweep_r8<false, 2>): %d\n", nb);
     if (atoi(getenv("PQA_RES_DEBUG")) > 1)
       for (int w = 0; w < 4; ++w)
@@ -141,44 +119,31 @@ static int r8_setup(pqa_handle* h) {
   }
   if (const char* a = getenv("PQA_R8_STAGGER")) RT.stagger = atoi(a);
   if (const char* a = getenv("PQA_R8_ABL")) RT.abl = atoi(a);  // (only timing builds read it)
-  h->r8_tab = RT;
-  h->res_lmax = lmax;
-  h->r8_ok = true;
+  h->r8.tab = RT;
+  h->r8.ok = true;
   return 0;
 }
 
-bool r8_eligible(pqa_handle* h) {
-  if (h->res_mode == 0) return false;  // PQA_RES=0: the launch-per-move sweep
-  if (!h->r8_ready) {
-    if (r8_setup(h) != 0) { h->r8_ok = false; h->err.clear(); }
-  }
-  if (!h->r8_ok) return false;
-  if (h->r8_mode > 0) return true;
-  return h->r8_util >= 0.5 && std::max(h->nup, h->ndn) >= 16;
+int r8_plan(pqa_handle* h, bool* use) {
+  *use = false;
+  if (h->res.mode == 0) return 0;  // PQA_RES=0: the launch-per-move sweep
+  if (!h->r8.ready) { TRY(r8_setup(h)); h->r8.ready = true; }  // (a setup that failed is tried, and fails, again)
+  *use = h->r8.ok && (h->r8.mode > 0 || (h->r8.util >= 0.5 && std::max(h->nup, h->ndn) >= 16));
+  return 0;
 }
 
 int sweep_r8(pqa_handle* h, const MoveBuf& mb) {
-  if (!mb.gauss || !mb.unif) FAIL("resident sweep: the random-number tapes are missing");
+  hipEvent_t e1 = nullptr;
+  TRY(sweep_launch_begin(h, mb, &e1));
   const long W = h->W;
   const LwState L = lw_state(h);
   ChunkTab Tc = h->tab[0];
   Tc.cpad[0] = h->d_cres[0]; Tc.cpad[1] = h->d_cres[1];
   const dim3 grid((unsigned)((W + PQA_R8_NW - 1) / PQA_R8_NW)), block(PQA_R8_NT);
-  h->r8_tab.xaos = h->r8_xaos_next ? h->js.x : nullptr;  // (pqa_vmc_sweeps: an energy evaluation with ECP passes follows)
-  h->jsx_current = h->r8_xaos_next;
-  h->r8_xaos_next = false;
-  hipEvent_t e1 = nullptr;
-  if (h->profile) {  // every launch is bracketed (one launch per sweep)
-    hipEvent_t e0 = nullptr;
-    TRY(prof_acquire(h, h->prof_orb, e0, e1));
-    HIPCHK(hipEventRecord(e0, h->stream));
-    h->prof_orb.launches += 1;
-    h->prof_pc += (double)W * h->N * 5;
-  }
-#define PQA_R8_LAUNCH(D, LM) hipLaunchKernelGGL((k_sweep_r8<D, LM>), grid, block, h->r8_lds, h->stream, h->S, L, mb, Tc, h->r8_tab, (int)h->has_jastrow, W, 0L, W)
-  if (mb.dmc) { if (h->res_lmax <= 2) PQA_R8_LAUNCH(true, 2); else PQA_R8_LAUNCH(true, 3); }
-  else { if (h->res_lmax <= 2) PQA_R8_LAUNCH(false, 2); else PQA_R8_LAUNCH(false, 3); }
-#undef PQA_R8_LAUNCH
+  h->r8.tab.xaos = h->r8.xaos_next ? h->js.x : nullptr;  // (pqa_vmc_sweeps: an energy evaluation with ECP passes follows)
+  h->r8.jsx_current = h->r8.xaos_next;
+  h->r8.xaos_next = false;
+  hipLaunchKernelGGL(r8_kernels[h->lmax <= 2 ? 0 : 1][mb.dmc ? 1 : 0], grid, block, h->r8.lds, h->stream, h->S, L, mb, Tc, h->r8.tab, (int)h->has_jastrow, W, 0L, W);
   if (e1) HIPCHK(hipEventRecord(e1, h->stream));
   return check_launch(h, "k_sweep_r8");
 }

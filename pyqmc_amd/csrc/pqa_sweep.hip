@@ -88,13 +88,13 @@ int lw_setup(pqa_handle* h, bool lw, LwCtx& c) {
   c.Gm = 4;
   if ((long)4 * W < 1664L * 64) c.Gm = 8;
   if (c.Gm == 8 && (long)8 * W < 2048L * 64) c.Gm = 16;
-  if (h->lw_gm > 0) c.Gm = std::min(h->lw_gm, 16);
+  if (h->lw.gm > 0) c.Gm = std::min(h->lw.gm, 16);
   c.nmax = std::max(h->nup, h->ndn);
   // block size of the delayed Sherman-Morrison update: 4 from 16 electrons per spin (8 flushes at 32), 5 from 24 (7 flushes at 32:
   // 35.60 -> 35.32 ms per step of the 64-electron benchmark; 6 is slower again — the per-move commit touches KB rows)
   // small shards (every launch a latency chain, one block row per thread group): 8 — fewer flush launches and split step launches
   // ((H2O)8 at 4096 walkers: 4.08 ms per step with 5, 3.97 with 8, 3.94 with 11, 4.01 with 16; 8192: 5.97 / 5.80 / 5.90 / 6.00)
-  const int kb = h->lw_kb < 0 ? (c.nmax >= 24 ? (W <= 8192 ? 8 : 5) : (c.nmax >= 16 ? 4 : 0)) : h->lw_kb;
+  const int kb = h->lw.kb < 0 ? (c.nmax >= 24 ? (W <= 8192 ? 8 : 5) : (c.nmax >= 16 ? 4 : 0)) : h->lw.kb;
   c.KB = (kb > 0) ? std::min(kb, std::max(c.nmax, 1)) : std::max(c.nmax, 1);  // KB = n: plain per-move update
   if (!lw) TRY(sync_aos(h));
   if (lw) {
@@ -112,51 +112,66 @@ int lw_setup(pqa_handle* h, bool lw, LwCtx& c) {
 int draws_ahead(pqa_handle* h, uint64_t seed, uint32_t next_step) {
   const long W = h->W;
   const size_t NW = (size_t)h->N * W;
-  if (!h->draw_stream) {
-    TRY(new_stream(h, &h->draw_stream));
-    for (hipEvent_t& e : h->draw_ev) TRY(new_event(h, &e, hipEventDisableTiming));
+  if (!h->draw.stream) {
+    TRY(new_stream(h, &h->draw.stream));
+    for (hipEvent_t& e : h->draw.ev) TRY(new_event(h, &e, hipEventDisableTiming));
   }
-  DevBuf& bg = (next_step & 1) ? h->b_gauss_b : h->b_gauss;
-  DevBuf& bu = (next_step & 1) ? h->b_unif_b : h->b_unif;
+  DevBuf& bg = (next_step & 1) ? h->draw.b_gauss_b : h->b_gauss;
+  DevBuf& bu = (next_step & 1) ? h->draw.b_unif_b : h->b_unif;
   TRY(ensure(h, bg, NW * 3 * sizeof(double)));
   TRY(ensure(h, bu, NW * sizeof(double)));
-  HIPCHK(hipEventRecord(h->draw_ev[0], h->stream));
-  HIPCHK(hipStreamWaitEvent(h->draw_stream, h->draw_ev[0], 0));
-  hipLaunchKernelGGL((k_tile_draws<>), dim3((unsigned)((NW + 255) / 256)), dim3(256), 0, h->draw_stream, seed, next_step, h->N, W, (double*)bg.p, (double*)bu.p);
-  HIPCHK(hipEventRecord(h->draw_ev[1], h->draw_stream));
-  h->draw_ahead_valid = true; h->draw_ahead_step = next_step; h->draw_ahead_seed = seed; h->draw_ahead_W = W;
+  HIPCHK(hipEventRecord(h->draw.ev[0], h->stream));
+  HIPCHK(hipStreamWaitEvent(h->draw.stream, h->draw.ev[0], 0));
+  hipLaunchKernelGGL((k_tile_draws<>), dim3((unsigned)((NW + 255) / 256)), dim3(256), 0, h->draw.stream, seed, next_step, h->N, W, (double*)bg.p, (double*)bu.p);
+  HIPCHK(hipEventRecord(h->draw.ev[1], h->draw.stream));
+  h->draw.ahead_valid = true; h->draw.ahead_step = next_step; h->draw.ahead_seed = seed; h->draw.ahead_W = W;
+  return 0;
+}
+
+// Which kernels a sweep of W walkers runs on this handle.  Single-determinant handles (lw_eligible): the resident sweeps where the system
+// is in their scope (one launch per sweep, state on chip; they read both tapes, so a call that brings one tape of the two takes the
+// launches) — k_sweep_r8 (second generation, open-boundary real handles: pqa_res8.hpp) ahead of k_sweep_res (pqa_res.hpp) — else the
+// launch-per-move sweep.  Every other handle: the wave-per-walker kernels, in one launch for small shards (pqa_ww.hpp).  A resident
+// sweep's setup runs when the route first asks for it: res_setup never runs on a handle whose sweeps all go to k_sweep_r8.
+static int sweep_route(pqa_handle* h, long W, bool tapes_ok, SweepRoute* route) {
+  if (!lw_eligible(h)) { *route = ww_eligible(h, W) ? SweepRoute::ww : SweepRoute::ww_launches; return 0; }
+  *route = SweepRoute::lw;
+  if (!tapes_ok) return 0;
+  bool use = false;
+  TRY(r8_plan(h, &use));
+  if (use) { *route = SweepRoute::r8; return 0; }
+  TRY(res_plan(h, W, &use));
+  if (use) *route = SweepRoute::res;
   return 0;
 }
 
 static bool N_ok(const pqa_handle* h) { return h->N <= 64 && h->natom <= 64 && std::max(h->nup, h->ndn) <= 64; }
-static int sweep_electrons_fused(pqa_handle* h, const MoveBuf& mb_in, const LwCtx& lc) {
+// The lane-per-walker routes.  The sweep's draws first, if the call brought no tapes and the route reads them from memory.
+static int sweep_electrons_fused(pqa_handle* h, const MoveBuf& mb_in, const LwCtx& lc, SweepRoute route) {
   const long W = h->W;
   MoveBuf mb = mb_in;
-  // the resident sweep (pqa_res.hpp: one launch per sweep, state on chip) where the system is in its scope; it reads both tapes
-  const bool tapes_ok = (mb.gauss != nullptr) == (mb.unif != nullptr);
-  const bool r8 = tapes_ok && r8_eligible(h);  // (second generation, open-boundary real handles: pqa_res8.hpp)
-  const bool res = r8 || (tapes_ok && res_eligible(h, W));
+  const bool res = route != SweepRoute::lw;
   constexpr long draws_max = 16384;  // walker counts up to which a fused sweep draws its random numbers ahead (k_tile_draws)
   if (!mb.gauss && !mb.unif && (res || W <= draws_max)) {
     // small shards: the sweep's normals and uniforms drawn ahead by one launch from the same Philox streams (k_tile_draws) — in
     // k_step_lw the lead group's Box-Muller pairs are ~600 dependent instructions of every move's chain with one wave per SIMD
     const size_t NW = (size_t)h->N * W;
     // two tape sets, step s in set s & 1: pqa_vmc_sweeps draws step s + 1 on a side stream while step s's energy pass runs (draws_ahead)
-    DevBuf& bg = (mb.step & 1) ? h->b_gauss_b : h->b_gauss;
-    DevBuf& bu = (mb.step & 1) ? h->b_unif_b : h->b_unif;
-    if (h->draw_ahead_valid && h->draw_ahead_step == mb.step && h->draw_ahead_seed == mb.seed && h->draw_ahead_W == W) {
-      HIPCHK(hipStreamWaitEvent(h->stream, h->draw_ev[1], 0));
+    DevBuf& bg = (mb.step & 1) ? h->draw.b_gauss_b : h->b_gauss;
+    DevBuf& bu = (mb.step & 1) ? h->draw.b_unif_b : h->b_unif;
+    if (h->draw.ahead_valid && h->draw.ahead_step == mb.step && h->draw.ahead_seed == mb.seed && h->draw.ahead_W == W) {
+      HIPCHK(hipStreamWaitEvent(h->stream, h->draw.ev[1], 0));
     } else {
       TRY(ensure(h, bg, NW * 3 * sizeof(double)));
       TRY(ensure(h, bu, NW * sizeof(double)));
       hipLaunchKernelGGL((k_tile_draws<>), dim3((unsigned)((NW + 255) / 256)), dim3(256), 0, h->stream, mb.seed, mb.step, h->N, W, (double*)bg.p, (double*)bu.p);
     }
-    h->draw_ahead_valid = false;
-    h->draws_on_device = true;
+    h->draw.ahead_valid = false;
+    h->draw.on_device = true;
     mb.gauss = (const double*)bg.p; mb.unif = (const double*)bu.p;
   }
-  if (r8) return sweep_r8(h, mb);
-  if (res) return sweep_res(h, mb);
+  if (route == SweepRoute::r8) return sweep_r8(h, mb);
+  if (route == SweepRoute::res) return sweep_res(h, mb);
   const int N = h->N, KB = lc.KB, nmax = lc.nmax;
   const LwState L = lw_state(h);
   const int cfi = h->cplx ? 2 : 1, rowlen = cfi * nmax;  // doubles per inverse row
@@ -221,12 +236,9 @@ static int sweep_electrons_fused(pqa_handle* h, const MoveBuf& mb_in, const LwCt
   return 0;
 }
 
-// One proposal per electron, in index order, on the SoA state (lw: two launches per move, above) or the AoS state with the
-// wave-per-walker kernels (multi-determinant, three-body, large complex determinants); mb.dmc selects the DMC variant.
-int sweep_electrons(pqa_handle* h, const MoveBuf& mb, bool lw, const LwCtx& lc) {
-  if (lw) return sweep_electrons_fused(h, mb, lc);
+// the wave-per-walker kernels on the AoS state, launch by launch: k_propose -> orbitals at the proposals -> k_accept per move
+static int sweep_ww_launches(pqa_handle* h, const MoveBuf& mb) {
   const long W = h->W;
-  if (ww_eligible(h, W)) return sweep_ww(h, mb);  // small shards: the whole sweep of a walker in one launch, one wave per walker (pqa_ww.hpp)
   const size_t lds_acc = std::max(lds_sm(h), lds_det(h, 5));
   for (int e = 0; e < h->N; ++e) {
     const int s = e >= h->nup;
@@ -246,6 +258,23 @@ int sweep_electrons(pqa_handle* h, const MoveBuf& mb, bool lw, const LwCtx& lc) 
                        (int)h->has_jastrow, mo, W);
   }
   return 0;
+}
+
+// One proposal per electron, in index order, on the SoA state (the lane-per-walker routes above) or the AoS state with the
+// wave-per-walker kernels (multi-determinant, three-body, large complex determinants); mb.dmc selects the DMC variant.
+int sweep_electrons(pqa_handle* h, const MoveBuf& mb, const LwCtx& lc) {
+  SweepRoute route;
+  TRY(sweep_route(h, h->W, (mb.gauss != nullptr) == (mb.unif != nullptr), &route));
+  if (h->route.debug && route != h->route.reported) {  // PQA_RES_DEBUG: the kernel a sweep runs, whenever it is not the last sweep's
+    static const char* const names[] = {"k_sweep_r8", "k_sweep_res", "k_step_lw", "k_sweep_ww", "k_propose/k_accept"};
+    fprintf(stderr, "[pqa] sweep route: %s\n", names[(int)route]);
+    h->route.reported = route;
+  }
+  switch (route) {
+    case SweepRoute::ww: return sweep_ww(h, mb);  // small shards: the whole sweep of a walker in one launch, one wave per walker (pqa_ww.hpp)
+    case SweepRoute::ww_launches: return sweep_ww_launches(h, mb);
+    default: return sweep_electrons_fused(h, mb, lc, route);
+  }
 }
 
 extern "C" int pqa_vmc_sweeps(pqa_handle_t* h, double tstep, int nsteps, const double* gauss, const double* unif, double threshold,
@@ -283,7 +312,7 @@ extern "C" int pqa_vmc_sweeps(pqa_handle_t* h, double tstep, int nsteps, const d
   const bool lw = lw_eligible(h);
   LwCtx lc;
   TRY(lw_setup(h, lw, lc));
-  h->draw_ahead_valid = false;
+  h->draw.ahead_valid = false;
   for (int step = 0; step < nsteps; ++step) {
     MoveBuf mb{};
     mb.newpos = (double*)h->b_newpos.p; mb.aux = (double*)h->b_aux.p; mb.accept = (uint8_t*)h->b_accept.p;
@@ -298,12 +327,12 @@ extern "C" int pqa_vmc_sweeps(pqa_handle_t* h, double tstep, int nsteps, const d
       mb.unif = (const double*)h->b_unif.p;
     }
     if (accept_rec) mb.accept_rec = (uint8_t*)h->b_accrec.p;
-    h->jsx_current = false;
-    h->r8_xaos_next = energy_mean != nullptr && h->necp > 0;  // (consumed by sweep_r8 only)
-    h->draws_on_device = false;
-    TRY(sweep_electrons(h, mb, lw, lc));
-    h->r8_xaos_next = false;
-    if (h->draws_on_device && energy_mean && step + 1 < nsteps && W >= 16384) TRY(draws_ahead(h, seed, (uint32_t)(step + 1)));
+    h->r8.jsx_current = false;
+    h->r8.xaos_next = energy_mean != nullptr && h->necp > 0;  // (consumed by sweep_r8 only)
+    h->draw.on_device = false;
+    TRY(sweep_electrons(h, mb, lc));
+    h->r8.xaos_next = false;
+    if (h->draw.on_device && energy_mean && step + 1 < nsteps && W >= 16384) TRY(draws_ahead(h, seed, (uint32_t)(step + 1)));
     // small shards: the accepted-move count, the energy rows and their means in one launch at the end of the step (three launches of ~5 us
     // otherwise — 2 % of the 50-determinant molecule's step at 2 048 walkers)
     const bool finish1 = energy_mean && W <= 16384;

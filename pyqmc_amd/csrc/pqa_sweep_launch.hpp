@@ -10,7 +10,7 @@
 static constexpr long step_pre_max = 8192;
 // what k_step_pre's scope asks of the system whatever its group count (pqa_lw.hpp)
 static inline bool step_pre_system_ok(const pqa_handle* h, int rowlen) {
-  return !h->cplx && h->step_pre && h->S.occ_ident[0] && h->S.occ_ident[1] && h->S.nb <= PQA_JAS_NF && h->S.na <= PQA_JAS_NF && rowlen <= 64;
+  return !h->cplx && h->lw.step_pre && h->S.occ_ident[0] && h->S.occ_ident[1] && h->S.nb <= PQA_JAS_NF && h->S.na <= PQA_JAS_NF && rowlen <= 64;
 }
 template <bool PBC, bool CX>
 static void launch_step_lw(pqa_handle* h, const LwState& L, const MoveBuf& mb, const StepArgs& a, int rowlen) {

@@ -17,22 +17,17 @@ static size_t ww_lds(const pqa_handle* h) {
 }
 
 bool ww_eligible(pqa_handle* h, long W) {
-  if (h->ww_mode == 0 || h->cplx || h->S.pbc) return false;
-  if (ww_lds(h) > 64 * 1024) return false;
-  for (int l : h->shell_l)
-    if (l > 5) return false;
-  return h->ww_mode > 0 || W <= h->ww_max;
+  if (h->ww.mode == 0 || h->cplx || h->S.pbc) return false;
+  if (ww_lds(h) > 64 * 1024 || h->lmax > 5) return false;
+  return h->ww.mode > 0 || W <= h->ww.max;
 }
 
 int sweep_ww(pqa_handle* h, const MoveBuf& mb) {
+  using WwKernel = void (*)(SysDev, SlaterState, JastrowState, MoveBuf, int, int, int, int, long);
+  static const WwKernel kernels[3] = {k_sweep_ww<2>, k_sweep_ww<3>, k_sweep_ww<5>};  // LMAX 2 | 3 | 5
   const long W = h->W;
-  int lmax = 0;
-  for (int l : h->shell_l) lmax = std::max(lmax, l);
   const dim3 grid((unsigned)W), block(64);
-  const size_t lds = ww_lds(h);
-  const int xoff = (int)ww_xoff(h);
-#define PQA_WW_LAUNCH(LM) hipLaunchKernelGGL((k_sweep_ww<LM>), grid, block, lds, h->stream, h->S, h->st, h->js, mb, (int)h->has_slater, (int)h->has_jastrow, xoff, (int)ww_cstage(h), W)
-  if (lmax <= 2) PQA_WW_LAUNCH(2); else if (lmax <= 3) PQA_WW_LAUNCH(3); else PQA_WW_LAUNCH(5);
-#undef PQA_WW_LAUNCH
+  hipLaunchKernelGGL(kernels[h->lmax <= 2 ? 0 : (h->lmax <= 3 ? 1 : 2)], grid, block, ww_lds(h), h->stream, h->S, h->st, h->js, mb, (int)h->has_slater,
+                     (int)h->has_jastrow, (int)ww_xoff(h), (int)ww_cstage(h), W);
   return check_launch(h, "k_sweep_ww");
 }

@@ -17,6 +17,7 @@ import ast
 import copy
 import functools
 import os
+import re
 
 import numpy as np
 
@@ -36,6 +37,10 @@ CASES = {
     "general-1e-5": (systems.water_general, 1e-5, 13, 100, (5, 50)),  # 5 + 5 all-electron, 24 AOs
     "cluster-1e-5": (systems.water_cluster, 1e-5, 13, 12, (3,)),      # n = 32: two orbital tiles; one full + one partly filled r8 block
 }
+# the switches that pin each of the three single-determinant sweeps (read when a handle is created)
+PATHS = {"r8": {"PQA_RES": "1", "PQA_R8": "1"},      # k_sweep_r8
+         "res16": {"PQA_RES": "1", "PQA_R8": "0"},   # k_sweep_res
+         "launches": {"PQA_RES": "0"}}               # k_orb + k_step_lw / k_step_pre per move
 # max cond(D) over the final walkers, measured with the oracle (asserted within a decade by test_conditioning_cpu.py)
 COND = {"water-1e-5": 3e6, "water-1e-7": 3e8, "general-1e-5": 2e7, "cluster-1e-5": 9e6}
 
@@ -127,6 +132,13 @@ def permuted_mf(mf, seed):
     r = np.random.default_rng(seed)
     mo = np.array(mf.mo_coeff)
     return systems.MeanField(np.stack([mo[s][:, r.permutation(mo.shape[2])] for s in (0, 1)]), np.array(mf.mo_occ))
+
+
+def reported_routes(stderr):
+    """The kernel names of the ``[pqa] sweep route: <kernel>`` lines in a captured stderr, in order.  Under PQA_RES_DEBUG a handle prints
+    one whenever a sweep takes another route than the handle's last sweep did (the first sweep always): k_sweep_r8, k_sweep_res, k_step_lw
+    (launch per move: k_step_lw / k_step_pre), k_sweep_ww, or k_propose/k_accept (wave-per-walker launches)."""
+    return re.findall(r"^\[pqa\] sweep route: (.+)$", stderr, flags=re.M)
 
 
 def tapes(mol, W, nsteps, forced=(), seed=3):

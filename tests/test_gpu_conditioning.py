@@ -17,7 +17,7 @@ factors (k_sweep_ww and the k_propose / k_accept launches; every unique determin
 host tapes (launch-per-move sweep and k_sweep_res<DMC, PBC>); their oracle side is the fixture g51 or runs live.  Largest device / oracle ratio: 4.5 through k_sweep_res<PBC[, CX]>, 6.3
 through the periodic launch-per-move sweep, 4.5 through the wave-per-walker launches, 6.3 through k_sweep_ww, 3.9 through k_propose /
 k_accept, 4.4 in the periodic DMC chains (2.5 through k_sweep_res<DMC, PBC>).  Which sweep ran is asserted from the profiler's bracket
-counts (_sweep_launches) or the resident sweep's set-up report.
+counts (_sweep_launches) or, for the resident sweeps, the route every handle reports under PQA_RES_DEBUG (conditioning.reported_routes).
 """
 
 import json
@@ -34,9 +34,7 @@ pytestmark = pytest.mark.gpu
 
 MARGIN = 8.0  # device error <= 8 x the oracle's own (test_conditioning_cpu.py::test_summation_order_spread)
 NQ = 4  # walkers of the 16 384 that the oracle replays in (c)
-PATHS = {"r8": {"PQA_RES": "1", "PQA_R8": "1"},      # k_sweep_r8
-         "res16": {"PQA_RES": "1", "PQA_R8": "0"},   # k_sweep_res
-         "launches": {"PQA_RES": "0"}}               # k_orb + k_step_lw / k_step_pre per move
+PATHS = cond.PATHS
 _report = {}
 
 
@@ -65,12 +63,19 @@ def _handle(mol, mf, path, monkeypatch, capfd=None):
     return wf, wf.fused_device()
 
 
-def _assert_r8_ran(capfd):
-    """PQA_RES_DEBUG makes r8_setup report its tile once it has accepted the system: the 'r8' cases did run k_sweep_r8 and not the sweep
-    the handle falls back to."""
+def _assert_only_route(capfd, setup_tag, kernel):
+    """PQA_RES_DEBUG makes a resident sweep's setup report its plan once it has accepted the system (``setup_tag``), and every handle
+    report the kernel a sweep runs whenever it is not the one its last sweep ran: ``kernel`` was reported and no other."""
     out, err = capfd.readouterr()
     print(out, end="")
-    assert "[pqa_res8]" in err
+    assert setup_tag in err
+    routes = cond.reported_routes(err)
+    assert routes and set(routes) == {kernel}, routes
+
+
+def _assert_r8_ran(capfd):
+    """The 'r8' cases did run k_sweep_r8 and not a sweep the handle falls back to."""
+    _assert_only_route(capfd, "[pqa_res8]", "k_sweep_r8")
 
 
 def _device_errors(mol, mf, wf, dev):
@@ -293,10 +298,8 @@ def _pbc_handle(c, path, monkeypatch):
 
 
 def _assert_res_ran(capfd):
-    """PQA_RES_DEBUG makes res_setup report its tables once it has accepted the system: with PQA_RES=1 the sweep then is k_sweep_res."""
-    out, err = capfd.readouterr()
-    print(out, end="")
-    assert "[pqa_res]" in err
+    """With PQA_RES=1 on a cell that res_setup accepts every sweep is k_sweep_res."""
+    _assert_only_route(capfd, "[pqa_res]", "k_sweep_res")
 
 
 def _sweep_launches(dev):
