@@ -477,6 +477,20 @@ int pqa_tbdm_sweep(pqa_handle_t* wf, pqa_handle_t* ev, int k, int spin_a, int sp
 int pqa_obdm_sweeps(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
                     uint64_t seed, int mean, int first, int64_t walker_chunk, double* ratio, int32_t* assign_out, double* value_mean,
                     double* norm_mean);
+/* The mean mode of pqa_obdm_sweeps with walker weights (the mixed estimator of DMC): weights (W) host, finite and >= 0 with a
+   positive sum, otherwise refused;
+     value_mean = sum_s sum_w w_w b_s[w] (x) t_s[w] / (nsweeps sum_w w_w),   norm_mean likewise.
+   One body with pqa_obdm_sweeps: the weight multiplies the B operand of the matrix-core product as it is loaded and the norm term as
+   it is added, sum_w w_w comes from one fixed-order tree, and slices, chunk rounding and the slice-order reduction are those of the
+   unweighted mean.  So one chunk or several, and two calls, give the same bits, and unit weights give the bits of
+   pqa_obdm_sweeps(mean = 1).  assign = NULL / assign_out as there; the ratios are not offered.  Same scope. */
+int pqa_obdm_sweeps_w(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
+                      uint64_t seed, int64_t walker_chunk, const double* weights, int32_t* assign_out, double* value_mean,
+                      double* norm_mean);
+/* pqa_dm_points for the listed electrons es (ne) of wf's resident walkers: their coordinates are gathered on the device and ev's
+   orbitals of the spin of the slot's walk (pqa_dm_walk comes first) are evaluated there into `slot`, rows (W, ne, norb) — the first
+   stage of pqa_obdm_sweeps, with its scope checks.  wf's state is not modified. */
+int pqa_dm_points_resident(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_t* es, int ne);
 /* Device bytes ev holds for pqa_obdm_sweeps: scratch = the mean mode's panels, partial tiles and sums plus a walker chunk's ratios;
    per_walker = the per-walker accumulators (value, norms), which the mean mode never allocates. */
 int pqa_obdm_bytes(pqa_handle_t* ev, int64_t* scratch, int64_t* per_walker);
@@ -484,6 +498,11 @@ int pqa_obdm_bytes(pqa_handle_t* ev, int64_t* scratch, int64_t* per_walker);
    norm_a, 2 norm_b (ncol = orbitals).  mean = 0: (nconf,ncol); mean != 0: (ncol,) averaged over the configurations on
    the device (the accumulators' avg(), obdm.py:195-197). */
 int pqa_dm_fetch(pqa_handle_t* h, int which, int ncol, double scale, int mean, double* out);
+/* The weighted walker mean of an accumulator times `scale`: out (ncol) = scale sum_n w_n acc[n][.] / sum_n w_n with `which` / ncol
+   as in pqa_dm_fetch and weights (nconf) host, finite and >= 0 with a positive sum.  A block sums a run of 64 consecutive columns
+   over a slice of configurations (k_wcol_means, pqa_estim.hpp), the slices are added in order: no atomics, two calls give the same
+   bits. */
+int pqa_dm_fetch_w(pqa_handle_t* h, int which, int ncol, double scale, const double* weights, double* out);
 /* C (P,Q) = A^T B for A (n,P), B (n,Q) on the fp64 matrix cores: the moment matrix dpidpj = dp^T diag(w f) dp of
    StochasticReconfiguration.avg (stochastic_reconfiguration.py:106-114). */
 int pqa_gram(pqa_handle_t* h, int64_t n, int P, int Q, const double* A, const double* B, double* C);
@@ -533,6 +552,10 @@ int pqa_symmetry(pqa_handle_t* h, int nop, const double* ops, const double* orig
    device in a fixed order (no atomics: two calls give the same bits).  Every handle kind; read-only on the resident state
    (coordinates are read in place from whichever layout holds them: no layout sync, no change to anything a sweep reads). */
 int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, const double* recip, int mean, double* sq, double* spinsq);
+/* pqa_sq(mean = 1) with walker weights: sq, spinsq (nqv) = sum_w w_w value[w][.] / sum_w w_w; weights (W) host, finite and >= 0
+   with a positive sum.  Every handle kind, read-only, reduced in a fixed order (no atomics: two calls give the same bits). */
+int pqa_sq_w(pqa_handle_t* h, int nqv, const double* q, const int* qn, const double* recip, const double* weights, double* sq,
+             double* spinsq);
 
 /* ---- slab (2D) Ewald energy ------------------------------------------------------------------------ */
 /* Ewald (pyqmc/observables/ewald2d.py; Yeh and Berkowitz, J. Chem. Phys. 111, 3155): Coulomb energy of a cell that is periodic along

@@ -131,6 +131,11 @@ _PROTOTYPES = {
     "pqa_tbdm_sweep": (C.c_int, [_H, _H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "pqa_obdm_sweeps": (C.c_int, [_H, _H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pqa_obdm_sweeps_w": (C.c_int, [_H, _H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "pqa_dm_points_resident": (C.c_int, [_H, _H, C.c_int, C.c_void_p, C.c_int]),
+    "pqa_dm_fetch_w": (C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
+    "pqa_sq_w": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pqa_obdm_bytes": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pqa_dm_fetch": (C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]),
     "pqa_gram": (C.c_int, [_H, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -212,3 +217,16 @@ def ptr(a):
 
 def f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def walker_weights(weights, W):
+    """``weights`` as the (W,) float64 array the weighted walker means take: finite, >= 0, with a positive sum (``ValueError``
+    otherwise, before anything reaches the device)."""
+    w = f64(weights)
+    if w.shape != (W,):
+        raise ValueError(f"weights ({W},) expected, got {w.shape}")
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError("weights must be finite and >= 0")
+    if not w.sum() > 0:
+        raise ValueError("the weights must have a positive sum")
+    return w

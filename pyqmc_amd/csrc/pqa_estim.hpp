@@ -5,6 +5,8 @@
 // bcoeff entries (k, pair)), and so are grad_e U, lap_e U and U(e -> q) - U(e).  jas_rows writes R[m * P + p] = grad_e B_p
 // (m = 0, 1, 2) and lap_e B_p (m = 3) for electron e, jas_diff_rows R[p] = B_p(e -> q) - B_p(e), and a caller contracts them with
 // whichever coefficient set it needs.
+//
+// Weighted walker means (pqa_obdm, pqa_sq): the weight sum k_wsum and the column reduction k_wcol_means / k_wcol_fold.
 #pragma once
 #include "pqa_internal.hpp"
 
@@ -181,8 +183,90 @@ __device__ __forceinline__ double block_sum256(double v, double* sh) {
   return r;
 }
 
+// Weighted walker means (the mixed estimators of DMC: sum_w w_w res_w / sum_w w_w).
+//
+// sum of the W weights: one block, a fixed-order tree (the order of pqa_sr's k_sr_wsum)
+template <int PQA_UNIT = 0>  // (a template so that only the units that launch it compile it)
+static __global__ __launch_bounds__(256) void k_wsum(const double* __restrict__ wts, long W, double* __restrict__ out) {
+  __shared__ double part[256];
+  double a = 0.0;
+  for (long w = threadIdx.x; w < W; w += 256) a += wts[w];
+  a = block_sum256(a, part);
+  if (threadIdx.x == 0) out[0] = a;
+}
+
+constexpr int kWcolCols = 64;    // columns per block of k_wcol_means: a wave reads 64 consecutive doubles of a row
+constexpr long kWcolRows = 256;  // least rows per slice
+constexpr long kWcolSlices = 256;  // most slices
+
+inline long wcol_slice_rows(long rows) { return std::max<long>(kWcolRows, (rows + kWcolSlices - 1) / kWcolSlices); }
+inline long wcol_slices(long rows) { const long rp = wcol_slice_rows(rows); return (rows + rp - 1) / rp; }
+inline long wcol_slices_max(long rows) { return rows <= kWcolRows * kWcolSlices ? wcol_slices(rows) : kWcolSlices; }  // most slices of <= rows rows
+
+// part[z][sl][c] = sum over the rows r of slice sl (rp rows each) of wts[r] in[z][r][c], for nz = gridDim.z row-major arrays
+// in[z] (rows, cols).  A block takes kWcolCols consecutive columns and one slice: wave v adds rows lo + v, lo + v + 4, ... (every
+// load of a wave is one contiguous 512-byte piece of a row), the four waves' sums are added in wave order.  No atomics; the order
+// depends on (rows, rp) alone.
+template <int PQA_UNIT = 0>  // (a template so that only the units that launch it compile it)
+static __global__ __launch_bounds__(256) void k_wcol_means(const double* __restrict__ in, const double* __restrict__ wts, long rows, long cols,
+                                                           long rp, long nsl, double* __restrict__ part) {
+  __shared__ double sh[4][kWcolCols];
+  const int lane = threadIdx.x & 63, v = threadIdx.x >> 6;
+  const long c = (long)blockIdx.x * kWcolCols + lane, sl = blockIdx.y, z = blockIdx.z;
+  const long lo = sl * rp, hi = (lo + rp < rows) ? lo + rp : rows;
+  const double* p = in + (size_t)z * rows * cols;
+  double s = 0.0;
+  if (c < cols) {
+#pragma unroll 4
+    for (long r = lo + v; r < hi; r += 4) s += wts[r] * p[(size_t)r * cols + c];
+  }
+  sh[v][lane] = s;
+  __syncthreads();
+  if (v == 0 && c < cols) part[((size_t)z * nsl + sl) * cols + c] = ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
+}
+
+// acc[z cols + c] = (first ? 0 : acc) + part[z][0][c] + part[z][1][c] + ... in slice order; last: times scale / wsum[0]
+template <int PQA_UNIT = 0>  // (a template so that only the units that launch it compile it)
+static __global__ __launch_bounds__(256) void k_wcol_fold(const double* __restrict__ part, long nsl, long cols, long nz, int first, int last,
+                                                          double scale, const double* __restrict__ wsum, double* __restrict__ acc) {
+  const long k = (long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= nz * cols) return;
+  const long z = k / cols, c = k - z * cols;
+  double s = first ? 0.0 : acc[k];
+  for (long sl = 0; sl < nsl; ++sl) s += part[((size_t)z * nsl + sl) * cols + c];
+  if (last) s = scale * s / wsum[0];
+  acc[k] = s;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // host
+
+// The walker weights of a weighted mean: W finite doubles >= 0 with a positive sum.
+inline int check_weights(pqa_handle* h, const char* fn, const double* weights, long W) {
+  if (!weights) FAIL(std::string(fn) + ": weights is NULL");
+  double s = 0.0;
+  for (long w = 0; w < W; ++w) {
+    if (!std::isfinite(weights[w]) || weights[w] < 0.0) FAIL(std::string(fn) + ": weights must be finite and >= 0");
+    s += weights[w];
+  }
+  if (!(s > 0.0) || !std::isfinite(s)) FAIL(std::string(fn) + ": the weights must have a positive sum");
+  return 0;
+}
+
+// Weighted column means of nz row-major arrays in[z] (rows, cols) on stream-ordered scratch: d_wts (rows) the weights of these
+// rows, part (nz, wcol_slices(rows), cols) scratch, acc (nz cols) the running sums over calls (first starts them; last: times
+// scale / wsum[0]).
+template <int PQA_UNIT = 0>  // (a template so that only the units that call it compile the kernels)
+inline int wcol_means_dev(pqa_handle* h, const double* in, const double* d_wts, long rows, long cols, int nz, int first, int last, double scale,
+                          const double* d_wsum, double* part, double* acc) {
+  const long rp = wcol_slice_rows(rows), nsl = wcol_slices(rows);
+  hipLaunchKernelGGL((k_wcol_means<PQA_UNIT>), dim3((unsigned)((cols + kWcolCols - 1) / kWcolCols), (unsigned)nsl, (unsigned)nz), dim3(256), 0, h->stream,
+                     in, d_wts, rows, cols, rp, nsl, part);
+  TRY(check_launch(h, "k_wcol_means"));
+  hipLaunchKernelGGL((k_wcol_fold<PQA_UNIT>), dim3((unsigned)(((long)nz * cols + 255) / 256)), dim3(256), 0, h->stream, (const double*)part, nsl, cols,
+                     (long)nz, first, last, scale, d_wsum, acc);
+  return check_launch(h, "k_wcol_fold");
+}
 
 // Per-walker scratch of an estimator is allocated for a walker chunk of at most this many bytes.
 constexpr size_t kChunkScratchBytes = size_t(256) << 20;

@@ -185,9 +185,11 @@ __global__ __launch_bounds__(64) void k_obdm_rt(SysDev S, SlaterState st, Jastro
 
 // Partial tiles of B^T T and partial column sums of Nn for the slices of a chunk: one wave per 16 x 16 tile (p0, q0) and slice of
 // kSlice walkers.  part [slice][P P + P]: the tile's entries, and from the waves of the q0 = 0 tiles the norm columns p0 .. p0 + 15
-// summed walker after walker.
+// summed walker after walker.  WT: walker r of the chunk carries the weight wts[r], applied to the B operand as it is loaded and to
+// the norm term as it is added (a weight of 1 leaves every bit as the unweighted instance has it).
+template <bool WT>
 __global__ __launch_bounds__(64) void k_obdm_mean(const double* __restrict__ B, const double* __restrict__ T, const double* __restrict__ Nn,
-                                                  long wc, int P, double* __restrict__ part) {
+                                                  const double* __restrict__ wts, long wc, int P, double* __restrict__ part) {
   const int lane = threadIdx.x, i16 = lane & 15, kq = lane >> 4;
   const int p0 = blockIdx.x * 16, q0 = blockIdx.y * 16;
   const long sl = blockIdx.z, n_lo = sl * kSlice, n_hi = (n_lo + kSlice < wc) ? n_lo + kSlice : wc;
@@ -196,7 +198,8 @@ __global__ __launch_bounds__(64) void k_obdm_mean(const double* __restrict__ B, 
   d4 acc = {0.0, 0.0, 0.0, 0.0};
   for (long r = n_lo; r < n_hi; r += 4) {
     const long rr = r + kq;
-    const double a = (pin && rr < n_hi) ? B[rr * P + p0 + i16] : 0.0;
+    double a = (pin && rr < n_hi) ? B[rr * P + p0 + i16] : 0.0;
+    if (WT) a *= rr < n_hi ? wts[rr] : 0.0;
     const double b = (qin && rr < n_hi) ? T[rr * P + q0 + i16] : 0.0;
     acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
   }
@@ -207,7 +210,7 @@ __global__ __launch_bounds__(64) void k_obdm_mean(const double* __restrict__ B, 
   }
   if (q0 == 0 && kq == 0 && pin) {
     double s = 0.0;
-    for (long r = n_lo; r < n_hi; ++r) s += Nn[r * P + p0 + i16];
+    for (long r = n_lo; r < n_hi; ++r) s += WT ? wts[r] * Nn[r * P + p0 + i16] : Nn[r * P + p0 + i16];
     out[(size_t)P * P + p0 + i16] = s;
   }
 }
@@ -221,53 +224,99 @@ __global__ __launch_bounds__(256) void k_obdm_reduce(const double* __restrict__ 
   sums[i] = s;
 }
 
-}  // namespace
+// out[i] = in[i] / (mult wsum[0]): the final scale of the weighted mean
+__global__ __launch_bounds__(256) void k_obdm_wscale(const double* __restrict__ in, long n, const double* __restrict__ wsum, double mult,
+                                                     double* __restrict__ out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = (1.0 / (mult * wsum[0])) * in[i];
+}
 
-extern "C" int pqa_obdm_sweeps(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
-                               uint64_t seed, int mean, int first, int64_t chunk, double* ratio, int32_t* assign_out, double* value_mean,
-                               double* norm_mean) {
+
+// Scope of the entries that read wf's resident walkers for the evaluator ev (pqa_obdm_sweeps, pqa_obdm_sweeps_w,
+// pqa_dm_points_resident): two real handles on one device, wf in the read-only scope with a state, the listed electrons distinct.
+// spins: bit 0 / 1 set when an up / down electron is listed.  Leaves wf's walker-major arrays current.
+int resident_scope(pqa_handle* h, pqa_handle* ev, int slot, const int32_t* es, int ne, const std::string& fn, int* spins_out) {
   if (!h) return -2;
-  if (!ev) FAIL("pqa_obdm_sweeps: the orbital evaluator's handle is NULL");
+  if (!ev) FAIL(fn + ": the orbital evaluator's handle is NULL");
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
-  if (h->W == 0) FAIL("pqa_obdm_sweeps: state not initialised (call recompute)");
-  TRY(readonly_scope(h, "pqa_obdm_sweeps"));
-  if (ev == h) FAIL("pqa_obdm_sweeps: the wave function and the orbital evaluator must be two handles");
-  if (ev->cplx || ev->twist) FAIL("pqa_obdm_sweeps: complex orbital evaluator (outside the fused scope: use the protocol route)");
-  if (ev->device != h->device) FAIL("pqa_obdm_sweeps: the two handles are on different devices (use the protocol route)");
-  if (slot < 0 || slot > 1) FAIL("pqa_obdm_sweeps: slot must be 0 or 1");
-  if (!es || ne < 1) FAIL("pqa_obdm_sweeps: no electron listed (use the protocol route)");
+  if (h->W == 0) FAIL(fn + ": state not initialised (call recompute)");
+  TRY(readonly_scope(h, fn.c_str()));
+  if (ev == h) FAIL(fn + ": the wave function and the orbital evaluator must be two handles");
+  if (ev->cplx || ev->twist) FAIL(fn + ": complex orbital evaluator (outside the fused scope: use the protocol route)");
+  if (ev->device != h->device) FAIL(fn + ": the two handles are on different devices (use the protocol route)");
+  if (slot < 0 || slot > 1) FAIL(fn + ": slot must be 0 or 1");
+  if (!es || ne < 1) FAIL(fn + ": no electron listed (use the protocol route)");
+  int spins = 0;
+  std::vector<char> seen((size_t)h->N, 0);
+  for (int t = 0; t < ne; ++t) {
+    if (es[t] < 0 || es[t] >= h->N) FAIL(fn + ": electron index out of range (use the protocol route)");
+    if (seen[es[t]]) FAIL(fn + ": an electron is listed twice (use the protocol route)");
+    seen[es[t]] = 1;
+    spins |= es[t] >= h->nup ? 2 : 1;
+  }
+  *spins_out = spins;
+  return 0;
+}
+
+int on_ev(pqa_handle* h, pqa_handle* ev, int rc) {  // (errors are reported on the wave function's handle)
+  if (rc) h->err = ev->err;
+  return rc;
+}
+
+// ev's orbitals of the slot's spin at the listed electrons of wf's resident walkers, into the slot's rows (what pqa_dm_points leaves
+// from a host array): the coordinates are gathered on wf's stream after ev's queued work, which may still read b_pts, and the
+// orbitals run on ev's own stream; tb_ev[1] is recorded on ev's stream behind them.  The caller has passed resident_scope.
+int resident_points(pqa_handle* h, pqa_handle* ev, int slot, const int32_t* es, int ne) {
+  auto& d = ev->dm[slot];
+  const long W = h->W;
+  const int norb = ev->nmo[d.spin];
+  TRY(on_ev(h, ev, ensure(ev, ev->b_pts, (size_t)W * ne * 3 * sizeof(double))));
+  TRY(on_ev(h, ev, ensure(ev, d.cfg, (size_t)W * ne * norb * sizeof(double))));
+  TRY(ensure(h, h->b_tves, (size_t)ne * sizeof(int)));
+  if (!h->tb_ev[0])
+    for (hipEvent_t& e : h->tb_ev) TRY(new_event(h, &e, hipEventDisableTiming));
+  const hipEvent_t produced = h->tb_ev[0], consumed = h->tb_ev[1];
+  TpTuneGuard tune_ev(ev);
+  ev->saved_valid = false;
+  d.ncfg = W * ne;
+  HIPCHK(hipEventRecord(consumed, ev->stream));
+  HIPCHK(hipStreamWaitEvent(h->stream, consumed, 0));
+  TRY(copy_in(h, h->b_tves.p, es, (size_t)ne * sizeof(int)));
+  hipLaunchKernelGGL(k_obdm_epts, dim3((unsigned)((W * ne + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->js.x,
+                     (const int*)h->b_tves.p, ne, h->N, W, (double*)ev->b_pts.p);
+  TRY(check_launch(h, "k_obdm_epts"));
+  HIPCHK(hipEventRecord(produced, h->stream));
+  HIPCHK(hipStreamWaitEvent(ev->stream, produced, 0));
+  TRY(on_ev(h, ev, launch_orb(ev, d.spin, plain_points((const double*)ev->b_pts.p, W * ne), W * ne, 1, (double*)d.cfg.p)));
+  HIPCHK(hipEventRecord(consumed, ev->stream));
+  return 0;
+}
+
+// pqa_obdm_sweeps (weights == NULL) and pqa_obdm_sweeps_w (the mean mode with the walker weights `weights`)
+int obdm_sweeps(pqa_handle* h, pqa_handle* ev, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign, uint64_t seed, int mean,
+                int first, int64_t chunk, double* ratio, int32_t* assign_out, double* value_mean, double* norm_mean, const double* weights,
+                const std::string& fn) {
+  int spins = 0;
+  TRY(resident_scope(h, ev, slot, es, ne, fn, &spins));
   const long W = h->W;
   const int N = h->N;
-  int spins = 0;
-  {
-    std::vector<char> seen((size_t)N, 0);
-    for (int t = 0; t < ne; ++t) {
-      if (es[t] < 0 || es[t] >= N) FAIL("pqa_obdm_sweeps: electron index out of range (use the protocol route)");
-      if (seen[es[t]]) FAIL("pqa_obdm_sweeps: an electron is listed twice (use the protocol route)");
-      seen[es[t]] = 1;
-      spins |= es[t] >= h->nup ? 2 : 1;
-    }
-  }
   auto& d = ev->dm[slot];
-  if (nsweeps < 1 || nsweeps > d.nkeep) FAIL("pqa_obdm_sweeps: more sweeps than pqa_dm_walk kept samples (use the protocol route)");
-  if (d.n <= 0) FAIL("pqa_obdm_sweeps: no auxiliary walkers (call pqa_dm_walk)");
-  if (mean && (!value_mean || !norm_mean)) FAIL("pqa_obdm_sweeps: the mean mode needs value_mean and norm_mean");
+  if (nsweeps < 1 || nsweeps > d.nkeep) FAIL(fn + ": more sweeps than pqa_dm_walk kept samples (use the protocol route)");
+  if (d.n <= 0) FAIL(fn + ": no auxiliary walkers (call pqa_dm_walk)");
+  if (mean && (!value_mean || !norm_mean)) FAIL(fn + ": the mean mode needs value_mean and norm_mean");
   if (!mean && !first && ev->dm_nconf != W)
-    FAIL("pqa_obdm_sweeps: the wave function holds another number of walkers than the accumulators were started with (use the protocol route)");
-  if (mean && !first) FAIL("pqa_obdm_sweeps: the mean mode starts its sums in every call (first must be set)");
+    FAIL(fn + ": the wave function holds another number of walkers than the accumulators were started with (use the protocol route)");
+  if (mean && !first) FAIL(fn + ": the mean mode starts its sums in every call (first must be set)");
   if (assign)
     for (size_t i = 0; i < (size_t)nsweeps * W; ++i)
-      if (assign[i] < 0 || assign[i] >= d.n) FAIL("pqa_obdm_sweeps: assignment outside the auxiliary walkers");
-  auto on_ev = [&](int rc) {  // (errors are reported on the wave function's handle)
-    if (rc) h->err = ev->err;
-    return rc;
-  };
+      if (assign[i] < 0 || assign[i] >= d.n) FAIL(fn + ": assignment outside the auxiliary walkers");
+  if (weights) TRY(check_weights(h, fn.c_str(), weights, W));
   const int norb = ev->nmo[d.spin];
-  if (norb <= 0) FAIL("pqa_obdm_sweeps: the evaluator has no orbitals of the walk's spin");
+  if (norb <= 0) FAIL(fn + ": the evaluator has no orbitals of the walk's spin");
   const int D = h->ndet;
   const size_t lds = ((size_t)3 * N + 2 * (size_t)ne + (D > 1 ? D : 0) + (size_t)h->ndet_s[0] * h->nup + (size_t)h->ndet_s[1] * h->ndn) * sizeof(double);
-  if (lds > 160 * 1024) FAIL("pqa_obdm_sweeps: more determinants than one LDS block holds (use the protocol route)");
+  if (lds > 160 * 1024) FAIL(fn + ": more determinants than one LDS block holds (use the protocol route)");
   if (lds > 64 * 1024) TRY(raise_lds_limit(h, h->S.pbc ? (const void*)k_obdm_rt<true> : (const void*)k_obdm_rt<false>));
   // scratch per walker: the point, the orbital rows of the spins present, and the ratios (per-walker mode) or the three panels and
   // the walker's share of a slice's partial tile (mean mode)
@@ -278,28 +327,20 @@ extern "C" int pqa_obdm_sweeps(pqa_handle_t* h, pqa_handle_t* ev, int slot, cons
   long Wc = chunk > 0 ? std::min<long>(W, chunk) : walker_chunk(W, per_walker);
   if (mean && Wc < W) Wc = std::max<long>(kSlice, Wc - Wc % kSlice);  // (whole slices: the slices do not depend on the chunk)
   const long nsl_max = (std::min(Wc, W) + kSlice - 1) / kSlice;
-  TRY(on_ev(ensure(ev, ev->dm_assign[0], (size_t)nsweeps * W * sizeof(int))));
-  if (assign) TRY(on_ev(copy_in(ev, ev->dm_assign[0].p, assign, (size_t)nsweeps * W * sizeof(int))));
-  TRY(on_ev(ensure(ev, ev->b_pts, (size_t)W * ne * 3 * sizeof(double))));
-  TRY(on_ev(ensure(ev, d.cfg, (size_t)W * ne * norb * sizeof(double))));
-  if (need_R) TRY(on_ev(ensure(ev, ev->dm_ratio, (size_t)Wc * ne * sizeof(double))));
-  if (mean) TRY(on_ev(ensure(ev, ev->b_obdm, ((size_t)3 * Wc * norb + (size_t)(nsl_max + 2) * npart) * sizeof(double))));
-  else TRY(on_ev(dm_prepare(ev, W, (long)norb * norb, 0, first, norb, 0)));
-  TRY(ensure(h, h->b_tves, (size_t)ne * sizeof(int)));
+  TRY(on_ev(h, ev, ensure(ev, ev->dm_assign[0], (size_t)nsweeps * W * sizeof(int))));
+  if (assign) TRY(on_ev(h, ev, copy_in(ev, ev->dm_assign[0].p, assign, (size_t)nsweeps * W * sizeof(int))));
+  if (need_R) TRY(on_ev(h, ev, ensure(ev, ev->dm_ratio, (size_t)Wc * ne * sizeof(double))));
+  // (weighted: the W weights and their sum behind the mean mode's scratch)
+  if (mean) TRY(on_ev(h, ev, ensure(ev, ev->b_obdm, ((size_t)3 * Wc * norb + (size_t)(nsl_max + 2) * npart + (weights ? (size_t)W + 1 : 0)) * sizeof(double))));
+  else TRY(on_ev(h, ev, dm_prepare(ev, W, (long)norb * norb, 0, first, norb, 0)));
   TRY(ensure(h, h->b_tbpts, (size_t)3 * Wc * sizeof(double)));
   if (nm0) TRY(ensure(h, h->b_orbphi[0], (size_t)Wc * nm0 * sizeof(double)));
   if (nm1) TRY(ensure(h, h->b_orbphi[1], (size_t)Wc * nm1 * sizeof(double)));
-  if (!h->tb_ev[0])
-    for (hipEvent_t& e : h->tb_ev) TRY(new_event(h, &e, hipEventDisableTiming));
-  const hipEvent_t produced = h->tb_ev[0], consumed = h->tb_ev[1];
   TpTuneGuard tune(h), tune_ev(ev);
-  ev->saved_valid = false;
-  d.ncfg = W * ne;
-  const int* d_es = (const int*)h->b_tves.p;
   int* d_assign = (int*)ev->dm_assign[0].p;
   double* d_pts = (double*)h->b_tbpts.p;
   double* d_R = need_R ? (double*)ev->dm_ratio.p : nullptr;
-  double *d_T = nullptr, *d_B = nullptr, *d_N = nullptr, *d_part = nullptr, *d_sums = nullptr, *d_out = nullptr;
+  double *d_T = nullptr, *d_B = nullptr, *d_N = nullptr, *d_part = nullptr, *d_sums = nullptr, *d_out = nullptr, *d_wts = nullptr, *d_wsum = nullptr;
   if (mean) {
     d_T = (double*)ev->b_obdm.p;
     d_B = d_T + (size_t)Wc * norb;
@@ -307,19 +348,16 @@ extern "C" int pqa_obdm_sweeps(pqa_handle_t* h, pqa_handle_t* ev, int slot, cons
     d_part = d_N + (size_t)Wc * norb;
     d_sums = d_part + (size_t)nsl_max * npart;
     d_out = d_sums + npart;
+    if (weights) { d_wts = d_out + npart; d_wsum = d_wts + W; }
   }
-  // the listed electrons' coordinates, gathered from the resident walkers on the wave function's stream (after the evaluator's
-  // queued work, which may still read b_pts), and the evaluator's orbitals there on its own stream
-  HIPCHK(hipEventRecord(consumed, ev->stream));
-  HIPCHK(hipStreamWaitEvent(h->stream, consumed, 0));
-  TRY(copy_in(h, h->b_tves.p, es, (size_t)ne * sizeof(int)));
-  hipLaunchKernelGGL(k_obdm_epts, dim3((unsigned)((W * ne + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->js.x, d_es, ne, N, W,
-                     (double*)ev->b_pts.p);
-  TRY(check_launch(h, "k_obdm_epts"));
-  HIPCHK(hipEventRecord(produced, h->stream));
-  HIPCHK(hipStreamWaitEvent(ev->stream, produced, 0));
-  TRY(on_ev(launch_orb(ev, d.spin, plain_points((const double*)ev->b_pts.p, W * ne), W * ne, 1, (double*)d.cfg.p)));
-  HIPCHK(hipEventRecord(consumed, ev->stream));
+  TRY(resident_points(h, ev, slot, es, ne));
+  const int* d_es = (const int*)h->b_tves.p;  // (allocated and filled by resident_points)
+  const hipEvent_t produced = h->tb_ev[0], consumed = h->tb_ev[1];
+  if (weights) {
+    TRY(on_ev(h, ev, copy_in(ev, d_wts, weights, (size_t)W * sizeof(double))));
+    hipLaunchKernelGGL((k_wsum<>), dim3(1), dim3(256), 0, ev->stream, (const double*)d_wts, W, d_wsum);
+    TRY(on_ev(h, ev, check_launch(ev, "k_wsum")));
+  }
   for (int s = 0; s < nsweeps; ++s) {
     const double* keep_pos = (const double*)d.keep_pos.p + (size_t)s * d.n * 3;
     const double* keep_row = (const double*)d.keep_row.p + (size_t)s * d.n * norb;
@@ -349,31 +387,100 @@ extern "C" int pqa_obdm_sweeps(pqa_handle_t* h, pqa_handle_t* ev, int slot, cons
       if (mean) {
         const long nsl = (wc + kSlice - 1) / kSlice;
         const unsigned tiles = (unsigned)((norb + 15) / 16);
-        hipLaunchKernelGGL(k_obdm_mean, dim3(tiles, tiles, (unsigned)nsl), dim3(64), 0, ev->stream, (const double*)d_B, (const double*)d_T,
-                           (const double*)d_N, wc, norb, d_part);
+        if (weights)
+          hipLaunchKernelGGL(k_obdm_mean<true>, dim3(tiles, tiles, (unsigned)nsl), dim3(64), 0, ev->stream, (const double*)d_B, (const double*)d_T,
+                             (const double*)d_N, (const double*)d_wts + w0, wc, norb, d_part);
+        else
+          hipLaunchKernelGGL(k_obdm_mean<false>, dim3(tiles, tiles, (unsigned)nsl), dim3(64), 0, ev->stream, (const double*)d_B, (const double*)d_T,
+                             (const double*)d_N, (const double*)nullptr, wc, norb, d_part);
         hipLaunchKernelGGL(k_obdm_reduce, dim3((unsigned)((npart + 255) / 256)), dim3(256), 0, ev->stream, (const double*)d_part, (long)npart,
                            nsl, (int)(s == 0 && w0 == 0), d_sums);
-        TRY(on_ev(check_launch(ev, "k_obdm_mean")));
+        TRY(on_ev(h, ev, check_launch(ev, "k_obdm_mean")));
       } else {
         hipLaunchKernelGGL((k_obdm_acc<>), dim3((unsigned)wc), dim3(256), (size_t)2 * norb * sizeof(double), ev->stream, keep_row, keep_f,
                            (const int*)asg + w0, (const double*)d.cfg.p + (size_t)w0 * ne * norb, (const double*)d_R, 0, 0, ne, norb,
                            (int)(first && s == 0), (double*)ev->dm_val.p + (size_t)w0 * norb * norb, (double*)ev->dm_norm[0].p + (size_t)w0 * norb);
-        TRY(on_ev(check_launch(ev, "k_obdm_acc")));
+        TRY(on_ev(h, ev, check_launch(ev, "k_obdm_acc")));
       }
       HIPCHK(hipEventRecord(consumed, ev->stream));
     }
   }
   if (ratio) HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's array is complete on return)
   if (mean) {
-    hipLaunchKernelGGL((k_scale_copy<>), dim3((unsigned)((npart + 255) / 256)), dim3(256), 0, ev->stream, (const double*)d_sums, (long)npart,
-                       1.0 / ((double)W * nsweeps), d_out);
-    TRY(on_ev(check_launch(ev, "k_scale_copy")));
+    if (weights)
+      hipLaunchKernelGGL(k_obdm_wscale, dim3((unsigned)((npart + 255) / 256)), dim3(256), 0, ev->stream, (const double*)d_sums, (long)npart,
+                         (const double*)d_wsum, (double)nsweeps, d_out);
+    else
+      hipLaunchKernelGGL((k_scale_copy<>), dim3((unsigned)((npart + 255) / 256)), dim3(256), 0, ev->stream, (const double*)d_sums, (long)npart,
+                         1.0 / ((double)W * nsweeps), d_out);
+    TRY(on_ev(h, ev, check_launch(ev, "k_scale_copy")));
     HIPCHK(hipMemcpyAsync(value_mean, d_out, (size_t)norb * norb * sizeof(double), hipMemcpyDefault, ev->stream));
     HIPCHK(hipMemcpyAsync(norm_mean, d_out + (size_t)norb * norb, (size_t)norb * sizeof(double), hipMemcpyDefault, ev->stream));
   }
   if (assign_out) HIPCHK(hipMemcpyAsync(assign_out, d_assign, (size_t)nsweeps * W * sizeof(int), hipMemcpyDefault, ev->stream));
   if (mean || assign_out) HIPCHK(hipStreamSynchronize(ev->stream));
   return 0;
+}
+
+}  // namespace
+
+extern "C" int pqa_obdm_sweeps(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
+                               uint64_t seed, int mean, int first, int64_t chunk, double* ratio, int32_t* assign_out, double* value_mean,
+                               double* norm_mean) {
+  return obdm_sweeps(h, ev, slot, es, ne, nsweeps, assign, seed, mean, first, chunk, ratio, assign_out, value_mean, norm_mean, nullptr,
+                     "pqa_obdm_sweeps");
+}
+
+// The mean mode with walker weights: value_mean = sum_s sum_w w_w b_s[w] (x) t_s[w] / (nsweeps sum_w w_w), norm_mean likewise.
+extern "C" int pqa_obdm_sweeps_w(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
+                                 uint64_t seed, int64_t chunk, const double* weights, int32_t* assign_out, double* value_mean,
+                                 double* norm_mean) {
+  if (!h) return -2;
+  if (!weights) FAIL("pqa_obdm_sweeps_w: weights is NULL");
+  return obdm_sweeps(h, ev, slot, es, ne, nsweeps, assign, seed, 1, 1, chunk, nullptr, assign_out, value_mean, norm_mean, weights,
+                     "pqa_obdm_sweeps_w");
+}
+
+// pqa_dm_points with the listed electrons' coordinates gathered from wf's resident walkers, device to device
+extern "C" int pqa_dm_points_resident(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne) {
+  int spins = 0;
+  TRY(resident_scope(h, ev, slot, es, ne, "pqa_dm_points_resident", &spins));
+  if (ev->dm[slot].n <= 0) FAIL("pqa_dm_points_resident: no auxiliary walkers in the slot (call pqa_dm_walk: it names the slot's spin)");
+  if (ev->nmo[ev->dm[slot].spin] <= 0) FAIL("pqa_dm_points_resident: the evaluator has no orbitals of the walk's spin");
+  return resident_points(h, ev, slot, es, ne);
+}
+
+// Weighted walker mean of one of ev's per-walker accumulators (pqa_dm_fetch's `which`), times scale
+extern "C" int pqa_dm_fetch_w(pqa_handle_t* h, int which, int ncol, double scale, const double* weights, double* out) {
+  if (!h) return -2;
+  HIPCHK(hipSetDevice(h->device));
+  if (h->dm_nconf <= 0) FAIL("pqa_dm_fetch_w: nothing accumulated");
+  if (!out) FAIL("pqa_dm_fetch_w: out is NULL");
+  const long rows = h->dm_nconf;
+  const double* src;
+  long cols;
+  if (which == 0) {
+    src = (const double*)h->dm_val.p;
+    cols = h->dm_nval * (h->dm_cx ? 2 : 1);
+    if (ncol != cols) FAIL("pqa_dm_fetch_w: ncol does not match the accumulated value");
+  } else if (which == 1 || which == 2) {
+    src = (const double*)h->dm_norm[which - 1].p;
+    cols = ncol;
+    if (cols < 1 || (size_t)rows * cols * sizeof(double) > h->dm_norm[which - 1].cap) FAIL("pqa_dm_fetch_w: ncol exceeds the accumulated norm");
+  } else FAIL("pqa_dm_fetch_w: which must be 0, 1 or 2");
+  TRY(check_weights(h, "pqa_dm_fetch_w", weights, rows));
+  const long nsl = wcol_slices(rows);
+  // scratch: [means (cols) | partials (nsl, cols) | weights (rows) | their sum]
+  TRY(ensure(h, h->dm_tmp, ((size_t)cols * (nsl + 1) + rows + 1) * sizeof(double)));
+  double* d_acc = (double*)h->dm_tmp.p;
+  double* d_part = d_acc + cols;
+  double* d_wts = d_part + (size_t)nsl * cols;
+  double* d_wsum = d_wts + rows;
+  TRY(copy_in(h, d_wts, weights, (size_t)rows * sizeof(double)));
+  hipLaunchKernelGGL((k_wsum<>), dim3(1), dim3(256), 0, h->stream, (const double*)d_wts, rows, d_wsum);
+  TRY(check_launch(h, "k_wsum"));
+  TRY(wcol_means_dev<>(h, src, d_wts, rows, cols, 1, 1, 1, scale, d_wsum, d_part, d_acc));
+  return copy_out(h, out, d_acc, (size_t)cols * sizeof(double));
 }
 
 // Bytes the evaluator holds for the fused one-body estimator: scratch = the mean mode's panels, partial tiles and sums plus the

@@ -132,14 +132,15 @@ __global__ __launch_bounds__(256) void k_sq_fold(const double* __restrict__ part
   acc[k] = v;
 }
 
-}  // namespace
-
-extern "C" int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, const double* recip, int mean, double* sq, double* spinsq) {
+// pqa_sq (weights == NULL) and pqa_sq_w (the walker means with the weights `weights`)
+int sq_run(pqa_handle* h, int nqv, const double* q, const int* qn, const double* recip, int mean, const double* weights, double* sq,
+           double* spinsq, const std::string& fn) {
   HIPCHK(hipSetDevice(h->device));
-  if (h->W == 0) FAIL("pqa_sq: state not initialised (call recompute)");
-  if (nqv < 0) FAIL("pqa_sq: negative q count");
+  if (h->W == 0) FAIL(fn + ": state not initialised (call recompute)");
+  if (nqv < 0) FAIL(fn + ": negative q count");
+  if (weights) TRY(check_weights(h, fn.c_str(), weights, h->W));
   if (nqv == 0) return 0;
-  if (!q || !sq || !spinsq) FAIL("pqa_sq: q / sq / spinsq is NULL");
+  if (!q || !sq || !spinsq) FAIL(fn + ": q / sq / spinsq is NULL");
   const long W = h->W;
   const int N = h->N, Q = nqv;
   // the live coordinates, in place: the sweep's planes [N*3][W] when the walker-major arrays are stale, else js.x [W][N][3]
@@ -160,7 +161,7 @@ extern "C" int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, 
   A.N = N; A.nup = h->nup; A.Q = Q; A.M = nmax + 1;
   A.stride = stride_of(rec);
   const size_t tab = (size_t)A.stride * sizeof(double);
-  if (tab > kSqLdsMax) FAIL("pqa_sq: too many electrons for the coordinate table in LDS");
+  if (tab > kSqLdsMax) FAIL(fn + ": too many electrons for the coordinate table in LDS");
   if (rec)
     for (int k = 0; k < 9; ++k) A.recip[k] = recip[k];
 
@@ -184,7 +185,16 @@ extern "C" int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, 
   TRY(ensure(h, h->b_sqout, (size_t)2 * Wc * Q * sizeof(double)));
   double* d_out = (double*)h->b_sqout.p;
   const long R = std::min<long>(kSqRowSlices, Wc);
-  if (mean) {
+  double *d_wts = nullptr, *d_wsum = nullptr;
+  if (weights) {  // sums [2][Q], then the W weights and their sum; partials of the weighted column sums [2][slices][Q]
+    TRY(ensure(h, h->b_sqpart, (size_t)2 * wcol_slices_max(std::min(Wc, W)) * Q * sizeof(double)));
+    TRY(ensure(h, h->b_sqacc, ((size_t)2 * Q + W + 1) * sizeof(double)));
+    d_wts = (double*)h->b_sqacc.p + (size_t)2 * Q;
+    d_wsum = d_wts + W;
+    TRY(copy_in(h, d_wts, weights, (size_t)W * sizeof(double)));
+    hipLaunchKernelGGL((k_wsum<>), dim3(1), dim3(256), 0, h->stream, (const double*)d_wts, W, d_wsum);
+    TRY(check_launch(h, "k_wsum"));
+  } else if (mean) {
     TRY(ensure(h, h->b_sqpart, (size_t)2 * R * Q * sizeof(double)));
     TRY(ensure(h, h->b_sqacc, (size_t)2 * Q * sizeof(double)));
   }
@@ -201,6 +211,11 @@ extern "C" int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, 
       TRY(copy_out(h, spinsq + (size_t)w0 * Q, d_out + (size_t)wc * Q, (size_t)wc * Q * sizeof(double)));
       continue;
     }
+    if (weights) {  // sum_w w_w v[z][w][q] of the chunk in the fixed order of k_wcol_means, the chunks one after the other
+      TRY(wcol_means_dev<>(h, d_out, d_wts + w0, wc, Q, 2, (int)(w0 == 0), (int)(w0 + wc == W), 1.0, d_wsum, (double*)h->b_sqpart.p,
+                         (double*)h->b_sqacc.p));
+      continue;
+    }
     const long rp = (wc + R - 1) / R;
     const int Rc = (int)((wc + rp - 1) / rp);  // slices this chunk fills
     hipLaunchKernelGGL(k_sq_rows, dim3((unsigned)((Q + 63) / 64), (unsigned)Rc, 2), dim3(64), 0, h->stream, (const double*)d_out, wc, Q,
@@ -213,4 +228,17 @@ extern "C" int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, 
   if (!mean) return 0;
   TRY(copy_out(h, sq, h->b_sqacc.p, (size_t)Q * sizeof(double)));
   return copy_out(h, spinsq, (const double*)h->b_sqacc.p + Q, (size_t)Q * sizeof(double));
+}
+
+}  // namespace
+
+extern "C" int pqa_sq(pqa_handle_t* h, int nqv, const double* q, const int* qn, const double* recip, int mean, double* sq, double* spinsq) {
+  return sq_run(h, nqv, q, qn, recip, mean, nullptr, sq, spinsq, "pqa_sq");
+}
+
+extern "C" int pqa_sq_w(pqa_handle_t* h, int nqv, const double* q, const int* qn, const double* recip, const double* weights, double* sq,
+                        double* spinsq) {
+  if (!h) return -2;
+  if (!weights) FAIL("pqa_sq_w: weights is NULL");
+  return sq_run(h, nqv, q, qn, recip, 1, weights, sq, spinsq, "pqa_sq_w");
 }

@@ -6,6 +6,11 @@ index computation on W weights) and the block loop of ``rundmc`` (:413-591) with
 per-electron host loop is not restated: the parity tests drive the protocol entry points through
 ``tests/helpers.protocol_dmc_propagate``, and an unmodified ``pyqmc.method.dmc`` runs over the wave-function objects.
 
+Accumulators besides the energy (density matrices, S^2, S(q), symmetry ratios) enter a block as the steps' weighted walker means
+(dmc.py:205-207).  ``dmc_accumulator_route`` names the route: "resident" — every accumulator gives its weighted mean from the resident
+walkers (``avg_resident(wf, weights=w)``), nothing but the means crosses the bus — or "host", the per-walker results of the fetched
+walkers weighted in NumPy.
+
 ``rng`` (optional, tests) supplies the random draws to replay the reference's:
 ``normal(W)->(W,3)``, ``rand(W)->(W,)``, ``rand1()->float``, ``rot()->(3,3)``, ``random(W)->(W,)``.
 """
@@ -134,11 +139,89 @@ def _propagate_host_accumulators(dev, wf, configs, weights, tstep, branchcut, e_
         d["weight"], d["acceptance"], d["tmove_acceptance"] = wavg, stat[0, 0], stat[0, 1]
         df.append(d)
     weights[:] = w
+    return combine_steps(df), configs, weights
+
+
+def combine_steps(df):
+    """Block averages of the per-step dictionaries ``df`` (dmc.py:212-219): every key averaged over the steps with the steps'
+    relative weights, ``weight`` their plain mean."""
     wts = np.asarray([d["weight"] for d in df])
     rel = wts / wts.mean()
     out = {k: np.mean([d[k] * r for d, r in zip(df, rel)], axis=0) for k in df[0]}
     out["weight"] = wts.mean()
-    return out, configs, weights
+    return out
+
+
+def _propagate_resident_accumulators(dev, wf, configs, weights, tstep, branchcut, e_trial, e_est, nsteps, accumulators, ekey, state_current=False,
+                                     rng=None):
+    """``dmc_propagate`` with further accumulators, all of them evaluated from the resident state: every step is the device call of
+    ``_propagate_host_accumulators`` (same seed draws, same continuation), after which each other accumulator's
+    ``avg_resident(wf, weights=w)`` gives the step's weighted walker mean sum_w w_w res_w / sum_w w_w (dmc.py:205-207) on the device.
+    Neither the walkers nor a per-walker array cross the bus during the block: the walkers are fetched once after the last step
+    (periodic containers: after every step, for the wrap counters, which ``pqa_get_wrap`` hands out as increments)."""
+    from .energy import KEYS
+    from .vmc import _fetch
+
+    acc, name = accumulators[ekey[0]], ekey[0]
+    W = configs.configs.shape[0]
+    _refuse_batched_tmoves(acc, getattr(dev, "necp", 0))
+    if not state_current:
+        wf.recompute(configs)
+    acc.bind(dev)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    df = []
+    tapes = None
+    if rng is not None:
+        N, necp = configs.configs.shape[1], getattr(dev, "necp", 0)
+        tapes = _record_tapes(rng, nsteps, N, necp, W, acc.has_nonlocal_moves() and necp > 0)
+    per_step_fetch = bool(getattr(dev, "pbc", False))
+    for i in range(nsteps):
+        step_tapes = None
+        if tapes is not None:  # (sliced as on the host route)
+            step_tapes = {k: (np.stack([v[0 if i == 0 else i], v[i + 1]]) if k.startswith("ecp_") else v[i:i + 1]) for k, v in tapes.items()}
+        avg, stat = dev.dmc_steps(tstep, 1, w, branchcut, e_trial, e_est, threshold=acc.threshold, tapes=step_tapes,
+                                  seed=int(np.random.randint(0, 2**31 - 1)), cont=i > 0 and dev.dmc_can_continue())
+        if per_step_fetch:
+            _fetch(dev, configs)
+        wavg = float(avg[0, 6])
+        d = {name + k: avg[0, i] for i, k in enumerate(KEYS[:6])}
+        for k, other in accumulators.items():
+            if k == name:
+                continue
+            for m, res in other.avg_resident(wf, weights=w).items():
+                d[k + m] = res
+        d["weight"], d["acceptance"], d["tmove_acceptance"] = wavg, stat[0, 0], stat[0, 1]
+        df.append(d)
+    if not per_step_fetch:
+        _fetch(dev, configs)
+    weights[:] = w
+    return combine_steps(df), configs, weights
+
+
+ACCUMULATOR_ROUTES = (None, "resident", "host")
+
+
+def dmc_accumulator_route(wf, accumulators, ekey=("energy", "total")):
+    """``(route, reason)``: how ``dmc_propagate`` evaluates a block with these accumulators.  ``"fused"``: the energy alone, the whole
+    step loop in one device call.  ``"resident"``: further accumulators, every one of them able to give its weighted walker mean
+    from the resident state (``avg_resident`` / ``resident_scope``) of a real wave function without a three-body factor on one
+    handle.  ``"host"``: anything else — the walkers come back after every step and the accumulators' per-walker ``__call__`` is
+    weighted on the host."""
+    from .wf import readonly_device
+
+    others = [k for k in accumulators if k != ekey[0]]
+    if not others:
+        return "fused", "the energy is the only accumulator"
+    if readonly_device(wf) is None:
+        return "host", "the wave function is not a real Slater (x two-body Jastrow) product on one device handle (complex, twisted and three-body handles are outside the resident scope)"
+    for k in others:
+        a = accumulators[k]
+        if not (callable(getattr(a, "avg_resident", None)) and callable(getattr(a, "resident_scope", None))):
+            return "host", f"{k}: {type(a).__name__} has no avg_resident / resident_scope"
+        why = a.resident_scope(wf)
+        if why is not None:
+            return "host", f"{k}: {why}"
+    return "resident", "every accumulator besides the energy gives its weighted mean from the resident state"
 
 
 def fused_dmc_supported(wf, accumulators, ekey):
@@ -154,7 +237,7 @@ def fused_dmc_supported(wf, accumulators, ekey):
 
 
 def dmc_propagate(wf, configs, weights, tstep, branchcut_start, e_trial, e_est, nsteps=5, accumulators=None,
-                  ekey=("energy", "total"), rng=None, state_current=False):
+                  ekey=("energy", "total"), rng=None, state_current=False, accumulator_route=None):
     """Propagate ``nsteps`` DMC steps without branching; returns (block averages, configs, weights) with the
     reference's keys (``<acc><quantity>``, ``weight``, ``acceptance``, ``tmove_acceptance``).
 
@@ -164,13 +247,26 @@ def dmc_propagate(wf, configs, weights, tstep, branchcut_start, e_trial, e_est, 
     weight-averaged as dmc.py:205-212 does.  ``rng`` replays the reference's draws (tests); ``state_current=True``
     promises that the device already holds the wave-function state of ``configs`` — ``rundmc`` passes it after branching on
     the device (``DeviceWF.resample``) — and skips the initial recompute.  (``tests/helpers.protocol_dmc_propagate`` is the
-    protocol-route harness the parity tests use.)"""
+    protocol-route harness the parity tests use.)
+
+    ``accumulator_route`` (further accumulators only; see ``dmc_accumulator_route``): None takes ``"resident"`` — the accumulators'
+    weighted means come from the resident walkers, nothing but the means crosses the bus — when every accumulator is in its scope
+    and ``"host"`` otherwise; ``"resident"`` raises ``NotImplementedError`` with the reason outside the scope; ``"host"`` fetches the
+    walkers after every step and weights the per-walker results on the host."""
     assert accumulators is not None, "Need an energy accumulator for DMC"
+    if accumulator_route not in ACCUMULATOR_ROUTES:
+        raise ValueError(f"accumulator_route must be one of {ACCUMULATOR_ROUTES}, got {accumulator_route!r}")
     dev = fused_dmc_supported(wf, accumulators, ekey)
     if dev is None:
         raise NotImplementedError("pyqmc_amd.dmc_propagate runs wave functions on one device handle whose energy comes from "
                                   "pyqmc_amd.EnergyAccumulator; drive pyqmc.method.dmc.dmc_propagate over the protocol objects for anything else")
     if set(accumulators) != {ekey[0]}:
+        route, why = dmc_accumulator_route(wf, accumulators, ekey)
+        if accumulator_route == "resident" and route != "resident":
+            raise NotImplementedError(f"dmc_propagate(accumulator_route='resident'): {why}")
+        if route == "resident" and accumulator_route != "host":
+            return _propagate_resident_accumulators(dev, wf, configs, weights, tstep, branchcut_start, e_trial, e_est, nsteps, accumulators, ekey,
+                                                    state_current=state_current, rng=rng)
         return _propagate_host_accumulators(dev, wf, configs, weights, tstep, branchcut_start, e_trial, e_est, nsteps, accumulators, ekey,
                                             state_current=state_current, rng=rng)
     return _propagate_fused(dev, wf, configs, weights, tstep, branchcut_start, e_trial, e_est, nsteps, accumulators[ekey[0]], ekey[0], rng,
@@ -201,7 +297,7 @@ def branch(configs, weights, base_u=None, on_resample=None):
 
 def rundmc(wf, configs, weights=None, tstep=0.01, nblocks=10, nsteps_per_block=None, accumulators=None, verbose=False,
            ekey=("energy", "total"), vmc_warmup=10, branchcut_start=10, feedback=1.0, distributed=False, recompute_every=10,
-           hdf_file=None, continue_from=None, blockoffset=0, propagate=None, vmc_worker=None):
+           hdf_file=None, continue_from=None, blockoffset=0, propagate=None, vmc_worker=None, accumulator_route=None):
     """Block loop of the reference's ``rundmc`` (dmc.py:413-591): VMC warm-up and energy reference — or, when ``hdf_file``
     exists / ``continue_from`` is given, the walkers, weights, ``e_trial``, ``e_est``, ``esigma`` and block offset of that
     file (dmc.py:466-500) — then propagate -> branch -> trial-energy feedback per block.  With ``distributed=True`` every
@@ -217,7 +313,8 @@ def rundmc(wf, configs, weights=None, tstep=0.01, nblocks=10, nsteps_per_block=N
     ``hdf_file + ".rank<r>"`` — each with the (identical, all-reduced) block record and that rank's own walkers and
     weights, so no two processes ever touch one file and every rank can continue from its own.
     ``propagate`` / ``vmc_worker``: callables with the signatures of ``dmc_propagate`` / ``vmc.vmc_worker`` to run the blocks
-    with instead of the device drivers (the CPU tests pass protocol-route drivers for the oracle's wave functions)."""
+    with instead of the device drivers (the CPU tests pass protocol-route drivers for the oracle's wave functions).
+    ``accumulator_route``: handed to ``dmc_propagate``."""
     from . import dist as pdist
     from .blockfile import BlockFile
     from .vmc import vmc
@@ -277,7 +374,8 @@ def rundmc(wf, configs, weights=None, tstep=0.01, nblocks=10, nsteps_per_block=N
         else:
             blk, configs, weights = dmc_propagate(wf, configs, weights, tstep, branchcut_start * esigma, e_trial, e_est,
                                                   nsteps=nsteps_per_block, accumulators=accumulators, ekey=ekey,
-                                                  state_current=current and block % max(int(recompute_every), 1) != 0)
+                                                  state_current=current and block % max(int(recompute_every), 1) != 0,
+                                                  accumulator_route=accumulator_route)
         if distributed:  # weighted recombination of the per-rank block averages (dmc.py:238-304)
             keys = sorted(k for k in blk if k != "weight")
             parts = [np.asarray(blk[k] * blk["weight"] * W).ravel() for k in keys]  # (array-valued accumulators, complex energies)

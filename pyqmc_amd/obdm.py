@@ -25,6 +25,9 @@ Two routes give the ratios (``route``, as in ``TBDMAccumulator``):
   per-configuration matrix.  With ``rng="numpy"`` the draws are those of the protocol route; ``rng="device"`` draws the walk and the
   assignments from the device's Philox streams, keyed by one ``numpy.random`` integer per evaluation.
 
+``avg_resident(wf, weights=w)`` is the weighted walker mean sum_w w_w res_w / sum_w w_w of DMC's mixed estimator
+(``pqa_obdm_sweeps_w``: the same product with the weight applied to B as it is loaded; unit weights give the bits of ``avg``).
+
 ``last_route`` names the route of the last evaluation.
 """
 
@@ -132,6 +135,20 @@ class OrbitalEvaluator:
         out = out.view(complex) if cplx else out
         return out.reshape(shape) if mean else out.reshape((nconf,) + tuple(shape))
 
+    def points_resident(self, slot, dev, electrons):
+        """``pqa_dm_points_resident``: what ``points`` leaves in ``slot``, for the listed ``electrons`` of the walkers resident
+        behind the wave-function handle ``dev``, gathered device to device (the slot's walk names the spin)."""
+        es = np.ascontiguousarray(np.asarray(electrons).ravel(), dtype=np.int32)
+        dev.call("pqa_dm_points_resident", self.dev._h, int(slot), _ffi.ptr(es), len(es))
+
+    def fetch_w(self, which, nconf, shape, scale, weights, cplx=False):
+        """``pqa_dm_fetch_w``: the walker mean of accumulator ``which`` with the walker ``weights`` (nconf,), times ``scale``."""
+        w = _ffi.walker_weights(weights, nconf)
+        ncol = int(np.prod(shape)) * (2 if cplx else 1)
+        out = np.empty(ncol)
+        self.dev.call("pqa_dm_fetch_w", int(which), ncol, float(scale), _ffi.ptr(w), _ffi.ptr(out))
+        return (out.view(complex) if cplx else out).reshape(shape)
+
 
 def draw_walk_tapes(n, nsamples):
     """Standard normals (nsamples,n,3) and uniforms (nsamples,n) in the order the reference's walk consumes
@@ -222,6 +239,25 @@ def device_obdm_sweeps(dev, ev, electrons, nsweeps, assign=None, seed=0, mean=Fa
     dev.call("pqa_obdm_sweeps", ev.dev._h, 0, _ffi.ptr(es), len(es), int(nsweeps), _ffi.ptr(assign), int(seed), int(mean), int(first),
              int(walker_chunk), _ffi.ptr(out.get("ratio")), None if assign is not None else _ffi.ptr(out["assign"]), _ffi.ptr(out.get("value")),
              _ffi.ptr(out.get("norm")))
+    return out
+
+
+def device_obdm_sweeps_w(dev, ev, electrons, nsweeps, weights, assign=None, seed=0, walker_chunk=0):
+    """``pqa_obdm_sweeps_w``: the mean mode of ``device_obdm_sweeps`` with the walker ``weights`` (W,): ``value`` and ``norm`` are
+    sum_s sum_w w_w (...) / (nsweeps sum_w w_w).  Returns a dict with ``assign``, ``value`` and ``norm``."""
+    es = np.ascontiguousarray(np.asarray(electrons).ravel(), dtype=np.int32)
+    W, norb = dev.W, ev.norb
+    w = _ffi.walker_weights(weights, W)
+    out = {"value": np.empty((norb, norb)), "norm": np.empty(norb)}
+    if assign is not None:
+        assign = np.ascontiguousarray(assign, dtype=np.int32)
+        if assign.shape != (nsweeps, W):
+            raise ValueError(f"assignments ({nsweeps}, {W}) expected, got {assign.shape}")
+        out["assign"] = assign
+    else:
+        out["assign"] = np.empty((nsweeps, W), dtype=np.int32)
+    dev.call("pqa_obdm_sweeps_w", ev.dev._h, 0, _ffi.ptr(es), len(es), int(nsweeps), _ffi.ptr(assign), int(seed), int(walker_chunk),
+             _ffi.ptr(w), None if assign is not None else _ffi.ptr(out["assign"]), _ffi.ptr(out["value"]), _ffi.ptr(out["norm"]))
     return out
 
 
@@ -320,11 +356,13 @@ class OBDMAccumulator:
         self._walkers.x = np.ascontiguousarray(kept[-1][pick[-1]])
         return cplx
 
-    def _sample_fused(self, dev, mean, with_ratios=False):
-        """One evaluation on the fused route: the walk, then ONE ``pqa_obdm_sweeps`` call on the walkers resident behind ``dev``.
-        Returns (value_mean, norm_mean) of the mean mode (else None, the evaluator's accumulators hold the result) and the ratios
-        (nsweeps, W, nelec) when asked for."""
+    def _sample_fused(self, dev, mean, with_ratios=False, weights=None):
+        """One evaluation on the fused route: the walk, then ONE ``pqa_obdm_sweeps`` call on the walkers resident behind ``dev``
+        (``weights``: ``pqa_obdm_sweeps_w``, the weighted mean).  Returns (value_mean, norm_mean) of the mean mode (else None, the
+        evaluator's accumulators hold the result) and the ratios (nsweeps, W, nelec) when asked for."""
         ev, nconf, nsw = self.orbitals, dev.W, self._nsweeps
+        if weights is not None:  # (refused before numpy.random is touched)
+            weights = _ffi.walker_weights(weights, nconf)
         seed = int(np.random.randint(0, 2**31 - 1)) if self._rng == "device" else None
         self._start(nconf, seed)
         naux = len(self._walkers.x)
@@ -332,8 +370,12 @@ class OBDMAccumulator:
         if seed is None:
             pick = np.random.randint(0, naux, size=(nsw, nconf)).astype(np.int32)  # drawn before the walk (obdm.py:150)
         _, kept = self._walkers.advance(0, nsw, self._tstep, keep=nsw, seed=seed)
-        out = device_obdm_sweeps(dev, ev, self._electrons, nsw, assign=pick, seed=0 if seed is None else seed, mean=mean,
-                                 walker_chunk=self._walker_chunk, with_ratios=with_ratios)
+        if weights is not None:
+            out = device_obdm_sweeps_w(dev, ev, self._electrons, nsw, weights, assign=pick, seed=0 if seed is None else seed,
+                                       walker_chunk=self._walker_chunk)
+        else:
+            out = device_obdm_sweeps(dev, ev, self._electrons, nsw, assign=pick, seed=0 if seed is None else seed, mean=mean,
+                                     walker_chunk=self._walker_chunk, with_ratios=with_ratios)
         vm, nm, ratio, used = out.get("value"), out.get("norm"), out.get("ratio"), out["assign"]
         self.last_assign = used
         self._walkers.x = np.ascontiguousarray(kept[-1][self.last_assign[-1]])  # the reference's resampling step, as in _sample
@@ -359,12 +401,19 @@ class OBDMAccumulator:
         """Mean over the configurations, reduced on the device (obdm.py:195-197)."""
         return self._result(configs, wf, True)
 
-    def avg_resident(self, wf):
-        """``avg`` on the fused route for the walkers resident behind ``wf``, without a host container."""
+    def resident_scope(self, wf):
+        """None when ``avg_resident`` can run for ``wf``, else the reason (the fused route's rules)."""
+        if self._route == "protocol":
+            return "the accumulator is bound to route='protocol'"
+        return self._out_of_scope(wf)
+
+    def avg_resident(self, wf, weights=None):
+        """``avg`` on the fused route for the walkers resident behind ``wf``, without a host container.  ``weights`` (W,): the
+        weighted walker mean sum_w w_w res_w / sum_w w_w (DMC's mixed estimator) instead of the plain one."""
         if self.resolve_route(wf) != "fused":
             raise ValueError("OBDMAccumulator.avg_resident needs the fused route")
         self.last_route = "fused"
-        (vm, nm), _ = self._sample_fused(readonly_device(wf), True)
+        (vm, nm), _ = self._sample_fused(readonly_device(wf), True, weights=weights)
         return {"value": vm, "norm": nm}
 
     def evaluate_orbitals(self, configs):

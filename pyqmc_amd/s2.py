@@ -78,6 +78,28 @@ class S2Accumulator:
     def avg(self, configs, wf):
         return {k: np.mean(v, axis=0) for k, v in self(configs, wf).items()}
 
+    def resident_scope(self, wf):
+        """None when ``avg_resident`` can run for ``wf``, else the reason (the fused route's rules)."""
+        dev = fused_handle(wf)
+        if dev is None:
+            return "the wave function is not a real Slater (x two-body Jastrow) product on one device handle"
+        if tuple(dev.nelec) != self.nelec:
+            return "the wave function has other electron numbers than the accumulator"
+        return None
+
+    def avg_resident(self, wf, weights=None):
+        """The walker mean of S^2 for the walkers resident behind ``wf``, without a host container; with ``weights`` (W,) the
+        weighted mean sum_w w_w S2_w / sum_w w_w (W doubles come back, the weighting is done on the host)."""
+        why = self.resident_scope(wf)
+        if why is not None:
+            raise ValueError(f"S2Accumulator.avg_resident: {why}")
+        dev = fused_handle(wf)
+        if weights is not None:
+            weights = _ffi.walker_weights(weights, dev.W)
+        self.last_route = "fused"
+        s2 = device_s2(dev)
+        return {"S2": np.mean(s2) if weights is None else np.dot(weights, s2) / weights.sum()}
+
     def keys(self):
         return self.shapes().keys()
 

@@ -43,6 +43,19 @@ def device_sq(dev, qlist, qn=None, recip=None, mean=False):
     return sq, sp
 
 
+def device_sq_w(dev, qlist, weights, qn=None, recip=None):
+    """``pqa_sq_w`` on a device handle: the weighted walker means (Sq, spinSq), each (Q,), of the resident walkers with the walker
+    ``weights`` (W,); ``qn`` / ``recip`` as in ``device_sq``."""
+    w = _ffi.walker_weights(weights, dev.W)
+    q = _ffi.f64(np.reshape(qlist, (-1, 3)))
+    nq = q.shape[0]
+    qi = None if qn is None else np.ascontiguousarray(np.reshape(qn, (nq, 3)), dtype=np.int32)
+    rc = None if qi is None else _ffi.f64(np.reshape(recip, (3, 3)))
+    sq, sp = np.empty(nq), np.empty(nq)
+    dev.call("pqa_sq_w", int(nq), _ffi.ptr(q), _ffi.ptr(qi), _ffi.ptr(rc), _ffi.ptr(w), _ffi.ptr(sq), _ffi.ptr(sp))
+    return sq, sp
+
+
 class SqAccumulator:
     """Charge and spin structure factors (accumulators.py:191-234): ``__call__`` -> {"Sq": (nconf, Q), "spinSq": (nconf, Q)},
     ``avg`` -> the walker means (Q,).
@@ -66,7 +79,9 @@ class SqAccumulator:
 
     def _fused(self, configs, wf):
         dev = device_handle(wf)
-        if dev is None or tuple(dev.nelec) != (self.nup, self.nelec - self.nup) or dev.W != configs.configs.shape[0]:
+        if dev is None or tuple(dev.nelec) != (self.nup, self.nelec - self.nup):
+            return None
+        if configs is not None and dev.W != configs.configs.shape[0]:  # (configs = None: the resident walkers themselves)
             return None
         # the handle's resident walkers are `configs` (the drivers fetch them from the device before any host accumulator)
         return dev
@@ -99,6 +114,31 @@ class SqAccumulator:
 
     def avg(self, configs, wf):
         return self._eval(configs, wf, True)
+
+    def resident_scope(self, wf):
+        """None when ``avg_resident`` can run for ``wf``, else the reason (the fused route's rules)."""
+        dev = device_handle(wf)
+        if dev is None:
+            return "the wave function does not live on one device handle"
+        if tuple(dev.nelec) != (self.nup, self.nelec - self.nup):
+            return "the wave function has other electron numbers than the accumulator's system"
+        if self._fused(None, wf) is None:  # (the route predicate of __call__ / avg decides here too)
+            return "the accumulator's fused route does not take this wave function"
+        return None
+
+    def avg_resident(self, wf, weights=None):
+        """The walker means for the walkers resident behind ``wf``, without a host container; with ``weights`` (W,) the weighted
+        means sum_w w_w res_w / sum_w w_w, reduced on the device (``pqa_sq_w``)."""
+        why = self.resident_scope(wf)
+        if why is not None:
+            raise ValueError(f"SqAccumulator.avg_resident: {why}")
+        dev = self._fused(None, wf)
+        self.last_route = "fused"
+        if weights is None:
+            sq, sp = device_sq(dev, self.qlist, self.qn, self.recip, mean=True)
+        else:
+            sq, sp = device_sq_w(dev, self.qlist, weights, self.qn, self.recip)
+        return {"Sq": sq, "spinSq": sp}
 
     def keys(self):
         return set(["Sq", "spinSq"])

@@ -50,20 +50,41 @@ class SymmetryAccumulator:
     def _origins(self):
         return None
 
+    def _fused(self, dev):
+        """{name: (W,)} of the walkers resident behind the handle ``dev``."""
+        names = list(self.symmetry_operators)
+        self.last_route = "fused"
+        if not names:
+            return {}
+        org = self._origins()
+        ops = np.stack([np.asarray(self.symmetry_operators[k], dtype=float) for k in names])
+        out = device_symmetry(dev, ops, None if org is None else np.stack([np.asarray(org[k], dtype=float) for k in names]))
+        return dict(zip(names, out))
+
     def __call__(self, configs, wf):
         dev = readonly_device(wf)
-        names = list(self.symmetry_operators)
         if dev is not None and dev.W == configs.configs.shape[0]:
             # the handle's resident walkers are `configs` (the drivers fetch them from the device before any host accumulator)
-            self.last_route = "fused"
-            if not names:
-                return {}
-            org = self._origins()
-            ops = np.stack([np.asarray(self.symmetry_operators[k], dtype=float) for k in names])
-            out = device_symmetry(dev, ops, None if org is None else np.stack([np.asarray(org[k], dtype=float) for k in names]))
-            return dict(zip(names, out))
+            return self._fused(dev)
         self.last_route = "protocol"
         return self._protocol(configs, wf)
+
+    def resident_scope(self, wf):
+        """None when ``avg_resident`` can run for ``wf``, else the reason (the fused route's rules)."""
+        if readonly_device(wf) is None:
+            return "the wave function is not a real Slater (x two-body Jastrow) product on one device handle"
+        return None
+
+    def avg_resident(self, wf, weights=None):
+        """The walker means for the walkers resident behind ``wf``, without a host container; with ``weights`` (W,) the weighted
+        means sum_w w_w ratio_w / sum_w w_w (nop W doubles come back, the weighting is done on the host)."""
+        why = self.resident_scope(wf)
+        if why is not None:
+            raise ValueError(f"{type(self).__name__}.avg_resident: {why}")
+        dev = readonly_device(wf)
+        if weights is not None:
+            weights = _ffi.walker_weights(weights, dev.W)
+        return {k: np.mean(v) if weights is None else np.dot(weights, v) / weights.sum() for k, v in self._fused(dev).items()}
 
     def _protocol(self, configs, wf):
         symmetry_observables = {}

@@ -108,9 +108,50 @@ class TBDMAccumulator:
                              "walkers are the configurations, and a real orbital evaluator on the same device")
         return dev if ok else None
 
-    def _sample(self, configs, wf):
-        ev, nconf = self.orbitals, configs.configs.shape[0]
-        dev = self._fused_device(configs, wf)
+    def resident_scope(self, wf):
+        """None when ``avg_resident`` can run for ``wf``, else the reason (the fused route's rules)."""
+        if self._route == "protocol":
+            return "the accumulator is bound to route='protocol'"
+        dev, ev = readonly_device(wf), self.orbitals.dev
+        if dev is None:
+            return "the wave function is not a real Slater (x two-body Jastrow) product on one device handle"
+        if ev.cplx or ev.twisted:
+            return "the orbital evaluator is complex"
+        if ev.device != dev.device:
+            return "the wave function and the evaluator are on different devices"
+        if tuple(dev.nelec) != tuple(self._mol.nelec):
+            return "the wave function has other electron numbers than the accumulator's system"
+        if min(len(e) for e in self._electrons) < 1:
+            return "a spin block of the sector is empty"
+        return None
+
+    def avg_resident(self, wf, weights=None):
+        """The walker mean for the walkers resident behind ``wf``, without a host container: the electrons' coordinates are gathered
+        on the device (``pqa_dm_points_resident``), the sweeps are those of the fused route, and with ``weights`` (W,) the three
+        means are the weighted ones sum_w w_w res_w / sum_w w_w (``pqa_dm_fetch_w``).  ``numpy.random`` is consumed as by
+        ``__call__``."""
+        why = self.resident_scope(wf)
+        if why is not None:
+            raise ValueError(f"TBDMAccumulator.avg_resident: {why}")
+        dev = readonly_device(wf)
+        nconf, scale = dev.W, 1.0 / self._nsweeps
+        if weights is not None:
+            weights = _ffi.walker_weights(weights, nconf)
+        self._sample(None, wf, resident=dev)
+        na, nb = self.orbitals.nmo()
+        shapes = ((self._ijkl.shape[1],), (na,), (nb,))
+        if weights is None:
+            out = [self.orbitals.fetch(i, nconf, sh, scale, True) for i, sh in enumerate(shapes)]
+        else:
+            out = [self.orbitals.fetch_w(i, nconf, sh, scale, weights) for i, sh in enumerate(shapes)]
+        return dict(zip(("value", "norm_a", "norm_b"), out))
+
+    def _sample(self, configs, wf, resident=None):
+        """One evaluation into the evaluator's accumulators.  ``resident``: the wave function's handle, whose resident walkers are
+        the configurations (no host container: fused route, coordinates gathered on the device)."""
+        ev = self.orbitals
+        nconf = configs.configs.shape[0] if resident is None else resident.W
+        dev = self._fused_device(configs, wf) if resident is None else resident
         self.last_route = "protocol" if dev is None else "fused"
         if self._walkers is None:
             naux = nconf if self._naux is None else self._naux
@@ -122,9 +163,13 @@ class TBDMAccumulator:
         for s, w in enumerate(self._walkers):
             kept.append(w.advance(s, self._nsweeps, self._tstep, keep=self._nsweeps)[1])
             pick.append(np.random.randint(0, len(w.x), size=(self._nsweeps, nconf)).astype(np.int32))  # after the walk (tbdm.py:156-161)
-        x = ev.true_positions(configs)
-        for s in (0, 1):
-            ev.points(s, s, x[:, self._electrons[s]])
+        if resident is None:
+            x = ev.true_positions(configs)
+            for s in (0, 1):
+                ev.points(s, s, x[:, self._electrons[s]])
+        else:
+            for s in (0, 1):
+                ev.points_resident(s, dev, self._electrons[s])
         cplx = False
         for sw in range(self._nsweeps if dev is not None else 0):  # the ratios stay on the device
             device_tbdm_sweep(dev, ev, sw, self._spin_sector, pick[0][sw], pick[1][sw], self._ijkl, sw == 0, self._walker_chunk)
