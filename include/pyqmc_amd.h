@@ -628,10 +628,28 @@ int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, const double* b
    not written; as pqa_energy the call syncs a lane-per-walker layout back and drops saved gradient_value rows, as pqa_wf_value it
    refreshes stale basis sums.  Real handles (open or periodic, one or more determinants, with or without the three-body factor,
    either ECP integrator); complex / twisted handles, a column of a factor the handle lacks, and moments beyond 256 MiB are refused
-   (<0): those go through the protocol route.  Orbital coefficients are not a source. */
+   (<0): those go through the protocol route.  Orbital coefficients are not a source here: pqa_sr_moments_orb below takes them. */
 int pqa_sr_moments(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff, const double* weights,
                    double threshold, const double* rot, const double* unif, uint64_t seed, double* en_mean, double* moments,
                    double* en_walker);
+
+/* pqa_sr_moments with the orbital coefficients as sources: everything above, and
+     src 4 mo_coeff_alpha, 5 mo_coeff_beta   pos: flat C-order index into (nao, nmo_s);
+     walker_chunk       walkers per chunk; 0: as many as keep a chunk's gathered columns and AO rows, (P + 2 + N nao) doubles per walker,
+                        within 256 MiB (a smaller value makes a small case run several chunks);
+     dp_walker (W, P)   host array or NULL: the compact derivative matrix dp the moments were formed from (tests and tools).
+   The derivative of walker w and spin s, G[a][m] = sum_u wu[u] sum_e ao[e][a] T_u[e][col_u(m)] with wu[u] the sum of
+   det_coeff[di] d_det[w][di] over the determinants whose spin-s part is u (Slater.pgradient, slater.py:507-533), is formed as
+   G = ao^T B with B[e][m] = sum_u wu[u] T_u[e][col_u(m)]: one fp64 matrix-core product per walker and spin whatever the number of
+   determinants (k_sr_orb), its entries stored straight into the selected columns.  No (W, nao, nmo) or (W N, nao) array exists:
+   the AO values are evaluated per walker chunk.  Sums run k-steps ascending, determinants ascending: two calls give the same bits.
+   Without a source 4 / 5 the result is pqa_sr_moments' bit for bit.  Writes go to scratch only, as there.  Orbital sources need a
+   real open-boundary handle with at most 64 electrons and 64 orbitals of the spin and at least one electron of it; periodic (per-k
+   parameter layout), complex and twisted handles, a pos outside (nao, nmo_s) or named twice are refused (<0): those go through the
+   protocol route. */
+int pqa_sr_moments_orb(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff, const double* weights,
+                       double threshold, const double* rot, const double* unif, uint64_t seed, int64_t walker_chunk, double* en_mean,
+                       double* moments, double* en_walker, double* dp_walker);
 
 /* ---- variance of the local energy at parameter sets (variance optimisation) ------------------------------------------------------ */
 /* optvariance.py:44-54 on the resident walkers, for K sets of two-body Jastrow coefficients acoeff (K,natom,na,2),

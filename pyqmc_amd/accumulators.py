@@ -11,7 +11,8 @@ Public names, argument meaning and returned keys are those of the reference's ``
   ``A^T B = [[dpidpj], [dpH], [dppsi]]``.  The per-walker derivatives come from ``wf.pgradient()`` (``k_pgrad_det``,
   ``k_pgrad_mo``, ``k_j3_pgrad``).
 * On the device route (``sr_route``) ``avg`` takes energy means and moments from ONE call on the resident state (``pqa_sr_moments``):
-  neither the walkers nor the derivative arrays come to the host.
+  neither the walkers nor the derivative arrays come to the host.  With ``route="device"`` the orbital coefficients of an open
+  system are columns too (``pqa_sr_moments_orb``: ``k_sr_orb`` writes them straight into the gathered matrix).
 """
 
 import numpy as np
@@ -116,6 +117,19 @@ def sr_columns(transform):
     return (np.concatenate(src), np.concatenate(pos)) if src else (np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))
 
 
+SR_ORBITAL_SOURCES = {"wf1mo_coeff_alpha": 4, "wf1mo_coeff_beta": 5}  # the further source codes of pqa_sr_moments_orb
+SR_MOMENT_BYTES = 256 << 20  # most bytes of the (P + 2, P) moments the device calls take
+
+
+def sr_columns_orb(transform):
+    """``sr_columns`` for a transform whose keys may include the orbital coefficients: ``(src, pos)`` of ``pqa_sr_moments_orb``,
+    ``pos`` of an orbital column the flat C-order index into its (nao, nmo_s) matrix."""
+    codes = {**SR_SOURCES, **SR_ORBITAL_SOURCES}
+    src = [np.full(len(p), codes[k], dtype=np.int32) for k, p in transform._pos.items()]
+    pos = [np.asarray(p, dtype=np.int32) for p in transform._pos.values()]
+    return (np.concatenate(src), np.concatenate(pos)) if src else (np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))
+
+
 def _sr_device(wf):
     """(device handle, None) when ``wf`` is ``generate_wf``'s product on one real handle, else (None, reason)."""
     from . import wf as pwf
@@ -137,7 +151,10 @@ def sr_route(wf, sr):
     """``("device", reason)`` when ``sr.avg`` can take its moments from the resident state (``pqa_sr_moments``), else
     ``("protocol", reason)``.  The device route needs: ``wf`` on one real device handle (``generate_wf``'s Slater x two-body Jastrow,
     with or without the three-body factor); ``sr.enacc`` a ``pyqmc_amd.EnergyAccumulator`` itself (not a subclass or a stand-in);
-    ``sr.transform`` a ``LinearTransform`` whose optimised keys are all among ``SR_SOURCES``; no injected ``gram``."""
+    ``sr.transform`` a ``LinearTransform`` whose optimised keys are all among ``SR_SOURCES``; no injected ``gram``.  The orbital
+    coefficients (``SR_ORBITAL_SOURCES``) are in the scope only when ``sr.route == "device"`` asks for them, and then for an open
+    system (no ``_fold``, no cell) with at most 64 electrons and orbitals of a spin and moments within ``SR_MOMENT_BYTES``; with
+    ``route=None`` they keep the protocol route."""
     from .energy import EnergyAccumulator
 
     dev, why = _sr_device(wf)
@@ -150,8 +167,22 @@ def sr_route(wf, sr):
     if type(sr.transform) is not LinearTransform:
         return "protocol", f"the transform is a {type(sr.transform).__name__}, not a pyqmc_amd.LinearTransform"
     other = [k for k in sr.transform.to_opt if k not in SR_SOURCES]
-    if other:
-        return "protocol", "parameters without a device source: " + ", ".join(other)
+    orbital = [k for k in other if k in SR_ORBITAL_SOURCES]
+    if len(orbital) < len(other):
+        return "protocol", "parameters without a device source: " + ", ".join(k for k in other if k not in orbital)
+    if orbital:
+        if sr.route != "device":
+            return "protocol", "orbital coefficients (" + ", ".join(orbital) + ") are device columns only on request: route='device' takes them"
+        from .wf import orbital_sr_scope
+
+        why = orbital_sr_scope(dev)
+        if why is None and getattr(wf.wf_factors[0], "_fold", None) is not None:
+            why = "orbital coefficients in the per-k parameter layout (the chain rule of pbc.unfold_mo_gradient)"
+        p = sr.transform.nparams
+        if why is None and (p + 2) * p * 8 > SR_MOMENT_BYTES:
+            why = f"the moments of {p} parameters exceed the {SR_MOMENT_BYTES >> 20} MiB the device call takes"
+        if why:
+            return "protocol", why
     if sr.transform.nparams == 0:
         return "protocol", "no parameter is optimised"
     return "device", "one real device handle, device energy, every parameter has a device source"
@@ -203,7 +234,7 @@ class StochasticReconfiguration:
     def avg_resident(self, wf, weights=None):
         """``avg`` on the device route for the walkers resident behind ``wf``, without comparing them with a host container: binds
         the energy object, advances its call count and derives the key of the energy draws as ``EnergyAccumulator.__call__`` does,
-        then one ``pqa_sr_moments`` call."""
+        then one ``pqa_sr_moments`` call (``pqa_sr_moments_orb`` when orbital coefficients are optimised)."""
         from .energy import KEYS
 
         dev, why = _sr_device(wf)
@@ -213,9 +244,10 @@ class StochasticReconfiguration:
         enacc.bind(dev)
         enacc._calls += 1
         key = int(np.random.randint(0, 2**31 - 1)) if enacc.seed is None else enacc.seed + enacc._calls
-        src, pos = sr_columns(self.transform)
+        orbital = any(k in SR_ORBITAL_SOURCES for k in self.transform.to_opt)
+        src, pos = (sr_columns_orb if orbital else sr_columns)(self.transform)
         # the reference regularises with the default cut-off in avg (:105)
-        en, m = dev.sr_moments(src, pos, 1e-3, weights=weights, threshold=enacc.threshold, seed=key)
+        en, m = (dev.sr_moments_orb if orbital else dev.sr_moments)(src, pos, 1e-3, weights=weights, threshold=enacc.threshold, seed=key)
         self.last_route = "device"
         d = {k: en[i] for i, k in enumerate(KEYS)}
         d["dpidpj"], d["dpH"], d["dppsi"] = m[:-2], m[-2], m[-1]

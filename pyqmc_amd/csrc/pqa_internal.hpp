@@ -165,8 +165,8 @@ struct pqa_handle {
   // pqa_add_* (pqa_add.hip), on the first handle of the call: one sweep's tapes, the (K, W) weights, the old-position drift, acceptance
   // counts and per-sweep fractions; or the weights and the six combined energy rows
   DevBuf b_add;
-  // pqa_sr_moments (pqa_sr.hip): the running moments, energy means, weights, a walker chunk's gathered matrix and scales, the slices'
-  // partial tiles, the column description
+  // pqa_sr_moments / pqa_sr_moments_orb (pqa_sr.hip): the running moments, energy means, weights, a walker chunk's gathered matrix and
+  // scales, the slices' partial tiles, the column description and the orbital columns' inverse map
   DevBuf b_sr;
   // pqa_obdm_sweeps (pqa_obdm.hip), on the evaluator's handle in the mean mode: a walker chunk's panels T, B and norm terms, the slices'
   // partial tiles, the running sums and their scaled copy

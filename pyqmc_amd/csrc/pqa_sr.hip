@@ -16,6 +16,15 @@
 //                    the upper one (dpidpj is exactly symmetric), added to the running moments of the chunks before;
 //   k_sr_means       the six weighted energy means, a fixed-order tree.
 // Only the (P + 2) x P moments and the six means leave the device (and the (W, 6) per-walker energies when the caller asks for them).
+//
+// pqa_sr_moments_orb adds the orbital coefficients as sources (4: mo_coeff_alpha, 5: mo_coeff_beta).  Their derivative
+//   G[a][m] = sum_u wu[u] sum_e ao[e][a] T_u[e][col_u(m)],   wu[u] = sum_{di: det_map[di] = u} det_coeff[di] d_det[di]
+// (k_pgrad_mo) never exists as a (W, nao, nmo) array: the AO values do not depend on u, so per walker and spin
+//   B[e][m] = sum_u wu[u] T_u[e][col_u(m)]   (n x nmo, zero where u does not occupy m),   G = ao^T B.
+//   launch_ao        value-only AO rows of the chunk's electrons (b_ao: the chunk's (Wc N, nao) rows, nothing of size W N nao);
+//   k_sr_orb         a block per walker: wu and B in LDS, G tile by tile on v_mfma_f64_16x16x4_f64, every entry stored through the
+//                    inverse column map colof straight into the chunk's A (entries nobody optimises are dropped);
+//   k_sr_gather      then fills the other columns and leaves the orbital ones alone.
 #include "pqa_estim.hpp"
 
 namespace {
@@ -61,7 +70,7 @@ __global__ __launch_bounds__(256) void k_sr_means(const double* __restrict__ en 
 }
 
 // One thread per (walker of the chunk, column of A): A[w][i] = derivative column i (i < P), the local energy (P), 1 (P + 1); the
-// thread of column 0 also writes the walker's scale.
+// thread of column 0 also writes the walker's scale.  Orbital-coefficient columns (src > 3) are k_sr_orb's and are left alone.
 __global__ __launch_bounds__(256) void k_sr_gather(SrSources S, const int* __restrict__ src, const int* __restrict__ pos, int P,
                                                    const double* __restrict__ en /*[6][W]*/, const double* __restrict__ wts,
                                                    const double* __restrict__ wsum, double cutoff, long W, long w0, long Wc,
@@ -72,13 +81,89 @@ __global__ __launch_bounds__(256) void k_sr_gather(SrSources S, const int* __res
   const long bw = idx / lda, w = w0 + bw;
   const int i = (int)(idx - bw * lda);
   double v;
+  bool mine = true;
   if (i < P) {
     const int s = src[i];
-    v = S.base[s][(size_t)w * S.stride[s] + pos[i]];
+    mine = s <= 3;
+    v = mine ? S.base[s][(size_t)w * S.stride[s] + pos[i]] : 0.0;
   } else
     v = i == P ? en[5 * W + w] : 1.0;
-  A[idx] = v;
+  if (mine) A[idx] = v;
   if (i == 0) scale[bw] = sr_weight(wts, wsum, W, w) * sr_nodal_f(en[4 * W + w], cutoff);
+}
+
+// doubles per row of B in LDS: whole 16-column tiles, and = 16 mod 32, so that rows kq and kq + 1 of an operand read (the two rows
+// of a half-wave's ds_read_b64) land in different halves of the 64 banks
+inline int sr_orb_ldb(int nmo) {
+  const int mp = (nmo + 15) / 16 * 16;
+  return mp % 32 == 16 ? mp : mp + 16;
+}
+
+// Orbital-coefficient columns of spin s for the walkers w0 .. of a chunk: grid = (walkers of the chunk), block = 64 x (waves: the
+// 16-row AO tiles, at most 4).  LDS: B [kpad][ldb] (kpad: n in whole k-steps of 4; the padding is zero), wu [ndet_s].
+//   wu, B     as k_pgrad_mo forms its weights; determinants ascending;
+//   G = ao^T B  a wave owns an AO tile a0 and all (at most 4) orbital tiles: per k-step lane (i16, kq) loads ao[e0 + kq][a0 + i16] once
+//             (coalesced along a) and B[e0 + kq][m0 + i16] per orbital tile; k-steps ascending.  The lane holds D[a0 + kq + 4 r][m0 + i16];
+//   store     A[bw][colof[a nmo + m]] where the map names a column.
+// ao: the chunk's AO rows [Wc N][nao]; d_det [W][ndet]; colmap [ndet_s][nmo]; colof [nao][nmo].
+__global__ __launch_bounds__(256) void k_sr_orb(SysDev S, SlaterState st, int s, const double* __restrict__ ao, const double* __restrict__ d_det,
+                                                const int* __restrict__ colmap, const int* __restrict__ colof, long w0, int lda, int ldb,
+                                                double* __restrict__ A) {
+  extern __shared__ double sr_orb_lds[];
+  const long bw = blockIdx.x, w = w0 + bw;
+  const int n = s ? S.ndn : S.nup, D = S.ndet_s[s], nmo = S.nmo[s], nao = S.nao;
+  const int kpad = (n + 3) & ~3, nmt = (nmo + 15) >> 4, nat = (nao + 15) >> 4;
+  double* B = sr_orb_lds;
+  double* wu = B + kpad * ldb;
+  for (int u = threadIdx.x; u < D; u += blockDim.x) {
+    double acc = 0.0;
+    for (int di = 0; di < S.ndet; ++di)
+      if (S.det_map[s * S.ndet + di] == u) acc += S.det_coeff[di] * d_det[w * S.ndet + di];
+    wu[u] = acc;
+  }
+  __syncthreads();
+  const double* Tw = st.T[s] + (size_t)w * D * n * n;
+  for (int idx = threadIdx.x; idx < kpad * ldb; idx += blockDim.x) {
+    const int e = idx / ldb, m = idx - e * ldb;
+    double acc = 0.0;
+    if (e < n && m < nmo)
+      for (int u = 0; u < D; ++u) {
+        const int col = colmap[u * nmo + m];
+        if (col >= 0) acc += wu[u] * Tw[((size_t)u * n + e) * n + col];
+      }
+    B[idx] = acc;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6, i16 = lane & 15, kq = lane >> 4;
+  const double* aow = ao + ((size_t)bw * S.nelec + (size_t)s * S.nup) * nao;
+  double* Aw = A + (size_t)bw * lda;
+  for (int at = wave; at < nat; at += nwave) {
+    const int a = at * 16 + i16;
+    d4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = d4{0.0, 0.0, 0.0, 0.0};
+    for (int e0 = 0; e0 < kpad; e0 += 4) {
+      const int e = e0 + kq;
+      const double av = (a < nao && e < n) ? aow[(size_t)e * nao + a] : 0.0;
+      const double* brow = B + e * ldb + i16;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < nmt) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, brow[16 * j], acc[j], 0, 0, 0);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j >= nmt) continue;
+      const int m = 16 * j + i16;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int ar = at * 16 + kq + 4 * r;
+        if (ar < nao && m < nmo) {
+          const int c = colof[ar * nmo + m];
+          if (c >= 0) Aw[c] = acc[j][r];
+        }
+      }
+    }
+  }
 }
 
 // part[sl] (P + 2, P) += tile (32 bi .., 32 bj ..) of A^T diag(s) A[:, :P] over the walkers of slice sl.  grid = (column blocks,
@@ -145,24 +230,48 @@ __global__ __launch_bounds__(256) void k_sr_reduce(const double* __restrict__ pa
 
 }  // namespace
 
-extern "C" int pqa_sr_moments(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff, const double* weights,
-                              double threshold, const double* rot, const double* unif, uint64_t seed, double* en_mean, double* moments,
-                              double* en_walker) {
+// Both entries.  fn: the entry's name (its messages); orb: sources 4 / 5 are accepted; chunk: walkers per chunk (0: the scratch rule);
+// dp_walker: host (W, P) or NULL.
+static int sr_moments(pqa_handle_t* h, const std::string& fn, bool orb, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff,
+               const double* weights, double threshold, const double* rot, const double* unif, uint64_t seed, long chunk, double* en_mean,
+               double* moments, double* en_walker, double* dp_walker) {
   // argument checks first: they need nothing but the handle's host-side sizes
-  if (P < 1) FAIL("pqa_sr_moments: P must be at least 1");
-  if (!src || !pos || !en_mean || !moments) FAIL("pqa_sr_moments: src, pos, en_mean and moments must not be NULL");
-  if (!(nodal_cutoff > 0.0)) FAIL("pqa_sr_moments: nodal_cutoff must be positive");
-  if (h->cplx) FAIL("pqa_sr_moments: complex orbitals / twisted cell (outside the device scope: use the protocol route)");
+  if (P < 1) FAIL(fn + ": P must be at least 1");
+  if (!src || !pos || !en_mean || !moments) FAIL(fn + ": src, pos, en_mean and moments must not be NULL");
+  if (!(nodal_cutoff > 0.0)) FAIL(fn + ": nodal_cutoff must be positive");
+  if (h->cplx) FAIL(fn + ": complex orbitals / twisted cell (outside the device scope: use the protocol route)");
   const long size[4] = {h->has_slater ? (long)h->ndet : 0, h->has_j2 ? (long)h->natom * h->na * 2 : 0, h->has_j2 ? (long)h->nb * 3 : 0,
                         h->has_j3 ? (long)h->natom * h->na3 * h->na3 * h->nb3 * 3 : 0};
   bool need[4] = {false, false, false, false};
+  bool orb_spin[2] = {false, false};
+  std::vector<int> colof[2];  // [nao][nmo_s]: the column of A an orbital-coefficient entry fills, or -1
   for (int i = 0; i < P; ++i) {
-    if (src[i] < 0 || src[i] > 3) FAIL("pqa_sr_moments: src must be 0 (det_coeff), 1 (acoeff), 2 (bcoeff) or 3 (ccoeff)");
-    if (pos[i] < 0 || pos[i] >= size[src[i]]) FAIL("pqa_sr_moments: pos outside the parameter src names (or the handle has no such factor)");
+    if (orb && (src[i] == 4 || src[i] == 5)) {
+      const int s = src[i] - 4, n = s ? h->ndn : h->nup;
+      const char* why = !h->has_slater                ? "the handle has no Slater factor"
+                        : h->twist                     ? "twisted cell"
+                        : h->S.pbc != 0                ? "periodic cell (per-k parameter layout)"
+                        : n == 0                       ? "a spin without electrons"
+                        : (n > 64 || h->nmo[s] > 64)   ? "more than 64 electrons or orbitals of a spin"
+                                                       : nullptr;
+      if (why) FAIL(fn + ": orbital coefficients: " + why + " (outside the device scope: use the protocol route)");
+      if (pos[i] < 0 || pos[i] >= (long)h->nao * h->nmo[s]) FAIL(fn + ": pos outside the (nao, nmo) orbital coefficients src names");
+      if (colof[s].empty()) colof[s].assign((size_t)h->nao * h->nmo[s], -1);
+      if (colof[s][pos[i]] >= 0) FAIL(fn + ": an orbital coefficient is named twice");
+      colof[s][pos[i]] = i;
+      orb_spin[s] = true;
+      continue;
+    }
+    if (src[i] < 0 || src[i] > 3)
+      FAIL(fn + (orb ? ": src must be 0 (det_coeff), 1 (acoeff), 2 (bcoeff), 3 (ccoeff), 4 (mo_coeff_alpha) or 5 (mo_coeff_beta)"
+                     : ": src must be 0 (det_coeff), 1 (acoeff), 2 (bcoeff) or 3 (ccoeff)"));
+    if (pos[i] < 0 || pos[i] >= size[src[i]]) FAIL(fn + ": pos outside the parameter src names (or the handle has no such factor)");
     need[src[i]] = true;
   }
+  const bool has_orb = orb_spin[0] || orb_spin[1];
+  if (chunk < 0) FAIL(fn + ": walker_chunk must not be negative");
   const size_t nmom = (size_t)(P + 2) * P;
-  if (nmom * sizeof(double) > kChunkScratchBytes) FAIL("pqa_sr_moments: the (P + 2) x P moments exceed the 256 MiB scratch limit (use the protocol route)");
+  if (nmom * sizeof(double) > kChunkScratchBytes) FAIL(fn + ": the (P + 2) x P moments exceed the 256 MiB scratch limit (use the protocol route)");
   if (h->W == 0) FAIL("state not initialised (call pqa_wf_recompute)");
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
@@ -172,7 +281,7 @@ extern "C" int pqa_sr_moments(pqa_handle_t* h, int P, const int32_t* src, const 
   const double* d_en = (const double*)h->b_en.p;
   // derivative sources
   SrSources S{};
-  if (need[0]) {
+  if (need[0] || has_orb) {  // (the orbital columns need d_det for the determinant weights)
     TRY(slater_value_dev(h));  // sign / log of the determinant expansion -> b_sign, b_log
     TRY(ensure(h, h->b_pgdet, (size_t)W * h->ndet * sizeof(double)));
     hipLaunchKernelGGL((k_pgrad_det<>), dim3((unsigned)((W * h->ndet + 255) / 256)), dim3(256), 0, h->stream, h->S, h->st,
@@ -195,15 +304,24 @@ extern "C" int pqa_sr_moments(pqa_handle_t* h, int P, const int32_t* src, const 
     S.base[3] = (const double*)h->b_out.p; S.stride[3] = size[3];
   }
   // scratch: [moments | means (6) | weight sum (1) | weights (W) | per-walker energies (W, 6) | scale (Wc) | A (Wc, P + 2) |
-  // partials (nslice, P + 2, P) | src, pos]
+  // partials (nslice, P + 2, P) | src, pos | colof of each spin]; with orbital columns a chunk's A and AO rows (b_ao) together stay
+  // within the chunk limit
   const int lda = P + 2;
-  const long Wc = walker_chunk(W, (size_t)lda * sizeof(double));
+  long Wc = walker_chunk(W, ((size_t)lda + (has_orb ? (size_t)h->N * h->nao : 0)) * sizeof(double));
+  if (chunk > 0) Wc = std::min(Wc, chunk);
+  size_t orb_lds[2] = {0, 0};
+  for (int s = 0; s < 2; ++s)
+    if (orb_spin[s]) {
+      const int n = s ? h->ndn : h->nup;
+      orb_lds[s] = ((size_t)((n + 3) & ~3) * sr_orb_ldb(h->nmo[s]) + h->ndet_s[s]) * sizeof(double);
+      if (orb_lds[s] > 150 * 1024) FAIL(fn + ": orbital coefficients: the determinant weights of one walker do not fit LDS (use the protocol route)");
+    }
   const int nbi = (lda + 31) / 32, nbj = (P + 31) / 32;
   long nslice = std::min<long>(std::max<long>(1, 1024 / ((long)nbi * nbj)), std::max<long>(1, Wc / 64));
   nslice = std::max<long>(1, std::min<long>(nslice, (long)(kChunkScratchBytes / (nmom * sizeof(double)))));
   const size_t nw = weights ? (size_t)W : 0, nenw = en_walker ? (size_t)6 * W : 0;
   const size_t ndbl = nmom + 6 + 1 + nw + nenw + (size_t)Wc + (size_t)Wc * lda + (size_t)nslice * nmom;
-  TRY(ensure(h, h->b_sr, ndbl * sizeof(double) + (size_t)2 * P * sizeof(int)));
+  TRY(ensure(h, h->b_sr, ndbl * sizeof(double) + ((size_t)2 * P + colof[0].size() + colof[1].size()) * sizeof(int)));
   double* d_mom = (double*)h->b_sr.p;
   double* d_mean = d_mom + nmom;
   double* d_wsum = d_mean + 6;
@@ -216,6 +334,9 @@ extern "C" int pqa_sr_moments(pqa_handle_t* h, int P, const int32_t* src, const 
   int* d_pos = d_src + P;
   TRY(copy_in(h, d_src, src, (size_t)P * sizeof(int)));
   TRY(copy_in(h, d_pos, pos, (size_t)P * sizeof(int)));
+  int* d_colof[2] = {d_pos + P, d_pos + P + colof[0].size()};
+  for (int s = 0; s < 2; ++s) TRY(copy_in(h, d_colof[s], colof[s].data(), colof[s].size() * sizeof(int)));
+  if (has_orb) TRY(ensure(h, h->b_ao, (size_t)Wc * h->N * h->nao * sizeof(double)));
   const double* wts = nullptr;
   if (weights) {
     TRY(copy_in(h, d_wts, weights, (size_t)W * sizeof(double)));
@@ -229,9 +350,26 @@ extern "C" int pqa_sr_moments(pqa_handle_t* h, int P, const int32_t* src, const 
     const long wc = std::min(Wc, W - w0);
     const long ns = std::min<long>(nslice, std::max<long>(1, wc / 64));
     const long per = ((wc + ns - 1) / ns + kSrKB - 1) / kSrKB * kSrKB;  // walkers per slice, whole staging steps
+    if (has_orb) {
+      TRY(launch_ao(h, plain_points(h->js.x + (size_t)w0 * h->N * 3, wc * h->N), wc * h->N, 1, (double*)h->b_ao.p));
+      const unsigned nwave = (unsigned)std::min(4, (h->nao + 15) / 16);
+      for (int s = 0; s < 2; ++s) {
+        if (!orb_spin[s]) continue;
+        if (orb_lds[s] > 64 * 1024) TRY(raise_lds_limit(h, reinterpret_cast<const void*>(k_sr_orb)));
+        hipLaunchKernelGGL(k_sr_orb, dim3((unsigned)wc), dim3(64 * nwave), orb_lds[s], h->stream, h->S, h->st, s, (const double*)h->b_ao.p,
+                           (const double*)h->b_pgdet.p, (const int*)h->d_colmap[s], (const int*)d_colof[s], w0, lda, sr_orb_ldb(h->nmo[s]),
+                           d_A);
+        TRY(check_launch(h, "k_sr_orb"));
+      }
+    }
     hipLaunchKernelGGL(k_sr_gather, dim3((unsigned)((wc * lda + 255) / 256)), dim3(256), 0, h->stream, S, (const int*)d_src,
                        (const int*)d_pos, P, d_en, wts, (const double*)d_wsum, nodal_cutoff, W, w0, wc, d_A, d_scale);
     TRY(check_launch(h, "k_sr_gather"));
+    if (dp_walker) {  // the chunk's dp = A[:, :P], before the next chunk overwrites it
+      HIPCHK(hipMemcpy2DAsync(dp_walker + (size_t)w0 * P, (size_t)P * sizeof(double), d_A, (size_t)lda * sizeof(double),
+                              (size_t)P * sizeof(double), (size_t)wc, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+    }
     hipLaunchKernelGGL(k_sr_syrk, dim3((unsigned)nbj, (unsigned)nbi, (unsigned)ns), dim3(256), 0, h->stream, (const double*)d_A,
                        (const double*)d_scale, wc, P, per, d_part);
     TRY(check_launch(h, "k_sr_syrk"));
@@ -246,4 +384,18 @@ extern "C" int pqa_sr_moments(pqa_handle_t* h, int P, const int32_t* src, const 
     TRY(copy_in(h, en_walker, d_enw, (size_t)6 * W * sizeof(double)));
   }
   return copy_out(h, en_mean, d_mean, 6 * sizeof(double));
+}
+
+extern "C" int pqa_sr_moments(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff, const double* weights,
+                              double threshold, const double* rot, const double* unif, uint64_t seed, double* en_mean, double* moments,
+                              double* en_walker) {
+  return sr_moments(h, "pqa_sr_moments", false, P, src, pos, nodal_cutoff, weights, threshold, rot, unif, seed, 0, en_mean, moments, en_walker,
+                    nullptr);
+}
+
+extern "C" int pqa_sr_moments_orb(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff, const double* weights,
+                                  double threshold, const double* rot, const double* unif, uint64_t seed, int64_t walker_chunk,
+                                  double* en_mean, double* moments, double* en_walker, double* dp_walker) {
+  return sr_moments(h, "pqa_sr_moments_orb", true, P, src, pos, nodal_cutoff, weights, threshold, rot, unif, seed, (long)walker_chunk, en_mean,
+                    moments, en_walker, dp_walker);
 }

@@ -311,6 +311,35 @@ class DeviceWF:
                   _ffi.ptr(unif), int(seed), _ffi.ptr(en_mean), _ffi.ptr(moments), _ffi.ptr(en_walker))
         return (en_mean, moments, en_walker) if per_walker else (en_mean, moments)
 
+    def sr_moments_orb(self, src, pos, nodal_cutoff, weights=None, threshold=10.0, rot=None, unif=None, seed=0, per_walker=False,
+                       walker_chunk=0, dp_walker=False):
+        """``pqa_sr_moments_orb``: ``sr_moments`` with the orbital coefficients as sources 4 (mo_coeff_alpha) and 5 (mo_coeff_beta),
+        ``pos`` the flat C-order index into (nao, nmo_s).  ``walker_chunk``: walkers per chunk (0: by the scratch limit);
+        ``dp_walker``: also return the (W, P) derivative matrix the moments were formed from.
+        Returns (en_mean, moments[, en_walker with ``per_walker``][, dp with ``dp_walker``]).  Orbital sources on a periodic, complex or
+        twisted handle, or with more than 64 electrons / orbitals of a spin, raise ``NotImplementedError`` (the protocol route takes
+        those)."""
+        src, pos = np.ascontiguousarray(src, dtype=np.int32), np.ascontiguousarray(pos, dtype=np.int32)
+        P = len(src)
+        if src.shape != (P,) or pos.shape != (P,):
+            raise ValueError(f"src and pos must be one-dimensional and equally long, got {src.shape}, {pos.shape}")
+        if np.any(src >= 4):
+            why = orbital_sr_scope(self)
+            if why:
+                raise NotImplementedError(f"sr_moments_orb: {why} (use the protocol route)")
+        w = None if weights is None else _ffi.f64(weights)
+        if w is not None and w.shape != (self.W,):
+            raise ValueError(f"weights ({self.W},) expected, got {w.shape}")
+        rot = None if rot is None else _ffi.f64(rot)
+        unif = None if unif is None else _ffi.f64(unif)
+        en_mean, moments = np.empty(6), np.empty((P + 2, P))
+        en_walker = np.empty((self.W, 6)) if per_walker else None
+        dp = np.empty((self.W, P)) if dp_walker else None
+        self.call("pqa_sr_moments_orb", int(P), _ffi.ptr(src), _ffi.ptr(pos), float(nodal_cutoff), _ffi.ptr(w), float(threshold),
+                  _ffi.ptr(rot), _ffi.ptr(unif), int(seed), int(walker_chunk), _ffi.ptr(en_mean), _ffi.ptr(moments), _ffi.ptr(en_walker),
+                  _ffi.ptr(dp))
+        return (en_mean, moments) + ((en_walker,) if per_walker else ()) + ((dp,) if dp_walker else ())
+
     def variance(self, acoeff, bcoeff, eoff, grad=False, ke=False):
         """``pqa_variance``: population variance over the resident walkers of ``eoff + ke_k`` at K sets of two-body Jastrow
         coefficients, acoeff (K, natom, na, 2) and bcoeff (K, nb, 3), with ``eoff`` (W) the fixed part of the local energy ->
@@ -611,6 +640,17 @@ def _testvalue_many(dev, factors, e, epos, mask):
     if len(pts) and len(es):
         dev.call("pqa_testvalue_many", _ffi.ptr(es), len(es), _ffi.ptr(pts), len(pts), _ffi.ptr(widx), int(factors), _ffi.ptr(out))
     return out if cplx else np.real(out)
+
+
+def orbital_sr_scope(dev):
+    """None when the handle ``dev`` can form orbital-coefficient columns on the device (``pqa_sr_moments_orb``), else the reason."""
+    if dev.cplx or dev.twisted:
+        return "complex orbitals / twisted cell"
+    if getattr(dev, "pbc", False):
+        return "orbital coefficients of a periodic cell (per-k parameter layout, the chain rule of pbc.unfold_mo_gradient)"
+    if max(max(dev.nelec), max(dev.nmo)) > 64:
+        return f"orbital coefficients with more than 64 electrons or orbitals of a spin ({dev.nelec}, {dev.nmo})"
+    return None
 
 
 def orbital_inputs(mol, mf, determinants=None, with_fold=False):
