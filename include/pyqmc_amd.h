@@ -612,6 +612,24 @@ int pqa_ewald2d(pqa_handle_t* h, const pqa_ewald2d_t* tab, int mean, double* ee,
 int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, const double* bcoeff, double threshold, const double* rot,
                    const double* unif, uint64_t seed, double* logpsi, double* en);
 
+/* The same evaluation for one or more determinants, with the determinant coefficients varying between the sets as well
+   (correlated_compute_worker, linemin.py:378-409, for the Slater.parameters["det_coeff"] of slater.py:301-380 and
+   determinant_tools.compute_value, determinant_tools.py:74-88): det_coeff (K, ndet), acoeff (K, natom, na, 2), bcoeff (K, nb, 3);
+   NULL for a coefficient array means that every set uses the handle's own.  Row k equals, within rounding, upload set k's
+   det_coeff / acoeff / bcoeff; pqa_wf_recompute -> logpsi[k]; pqa_energy(threshold, rot, unif, seed) -> en[k] (6, W: ke, ee, ei,
+   ecp, grad2, total).  The Slater factor is linear in det_coeff and nothing about a determinant changes between the sets: with
+   omega_d the weight of determinant d without its coefficient and rho_u the row products of unique determinant u (gradient,
+   laplacian, ECP point), set k has S_k = sum_d c_kd omega_d, grad D / D = sum_d c_kd omega_d rho_u(d) / S_k, and
+   logpsi[k] = log|Psi| - log|S_0| + log|S_k| - U_0 + U_k.  One Slater-only energy pass supplies Coulomb / Ewald, the local ECP
+   channel and the ECP point lists with their orbital rows; the determinant sums of all sets are one product per walker on the fp64
+   matrix cores (k_corr_md, csrc/pqa_correlated.hip), the Jastrow part is pqa_correlated's.  Every sum has a fixed order: two calls
+   give the same bits, and the result does not depend on walker_chunk (walkers per output chunk; 0: at most 256 MiB).  Writes as
+   pqa_correlated: none to the walkers, inverses, determinants or coefficients.  Real Slater x two-body Jastrow handles, open or
+   periodic (untwisted), no three-body factor, the semi-local ECP integrator or no ECP; anything else, and an LDS plan that does
+   not fit, is refused. */
+int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff, const double* acoeff, const double* bcoeff, double threshold,
+                      const double* rot, const double* unif, uint64_t seed, long walker_chunk, double* logpsi, double* en);
+
 /* ---- stochastic-reconfiguration moments from the resident state ----------------------------------- */
 /* StochasticReconfiguration.avg (stochastic_reconfiguration.py:49-118) on the resident walkers, without the walkers or the
    derivative arrays crossing the bus.  Column i of the serialised derivative matrix dp (W, P) is entry pos[i] (flat C-order index)

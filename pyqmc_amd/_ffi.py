@@ -145,6 +145,8 @@ _PROTOTYPES = {
     "pqa_ewald2d": (C.c_int, [_H, C.POINTER(Ewald2dTab), C.c_int, C.c_void_p, C.c_void_p]),
     "pqa_correlated": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                  C.c_void_p]),
+    "pqa_correlated_md": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_uint64, C.c_long,
+                                    C.c_void_p, C.c_void_p]),
     "pqa_sr_moments": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_uint64,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "pqa_sr_moments_orb": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_uint64,

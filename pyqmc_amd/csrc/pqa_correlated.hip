@@ -12,6 +12,7 @@
 //                   ke_k = -1/2 sum_e [lap D/D + 2 grad D/D . grad U_k + lap U_k + |grad U_k|^2],  grad2_k = sum_e |grad D/D + grad U_k|^2,
 //                   ecp_k = local + sum_q s_q exp(dU_k(q)),  total_k = ke_k + ee + ei + ecp_k + ii.
 // The handle's coefficients are never changed.  Outputs are written per walker chunk of at most 256 MiB.
+// Several determinants, with det_coeff varying between the sets too: pqa_correlated_md / k_corr_md, further down.
 #include "pqa_estim.hpp"
 
 namespace {
@@ -93,6 +94,248 @@ __global__ __launch_bounds__(64) void k_corr_energy(SysDev S, SlaterState st, Ja
   o[0] = ke; o[A.Wc] = ee; o[2 * A.Wc] = ei; o[3 * A.Wc] = ec; o[4 * A.Wc] = g2; o[5 * A.Wc] = ke + ee + ei + ec + A.ii;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Several determinants (pqa_correlated_md): det_coeff varies between the sets as well.  Nothing about a determinant changes between
+// the sets, the Slater factor is linear in det_coeff and U in acoeff / bcoeff.  For walker w and full determinant d with unique spin
+// determinants u_up(d), u_dn(d) (det_map):
+//   omega_d      = sign_up sign_dn exp(log_up + log_dn - ref)            det_weight (pqa_slater.hpp) without det_coeff[d], ref = det_ref
+//   rho_u[e][c]  = sum_j cache[w][i][c][occ_u[j]] T_u[i][j]              electron e = (spin s, index i), unique determinant u of s,
+//                                                                        c = value, d/dx, d/dy, d/dz, laplacian (slater_ratios<5>'s
+//                                                                        products before it mixes determinants); for an ECP point q
+//                                                                        of e the same with the point's orbital row b_emo[s][q][.]
+// and for set k with determinant coefficients c_k, S_k = sum_d c_kd omega_d:
+//   G_k[e][c]    = sum_d c_kd omega_d rho_{u_s(d)}[e][c] / S_k           grad D / D (c = x, y, z) and lap D / D of set k; the kernel
+//                                                                        divides by the value component's sum instead of S_k, the
+//                                                                        quotient ke_electron and the reference's gradient_laplacian
+//                                                                        form: rho[value] = 1 for an exact inverse, and where a sweep's
+//                                                                        rank-1 updates left rounding in T the quotient cancels it
+//   r_k(q)       = sum_d c_kd omega_d rho_{u_s(d)}(q) / S_k              Slater ratio Psi_S,k(e -> q) / Psi_S,k
+//   log|Psi_k|   = log|Psi| - log|S_0| + log|S_k| - U_0 + U_k            0: the handle's own coefficients (column K of the matrices)
+//   lap_e        = G_k[e][lap] + lap U_k + |grad U_k|^2 + 2 G_k[e][xyz] . grad U_k,   ke_k = -1/2 sum_e lap_e,
+//   grad2_k      = sum_e |G_k[e][xyz] + grad U_k|^2,   ecp_k = local + sum_q wgt_q r_k(q) exp(dU_k(q)),   ee, ei, ii as they are.
+// The determinant part is one product ((5 N + npts) x ndet) . (ndet x K) per walker, the only cost that grows as ndet K: it runs on
+// v_mfma_f64_16x16x4_f64.
+//
+// k_corr_md: one wave per walker (grid.x), set columns kb .. kb + 63 (grid.y).  One wave, not four: the Jastrow rows come from
+// jas_rows / jas_diff_rows, the one-wave helpers k_corr_energy and k_var_ke share.
+//   phase 0  omega_d into LDS (det_ref first); lane = set: S_k, determinants ascending.
+//   per tile of 16 electrons (both spins in index order) or 16 ECP points of one list segment:
+//   phase 1  rho_u[row][c] for every unique determinant of the row's spin on the vector unit (slots ascending), into LDS
+//            [row][c][u], row stride = 2 mod 32 doubles: the 16 rows x 2 k-steps a half-wave reads lie 32 banks apart;
+//   phase 2  num[c][row][k] = sum_d (omega_d rho_{u(d)}[row][c]) C[d][k] through mfma_tiles / mfma_tile: the A operand is gathered
+//            through det_map on load (zero beyond ndet and the row tail), the B operand is the coefficient matrix in L2 (zero
+//            beyond K); the five component accumulators of a tile are independent; the tile goes to LDS [c][row][column] for the
+//            transpose to lane = set;
+//   phase 3  per row the Jastrow rows and their contraction with ct, one set per lane, combined with num[c] / num[value] (an
+//            electron) or num / S_k (a point) as above; the ECP
+//            points in k_ecp_sum's order (spin up then down, segment by segment, points ascending).
+// Every sum has a fixed order (k-steps, determinants, electrons, points ascending): two calls give the same bits, whatever the chunk.
+struct CorrMdArgs {
+  long w0, Wc, W;           // first walker of the chunk, walkers in it, resident walkers
+  int K, K1, P, Pa;         // sets, columns of cd (K + 1), Jastrow coefficients per set, of which acoeff
+  int DP, RS, GS;           // LDS strides: unique determinants of a component, a row of rho (= 2 mod 32), a row of num
+  const double* ct;         // [P][K] Jastrow coefficient matrix
+  const double* cd;         // [ndet][K1] determinant coefficient matrix (column K: the handle's own)
+  const double* kc;         // [4][W] rows ke, ee, ei, grad2 of the Slater-only pass (ee, ei used)
+  const double* local;      // [W] local ECP channel
+  const double* wgt[2];     // per spin: point weights
+  const double* emo[2];     // per spin: orbital rows of the points [n][nmo_s]
+  const double* pts[2];     // per spin: point positions [n][3]
+  const int* pte[2];        // per spin: electron of the point
+  const long* off;          // [2][nseg W + 1] list offsets
+  int nseg, has_ecp;
+  double ii;
+  double* out;              // [K][6][Wc]
+};
+
+__device__ __forceinline__ double md_omega(const SysDev& S, const SlaterState& st, long w, int d, double ref) {
+  const double su = st.dsign[0][w * S.ndet_s[0] + S.det_map[d]];
+  const double sd = st.dsign[1][w * S.ndet_s[1] + S.det_map[S.ndet + d]];
+  const double l = det_logsum(S, st, w, d);
+  return su * sd * ((l == -INFINITY) ? 0.0 : exp(l - ref));
+}
+
+// S[k][w] = sum_d cd[d][k] omega_d for k < K1 (determinants ascending, as k_corr_md's phase 0).  One wave per walker; LDS: ndet doubles.
+__global__ __launch_bounds__(64) void k_corr_md_s(SysDev S, SlaterState st, const double* __restrict__ cd, int K1, long W,
+                                                   double* __restrict__ out /*[K1][W]*/) {
+  extern __shared__ double om[];
+  const long w = blockIdx.x;
+  const int lane = threadIdx.x;
+  const double ref = det_ref(S, st, w);
+  for (int d = lane; d < S.ndet; d += 64) om[d] = md_omega(S, st, w, d, ref);
+  __syncthreads();
+  for (int k = lane; k < K1; k += 64) {
+    double s = 0.0;
+    for (int d = 0; d < S.ndet; ++d) s += cd[(size_t)d * K1 + k] * om[d];
+    out[(size_t)k * W + w] = s;
+  }
+}
+
+// LDS of k_corr_md in doubles: omega [ndet (even)], rho [16][RS], num [5][16][GS], R [4][P]
+inline size_t corr_md_lds(int ndet, int RS, int GS, int P) { return (size_t)((ndet + 1) & ~1) + (size_t)16 * RS + (size_t)80 * GS + (size_t)4 * P; }
+
+template <bool PBC>
+__global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, JastrowState js, CorrMdArgs A) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x, i16 = lane & 15, kq = lane >> 4;
+  const long bw = blockIdx.x, w = A.w0 + bw;
+  const int kb = blockIdx.y * 64, k = kb + lane;
+  const bool act = k < A.K;
+  const int ndet = S.ndet, N = S.nelec, P = A.P, Pa = A.Pa, DP = A.DP, RS = A.RS, GS = A.GS;
+  const int ntile = ((A.K - kb < 64 ? A.K - kb : 64) + 15) / 16;  // 16-set column tiles of this block
+  double* om = sm;
+  double* rho = om + ((ndet + 1) & ~1);
+  double* G = rho + (size_t)16 * RS;
+  double* R = G + (size_t)80 * GS;
+  const double* xw = js.x + (size_t)w * N * 3;
+  const double irb = 1.0 / S.rcut_b, ira = 1.0 / S.rcut_a;
+  // phase 0
+  const double ref = det_ref(S, st, w);
+  for (int d = lane; d < ndet; d += 64) om[d] = md_omega(S, st, w, d, ref);
+  __syncthreads();
+  double Sk = 0.0;
+  if (act)
+    for (int d = 0; d < ndet; ++d) Sk += A.cd[(size_t)d * A.K1 + k] * om[d];
+  const double invS = 1.0 / Sk;
+  auto bop = [&](int col) {
+    return [&A, col](int kd, bool kin) { return (kin && col < A.K) ? A.cd[(size_t)kd * A.K1 + col] : 0.0; };
+  };
+  // kinetic terms: tiles of 16 electrons
+  double ke = 0.0, g2 = 0.0;
+  for (int e0 = 0; e0 < N; e0 += 16) {
+    const int rows = N - e0 < 16 ? N - e0 : 16;
+    for (int q = lane; q < 16 * DP; q += 64) {  // phase 1
+      const int row = q / DP, u = q - row * DP, e = e0 + row;
+      if (row >= rows) continue;
+      const int s = e >= S.nup, D = S.ndet_s[s];
+      if (u >= D) continue;
+      const int i = e - s * S.nup, n = s ? S.ndn : S.nup, nmo = S.nmo[s];
+      const double* T = st.T[s] + (((size_t)w * D + u) * n + i) * n;
+      const int* occ = S.det_occ[s] + (size_t)u * n;
+      const double* ch = st.cache[s] + ((size_t)w * n + i) * 5 * nmo;
+      double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+      for (int j = 0; j < n; ++j) {
+        const double t = T[j];
+        const int o = occ[j];
+#pragma unroll
+        for (int c = 0; c < 5; ++c) a[c] += ch[c * nmo + o] * t;
+      }
+#pragma unroll
+      for (int c = 0; c < 5; ++c) rho[row * RS + c * DP + u] = a[c];
+    }
+    __syncthreads();
+    {  // phase 2
+      const int erow = e0 + i16;
+      const bool rin = i16 < rows;
+      const int* dm = S.det_map + ((rin && erow >= S.nup) ? ndet : 0);
+      const double* rr = rho + i16 * RS;
+      for (int t = 0; t < ntile; ++t) {
+        d4 acc[5];
+        mfma_tiles<5>(ndet, kq, [&](int c, int kd, bool kin) { return (kin && rin) ? om[kd] * rr[c * DP + dm[kd]] : 0.0; },
+                      bop(kb + t * 16 + i16), acc);
+#pragma unroll
+        for (int c = 0; c < 5; ++c)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) G[(c * 16 + kq + 4 * r) * GS + t * 16 + i16] = acc[c][r];
+      }
+    }
+    __syncthreads();
+    for (int row = 0; row < rows; ++row) {  // phase 3
+      const int e = e0 + row, s = e >= S.nup;
+      jas_rows<PBC>(S, xw, e, s, xw[3 * e], xw[3 * e + 1], xw[3 * e + 2], P, Pa, ira, irb, R);
+      if (act) {
+        const double v = G[row * GS + lane];
+        const double G0 = G[(16 + row) * GS + lane] / v, G1 = G[(32 + row) * GS + lane] / v, G2 = G[(48 + row) * GS + lane] / v;
+        const double L = G[(64 + row) * GS + lane] / v;
+        double gx = 0.0, gy = 0.0, gz = 0.0, lp = 0.0;
+        for (int q = 0; q < S.natom * S.na; ++q) {
+          const int p = 2 * q + s;
+          const double c = A.ct[(size_t)p * A.K + k];
+          gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
+        }
+        for (int q = 0; q < 2 * S.nb; ++q) {
+          const int p = Pa + (q >> 1) * 3 + s + (q & 1);
+          const double c = A.ct[(size_t)p * A.K + k];
+          gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
+        }
+        const double lj = lp + gx * gx + gy * gy + gz * gz;
+        const double lap = L + lj + 2.0 * (G0 * gx + G1 * gy + G2 * gz);
+        const double tx = G0 + gx, ty = G1 + gy, tz = G2 + gz;
+        ke += -0.5 * lap;
+        g2 += tx * tx + ty * ty + tz * tz;
+      }
+      __syncthreads();
+    }
+  }
+  // ECP: tiles of 16 points of one list segment
+  double tot = 0.0;
+  if (A.has_ecp) {
+    const size_t SS = (size_t)A.nseg * A.W + 1;
+    for (int sp = 0; sp < 2; ++sp) {
+      const int n = sp ? S.ndn : S.nup, nmo = S.nmo[sp], D = S.ndet_s[sp];
+      const int* dm = S.det_map + sp * ndet;
+      for (int seg = 0; seg < A.nseg; ++seg) {
+        const long* o = A.off + sp * SS + (size_t)seg * A.W + w;
+        const long p0 = o[0], p1 = o[1];
+        for (long pb = p0; pb < p1; pb += 16) {
+          const int rows = p1 - pb < 16 ? (int)(p1 - pb) : 16;
+          for (int q = lane; q < 16 * DP; q += 64) {  // phase 1
+            const int row = q / DP, u = q - row * DP;
+            if (row >= rows || u >= D) continue;
+            const int i = A.pte[sp][pb + row] - sp * S.nup;
+            const double* T = st.T[sp] + (((size_t)w * D + u) * n + i) * n;
+            const int* occ = S.det_occ[sp] + (size_t)u * n;
+            const double* mo = A.emo[sp] + (size_t)(pb + row) * nmo;
+            double a = 0.0;
+            for (int j = 0; j < n; ++j) a += mo[occ[j]] * T[j];
+            rho[row * RS + u] = a;
+          }
+          __syncthreads();
+          {  // phase 2
+            const bool rin = i16 < rows;
+            const double* rr = rho + i16 * RS;
+            for (int t = 0; t < ntile; ++t) {
+              const d4 acc = mfma_tile(ndet, kq, [&](int kd, bool kin) { return (kin && rin) ? om[kd] * rr[dm[kd]] : 0.0; },
+                                       bop(kb + t * 16 + i16));
+#pragma unroll
+              for (int r = 0; r < 4; ++r) G[(kq + 4 * r) * GS + t * 16 + i16] = acc[r];
+            }
+          }
+          __syncthreads();
+          for (int row = 0; row < rows; ++row) {  // phase 3
+            const long pt = pb + row;
+            const int e = A.pte[sp][pt];
+            jas_diff_rows<PBC>(S, xw, e, sp, A.pts[sp][3 * pt], A.pts[sp][3 * pt + 1], A.pts[sp][3 * pt + 2], P, Pa, ira, irb, R);
+            if (act) {
+              double du = 0.0;
+              for (int q = 0; q < S.natom * S.na; ++q) { const int p = 2 * q + sp; du += A.ct[(size_t)p * A.K + k] * R[p]; }
+              for (int q = 0; q < 2 * S.nb; ++q) { const int p = Pa + (q >> 1) * 3 + sp + (q & 1); du += A.ct[(size_t)p * A.K + k] * R[p]; }
+              tot += A.wgt[sp][pt] * (G[row * GS + lane] * invS) * exp(du);
+            }
+            __syncthreads();
+          }
+        }
+      }
+    }
+  }
+  if (!act) return;
+  const double ee = A.kc[A.W + w], ei = A.kc[2 * A.W + w], ec = A.has_ecp ? A.local[w] + tot : 0.0;
+  double* o = A.out + (size_t)k * 6 * A.Wc + bw;
+  o[0] = ke; o[A.Wc] = ee; o[2 * A.Wc] = ei; o[3 * A.Wc] = ec; o[4 * A.Wc] = g2; o[5 * A.Wc] = ke + ee + ei + ec + A.ii;
+}
+
+// Scope of pqa_correlated_md: a real, untwisted Slater x two-body Jastrow handle, one or more determinants, no three-body factor, the
+// semi-local ECP integrator or no ECP.
+int linear_det_jastrow_scope(pqa_handle* h, const char* fn) {
+  const char* why = (!h->has_slater || !h->has_j2) ? "needs a Slater x two-body Jastrow handle"
+                    : (h->cplx || h->twist)        ? "complex orbitals / twisted cell"
+                    : h->has_j3                    ? "three-body Jastrow factor"
+                    : (h->necp > 0 && h->ecpb_on)  ? "batched ECP integrator"
+                                                   : nullptr;
+  if (why) FAIL(std::string(fn) + ": " + why + " (others: set, recompute and evaluate per set)");
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, const double* bcoeff, double threshold, const double* rot,
@@ -167,6 +410,112 @@ extern "C" int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, cons
   std::vector<double> lp((size_t)K * W);
   for (int k = 0; k < K; ++k)
     for (long w = 0; w < W; ++w) lp[(size_t)k * W + w] = lg0[w] - u[(size_t)K * W + w] + u[(size_t)k * W + w];
+  HIPCHK(hipMemcpy(logpsi, lp.data(), lp.size() * sizeof(double), hipMemcpyDefault));
+  return 0;
+}
+
+extern "C" int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff, const double* acoeff, const double* bcoeff, double threshold,
+                                 const double* rot, const double* unif, uint64_t seed, long walker_chunk_arg, double* logpsi, double* en) {
+  HIPCHK(hipSetDevice(h->device));
+  if (h->W == 0) FAIL("state not initialised (call pqa_wf_recompute)");
+  if (K < 1) FAIL("pqa_correlated_md: K must be at least 1");
+  if (!logpsi || !en) FAIL("pqa_correlated_md: logpsi and en must not be NULL");
+  if (walker_chunk_arg < 0) FAIL("pqa_correlated_md: walker_chunk must be 0 (the 256 MiB rule) or positive");
+  TRY(linear_det_jastrow_scope(h, "pqa_correlated_md"));
+  const long W = h->W;
+  const int ndet = h->ndet, Pa = h->natom * h->na * 2, Pb = h->nb * 3, P = Pa + Pb, K1 = K + 1;
+  // the LDS plan: refused where it does not fit, never truncated
+  const int DP = std::max(h->ndet_s[0], h->ndet_s[1]), RS = ((5 * DP + 29) / 32) * 32 + 2;
+  const int ncol = ((std::min(K, 64) + 15) / 16) * 16, GS = ncol + ((ncol % 32 == 0) ? 16 : 0);
+  const size_t lds = corr_md_lds(ndet, RS, GS, P) * sizeof(double);
+  if (lds > 160 * 1024)
+    FAIL("pqa_correlated_md: the determinant rows and Jastrow rows of a 16-row tile exceed the LDS of a CU (others: set, recompute and evaluate per set)");
+  if (lds > 64 * 1024) TRY(raise_lds_limit(h, h->S.pbc ? (const void*)k_corr_md<true> : (const void*)k_corr_md<false>));
+  // log|Psi| at the handle's own coefficients (as pqa_wf_value: refreshes the basis sums a fused sweep left stale)
+  std::vector<double> lg0((size_t)W);
+  TRY(pqa_wf_value(h, nullptr, lg0.data()));
+  // rows 0 .. K-1: the sets (NULL: the handle's own); row K: the handle's own
+  std::vector<double> ca((size_t)K1 * Pa), cb((size_t)K1 * Pb), cdr((size_t)K1 * ndet);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (Pa) HIPCHK(hipMemcpy(ca.data() + (size_t)K * Pa, h->d_acoeff, Pa * sizeof(double), hipMemcpyDeviceToHost));
+  if (Pb) HIPCHK(hipMemcpy(cb.data() + (size_t)K * Pb, h->d_bcoeff, Pb * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cdr.data() + (size_t)K * ndet, h->d_detcoeff, ndet * sizeof(double), hipMemcpyDeviceToHost));
+  auto rows_in = [&](std::vector<double>& dst, const double* src, int n) -> int {
+    if (!n) return 0;
+    if (src) HIPCHK(hipMemcpy(dst.data(), src, (size_t)K * n * sizeof(double), hipMemcpyDefault));
+    else
+      for (int k = 0; k < K; ++k) std::copy(dst.begin() + (size_t)K * n, dst.begin() + (size_t)K1 * n, dst.begin() + (size_t)k * n);
+    return 0;
+  };
+  TRY(rows_in(ca, acoeff, Pa));
+  TRY(rows_in(cb, bcoeff, Pb));
+  TRY(rows_in(cdr, det_coeff, ndet));
+  const std::vector<double> ct = pack_coef_sets(ca.data(), cb.data(), K, Pa, Pb);
+  std::vector<double> cd((size_t)ndet * K1);  // [ndet][K1]
+  for (int k = 0; k < K1; ++k)
+    for (int d = 0; d < ndet; ++d) cd[(size_t)d * K1 + k] = cdr[(size_t)k * ndet + d];
+  // the Slater-only energy pass, once: the Jastrow switched off and the ECP totals read on the host (restored on every exit)
+  struct Flags {
+    pqa_handle* h; bool has_jastrow, has_j2; int defer;
+    ~Flags() { h->has_jastrow = has_jastrow; h->has_j2 = has_j2; h->ecp_defer = defer; }
+  } flags{h, h->has_jastrow, h->has_j2, h->ecp_defer};
+  TRY(sync_aos(h));
+  h->saved_valid = false;  // (as pqa_energy: the saved orbital rows of a gradient_value call are overwritten)
+  h->has_jastrow = false; h->has_j2 = false; h->ecp_defer = 0;
+  TRY(energy_dev(h, threshold, rot, unif, seed, 0u));
+  h->has_jastrow = flags.has_jastrow; h->has_j2 = flags.has_j2; h->ecp_defer = flags.defer;
+  const bool has_ecp = h->necp > 0;
+  if (has_ecp && (h->ecp_last_tot[0] < 0 || h->ecp_last_tot[1] < 0)) FAIL("pqa_correlated_md: ECP point totals were left on the device");
+  // device scratch (b_out is sized by every user on entry): coefficient rows for k_corr_u, U, the two matrices, S, a chunk of outputs
+  const size_t nca = (size_t)K1 * std::max(Pa, 1), ncb = (size_t)K1 * std::max(Pb, 1), nu = (size_t)K1 * W, nct = (size_t)P * K;
+  const size_t ncd = (size_t)ndet * K1;
+  const long Wc = walker_chunk_arg > 0 ? std::min(W, walker_chunk_arg) : walker_chunk(W, (size_t)K * 6 * sizeof(double));
+  TRY(ensure(h, h->b_out, (nca + ncb + 2 * nu + nct + ncd + (size_t)K * 6 * Wc) * sizeof(double)));
+  double* d_ca = (double*)h->b_out.p;
+  double* d_cb = d_ca + nca;
+  double* d_u = d_cb + ncb;
+  double* d_s = d_u + nu;
+  double* d_ct = d_s + nu;
+  double* d_cd = d_ct + nct;
+  double* d_o = d_cd + ncd;
+  if (Pa) TRY(copy_in(h, d_ca, ca.data(), (size_t)K1 * Pa * sizeof(double)));
+  if (Pb) TRY(copy_in(h, d_cb, cb.data(), (size_t)K1 * Pb * sizeof(double)));
+  TRY(copy_in(h, d_ct, ct.data(), nct * sizeof(double)));
+  TRY(copy_in(h, d_cd, cd.data(), ncd * sizeof(double)));
+  hipLaunchKernelGGL(k_corr_u, dim3((unsigned)W), dim3(64), 0, h->stream, (const double*)h->js.avalues, (const double*)h->js.bvalues,
+                     (const double*)d_ca, (const double*)d_cb, Pa, Pb, K1, W, d_u);
+  TRY(check_launch(h, "k_corr_u"));
+  hipLaunchKernelGGL(k_corr_md_s, dim3((unsigned)W), dim3(64), (size_t)ndet * sizeof(double), h->stream, h->S, h->st, (const double*)d_cd, K1, W, d_s);
+  TRY(check_launch(h, "k_corr_md_s"));
+  CorrMdArgs A{};
+  A.W = W; A.K = K; A.K1 = K1; A.P = P; A.Pa = Pa; A.DP = DP; A.RS = RS; A.GS = GS; A.ct = d_ct; A.cd = d_cd;
+  A.kc = (const double*)h->b_kc.p; A.ii = h->ii_energy; A.out = d_o; A.has_ecp = has_ecp;
+  if (has_ecp) {
+    A.local = (const double*)h->b_elocal.p; A.off = (const long*)h->b_eoff.p; A.nseg = h->ecp_last_nseg;
+    for (int s = 0; s < 2; ++s) {
+      A.wgt[s] = (const double*)h->b_ewgt[s].p; A.emo[s] = (const double*)h->b_emo[s].p;
+      A.pts[s] = (const double*)h->b_epts[s].p; A.pte[s] = (const int*)h->b_epte[s].p;
+    }
+  }
+  for (long w0 = 0; w0 < W; w0 += Wc) {
+    A.w0 = w0; A.Wc = std::min(Wc, W - w0);
+    const dim3 g((unsigned)A.Wc, (unsigned)((K + 63) / 64));
+    if (h->S.pbc) hipLaunchKernelGGL(k_corr_md<true>, g, dim3(64), lds, h->stream, h->S, h->st, h->js, A);
+    else hipLaunchKernelGGL(k_corr_md<false>, g, dim3(64), lds, h->stream, h->S, h->st, h->js, A);
+    TRY(check_launch(h, "k_corr_md"));
+    // [K][6][Wc] -> en [K][6][W] columns w0 ..
+    HIPCHK(hipMemcpy2DAsync(en + w0, (size_t)W * sizeof(double), d_o, (size_t)A.Wc * sizeof(double), (size_t)A.Wc * sizeof(double),
+                            (size_t)K * 6, hipMemcpyDefault, h->stream));
+  }
+  std::vector<double> u((size_t)K1 * W), sv((size_t)K1 * W);
+  TRY(copy_out(h, u.data(), d_u, u.size() * sizeof(double)));
+  TRY(copy_out(h, sv.data(), d_s, sv.size() * sizeof(double)));
+  std::vector<double> lp((size_t)K * W);
+  for (int k = 0; k < K; ++k)
+    for (long w = 0; w < W; ++w) {
+      const size_t i = (size_t)k * W + w, i0 = (size_t)K * W + w;
+      lp[i] = lg0[w] + (std::log(std::fabs(sv[i])) - std::log(std::fabs(sv[i0]))) + (u[i] - u[i0]);
+    }
   HIPCHK(hipMemcpy(logpsi, lp.data(), lp.size() * sizeof(double), hipMemcpyDefault));
   return 0;
 }

@@ -169,6 +169,21 @@ __device__ __forceinline__ d4 mfma_tile(int n, int kq, FA&& a, FB&& b) {
   return c;
 }
 
+// NC tiles C_m = A_m B that share the B operand (k_corr_md: the components of a row tile against one coefficient tile): a(m, k, kin),
+// b(k, kin) as above, k-steps ascending.  The NC accumulators are independent, so one tile's MFMA latency is covered by the others'.
+template <int NC, class FA, class FB>
+__device__ __forceinline__ void mfma_tiles(int n, int kq, FA&& a, FB&& b, d4 (&c)[NC]) {
+#pragma unroll
+  for (int m = 0; m < NC; ++m) c[m] = d4{0.0, 0.0, 0.0, 0.0};
+  for (int k0 = 0; k0 < n; k0 += 4) {
+    const int k = k0 + kq;
+    const bool kin = k < n;
+    const double bk = b(k, kin);
+#pragma unroll
+    for (int m = 0; m < NC; ++m) c[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(a(m, k, kin), bk, c[m], 0, 0, 0);
+  }
+}
+
 // Fixed-order sum over the 256 threads of a block (sh: 256 doubles of LDS); every thread gets the total.
 __device__ __forceinline__ double block_sum256(double v, double* sh) {
   const int t = threadIdx.x;

@@ -11,8 +11,12 @@ step along it by correlated sampling: the walkers are drawn from the mixture of 
   parameters are Jastrow coefficients only (``wf2acoeff`` / ``wf2bcoeff``), with the semi-local ECP integrator: ONE C call,
   ``pqa_correlated``, evaluates all sets on the resident walkers: the Slater part once, then per set only the contraction of
   basis-resolved Jastrow rows with its coefficients (csrc/pqa_correlated.hip);
+  with ``evaluation_route="fused"`` also several determinants and ``wf1det_coeff`` among the parameters (real, untwisted, no
+  three-body factor): ONE C call, ``pqa_correlated_md``, which adds the determinant sums of all sets as one matrix-core product
+  per walker (``data["entry"]`` names the call that ran);
 * ``"protocol"`` — anything else: per set, the parameters are set, the wave function recomputed and the energy accumulator
-  run, as the reference does.
+  run, as the reference does.  It is the default for several determinants; ``evaluation_route`` (``line_minimization``,
+  ``correlated_sampling_minimum``, ``correlated_compute``, ``correlated_compute_worker``) selects a route by name.
 
 One deliberate difference from the reference: both routes leave ``wf`` at its original parameters (the reference leaves it at
 the last point of the line).  ``line_minimization`` sets the chosen parameters afterwards either way.
@@ -29,7 +33,7 @@ import numpy as np
 
 from . import sample_many as sm
 from .energy import EnergyAccumulator
-from .wf import linear_jastrow_device
+from .wf import linear_det_jastrow_device, linear_jastrow_device
 
 
 def opt_hdf(hdf_file, data, attr, configs, parameters):
@@ -93,9 +97,10 @@ def _no_client(client, npartitions):
 
 def line_minimization(wf, coords, pgrad_acc, steprange=0.2, max_iterations=30, warmup_options=None, correlated_reference_wfs=None,
                       stderr_weight=3.0, vmcoptions=None, lmoptions=None, correlatedoptions=None, update_kws=None, verbose=False, npts=40,
-                      hdf_file=None, client=None, npartitions=None, correlated_sampling=True):
+                      hdf_file=None, client=None, npartitions=None, correlated_sampling=True, evaluation_route=None):
     """Optimise the energy by stochastic-reconfiguration directions and correlated-sampling line searches (linemin.py:103-260).
     ``pgrad_acc``: a ``StochasticReconfiguration`` (e.g. ``accumulators.gradient_generator``) or a list of them (sub-iterations).
+    ``evaluation_route``: the route of the line points' evaluation (``correlated_route``; None: the default choice).
     Returns (wf, list of per-step dictionaries)."""
     _no_client(client, npartitions)
     from .blockfile import BlockFile
@@ -160,7 +165,8 @@ def line_minimization(wf, coords, pgrad_acc, steprange=0.2, max_iterations=30, w
                          "nconfig": coords.configs.shape[0]}
             if correlated_sampling:
                 x0, min_data = correlated_sampling_minimum(steprange, npts, stderr_weight, correlated_reference_wfs, pgrad, wf, data, x0,
-                                                           coords, client, npartitions, **correlatedoptions)
+                                                           coords, client, npartitions, evaluation_route=evaluation_route,
+                                                           **correlatedoptions)
                 step_data.update(min_data)
                 if verbose:
                     print("Moved", step_data["est_min"])
@@ -181,15 +187,16 @@ def sr_step(steprange, pgrad, data, x0):
 
 
 def correlated_sampling_minimum(steprange, npts, stderr_weight, correlated_reference_wfs, pgrad, wf, data, x0, coords, client, npartitions,
-                                **correlatedoptions):
+                                evaluation_route=None, **correlatedoptions):
     """Step along the SR direction that minimises ``mean energy + stderr_weight * spread`` over ``npts`` points of
     ``np.linspace(-steprange / (npts - 2), steprange, npts)`` (linemin.py:280-328).  ``correlatedoptions``: ``nsteps`` / ``nblocks``
-    / ``tstep`` of the mixture sampling (the reference accepts them and drops them, sampling 10 blocks x 10 sweeps)."""
+    / ``tstep`` of the mixture sampling (the reference accepts them and drops them, sampling 10 blocks x 10 sweeps);
+    ``evaluation_route`` goes to ``correlated_compute_worker``, not into the sampling's options."""
     steps = np.linspace(-steprange / (npts - 2), steprange, npts)
     dps, update_report = pgrad.delta_p(steps, data, verbose=False)
     params = [x0 + dp for dp in dps]
     correlated_data = correlated_compute(wf, coords, params, pgrad, client=client, npartitions=npartitions, ref_wfs=correlated_reference_wfs,
-                                         **correlatedoptions)
+                                         evaluation_route=evaluation_route, **correlatedoptions)
     w = correlated_data["weight"].copy()
     w = w / np.mean(w, axis=1, keepdims=True)
     en = np.real(np.mean(correlated_data["total"] * w, axis=1))
@@ -205,7 +212,7 @@ def correlated_sampling_minimum(steprange, npts, stderr_weight, correlated_refer
     return x0, update_report
 
 
-def correlated_compute(wf, configs, params, pgrad_acc, client=None, npartitions=None, ref_wfs=None, **kws):
+def correlated_compute(wf, configs, params, pgrad_acc, client=None, npartitions=None, ref_wfs=None, evaluation_route=None, **kws):
     """Walkers drawn from the mixture of the ``ref_wfs`` parameter sets (deep copies of ``wf``), then every set of ``params``
     evaluated on them (linemin.py:331-375).  ``kws``: ``nsteps`` / ``nblocks`` / ``tstep`` of ``sample_many.sample_overlap``."""
     _no_client(client, npartitions)
@@ -216,15 +223,35 @@ def correlated_compute(wf, configs, params, pgrad_acc, client=None, npartitions=
         set_wf_params(wfs[i], params[i], pgrad_acc)
     _, _, configs = sm.sample_overlap(wfs, configs, None, **kws)
     del wfs  # (their device handles)
-    return correlated_compute_worker(wf, configs, params, pgrad_acc, ref_wfs)
+    return correlated_compute_worker(wf, configs, params, pgrad_acc, ref_wfs, evaluation_route=evaluation_route)
 
 
-def correlated_route(wf, pgrad_acc):
-    """``"fused"`` when ``pqa_correlated`` covers this wave function, accumulator and parameter selection, else ``"protocol"``."""
-    enacc = getattr(pgrad_acc, "enacc", None)
-    if type(enacc) is not EnergyAccumulator or not enacc.use_old_ecp:
+def correlated_route(wf, pgrad_acc, route=None):
+    """The route ``correlated_compute_worker`` takes.  ``route=None``: ``"fused"`` when ``pqa_correlated`` covers this wave function,
+    accumulator and parameter selection, else ``"protocol"``.  ``route="fused"``: ``"fused"`` also where only ``pqa_correlated_md``
+    covers them (several determinants, ``wf1det_coeff`` among the parameters); ``NotImplementedError`` with the reason where neither
+    does.  ``route="protocol"``: ``"protocol"``."""
+    if route not in (None, "fused", "protocol"):
+        raise ValueError(f"evaluation route {route!r}: None, 'fused' or 'protocol' expected")
+    if route == "protocol":
         return "protocol"
-    return "protocol" if linear_jastrow_device(wf, pgrad_acc.transform.to_opt) is None else "fused"
+    enacc = getattr(pgrad_acc, "enacc", None)
+    plain = type(enacc) is EnergyAccumulator and enacc.use_old_ecp
+    if route is None:
+        if not plain:
+            return "protocol"
+        return "protocol" if linear_jastrow_device(wf, pgrad_acc.transform.to_opt) is None else "fused"
+    why = []
+    if not plain:
+        why.append("the energy accumulator is not an EnergyAccumulator with the semi-local ECP integrator (use_old_ecp=True)")
+    elif linear_det_jastrow_device(wf, _opt_keys(pgrad_acc), why) is not None:
+        return "fused"
+    raise NotImplementedError(f"evaluation_route='fused': {why[0]}; use the set-recompute-energy route (evaluation_route='protocol')")
+
+
+def _opt_keys(pgrad_acc):
+    """The parameters with at least one optimised entry."""
+    return {k for k, v in pgrad_acc.transform.to_opt.items() if np.any(v)}
 
 
 def _weights(psi, ref_wfs):
@@ -234,11 +261,12 @@ def _weights(psi, ref_wfs):
     return psirel / rho
 
 
-def correlated_compute_worker(wf, configs, params, pgrad_acc, ref_wfs):
+def correlated_compute_worker(wf, configs, params, pgrad_acc, ref_wfs, evaluation_route=None):
     """Energies and log values of ``wf`` at every parameter set of ``params`` on the same walkers, with the same random draws for
     every set (linemin.py:378-409).  Returns ``{energy key: (nsets, nconf)}``, ``weight`` (nsets, nconf) relative to the mixture
-    of the ``ref_wfs`` sets, and ``route``.  ``wf`` keeps its parameters; its device state is that of ``configs``."""
-    route = correlated_route(wf, pgrad_acc)
+    of the ``ref_wfs`` sets, ``route`` and, on the fused route, ``entry`` (the C call).  ``wf`` keeps its parameters; its device
+    state is that of ``configs``.  ``evaluation_route``: see ``correlated_route``."""
+    route = correlated_route(wf, pgrad_acc, evaluation_route)
     if route == "fused":
         return _correlated_fused(wf, configs, params, pgrad_acc, ref_wfs)
     x_orig = pgrad_acc.transform.serialize_parameters(wf.parameters)
@@ -277,10 +305,18 @@ def _correlated_fused(wf, configs, params, pgrad_acc, ref_wfs):
     enacc._calls += 1
     # the draws one accumulator call makes (EnergyAccumulator.__call__), shared by every set as the reference's reset gives them
     key = int(np.random.randint(0, 2**31 - 1)) if enacc.seed is None else enacc.seed + enacc._calls
-    psi, en = dev.correlated(acoeff, bcoeff, enacc.threshold, seed=key)
+    if dev.ndet > 1 or "wf1det_coeff" in _opt_keys(pgrad_acc):
+        dc = wf.wf_factors[0].parameters["det_coeff"]
+        det_coeff = np.stack([s.get("wf1det_coeff", dc) for s in sets])
+        psi, en = dev.correlated_md(det_coeff, acoeff, bcoeff, enacc.threshold, seed=key)
+        entry = "pqa_correlated_md"
+    else:
+        psi, en = dev.correlated(acoeff, bcoeff, enacc.threshold, seed=key)
+        entry = "pqa_correlated"
     data_ret = {k: en[:, i, :] for i, k in enumerate(KEYS)}
     data_ret["weight"] = _weights(psi, ref_wfs)
     data_ret["route"] = "fused"
+    data_ret["entry"] = entry
     return data_ret
 
 

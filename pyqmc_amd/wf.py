@@ -291,6 +291,25 @@ class DeviceWF:
                   _ffi.ptr(logpsi), _ffi.ptr(en))
         return logpsi, en
 
+    def correlated_md(self, det_coeff=None, acoeff=None, bcoeff=None, threshold=10.0, rot=None, unif=None, seed=0, walker_chunk=0):
+        """``pqa_correlated_md``: the resident walkers at K sets of determinant coefficients det_coeff (K, ndet) and two-body Jastrow
+        coefficients acoeff (K, natom, na, 2), bcoeff (K, nb, 3), every set with the same energy draws -> (logpsi (K, W), energy
+        rows (K, 6, W)).  None for an array: every set uses the handle's own (K from the arrays given; 1 when none is).  The handle
+        keeps its own coefficients and state; the result does not depend on ``walker_chunk`` (0: output chunks of 256 MiB)."""
+        shapes = {"det_coeff": (self.ndet,), "acoeff": (self.natom, self.na, 2), "bcoeff": (self.nb, 3)}
+        arrs = {k: None if v is None else _ffi.f64(v) for k, v in (("det_coeff", det_coeff), ("acoeff", acoeff), ("bcoeff", bcoeff))}
+        Ks = {v.shape[0] for v in arrs.values() if v is not None and v.ndim >= 1}
+        K = Ks.pop() if len(Ks) == 1 else (1 if not Ks and all(v is None for v in arrs.values()) else None)
+        for name, v in arrs.items():
+            if K is None or (v is not None and v.shape != (K,) + shapes[name]):
+                raise ValueError(f"{name}: (K,) + {shapes[name]} expected with one K for all arrays, got {None if v is None else v.shape}")
+        logpsi, en = np.empty((K, self.W)), np.empty((K, 6, self.W))
+        rot = None if rot is None else _ffi.f64(rot)
+        unif = None if unif is None else _ffi.f64(unif)
+        self.call("pqa_correlated_md", int(K), _ffi.ptr(arrs["det_coeff"]), _ffi.ptr(arrs["acoeff"]), _ffi.ptr(arrs["bcoeff"]), float(threshold),
+                  _ffi.ptr(rot), _ffi.ptr(unif), int(seed), int(walker_chunk), _ffi.ptr(logpsi), _ffi.ptr(en))
+        return logpsi, en
+
     def sr_moments(self, src, pos, nodal_cutoff, weights=None, threshold=10.0, rot=None, unif=None, seed=0, per_walker=False):
         """``pqa_sr_moments``: the moments of ``StochasticReconfiguration.avg`` from the resident state.  Column i of the serialised
         derivative matrix is flat entry ``pos[i]`` of the parameter ``src[i]`` (0 det_coeff, 1 acoeff, 2 bcoeff, 3 ccoeff);
@@ -1182,6 +1201,34 @@ def linear_jastrow_device(wf, keys):
     if dev is None or dev.cplx or dev.ndet != 1 or dev.has_j3:
         return None
     return dev if set(keys) <= LINEAR_JASTROW_KEYS else None
+
+
+LINEAR_DET_KEYS = LINEAR_JASTROW_KEYS | {"wf1det_coeff"}  # the parameters ``pqa_correlated_md`` varies
+
+
+def linear_det_jastrow_device(wf, keys, why=None):
+    """The device handle ``pqa_correlated_md`` can evaluate ``wf`` on while the parameters ``keys`` vary, or None: ``wf`` must be
+    Slater x JastrowSpin on one handle, real and untwisted, with one or more determinants and no three-body factor, and ``keys``
+    within ``LINEAR_DET_KEYS``.  ``why``: a list that receives the reason for a None."""
+    f = getattr(wf, "wf_factors", None)
+    reason, dev = None, None
+    if f is None or len(f) != 2 or type(f[0]) is not Slater or type(f[1]) is not JastrowSpin:
+        reason = "the wave function is not Slater x two-body Jastrow (JastrowSpin) on one device handle"
+    else:
+        dev = wf.fused_device()
+        if dev is None:
+            reason = "the wave function has no fused device handle"
+        elif dev.cplx or dev.twisted:
+            reason = "complex orbitals / twisted cell"
+        elif dev.has_j3:
+            reason = "three-body Jastrow factor"
+        elif not set(keys) <= LINEAR_DET_KEYS:
+            reason = f"parameters outside {sorted(LINEAR_DET_KEYS)}: {sorted(set(keys) - LINEAR_DET_KEYS)}"
+    if reason is not None:
+        if why is not None:
+            why.append(reason)
+        return None
+    return dev
 
 
 def _ion_cusp_list(mol, ion_cusp):

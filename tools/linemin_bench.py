@@ -7,6 +7,13 @@
 2. One line_minimization iteration at the smaller walker count (mixture sampling 1 x 3 and the reference's 10 x 10 sweeps), split into warm-up VMC, gradient VMC, mixture sampling and
    correlated evaluation (wall clock of the driver's own calls, synchronised by their host read-backs).
 --fused-only: part 1's fused route only (for a rocprofv3 --kernel-trace --stats run).
+
+    python tools/linemin_bench.py --ndet 50 --system water --walkers 16384
+
+--ndet N: instead of the above, correlated_compute_worker for a multi-determinant handle (N determinants from
+systems.random_determinants over random_mf(nvirt=6) orbitals; --system water | cluster), det_coeff, acoeff and bcoeff varying:
+evaluation_route="fused" (pqa_correlated_md) against "protocol" on the same handle in one process, alternately, each after a
+warm-up, --repeats timed calls of each; the rows are appended to --out.
 """
 
 import argparse
@@ -66,6 +73,36 @@ def correlated(W, npts, fused_only):
     return rows
 
 
+def correlated_md(W, npts, ndet, system, fused_only, repeats):
+    mol = systems.water() if system == "water" else systems.water_cluster()
+    mf = systems.random_mf(mol, nvirt=6)
+    wf = pa.generate_wf(mol, mf, determinants=systems.random_determinants(mol, mf, ndet))
+    rng = np.random.default_rng(11)
+    ja = wf.wf_factors[1].parameters
+    wf.parameters["wf2acoeff"] = 0.05 * rng.standard_normal(np.shape(ja["acoeff"]))
+    wf.parameters["wf2bcoeff"] = np.concatenate([np.asarray(ja["bcoeff"])[:1], 0.05 * rng.standard_normal((np.shape(ja["bcoeff"])[0] - 1, 3))])
+    configs = OpenConfigs(systems.initial_guess(mol, W, rng=np.random.default_rng(1)).configs.copy())
+    pgrad = gradient_generator(mol, wf, pwf.default_to_opt(wf))
+    params = _params(wf, pgrad, npts)
+    wf.recompute(configs)
+    routes = ["fused"] if fused_only else ["fused", "protocol"]
+    for route in routes:  # (warm-up)
+        linemin.correlated_compute_worker(wf, configs, params[:3], pgrad, [0, 1], evaluation_route=route)
+    rows = []
+    for rep in range(repeats):
+        for route in routes:
+            t0 = time.perf_counter()
+            res = linemin.correlated_compute_worker(wf, configs, params, pgrad, [0, 1], evaluation_route=route)
+            dt = time.perf_counter() - t0
+            assert res["route"] == route
+            rows.append({"what": "correlated_compute_worker", "system": "H2O" if system == "water" else "(H2O)8", "ndet": ndet,
+                         "ndet_unique": list(wf.fused_device().ndet_s), "walkers": W, "npts": npts, "route": route, "entry": res.get("entry"),
+                         "repeat": rep, "seconds": dt, "ms_per_set": 1e3 * dt / npts,
+                         "mean_total_first_last": [float(res["total"][0].mean()), float(res["total"][-1].mean())]})
+            print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
 def one_iteration(W, npts, correlatedoptions):
     """Wall clock of the parts of one line_minimization iteration (the driver's own functions, wrapped)."""
     mol = systems.water_cluster()
@@ -115,9 +152,20 @@ def main():
     ap.add_argument("--walkers", type=int, nargs="+", default=[16384, 65536])
     ap.add_argument("--npts", type=int, default=40)
     ap.add_argument("--fused-only", action="store_true")
+    ap.add_argument("--ndet", type=int, default=0)
+    ap.add_argument("--system", choices=["water", "cluster"], default="water")
+    ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "linemin_bench.jsonl"))
     a = ap.parse_args()
     rows = []
+    if a.ndet > 0:
+        for W in a.walkers:
+            rows += correlated_md(W, a.npts, a.ndet, a.system, a.fused_only, a.repeats)
+        if a.out:
+            with open(a.out, "a") as f:
+                for r in rows:
+                    f.write(json.dumps(r) + "\n")
+        return
     for W in a.walkers:
         rows += correlated(W, a.npts, a.fused_only)
     if not a.fused_only:
