@@ -746,6 +746,10 @@ int pqa_profile_query_commit(pqa_handle_t* h, int64_t* launches, double* total_m
    proposal, jastrowspin.py:296-340): launches bracketed (the proposal-side launch of every prof-stride-th electron), their
    total ms, and the number of partial-sum groups per walker the launch geometry uses at the resident walker count */
 int pqa_profile_query_part(pqa_handle_t* h, int64_t* launches, double* total_ms, int* groups);
+/* the per-walker energy rows of the LAST evaluation on the resident walkers, in pqa_energy's layout ([6][W]: ke, ee, ei, ecp, grad2,
+   total; complex wave functions [7][W]) — also of the evaluation that ended the last step of pqa_vmc_sweeps / pqa_dmc_steps, which
+   return walker means only.  Fails when no evaluation has run at the resident walker count. */
+int pqa_energy_last(pqa_handle_t* h, double* out);
 /* points evaluated by the ECP integrator in the last pqa_energy call (data dependent) */
 int pqa_last_ecp_points(pqa_handle_t* h, int64_t* npoints);
 

@@ -293,11 +293,13 @@ static __global__ __launch_bounds__(64 * PQA_ECP_WB) void k_ecp_fill_t(SysDev S,
 // CX: complex determinants (inverse planes [row][2 k + re|im][W], orbital rows [re block | im block]); the imaginary parts of the
 // contributions go to contrib[npts + p].  (k_ecp_accum walked a walker's points one after the other on one wave, 16 of its lanes
 // busy in the 16-electron dots: 0.99 ms per evaluation of the twisted 32-electron cell at 8 192 walkers, 11 % of its step.)
+// rat (rat1: grid row 1): the points' Slater ratios from k_ecp_orbcol (pqa_ecp_orbcol.hpp) — one load instead of the dot product, no orbital rows.
 template <bool PBC, bool CX = false>
 static __global__ __launch_bounds__(256) void k_ecp_point_lw(SysDev S, LwState L, EcpBuf B, int s, int has_slater, int has_jastrow,
                                                       const double* __restrict__ mo, long npts, long W, double* __restrict__ contrib,
-                                                      const double* __restrict__ mo1 = nullptr, long npts1 = 0, double* __restrict__ contrib1 = nullptr) {
-  if (blockIdx.y) { s = 1; mo = mo1; npts = npts1; contrib = contrib1; }  // (small shards: both spin channels in one launch, grid rows 0 / 1)
+                                                      const double* __restrict__ mo1 = nullptr, long npts1 = 0, double* __restrict__ contrib1 = nullptr,
+                                                      const double* __restrict__ rat = nullptr, const double* __restrict__ rat1 = nullptr) {
+  if (blockIdx.y) { s = 1; mo = mo1; npts = npts1; contrib = contrib1; rat = rat1; }  // (small shards: both spin channels in one launch, grid rows 0 / 1)
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
   if (p >= npts || (B.ptot[s] && p >= *B.ptot[s])) return;
   const int e = B.pte[s][p];
@@ -336,7 +338,8 @@ static __global__ __launch_bounds__(256) void k_ecp_point_lw(SysDev S, LwState L
           if (k0 + u < n) { rr += a[u] * tr[u] - b[u] * ti[u]; ri += a[u] * ti[u] + b[u] * tr[u]; }
       }
       ratio = rr; ratio_im = ri;
-    } else {
+    } else if (rat) ratio = rat[p];
+    else {
     const double* Ti = L.Tt[s] + (size_t)i * n * W + w;
     double r = 0.0;
     if (S.occ_ident[s] && (n % 16) == 0 && (nmo % 4) == 0) {

@@ -1,6 +1,20 @@
 // pyqmc_amd C ABI implementation (host side): local energy on the device (kinetic, Coulomb / Ewald, ECP), pqa_energy, pqa_set_ewald, pqa_get_wrap.
 // See include/pyqmc_amd.h for the contract and pqa_internal.hpp for what the units share.
 #include "pqa_internal.hpp"
+#include "pqa_ecp_orbcol.hpp"
+
+// Which orbital stage the ECP pass of this evaluation takes: k_ecp_orbcol (one Slater ratio per quadrature point from the inverse column,
+// pqa_ecp_orbcol.hpp) exactly where the thread-per-point pass reads the resident planes of a real, open-boundary, single-determinant handle
+// without a three-body factor, and the kernel's tables and the columns of PQA_OC_R runs fit a block's LDS (then two blocks fit a CU).
+// Everything else — periodic, complex, the wave-per-walker accumulation, PQA_ECP_POINT_LW=0, the batched integrator, oversized bases —
+// keeps the orbital rows of launch_orb and the dot product.
+static bool ecp_orbcol_route(const pqa_handle* h, bool soa_current) {
+  if (h->S.pbc || h->S.nL > 0 || h->cplx) return false;
+  if (h->ndet != 1 || h->has_j3 || !h->has_slater) return false;
+  if (!soa_current || !h->ecp_point_lw || h->ecp_wave != 0 || h->ecpb_on != 0) return false;
+  if (h->nshell > PQA_WS_MAXSH || (int)h->S.nprim > PQA_WS_MAXP) return false;
+  return PQA_OC_STATIC_LDS + ecp_orbcol_lds(h->S.nao, std::max(h->nup, h->ndn)) <= (size_t)64 * 1024;
+}
 
 int energy_dev(pqa_handle* h, double threshold, const double* rot, const double* unif, uint64_t seed, uint32_t step,
                bool soa_current, bool aos_T_needed, bool assemble) {
@@ -12,6 +26,7 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
   bool side_join = false;
   TRY(ensure(h, h->b_kc, (size_t)4 * W * sizeof(double)));
   TRY(ensure(h, h->b_en, (size_t)(h->cplx ? 7 : 6) * W * sizeof(double)));
+  h->en_W = W;  // (pqa_energy_last: the rows this evaluation, or its caller's k_energy_finish, leaves in b_en)
   // will the ECP passes below leave their point totals on the device (no host synchronisation inside this evaluation)?
   const bool will_defer = h->necp > 0 && h->ecpb_on == 0 && h->ecp_defer != 0 && !h->S.pbc && h->ecp_hint_valid && (h->ecp_evals % 16) != 0 &&
                           (W * (long)h->N * h->necp * std::max(h->S.ecp_naip_max, 1)) * (long)(64 + 8 * std::max(h->nmo[0], h->nmo[1])) <= (long)256 << 20;
@@ -105,6 +120,11 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
     EcpBuf B{};
     B.rot = (const double*)h->b_rot.p;
     const bool batched = h->ecpb_on != 0;
+    const bool orbcol = ecp_orbcol_route(h, soa_current);
+    if (h->route.debug && (int)orbcol != h->ecp_route_reported) {  // PQA_RES_DEBUG: the orbital stage of the ECP pass, whenever it is not the last one's
+      fprintf(stderr, "[pqa] ecp route: %s\n", orbcol ? "k_ecp_orbcol" : "k_orb rows + dot product");
+      h->ecp_route_reported = (int)orbcol;
+    }
     if (unif && !batched) {
       TRY(ensure(h, h->b_eunif, nrot * W * sizeof(double)));
       TRY(copy_in(h, h->b_eunif.p, unif, nrot * W * sizeof(double)));
@@ -199,7 +219,8 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
       TRY(ensure(h, h->b_eu0[s], n * sizeof(double)));
       B.ptw[s] = (int*)h->b_eptw[s].p;
       B.u0[s] = (double*)h->b_eu0[s].p;
-      TRY(ensure(h, h->b_emo[s], n * std::max(h->nmo[s], 1) * sizeof(double)));
+      if (orbcol) TRY(ensure(h, h->b_erat[s], n * sizeof(double)));  // (no orbital rows on this route)
+      else TRY(ensure(h, h->b_emo[s], n * std::max(h->nmo[s], 1) * sizeof(double)));
       B.pts[s] = (double*)h->b_epts[s].p; B.wgt[s] = (double*)h->b_ewgt[s].p; B.pte[s] = (int*)h->b_epte[s].p;
     }
     if (batched) {  // (also with no point at all: the local channels and the list offsets come from this launch)
@@ -224,6 +245,16 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
       if (h->S.pbc) hipLaunchKernelGGL(k_ecp_fill<true>, dim3((unsigned)W), dim3(64), 0, h->stream, h->S, h->js, B, W);
       else hipLaunchKernelGGL(k_ecp_fill<false>, dim3((unsigned)W), dim3(64), 0, h->stream, h->S, h->js, B, W);
       TRY(check_launch(h, "k_ecp_fill"));
+      if (orbcol) {
+        for (int s = 0; s < 2; ++s) {
+          if (tot[s] <= 0 || h->nmo[s] == 0) continue;  // (a spin without a point: no launch)
+          PointAddr pa = plain_points(B.pts[s], tot[s]);
+          if (defer) pa.count = cnt_dev[s];
+          hipLaunchKernelGGL((k_ecp_orbcol), dim3((unsigned)((tot[s] + 63) / 64)), dim3(256), ecp_orbcol_lds(h->S.nao, s ? h->ndn : h->nup), h->stream,
+                             h->S, lw_state(h), h->tab[1], s, pa, tot[s], (const int*)B.pte[s], (const int*)B.ptw[s], W, (double*)h->b_erat[s].p);
+        }
+        TRY(check_launch(h, "k_ecp_orbcol"));
+      } else
       if (h->has_slater)
         for (int s = 0; s < 2; ++s) {
           PointAddr pa = plain_points(B.pts[s], tot[s]);
@@ -253,7 +284,8 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
       if (both) {
         const dim3 g2((unsigned)((std::max(tot[0], tot[1]) + 255) / 256), 2);
 #define PQA_PT2(PB, CXF) hipLaunchKernelGGL((k_ecp_point_lw<PB, CXF>), g2, dim3(256), 0, h->stream, h->S, lw_state(h), B, 0, (int)h->has_slater, (int)h->has_jastrow, \
-                                            (const double*)h->b_emo[0].p, tot[0], W, (double*)h->b_econ[0].p, (const double*)h->b_emo[1].p, tot[1], (double*)h->b_econ[1].p)
+                                            (const double*)h->b_emo[0].p, tot[0], W, (double*)h->b_econ[0].p, (const double*)h->b_emo[1].p, tot[1], (double*)h->b_econ[1].p, \
+                                            orbcol ? (const double*)h->b_erat[0].p : nullptr, orbcol ? (const double*)h->b_erat[1].p : nullptr)
         if (cx_points) { if (h->S.pbc) PQA_PT2(true, true); else PQA_PT2(false, true); }
         else { if (h->S.pbc) PQA_PT2(true, false); else PQA_PT2(false, false); }
 #undef PQA_PT2
@@ -280,7 +312,8 @@ int energy_dev(pqa_handle* h, double threshold, const double* rot, const double*
                                (int)h->has_jastrow, (const double*)h->b_emo[s].p, tot[s], W, (double*)h->b_econ[s].p);
           else
             hipLaunchKernelGGL(k_ecp_point_lw<false>, g, dim3(256), 0, h->stream, h->S, lw_state(h), B, s, (int)h->has_slater,
-                               (int)h->has_jastrow, (const double*)h->b_emo[s].p, tot[s], W, (double*)h->b_econ[s].p);
+                               (int)h->has_jastrow, (const double*)h->b_emo[s].p, tot[s], W, (double*)h->b_econ[s].p, nullptr, 0L, nullptr,
+                               orbcol ? (const double*)h->b_erat[s].p : nullptr, nullptr);
         } else
         if (h->S.pbc)
           hipLaunchKernelGGL(k_ecp_point<true>, g, dim3(256), 0, h->stream, h->S, h->st, h->js, B, s, (int)h->has_slater,
@@ -425,6 +458,12 @@ extern "C" int pqa_energy(pqa_handle_t* h, double threshold, const double* rot, 
   if (h->W == 0) FAIL("state not initialised (call pqa_wf_recompute)");
   h->saved_valid = false;
   TRY(energy_dev(h, threshold, rot, unif, seed, 0u));
+  return copy_out(h, out, h->b_en.p, (size_t)(h->cplx ? 7 : 6) * h->W * sizeof(double));
+}
+
+extern "C" int pqa_energy_last(pqa_handle_t* h, double* out) {
+  HIPCHK(hipSetDevice(h->device));
+  if (h->W == 0 || h->en_W != h->W) FAIL("no energy evaluation has run on the resident walkers");
   return copy_out(h, out, h->b_en.p, (size_t)(h->cplx ? 7 : 6) * h->W * sizeof(double));
 }
 

@@ -186,6 +186,9 @@ struct pqa_handle {
   // for small shards too (A/B, bitwise check)
   struct { int mode = 1, kb = -1, gm = 0, step_pre = 1; } lw;
   DevBuf b_rot, b_eunif, b_elocal, b_ecnt, b_eoff, b_epts[2], b_ewgt[2], b_epte[2], b_emo[2], b_ecp;
+  DevBuf b_erat[2];  // Slater ratios of the ECP points, per spin (k_ecp_orbcol: the route that keeps no orbital rows in b_emo)
+  long en_W = 0;     // walkers of the evaluation whose per-walker rows b_en holds (pqa_energy_last)
+  int ecp_route_reported = -1;  // PQA_RES_DEBUG: the ECP orbital route last reported (energy_dev; 1: k_ecp_orbcol, 0: k_orb rows + dot product)
   int orb_tp = 0;  // 0 = automatic
   struct TpTune { float ms[2] = {1e30f, 1e30f}; int n[2] = {0, 0}; int choice = 0; };  // periodic k_orb: [0] 32-point, [1] 64-point tiles
   TpTune tp_tune[2][48];  // per chunk table (5 / 1 components) and log2 bucket of the point count

@@ -262,6 +262,13 @@ class DeviceWF:
         self.call("pqa_energy", float(threshold), _ffi.ptr(rot), _ffi.ptr(unif), int(seed), _ffi.ptr(out))
         return self._complex_energy(out, 0) if self.cplx else out
 
+    def energy_last(self):
+        """``energy``'s rows of the LAST evaluation on the resident walkers (``pqa_energy_last``): also of the one that ended the last
+        step of ``vmc_sweeps`` / ``dmc_steps``, which return walker means only."""
+        out = np.empty((7 if self.cplx else 6, self.W))
+        self.call("pqa_energy_last", _ffi.ptr(out))
+        return self._complex_energy(out, 0) if self.cplx else out
+
     @staticmethod
     def _complex_energy(a, axis):
         """rows/columns (ke, ee, ei, Re ecp, grad2, Re total, Im ecp) -> six complex entries (Im total = Im ecp)."""
