@@ -146,8 +146,8 @@ static std::array<WalkerRow, 12> walker_rows(pqa_handle* h) {
 static int ensure_walkers(pqa_handle* h, long W) {
   if (W <= 0) FAIL("number of walkers must be positive");
   if (W != h->W) {  // (the deferred ECP point totals and the kernel-choice hints describe the shard they were measured on: ADVICE r5)
-    h->ecp_hint_valid = false; h->last_ecp_dev[0] = h->last_ecp_dev[1] = nullptr;
-    if (h->last_ecp_points < 0) h->last_ecp_points = 0;
+    h->en.hint_valid = false; h->en.last_dev[0] = h->en.last_dev[1] = nullptr;
+    if (h->en.last_points < 0) h->en.last_points = 0;
   }
   h->W = W;
   h->saved_valid = false;
@@ -1130,8 +1130,8 @@ extern "C" int pqa_set_ecp_naip(pqa_handle_t* h, int32_t naip) {
     qo[k] = ecp_quadrature_offset(na[k]);
   }
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->ecp_hint_valid = false; h->last_ecp_dev[0] = h->last_ecp_dev[1] = nullptr;  // (another rule: other point totals)
-  if (h->last_ecp_points < 0) h->last_ecp_points = 0;
+  h->en.hint_valid = false; h->en.last_dev[0] = h->en.last_dev[1] = nullptr;  // (another rule: other point totals)
+  if (h->en.last_points < 0) h->en.last_points = 0;
   h->S.ecp_naip_max = 0;
   for (int k = 0; k < h->necp; ++k) h->S.ecp_naip_max = std::max(h->S.ecp_naip_max, na[k]);
   HIPCHK(hipMemcpy(h->d_ecp_naip, na.data(), na.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -1140,13 +1140,13 @@ extern "C" int pqa_set_ecp_naip(pqa_handle_t* h, int32_t naip) {
   return 0;
 }
 extern "C" int pqa_last_ecp_points(pqa_handle_t* h, int64_t* npoints) {
-  if (h->last_ecp_points < 0 && h->last_ecp_dev[0]) {  // the last evaluation left its totals on the device (pqa_energy.hip)
+  if (h->en.last_points < 0 && h->en.last_dev[0]) {  // the last evaluation left its totals on the device (pqa_energy.hip)
     HIPCHK(hipSetDevice(h->device));
     long t[2];
-    TRY(copy_in(h, &t[0], h->last_ecp_dev[0], sizeof(long)));
-    TRY(copy_out(h, &t[1], h->last_ecp_dev[1], sizeof(long)));
-    h->last_ecp_points = t[0] + t[1];
+    TRY(copy_in(h, &t[0], h->en.last_dev[0], sizeof(long)));
+    TRY(copy_out(h, &t[1], h->en.last_dev[1], sizeof(long)));
+    h->en.last_points = t[0] + t[1];
   }
-  *npoints = h->last_ecp_points;
+  *npoints = h->en.last_points;
   return 0;
 }

@@ -3,7 +3,7 @@
 // The reference sets each parameter set, recomputes the whole wave function and runs the energy accumulator, with the random state
 // reset before every set.  Only the two-body Jastrow coefficients differ between the sets here, and U is linear in them:
 // U = sum_p c_p B_p(R), and so are grad_e U, lap_e U and the ECP exponent U(e -> q) - U(e).  The call therefore splits into
-//   once per call   the Slater-only energy pass (energy_dev with the Jastrow switched off): Coulomb / Ewald, the local ECP channel and
+//   once per call   the Slater-only energy pass (energy_dev with EnergyOpts::slater_only): Coulomb / Ewald, the local ECP channel and
 //                   the ECP point lists with their Slater-weighted values s_q = (D(e -> q) / D) w_q (b_econ), the same draws for all
 //                   sets; the log values from the basis sums the handle keeps (k_corr_u);
 //   per walker      k_corr_energy: per electron grad D / D and lap D / D (from the orbital-row cache), the basis-resolved Jastrow rows
@@ -345,7 +345,7 @@ extern "C" int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, cons
   if (K < 1) FAIL("pqa_correlated: K must be at least 1");
   if (!acoeff || !bcoeff || !logpsi || !en) FAIL("pqa_correlated: acoeff, bcoeff, logpsi and en must not be NULL");
   TRY(linear_jastrow_scope(h, "pqa_correlated"));
-  if (h->ecpb_on || h->ecp_wave) FAIL("pqa_correlated: needs the semi-local ECP integrator's thread-per-point pass (evaluate per set)");
+  if (h->ecpb_on || h->en.ecp_wave) FAIL("pqa_correlated: needs the semi-local ECP integrator's thread-per-point pass (evaluate per set)");
   const long W = h->W;
   const int Pa = h->natom * h->na * 2, Pb = h->nb * 3, P = Pa + Pb, K1 = K + 1;
   // log|Psi| at the handle's own coefficients (as pqa_wf_value: refreshes the basis sums a fused sweep left stale)
@@ -358,18 +358,14 @@ extern "C" int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, cons
   if (Pa) HIPCHK(hipMemcpy(ca.data() + (size_t)K * Pa, h->d_acoeff, Pa * sizeof(double), hipMemcpyDeviceToHost));
   if (Pb) HIPCHK(hipMemcpy(cb.data() + (size_t)K * Pb, h->d_bcoeff, Pb * sizeof(double), hipMemcpyDeviceToHost));
   const std::vector<double> ct = pack_coef_sets(ca.data(), cb.data(), K, Pa, Pb);
-  // the Slater-only energy pass, once: the Jastrow switched off and the ECP totals read on the host (restored on every exit)
-  struct Flags {
-    pqa_handle* h; bool has_jastrow, has_j2; int defer;
-    ~Flags() { h->has_jastrow = has_jastrow; h->has_j2 = has_j2; h->ecp_defer = defer; }
-  } flags{h, h->has_jastrow, h->has_j2, h->ecp_defer};
+  // the Slater-only energy pass, once, with the ECP totals read on the host
   TRY(sync_aos(h));
   h->saved_valid = false;  // (as pqa_energy: the saved orbital rows of a gradient_value call are overwritten)
-  h->has_jastrow = false; h->has_j2 = false; h->ecp_defer = 0;
-  TRY(energy_dev(h, threshold, rot, unif, seed, 0u));
-  h->has_jastrow = flags.has_jastrow; h->has_j2 = flags.has_j2; h->ecp_defer = flags.defer;
+  EnergyOpts eo;
+  eo.slater_only = true; eo.host_totals = true;
+  TRY(energy_dev(h, threshold, rot, unif, seed, 0u, eo));
   const bool has_ecp = h->necp > 0;
-  if (has_ecp && (h->ecp_last_tot[0] < 0 || h->ecp_last_tot[1] < 0)) FAIL("pqa_correlated: ECP point totals were left on the device");
+  if (has_ecp && (h->en.last_tot[0] < 0 || h->en.last_tot[1] < 0)) FAIL("pqa_correlated: ECP point totals were left on the device");
   // device scratch (b_out is sized by every user on entry): coefficient rows for k_corr_u, U, the [P][K] matrix, a chunk of outputs
   const size_t nca = (size_t)K1 * std::max(Pa, 1), ncb = (size_t)K1 * std::max(Pb, 1), nu = (size_t)K1 * W, nct = (size_t)P * K;
   const long Wc = walker_chunk(W, (size_t)K * 6 * sizeof(double));
@@ -389,7 +385,7 @@ extern "C" int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, cons
   A.W = W; A.K = K; A.P = P; A.Pa = Pa; A.ct = d_ct; A.kc = (const double*)h->b_kc.p; A.ii = h->ii_energy; A.out = d_o;
   A.has_ecp = has_ecp;
   if (has_ecp) {
-    A.local = (const double*)h->b_elocal.p; A.off = (const long*)h->b_eoff.p; A.nseg = h->ecp_last_nseg;
+    A.local = (const double*)h->b_elocal.p; A.off = (const long*)h->b_eoff.p; A.nseg = h->en.last_nseg;
     for (int s = 0; s < 2; ++s) {
       A.econ[s] = (const double*)h->b_econ[s].p; A.pts[s] = (const double*)h->b_epts[s].p; A.pte[s] = (const int*)h->b_epte[s].p;
     }
@@ -454,18 +450,14 @@ extern "C" int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff
   std::vector<double> cd((size_t)ndet * K1);  // [ndet][K1]
   for (int k = 0; k < K1; ++k)
     for (int d = 0; d < ndet; ++d) cd[(size_t)d * K1 + k] = cdr[(size_t)k * ndet + d];
-  // the Slater-only energy pass, once: the Jastrow switched off and the ECP totals read on the host (restored on every exit)
-  struct Flags {
-    pqa_handle* h; bool has_jastrow, has_j2; int defer;
-    ~Flags() { h->has_jastrow = has_jastrow; h->has_j2 = has_j2; h->ecp_defer = defer; }
-  } flags{h, h->has_jastrow, h->has_j2, h->ecp_defer};
+  // the Slater-only energy pass, once, with the ECP totals read on the host
   TRY(sync_aos(h));
   h->saved_valid = false;  // (as pqa_energy: the saved orbital rows of a gradient_value call are overwritten)
-  h->has_jastrow = false; h->has_j2 = false; h->ecp_defer = 0;
-  TRY(energy_dev(h, threshold, rot, unif, seed, 0u));
-  h->has_jastrow = flags.has_jastrow; h->has_j2 = flags.has_j2; h->ecp_defer = flags.defer;
+  EnergyOpts eo;
+  eo.slater_only = true; eo.host_totals = true;
+  TRY(energy_dev(h, threshold, rot, unif, seed, 0u, eo));
   const bool has_ecp = h->necp > 0;
-  if (has_ecp && (h->ecp_last_tot[0] < 0 || h->ecp_last_tot[1] < 0)) FAIL("pqa_correlated_md: ECP point totals were left on the device");
+  if (has_ecp && (h->en.last_tot[0] < 0 || h->en.last_tot[1] < 0)) FAIL("pqa_correlated_md: ECP point totals were left on the device");
   // device scratch (b_out is sized by every user on entry): coefficient rows for k_corr_u, U, the two matrices, S, a chunk of outputs
   const size_t nca = (size_t)K1 * std::max(Pa, 1), ncb = (size_t)K1 * std::max(Pb, 1), nu = (size_t)K1 * W, nct = (size_t)P * K;
   const size_t ncd = (size_t)ndet * K1;
@@ -491,7 +483,7 @@ extern "C" int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff
   A.W = W; A.K = K; A.K1 = K1; A.P = P; A.Pa = Pa; A.DP = DP; A.RS = RS; A.GS = GS; A.ct = d_ct; A.cd = d_cd;
   A.kc = (const double*)h->b_kc.p; A.ii = h->ii_energy; A.out = d_o; A.has_ecp = has_ecp;
   if (has_ecp) {
-    A.local = (const double*)h->b_elocal.p; A.off = (const long*)h->b_eoff.p; A.nseg = h->ecp_last_nseg;
+    A.local = (const double*)h->b_elocal.p; A.off = (const long*)h->b_eoff.p; A.nseg = h->en.last_nseg;
     for (int s = 0; s < 2; ++s) {
       A.wgt[s] = (const double*)h->b_ewgt[s].p; A.emo[s] = (const double*)h->b_emo[s].p;
       A.pts[s] = (const double*)h->b_epts[s].p; A.pte[s] = (const int*)h->b_epte[s].p;

@@ -499,9 +499,9 @@ static int create_switches(pqa_handle* h, const pqa_system_t* sys) {
   // error and, whenever a handle's sweep takes another route than its last one, "[pqa] sweep route: <kernel>" (sweep_electrons); PQA_R8_STAGGER and PQA_R8_ABL set fields of k_sweep_r8's table (pqa_res8.hip; PQA_R8_ABL: timing builds only).
   const struct { const char* name; int* field; } sw[] = {
       {"PQA_ORB_TP", &h->orb_tp}, {"PQA_LW", &h->lw.mode}, {"PQA_RES", &h->res.mode}, {"PQA_R8", &h->r8.mode}, {"PQA_WW", &h->ww.mode},
-      {"PQA_ECP_DEFER", &h->ecp_defer}, {"PQA_ORB_WS", &h->orb_ws}, {"PQA_LW_KB", &h->lw.kb}, {"PQA_LW_GM", &h->lw.gm},
-      {"PQA_ECP_WAVE", &h->ecp_wave}, {"PQA_ECP_POINT_LW", &h->ecp_point_lw}, {"PQA_ECP_LDS", &h->ecp_lds}, {"PQA_JAS_FOLD", &h->jas_fold_allowed},
-      {"PQA_ECP_ACC_WAVES", &h->ecp_acc_waves}, {"PQA_STEP_PRE", &h->lw.step_pre}, {"PQA_JAS_MERGE", &h->jas_merge}};
+      {"PQA_ECP_DEFER", &h->en.ecp_defer}, {"PQA_ORB_WS", &h->orb_ws}, {"PQA_LW_KB", &h->lw.kb}, {"PQA_LW_GM", &h->lw.gm},
+      {"PQA_ECP_WAVE", &h->en.ecp_wave}, {"PQA_ECP_POINT_LW", &h->en.ecp_point_lw}, {"PQA_ECP_LDS", &h->en.ecp_lds}, {"PQA_JAS_FOLD", &h->jas_fold_allowed},
+      {"PQA_ECP_ACC_WAVES", &h->en.ecp_acc_waves}, {"PQA_STEP_PRE", &h->lw.step_pre}, {"PQA_JAS_MERGE", &h->jas_merge}};
   for (const auto& w : sw)
     if (const char* e = getenv(w.name)) *w.field = atoi(e);
   h->route.debug = getenv("PQA_RES_DEBUG") != nullptr;

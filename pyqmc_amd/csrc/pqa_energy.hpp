@@ -407,31 +407,6 @@ static __global__ __launch_bounds__(64) void k_ecp_count(SysDev S, JastrowState 
   if (lane == 0) { B.local[w] = loc; B.cnt[w] = c_up; B.cnt[W + w] = c_dn; }  // (walker-major: nseg = 1)
 }
 
-// exclusive scan of cnt[2][W] -> off[2][W+1]; one block of 1024 threads
-template <int PQA_UNIT = 0>  // (a template so that only the units that launch it compile it)
-static __global__ __launch_bounds__(1024) void k_scan2(const int* __restrict__ cnt, long* __restrict__ off, long W) {
-  __shared__ long part[1024];
-  for (int s = 0; s < 2; ++s) {
-    const int* c = cnt + (size_t)s * W;
-    long* o = off + (size_t)s * (W + 1);
-    const long per = (W + 1023) / 1024;
-    const long b = (long)threadIdx.x * per, e = (b + per < W) ? b + per : W;
-    long sum = 0;
-    for (long i = b; i < e; ++i) sum += c[i];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      long run = 0;
-      for (int t = 0; t < 1024; ++t) { const long v = part[t]; part[t] = run; run += v; }
-      o[W] = run;
-    }
-    __syncthreads();
-    long run = part[threadIdx.x];
-    for (long i = b; i < e; ++i) { o[i] = run; run += c[i]; }
-    __syncthreads();
-  }
-}
-
 // pass B: emit auxiliary points, per-point weights and electron index.  grid = W, block = 64.
 template <bool PBC>
 static __global__ __launch_bounds__(64) void k_ecp_fill(SysDev S, JastrowState js, EcpBuf B, long W) {

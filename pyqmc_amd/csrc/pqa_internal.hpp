@@ -121,11 +121,7 @@ struct pqa_handle {
   // scratch
   DevBuf b_pts, b_motmp, b_out, b_widx, b_mask, b_ao, b_flag, b_newpos, b_aux, b_accept, b_accrec, b_acccnt, b_accw, b_dwrap, b_wrap, b_epass, b_eptw[2], b_econ[2], b_eu0[2], b_tves, b_pgdet, b_pbcd0, b_pbcmask, b_pbcth, b_tmuold;
   int* d_colmap[2] = {nullptr, nullptr};  // [ndet_s][nmo_s] column of an orbital in a unique determinant, or -1
-  int ecp_wave = 0;  // PQA_ECP_WAVE=1: wave-per-walker ECP accumulation (A/B)
-  int ecp_point_lw = 1;  // PQA_ECP_POINT_LW=0: k_ecp_point on the planes instead of k_ecp_point_lw (A/B)
-  int ecp_acc_waves = 0; // PQA_ECP_ACC_WAVES: 1 / 4 waves per walker in k_ecp_accum / k_kinetic_coulomb (0: 4 while walkers x electrons <= 32768)
   int jas_fold_allowed = 1;  // PQA_JAS_FOLD=0: Voronoi reduction in every periodic Jastrow pair (A/B, bitwise check)
-  int ecp_lds = 1;       // PQA_ECP_LDS=0: first-generation k_ecp_count / k_ecp_fill (A/B)
   int ecp_nchan = 0, ecp_nterm = 0;
   long wrap_W = 0;
   DevBuf b_gauss, b_unif, b_kc, b_en, b_means, b_sign, b_log, b_ju;
@@ -187,8 +183,6 @@ struct pqa_handle {
   struct { int mode = 1, kb = -1, gm = 0, step_pre = 1; } lw;
   DevBuf b_rot, b_eunif, b_elocal, b_ecnt, b_eoff, b_epts[2], b_ewgt[2], b_epte[2], b_emo[2], b_ecp;
   DevBuf b_erat[2];  // Slater ratios of the ECP points, per spin (k_ecp_orbcol: the route that keeps no orbital rows in b_emo)
-  long en_W = 0;     // walkers of the evaluation whose per-walker rows b_en holds (pqa_energy_last)
-  int ecp_route_reported = -1;  // PQA_RES_DEBUG: the ECP orbital route last reported (energy_dev; 1: k_ecp_orbcol, 0: k_orb rows + dot product)
   int orb_tp = 0;  // 0 = automatic
   struct TpTune { float ms[2] = {1e30f, 1e30f}; int n[2] = {0, 0}; int choice = 0; };  // periodic k_orb: [0] 32-point, [1] 64-point tiles
   TpTune tp_tune[2][48];  // per chunk table (5 / 1 components) and log2 bucket of the point count
@@ -215,12 +209,31 @@ struct pqa_handle {
   // wave-per-walker sweep in one launch (pqa_ww.hpp).  mode (PQA_WW): -1 by shard size (up to max walkers), 0 off, 1 always.  50-determinant
   // water molecule, VMC step with energy, launches -> one launch: 0.722 -> 0.663 ms at 1 024 walkers, 0.884 -> 0.801 at 2 048, 1.428 -> 1.382 at 4 096, 2.25 -> 2.38 at 8 192
   struct { int mode = -1; long max = 4096; } ww;
-  // ECP point totals left on the device (pqa_energy.hip: small shards on the k_ecp_accum path; PQA_ECP_DEFER=0 reads them every time)
-  const double* en_d_ecp = nullptr;  // energy_dev: the ECP row(s) of its last evaluation (nullptr: no ECP)
-  long ecp_last_tot[2] = {0, 0};  // energy_dev: points of each spin's list in its last evaluation (-1: totals left on the device)
-  int ecp_last_nseg = 1;           // ... and the segments per walker of those lists (EcpBuf::nseg)
-  long* pin_tot = nullptr;  // pinned host words the scan kernels write the ECP point totals to (device-visible: hipHostMallocMapped)
-  int ecp_defer = 1;
+  // energy pass (energy_dev, pqa_energy.hip).  The five switches, read by energy_plan alone: ecp_wave (PQA_ECP_WAVE=1) wave-per-walker ECP
+  // accumulation; ecp_point_lw (PQA_ECP_POINT_LW=0) k_ecp_point on the planes instead of k_ecp_point_lw; ecp_acc_waves (PQA_ECP_ACC_WAVES) 1 / 4
+  // waves per walker in k_ecp_accum / k_kinetic_coulomb (0: 4 while walkers x electrons <= 32768); ecp_lds (PQA_ECP_LDS=0) first-generation
+  // k_ecp_count / k_ecp_fill; ecp_defer (PQA_ECP_DEFER=0) point totals read back in every evaluation (all A/B, tests).  stream / ev: the side
+  // stream the kinetic pass of a small shard runs on beside the ECP passes, with its fork, coordinates and hand-over events.  W: walkers of
+  // the evaluation whose per-walker rows b_en holds (pqa_energy_last); d_ecp: its ECP row(s) (nullptr: no ECP).  pin_tot: pinned,
+  // device-visible host words the scan kernel writes the point totals to.  Point totals may stay on the device (small shards): hint / hint_valid
+  // are the totals of the last evaluation that read them (every 16th of evals does) and pick the launch sizes in between.  last_*: the
+  // lists the last evaluation left — points per spin (-1: on the device, then last_dev points at them), their sum (pqa_last_ecp_points),
+  // segments per walker (EcpBuf::nseg).  ecp_route_reported / route_reported: what PQA_RES_DEBUG last printed (1: k_ecp_orbcol, 0: rows)
+  struct {
+    int ecp_wave = 0, ecp_point_lw = 1, ecp_acc_waves = 0, ecp_lds = 1, ecp_defer = 1;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    long W = 0;
+    const double* d_ecp = nullptr;
+    long* pin_tot = nullptr;
+    bool hint_valid = false;
+    long hint[2] = {0, 0}, evals = 0;
+    long last_tot[2] = {0, 0}, last_points = 0;
+    const long* last_dev[2] = {nullptr, nullptr};
+    int last_nseg = 1;
+    int ecp_route_reported = -1;
+    std::string route_reported;
+  } en;
   // the NEXT step's sweep draws (k_tile_draws) generated beside the energy pass of the current step: second tape set, its stream and events
   // (ahead_*: the step, seed and walker count the set was drawn for; on_device: the last sweep took its draws from k_tile_draws)
   struct {
@@ -232,11 +245,6 @@ struct pqa_handle {
     uint64_t ahead_seed = 0;
     long ahead_W = 0;
   } draw;
-  hipStream_t en_stream = nullptr;
-  hipEvent_t en_ev[3] = {nullptr, nullptr, nullptr};
-  bool ecp_hint_valid = false;
-  long ecp_hint[2] = {0, 0}, ecp_evals = 0;
-  const long* last_ecp_dev[2] = {nullptr, nullptr};
   long orb_p_hint = 0;  // launch_orb: points the next launch is expected to work on when its P is an upper bound (0: P)
   // density-matrix sampling (pqa_dm.hpp): per slot the auxiliary walkers (position, orbital row, density), the kept samples
   // and the orbitals at the configurations' electrons; accumulators of the estimator in dm_val / dm_norm
@@ -249,7 +257,6 @@ struct pqa_handle {
   bool saved_valid = false;
   bool jas_stale = false;  // fused sweeps move x without patching avalues/bvalues
   int saved_e = -1;
-  long last_ecp_points = 0;
   // measurement
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool profile = false;
@@ -433,9 +440,12 @@ int sweep_r8(pqa_handle* h, const MoveBuf& mb);
 bool ww_eligible(pqa_handle* h, long W);
 int sweep_ww(pqa_handle* h, const MoveBuf& mb);
 // pqa_energy.hip
-// assemble = false: the rows of b_en are left to the caller (k_energy_finish, from b_kc and en_d_ecp)
-int energy_dev(pqa_handle* h, double threshold, const double* rot, const double* unif, uint64_t seed, uint32_t step,
-               bool soa_current = false, bool aos_T_needed = true, bool assemble = true);
+// What a caller tells energy_dev about its evaluation.  soa_current: the lane-per-walker planes hold the live state (a fused sweep just ran);
+// aos_T_needed: the caller works on the walker-major inverses next (the DMC step's T-moves); assemble = false: the rows of b_en are left to
+// the caller (k_energy_finish, from b_kc and en.d_ecp); slater_only: the Slater factor's energy terms alone (the correlated evaluations add
+// every set's Jastrow themselves); host_totals: the ECP point totals are read on the host in this evaluation (en.last_tot >= 0 afterwards)
+struct EnergyOpts { bool soa_current = false, aos_T_needed = true, assemble = true, slater_only = false, host_totals = false; };
+int energy_dev(pqa_handle* h, double threshold, const double* rot, const double* unif, uint64_t seed, uint32_t step, const EnergyOpts& o = {});
 // pqa_dmcsteps.hip
 int scan_ints(pqa_handle* h, const int* c, long* o, long n, long Wm, long* marks);
 // pqa_create.hip

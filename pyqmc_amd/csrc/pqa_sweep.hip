@@ -340,10 +340,12 @@ extern "C" int pqa_vmc_sweeps(pqa_handle_t* h, double tstep, int nsteps, const d
     TRY(check_launch(h, "k_propose/k_accept"));
     if (accept_rec) TRY(copy_in(h, accept_rec + (size_t)step * N * W, h->b_accrec.p, (size_t)N * W));
     if (energy_mean) {
+      EnergyOpts eo;
+      eo.soa_current = lw; eo.aos_T_needed = false; eo.assemble = !finish1;
       TRY(energy_dev(h, threshold, ecp_rot ? ecp_rot + (size_t)step * nrot * 9 : nullptr,
-                     ecp_unif ? ecp_unif + (size_t)step * nrot * W : nullptr, seed, (uint32_t)step, lw, /*aos_T_needed=*/false, /*assemble=*/!finish1));
+                     ecp_unif ? ecp_unif + (size_t)step * nrot * W : nullptr, seed, (uint32_t)step, eo));
       if (finish1)
-        hipLaunchKernelGGL((k_energy_finish<>), dim3(nen + 1), dim3(256), 0, h->stream, (const double*)h->b_kc.p, h->en_d_ecp, h->ii_energy, W,
+        hipLaunchKernelGGL((k_energy_finish<>), dim3(nen + 1), dim3(256), 0, h->stream, (const double*)h->b_kc.p, h->en.d_ecp, h->ii_energy, W,
                            (double*)h->b_en.p, (double*)h->b_means.p + (size_t)step * nen, nen, (int*)h->b_accw.p, (int*)h->b_acccnt.p + step);
       else
         hipLaunchKernelGGL((k_row_means<>), dim3(nen), dim3(256), 0, h->stream, (const double*)h->b_en.p, W, (double*)h->b_means.p + (size_t)step * nen);
