@@ -669,6 +669,26 @@ int pqa_sr_moments_orb(pqa_handle_t* h, int P, const int32_t* src, const int32_t
                        double threshold, const double* rot, const double* unif, uint64_t seed, int64_t walker_chunk, double* en_mean,
                        double* moments, double* en_walker, double* dp_walker);
 
+/* pqa_sr_moments for complex columns: complex or twisted handles (complex determinant derivatives, complex local energy) and the
+   imaginary-part tail of the reference's serialised derivative matrix (LinearTransform.serialize_gradients, accumulators.py:134-150).
+     src / pos (P)      as pqa_sr_moments: sources 0 det_coeff, 1 acoeff, 2 bcoeff, 3 ccoeff (orbital sources 4 / 5 are refused);
+     ntail, tail        tail column t is i times primary column tail[t]; Pt = P + ntail columns in all.  An index outside 0 .. P - 1
+                        or named twice is refused;
+     walker_chunk       walkers per chunk; 0: as many as keep the two planes of a chunk's gathered columns within 256 MiB;
+     en_mean (7)        weighted means of ke, ee, ei, Re ecp, grad2, Re total, Im ecp (Im total = Im ecp; a real handle: 0);
+     moments            (Pt + 2, Pt) complex, (re, im) interleaved: rows dpidpj (Pt), dpH, dppsi.  No conjugation anywhere:
+                        dpidpj = dp^T diag(w f) dp is complex symmetric, exactly;
+     en_walker (W, 7)   the per-walker rows, or NULL;
+     dp_walker (W, Pt)  complex interleaved host array or NULL: the derivative matrix the moments were formed from (tests and tools).
+   With A = [dp | E | 1] = Ar + i Ai the product is Re M = Ar^T s Ar - Ai^T s Ai, Im M = Ar^T s Ai + Ai^T s Ar on the fp64 matrix
+   cores; a 32-column block without a column that can have an imaginary part (every Jastrow column, the 1 column, everything of a real
+   handle) stages no imaginary panel, so a block pair costs 1, 2 or 4 matrix instructions per step.  Fixed summation order (two calls
+   give the same bits); state left alone and saved gradient_value rows dropped as in pqa_sr_moments.  Real handles are accepted (their
+   imaginary parts are exactly zero).  Complex moments beyond 256 MiB are refused (<0): those go through the protocol route. */
+int pqa_sr_moments_c(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, int ntail, const int32_t* tail, double nodal_cutoff,
+                     const double* weights, double threshold, const double* rot, const double* unif, uint64_t seed, int64_t walker_chunk,
+                     double* en_mean, double* moments, double* en_walker, double* dp_walker);
+
 /* ---- variance of the local energy at parameter sets (variance optimisation) ------------------------------------------------------ */
 /* optvariance.py:44-54 on the resident walkers, for K sets of two-body Jastrow coefficients acoeff (K,natom,na,2),
    bcoeff (K,nb,3).  eoff (W) = Enref total - Enref ke per walker.  For set k:

@@ -12,7 +12,8 @@ Public names, argument meaning and returned keys are those of the reference's ``
   ``k_pgrad_mo``, ``k_j3_pgrad``).
 * On the device route (``sr_route``) ``avg`` takes energy means and moments from ONE call on the resident state (``pqa_sr_moments``):
   neither the walkers nor the derivative arrays come to the host.  With ``route="device"`` the orbital coefficients of an open
-  system are columns too (``pqa_sr_moments_orb``: ``k_sr_orb`` writes them straight into the gathered matrix).
+  system are columns too (``pqa_sr_moments_orb``: ``k_sr_orb`` writes them straight into the gathered matrix).  With
+  ``complex_device=True`` complex and twisted handles take the route as well (``pqa_sr_moments_c``: complex columns, complex energy).
 """
 
 import numpy as np
@@ -130,8 +131,16 @@ def sr_columns_orb(transform):
     return (np.concatenate(src), np.concatenate(pos)) if src else (np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))
 
 
-def _sr_device(wf):
-    """(device handle, None) when ``wf`` is ``generate_wf``'s product on one real handle, else (None, reason)."""
+def sr_columns_c(transform):
+    """``(src, pos, tail)`` of ``pqa_sr_moments_c``: ``sr_columns`` and the primary indices of the entries of complex-dtype keys, whose
+    ``1j *`` twins form the tail of the serialised derivative matrix (``LinearTransform.serialize_gradients``)."""
+    src, pos = sr_columns(transform)
+    return src, pos, np.flatnonzero(transform.complex_inds).astype(np.int32)
+
+
+def _sr_device(wf, complex_device=False):
+    """(device handle, None) when ``wf`` is ``generate_wf``'s product on one real handle - with ``complex_device`` also on a complex or
+    twisted one (``pqa_sr_moments_c``) -, else (None, reason)."""
     from . import wf as pwf
 
     if not isinstance(wf, pwf.MultiplyWF):
@@ -142,7 +151,7 @@ def _sr_device(wf):
     dev = wf.fused_device()
     if dev is None or not hasattr(dev, "sr_moments"):
         return None, "the factors do not share one device handle"
-    if dev.cplx or dev.twisted:
+    if (dev.cplx or dev.twisted) and not complex_device:
         return None, "complex orbitals / twisted cell"
     return dev, None
 
@@ -154,10 +163,11 @@ def sr_route(wf, sr):
     ``sr.transform`` a ``LinearTransform`` whose optimised keys are all among ``SR_SOURCES``; no injected ``gram``.  The orbital
     coefficients (``SR_ORBITAL_SOURCES``) are in the scope only when ``sr.route == "device"`` asks for them, and then for an open
     system (no ``_fold``, no cell) with at most 64 electrons and orbitals of a spin and moments within ``SR_MOMENT_BYTES``; with
-    ``route=None`` they keep the protocol route."""
+    ``route=None`` they keep the protocol route.  A complex or twisted handle is in the scope only for an ``sr`` built with
+    ``complex_device=True`` (``pqa_sr_moments_c``), and never with orbital coefficients."""
     from .energy import EnergyAccumulator
 
-    dev, why = _sr_device(wf)
+    dev, why = _sr_device(wf, getattr(sr, "complex_device", False))
     if dev is None:
         return "protocol", why
     if type(sr.enacc) is not EnergyAccumulator:
@@ -170,6 +180,8 @@ def sr_route(wf, sr):
     orbital = [k for k in other if k in SR_ORBITAL_SOURCES]
     if len(orbital) < len(other):
         return "protocol", "parameters without a device source: " + ", ".join(k for k in other if k not in orbital)
+    if orbital and (dev.cplx or dev.twisted):
+        return "protocol", "orbital coefficients (" + ", ".join(orbital) + ") of complex orbitals / a twisted cell"
     if orbital:
         if sr.route != "device":
             return "protocol", "orbital coefficients (" + ", ".join(orbital) + ") are device columns only on request: route='device' takes them"
@@ -185,6 +197,11 @@ def sr_route(wf, sr):
             return "protocol", why
     if sr.transform.nparams == 0:
         return "protocol", "no parameter is optimised"
+    if dev.cplx or dev.twisted:
+        pt = sr.transform.nparams + int(np.count_nonzero(sr.transform.complex_inds))
+        if (pt + 2) * pt * 16 > SR_MOMENT_BYTES:
+            return "protocol", f"the complex moments of {pt} columns exceed the {SR_MOMENT_BYTES >> 20} MiB the device call takes"
+        return "device", "one complex device handle (complex_device), device energy, every parameter has a device source"
     return "device", "one real device handle, device energy, every parameter has a device source"
 
 
@@ -198,16 +215,20 @@ class StochasticReconfiguration:
     ``route``: where ``avg`` forms its averages.  ``"protocol"``: derivatives through ``wf.pgradient()``, energies through the energy
     object, one product (``pqa_gram``).  ``"device"``: one ``pqa_sr_moments`` call on the resident state; ``NotImplementedError`` with
     the reason when ``sr_route`` says the case is out of its scope.  None (default): the device route when in scope, else the protocol
-    route.  ``last_route`` records what the last evaluation took."""
+    route.  ``last_route`` records what the last evaluation took.
+
+    ``complex_device``: with True a complex or twisted handle is in the device scope too (``pqa_sr_moments_c``: complex columns and
+    the imaginary-part tail of complex-dtype keys); False (default) keeps those on the protocol route."""
 
     def __init__(self, enacc, transform, nodal_cutoff=1e-3, eps=1e-1, inverse_strategy="pseudo_inverse", verbose=False, gram=None,
-                 route=None):
+                 route=None, complex_device=False):
         if route not in (None, "device", "protocol"):
             raise ValueError(f"route must be None, 'device' or 'protocol', got {route!r}")
         self.enacc, self.transform = enacc, transform
         self.nodal_cutoff, self.eps, self.inverse_strategy, self.verbose = nodal_cutoff, eps, inverse_strategy, verbose
         self._gram = gram
         self.route, self.last_route = route, None
+        self.complex_device = bool(complex_device)
 
     def resolve_route(self, wf):
         """The route ``avg`` takes for ``wf``: ``"device"`` or ``"protocol"`` (see ``route``)."""
@@ -234,16 +255,24 @@ class StochasticReconfiguration:
     def avg_resident(self, wf, weights=None):
         """``avg`` on the device route for the walkers resident behind ``wf``, without comparing them with a host container: binds
         the energy object, advances its call count and derives the key of the energy draws as ``EnergyAccumulator.__call__`` does,
-        then one ``pqa_sr_moments`` call (``pqa_sr_moments_orb`` when orbital coefficients are optimised)."""
+        then one ``pqa_sr_moments`` call (``pqa_sr_moments_orb`` when orbital coefficients are optimised; ``pqa_sr_moments_c`` on a
+        complex or twisted handle, whose ``ecp`` and ``total`` means are complex as ``EnergyAccumulator``'s are)."""
         from .energy import KEYS
 
-        dev, why = _sr_device(wf)
+        dev, why = _sr_device(wf, self.complex_device)
         if dev is None:
             raise NotImplementedError(f"StochasticReconfiguration.avg_resident: {why}")
         enacc = self.enacc
         enacc.bind(dev)
         enacc._calls += 1
         key = int(np.random.randint(0, 2**31 - 1)) if enacc.seed is None else enacc.seed + enacc._calls
+        if dev.cplx or dev.twisted:
+            src, pos, tail = sr_columns_c(self.transform)
+            en, m = dev.sr_moments_c(src, pos, tail, 1e-3, weights=weights, threshold=enacc.threshold, seed=key)
+            self.last_route = "device"
+            d = {k: (en[i] if k in ("ecp", "total") else en[i].real) for i, k in enumerate(KEYS)}
+            d["dpidpj"], d["dpH"], d["dppsi"] = m[:-2], m[-2], m[-1]
+            return d
         orbital = any(k in SR_ORBITAL_SOURCES for k in self.transform.to_opt)
         src, pos = (sr_columns_orb if orbital else sr_columns)(self.transform)
         # the reference regularises with the default cut-off in avg (:105)
@@ -253,10 +282,16 @@ class StochasticReconfiguration:
         d["dpidpj"], d["dpH"], d["dppsi"] = m[:-2], m[-2], m[-1]
         return d
 
+    @staticmethod
+    def _same_walkers(dev, configs):
+        if dev.twisted:  # twisted handles hold unfolded coordinates (the comparison of EnergyAccumulator.__call__)
+            return np.allclose(dev.configs(), configs.configs + configs.wrap @ configs.lvecs, rtol=0, atol=1e-9)
+        return np.array_equal(dev.configs(), configs.configs)
+
     def avg(self, configs, wf, weights=None):
         if self.resolve_route(wf) == "device":
-            dev = _sr_device(wf)[0]
-            if self.enacc.check_configs and not (dev.W == len(configs.configs) and np.array_equal(dev.configs(), configs.configs)):
+            dev = _sr_device(wf, self.complex_device)[0]
+            if self.enacc.check_configs and not (dev.W == len(configs.configs) and self._same_walkers(dev, configs)):
                 raise ValueError("walkers on the device differ from `configs`: call wf.recompute(configs) "
                                  "(or keep wf.updateinternals in step with configs.move) first")
             return self.avg_resident(wf, weights)
@@ -303,13 +338,15 @@ class StochasticReconfiguration:
 PGradTransform = StochasticReconfiguration
 
 
-def gradient_generator(mol, wf, to_opt=None, nodal_cutoff=1e-3, eps=1e-3, inverse_strategy="regularized_inverse", route=None, **ewald_kwargs):
+def gradient_generator(mol, wf, to_opt=None, nodal_cutoff=1e-3, eps=1e-3, inverse_strategy="regularized_inverse", route=None,
+                       complex_device=False, **ewald_kwargs):
     """The gradient object of line minimisation (``observables/accumulators.py:27-42``): an ``EnergyAccumulator`` and the
-    ``LinearTransform`` of ``to_opt`` in a ``StochasticReconfiguration``.  ``route``: see ``StochasticReconfiguration``;
-    ``"device"`` is checked against ``wf`` here already."""
+    ``LinearTransform`` of ``to_opt`` in a ``StochasticReconfiguration``.  ``route`` / ``complex_device``: see
+    ``StochasticReconfiguration``; ``"device"`` is checked against ``wf`` here already."""
     from .energy import EnergyAccumulator
 
     sr = StochasticReconfiguration(EnergyAccumulator(mol, **ewald_kwargs), LinearTransform(wf.parameters, to_opt),
-                                   nodal_cutoff=nodal_cutoff, eps=eps, inverse_strategy=inverse_strategy, route=route)
+                                   nodal_cutoff=nodal_cutoff, eps=eps, inverse_strategy=inverse_strategy, route=route,
+                                   complex_device=complex_device)
     sr.resolve_route(wf)  # (route="device" out of scope: NotImplementedError now, not at the first block)
     return sr

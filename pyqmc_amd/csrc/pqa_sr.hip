@@ -25,6 +25,10 @@
 //   k_sr_orb         a block per walker: wu and B in LDS, G tile by tile on v_mfma_f64_16x16x4_f64, every entry stored through the
 //                    inverse column map colof straight into the chunk's A (entries nobody optimises are dropped);
 //   k_sr_gather      then fills the other columns and leaves the orbital ones alone.
+//
+// pqa_sr_moments_c takes complex and twisted handles (complex d_det, complex local energy) and the imaginary-part tail of the
+// reference's serialised matrix, with kernels of its own (k_sr_gather_c, k_sr_syrk_c, k_sr_reduce_c below): planar real / imaginary
+// panels, one to four matrix instructions per k-step by what the two column blocks of a tile can hold.
 #include "pqa_estim.hpp"
 
 namespace {
@@ -228,6 +232,145 @@ __global__ __launch_bounds__(256) void k_sr_reduce(const double* __restrict__ pa
   mom[idx] = first ? s : mom[idx] + s;
 }
 
+// ---- complex columns (pqa_sr_moments_c) -------------------------------------------------------------------------------------------------
+// dp is complex on a complex / twisted handle (d_det is; the Jastrow sums stay real) and the reference's serialised matrix carries, after
+// the P primary columns, ntail columns i dp[:, tail[t]].  With A = [dp | E | 1] = Ar + i Ai (planar, (Wc, Pt + 2) each, Pt = P + ntail)
+// the moments M = A^T diag(s) A[:, :Pt] (no conjugation: M is complex symmetric) are
+//   Re M = Ar^T s Ar - Ai^T s Ai,   Im M = Ar^T s Ai + Ai^T s Ar.
+
+// One thread per (walker of the chunk, column of A): primary column i gets (Re, Im) of its source entry (sources 1 - 3 are real; source 0
+// of a complex handle is the interleaved b_pgdet), tail column t gets i times its twin: (-Im, Re).  Column Pt is (Re total, Im ecp),
+// column Pt + 1 is (1, 0).  en: [7][W] on a complex handle, [6][W] on a real one (whose imaginary plane is zero).  dpz: the chunk's
+// interleaved (Wc, Pt) dp for the caller that asked for it, or nullptr.
+__global__ __launch_bounds__(256) void k_sr_gather_c(SrSources S, const int* __restrict__ src, const int* __restrict__ pos, int P,
+                                                     const int* __restrict__ tail, int ntail, int cplx, const double* __restrict__ en,
+                                                     const double* __restrict__ wts, const double* __restrict__ wsum, double cutoff, long W,
+                                                     long w0, long Wc, double* __restrict__ Ar, double* __restrict__ Ai,
+                                                     double* __restrict__ scale /*[Wc]*/, double* __restrict__ dpz) {
+  const int Pt = P + ntail, lda = Pt + 2;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= Wc * lda) return;
+  const long bw = idx / lda, w = w0 + bw;
+  const int i = (int)(idx - bw * lda);
+  double re, im = 0.0;
+  if (i < Pt) {
+    const int c = i < P ? i : tail[i - P], s = src[c];
+    if (s == 0 && cplx) {
+      const double* z = S.base[0] + 2 * ((size_t)w * S.stride[0] + pos[c]);
+      re = z[0]; im = z[1];
+    } else
+      re = S.base[s][(size_t)w * S.stride[s] + pos[c]];
+    if (i >= P) { const double t = re; re = -im; im = t; }
+    if (dpz) { dpz[2 * ((size_t)bw * Pt + i)] = re; dpz[2 * ((size_t)bw * Pt + i) + 1] = im; }
+  } else if (i == Pt) {
+    re = en[5 * W + w];
+    if (cplx) im = en[6 * W + w];
+  } else
+    re = 1.0;
+  Ar[idx] = re;
+  Ai[idx] = im;
+  if (i == 0) scale[bw] = sr_weight(wts, wsum, W, w) * sr_nodal_f(en[4 * W + w], cutoff);
+}
+
+// The tile of one block of k_sr_syrk_c.  FI / FJ: the left / right column block holds a column that can have an imaginary part, so its
+// imaginary panel is staged too.  MFMAs per k-step: 1 (neither), 2 (one of them), 4 (both): Lr Rr [- Li Ri] and [Lr Ri] [+ Li Rr].
+template <bool FI, bool FJ>
+__device__ __forceinline__ void sr_syrk_c_tile(const double* __restrict__ Ar, const double* __restrict__ Ai, const double* __restrict__ scale,
+                                               long Wc, int Pt, long per, double* __restrict__ part, double* Lr, double* Li, double* Rr,
+                                               double* Ri) {
+  const int bj = blockIdx.x, bi = blockIdx.y, sl = blockIdx.z;
+  const int lda = Pt + 2;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, i16 = lane & 15, kq = lane >> 4, wi = wave >> 1, wj = wave & 1;
+  const long k_lo = (long)sl * per, k_hi = k_lo + per < Wc ? k_lo + per : Wc;
+  // staging: thread t holds rows r0 and r0 + 8 of column c of each staged 16 x 32 panel
+  const int c = t & 31, r0 = t >> 5;
+  const int ca = bi * 32 + c, cb = bj * 32 + c;
+  const bool ain = ca < lda, bin = cb < Pt;
+  double vlr[2], vli[2], vrr[2], vri[2];
+  auto fetch = [&](long k0) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const long row = k0 + r0 + 8 * q;
+      const bool rin = row < k_hi;
+      const double s = (rin && bin) ? scale[row] : 0.0;
+      vlr[q] = (rin && ain) ? Ar[(size_t)row * lda + ca] : 0.0;
+      if (FI) vli[q] = (rin && ain) ? Ai[(size_t)row * lda + ca] : 0.0;
+      vrr[q] = (rin && bin) ? Ar[(size_t)row * lda + cb] * s : 0.0;
+      if (FJ) vri[q] = (rin && bin) ? Ai[(size_t)row * lda + cb] * s : 0.0;
+    }
+  };
+  d4 re = {0.0, 0.0, 0.0, 0.0}, im = {0.0, 0.0, 0.0, 0.0};
+  if (k_lo < k_hi) fetch(k_lo);
+  for (long k0 = k_lo; k0 < k_hi; k0 += kSrKB) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int o = (r0 + 8 * q) * kSrLd + c;
+      Lr[o] = vlr[q];
+      if (FI) Li[o] = vli[q];
+      Rr[o] = vrr[q];
+      if (FJ) Ri[o] = vri[q];
+    }
+    __syncthreads();
+    if (k0 + kSrKB < k_hi) fetch(k0 + kSrKB);  // (the next step's loads fly while this one multiplies)
+#pragma unroll
+    for (int kk = 0; kk < kSrKB / 4; ++kk) {
+      const int oa = (kk * 4 + kq) * kSrLd + wi * 16 + i16, ob = (kk * 4 + kq) * kSrLd + wj * 16 + i16;
+      const double lr = Lr[oa], rr = Rr[ob];
+      re = __builtin_amdgcn_mfma_f64_16x16x4f64(lr, rr, re, 0, 0, 0);
+      if (FI && FJ) re = __builtin_amdgcn_mfma_f64_16x16x4f64(-Li[oa], Ri[ob], re, 0, 0, 0);
+      if (FJ) im = __builtin_amdgcn_mfma_f64_16x16x4f64(lr, Ri[ob], im, 0, 0, 0);
+      if (FI) im = __builtin_amdgcn_mfma_f64_16x16x4f64(Li[oa], rr, im, 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  const int ti = 2 * bi + wi, tj = 2 * bj + wj;
+  if (ti > tj && ti * 16 + 15 < Pt) return;
+  // lane holds D[row = kq + 4 r][col = i16]; the two planes of slice sl follow each other
+  const size_t n = (size_t)lda * Pt;
+  double* pr = part + (size_t)sl * 2 * n;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int p = ti * 16 + kq + 4 * r, q = tj * 16 + i16;
+    if (p < lda && q < Pt) {
+      pr[(size_t)p * Pt + q] = re[r];
+      pr[n + (size_t)p * Pt + q] = im[r];
+    }
+  }
+}
+
+// part[sl][plane] (Pt + 2, Pt) = tile (32 bi .., 32 bj ..) of A^T diag(s) A[:, :Pt] over the walkers of slice sl, with k_sr_syrk's
+// mapping: grid = (column blocks, row blocks, slices), block = 256, wave (wi, wj) owns the 16 x 16 tile (2 bi + wi, 2 bj + wj); blocks and
+// wave tiles strictly below the diagonal are skipped unless they hold a row >= Pt.  flag[b]: column block b of A holds a column that
+// can have an imaginary part; the choice of the tile's form is block-uniform.
+__global__ __launch_bounds__(256) void k_sr_syrk_c(const double* __restrict__ Ar, const double* __restrict__ Ai, const double* __restrict__ scale,
+                                                   const int* __restrict__ flag, long Wc, int Pt, long per, double* __restrict__ part) {
+  __shared__ double Lr[kSrKB * kSrLd], Li[kSrKB * kSrLd], Rr[kSrKB * kSrLd], Ri[kSrKB * kSrLd];
+  const int bj = blockIdx.x, bi = blockIdx.y;
+  if (bi > bj && bi * 32 + 31 < Pt) return;
+  const bool fi = flag[bi] != 0, fj = flag[bj] != 0;
+  if (fi && fj) sr_syrk_c_tile<true, true>(Ar, Ai, scale, Wc, Pt, per, part, Lr, Li, Rr, Ri);
+  else if (fi) sr_syrk_c_tile<true, false>(Ar, Ai, scale, Wc, Pt, per, part, Lr, Li, Rr, Ri);
+  else if (fj) sr_syrk_c_tile<false, true>(Ar, Ai, scale, Wc, Pt, per, part, Lr, Li, Rr, Ri);
+  else sr_syrk_c_tile<false, false>(Ar, Ai, scale, Wc, Pt, per, part, Lr, Li, Rr, Ri);
+}
+
+// mom (Pt + 2, Pt) complex interleaved = (first ? 0 : mom) + sum over the slices in slice order of both planes; element (i, j) of the
+// symmetric block is read at (min, max): the tiles below the diagonal were never written.
+__global__ __launch_bounds__(256) void k_sr_reduce_c(const double* __restrict__ part, int Pt, int nslice, int first, double* __restrict__ mom) {
+  const long n = (long)(Pt + 2) * Pt;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n) return;
+  const int i = (int)(idx / Pt), j = (int)(idx - (long)i * Pt);
+  const long from = (i < Pt && j < i) ? (long)j * Pt + i : idx;
+  double sr = 0.0, si = 0.0;
+  for (int sl = 0; sl < nslice; ++sl) {
+    sr += part[(size_t)sl * 2 * n + from];
+    si += part[(size_t)sl * 2 * n + n + from];
+  }
+  mom[2 * idx] = first ? sr : mom[2 * idx] + sr;
+  mom[2 * idx + 1] = first ? si : mom[2 * idx + 1] + si;
+}
+
 }  // namespace
 
 // Both entries.  fn: the entry's name (its messages); orb: sources 4 / 5 are accepted; chunk: walkers per chunk (0: the scratch rule);
@@ -398,4 +541,152 @@ extern "C" int pqa_sr_moments_orb(pqa_handle_t* h, int P, const int32_t* src, co
                                   double* en_mean, double* moments, double* en_walker, double* dp_walker) {
   return sr_moments(h, "pqa_sr_moments_orb", true, P, src, pos, nodal_cutoff, weights, threshold, rot, unif, seed, (long)walker_chunk, en_mean,
                     moments, en_walker, dp_walker);
+}
+
+// The complex entry: the steps of sr_moments with complex columns (k_sr_gather_c, k_sr_syrk_c, k_sr_reduce_c).  Real handles are taken
+// too (zero imaginary planes, six energy rows): a cross-check against pqa_sr_moments.
+extern "C" int pqa_sr_moments_c(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, int ntail, const int32_t* tail,
+                                double nodal_cutoff, const double* weights, double threshold, const double* rot, const double* unif,
+                                uint64_t seed, int64_t walker_chunk_arg, double* en_mean, double* moments, double* en_walker,
+                                double* dp_walker) {
+  const std::string fn = "pqa_sr_moments_c";
+  // argument checks first: they need nothing but the handle's host-side sizes
+  if (P < 1) FAIL(fn + ": P must be at least 1");
+  if (!src || !pos || !en_mean || !moments) FAIL(fn + ": src, pos, en_mean and moments must not be NULL");
+  if (ntail < 0 || ntail > P || (ntail > 0 && !tail)) FAIL(fn + ": ntail must be within 0 .. P, with tail given");
+  if (!(nodal_cutoff > 0.0)) FAIL(fn + ": nodal_cutoff must be positive");
+  const long size[4] = {h->has_slater ? (long)h->ndet : 0, h->has_j2 ? (long)h->natom * h->na * 2 : 0, h->has_j2 ? (long)h->nb * 3 : 0,
+                        h->has_j3 ? (long)h->natom * h->na3 * h->na3 * h->nb3 * 3 : 0};
+  bool need[4] = {false, false, false, false};
+  for (int i = 0; i < P; ++i) {
+    if (src[i] == 4 || src[i] == 5) FAIL(fn + ": orbital coefficients are not a source here (complex / periodic layouts: use the protocol route)");
+    if (src[i] < 0 || src[i] > 3) FAIL(fn + ": src must be 0 (det_coeff), 1 (acoeff), 2 (bcoeff) or 3 (ccoeff)");
+    if (pos[i] < 0 || pos[i] >= size[src[i]]) FAIL(fn + ": pos outside the parameter src names (or the handle has no such factor)");
+    need[src[i]] = true;
+  }
+  {
+    std::vector<char> seen((size_t)P, 0);
+    for (int t = 0; t < ntail; ++t) {
+      if (tail[t] < 0 || tail[t] >= P) FAIL(fn + ": tail names a primary column out of range");
+      if (seen[tail[t]]) FAIL(fn + ": tail names a primary column twice");
+      seen[tail[t]] = 1;
+    }
+  }
+  if (walker_chunk_arg < 0) FAIL(fn + ": walker_chunk must not be negative");
+  const int Pt = P + ntail, lda = Pt + 2;
+  const size_t nmom = (size_t)lda * Pt;  // complex entries of the moments
+  if (2 * nmom * sizeof(double) > kChunkScratchBytes) FAIL(fn + ": the (Pt + 2) x Pt complex moments exceed the 256 MiB scratch limit (use the protocol route)");
+  if (h->W == 0) FAIL("state not initialised (call pqa_wf_recompute)");
+  TRY(sync_aos(h));
+  HIPCHK(hipSetDevice(h->device));
+  const long W = h->W;
+  const int cplx = h->cplx ? 1 : 0, nen = cplx ? 7 : 6;
+  h->saved_valid = false;  // (as pqa_energy: the saved orbital rows of a gradient_value call are overwritten)
+  TRY(energy_dev(h, threshold, rot, unif, seed, 0u));
+  const double* d_en = (const double*)h->b_en.p;
+  // derivative sources
+  SrSources S{};
+  if (need[0]) {
+    TRY(slater_value_dev(h));  // sign (complex: phase) / log of the determinant expansion -> b_sign, b_log
+    TRY(ensure(h, h->b_pgdet, (size_t)(cplx ? 2 : 1) * W * h->ndet * sizeof(double)));
+    const dim3 gd((unsigned)((W * h->ndet + 255) / 256));
+    if (cplx)
+      hipLaunchKernelGGL((k_pgrad_det_c<>), gd, dim3(256), 0, h->stream, h->S, h->st, (const double*)h->b_sign.p, (const double*)h->b_log.p, W,
+                         (double*)h->b_pgdet.p);
+    else
+      hipLaunchKernelGGL((k_pgrad_det<>), gd, dim3(256), 0, h->stream, h->S, h->st, (const double*)h->b_sign.p, (const double*)h->b_log.p, W,
+                         (double*)h->b_pgdet.p);
+    TRY(check_launch(h, "k_pgrad_det"));
+    S.base[0] = (const double*)h->b_pgdet.p; S.stride[0] = size[0];
+  }
+  if (need[1] || need[2]) {
+    TRY(jas_refresh(h));
+    S.base[1] = h->js.avalues; S.stride[1] = size[1];
+    S.base[2] = h->js.bvalues; S.stride[2] = size[2];
+  }
+  if (need[3]) {
+    const size_t lds = ((size_t)h->N * h->natom * h->na3 + (size_t)h->N * (h->N - 1) / 2 * h->nb3) * sizeof(double);
+    if (lds > 150 * 1024) FAIL("three-body parameter gradient: the a/b value tables of one walker do not fit LDS");
+    TRY(ensure(h, h->b_out, (size_t)W * size[3] * sizeof(double)));
+    if (lds > 64 * 1024) TRY(raise_lds_limit(h, reinterpret_cast<const void*>(k_j3_pgrad<>)));
+    hipLaunchKernelGGL((k_j3_pgrad<>), dim3((unsigned)W), dim3(64), lds, h->stream, h->S, h->js, (double*)h->b_out.p);
+    TRY(check_launch(h, "k_j3_pgrad"));
+    S.base[3] = (const double*)h->b_out.p; S.stride[3] = size[3];
+  }
+  // one flag per 32-column block of A: does it hold a column that can have an imaginary part (source 0 of a complex handle, a tail
+  // column, the E column of a complex handle)
+  const int nbi = (lda + 31) / 32, nbj = (Pt + 31) / 32;
+  std::vector<int> flag((size_t)nbi, 0);
+  for (int i = 0; i < P; ++i)
+    if (cplx && src[i] == 0) flag[i / 32] = 1;
+  for (int i = P; i < Pt; ++i) flag[i / 32] = 1;
+  if (cplx) flag[Pt / 32] = 1;
+  // scratch: [moments (2 nmom) | means (7) | weight sum (1) | weights (W) | per-walker energies (W, nen) | scale (Wc) | Ar, Ai (Wc, Pt + 2) |
+  // interleaved dp (Wc, Pt) when asked for | partials (nslice, 2, Pt + 2, Pt) | src, pos, tail, flag]
+  long Wc = walker_chunk(W, (size_t)2 * lda * sizeof(double));
+  if (walker_chunk_arg > 0) Wc = std::min<long>(Wc, (long)walker_chunk_arg);
+  long nslice = std::min<long>(std::max<long>(1, 1024 / ((long)nbi * nbj)), std::max<long>(1, Wc / 64));
+  nslice = std::max<long>(1, std::min<long>(nslice, (long)(kChunkScratchBytes / (2 * nmom * sizeof(double)))));
+  const size_t nw = weights ? (size_t)W : 0, nenw = en_walker ? (size_t)nen * W : 0, ndp = dp_walker ? (size_t)2 * Wc * Pt : 0;
+  const size_t ndbl = 2 * nmom + 7 + 1 + nw + nenw + (size_t)Wc + (size_t)2 * Wc * lda + ndp + (size_t)nslice * 2 * nmom;
+  TRY(ensure(h, h->b_sr, ndbl * sizeof(double) + ((size_t)2 * P + ntail + nbi) * sizeof(int)));
+  double* d_mom = (double*)h->b_sr.p;
+  double* d_mean = d_mom + 2 * nmom;
+  double* d_wsum = d_mean + 7;
+  double* d_wts = d_wsum + 1;
+  double* d_enw = d_wts + nw;
+  double* d_scale = d_enw + nenw;
+  double* d_Ar = d_scale + Wc;
+  double* d_Ai = d_Ar + (size_t)Wc * lda;
+  double* d_dp = d_Ai + (size_t)Wc * lda;
+  double* d_part = d_dp + ndp;
+  int* d_src = (int*)(d_part + (size_t)nslice * 2 * nmom);
+  int* d_pos = d_src + P;
+  int* d_tail = d_pos + P;
+  int* d_flag = d_tail + ntail;
+  TRY(copy_in(h, d_src, src, (size_t)P * sizeof(int)));
+  TRY(copy_in(h, d_pos, pos, (size_t)P * sizeof(int)));
+  TRY(copy_in(h, d_tail, tail, (size_t)ntail * sizeof(int)));
+  TRY(copy_in(h, d_flag, flag.data(), (size_t)nbi * sizeof(int)));
+  HIPCHK(hipStreamSynchronize(h->stream));  // (flag is a local: the copy has read it before it goes)
+  const double* wts = nullptr;
+  if (weights) {
+    TRY(copy_in(h, d_wts, weights, (size_t)W * sizeof(double)));
+    hipLaunchKernelGGL(k_sr_wsum, dim3(1), dim3(256), 0, h->stream, (const double*)d_wts, W, d_wsum);
+    TRY(check_launch(h, "k_sr_wsum"));
+    wts = d_wts;
+  }
+  hipLaunchKernelGGL(k_sr_means, dim3((unsigned)nen), dim3(256), 0, h->stream, d_en, wts, (const double*)d_wsum, W, d_mean);
+  TRY(check_launch(h, "k_sr_means"));
+  for (long w0 = 0; w0 < W; w0 += Wc) {
+    const long wc = std::min(Wc, W - w0);
+    const long ns = std::min<long>(nslice, std::max<long>(1, wc / 64));
+    const long per = ((wc + ns - 1) / ns + kSrKB - 1) / kSrKB * kSrKB;  // walkers per slice, whole staging steps
+    hipLaunchKernelGGL(k_sr_gather_c, dim3((unsigned)((wc * lda + 255) / 256)), dim3(256), 0, h->stream, S, (const int*)d_src, (const int*)d_pos, P,
+                       (const int*)d_tail, ntail, cplx, d_en, wts, (const double*)d_wsum, nodal_cutoff, W, w0, wc, d_Ar, d_Ai, d_scale,
+                       dp_walker ? d_dp : nullptr);
+    TRY(check_launch(h, "k_sr_gather_c"));
+    if (dp_walker)  // the chunk's dp, before the next chunk overwrites it
+      TRY(copy_out(h, dp_walker + (size_t)2 * w0 * Pt, d_dp, (size_t)2 * wc * Pt * sizeof(double)));
+    hipLaunchKernelGGL(k_sr_syrk_c, dim3((unsigned)nbj, (unsigned)nbi, (unsigned)ns), dim3(256), 0, h->stream, (const double*)d_Ar,
+                       (const double*)d_Ai, (const double*)d_scale, (const int*)d_flag, wc, Pt, per, d_part);
+    TRY(check_launch(h, "k_sr_syrk_c"));
+    hipLaunchKernelGGL(k_sr_reduce_c, dim3((unsigned)((nmom + 255) / 256)), dim3(256), 0, h->stream, (const double*)d_part, Pt, (int)ns,
+                       (int)(w0 == 0), d_mom);
+    TRY(check_launch(h, "k_sr_reduce_c"));
+  }
+  TRY(copy_in(h, moments, d_mom, 2 * nmom * sizeof(double)));
+  if (en_walker) {
+    transpose(h, d_en, d_enw, nen, W);  // rows (nen, W) -> (W, nen)
+    TRY(check_launch(h, "k_transpose"));
+    HIPCHK(hipMemcpy2DAsync(en_walker, 7 * sizeof(double), d_enw, (size_t)nen * sizeof(double), (size_t)nen * sizeof(double), (size_t)W,
+                            hipMemcpyDeviceToHost, h->stream));
+  }
+  TRY(copy_out(h, en_mean, d_mean, (size_t)nen * sizeof(double)));
+  if (!cplx) {  // a real handle has no seventh row
+    en_mean[6] = 0.0;
+    if (en_walker)
+      for (long w = 0; w < W; ++w) en_walker[7 * w + 6] = 0.0;
+  }
+  return 0;
 }

@@ -366,6 +366,32 @@ class DeviceWF:
                   _ffi.ptr(dp))
         return (en_mean, moments) + ((en_walker,) if per_walker else ()) + ((dp,) if dp_walker else ())
 
+    def sr_moments_c(self, src, pos, tail, nodal_cutoff, weights=None, threshold=10.0, rot=None, unif=None, seed=0, per_walker=False,
+                     walker_chunk=0, dp_walker=False):
+        """``pqa_sr_moments_c``: ``sr_moments`` with complex columns, for complex / twisted handles (real ones are taken too).
+        ``src`` / ``pos`` (P) as there (sources 0 - 3); ``tail``: primary indices whose ``1j *`` twins follow the P primary columns
+        (``LinearTransform.complex_inds``), Pt = P + len(tail).  Returns (en_mean (6) complex, moments (Pt + 2, Pt) complex: rows
+        dpidpj, dpH, dppsi[, en_walker (W, 6) complex with ``per_walker``][, dp (W, Pt) complex with ``dp_walker``])."""
+        src, pos = np.ascontiguousarray(src, dtype=np.int32), np.ascontiguousarray(pos, dtype=np.int32)
+        tail = np.ascontiguousarray(tail, dtype=np.int32)
+        P, ntail = len(src), len(tail)
+        if src.shape != (P,) or pos.shape != (P,) or tail.shape != (ntail,):
+            raise ValueError(f"src, pos (equally long) and tail must be one-dimensional, got {src.shape}, {pos.shape}, {tail.shape}")
+        w = None if weights is None else _ffi.f64(weights)
+        if w is not None and w.shape != (self.W,):
+            raise ValueError(f"weights ({self.W},) expected, got {w.shape}")
+        rot = None if rot is None else _ffi.f64(rot)
+        unif = None if unif is None else _ffi.f64(unif)
+        Pt = P + ntail
+        en_mean, moments = np.empty(7), np.empty((Pt + 2, Pt), dtype=complex)
+        en_walker = np.empty((self.W, 7)) if per_walker else None
+        dp = np.empty((self.W, Pt), dtype=complex) if dp_walker else None
+        self.call("pqa_sr_moments_c", int(P), _ffi.ptr(src), _ffi.ptr(pos), int(ntail), _ffi.ptr(tail) if ntail else None, float(nodal_cutoff),
+                  _ffi.ptr(w), float(threshold), _ffi.ptr(rot), _ffi.ptr(unif), int(seed), int(walker_chunk), _ffi.ptr(en_mean),
+                  _ffi.ptr(moments), _ffi.ptr(en_walker), _ffi.ptr(dp))
+        out = (self._complex_energy(en_mean, 0), moments)
+        return out + ((self._complex_energy(en_walker, 1),) if per_walker else ()) + ((dp,) if dp_walker else ())
+
     def variance(self, acoeff, bcoeff, eoff, grad=False, ke=False):
         """``pqa_variance``: population variance over the resident walkers of ``eoff + ke_k`` at K sets of two-body Jastrow
         coefficients, acoeff (K, natom, na, 2) and bcoeff (K, nb, 3), with ``eoff`` (W) the fixed part of the local energy ->
