@@ -719,6 +719,44 @@ int pqa_variance(pqa_handle_t* h, int K, const double* acoeff, const double* bco
 int pqa_overlap_sweeps(pqa_handle_t* const* hs, int K, double tstep, int nsteps, const double* gauss, const double* unif,
                        double* overlap, double* weights, double* acc_ratio);
 
+/* ---- estimators over the mixture of several wave functions (excited-state optimisation) ------------------------------------------- */
+/* StochasticReconfigurationMultipleWF.avg (stochastic_reconfiguration.py:195-227) and EnergyAccumulatorMultipleWF.avg
+   (accumulators_multiwf.py:29-60) on the walkers resident on the K handles hs[0..K-1] (which hold the same walkers, e.g. after
+   pqa_overlap_sweeps), without the walkers, the per-walker energies or the derivative arrays crossing the bus.  With compute_weights'
+   (sample_many.py:42-55) a_k = phase_k exp(log|Psi_k| - max_j log|Psi_j|), rho = mean_k a_k^2 and weights[i][j][c] = a_i (a_j / rho)
+   per walker c (its nan_to_num rules included; the code is pqa_overlap_sweeps'):
+     overlap (K, K)      mean_c weights[i][j][c],
+     en (6, K, K)        en[r][i][j] = sum_c (E_j^r(c) - offset) weights[i][j][c] / W for the rows r = ke, ee, ei, ecp, grad2, total of
+                         state j's local energy,
+     moments             state after state, for the states with P[i] > 0, (P[i] + 2K, P[i]) row-major: rows 0 .. P[i]-1
+                         dpipj = sum_c dp_p dp_q weights[i][i][c] / W; rows P[i] + j: dp[:, j] = sum_c dp_p weights[i][j][c] / W; rows
+                         P[i] + K + j: dpH[:, j] = sum_c E_j dp_p weights[i][j][c] / W with E_j state j's total energy (no offset),
+     u_walker (K, W)     a_k / sqrt(rho) per walker, or NULL,
+     en_walker (K, W, 6) every state's per-walker energies, or NULL: nothing of size W leaves the device.
+   Column q of state i's derivative matrix dp (W, P[i]) is entry pos[q] (flat C-order index) of the parameter src[q] names on hs[i]:
+   0 det_coeff (ndet), 1 acoeff (natom, na, 2), 2 bcoeff (nb, 3); src and pos hold sum_i P[i] entries, state after state; P[i] = 0: the
+   state has no columns (all zero: only overlap and en are formed).  Each handle runs pqa_energy's pass with its own key seeds[k], or,
+   with rot / unif given, its own set of draws (K sets as pqa_energy takes them, one after the other): the per-walker energies are the
+   bits pqa_energy gives for that key.  The weights have rank one per walker, so all moments of a state are one product
+   A^T diag(1 / (rho W)) A[:, :P] with A = [a_i dp | a_0 .. a_{K-1} | E_0 a_0 .. E_{K-1} a_{K-1}]: it runs on the fp64 matrix cores over
+   walker chunks of at most 256 MiB of gathered columns (walker_chunk > 0: at most that many walkers per chunk); the walker sums have
+   a fixed order (two calls give the same bits; the result does not depend on walker_chunk) and dpipj is exactly symmetric.
+   Scope: pqa_overlap_sweeps' (real Slater x two-body Jastrow handles, any number of determinants, open boundaries, one device, equal
+   W, N and nelec_up, distinct handles, K <= 8) and sources 0 - 2; periodic, twisted, complex or three-body handles, other sources and
+   moments of a state beyond 256 MiB are refused (<0): those go through the protocol route.  All K handles' work runs on hs[0]'s
+   stream; errors are reported on hs[0].  The walkers, inverses, determinants and coefficients are not written; as pqa_sr_moments the
+   call syncs a lane-per-walker layout back, drops saved gradient_value rows and refreshes stale basis sums.
+
+   pqa_mix_wtdp: StochasticReconfigurationWfbyWf.avg (ensemble_optimization_wfbywf.py:57-66): wtdp[j][k][p] = sum_c dp_p(c)
+   weights[j][k][c] / W with the derivatives dp (W, P) of the LAST state hs[K-1] (src, pos as above, P >= 1), and overlap (K, K).  No
+   energy pass.  The thin product of the K (K + 1) / 2 weight columns with j <= k against dp, on the same kernels; wtdp[j][k] and
+   wtdp[k][j] are the same row (equal bits).  Scope, stream, determinism and writes as pqa_mix_moments. */
+int pqa_mix_moments(pqa_handle_t* const* hs, int K, const int32_t* P, const int32_t* src, const int32_t* pos, double offset,
+                    double threshold, const double* rot, const double* unif, const uint64_t* seeds, int64_t walker_chunk,
+                    double* overlap, double* en, double* moments, double* u_walker, double* en_walker);
+int pqa_mix_wtdp(pqa_handle_t* const* hs, int K, int P, const int32_t* src, const int32_t* pos, int64_t walker_chunk, double* overlap,
+                 double* wtdp);
+
 /* ---- superposition of several wave functions (AddWF) ------------------------------------------------------------------------------- */
 /* Psi = sum_k coeffs[k] Psi_k (pyqmc/wf/addwf.py) over the walkers resident on the K handles hs[0..K-1], which hold the same walkers.
    With w_k = coeffs[k] Psi_k / Psi per walker (sum_k w_k = 1), formed as c_k sign_k exp(log|Psi_k| - max_j log|Psi_j|) over their sum

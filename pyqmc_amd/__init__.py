@@ -20,7 +20,8 @@ from .symmetry import SymmetryAccumulator, SymmetryAccumulatorPBC  # noqa: F401
 from .sq import SqAccumulator  # noqa: F401
 from . import ewald2d  # noqa: F401
 from .ewald2d import SlabEnergyAccumulator  # noqa: F401
-from .accumulators import LinearTransform, PGradTransform, StochasticReconfiguration, gradient_generator  # noqa: F401
+from .accumulators import (LinearTransform, PGradTransform, StochasticReconfiguration, StochasticReconfigurationMultipleWF,  # noqa: F401
+                           gradient_generator, mix_route)
 from . import sample_many  # noqa: F401
 from .linemin import line_minimization  # noqa: F401
 from .optvariance import optvariance  # noqa: F401

@@ -337,6 +337,236 @@ class StochasticReconfiguration:
 
 PGradTransform = StochasticReconfiguration
 
+MIX_SOURCES = {k: v for k, v in SR_SOURCES.items() if v <= 2}  # the parameters pqa_mix_moments / pqa_mix_wtdp have columns for
+
+
+def mix_route(wfs, acc):
+    """``("device", reason)`` when a multi-state accumulator ``acc`` can take its averages from the walkers resident behind ``wfs``
+    (``pqa_mix_moments`` / ``pqa_mix_wtdp``), else ``("protocol", reason)``.  The device route needs: ``sample_many.fused_scope(wfs)``
+    (real Slater x two-body Jastrow products on distinct handles of one device, open boundaries, at most 8 states); ``acc.enacc`` a
+    ``pyqmc_amd.EnergyAccumulator`` itself; every transform of ``acc`` (``acc.transforms``, or ``acc.transform``; an accumulator
+    without either has none) a ``LinearTransform`` whose optimised keys are all among ``MIX_SOURCES``, with moments within
+    ``SR_MOMENT_BYTES``."""
+    from .energy import EnergyAccumulator
+    from .sample_many import fused_scope
+
+    devs, why = fused_scope(wfs)
+    if devs is None:
+        return "protocol", why
+    if type(acc.enacc) is not EnergyAccumulator:
+        return "protocol", f"the energy object is a {type(acc.enacc).__name__}, not a pyqmc_amd.EnergyAccumulator"
+    transforms = getattr(acc, "transforms", None)
+    if transforms is None:
+        transforms = [acc.transform] if hasattr(acc, "transform") else []
+    K = len(wfs)
+    for i, t in enumerate(transforms):
+        if type(t) is not LinearTransform:
+            return "protocol", f"transform {i} is a {type(t).__name__}, not a pyqmc_amd.LinearTransform"
+        other = [k for k in t.to_opt if k not in MIX_SOURCES]
+        if other:
+            return "protocol", "parameters without a device source: " + ", ".join(other)
+        if (t.nparams + 2 * K) * t.nparams * 8 > SR_MOMENT_BYTES:
+            return "protocol", f"the moments of {t.nparams} parameters exceed the {SR_MOMENT_BYTES >> 20} MiB the device call takes"
+    return "device", "real open-boundary handles of one device, device energy, every parameter has a device source"
+
+
+def resolve_mix_route(acc, wfs, route, name):
+    """The route a multi-state accumulator ``acc`` (class ``name``) takes for ``wfs`` when it was asked for ``route``: "protocol" as
+    it is, "device" or ``NotImplementedError`` with ``mix_route``'s reason, None: what ``mix_route`` says."""
+    if route == "protocol":
+        return "protocol"
+    r, why = mix_route(wfs, acc)
+    if route == "device" and r != "device":
+        raise NotImplementedError(f"{name}(route='device'): {why}")
+    return r
+
+
+def mix_energy_keys(enacc, devs):
+    """Per state, in state order, what ``EnergyAccumulator.__call__`` does before its energy pass: bind the handle, advance the call
+    count, derive the key of the draws (one ``np.random.randint`` each without a seed) -> keys (K) of ``pqa_mix_moments``."""
+    keys = []
+    for dev in devs:
+        enacc.bind(dev)
+        enacc._calls += 1
+        keys.append(int(np.random.randint(0, 2**31 - 1)) if enacc.seed is None else enacc.seed + enacc._calls)
+    return keys
+
+
+class StochasticReconfigurationMultipleWF:
+    """Energies, overlap derivatives and SR moments of ALL states from one sample of their mixture
+    (``stochastic_reconfiguration.py:179-369``): ``avg(configs, wfs, weights)`` returns ``{energy key: (K, K)}`` and, for every state
+    ``i`` with optimised parameters, ``("dp", i)`` (P_i, K), ``("dpipj", i)`` (P_i, P_i) and ``("dpH", i)`` (P_i, K);
+    ``block_average``, ``_collect_terms`` and ``delta_p`` turn blocks of those into one step per state.  ``eps`` regularises
+    ``(S + eps 1)^-1``; the mixture has no nodal divergence, so there is no nodal cut-off.
+
+    ``route``: where ``avg`` forms its averages.  ``"protocol"``: the reference's host formula on ``wf.pgradient()``, the energy
+    object's per-walker rows and the (K, K, W) weights.  ``"device"``: one ``pqa_mix_moments`` call on the resident state (``weights``
+    are then recomputed there from the same values); ``NotImplementedError`` with the reason when ``mix_route`` says the case is out
+    of scope.  None (default): the device route when in scope, else the protocol route.  ``last_route`` records what the last
+    evaluation took.  On the device route ``avg_resident(wfs)`` is ``avg`` without a host container, and
+    ``sample_many.sample_overlap_worker`` calls it without fetching walkers or weights.
+
+    Three deliberate differences from the reference: ``shapes()`` raises there (it reads ``self.transform``, which does not exist);
+    here it returns the shapes ``avg`` returns, with K = ``len(transforms)``.  ``avg(weights=None)`` fails there on ``None.shape``;
+    here it raises a ``ValueError`` that says so.  ``delta_p`` fails there on an unbound ``report`` when no state has parameters;
+    here the report is then ``{}``."""
+
+    multiple_wf = True
+
+    def __init__(self, enacc, transforms, eps=1e-1, route=None):
+        if route not in (None, "device", "protocol"):
+            raise ValueError(f"route must be None, 'device' or 'protocol', got {route!r}")
+        self.enacc, self.transforms, self.eps = enacc, transforms, eps
+        self.route, self.last_route = route, None
+
+    def resolve_route(self, wfs):
+        """The route ``avg`` takes for ``wfs``: ``"device"`` or ``"protocol"`` (see ``route``)."""
+        return resolve_mix_route(self, wfs, self.route, "StochasticReconfigurationMultipleWF")
+
+    def avg_resident(self, wfs):
+        """``avg`` on the device route for the walkers resident behind ``wfs``: the energy object bound and keyed per state as the
+        protocol route does (``mix_energy_keys``), then one ``pqa_mix_moments`` call."""
+        from .energy import KEYS
+        from .sample_many import fused_scope, mix_moments
+
+        devs, why = fused_scope(wfs)
+        if devs is None:
+            raise NotImplementedError(f"StochasticReconfigurationMultipleWF.avg_resident: {why}")
+        keys = mix_energy_keys(self.enacc, devs)
+        for wf in wfs:
+            wf.wf_factors[0]._saved = None  # (the saved rows of a gradient_value call are overwritten)
+        _, en, mom = mix_moments(devs, [sr_columns(t) for t in self.transforms], threshold=self.enacc.threshold, seeds=keys)
+        self.last_route = "device"
+        K = len(wfs)
+        d = {k: en[i] for i, k in enumerate(KEYS)}
+        for i, m in enumerate(mom):
+            if m is None:
+                continue
+            p = m.shape[1]
+            d[("dp", i)], d[("dpipj", i)], d[("dpH", i)] = m[p:p + K].T.copy(), m[:p].copy(), m[p + K:].T.copy()
+        return d
+
+    def avg(self, configs, wfs, weights=None):
+        if weights is None:
+            raise ValueError("StochasticReconfigurationMultipleWF.avg needs the (K, K, nconf) mixture weights (sample_many.compute_weights)")
+        if self.resolve_route(wfs) == "device":
+            dev = wfs[0].fused_device()
+            if self.enacc.check_configs and not (dev.W == len(configs.configs) and np.array_equal(dev.configs(), configs.configs)):
+                raise ValueError("walkers on the device differ from `configs`: call wf.recompute(configs) "
+                                 "(or keep wf.updateinternals in step with configs.move) first")
+            return self.avg_resident(wfs)
+        from .sample_many import invert_list_of_dicts
+
+        self.last_route = "protocol"
+        energies = invert_list_of_dicts([self.enacc(configs, wf) for wf in wfs])
+        dppsi = [transform.serialize_gradients(wf.pgradient()) for transform, wf in zip(self.transforms, wfs)]
+        nconfig = weights.shape[-1]
+        d = {}
+        for k, en in energies.items():
+            d[k] = np.einsum("jc,ijc->ij", np.asarray(en), weights / nconfig)
+        for wfi, dp in enumerate(dppsi):
+            if self.transforms[wfi].nparams == 0:
+                continue
+            d[("dp", wfi)] = np.einsum("cp,jc->pj", dp, weights[wfi, :, :], optimize=True) / nconfig
+            d[("dpipj", wfi)] = np.einsum("cp,cq,c->pq", dp, dp, weights[wfi, wfi, :], optimize=True) / nconfig
+            d[("dpH", wfi)] = np.einsum("jc,cp,jc->pj", energies["total"], dp, weights[wfi, :, :]) / nconfig
+        return d
+
+    def keys(self):
+        return self.enacc.keys().union(["dpH", "dppsi", "dpidpj"])
+
+    def shapes(self):
+        K = len(self.transforms)
+        d = {k: (K, K) for k in self.enacc.shapes()}
+        for i, t in enumerate(self.transforms):
+            if t.nparams:
+                d[("dp", i)], d[("dpipj", i)], d[("dpH", i)] = (t.nparams, K), (t.nparams, t.nparams), (t.nparams, K)
+        return d
+
+    def update_state(self, hdf_file):
+        """Nothing to restore: the accumulator keeps no state."""
+        pass
+
+    def block_average(self, data, weights):
+        """Averages and errors over blocks: ``weights`` (block, K, K) the overlap blocks, ``data`` the blocks of ``avg``; energies
+        divided by sqrt(N_i N_j), state i's ``dp`` / ``dpH`` by its row of that and ``dpipj`` by N_i."""
+        import scipy.stats
+
+        weight_avg = np.mean(weights, axis=0)
+        N = np.abs(weight_avg.diagonal())
+        Nij = np.sqrt(np.outer(N, N))
+        avg, error = {}, {}
+        avg["total"] = np.mean(data["total"], axis=0) / Nij
+        error["total"] = scipy.stats.sem(data["total"], axis=0) / Nij
+        nwf = weights.shape[1]
+        for k in ["dp", "dpH"]:
+            for w in range(nwf):
+                if self.transforms[w].nparams == 0:
+                    continue
+                it = data[(k, w)]
+                avg[(k, w)] = np.mean(it, axis=0) / Nij[w]
+                error[(k, w)] = scipy.stats.sem(it, axis=0) / Nij[w]
+        for w in range(nwf):
+            if self.transforms[w].nparams == 0:
+                continue
+            it = data[("dpipj", w)]
+            avg[("dpipj", w)] = np.mean(it, axis=0) / Nij[w, w]
+            error[("dpipj", w)] = scipy.stats.sem(it, axis=0) / Nij[w, w]
+        avg["overlap"] = weight_avg
+        return avg, error
+
+    def _collect_terms(self, avg, error):
+        ret = {}
+        nwf = avg["total"].shape[0]
+        N = np.abs(avg["overlap"].diagonal())
+        Nij = np.sqrt(np.outer(N, N))
+        ret["norm"] = N
+        ret["overlap"] = avg["overlap"] / Nij
+        fac = np.ones((nwf, nwf)) + np.identity(nwf)
+        for wfi in range(nwf):
+            if self.transforms[wfi].nparams == 0:
+                continue
+            ret[("dp_energy", wfi)] = fac[wfi] * np.real(avg[("dpH", wfi)] - avg["total"][wfi] * avg[("dp", wfi)])
+            ret[("dp_norm", wfi)] = 2.0 * np.real(avg[("dp", wfi)][:, wfi])
+            norm_part = np.einsum("i,p->pi", avg["overlap"][wfi, :], ret[("dp_norm", wfi)]) / N[wfi]
+            ret[("dp_overlap", wfi)] = fac[wfi] * (avg[("dp", wfi)] - 0.5 * norm_part) / Nij[wfi]
+            ret[("dpipj", wfi)] = np.real(avg[("dpipj", wfi)] - np.einsum("i,j->ij", avg[("dp", wfi)][:, wfi], avg[("dp", wfi)][:, wfi]))
+        ret["energy"] = avg["total"]
+        return ret
+
+    def delta_p(self, steps, data, overlap_penalty, verbose=False):
+        """Per state ``[-step (S + eps 1)^-1 g for step in steps]`` (empty vectors for a state without parameters) with g the energy
+        gradient plus the penalised overlap gradient against the states before it; returns (steps per state, report of the last state
+        that has parameters)."""
+        data = self._collect_terms(data, None)
+        nwf = data["energy"].shape[0]
+        dp_all = []
+        report = {}
+        for wf in range(nwf):
+            overlap_cost = 0.0
+            for i in range(wf):
+                overlap_cost += overlap_penalty[wf, i] * data["overlap"][wf, i]
+            if verbose:
+                print("wave function", wf)
+                print("Overlap cost", overlap_cost)
+            if self.transforms[wf].nparams == 0:
+                dp_all.append([np.zeros((0)) for step in steps])
+                continue
+            Sij = np.real(data[("dpipj", wf)])
+            ovlp = 0.0
+            for i in range(wf):
+                ovlp += 2.0 * data[("dp_overlap", wf)][:, i] * overlap_penalty[wf, i] * data["overlap"][wf, i]
+            pgrad = data[("dp_energy", wf)][:, wf] + ovlp
+            invSij = np.linalg.inv(Sij + self.eps * np.eye(Sij.shape[0]))
+            v = np.einsum("ij,j->i", invSij, pgrad)
+            dp_all.append([-step * v for step in steps])
+            report = {"pgrad": np.linalg.norm(pgrad), "SRdot": np.dot(pgrad, v) / (np.linalg.norm(v) * np.linalg.norm(pgrad))}
+            if verbose:
+                print("overlap gradient norm", np.linalg.norm(ovlp))
+                print("Gradient norm: ", np.linalg.norm(pgrad))
+                print("Dot product between gradient and SR step: ", report["SRdot"])
+        return dp_all, report
+
 
 def gradient_generator(mol, wf, to_opt=None, nodal_cutoff=1e-3, eps=1e-3, inverse_strategy="regularized_inverse", route=None,
                        complex_device=False, **ewald_kwargs):

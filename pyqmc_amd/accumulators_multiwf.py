@@ -21,16 +21,57 @@ class EnergyAccumulatorMultipleWF:
     wave function minus ``offset``, weighted by ``weights[i, j, c]`` and averaged over the walkers; ``offset`` is returned as well.
 
     One deliberate difference: ``offset`` is returned as a NumPy array.  The reference returns it as given, and with its default
-    ``offset=0`` (a Python int) ``sample_overlap_worker``'s ``rolling_average`` fails on it (``it.shape``)."""
+    ``offset=0`` (a Python int) ``sample_overlap_worker``'s ``rolling_average`` fails on it (``it.shape``).
+
+    ``route``: None (default) or "protocol": the host formula on the energy object's per-walker rows.  "device": the energies from
+    one ``pqa_mix_moments`` call on the resident state (no state has columns), ``NotImplementedError`` with ``mix_route``'s reason
+    when out of its scope; ``avg_resident(wfs)`` is ``avg`` without a host container then.  ``last_route`` records what the last
+    evaluation took."""
 
     multiple_wf = True
 
-    def __init__(self, enacc, offset=0):
+    def __init__(self, enacc, offset=0, route=None):
+        if route not in (None, "device", "protocol"):
+            raise ValueError(f"route must be None, 'device' or 'protocol', got {route!r}")
         self.enacc = enacc
         self._offset = offset
+        self.route, self.last_route = route, None
+
+    def resolve_route(self, wfs):
+        """The route ``avg`` takes for ``wfs``: "device" only when asked for (see ``route``)."""
+        from .accumulators import resolve_mix_route
+
+        return resolve_mix_route(self, wfs, self.route or "protocol", "EnergyAccumulatorMultipleWF")
+
+    def avg_resident(self, wfs):
+        """``avg`` on the device route for the walkers resident behind ``wfs``: the energy object bound and keyed per state as the
+        protocol route does, then one ``pqa_mix_moments`` call without columns."""
+        from .accumulators import mix_energy_keys
+        from .energy import KEYS
+        from .sample_many import fused_scope, mix_moments
+
+        devs, why = fused_scope(wfs)
+        if devs is None:
+            raise NotImplementedError(f"EnergyAccumulatorMultipleWF.avg_resident: {why}")
+        keys = mix_energy_keys(self.enacc, devs)
+        for wf in wfs:
+            wf.wf_factors[0]._saved = None  # (the saved rows of a gradient_value call are overwritten)
+        empty = (np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))
+        _, en, _ = mix_moments(devs, [empty] * len(devs), offset=self._offset, threshold=self.enacc.threshold, seeds=keys)
+        self.last_route = "device"
+        weighted_dat = {k: en[i] for i, k in enumerate(KEYS)}
+        weighted_dat["offset"] = np.asarray(self._offset) + 0.0
+        return weighted_dat
 
     def avg(self, configs, wfs, weights):
         """weights (nwf, nwf, nconfig); returns {key: (nwf, nwf)} and ``offset``."""
+        if self.resolve_route(wfs) == "device":
+            dev = wfs[0].fused_device()
+            if self.enacc.check_configs and not (dev.W == len(configs.configs) and np.array_equal(dev.configs(), configs.configs)):
+                raise ValueError("walkers on the device differ from `configs`: call wf.recompute(configs) "
+                                 "(or keep wf.updateinternals in step with configs.move) first")
+            return self.avg_resident(wfs)
+        self.last_route = "protocol"
         energies = invert_list_of_dicts([self.enacc(configs, wf) for wf in wfs])
         weighted_dat = {}
         nconfig = configs.configs.shape[0]

@@ -1,9 +1,10 @@
 // Code shared by the units that drive K resident wave functions in one call (pqa_overlap: the mixture sum_k |Psi_k|^2; pqa_add: the
-// superposition sum_k c_k Psi_k); no other unit includes it.  Per electron both do the same around their own proposal and decision:
+// superposition sum_k c_k Psi_k; pqa_mix: the estimators over the mixture); no other unit includes it.  Per electron both do the same around their own proposal and decision:
 //   has-zero   the vanished-determinant test of slater.py:269-275 on spin s of every handle (k_has_zero), its flags copied to pinned
 //              host words behind an event the host waits on only before the updates (multi_flags)
 //   rows       per handle: e's current position gathered (k_ovl_gather), launch_orb + k_slater_eval<5> + k_jastrow_eval (mode 1) at
 //              the old and at the proposed position (rows_at); each handle's value left on the device (values_dev)
+//   weights    compute_weights (sample_many.py:42-55) per walker (ovl_psi_rho, k_ovl_weights) and its walker mean (k_ovl_mean)
 //   update     per handle under the one mask: k_sm_update with the saved rows + k_jastrow_update; a handle whose spin-s determinants
 //              had vanished instead gets k_jastrow_update and a rebuild of its Slater state from the moved walkers (multi_update)
 #pragma once
@@ -38,6 +39,47 @@ __device__ __forceinline__ double nan_to_num(double v) {
 __device__ __forceinline__ void limdrift1(double (&g)[3]) {  // mc.limdrift, cutoff 1
   const double tot = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
   if (tot > 1.0) for (int d = 0; d < 3; ++d) g[d] = g[d] / tot;
+}
+
+// compute_weights (sample_many.py:42-55) for walker w: psi[k] = phase_k exp(log_k - ref) with ref = max_k log_k; returns
+// rho = mean_k exp(2 (log_k - ref)).  nan_to_num where the reference applies it.
+__device__ __forceinline__ double ovl_psi_rho(const OvlPtrs& P, int K, long w, double (&psi)[kMaxK]) {
+  double ph[kMaxK], lv[kMaxK];
+  double ref = -DBL_MAX;
+  for (int k = 0; k < K; ++k) {
+    ph[k] = nan_to_num(P.sign[k][w]);
+    lv[k] = nan_to_num(P.lg[k][w] + P.ju[k][w]);
+    ref = k ? fmax(ref, lv[k]) : lv[k];
+  }
+  double rho = 0.0;
+  for (int k = 0; k < K; ++k) {
+    const double t = nan_to_num(exp(2.0 * (lv[k] - ref)));
+    rho = k ? rho + t : t;
+    psi[k] = ph[k] * nan_to_num(exp(lv[k] - ref));
+  }
+  return rho / K;
+}
+
+// weights[i][j][w] = psi_i psi_j / rho (compute_weights)
+template <int PQA_UNIT = 0>  // (a template so that only the units that launch it compile it)
+__global__ __launch_bounds__(256) void k_ovl_weights(OvlPtrs P, int K, long W, double* __restrict__ wts) {
+  const long w = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= W) return;
+  double psi[kMaxK];
+  const double rho = ovl_psi_rho(P, K, w, psi);
+  for (int i = 0; i < K; ++i)
+    for (int j = 0; j < K; ++j) wts[((size_t)i * K + j) * W + w] = psi[i] * (psi[j] / rho);
+}
+
+// out[ij] = mean over walkers of wts[ij][.]: one block per (i, j), a fixed-order tree (the same bits on every call)
+template <int PQA_UNIT = 0>  // (a template so that only the units that launch it compile it)
+__global__ __launch_bounds__(256) void k_ovl_mean(const double* __restrict__ wts, long W, double* __restrict__ out) {
+  __shared__ double part[256];
+  const double* row = wts + (size_t)blockIdx.x * W;
+  double a = 0.0;
+  for (long w = threadIdx.x; w < W; w += 256) a += row[w];
+  a = block_sum256(a, part);
+  if (threadIdx.x == 0) out[blockIdx.x] = a / (double)W;
 }
 
 __global__ __launch_bounds__(256) void k_ovl_gather(OvlPtrs P, int K, int N, int e, long W) {

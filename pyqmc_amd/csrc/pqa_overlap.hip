@@ -14,7 +14,7 @@
 //              had vanished instead gets k_jastrow_update and a rebuild of its Slater state from the moved walkers (the protocol's
 //              fallback: Slater.recompute(configs) then the Jastrow update)
 // After each sweep: every handle's value, then k_ovl_weights (compute_weights, sample_many.py:42-55: psi_i psi_j / rho per walker)
-// and k_ovl_mean (the walker mean, a fixed-order tree: block_sum256).
+// and k_ovl_mean (the walker mean, a fixed-order tree: block_sum256), both pqa_multi.hpp's (pqa_mix weights its estimators with them).
 #include "pqa_multi.hpp"
 
 #pragma clang fp contract(off)  // (as pqa_multi.hpp: this unit's own kernels too)
@@ -81,38 +81,6 @@ __global__ __launch_bounds__(256) void k_ovl_decide(OvlPtrs P, int K, long W, do
   nacc[w] += acc ? 1.0 : 0.0;
 }
 
-// weights[i][j][w] = psi_i psi_j / rho (compute_weights): psi_k = phase_k exp(log_k - ref), rho = mean_k exp(2 (log_k - ref))
-__global__ __launch_bounds__(256) void k_ovl_weights(OvlPtrs P, int K, long W, double* __restrict__ wts) {
-  const long w = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= W) return;
-  double ph[kMaxK], lv[kMaxK], psi[kMaxK];
-  double ref = -DBL_MAX;
-  for (int k = 0; k < K; ++k) {
-    ph[k] = nan_to_num(P.sign[k][w]);
-    lv[k] = nan_to_num(P.lg[k][w] + P.ju[k][w]);
-    ref = k ? fmax(ref, lv[k]) : lv[k];
-  }
-  double rho = 0.0;
-  for (int k = 0; k < K; ++k) {
-    const double t = nan_to_num(exp(2.0 * (lv[k] - ref)));
-    rho = k ? rho + t : t;
-    psi[k] = ph[k] * nan_to_num(exp(lv[k] - ref));
-  }
-  rho = rho / K;
-  for (int i = 0; i < K; ++i)
-    for (int j = 0; j < K; ++j) wts[((size_t)i * K + j) * W + w] = psi[i] * (psi[j] / rho);
-}
-
-// out[ij] = mean over walkers of wts[ij][.]: one block per (i, j), a fixed-order tree (the same bits on every call)
-__global__ __launch_bounds__(256) void k_ovl_mean(const double* __restrict__ wts, long W, double* __restrict__ out) {
-  __shared__ double part[256];
-  const double* row = wts + (size_t)blockIdx.x * W;
-  double a = 0.0;
-  for (long w = threadIdx.x; w < W; w += 256) a += row[w];
-  a = block_sum256(a, part);
-  if (threadIdx.x == 0) out[blockIdx.x] = a / (double)W;
-}
-
 }  // namespace
 
 extern "C" int pqa_overlap_sweeps(pqa_handle_t* const* hs, int K, double tstep, int nsteps, const double* gauss, const double* unif,
@@ -170,8 +138,8 @@ extern "C" int pqa_overlap_sweeps(pqa_handle_t* const* hs, int K, double tstep, 
       int rc = values_dev(hs[k]);
       if (rc) { h->err = hs[k]->err; return rc; }
     }
-    hipLaunchKernelGGL(k_ovl_weights, dim3(gb), dim3(256), 0, st, P, K, W, d_w);
-    hipLaunchKernelGGL(k_ovl_mean, dim3((unsigned)(K * K)), dim3(256), 0, st, (const double*)d_w, W, d_o + (size_t)n * K * K);
+    hipLaunchKernelGGL((k_ovl_weights<>), dim3(gb), dim3(256), 0, st, P, K, W, d_w);
+    hipLaunchKernelGGL((k_ovl_mean<>), dim3((unsigned)(K * K)), dim3(256), 0, st, (const double*)d_w, W, d_o + (size_t)n * K * K);
     TRY(check_launch(h, "k_ovl_weights / k_ovl_mean"));
   }
   if (nsteps > 0) TRY(copy_in(h, overlap, d_o, (size_t)nsteps * K * K * sizeof(double)));

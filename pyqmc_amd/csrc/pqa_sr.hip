@@ -29,18 +29,11 @@
 // pqa_sr_moments_c takes complex and twisted handles (complex d_det, complex local energy) and the imaginary-part tail of the
 // reference's serialised matrix, with kernels of its own (k_sr_gather_c, k_sr_syrk_c, k_sr_reduce_c below): planar real / imaginary
 // panels, one to four matrix instructions per k-step by what the two column blocks of a tile can hold.
-#include "pqa_estim.hpp"
+//
+// k_sr_syrk, k_sr_reduce and the preparation of the sources (sr_sources) are pqa_srk.hpp's: pqa_mix forms its moments with them too.
+#include "pqa_srk.hpp"
 
 namespace {
-
-constexpr int kSrKB = 16;      // walkers staged per step of k_sr_syrk
-constexpr int kSrLd = 48;      // doubles per staged row: 32 columns + 16 of padding, so rows kq and kq + 1 of an operand read land in
-                               // different halves of the 64 LDS banks (no conflict within a half-wave's ds_read_b64)
-
-struct SrSources {
-  const double* base[4];  // det_coeff, acoeff, bcoeff, ccoeff derivatives, walker-major
-  long stride[4];         // doubles per walker of each
-};
 
 // Pathak-Wagner weight (accumulators.nodal_regularization)
 __device__ __forceinline__ double sr_nodal_f(double grad2, double cutoff) {
@@ -168,68 +161,6 @@ __global__ __launch_bounds__(256) void k_sr_orb(SysDev S, SlaterState st, int s,
       }
     }
   }
-}
-
-// part[sl] (P + 2, P) += tile (32 bi .., 32 bj ..) of A^T diag(s) A[:, :P] over the walkers of slice sl.  grid = (column blocks,
-// row blocks, slices), block = 256: wave (wi, wj) = (wave >> 1, wave & 1) owns the 16 x 16 tile (2 bi + wi, 2 bj + wj).  Blocks strictly
-// below the diagonal are skipped unless they hold a row >= P (the dpH / dppsi rows); a wave's tile below the diagonal is not stored.
-__global__ __launch_bounds__(256) void k_sr_syrk(const double* __restrict__ A, const double* __restrict__ scale, long Wc, int P, long per,
-                                                 double* __restrict__ part) {
-  __shared__ double La[kSrKB * kSrLd], Lb[kSrKB * kSrLd];
-  const int bj = blockIdx.x, bi = blockIdx.y, sl = blockIdx.z;
-  if (bi > bj && bi * 32 + 31 < P) return;
-  const int lda = P + 2;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, i16 = lane & 15, kq = lane >> 4, wi = wave >> 1, wj = wave & 1;
-  const long k_lo = (long)sl * per, k_hi = k_lo + per < Wc ? k_lo + per : Wc;
-  // staging: element e = t + 256 q of the two 16 x 32 panels: panel e >> 9, row (e >> 5) & 15, column e & 31
-  const int c = t & 31, r0 = t >> 5;  // q advances the row by 8; q >= 2: the right-hand panel
-  const int ca = bi * 32 + c, cb = bj * 32 + c;
-  const bool ain = ca < lda, bin = cb < P;
-  double v[4];
-  auto fetch = [&](long k0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const long row = k0 + r0 + 8 * (q & 1);
-      const bool rin = row < k_hi;
-      if (q < 2) v[q] = (rin && ain) ? A[(size_t)row * lda + ca] : 0.0;
-      else v[q] = (rin && bin) ? A[(size_t)row * lda + cb] * scale[row] : 0.0;
-    }
-  };
-  d4 acc = {0.0, 0.0, 0.0, 0.0};
-  if (k_lo < k_hi) fetch(k_lo);
-  for (long k0 = k_lo; k0 < k_hi; k0 += kSrKB) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) (q < 2 ? La : Lb)[(r0 + 8 * (q & 1)) * kSrLd + c] = v[q];
-    __syncthreads();
-    if (k0 + kSrKB < k_hi) fetch(k0 + kSrKB);  // (the next step's loads fly while this one multiplies)
-#pragma unroll
-    for (int kk = 0; kk < kSrKB / 4; ++kk) {
-      const int row = kk * 4 + kq;
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(La[row * kSrLd + wi * 16 + i16], Lb[row * kSrLd + wj * 16 + i16], acc, 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  const int ti = 2 * bi + wi, tj = 2 * bj + wj;
-  if (ti > tj && ti * 16 + 15 < P) return;
-  // lane holds D[row = kq + 4 r][col = i16]
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int p = ti * 16 + kq + 4 * r, q = tj * 16 + i16;
-    if (p < lda && q < P) part[((size_t)sl * lda + p) * P + q] = acc[r];
-  }
-}
-
-// mom (P + 2, P) = (first ? 0 : mom) + sum over the slices in slice order; element (i, j) of the symmetric block is read at
-// (min, max): the tiles below the diagonal were never written.
-__global__ __launch_bounds__(256) void k_sr_reduce(const double* __restrict__ part, int P, int nslice, int first, double* __restrict__ mom) {
-  const long n = (long)(P + 2) * P;
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= n) return;
-  const int i = (int)(idx / P), j = (int)(idx - (long)i * P);
-  const long from = (i < P && j < i) ? (long)j * P + i : idx;
-  double s = 0.0;
-  for (int sl = 0; sl < nslice; ++sl) s += part[(size_t)sl * n + from];
-  mom[idx] = first ? s : mom[idx] + s;
 }
 
 // ---- complex columns (pqa_sr_moments_c) -------------------------------------------------------------------------------------------------
@@ -383,8 +314,8 @@ static int sr_moments(pqa_handle_t* h, const std::string& fn, bool orb, int P, c
   if (!src || !pos || !en_mean || !moments) FAIL(fn + ": src, pos, en_mean and moments must not be NULL");
   if (!(nodal_cutoff > 0.0)) FAIL(fn + ": nodal_cutoff must be positive");
   if (h->cplx) FAIL(fn + ": complex orbitals / twisted cell (outside the device scope: use the protocol route)");
-  const long size[4] = {h->has_slater ? (long)h->ndet : 0, h->has_j2 ? (long)h->natom * h->na * 2 : 0, h->has_j2 ? (long)h->nb * 3 : 0,
-                        h->has_j3 ? (long)h->natom * h->na3 * h->na3 * h->nb3 * 3 : 0};
+  long size[4];
+  sr_source_sizes(h, size);
   bool need[4] = {false, false, false, false};
   bool orb_spin[2] = {false, false};
   std::vector<int> colof[2];  // [nao][nmo_s]: the column of A an orbital-coefficient entry fills, or -1
@@ -424,28 +355,8 @@ static int sr_moments(pqa_handle_t* h, const std::string& fn, bool orb, int P, c
   const double* d_en = (const double*)h->b_en.p;
   // derivative sources
   SrSources S{};
-  if (need[0] || has_orb) {  // (the orbital columns need d_det for the determinant weights)
-    TRY(slater_value_dev(h));  // sign / log of the determinant expansion -> b_sign, b_log
-    TRY(ensure(h, h->b_pgdet, (size_t)W * h->ndet * sizeof(double)));
-    hipLaunchKernelGGL((k_pgrad_det<>), dim3((unsigned)((W * h->ndet + 255) / 256)), dim3(256), 0, h->stream, h->S, h->st,
-                       (const double*)h->b_sign.p, (const double*)h->b_log.p, W, (double*)h->b_pgdet.p);
-    TRY(check_launch(h, "k_pgrad_det"));
-    S.base[0] = (const double*)h->b_pgdet.p; S.stride[0] = size[0];
-  }
-  if (need[1] || need[2]) {
-    TRY(jas_refresh(h));
-    S.base[1] = h->js.avalues; S.stride[1] = size[1];
-    S.base[2] = h->js.bvalues; S.stride[2] = size[2];
-  }
-  if (need[3]) {
-    const size_t lds = ((size_t)h->N * h->natom * h->na3 + (size_t)h->N * (h->N - 1) / 2 * h->nb3) * sizeof(double);
-    if (lds > 150 * 1024) FAIL("three-body parameter gradient: the a/b value tables of one walker do not fit LDS");
-    TRY(ensure(h, h->b_out, (size_t)W * size[3] * sizeof(double)));
-    if (lds > 64 * 1024) TRY(raise_lds_limit(h, reinterpret_cast<const void*>(k_j3_pgrad<>)));
-    hipLaunchKernelGGL((k_j3_pgrad<>), dim3((unsigned)W), dim3(64), lds, h->stream, h->S, h->js, (double*)h->b_out.p);
-    TRY(check_launch(h, "k_j3_pgrad"));
-    S.base[3] = (const double*)h->b_out.p; S.stride[3] = size[3];
-  }
+  need[0] = need[0] || has_orb;  // (the orbital columns need d_det for the determinant weights)
+  TRY(sr_sources(h, need, S));
   // scratch: [moments | means (6) | weight sum (1) | weights (W) | per-walker energies (W, 6) | scale (Wc) | A (Wc, P + 2) |
   // partials (nslice, P + 2, P) | src, pos | colof of each spin]; with orbital columns a chunk's A and AO rows (b_ao) together stay
   // within the chunk limit
@@ -460,8 +371,7 @@ static int sr_moments(pqa_handle_t* h, const std::string& fn, bool orb, int P, c
       if (orb_lds[s] > 150 * 1024) FAIL(fn + ": orbital coefficients: the determinant weights of one walker do not fit LDS (use the protocol route)");
     }
   const int nbi = (lda + 31) / 32, nbj = (P + 31) / 32;
-  long nslice = std::min<long>(std::max<long>(1, 1024 / ((long)nbi * nbj)), std::max<long>(1, Wc / 64));
-  nslice = std::max<long>(1, std::min<long>(nslice, (long)(kChunkScratchBytes / (nmom * sizeof(double)))));
+  const long nslice = sr_slices(Wc, nbi, nbj, nmom);
   const size_t nw = weights ? (size_t)W : 0, nenw = en_walker ? (size_t)6 * W : 0;
   const size_t ndbl = nmom + 6 + 1 + nw + nenw + (size_t)Wc + (size_t)Wc * lda + (size_t)nslice * nmom;
   TRY(ensure(h, h->b_sr, ndbl * sizeof(double) + ((size_t)2 * P + colof[0].size() + colof[1].size()) * sizeof(int)));
@@ -514,10 +424,10 @@ static int sr_moments(pqa_handle_t* h, const std::string& fn, bool orb, int P, c
       HIPCHK(hipStreamSynchronize(h->stream));
     }
     hipLaunchKernelGGL(k_sr_syrk, dim3((unsigned)nbj, (unsigned)nbi, (unsigned)ns), dim3(256), 0, h->stream, (const double*)d_A,
-                       (const double*)d_scale, wc, P, per, d_part);
+                       (const double*)d_scale, wc, P, 2, 1, per, d_part);
     TRY(check_launch(h, "k_sr_syrk"));
-    hipLaunchKernelGGL(k_sr_reduce, dim3((unsigned)((nmom + 255) / 256)), dim3(256), 0, h->stream, (const double*)d_part, P, (int)ns,
-                       (int)(w0 == 0), d_mom);
+    hipLaunchKernelGGL(k_sr_reduce, dim3((unsigned)((nmom + 255) / 256)), dim3(256), 0, h->stream, (const double*)d_part, P, 2, 0, (int)ns,
+                       (int)(w0 == 0), 0, d_mom);
     TRY(check_launch(h, "k_sr_reduce"));
   }
   TRY(copy_in(h, moments, d_mom, nmom * sizeof(double)));

@@ -6,14 +6,14 @@ state ``wfi`` with the single-state SR accumulator (``transform.onewf()``), samp
 ``transform.allwfs()`` (the overlap derivatives), and takes one SR step on energy + ``overlap_penalty`` x overlap.  Names, arguments,
 defaults and the arithmetic are the reference's.  The optimisation file goes through ``BlockFile``: parameters ``wf/<i>/<key>``,
 overwritten every step, and one record per step (``energy{i}``, ``energy_error{i}``, ``overlap{i}``, ``iteration``, ``wavefunction``,
-``sub_iteration``).  ``client`` / ``npartitions`` are refused (one device); the reference's threaded variant is not restated.
+``sub_iteration``).  ``client`` / ``npartitions`` are refused (one device); the reference's threaded variant is ``ensemble_threaded``.
 """
 
 import numpy as np
 import scipy.stats
 
 from . import sample_many
-from .accumulators import StochasticReconfiguration
+from .accumulators import StochasticReconfiguration, resolve_mix_route, sr_columns
 
 
 def _nparams(transform):
@@ -27,15 +27,23 @@ class StochasticReconfigurationWfbyWf:
 
     ``onewf()`` is the reference's ``StochasticReconfiguration(enacc, transform, eps)``: the third positional argument there is
     ``nodal_cutoff``, so ``eps`` sets the nodal cut-off of the single-state accumulator (and its regularisation keeps its default).
-    This is restated as it is."""
+    This is restated as it is.
+
+    ``mixture_route``: where ``allwfs().avg`` forms ``wtdp``.  None (default) or "protocol": the host ``einsum`` over
+    ``wf.pgradient()`` of the last state and the (K, K, W) weights.  "device": ``pqa_mix_wtdp`` on the resident state,
+    ``NotImplementedError`` with ``mix_route``'s reason when out of its scope; ``avg_resident(wfs)`` is ``avg`` without a host
+    container then.  ``last_route`` records what the last mixture evaluation took."""
 
     multiple_wf = True
 
-    def __init__(self, enacc, transform, eps=1e-3, route=None):
+    def __init__(self, enacc, transform, eps=1e-3, route=None, mixture_route=None):
+        if mixture_route not in (None, "device", "protocol"):
+            raise ValueError(f"mixture_route must be None, 'device' or 'protocol', got {mixture_route!r}")
         self.enacc = enacc
         self.transform = transform
         self.eps = eps
         self._onewf = StochasticReconfiguration(enacc, transform, eps, route=route)  # route: of the single-state accumulator's avg
+        self.mixture_route, self.last_route = mixture_route, None
 
     def onewf(self):
         return self._onewf
@@ -43,8 +51,24 @@ class StochasticReconfigurationWfbyWf:
     def allwfs(self):
         return self
 
+    def resolve_route(self, wfs):
+        """The route ``avg`` takes for ``wfs``: "device" only when asked for (see ``mixture_route``)."""
+        return resolve_mix_route(self, wfs, self.mixture_route or "protocol", "StochasticReconfigurationWfbyWf")
+
+    def avg_resident(self, wfs):
+        """``avg`` on the device route for the walkers resident behind ``wfs``: one ``pqa_mix_wtdp`` call."""
+        devs, why = sample_many.fused_scope(wfs)
+        if devs is None:
+            raise NotImplementedError(f"StochasticReconfigurationWfbyWf.avg_resident: {why}")
+        _, wtdp = sample_many.mix_wtdp(devs, *sr_columns(self.transform))
+        self.last_route = "device"
+        return {"wtdp": np.ascontiguousarray(np.moveaxis(wtdp, -1, 0))}
+
     def avg(self, configs, wfs, weights=None):
         """``wtdp[p, j, k] = sum_c dp_p(c) weights[j, k, c] / nconfig`` with the parameter derivatives of the LAST wave function."""
+        if self.resolve_route(wfs) == "device":
+            return self.avg_resident(wfs)
+        self.last_route = "protocol"
         wfi = len(wfs) - 1
         dp = self.transform.serialize_gradients(wfs[wfi].pgradient())
         nconfig = weights.shape[-1]

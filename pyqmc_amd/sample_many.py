@@ -11,6 +11,11 @@ wave functions ``wfs`` (deep copies of one device wave function, each on a handl
 Both draw ``np.random.normal`` and ``np.random.rand`` in the reference's order, so seeded runs agree and a test can replay the draws.
 ``energy`` is a multiple-wave-function accumulator (``avg(configs, wfs, weights)``, e.g. ``EnergyAccumulatorMultipleWF``) or None;
 the route the last worker call took is in ``last_route``.
+
+A multi-state accumulator on its device route (``resolve_route(wfs) == "device"``: ``StochasticReconfigurationMultipleWF``, and on
+request ``StochasticReconfigurationWfbyWf`` and ``EnergyAccumulatorMultipleWF``) is evaluated on the resident walkers through its
+``avg_resident(wfs)`` (``mix_moments`` / ``mix_wtdp`` below: ``pqa_mix_moments`` / ``pqa_mix_wtdp``): the fused worker then fetches
+neither the walkers nor the weights between sweeps.
 """
 
 import ctypes as C
@@ -59,19 +64,31 @@ def rolling_average(block, data, nsteps):
         block[k] += it / nsteps
 
 
-def fused_handles(wfs, configs):
-    """The device handles of ``wfs`` when the fused route can take them, else None (see the module docstring)."""
-    if len(wfs) < 1 or len(wfs) > 8 or hasattr(configs, "wrap") or np.ndim(configs.configs) != 3:
-        return None
+def fused_scope(wfs, configs=None):
+    """``(handles, None)`` when the multi-handle device calls (``pqa_overlap_sweeps``, ``pqa_mix_moments``) can take ``wfs``, else
+    ``(None, reason)``; see the module docstring.  ``configs`` None: the walkers are the resident ones, only the handles are looked at."""
+    if len(wfs) < 1 or len(wfs) > 8:
+        return None, f"{len(wfs)} wave functions (the device calls take 1 to 8)"
+    if configs is not None and (hasattr(configs, "wrap") or np.ndim(configs.configs) != 3):
+        return None, "periodic walkers"
     devs = []
-    for wf in wfs:
+    for i, wf in enumerate(wfs):
         d = wf._product_device() if hasattr(wf, "_product_device") else None
-        if d is None or d.pbc or getattr(d, "twisted", False):
-            return None
+        if d is None:
+            return None, f"wave function {i} is not a real Slater x two-body Jastrow product on one device handle"
+        if d.pbc or getattr(d, "twisted", False):
+            return None, f"wave function {i} is periodic"
         devs.append(d)
-    if len({id(d) for d in devs}) != len(devs) or len({d.device for d in devs}) != 1:
-        return None
-    return devs
+    if len({id(d) for d in devs}) != len(devs):
+        return None, "two wave functions share a device handle"
+    if len({d.device for d in devs}) != 1:
+        return None, "the handles are on different devices"
+    return devs, None
+
+
+def fused_handles(wfs, configs=None):
+    """The device handles of ``wfs`` when the fused route can take them, else None (``fused_scope`` without the reason)."""
+    return fused_scope(wfs, configs)[0]
 
 
 def _route(wfs, configs, route):
@@ -102,6 +119,62 @@ def overlap_sweeps(devs, tstep, gauss, unif, weights=False):
     return ovl, wts, acc.value
 
 
+def _handles(devs):
+    return (C.c_void_p * len(devs))(*[d._h.value for d in devs])
+
+
+def mix_moments(devs, columns, offset=0.0, threshold=10.0, rot=None, unif=None, seeds=None, walker_chunk=0, per_walker=False):
+    """``pqa_mix_moments`` on the handles ``devs`` (which hold the same walkers).  ``columns``: per state ``(src, pos)`` as
+    ``accumulators.sr_columns`` gives them (empty: the state has no columns).  ``seeds`` (K) keys each handle's energy draws, or
+    ``rot`` / ``unif`` (K sets as ``DeviceWF.energy`` takes them) replay them.  Returns (overlap (K, K), en (6, K, K), moments: per
+    state None or (P_i + 2K, P_i) with the rows dpipj (P_i), dp[:, j] (K), dpH[:, j] (K)[, u (K, W), en_walker (K, W, 6) with
+    ``per_walker``])."""
+    K, W = len(devs), devs[0].W
+    if len(columns) != K:
+        raise ValueError(f"{K} column descriptions expected, got {len(columns)}")
+    cols = [(np.ascontiguousarray(s, dtype=np.int32).ravel(), np.ascontiguousarray(p, dtype=np.int32).ravel()) for s, p in columns]
+    if any(len(s) != len(p) for s, p in cols):
+        raise ValueError("src and pos of a state must be equally long")
+    P = np.array([len(s) for s, _ in cols], dtype=np.int32)
+    src, pos = np.concatenate([s for s, _ in cols]), np.concatenate([p for _, p in cols])
+    rot = None if rot is None else _ffi.f64(rot)
+    unif = None if unif is None else _ffi.f64(unif)
+    seeds = np.zeros(K, dtype=np.uint64) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+    if seeds.shape != (K,):
+        raise ValueError(f"seeds ({K},) expected, got {seeds.shape}")
+    overlap, en = np.empty((K, K)), np.empty((6, K, K))
+    sizes = [(int(p) + 2 * K) * int(p) for p in P]
+    moments = np.empty(max(sum(sizes), 1))
+    u = np.empty((K, W)) if per_walker else None
+    enw = np.empty((K, W, 6)) if per_walker else None
+    rc = _ffi.lib().pqa_mix_moments(_handles(devs), K, _ffi.ptr(P), _ffi.ptr(src), _ffi.ptr(pos), float(offset), float(threshold),
+                                    _ffi.ptr(rot), _ffi.ptr(unif), _ffi.ptr(seeds), int(walker_chunk), _ffi.ptr(overlap), _ffi.ptr(en),
+                                    _ffi.ptr(moments), _ffi.ptr(u), _ffi.ptr(enw))
+    _ffi.check(devs[0]._h, rc)
+    offs = np.concatenate(([0], np.cumsum(sizes)))
+    mom = [moments[offs[i]:offs[i + 1]].reshape(int(P[i]) + 2 * K, int(P[i])) if P[i] else None for i in range(K)]
+    return (overlap, en, mom, u, enw) if per_walker else (overlap, en, mom)
+
+
+def mix_wtdp(devs, src, pos, walker_chunk=0):
+    """``pqa_mix_wtdp`` on the handles ``devs``: (overlap (K, K), wtdp (K, K, P)) with the derivative columns ``(src, pos)`` of the LAST
+    state; ``wtdp[j, k]`` and ``wtdp[k, j]`` are equal bits."""
+    K = len(devs)
+    src, pos = np.ascontiguousarray(src, dtype=np.int32).ravel(), np.ascontiguousarray(pos, dtype=np.int32).ravel()
+    if len(src) != len(pos):
+        raise ValueError("src and pos must be equally long")
+    overlap, wtdp = np.empty((K, K)), np.empty((K, K, len(src)))
+    rc = _ffi.lib().pqa_mix_wtdp(_handles(devs), K, len(src), _ffi.ptr(src), _ffi.ptr(pos), int(walker_chunk), _ffi.ptr(overlap),
+                                 _ffi.ptr(wtdp))
+    _ffi.check(devs[0]._h, rc)
+    return overlap, wtdp
+
+
+def _resident(energy, wfs):
+    """True when ``energy`` takes its averages from the walkers resident behind ``wfs`` (``avg_resident``) for this call."""
+    return hasattr(energy, "avg_resident") and energy.resolve_route(wfs) == "device"
+
+
 def _worker_fused(devs, wfs, configs, tstep, nsteps, energy):
     for wf in wfs:
         wf.recompute(configs)
@@ -116,12 +189,15 @@ def _worker_fused(devs, wfs, configs, tstep, nsteps, energy):
         for i in range(m * nelec):
             gauss[i] = np.random.normal(scale=np.sqrt(tstep), size=(nconf, 3))
             unif[i] = np.random.rand(nconf)
-        overlap, weights, _ = overlap_sweeps(devs, tstep, gauss, unif, weights=energy is not None)
-        if energy is not None:
+        resident = energy is not None and _resident(energy, wfs)  # (the walkers and the weights stay on the device then)
+        overlap, weights, _ = overlap_sweeps(devs, tstep, gauss, unif, weights=energy is not None and not resident)
+        if energy is not None and not resident:
             configs.configs[...] = devs[0].configs()
         for j in range(m):
             rolling_average(unweighted_block, {"overlap": overlap[j]}, nsteps)
-            if energy is not None:
+            if resident:
+                rolling_average(weighted_block, energy.avg_resident(wfs), nsteps)
+            elif energy is not None:
                 rolling_average(weighted_block, energy.avg(configs, wfs, weights), nsteps)
     configs.configs[...] = devs[0].configs()
     return weighted_block, unweighted_block, configs
