@@ -108,27 +108,26 @@ def device_gram(wf):
 
 
 SR_SOURCES = {"wf1det_coeff": 0, "wf2acoeff": 1, "wf2bcoeff": 2, "wf3ccoeff": 3}  # parameter -> source code of pqa_sr_moments
+SR_ORBITAL_SOURCES = {"wf1mo_coeff_alpha": 4, "wf1mo_coeff_beta": 5}  # the further source codes of pqa_sr_moments_orb
+SR_MOMENT_BYTES = 256 << 20  # most bytes of the (P + 2, P) moments the device calls take
+
+
+def _sr_columns(transform, codes):
+    src = [np.full(len(p), codes[k], dtype=np.int32) for k, p in transform._pos.items()]
+    pos = [np.asarray(p, dtype=np.int32) for p in transform._pos.values()]
+    return (np.concatenate(src), np.concatenate(pos)) if src else (np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))
 
 
 def sr_columns(transform):
     """``(src, pos)`` of ``pqa_sr_moments`` for a ``LinearTransform`` whose keys are all in ``SR_SOURCES``: column i of the serialised
     derivative matrix is flat entry ``pos[i]`` of the parameter ``src[i]`` names (key after key, selected entries in C order)."""
-    src = [np.full(len(p), SR_SOURCES[k], dtype=np.int32) for k, p in transform._pos.items()]
-    pos = [np.asarray(p, dtype=np.int32) for p in transform._pos.values()]
-    return (np.concatenate(src), np.concatenate(pos)) if src else (np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))
-
-
-SR_ORBITAL_SOURCES = {"wf1mo_coeff_alpha": 4, "wf1mo_coeff_beta": 5}  # the further source codes of pqa_sr_moments_orb
-SR_MOMENT_BYTES = 256 << 20  # most bytes of the (P + 2, P) moments the device calls take
+    return _sr_columns(transform, SR_SOURCES)
 
 
 def sr_columns_orb(transform):
     """``sr_columns`` for a transform whose keys may include the orbital coefficients: ``(src, pos)`` of ``pqa_sr_moments_orb``,
     ``pos`` of an orbital column the flat C-order index into its (nao, nmo_s) matrix."""
-    codes = {**SR_SOURCES, **SR_ORBITAL_SOURCES}
-    src = [np.full(len(p), codes[k], dtype=np.int32) for k, p in transform._pos.items()]
-    pos = [np.asarray(p, dtype=np.int32) for p in transform._pos.values()]
-    return (np.concatenate(src), np.concatenate(pos)) if src else (np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))
+    return _sr_columns(transform, {**SR_SOURCES, **SR_ORBITAL_SOURCES})
 
 
 def sr_columns_c(transform):
@@ -266,19 +265,17 @@ class StochasticReconfiguration:
         enacc.bind(dev)
         enacc._calls += 1
         key = int(np.random.randint(0, 2**31 - 1)) if enacc.seed is None else enacc.seed + enacc._calls
-        if dev.cplx or dev.twisted:
-            src, pos, tail = sr_columns_c(self.transform)
-            en, m = dev.sr_moments_c(src, pos, tail, 1e-3, weights=weights, threshold=enacc.threshold, seed=key)
-            self.last_route = "device"
-            d = {k: (en[i] if k in ("ecp", "total") else en[i].real) for i, k in enumerate(KEYS)}
-            d["dpidpj"], d["dpH"], d["dppsi"] = m[:-2], m[-2], m[-1]
-            return d
-        orbital = any(k in SR_ORBITAL_SOURCES for k in self.transform.to_opt)
-        src, pos = (sr_columns_orb if orbital else sr_columns)(self.transform)
+        cx = dev.cplx or dev.twisted
+        if cx:
+            moments, cols = dev.sr_moments_c, sr_columns_c
+        elif any(k in SR_ORBITAL_SOURCES for k in self.transform.to_opt):
+            moments, cols = dev.sr_moments_orb, sr_columns_orb
+        else:
+            moments, cols = dev.sr_moments, sr_columns
         # the reference regularises with the default cut-off in avg (:105)
-        en, m = (dev.sr_moments_orb if orbital else dev.sr_moments)(src, pos, 1e-3, weights=weights, threshold=enacc.threshold, seed=key)
+        en, m = moments(*cols(self.transform), 1e-3, weights=weights, threshold=enacc.threshold, seed=key)
         self.last_route = "device"
-        d = {k: en[i] for i, k in enumerate(KEYS)}
+        d = {k: (en[i] if not cx or k in ("ecp", "total") else en[i].real) for i, k in enumerate(KEYS)}
         d["dpidpj"], d["dpH"], d["dppsi"] = m[:-2], m[-2], m[-1]
         return d
 

@@ -346,12 +346,7 @@ extern "C" int pqa_slater_pgradient(pqa_handle_t* h, double* d_det, double* d_mo
   if (!h->has_slater || h->W == 0) FAIL("Slater state not initialised (call recompute)");
   const long W = h->W;
   const size_t cf = h->cplx ? 2 : 1;  // complex handles: every output is complex, (re, im) interleaved; nmo below counts orbitals
-  TRY(slater_value_dev(h));  // sign (complex: phase) / log of the determinant expansion -> b_sign, b_log
-  TRY(ensure(h, h->b_pgdet, cf * W * h->ndet * sizeof(double)));
-  const dim3 gd((unsigned)((W * h->ndet + 255) / 256));
-  if (h->cplx) hipLaunchKernelGGL((k_pgrad_det_c<>), gd, dim3(256), 0, h->stream, h->S, h->st, (const double*)h->b_sign.p, (const double*)h->b_log.p, W, (double*)h->b_pgdet.p);
-  else hipLaunchKernelGGL((k_pgrad_det<>), gd, dim3(256), 0, h->stream, h->S, h->st, (const double*)h->b_sign.p, (const double*)h->b_log.p, W, (double*)h->b_pgdet.p);
-  TRY(check_launch(h, "k_pgrad_det"));
+  TRY(pgrad_det_dev(h));  // (with the sign / log of the determinant expansion -> b_sign, b_log, which k_pgrad_mo reads below)
   if (d_det) TRY(copy_out(h, d_det, h->b_pgdet.p, cf * W * h->ndet * sizeof(double)));
   double* outs[2] = {d_mo_up, d_mo_dn};
   if (!d_mo_up && !d_mo_dn) return 0;
@@ -527,15 +522,8 @@ extern "C" int pqa_j3_pgradient(pqa_handle_t* h, double* d_ccoeff) {
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_j3 || h->W == 0) FAIL("three-body Jastrow state not initialised (call recompute)");
-  const long W = h->W;
-  const size_t E = (size_t)h->natom * h->na3 * h->na3 * h->nb3 * 3;
-  const size_t lds = ((size_t)h->N * h->natom * h->na3 + (size_t)h->N * (h->N - 1) / 2 * h->nb3) * sizeof(double);
-  if (lds > 150 * 1024) FAIL("three-body parameter gradient: the a/b value tables of one walker do not fit LDS");
-  TRY(ensure(h, h->b_out, (size_t)W * E * sizeof(double)));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_j3_pgrad<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((k_j3_pgrad<>), dim3((unsigned)W), dim3(64), lds, h->stream, h->S, h->js, (double*)h->b_out.p);
-  TRY(check_launch(h, "k_j3_pgrad"));
-  return copy_out(h, d_ccoeff, h->b_out.p, (size_t)W * E * sizeof(double));
+  TRY(j3_pgrad_dev(h));
+  return copy_out(h, d_ccoeff, h->b_out.p, (size_t)h->W * h->natom * h->na3 * h->na3 * h->nb3 * 3 * sizeof(double));
 }
 
 extern "C" int pqa_j3_recompute(pqa_handle_t* h, const double* configs, int64_t W, double* logval) {

@@ -6,7 +6,7 @@
 // (m = 0, 1, 2) and lap_e B_p (m = 3) for electron e, jas_diff_rows R[p] = B_p(e -> q) - B_p(e), and a caller contracts them with
 // whichever coefficient set it needs.
 //
-// Weighted walker means (pqa_obdm, pqa_sq): the weight sum k_wsum and the column reduction k_wcol_means / k_wcol_fold.
+// Weighted walker means (pqa_obdm, pqa_sq): the weight sum k_wsum (pqa_sr's too) and the column reduction k_wcol_means / k_wcol_fold.
 #pragma once
 #include "pqa_internal.hpp"
 
@@ -200,7 +200,7 @@ __device__ __forceinline__ double block_sum256(double v, double* sh) {
 
 // Weighted walker means (the mixed estimators of DMC: sum_w w_w res_w / sum_w w_w).
 //
-// sum of the W weights: one block, a fixed-order tree (the order of pqa_sr's k_sr_wsum)
+// sum of the W weights: one block, a fixed-order tree (pqa_sr launches it too)
 template <int PQA_UNIT = 0>  // (a template so that only the units that launch it compile it)
 static __global__ __launch_bounds__(256) void k_wsum(const double* __restrict__ wts, long W, double* __restrict__ out) {
   __shared__ double part[256];
@@ -328,12 +328,4 @@ inline std::vector<double> pack_coef_sets(const double* ca, const double* cb, in
     for (int p = 0; p < Pb; ++p) ct[(size_t)(Pa + p) * K + k] = cb[(size_t)k * Pb + p];
   }
   return ct;
-}
-
-// Raises kernel fn's dynamic-LDS limit to the 160 KiB of a CU, once per handle.
-inline int raise_lds_limit(pqa_handle* h, const void* fn) {
-  if (std::find(h->wide_attr.begin(), h->wide_attr.end(), fn) != h->wide_attr.end()) return 0;
-  HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  h->wide_attr.push_back(fn);
-  return 0;
 }

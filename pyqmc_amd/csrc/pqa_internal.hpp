@@ -457,5 +457,42 @@ int ecp_quadrature_offset(int naip);                      // first row of a quad
 int jas_refresh(pqa_handle* h);       // basis sums a fused sweep left stale, recomputed
 int slater_rebuild(pqa_handle* h);    // orbital cache, inverses and determinants of both spins from js.x
 int slater_value_dev(pqa_handle* h);  // sign / log of the Slater factor -> b_sign / b_log
+
+// Raises kernel fn's dynamic-LDS limit to the 160 KiB of a CU, once per handle.
+inline int raise_lds_limit(pqa_handle* h, const void* fn) {
+  if (std::find(h->wide_attr.begin(), h->wide_attr.end(), fn) != h->wide_attr.end()) return 0;
+  HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  h->wide_attr.push_back(fn);
+  return 0;
+}
+
+// d log Psi / d det_coeff of the resident walkers -> b_pgdet (W, ndet), complex handles (re, im) interleaved; the sign (complex: phase)
+// and log of the determinant expansion it divides by -> b_sign, b_log.  On h's stream.
+template <int PQA_UNIT = 0>  // (a template so that only the units that call it compile the kernels)
+inline int pgrad_det_dev(pqa_handle* h) {
+  const long W = h->W;
+  TRY(slater_value_dev(h));
+  TRY(ensure(h, h->b_pgdet, (size_t)(h->cplx ? 2 : 1) * W * h->ndet * sizeof(double)));
+  const dim3 gd((unsigned)((W * h->ndet + 255) / 256));
+  if (h->cplx)
+    hipLaunchKernelGGL((k_pgrad_det_c<PQA_UNIT>), gd, dim3(256), 0, h->stream, h->S, h->st, (const double*)h->b_sign.p, (const double*)h->b_log.p, W,
+                       (double*)h->b_pgdet.p);
+  else
+    hipLaunchKernelGGL((k_pgrad_det<PQA_UNIT>), gd, dim3(256), 0, h->stream, h->S, h->st, (const double*)h->b_sign.p, (const double*)h->b_log.p, W,
+                       (double*)h->b_pgdet.p);
+  return check_launch(h, "k_pgrad_det");
+}
+
+// d log Psi / d ccoeff of the resident walkers -> b_out (W, natom, na3, na3, nb3, 3): k_j3_pgrad, one wave per walker with the a / b
+// value tables of that walker in LDS.  On h's stream.
+template <int PQA_UNIT = 0>  // (a template so that only the units that call it compile the kernel)
+inline int j3_pgrad_dev(pqa_handle* h) {
+  const size_t lds = ((size_t)h->N * h->natom * h->na3 + (size_t)h->N * (h->N - 1) / 2 * h->nb3) * sizeof(double);
+  if (lds > 150 * 1024) FAIL("three-body parameter gradient: the a/b value tables of one walker do not fit LDS");
+  TRY(ensure(h, h->b_out, (size_t)h->W * h->natom * h->na3 * h->na3 * h->nb3 * 3 * sizeof(double)));
+  if (lds > 64 * 1024) TRY(raise_lds_limit(h, reinterpret_cast<const void*>(k_j3_pgrad<PQA_UNIT>)));
+  hipLaunchKernelGGL((k_j3_pgrad<PQA_UNIT>), dim3((unsigned)h->W), dim3(64), lds, h->stream, h->S, h->js, (double*)h->b_out.p);
+  return check_launch(h, "k_j3_pgrad");
+}
 // accumulators of the density-matrix estimators: shapes recorded on the first sweep, checked on the others; buffers sized
 int dm_prepare(pqa_handle* h, long nconf, long nval, int cx, int first, long nnorm_a, long nnorm_b);

@@ -11,7 +11,7 @@
 //   rows P_i+K ..          dpH[:, j] = sum_c E_j dp_p weights[i][j][c] / W      (E_j: state j's total energy, no offset)
 // the shape pqa_sr's product has with 2K further rows instead of 2, so it runs on pqa_srk.hpp's k_sr_syrk / k_sr_reduce.
 //   energy_dev       per handle, with its own key or draws: the rows pqa_energy gives (b_en of each handle);
-//   sr_sources       per handle, the derivative arrays its columns name (sources 0 - 2);
+//   sr_check_columns, sr_sources  per handle, the derivative arrays its columns name (sources 0 - 2; pqa_srk.hpp);
 //   values_dev       per handle: sign, log of the Slater factor and the Jastrow exponent;
 //   k_ovl_weights    weights (K, K, W), k_ovl_mean their walker means (pqa_multi.hpp: the kernels of pqa_overlap_sweeps);
 //   k_mix_scale      a (K, W), s (W), and u = a / sqrt(rho) for a caller that asks for it;
@@ -124,19 +124,6 @@ int mix_begin(pqa_handle* const* hs, int K, const char* fn) {
   return 0;
 }
 
-// The columns of one state: sources 0 - 2 within the handle's parameters -> need
-int mix_columns(pqa_handle* h, pqa_handle* g, const std::string& fn, int P, const int32_t* src, const int32_t* pos, bool (&need)[4]) {
-  long size[4];
-  sr_source_sizes(g, size);
-  for (int i = 0; i < P; ++i) {
-    if (src[i] < 0 || src[i] > 2)
-      FAIL(fn + ": src must be 0 (det_coeff), 1 (acoeff) or 2 (bcoeff) (three-body and orbital coefficients: the protocol route)");
-    if (pos[i] < 0 || pos[i] >= size[src[i]]) FAIL(fn + ": pos outside the parameter src names");
-    need[src[i]] = true;
-  }
-  return 0;
-}
-
 // values of every handle, then the weights (K, K, W) and their walker means (K, K) on the first handle's stream
 int mix_weights(pqa_handle* const* hs, int K, OvlPtrs& P, double* d_w, double* d_ovl) {
   pqa_handle* h = hs[0];
@@ -219,7 +206,7 @@ extern "C" int pqa_mix_moments(pqa_handle_t* const* hs, int K, const int32_t* P,
   if (ptot > 0 && (!src || !pos || !moments)) FAIL(fn + ": src, pos and moments must not be NULL when a state has columns");
   TRY(mix_begin(hs, K, "pqa_mix_moments"));
   bool need[kMaxK][4] = {};
-  for (int k = 0, off = 0; k < K; off += P[k], ++k) TRY(mix_columns(h, hs[k], fn, P[k], src + off, pos + off, need[k]));
+  for (int k = 0, off = 0; k < K; off += P[k], ++k) TRY(sr_check_columns(h, hs[k], fn, P[k], src + off, pos + off, 2, need[k]));
   const long W = h->W;
   StreamShare share(hs, K);
   // every handle's energy pass (its own draws) and derivative sources
@@ -235,8 +222,7 @@ extern "C" int pqa_mix_moments(pqa_handle_t* const* hs, int K, const int32_t* P,
     orot += (size_t)g->N * g->necp * 9;
     ounif += (size_t)g->N * g->necp * W;
   }
-  // plans of the states' products; scratch on the first handle: [weights (K, K, W) | a (K, W) | s (W) | u (K, W) | overlap (K, K) |
-  // en (6, K, K) | per-walker energies of one handle (W, 6) | moments of one state | A of one chunk | partials | src, pos of one state]
+  // plans of the states' products
   MixPlan plan[kMaxK];
   size_t amax = 0, pamax = 0, mmax = 0;
   for (int k = 0; k < K; ++k) {
@@ -246,21 +232,26 @@ extern "C" int pqa_mix_moments(pqa_handle_t* const* hs, int K, const int32_t* P,
     pamax = std::max(pamax, (size_t)plan[k].nslice * plan[k].nmom);
     mmax = std::max(mmax, plan[k].nmom);
   }
-  const size_t nw = (size_t)K * K * W, nu = u_walker ? (size_t)K * W : 0, nenw = en_walker ? (size_t)6 * W : 0;
-  const size_t ndbl = nw + (size_t)K * W + W + nu + (size_t)K * K + (size_t)6 * K * K + nenw + mmax + amax + pamax;
-  TRY(ensure(h, h->b_sr, ndbl * sizeof(double) + (size_t)2 * pmax * sizeof(int)));
-  double* d_w = (double*)h->b_sr.p;
-  double* d_a = d_w + nw;
-  double* d_s = d_a + (size_t)K * W;
-  double* d_u = d_s + W;
-  double* d_ovl = d_u + nu;
-  double* d_en = d_ovl + (size_t)K * K;
-  double* d_enw = d_en + (size_t)6 * K * K;
-  double* d_mom = d_enw + nenw;
-  double* d_A = d_mom + mmax;
-  double* d_part = d_A + amax;
-  int* d_src = (int*)(d_part + pamax);
-  int* d_pos = d_src + pmax;
+  // scratch on the first handle
+  double *d_w, *d_a, *d_s, *d_u, *d_ovl, *d_en, *d_enw, *d_mom, *d_A, *d_part;
+  int *d_src, *d_pos;
+  auto layout = [&](Carver c) {
+    d_w = c.take<double>((size_t)K * K * W);  // weights (K, K, W)
+    d_a = c.take<double>((size_t)K * W);
+    d_s = c.take<double>(W);
+    d_u = c.take<double>(u_walker ? (size_t)K * W : 0);
+    d_ovl = c.take<double>((size_t)K * K);
+    d_en = c.take<double>((size_t)6 * K * K);
+    d_enw = c.take<double>(en_walker ? (size_t)6 * W : 0);  // per-walker energies of one handle (W, 6)
+    d_mom = c.take<double>(mmax);                            // moments of one state
+    d_A = c.take<double>(amax);                              // A of one chunk
+    d_part = c.take<double>(pamax);
+    d_src = c.take<int>(pmax);  // src, pos of one state
+    d_pos = c.take<int>(pmax);
+    return c.size();
+  };
+  TRY(ensure(h, h->b_sr, layout(Carver())));
+  layout(Carver(h->b_sr.p));
   OvlPtrs O{};
   TRY(mix_weights(hs, K, O, d_w, d_ovl));
   const unsigned gb = (unsigned)((W + 255) / 256);
@@ -309,7 +300,7 @@ extern "C" int pqa_mix_wtdp(pqa_handle_t* const* hs, int K, int P, const int32_t
   TRY(mix_begin(hs, K, "pqa_mix_wtdp"));
   pqa_handle* g = hs[K - 1];  // the derivatives are the last state's
   bool need[4] = {false, false, false, false};
-  TRY(mix_columns(h, g, fn, P, src, pos, need));
+  TRY(sr_check_columns(h, g, fn, P, src, pos, 2, need));
   const long W = h->W;
   StreamShare share(hs, K);
   SrSources S{};
@@ -317,18 +308,23 @@ extern "C" int pqa_mix_wtdp(pqa_handle_t* const* hs, int K, int P, const int32_t
     int rc = sr_sources(g, need, S);
     if (rc) { h->err = g->err; return rc; }
   }
-  // scratch on the first handle: [weights (K, K, W) | s (W) | overlap (K, K) | moments | A of one chunk | partials | src, pos]
   const MixPlan p = mix_plan(W, P, npair, (long)walker_chunk_arg);
-  const size_t nw = (size_t)K * K * W, na = (size_t)p.Wc * p.lda, npart = (size_t)p.nslice * p.nmom;
-  TRY(ensure(h, h->b_sr, (nw + W + (size_t)K * K + p.nmom + na + npart) * sizeof(double) + (size_t)2 * P * sizeof(int)));
-  double* d_w = (double*)h->b_sr.p;
-  double* d_s = d_w + nw;
-  double* d_ovl = d_s + W;
-  double* d_mom = d_ovl + (size_t)K * K;
-  double* d_A = d_mom + p.nmom;
-  double* d_part = d_A + na;
-  int* d_src = (int*)(d_part + npart);
-  int* d_pos = d_src + P;
+  // scratch on the first handle
+  double *d_w, *d_s, *d_ovl, *d_mom, *d_A, *d_part;
+  int *d_src, *d_pos;
+  auto layout = [&](Carver c) {
+    d_w = c.take<double>((size_t)K * K * W);  // weights (K, K, W)
+    d_s = c.take<double>(W);
+    d_ovl = c.take<double>((size_t)K * K);
+    d_mom = c.take<double>(p.nmom);
+    d_A = c.take<double>((size_t)p.Wc * p.lda);  // A of one chunk
+    d_part = c.take<double>((size_t)p.nslice * p.nmom);
+    d_src = c.take<int>(P);
+    d_pos = c.take<int>(P);
+    return c.size();
+  };
+  TRY(ensure(h, h->b_sr, layout(Carver())));
+  layout(Carver(h->b_sr.p));
   TRY(copy_in(h, d_src, src, (size_t)P * sizeof(int)));
   TRY(copy_in(h, d_pos, pos, (size_t)P * sizeof(int)));
   OvlPtrs O{};

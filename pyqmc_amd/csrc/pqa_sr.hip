@@ -2,35 +2,32 @@
 //
 // The protocol route brings the walkers and every factor's (W x parameters) derivative arrays to the host, gathers the optimised
 // columns there and uploads [dp | E | 1] and w f dp again for one product (pqa_gram).  Everything the estimator needs is on the handle
-// already, so this call leaves it there:
+// already, so one host driver (sr_moments) leaves it there, for all three entries:
 //   energy_dev       the energy pass of pqa_energy (same draws, same per-walker rows in b_en);
-//   sources          det_coeff: k_pgrad_det (b_pgdet); acoeff / bcoeff: the basis sums the handle keeps (refreshed where a fused sweep
-//                    left them stale); ccoeff: k_j3_pgrad (b_out) - only those the column description names;
-//   k_sr_gather      per walker chunk of at most 256 MiB: the compact row-major A = [dp | E | 1] (Wc, P + 2) and the scale
-//                    s_w = w_w f_w (w: the normalised weight, f: the Pathak-Wagner weight from grad2);
-//   k_sr_syrk        A^T diag(s) A[:, :P] on v_mfma_f64_16x16x4_f64, walkers as the k dimension.  A block of four waves owns a 32 x 32
-//                    tile (one 16 x 16 tile per wave) and a slice of the walkers; 16 walkers of both column panels are staged in LDS per
-//                    step, the right-hand panel scaled by s as it is loaded (w f dp never exists in memory).  dpidpj is symmetric: of
-//                    its tiles only those on or above the diagonal are computed;
-//   k_sr_reduce      the slices' partial tiles summed in slice order (the same bits on every call), the lower triangle mirrored from
-//                    the upper one (dpidpj is exactly symmetric), added to the running moments of the chunks before;
-//   k_sr_means       the six weighted energy means, a fixed-order tree.
-// Only the (P + 2) x P moments and the six means leave the device (and the (W, 6) per-walker energies when the caller asks for them).
-//
-// pqa_sr_moments_orb adds the orbital coefficients as sources (4: mo_coeff_alpha, 5: mo_coeff_beta).  Their derivative
-//   G[a][m] = sum_u wu[u] sum_e ao[e][a] T_u[e][col_u(m)],   wu[u] = sum_{di: det_map[di] = u} det_coeff[di] d_det[di]
-// (k_pgrad_mo) never exists as a (W, nao, nmo) array: the AO values do not depend on u, so per walker and spin
-//   B[e][m] = sum_u wu[u] T_u[e][col_u(m)]   (n x nmo, zero where u does not occupy m),   G = ao^T B.
-//   launch_ao        value-only AO rows of the chunk's electrons (b_ao: the chunk's (Wc N, nao) rows, nothing of size W N nao);
-//   k_sr_orb         a block per walker: wu and B in LDS, G tile by tile on v_mfma_f64_16x16x4_f64, every entry stored through the
-//                    inverse column map colof straight into the chunk's A (entries nobody optimises are dropped);
-//   k_sr_gather      then fills the other columns and leaves the orbital ones alone.
-//
-// pqa_sr_moments_c takes complex and twisted handles (complex d_det, complex local energy) and the imaginary-part tail of the
-// reference's serialised matrix, with kernels of its own (k_sr_gather_c, k_sr_syrk_c, k_sr_reduce_c below): planar real / imaginary
-// panels, one to four matrix instructions per k-step by what the two column blocks of a tile can hold.
-//
-// k_sr_syrk, k_sr_reduce and the preparation of the sources (sr_sources) are pqa_srk.hpp's: pqa_mix forms its moments with them too.
+//   sr_sources       the derivative arrays the column description names (pqa_srk.hpp), and only those;
+//   k_wsum, k_sr_means  the weight sum and the weighted energy means, fixed-order trees;
+//   per walker chunk of at most 256 MiB:
+//     gather         the compact row-major A = [dp | E | 1] (Wc, P + 2) and the scale s_w = w_w f_w (w: the normalised weight, f: the
+//                    Pathak-Wagner weight from grad2);
+//     product        A^T diag(s) A[:, :P] over slices of the chunk's walkers (w f dp never exists in memory);
+//     reduce         the slices' partial tiles summed in slice order (the same bits on every call), the lower triangle mirrored from
+//                    the upper one, added to the running moments of the chunks before.
+// Only the (P + 2) x P moments and the energy means leave the device (and the per-walker energies / dp when the caller asks for them).
+// The entries differ where their data do:
+//   pqa_sr_moments      real handles, sources 0 - 3: k_sr_gather, k_sr_syrk, k_sr_reduce (the last two are pqa_srk.hpp's: pqa_mix forms
+//                       its moments with them too).
+//   pqa_sr_moments_orb  also the orbital coefficients (4: mo_coeff_alpha, 5: mo_coeff_beta).  Their derivative
+//                         G[a][m] = sum_u wu[u] sum_e ao[e][a] T_u[e][col_u(m)],   wu[u] = sum_{di: det_map[di] = u} det_coeff[di] d_det[di]
+//                       (k_pgrad_mo) never exists as a (W, nao, nmo) array: the AO values do not depend on u, so per walker and spin
+//                         B[e][m] = sum_u wu[u] T_u[e][col_u(m)]   (n x nmo, zero where u does not occupy m),   G = ao^T B.
+//                       Before the gather of a chunk, launch_ao writes the value-only AO rows of its electrons (b_ao: (Wc N, nao),
+//                       nothing of size W N nao) and k_sr_orb, a block per walker, forms wu and B in LDS and G tile by tile on
+//                       v_mfma_f64_16x16x4_f64, every entry stored through the inverse column map colof straight into A (entries
+//                       nobody optimises are dropped); k_sr_gather leaves those columns alone.
+//   pqa_sr_moments_c    complex and twisted handles (complex d_det, complex local energy; real handles are taken too) and the
+//                       imaginary-part tail of the reference's serialised matrix: A as planar real / imaginary panels
+//                       (k_sr_gather_c), one to four matrix instructions per k-step by what the two column blocks of a tile can hold
+//                       (k_sr_syrk_c, by a flag per column block), both planes reduced (k_sr_reduce_c); seven energy slots.
 #include "pqa_srk.hpp"
 
 namespace {
@@ -39,15 +36,6 @@ namespace {
 __device__ __forceinline__ double sr_nodal_f(double grad2, double cutoff) {
   const double x = 1.0 / (grad2 * (cutoff * cutoff));
   return x < 1.0 ? x * (9.0 + x * (-15.0 + 7.0 * x)) : 1.0;
-}
-
-// sum of the W weights: one block, a fixed-order tree
-__global__ __launch_bounds__(256) void k_sr_wsum(const double* __restrict__ wts, long W, double* __restrict__ out) {
-  __shared__ double part[256];
-  double a = 0.0;
-  for (long w = threadIdx.x; w < W; w += 256) a += wts[w];
-  a = block_sum256(a, part);
-  if (threadIdx.x == 0) out[0] = a;
 }
 
 // normalised weight of walker w (wts == nullptr: 1 / W)
@@ -304,23 +292,33 @@ __global__ __launch_bounds__(256) void k_sr_reduce_c(const double* __restrict__ 
 
 }  // namespace
 
-// Both entries.  fn: the entry's name (its messages); orb: sources 4 / 5 are accepted; chunk: walkers per chunk (0: the scratch rule);
-// dp_walker: host (W, P) or NULL.
-static int sr_moments(pqa_handle_t* h, const std::string& fn, bool orb, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff,
-               const double* weights, double threshold, const double* rot, const double* unif, uint64_t seed, long chunk, double* en_mean,
-               double* moments, double* en_walker, double* dp_walker) {
+// What an entry is: its name (in messages), whether sources 4 / 5 are accepted, whether its columns are complex (then with the ntail
+// twins tail names), walkers per chunk (0: the scratch rule), dp_walker: host (W, P) doubles / (W, P + ntail) complex, or NULL.
+struct SrEntry {
+  const char* name;
+  bool orb, cx;
+  int ntail;
+  const int32_t* tail;
+  long chunk;
+  double* dp_walker;
+};
+
+static int sr_moments(pqa_handle_t* h, const SrEntry& e, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff, const double* weights,
+                      double threshold, const double* rot, const double* unif, uint64_t seed, double* en_mean, double* moments, double* en_walker) {
+  const std::string fn = e.name;
+  const int ntail = e.ntail;
   // argument checks first: they need nothing but the handle's host-side sizes
   if (P < 1) FAIL(fn + ": P must be at least 1");
   if (!src || !pos || !en_mean || !moments) FAIL(fn + ": src, pos, en_mean and moments must not be NULL");
+  if (e.cx && (ntail < 0 || ntail > P || (ntail > 0 && !e.tail))) FAIL(fn + ": ntail must be within 0 .. P, with tail given");
   if (!(nodal_cutoff > 0.0)) FAIL(fn + ": nodal_cutoff must be positive");
-  if (h->cplx) FAIL(fn + ": complex orbitals / twisted cell (outside the device scope: use the protocol route)");
-  long size[4];
-  sr_source_sizes(h, size);
+  if (h->cplx && !e.cx) FAIL(fn + ": complex orbitals / twisted cell (outside the device scope: use the protocol route)");
   bool need[4] = {false, false, false, false};
   bool orb_spin[2] = {false, false};
   std::vector<int> colof[2];  // [nao][nmo_s]: the column of A an orbital-coefficient entry fills, or -1
-  for (int i = 0; i < P; ++i) {
-    if (orb && (src[i] == 4 || src[i] == 5)) {
+  for (int i = 0; i < P; ++i) {  // (column by column: the first bad column is the one reported, of whichever kind)
+    const bool mo = src[i] == 4 || src[i] == 5;
+    if (mo && e.orb) {
       const int s = src[i] - 4, n = s ? h->ndn : h->nup;
       const char* why = !h->has_slater                ? "the handle has no Slater factor"
                         : h->twist                     ? "twisted cell"
@@ -336,20 +334,33 @@ static int sr_moments(pqa_handle_t* h, const std::string& fn, bool orb, int P, c
       orb_spin[s] = true;
       continue;
     }
-    if (src[i] < 0 || src[i] > 3)
-      FAIL(fn + (orb ? ": src must be 0 (det_coeff), 1 (acoeff), 2 (bcoeff), 3 (ccoeff), 4 (mo_coeff_alpha) or 5 (mo_coeff_beta)"
-                     : ": src must be 0 (det_coeff), 1 (acoeff), 2 (bcoeff) or 3 (ccoeff)"));
-    if (pos[i] < 0 || pos[i] >= size[src[i]]) FAIL(fn + ": pos outside the parameter src names (or the handle has no such factor)");
-    need[src[i]] = true;
+    if (mo && e.cx) FAIL(fn + ": orbital coefficients are not a source here (complex / periodic layouts: use the protocol route)");
+    if (e.orb && (src[i] < 0 || src[i] > 3))
+      FAIL(fn + ": src must be 0 (det_coeff), 1 (acoeff), 2 (bcoeff), 3 (ccoeff), 4 (mo_coeff_alpha) or 5 (mo_coeff_beta)");
+    TRY(sr_check_columns(h, h, fn, 1, src + i, pos + i, 3, need));
   }
   const bool has_orb = orb_spin[0] || orb_spin[1];
-  if (chunk < 0) FAIL(fn + ": walker_chunk must not be negative");
-  const size_t nmom = (size_t)(P + 2) * P;
-  if (nmom * sizeof(double) > kChunkScratchBytes) FAIL(fn + ": the (P + 2) x P moments exceed the 256 MiB scratch limit (use the protocol route)");
+  if (e.cx) {
+    std::vector<char> seen((size_t)P, 0);
+    for (int t = 0; t < ntail; ++t) {
+      if (e.tail[t] < 0 || e.tail[t] >= P) FAIL(fn + ": tail names a primary column out of range");
+      if (seen[e.tail[t]]) FAIL(fn + ": tail names a primary column twice");
+      seen[e.tail[t]] = 1;
+    }
+  }
+  if (e.chunk < 0) FAIL(fn + ": walker_chunk must not be negative");
+  // Pt columns (the primary ones and the tail), cf planes of (Pt + 2) x Pt moments
+  const int Pt = P + ntail, lda = Pt + 2, cf = e.cx ? 2 : 1;
+  const size_t nmom = (size_t)lda * Pt;
+  if (cf * nmom * sizeof(double) > kChunkScratchBytes)
+    FAIL(fn + (e.cx ? ": the (Pt + 2) x Pt complex moments exceed the 256 MiB scratch limit (use the protocol route)"
+                    : ": the (P + 2) x P moments exceed the 256 MiB scratch limit (use the protocol route)"));
   if (h->W == 0) FAIL("state not initialised (call pqa_wf_recompute)");
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   const long W = h->W;
+  const int cplx = h->cplx ? 1 : 0, nen = cplx ? 7 : 6;  // rows of b_en
+  const int nout = e.cx ? 7 : 6;                         // energy slots the entry returns (a real handle leaves the seventh zero)
   h->saved_valid = false;  // (as pqa_energy: the saved orbital rows of a gradient_value call are overwritten)
   TRY(energy_dev(h, threshold, rot, unif, seed, 0u));
   const double* d_en = (const double*)h->b_en.p;
@@ -357,12 +368,9 @@ static int sr_moments(pqa_handle_t* h, const std::string& fn, bool orb, int P, c
   SrSources S{};
   need[0] = need[0] || has_orb;  // (the orbital columns need d_det for the determinant weights)
   TRY(sr_sources(h, need, S));
-  // scratch: [moments | means (6) | weight sum (1) | weights (W) | per-walker energies (W, 6) | scale (Wc) | A (Wc, P + 2) |
-  // partials (nslice, P + 2, P) | src, pos | colof of each spin]; with orbital columns a chunk's A and AO rows (b_ao) together stay
-  // within the chunk limit
-  const int lda = P + 2;
-  long Wc = walker_chunk(W, ((size_t)lda + (has_orb ? (size_t)h->N * h->nao : 0)) * sizeof(double));
-  if (chunk > 0) Wc = std::min(Wc, chunk);
+  // with orbital columns a chunk's A and AO rows (b_ao) together stay within the chunk limit
+  long Wc = walker_chunk(W, ((size_t)cf * lda + (has_orb ? (size_t)h->N * h->nao : 0)) * sizeof(double));
+  if (e.chunk > 0) Wc = std::min(Wc, e.chunk);
   size_t orb_lds[2] = {0, 0};
   for (int s = 0; s < 2; ++s)
     if (orb_spin[s]) {
@@ -370,39 +378,61 @@ static int sr_moments(pqa_handle_t* h, const std::string& fn, bool orb, int P, c
       orb_lds[s] = ((size_t)((n + 3) & ~3) * sr_orb_ldb(h->nmo[s]) + h->ndet_s[s]) * sizeof(double);
       if (orb_lds[s] > 150 * 1024) FAIL(fn + ": orbital coefficients: the determinant weights of one walker do not fit LDS (use the protocol route)");
     }
-  const int nbi = (lda + 31) / 32, nbj = (P + 31) / 32;
-  const long nslice = sr_slices(Wc, nbi, nbj, nmom);
-  const size_t nw = weights ? (size_t)W : 0, nenw = en_walker ? (size_t)6 * W : 0;
-  const size_t ndbl = nmom + 6 + 1 + nw + nenw + (size_t)Wc + (size_t)Wc * lda + (size_t)nslice * nmom;
-  TRY(ensure(h, h->b_sr, ndbl * sizeof(double) + ((size_t)2 * P + colof[0].size() + colof[1].size()) * sizeof(int)));
-  double* d_mom = (double*)h->b_sr.p;
-  double* d_mean = d_mom + nmom;
-  double* d_wsum = d_mean + 6;
-  double* d_wts = d_wsum + 1;
-  double* d_enw = d_wts + nw;
-  double* d_scale = d_enw + nenw;
-  double* d_A = d_scale + Wc;
-  double* d_part = d_A + (size_t)Wc * lda;
-  int* d_src = (int*)(d_part + (size_t)nslice * nmom);
-  int* d_pos = d_src + P;
+  const int nbi = (lda + 31) / 32, nbj = (Pt + 31) / 32;
+  const long nslice = sr_slices(Wc, nbi, nbj, cf * nmom);
+  // complex columns: one flag per 32-column block of A: does it hold a column that can have an imaginary part (source 0 of a complex
+  // handle, a tail column, the E column of a complex handle)
+  std::vector<int> flag(e.cx ? (size_t)nbi : 0, 0);
+  if (e.cx) {
+    for (int i = 0; i < P; ++i)
+      if (cplx && src[i] == 0) flag[i / 32] = 1;
+    for (int i = P; i < Pt; ++i) flag[i / 32] = 1;
+    if (cplx) flag[Pt / 32] = 1;
+  }
+  // scratch
+  double *d_mom, *d_mean, *d_wsum, *d_wts, *d_enw, *d_scale, *d_A, *d_dp, *d_part;
+  int *d_src, *d_pos, *d_tail, *d_flag, *d_colof[2];
+  auto layout = [&](Carver c) {
+    d_mom = c.take<double>(cf * nmom);
+    d_mean = c.take<double>(nout);
+    d_wsum = c.take<double>(1);
+    d_wts = c.take<double>(weights ? W : 0);
+    d_enw = c.take<double>(en_walker ? (size_t)nen * W : 0);  // per-walker energies (W, nen)
+    d_scale = c.take<double>(Wc);
+    d_A = c.take<double>((size_t)cf * Wc * lda);  // complex columns: the real plane, then the imaginary one
+    d_dp = c.take<double>(e.cx && e.dp_walker ? (size_t)2 * Wc * Pt : 0);  // interleaved dp of a chunk
+    d_part = c.take<double>((size_t)nslice * cf * nmom);
+    d_src = c.take<int>(P);
+    d_pos = c.take<int>(P);
+    d_tail = c.take<int>(ntail);
+    d_flag = c.take<int>(flag.size());
+    for (int s = 0; s < 2; ++s) d_colof[s] = c.take<int>(colof[s].size());
+    return c.size();
+  };
+  TRY(ensure(h, h->b_sr, layout(Carver())));
+  layout(Carver(h->b_sr.p));
+  double* d_Ai = d_A + (size_t)Wc * lda;
   TRY(copy_in(h, d_src, src, (size_t)P * sizeof(int)));
   TRY(copy_in(h, d_pos, pos, (size_t)P * sizeof(int)));
-  int* d_colof[2] = {d_pos + P, d_pos + P + colof[0].size()};
+  TRY(copy_in(h, d_tail, e.tail, (size_t)ntail * sizeof(int)));
+  TRY(copy_in(h, d_flag, flag.data(), flag.size() * sizeof(int)));
   for (int s = 0; s < 2; ++s) TRY(copy_in(h, d_colof[s], colof[s].data(), colof[s].size() * sizeof(int)));
   if (has_orb) TRY(ensure(h, h->b_ao, (size_t)Wc * h->N * h->nao * sizeof(double)));
   const double* wts = nullptr;
   if (weights) {
     TRY(copy_in(h, d_wts, weights, (size_t)W * sizeof(double)));
-    hipLaunchKernelGGL(k_sr_wsum, dim3(1), dim3(256), 0, h->stream, (const double*)d_wts, W, d_wsum);
-    TRY(check_launch(h, "k_sr_wsum"));
+    hipLaunchKernelGGL((k_wsum<>), dim3(1), dim3(256), 0, h->stream, (const double*)d_wts, W, d_wsum);
+    TRY(check_launch(h, "k_wsum"));
     wts = d_wts;
   }
-  hipLaunchKernelGGL(k_sr_means, dim3(6), dim3(256), 0, h->stream, d_en, wts, (const double*)d_wsum, W, d_mean);
+  hipLaunchKernelGGL(k_sr_means, dim3((unsigned)nen), dim3(256), 0, h->stream, d_en, wts, (const double*)d_wsum, W, d_mean);
   TRY(check_launch(h, "k_sr_means"));
+  const dim3 gmom((unsigned)((nmom + 255) / 256));
   for (long w0 = 0; w0 < W; w0 += Wc) {
     const long wc = std::min(Wc, W - w0);
     const long ns = std::min<long>(nslice, std::max<long>(1, wc / 64));
     const long per = ((wc + ns - 1) / ns + kSrKB - 1) / kSrKB * kSrKB;  // walkers per slice, whole staging steps
+    const dim3 ggather((unsigned)((wc * lda + 255) / 256)), gsyrk((unsigned)nbj, (unsigned)nbi, (unsigned)ns);
     if (has_orb) {
       TRY(launch_ao(h, plain_points(h->js.x + (size_t)w0 * h->N * 3, wc * h->N), wc * h->N, 1, (double*)h->b_ao.p));
       const unsigned nwave = (unsigned)std::min(4, (h->nao + 15) / 16);
@@ -415,188 +445,69 @@ static int sr_moments(pqa_handle_t* h, const std::string& fn, bool orb, int P, c
         TRY(check_launch(h, "k_sr_orb"));
       }
     }
-    hipLaunchKernelGGL(k_sr_gather, dim3((unsigned)((wc * lda + 255) / 256)), dim3(256), 0, h->stream, S, (const int*)d_src,
-                       (const int*)d_pos, P, d_en, wts, (const double*)d_wsum, nodal_cutoff, W, w0, wc, d_A, d_scale);
-    TRY(check_launch(h, "k_sr_gather"));
-    if (dp_walker) {  // the chunk's dp = A[:, :P], before the next chunk overwrites it
-      HIPCHK(hipMemcpy2DAsync(dp_walker + (size_t)w0 * P, (size_t)P * sizeof(double), d_A, (size_t)lda * sizeof(double),
-                              (size_t)P * sizeof(double), (size_t)wc, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));
+    // gather, and the chunk's dp for the caller that asked for it, before the next chunk overwrites it
+    if (e.cx) {
+      hipLaunchKernelGGL(k_sr_gather_c, ggather, dim3(256), 0, h->stream, S, (const int*)d_src, (const int*)d_pos, P, (const int*)d_tail, ntail,
+                         cplx, d_en, wts, (const double*)d_wsum, nodal_cutoff, W, w0, wc, d_A, d_Ai, d_scale, e.dp_walker ? d_dp : nullptr);
+      TRY(check_launch(h, "k_sr_gather_c"));
+      if (e.dp_walker) TRY(copy_out(h, e.dp_walker + (size_t)2 * w0 * Pt, d_dp, (size_t)2 * wc * Pt * sizeof(double)));
+    } else {
+      hipLaunchKernelGGL(k_sr_gather, ggather, dim3(256), 0, h->stream, S, (const int*)d_src, (const int*)d_pos, P, d_en, wts,
+                         (const double*)d_wsum, nodal_cutoff, W, w0, wc, d_A, d_scale);
+      TRY(check_launch(h, "k_sr_gather"));
+      if (e.dp_walker) {  // dp = A[:, :P]
+        HIPCHK(hipMemcpy2DAsync(e.dp_walker + (size_t)w0 * P, (size_t)P * sizeof(double), d_A, (size_t)lda * sizeof(double),
+                                (size_t)P * sizeof(double), (size_t)wc, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+      }
     }
-    hipLaunchKernelGGL(k_sr_syrk, dim3((unsigned)nbj, (unsigned)nbi, (unsigned)ns), dim3(256), 0, h->stream, (const double*)d_A,
-                       (const double*)d_scale, wc, P, 2, 1, per, d_part);
-    TRY(check_launch(h, "k_sr_syrk"));
-    hipLaunchKernelGGL(k_sr_reduce, dim3((unsigned)((nmom + 255) / 256)), dim3(256), 0, h->stream, (const double*)d_part, P, 2, 0, (int)ns,
-                       (int)(w0 == 0), 0, d_mom);
-    TRY(check_launch(h, "k_sr_reduce"));
-  }
-  TRY(copy_in(h, moments, d_mom, nmom * sizeof(double)));
-  if (en_walker) {
-    transpose(h, d_en, d_enw, 6, W);  // rows (6, W) -> (W, 6)
-    TRY(check_launch(h, "k_transpose"));
-    TRY(copy_in(h, en_walker, d_enw, (size_t)6 * W * sizeof(double)));
-  }
-  return copy_out(h, en_mean, d_mean, 6 * sizeof(double));
-}
-
-extern "C" int pqa_sr_moments(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff, const double* weights,
-                              double threshold, const double* rot, const double* unif, uint64_t seed, double* en_mean, double* moments,
-                              double* en_walker) {
-  return sr_moments(h, "pqa_sr_moments", false, P, src, pos, nodal_cutoff, weights, threshold, rot, unif, seed, 0, en_mean, moments, en_walker,
-                    nullptr);
-}
-
-extern "C" int pqa_sr_moments_orb(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff, const double* weights,
-                                  double threshold, const double* rot, const double* unif, uint64_t seed, int64_t walker_chunk,
-                                  double* en_mean, double* moments, double* en_walker, double* dp_walker) {
-  return sr_moments(h, "pqa_sr_moments_orb", true, P, src, pos, nodal_cutoff, weights, threshold, rot, unif, seed, (long)walker_chunk, en_mean,
-                    moments, en_walker, dp_walker);
-}
-
-// The complex entry: the steps of sr_moments with complex columns (k_sr_gather_c, k_sr_syrk_c, k_sr_reduce_c).  Real handles are taken
-// too (zero imaginary planes, six energy rows): a cross-check against pqa_sr_moments.
-extern "C" int pqa_sr_moments_c(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, int ntail, const int32_t* tail,
-                                double nodal_cutoff, const double* weights, double threshold, const double* rot, const double* unif,
-                                uint64_t seed, int64_t walker_chunk_arg, double* en_mean, double* moments, double* en_walker,
-                                double* dp_walker) {
-  const std::string fn = "pqa_sr_moments_c";
-  // argument checks first: they need nothing but the handle's host-side sizes
-  if (P < 1) FAIL(fn + ": P must be at least 1");
-  if (!src || !pos || !en_mean || !moments) FAIL(fn + ": src, pos, en_mean and moments must not be NULL");
-  if (ntail < 0 || ntail > P || (ntail > 0 && !tail)) FAIL(fn + ": ntail must be within 0 .. P, with tail given");
-  if (!(nodal_cutoff > 0.0)) FAIL(fn + ": nodal_cutoff must be positive");
-  const long size[4] = {h->has_slater ? (long)h->ndet : 0, h->has_j2 ? (long)h->natom * h->na * 2 : 0, h->has_j2 ? (long)h->nb * 3 : 0,
-                        h->has_j3 ? (long)h->natom * h->na3 * h->na3 * h->nb3 * 3 : 0};
-  bool need[4] = {false, false, false, false};
-  for (int i = 0; i < P; ++i) {
-    if (src[i] == 4 || src[i] == 5) FAIL(fn + ": orbital coefficients are not a source here (complex / periodic layouts: use the protocol route)");
-    if (src[i] < 0 || src[i] > 3) FAIL(fn + ": src must be 0 (det_coeff), 1 (acoeff), 2 (bcoeff) or 3 (ccoeff)");
-    if (pos[i] < 0 || pos[i] >= size[src[i]]) FAIL(fn + ": pos outside the parameter src names (or the handle has no such factor)");
-    need[src[i]] = true;
-  }
-  {
-    std::vector<char> seen((size_t)P, 0);
-    for (int t = 0; t < ntail; ++t) {
-      if (tail[t] < 0 || tail[t] >= P) FAIL(fn + ": tail names a primary column out of range");
-      if (seen[tail[t]]) FAIL(fn + ": tail names a primary column twice");
-      seen[tail[t]] = 1;
+    // product and reduce
+    if (e.cx) {
+      hipLaunchKernelGGL(k_sr_syrk_c, gsyrk, dim3(256), 0, h->stream, (const double*)d_A, (const double*)d_Ai, (const double*)d_scale,
+                         (const int*)d_flag, wc, Pt, per, d_part);
+      TRY(check_launch(h, "k_sr_syrk_c"));
+      hipLaunchKernelGGL(k_sr_reduce_c, gmom, dim3(256), 0, h->stream, (const double*)d_part, Pt, (int)ns, (int)(w0 == 0), d_mom);
+      TRY(check_launch(h, "k_sr_reduce_c"));
+    } else {
+      hipLaunchKernelGGL(k_sr_syrk, gsyrk, dim3(256), 0, h->stream, (const double*)d_A, (const double*)d_scale, wc, P, 2, 1, per, d_part);
+      TRY(check_launch(h, "k_sr_syrk"));
+      hipLaunchKernelGGL(k_sr_reduce, gmom, dim3(256), 0, h->stream, (const double*)d_part, P, 2, 0, (int)ns, (int)(w0 == 0), 0, d_mom);
+      TRY(check_launch(h, "k_sr_reduce"));
     }
   }
-  if (walker_chunk_arg < 0) FAIL(fn + ": walker_chunk must not be negative");
-  const int Pt = P + ntail, lda = Pt + 2;
-  const size_t nmom = (size_t)lda * Pt;  // complex entries of the moments
-  if (2 * nmom * sizeof(double) > kChunkScratchBytes) FAIL(fn + ": the (Pt + 2) x Pt complex moments exceed the 256 MiB scratch limit (use the protocol route)");
-  if (h->W == 0) FAIL("state not initialised (call pqa_wf_recompute)");
-  TRY(sync_aos(h));
-  HIPCHK(hipSetDevice(h->device));
-  const long W = h->W;
-  const int cplx = h->cplx ? 1 : 0, nen = cplx ? 7 : 6;
-  h->saved_valid = false;  // (as pqa_energy: the saved orbital rows of a gradient_value call are overwritten)
-  TRY(energy_dev(h, threshold, rot, unif, seed, 0u));
-  const double* d_en = (const double*)h->b_en.p;
-  // derivative sources
-  SrSources S{};
-  if (need[0]) {
-    TRY(slater_value_dev(h));  // sign (complex: phase) / log of the determinant expansion -> b_sign, b_log
-    TRY(ensure(h, h->b_pgdet, (size_t)(cplx ? 2 : 1) * W * h->ndet * sizeof(double)));
-    const dim3 gd((unsigned)((W * h->ndet + 255) / 256));
-    if (cplx)
-      hipLaunchKernelGGL((k_pgrad_det_c<>), gd, dim3(256), 0, h->stream, h->S, h->st, (const double*)h->b_sign.p, (const double*)h->b_log.p, W,
-                         (double*)h->b_pgdet.p);
-    else
-      hipLaunchKernelGGL((k_pgrad_det<>), gd, dim3(256), 0, h->stream, h->S, h->st, (const double*)h->b_sign.p, (const double*)h->b_log.p, W,
-                         (double*)h->b_pgdet.p);
-    TRY(check_launch(h, "k_pgrad_det"));
-    S.base[0] = (const double*)h->b_pgdet.p; S.stride[0] = size[0];
-  }
-  if (need[1] || need[2]) {
-    TRY(jas_refresh(h));
-    S.base[1] = h->js.avalues; S.stride[1] = size[1];
-    S.base[2] = h->js.bvalues; S.stride[2] = size[2];
-  }
-  if (need[3]) {
-    const size_t lds = ((size_t)h->N * h->natom * h->na3 + (size_t)h->N * (h->N - 1) / 2 * h->nb3) * sizeof(double);
-    if (lds > 150 * 1024) FAIL("three-body parameter gradient: the a/b value tables of one walker do not fit LDS");
-    TRY(ensure(h, h->b_out, (size_t)W * size[3] * sizeof(double)));
-    if (lds > 64 * 1024) TRY(raise_lds_limit(h, reinterpret_cast<const void*>(k_j3_pgrad<>)));
-    hipLaunchKernelGGL((k_j3_pgrad<>), dim3((unsigned)W), dim3(64), lds, h->stream, h->S, h->js, (double*)h->b_out.p);
-    TRY(check_launch(h, "k_j3_pgrad"));
-    S.base[3] = (const double*)h->b_out.p; S.stride[3] = size[3];
-  }
-  // one flag per 32-column block of A: does it hold a column that can have an imaginary part (source 0 of a complex handle, a tail
-  // column, the E column of a complex handle)
-  const int nbi = (lda + 31) / 32, nbj = (Pt + 31) / 32;
-  std::vector<int> flag((size_t)nbi, 0);
-  for (int i = 0; i < P; ++i)
-    if (cplx && src[i] == 0) flag[i / 32] = 1;
-  for (int i = P; i < Pt; ++i) flag[i / 32] = 1;
-  if (cplx) flag[Pt / 32] = 1;
-  // scratch: [moments (2 nmom) | means (7) | weight sum (1) | weights (W) | per-walker energies (W, nen) | scale (Wc) | Ar, Ai (Wc, Pt + 2) |
-  // interleaved dp (Wc, Pt) when asked for | partials (nslice, 2, Pt + 2, Pt) | src, pos, tail, flag]
-  long Wc = walker_chunk(W, (size_t)2 * lda * sizeof(double));
-  if (walker_chunk_arg > 0) Wc = std::min<long>(Wc, (long)walker_chunk_arg);
-  long nslice = std::min<long>(std::max<long>(1, 1024 / ((long)nbi * nbj)), std::max<long>(1, Wc / 64));
-  nslice = std::max<long>(1, std::min<long>(nslice, (long)(kChunkScratchBytes / (2 * nmom * sizeof(double)))));
-  const size_t nw = weights ? (size_t)W : 0, nenw = en_walker ? (size_t)nen * W : 0, ndp = dp_walker ? (size_t)2 * Wc * Pt : 0;
-  const size_t ndbl = 2 * nmom + 7 + 1 + nw + nenw + (size_t)Wc + (size_t)2 * Wc * lda + ndp + (size_t)nslice * 2 * nmom;
-  TRY(ensure(h, h->b_sr, ndbl * sizeof(double) + ((size_t)2 * P + ntail + nbi) * sizeof(int)));
-  double* d_mom = (double*)h->b_sr.p;
-  double* d_mean = d_mom + 2 * nmom;
-  double* d_wsum = d_mean + 7;
-  double* d_wts = d_wsum + 1;
-  double* d_enw = d_wts + nw;
-  double* d_scale = d_enw + nenw;
-  double* d_Ar = d_scale + Wc;
-  double* d_Ai = d_Ar + (size_t)Wc * lda;
-  double* d_dp = d_Ai + (size_t)Wc * lda;
-  double* d_part = d_dp + ndp;
-  int* d_src = (int*)(d_part + (size_t)nslice * 2 * nmom);
-  int* d_pos = d_src + P;
-  int* d_tail = d_pos + P;
-  int* d_flag = d_tail + ntail;
-  TRY(copy_in(h, d_src, src, (size_t)P * sizeof(int)));
-  TRY(copy_in(h, d_pos, pos, (size_t)P * sizeof(int)));
-  TRY(copy_in(h, d_tail, tail, (size_t)ntail * sizeof(int)));
-  TRY(copy_in(h, d_flag, flag.data(), (size_t)nbi * sizeof(int)));
-  HIPCHK(hipStreamSynchronize(h->stream));  // (flag is a local: the copy has read it before it goes)
-  const double* wts = nullptr;
-  if (weights) {
-    TRY(copy_in(h, d_wts, weights, (size_t)W * sizeof(double)));
-    hipLaunchKernelGGL(k_sr_wsum, dim3(1), dim3(256), 0, h->stream, (const double*)d_wts, W, d_wsum);
-    TRY(check_launch(h, "k_sr_wsum"));
-    wts = d_wts;
-  }
-  hipLaunchKernelGGL(k_sr_means, dim3((unsigned)nen), dim3(256), 0, h->stream, d_en, wts, (const double*)d_wsum, W, d_mean);
-  TRY(check_launch(h, "k_sr_means"));
-  for (long w0 = 0; w0 < W; w0 += Wc) {
-    const long wc = std::min(Wc, W - w0);
-    const long ns = std::min<long>(nslice, std::max<long>(1, wc / 64));
-    const long per = ((wc + ns - 1) / ns + kSrKB - 1) / kSrKB * kSrKB;  // walkers per slice, whole staging steps
-    hipLaunchKernelGGL(k_sr_gather_c, dim3((unsigned)((wc * lda + 255) / 256)), dim3(256), 0, h->stream, S, (const int*)d_src, (const int*)d_pos, P,
-                       (const int*)d_tail, ntail, cplx, d_en, wts, (const double*)d_wsum, nodal_cutoff, W, w0, wc, d_Ar, d_Ai, d_scale,
-                       dp_walker ? d_dp : nullptr);
-    TRY(check_launch(h, "k_sr_gather_c"));
-    if (dp_walker)  // the chunk's dp, before the next chunk overwrites it
-      TRY(copy_out(h, dp_walker + (size_t)2 * w0 * Pt, d_dp, (size_t)2 * wc * Pt * sizeof(double)));
-    hipLaunchKernelGGL(k_sr_syrk_c, dim3((unsigned)nbj, (unsigned)nbi, (unsigned)ns), dim3(256), 0, h->stream, (const double*)d_Ar,
-                       (const double*)d_Ai, (const double*)d_scale, (const int*)d_flag, wc, Pt, per, d_part);
-    TRY(check_launch(h, "k_sr_syrk_c"));
-    hipLaunchKernelGGL(k_sr_reduce_c, dim3((unsigned)((nmom + 255) / 256)), dim3(256), 0, h->stream, (const double*)d_part, Pt, (int)ns,
-                       (int)(w0 == 0), d_mom);
-    TRY(check_launch(h, "k_sr_reduce_c"));
-  }
-  TRY(copy_in(h, moments, d_mom, 2 * nmom * sizeof(double)));
+  TRY(copy_in(h, moments, d_mom, cf * nmom * sizeof(double)));
   if (en_walker) {
-    transpose(h, d_en, d_enw, nen, W);  // rows (nen, W) -> (W, nen)
+    transpose(h, d_en, d_enw, nen, W);  // rows (nen, W) -> (W, nen), into the caller's (W, nout)
     TRY(check_launch(h, "k_transpose"));
-    HIPCHK(hipMemcpy2DAsync(en_walker, 7 * sizeof(double), d_enw, (size_t)nen * sizeof(double), (size_t)nen * sizeof(double), (size_t)W,
+    HIPCHK(hipMemcpy2DAsync(en_walker, (size_t)nout * sizeof(double), d_enw, (size_t)nen * sizeof(double), (size_t)nen * sizeof(double), (size_t)W,
                             hipMemcpyDeviceToHost, h->stream));
   }
   TRY(copy_out(h, en_mean, d_mean, (size_t)nen * sizeof(double)));
-  if (!cplx) {  // a real handle has no seventh row
+  if (nen < nout) {  // the complex entry on a real handle: there is no seventh row
     en_mean[6] = 0.0;
     if (en_walker)
       for (long w = 0; w < W; ++w) en_walker[7 * w + 6] = 0.0;
   }
   return 0;
+}
+
+extern "C" int pqa_sr_moments(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff, const double* weights,
+                              double threshold, const double* rot, const double* unif, uint64_t seed, double* en_mean, double* moments,
+                              double* en_walker) {
+  return sr_moments(h, {"pqa_sr_moments", false, false, 0, nullptr, 0, nullptr}, P, src, pos, nodal_cutoff, weights, threshold, rot, unif, seed,
+                    en_mean, moments, en_walker);
+}
+
+extern "C" int pqa_sr_moments_orb(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, double nodal_cutoff, const double* weights,
+                                  double threshold, const double* rot, const double* unif, uint64_t seed, int64_t walker_chunk,
+                                  double* en_mean, double* moments, double* en_walker, double* dp_walker) {
+  return sr_moments(h, {"pqa_sr_moments_orb", true, false, 0, nullptr, (long)walker_chunk, dp_walker}, P, src, pos, nodal_cutoff, weights,
+                    threshold, rot, unif, seed, en_mean, moments, en_walker);
+}
+
+extern "C" int pqa_sr_moments_c(pqa_handle_t* h, int P, const int32_t* src, const int32_t* pos, int ntail, const int32_t* tail,
+                                double nodal_cutoff, const double* weights, double threshold, const double* rot, const double* unif,
+                                uint64_t seed, int64_t walker_chunk, double* en_mean, double* moments, double* en_walker, double* dp_walker) {
+  return sr_moments(h, {"pqa_sr_moments_c", false, true, ntail, tail, (long)walker_chunk, dp_walker}, P, src, pos, nodal_cutoff, weights,
+                    threshold, rot, unif, seed, en_mean, moments, en_walker);
 }

@@ -3,15 +3,17 @@
 //
 // Both gather, per walker chunk, a compact row-major A = [derivative columns (P) | nx further columns] (Wc, P + nx) and a scale s (Wc)
 // and need M = A^T diag(s) A[:, :P]:
-//   sr_sources       the per-walker derivative arrays a column description names, left on the handle (det_coeff: k_pgrad_det; acoeff /
-//                    bcoeff: the basis sums the handle keeps, refreshed where a fused sweep left them stale; ccoeff: k_j3_pgrad);
+//   sr_check_columns the column description (src, pos) of an entry against the handle's parameters;
+//   sr_sources       the per-walker derivative arrays a column description names, left on the handle (det_coeff: pgrad_det_dev; acoeff /
+//                    bcoeff: the basis sums the handle keeps, refreshed where a fused sweep left them stale; ccoeff: j3_pgrad_dev);
 //   k_sr_syrk        M on v_mfma_f64_16x16x4_f64, walkers as the k dimension.  A block of four waves owns a 32 x 32 tile (one 16 x 16
 //                    tile per wave) and a slice of the walkers; 16 walkers of both column panels are staged in LDS per step, the
 //                    right-hand panel scaled by s as it is loaded.  The leading P x P block is symmetric: of its tiles only those on or
 //                    above the diagonal are computed (sym), or none at all (!sym: a caller that needs the nx further rows only);
 //   k_sr_reduce      the slices' partial tiles summed in slice order (the same bits on every call), the lower triangle mirrored from
 //                    the upper one (the P x P block is exactly symmetric), added to the running moments of the chunks before (pqa_sr:
-//                    as one term; pqa_mix: slice by slice, so that the chunking does not show in the result).
+//                    as one term; pqa_mix: slice by slice, so that the chunking does not show in the result);
+//   Carver           the scratch layout of a host function, stated once.
 #pragma once
 #include "pqa_estim.hpp"
 
@@ -98,6 +100,22 @@ inline long sr_slices(long Wc, int nbi, int nbj, size_t nmom) {
   return std::max<long>(1, std::min<long>(nslice, (long)(kChunkScratchBytes / (nmom * sizeof(double)))));
 }
 
+// Bump carver of a scratch buffer.  A host function states its layout once, as a function that takes its pieces from a Carver; run over
+// a null base it only adds up the bytes (size()), run over the buffer it hands out the pointers, so the two cannot disagree.  Every piece
+// starts on an 8-byte boundary.
+struct Carver {
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* b = nullptr) : base((char*)b) {}
+  template <class T>
+  T* take(size_t n) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += (n * sizeof(T) + 7) & ~(size_t)7;
+    return p;
+  }
+  size_t size() const { return off; }
+};
+
 }  // namespace
 
 // Entries of the four derivative sources of handle h (0 where it lacks the factor).
@@ -108,20 +126,33 @@ inline void sr_source_sizes(const pqa_handle* h, long (&size)[4]) {
   size[3] = h->has_j3 ? (long)h->natom * h->na3 * h->na3 * h->nb3 * 3 : 0;
 }
 
-// The derivative arrays of the sources need[] names, for the resident walkers of a real handle, on h's stream: S.base / S.stride.
-//   0  d log Psi / d det_coeff -> b_pgdet (W, ndet), after the sign / log of the determinant expansion -> b_sign, b_log
+// The plain columns of an entry fn: every src[i] within 0 .. max_src (2: the mixture entries, 3: the SR entries) and pos[i] within the
+// parameter of handle g it names -> need[src[i]].  A failure is reported on h.
+inline int sr_check_columns(pqa_handle* h, const pqa_handle* g, const std::string& fn, int P, const int32_t* src, const int32_t* pos, int max_src,
+                            bool (&need)[4]) {
+  long size[4];
+  sr_source_sizes(g, size);
+  for (int i = 0; i < P; ++i) {
+    if (src[i] < 0 || src[i] > max_src)
+      FAIL(fn + (max_src < 3 ? ": src must be 0 (det_coeff), 1 (acoeff) or 2 (bcoeff) (three-body and orbital coefficients: the protocol route)"
+                             : ": src must be 0 (det_coeff), 1 (acoeff), 2 (bcoeff) or 3 (ccoeff)"));
+    if (pos[i] < 0 || pos[i] >= size[src[i]])
+      FAIL(fn + (max_src < 3 ? ": pos outside the parameter src names" : ": pos outside the parameter src names (or the handle has no such factor)"));
+    need[src[i]] = true;
+  }
+  return 0;
+}
+
+// The derivative arrays of the sources need[] names, for the resident walkers of handle h, on h's stream: S.base / S.stride (doubles
+// per walker; S.base[0] of a complex handle is the interleaved (re, im) array of W x stride[0] pairs, as k_sr_gather_c reads it).
+//   0  pgrad_det_dev -> b_pgdet (W, ndet), after the sign / log of the determinant expansion -> b_sign, b_log
 //   1, 2  the Jastrow basis sums the handle keeps (refreshed when stale)
-//   3  k_j3_pgrad -> b_out
+//   3  j3_pgrad_dev -> b_out
 inline int sr_sources(pqa_handle* h, const bool (&need)[4], SrSources& S) {
-  const long W = h->W;
   long size[4];
   sr_source_sizes(h, size);
   if (need[0]) {
-    TRY(slater_value_dev(h));  // sign / log of the determinant expansion -> b_sign, b_log
-    TRY(ensure(h, h->b_pgdet, (size_t)W * h->ndet * sizeof(double)));
-    hipLaunchKernelGGL((k_pgrad_det<>), dim3((unsigned)((W * h->ndet + 255) / 256)), dim3(256), 0, h->stream, h->S, h->st,
-                       (const double*)h->b_sign.p, (const double*)h->b_log.p, W, (double*)h->b_pgdet.p);
-    TRY(check_launch(h, "k_pgrad_det"));
+    TRY(pgrad_det_dev(h));
     S.base[0] = (const double*)h->b_pgdet.p; S.stride[0] = size[0];
   }
   if (need[1] || need[2]) {
@@ -130,12 +161,7 @@ inline int sr_sources(pqa_handle* h, const bool (&need)[4], SrSources& S) {
     S.base[2] = h->js.bvalues; S.stride[2] = size[2];
   }
   if (need[3]) {
-    const size_t lds = ((size_t)h->N * h->natom * h->na3 + (size_t)h->N * (h->N - 1) / 2 * h->nb3) * sizeof(double);
-    if (lds > 150 * 1024) FAIL("three-body parameter gradient: the a/b value tables of one walker do not fit LDS");
-    TRY(ensure(h, h->b_out, (size_t)W * size[3] * sizeof(double)));
-    if (lds > 64 * 1024) TRY(raise_lds_limit(h, reinterpret_cast<const void*>(k_j3_pgrad<>)));
-    hipLaunchKernelGGL((k_j3_pgrad<>), dim3((unsigned)W), dim3(64), lds, h->stream, h->S, h->js, (double*)h->b_out.p);
-    TRY(check_launch(h, "k_j3_pgrad"));
+    TRY(j3_pgrad_dev(h));
     S.base[3] = (const double*)h->b_out.p; S.stride[3] = size[3];
   }
   return 0;

@@ -317,24 +317,43 @@ class DeviceWF:
                   _ffi.ptr(rot), _ffi.ptr(unif), int(seed), int(walker_chunk), _ffi.ptr(logpsi), _ffi.ptr(en))
         return logpsi, en
 
-    def sr_moments(self, src, pos, nodal_cutoff, weights=None, threshold=10.0, rot=None, unif=None, seed=0, per_walker=False):
-        """``pqa_sr_moments``: the moments of ``StochasticReconfiguration.avg`` from the resident state.  Column i of the serialised
-        derivative matrix is flat entry ``pos[i]`` of the parameter ``src[i]`` (0 det_coeff, 1 acoeff, 2 bcoeff, 3 ccoeff);
-        ``weights`` (W) are normalised by their sum (None: 1 / W); ``threshold`` / ``rot`` / ``unif`` / ``seed`` as in ``energy``.
-        Returns (en_mean (6), moments (P + 2, P): rows dpidpj, dpH, dppsi[, en_walker (W, 6) with ``per_walker``])."""
+    def _sr_call(self, entry, src, pos, nodal_cutoff, weights, threshold, rot, unif, seed, per_walker, tail=None, chunk=None, dp_walker=False,
+                 scope=None):
+        """The ``pqa_sr_moments*`` call ``entry``: prepares the columns (``tail`` not None: the complex entry, whose outputs are complex
+        and seven energy slots wide), weights and draws, makes the call (``chunk`` None: the entry takes no ``walker_chunk`` /
+        ``dp_walker``) and returns (en_mean, moments, en_walker or None, dp or None) as the entry wrote them.  ``scope(src)`` runs
+        between the column checks and the rest."""
+        cx = tail is not None
         src, pos = np.ascontiguousarray(src, dtype=np.int32), np.ascontiguousarray(pos, dtype=np.int32)
-        P = len(src)
+        tail = np.ascontiguousarray(tail if cx else (), dtype=np.int32)
+        P, ntail = len(src), len(tail)
+        if cx and (src.shape != (P,) or pos.shape != (P,) or tail.shape != (ntail,)):
+            raise ValueError(f"src, pos (equally long) and tail must be one-dimensional, got {src.shape}, {pos.shape}, {tail.shape}")
         if src.shape != (P,) or pos.shape != (P,):
             raise ValueError(f"src and pos must be one-dimensional and equally long, got {src.shape}, {pos.shape}")
+        if scope is not None:
+            scope(src)
         w = None if weights is None else _ffi.f64(weights)
         if w is not None and w.shape != (self.W,):
             raise ValueError(f"weights ({self.W},) expected, got {w.shape}")
         rot = None if rot is None else _ffi.f64(rot)
         unif = None if unif is None else _ffi.f64(unif)
-        en_mean, moments = np.empty(6), np.empty((P + 2, P))
-        en_walker = np.empty((self.W, 6)) if per_walker else None
-        self.call("pqa_sr_moments", int(P), _ffi.ptr(src), _ffi.ptr(pos), float(nodal_cutoff), _ffi.ptr(w), float(threshold), _ffi.ptr(rot),
-                  _ffi.ptr(unif), int(seed), _ffi.ptr(en_mean), _ffi.ptr(moments), _ffi.ptr(en_walker))
+        Pt, nen, dtype = P + ntail, 7 if cx else 6, complex if cx else float
+        en_mean, moments = np.empty(nen), np.empty((Pt + 2, Pt), dtype=dtype)
+        en_walker = np.empty((self.W, nen)) if per_walker else None
+        dp = np.empty((self.W, Pt), dtype=dtype) if dp_walker else None
+        self.call(entry, int(P), _ffi.ptr(src), _ffi.ptr(pos), *((int(ntail), _ffi.ptr(tail) if ntail else None) if cx else ()),
+                  float(nodal_cutoff), _ffi.ptr(w), float(threshold), _ffi.ptr(rot), _ffi.ptr(unif), int(seed),
+                  *(() if chunk is None else (int(chunk),)), _ffi.ptr(en_mean), _ffi.ptr(moments), _ffi.ptr(en_walker),
+                  *(() if chunk is None else (_ffi.ptr(dp),)))
+        return en_mean, moments, en_walker, dp
+
+    def sr_moments(self, src, pos, nodal_cutoff, weights=None, threshold=10.0, rot=None, unif=None, seed=0, per_walker=False):
+        """``pqa_sr_moments``: the moments of ``StochasticReconfiguration.avg`` from the resident state.  Column i of the serialised
+        derivative matrix is flat entry ``pos[i]`` of the parameter ``src[i]`` (0 det_coeff, 1 acoeff, 2 bcoeff, 3 ccoeff);
+        ``weights`` (W) are normalised by their sum (None: 1 / W); ``threshold`` / ``rot`` / ``unif`` / ``seed`` as in ``energy``.
+        Returns (en_mean (6), moments (P + 2, P): rows dpidpj, dpH, dppsi[, en_walker (W, 6) with ``per_walker``])."""
+        en_mean, moments, en_walker, _ = self._sr_call("pqa_sr_moments", src, pos, nodal_cutoff, weights, threshold, rot, unif, seed, per_walker)
         return (en_mean, moments, en_walker) if per_walker else (en_mean, moments)
 
     def sr_moments_orb(self, src, pos, nodal_cutoff, weights=None, threshold=10.0, rot=None, unif=None, seed=0, per_walker=False,
@@ -345,25 +364,13 @@ class DeviceWF:
         Returns (en_mean, moments[, en_walker with ``per_walker``][, dp with ``dp_walker``]).  Orbital sources on a periodic, complex or
         twisted handle, or with more than 64 electrons / orbitals of a spin, raise ``NotImplementedError`` (the protocol route takes
         those)."""
-        src, pos = np.ascontiguousarray(src, dtype=np.int32), np.ascontiguousarray(pos, dtype=np.int32)
-        P = len(src)
-        if src.shape != (P,) or pos.shape != (P,):
-            raise ValueError(f"src and pos must be one-dimensional and equally long, got {src.shape}, {pos.shape}")
-        if np.any(src >= 4):
-            why = orbital_sr_scope(self)
+        def scope(src):
+            why = orbital_sr_scope(self) if np.any(src >= 4) else None
             if why:
                 raise NotImplementedError(f"sr_moments_orb: {why} (use the protocol route)")
-        w = None if weights is None else _ffi.f64(weights)
-        if w is not None and w.shape != (self.W,):
-            raise ValueError(f"weights ({self.W},) expected, got {w.shape}")
-        rot = None if rot is None else _ffi.f64(rot)
-        unif = None if unif is None else _ffi.f64(unif)
-        en_mean, moments = np.empty(6), np.empty((P + 2, P))
-        en_walker = np.empty((self.W, 6)) if per_walker else None
-        dp = np.empty((self.W, P)) if dp_walker else None
-        self.call("pqa_sr_moments_orb", int(P), _ffi.ptr(src), _ffi.ptr(pos), float(nodal_cutoff), _ffi.ptr(w), float(threshold),
-                  _ffi.ptr(rot), _ffi.ptr(unif), int(seed), int(walker_chunk), _ffi.ptr(en_mean), _ffi.ptr(moments), _ffi.ptr(en_walker),
-                  _ffi.ptr(dp))
+
+        en_mean, moments, en_walker, dp = self._sr_call("pqa_sr_moments_orb", src, pos, nodal_cutoff, weights, threshold, rot, unif, seed,
+                                                        per_walker, chunk=walker_chunk, dp_walker=dp_walker, scope=scope)
         return (en_mean, moments) + ((en_walker,) if per_walker else ()) + ((dp,) if dp_walker else ())
 
     def sr_moments_c(self, src, pos, tail, nodal_cutoff, weights=None, threshold=10.0, rot=None, unif=None, seed=0, per_walker=False,
@@ -372,23 +379,8 @@ class DeviceWF:
         ``src`` / ``pos`` (P) as there (sources 0 - 3); ``tail``: primary indices whose ``1j *`` twins follow the P primary columns
         (``LinearTransform.complex_inds``), Pt = P + len(tail).  Returns (en_mean (6) complex, moments (Pt + 2, Pt) complex: rows
         dpidpj, dpH, dppsi[, en_walker (W, 6) complex with ``per_walker``][, dp (W, Pt) complex with ``dp_walker``])."""
-        src, pos = np.ascontiguousarray(src, dtype=np.int32), np.ascontiguousarray(pos, dtype=np.int32)
-        tail = np.ascontiguousarray(tail, dtype=np.int32)
-        P, ntail = len(src), len(tail)
-        if src.shape != (P,) or pos.shape != (P,) or tail.shape != (ntail,):
-            raise ValueError(f"src, pos (equally long) and tail must be one-dimensional, got {src.shape}, {pos.shape}, {tail.shape}")
-        w = None if weights is None else _ffi.f64(weights)
-        if w is not None and w.shape != (self.W,):
-            raise ValueError(f"weights ({self.W},) expected, got {w.shape}")
-        rot = None if rot is None else _ffi.f64(rot)
-        unif = None if unif is None else _ffi.f64(unif)
-        Pt = P + ntail
-        en_mean, moments = np.empty(7), np.empty((Pt + 2, Pt), dtype=complex)
-        en_walker = np.empty((self.W, 7)) if per_walker else None
-        dp = np.empty((self.W, Pt), dtype=complex) if dp_walker else None
-        self.call("pqa_sr_moments_c", int(P), _ffi.ptr(src), _ffi.ptr(pos), int(ntail), _ffi.ptr(tail) if ntail else None, float(nodal_cutoff),
-                  _ffi.ptr(w), float(threshold), _ffi.ptr(rot), _ffi.ptr(unif), int(seed), int(walker_chunk), _ffi.ptr(en_mean),
-                  _ffi.ptr(moments), _ffi.ptr(en_walker), _ffi.ptr(dp))
+        en_mean, moments, en_walker, dp = self._sr_call("pqa_sr_moments_c", src, pos, nodal_cutoff, weights, threshold, rot, unif, seed,
+                                                        per_walker, tail=tail, chunk=walker_chunk, dp_walker=dp_walker)
         out = (self._complex_energy(en_mean, 0), moments)
         return out + ((self._complex_energy(en_walker, 1),) if per_walker else ()) + ((dp,) if dp_walker else ())
 

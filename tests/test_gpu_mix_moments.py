@@ -416,3 +416,30 @@ def test_scope():
         w.recompute(PeriodicConfigs(xp, sup.lattice_vectors()))
     with pytest.raises(pa._ffi.PqaError, match="pqa_mix_moments"):
         sample_many.mix_moments(pdevs, [([], []), ([], [])], seeds=[1, 2])
+
+
+@pytest.fixture(scope="module")
+def two_states_16():
+    """K = 2 states of water at 16 walkers: (devs, entry -> call with one column description (src, pos))."""
+    wfs, x = _states(systems.water(), 2, 16, 1, 79)
+    _, devs = _recompute(wfs, x)
+    return devs, {
+        "pqa_sr_moments": lambda s, p: devs[0].sr_moments(s, p, 1e-3),
+        "pqa_sr_moments_orb": lambda s, p: devs[0].sr_moments_orb(s, p, 1e-3),
+        "pqa_sr_moments_c": lambda s, p: devs[0].sr_moments_c(s, p, [], 1e-3),
+        "pqa_mix_moments": lambda s, p: sample_many.mix_moments(devs, [(s, p), ([], [])], seeds=[1, 2]),
+        "pqa_mix_wtdp": lambda s, p: sample_many.mix_wtdp(devs, s, p),
+    }
+
+
+@pytest.mark.parametrize("bad", ["src", "pos"])
+@pytest.mark.parametrize("entry", ["pqa_sr_moments", "pqa_sr_moments_orb", "pqa_sr_moments_c", "pqa_mix_moments", "pqa_mix_wtdp"])
+def test_column_check_names_the_entry(two_states_16, entry, bad):
+    """The one column check of the family: a source no entry has, and a position one past the (nb, 3) bcoeff entries, behind a good
+    column; the message starts with the entry that was called."""
+    devs, call = two_states_16
+    nb3 = devs[0].nb * 3
+    call[entry]([2, 2], [0, nb3 - 1])  # (the good columns pass)
+    src, pos, why = ([2, 7], [0, 0], "src must be") if bad == "src" else ([2, 2], [0, nb3], "pos outside")
+    with pytest.raises(pa._ffi.PqaError, match=f"{entry}: {why}"):
+        call[entry](src, pos)

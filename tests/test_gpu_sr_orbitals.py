@@ -172,6 +172,27 @@ def test_walker_chunks_and_determinism():
     assert all(np.array_equal(x, y) for x, y in zip(old, new))
 
 
+def test_three_entries_one_driver():
+    """The 200-walker (3 x 64 + 8), 4-determinant water case of test_gpu_sr_moments.py, P no multiple of 16, with and without weights:
+    pqa_sr_moments_orb with sources 0 - 2 only gives pqa_sr_moments' bits, and pqa_sr_moments_c with an empty tail gives them as real
+    parts, with imaginary parts that are exactly zero."""
+    mol = systems.water()
+    mf = systems.random_mf(mol, nvirt=6)
+    wf = helpers.gpu_wf(mol, mf, determinants=systems.random_determinants(mol, mf, 4))
+    wf.recompute(_walkers(mol, 200, 1))
+    dev = wf.fused_device()
+    src, pos = sr_columns_orb(gradient_generator(mol, wf, pwf.default_to_opt(wf)).transform)
+    assert len(src) % 16 != 0 and set(src.tolist()) == {0, 1, 2}
+    for wts in (None, 0.5 + np.random.default_rng(2).random(200)):
+        mean, mom = dev.sr_moments(src, pos, 1e-3, weights=wts, seed=5)
+        orb = dev.sr_moments_orb(src, pos, 1e-3, weights=wts, seed=5)
+        meanc, momc = dev.sr_moments_c(src, pos, [], 1e-3, weights=wts, seed=5)
+        assert np.array_equal(orb[0], mean) and np.array_equal(orb[1], mom)
+        assert momc.shape == mom.shape and meanc.shape == mean.shape
+        assert np.array_equal(momc.real, mom) and np.array_equal(meanc.real, mean)
+        assert np.all(momc.imag == 0) and np.all(meanc.imag == 0)
+
+
 def test_state_untouched():
     mol = systems.water()
     wf = helpers.gpu_wf(mol, systems.random_mf(mol))
