@@ -487,12 +487,27 @@ int pqa_obdm_sweeps(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_t*
 int pqa_obdm_sweeps_w(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
                       uint64_t seed, int64_t walker_chunk, const double* weights, int32_t* assign_out, double* value_mean,
                       double* norm_mean);
+/* pqa_obdm_sweeps for complex and twisted wave-function handles and complex evaluators: the same steps, streams, chunks and fixed
+   summation orders, with ratio (nsweeps,W,ne) and value_mean (norb,norb) interleaved complex and norm_mean (norb) real;
+     value[j][k] += (phi_j(r')/F) conj(sum_e R_e phi_k(r_e)),   R_e = (sum_D w_D v_D(r')[e] / sum_D w_D) exp(A_e(r')),
+   w_D the complex determinant weights relative to the largest |determinant|.  mean = 0: ev's per-walker accumulators end as nsweeps
+   pqa_obdm_accumulate calls with complex ratios leave them.  mean != 0: value_mean = B^T T / (W nsweeps) from planar panels,
+   Re = Br^T Tr - Bi^T Ti, Im = Br^T Ti + Bi^T Tr on the fp64 matrix cores.  weights != NULL (mean mode only): the weighted mean of
+   pqa_obdm_sweeps_w; unit weights give the bits of the unweighted call.  Scope: wf a Slater handle with a state (one or more
+   determinants; real, complex or twisted; with or without the two-body Jastrow; no three-body factor), ev a second handle on the
+   same device, real or complex; a twisted ev needs a twisted wf (an untwisted periodic handle holds folded walkers, so the wrap
+   phase of phi_k(r_e) would be lost).  es, nsweeps, first, assign and weights follow pqa_obdm_sweeps / pqa_obdm_sweeps_w.  Everything
+   else is refused (<0) and goes through the protocol route.  wf's state is not modified. */
+int pqa_obdm_sweeps_c(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
+                      uint64_t seed, int mean, int first, int64_t walker_chunk, const double* weights, double* ratio,
+                      int32_t* assign_out, double* value_mean, double* norm_mean);
 /* pqa_dm_points for the listed electrons es (ne) of wf's resident walkers: their coordinates are gathered on the device and ev's
    orbitals of the spin of the slot's walk (pqa_dm_walk comes first) are evaluated there into `slot`, rows (W, ne, norb) — the first
    stage of pqa_obdm_sweeps, with its scope checks.  wf's state is not modified. */
 int pqa_dm_points_resident(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_t* es, int ne);
 /* Device bytes ev holds for pqa_obdm_sweeps: scratch = the mean mode's panels, partial tiles and sums plus a walker chunk's ratios;
-   per_walker = the per-walker accumulators (value, norms), which the mean mode never allocates. */
+   per_walker = the per-walker accumulators (value, norms), which the mean mode never allocates.  These are the buffers' capacities,
+   so after a pqa_obdm_sweeps_c call they are the complex sizes (five panels, 2 norb^2 + norb partials, interleaved ratios and values). */
 int pqa_obdm_bytes(pqa_handle_t* ev, int64_t* scratch, int64_t* per_walker);
 /* Read an accumulator times `scale`: which = 0 value (ncol = entries per configuration, doubled when complex), 1 norm /
    norm_a, 2 norm_b (ncol = orbitals).  mean = 0: (nconf,ncol); mean != 0: (ncol,) averaged over the configurations on

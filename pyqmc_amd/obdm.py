@@ -25,6 +25,13 @@ Two routes give the ratios (``route``, as in ``TBDMAccumulator``):
   per-configuration matrix.  With ``rng="numpy"`` the draws are those of the protocol route; ``rng="device"`` draws the walk and the
   assignments from the device's Philox streams, keyed by one ``numpy.random`` integer per evaluation.
 
+With ``complex_device=True`` (opt-in) complex and twisted handles and complex evaluators take the fused route as well
+(``pqa_obdm_sweeps_c``): the complex ratios come in closed form from the resident complex inverse, the per-configuration mode hands
+them to the same contraction kernel the protocol route uses, and ``avg`` / ``avg_resident`` form ``B^T T / W`` from planar real and
+imaginary panels (Re = Br^T Tr - Bi^T Ti, Im = Br^T Ti + Bi^T Tr).  ``value`` is complex and ``norm`` real, as on the protocol route.
+A twisted evaluator needs a twisted wave-function handle (an untwisted periodic handle holds folded walkers, which have lost the wrap
+phase of the orbitals at the electrons): that pair stays on the protocol route.
+
 ``avg_resident(wf, weights=w)`` is the weighted walker mean sum_w w_w res_w / sum_w w_w of DMC's mixed estimator
 (``pqa_obdm_sweeps_w``: the same product with the weight applied to B as it is loaded; unit weights give the bits of ``avg``).
 
@@ -37,7 +44,7 @@ from . import _ffi
 from . import pbc as _pbc
 from .configs import OpenConfigs, PeriodicConfigs
 from .systems import initial_guess
-from .wf import DeviceWF, readonly_device
+from .wf import DeviceWF, readonly_device, readonly_device_c
 
 ROUTES = (None, "fused", "protocol")
 
@@ -261,6 +268,36 @@ def device_obdm_sweeps_w(dev, ev, electrons, nsweeps, weights, assign=None, seed
     return out
 
 
+def device_obdm_sweeps_c(dev, ev, electrons, nsweeps, assign=None, seed=0, mean=False, first=True, walker_chunk=0, with_ratios=False,
+                         weights=None):
+    """``pqa_obdm_sweeps_c``: ``device_obdm_sweeps`` for complex and twisted handles ``dev`` and complex evaluators ``ev`` (real ones are
+    taken too).  The same dict, with complex ``ratio`` (nsweeps, W, nelec) and ``value`` (norb, norb) and a real ``norm``; ``weights``
+    (W,): the weighted mean of ``device_obdm_sweeps_w`` (``mean`` only).  Without ``mean`` the evaluator's per-configuration accumulators
+    hold complex sums (``ev.fetch(..., cplx=True)``)."""
+    es = np.ascontiguousarray(np.asarray(electrons).ravel(), dtype=np.int32)
+    W, norb = dev.W, ev.norb
+    if weights is not None:
+        if not mean:
+            raise ValueError("walker weights need the mean mode")
+        weights = _ffi.walker_weights(weights, W)
+    out = {}
+    if assign is not None:
+        assign = np.ascontiguousarray(assign, dtype=np.int32)
+        if assign.shape != (nsweeps, W):
+            raise ValueError(f"assignments ({nsweeps}, {W}) expected, got {assign.shape}")
+        out["assign"] = assign
+    else:
+        out["assign"] = np.empty((nsweeps, W), dtype=np.int32)
+    if with_ratios:
+        out["ratio"] = np.empty((nsweeps, W, len(es)), dtype=complex)
+    if mean:
+        out["value"], out["norm"] = np.empty((norb, norb), dtype=complex), np.empty(norb)
+    dev.call("pqa_obdm_sweeps_c", ev.dev._h, 0, _ffi.ptr(es), len(es), int(nsweeps), _ffi.ptr(assign), int(seed), int(mean), int(first),
+             int(walker_chunk), _ffi.ptr(weights), _ffi.ptr(out.get("ratio")), None if assign is not None else _ffi.ptr(out["assign"]),
+             _ffi.ptr(out.get("value")), _ffi.ptr(out.get("norm")))
+    return out
+
+
 class OBDMAccumulator:
     """Keys ``value`` (norb,norb), ``norm`` (norb,) per configuration (obdm.py:26-213).
 
@@ -272,17 +309,23 @@ class OBDMAccumulator:
     otherwise; "fused" raises outside the scope; "protocol" always goes through ``wf.testvalue_many``.  ``rng``: "numpy" draws the
     walk and the assignments from ``numpy.random`` in the reference's order on both routes; "device" (fused route only) draws one
     ``numpy.random`` integer per evaluation and leaves the rest to the device's Philox streams.  ``walker_chunk``: walkers per
-    scratch chunk of the fused route (0: the library's bound).  ``last_route`` names the route of the last evaluation."""
+    scratch chunk of the fused route (0: the library's bound).  ``last_route`` names the route of the last evaluation.
+    ``complex_device``: with True complex and twisted handles and complex evaluators are in the fused scope too
+    (``pqa_obdm_sweeps_c``), except a twisted evaluator with an untwisted handle; with False (the default) they take the protocol
+    route and ``route="fused"`` raises for them."""
 
     def __init__(self, mol, orb_coeff, nsweeps=5, tstep=0.50, warmup=10000, naux=None, spin=None, electrons=None, kpts=None,
-                 eval_gto_precision=None, device=0, route=None, rng="numpy", walker_chunk=0):
+                 eval_gto_precision=None, device=0, route=None, rng="numpy", walker_chunk=0, complex_device=False):
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}")
         if rng not in ("numpy", "device"):
             raise ValueError("rng must be 'numpy' or 'device'")
         if rng == "device" and route == "protocol":
             raise ValueError("rng='device' draws inside pqa_obdm_sweeps: it needs the fused route")
+        if not isinstance(complex_device, (bool, np.bool_)):
+            raise ValueError("complex_device must be True or False")
         self._route, self._rng, self._walker_chunk, self.last_route = route, rng, int(walker_chunk), None
+        self.complex_device = bool(complex_device)
         self.last_assign = None  # (nsweeps, nconf) assignments of the last fused evaluation
         nup, ntot = mol.nelec[0], int(np.sum(mol.nelec))
         if spin is not None:
@@ -301,13 +344,26 @@ class OBDMAccumulator:
     def _extra_config(self):
         return None if self._walkers is None else self._walkers.configs
 
+    def _device(self, wf):
+        """The handle the fused route reads ``wf`` from, or None."""
+        return readonly_device_c(wf) if self.complex_device else readonly_device(wf)
+
+    def _complex_entry(self, dev):
+        """Whether the evaluation of the handle ``dev`` goes through ``pqa_obdm_sweeps_c``."""
+        return self.complex_device and bool(dev.cplx or dev.twisted or self.orbitals.dev.cplx or self.orbitals.dev.twisted)
+
     def _out_of_scope(self, wf, nconf=None):
         """Why the fused route cannot take ``wf`` (and ``nconf`` configurations), or None when it can."""
-        dev, ev = readonly_device(wf), self.orbitals.dev
+        dev, ev = self._device(wf), self.orbitals.dev
         es = np.asarray(self._electrons).ravel()
         if dev is None:
+            if self.complex_device:
+                return "the wave function is not a Slater (x two-body Jastrow) product on one device handle"
             return "the wave function is not a real Slater (x two-body Jastrow) product on one device handle"
-        if ev.cplx or ev.twisted:
+        if self.complex_device:
+            if ev.twisted and not dev.twisted:
+                return "the orbital evaluator is twisted and the wave function's handle is not (its folded walkers have lost the wrap phase)"
+        elif ev.cplx or ev.twisted:
             return "the orbital evaluator is complex"
         if ev.device != dev.device:
             return "the wave function and the evaluator are on different devices"
@@ -370,7 +426,10 @@ class OBDMAccumulator:
         if seed is None:
             pick = np.random.randint(0, naux, size=(nsw, nconf)).astype(np.int32)  # drawn before the walk (obdm.py:150)
         _, kept = self._walkers.advance(0, nsw, self._tstep, keep=nsw, seed=seed)
-        if weights is not None:
+        if self._complex_entry(dev):
+            out = device_obdm_sweeps_c(dev, ev, self._electrons, nsw, assign=pick, seed=0 if seed is None else seed, mean=mean,
+                                       walker_chunk=self._walker_chunk, with_ratios=with_ratios, weights=weights)
+        elif weights is not None:
             out = device_obdm_sweeps_w(dev, ev, self._electrons, nsw, weights, assign=pick, seed=0 if seed is None else seed,
                                        walker_chunk=self._walker_chunk)
         else:
@@ -385,10 +444,11 @@ class OBDMAccumulator:
         nconf, scale = configs.configs.shape[0], 1.0 / self._nsweeps
         self.last_route = self.resolve_route(wf, nconf)
         if self.last_route == "fused":
-            (vm, nm), _ = self._sample_fused(readonly_device(wf), mean)
+            dev = self._device(wf)
+            (vm, nm), _ = self._sample_fused(dev, mean)
             if mean:
                 return {"value": vm, "norm": nm}
-            cplx = False
+            cplx = self._complex_entry(dev)
         else:
             cplx = self._sample(configs, wf)
         return {"value": self.orbitals.fetch(0, nconf, (self.norb, self.norb), scale, mean, cplx),
@@ -413,7 +473,7 @@ class OBDMAccumulator:
         if self.resolve_route(wf) != "fused":
             raise ValueError("OBDMAccumulator.avg_resident needs the fused route")
         self.last_route = "fused"
-        (vm, nm), _ = self._sample_fused(readonly_device(wf), True, weights=weights)
+        (vm, nm), _ = self._sample_fused(self._device(wf), True, weights=weights)
         return {"value": vm, "norm": nm}
 
     def evaluate_orbitals(self, configs):

@@ -1212,6 +1212,20 @@ def readonly_device(wf):
     return dev
 
 
+def readonly_device_c(wf):
+    """``readonly_device`` with complex and twisted handles admitted (``pqa_obdm_sweeps_c``): the same rules otherwise."""
+    factors = wf.wf_factors if isinstance(wf, MultiplyWF) else [wf]
+    kinds = [type(f) for f in factors]
+    if any(k not in (Slater, JastrowSpin) for k in kinds) or len(set(kinds)) != len(kinds) or Slater not in kinds:
+        return None
+    dev = wf.fused_device() if isinstance(wf, MultiplyWF) else getattr(wf, "_dev", None)
+    if dev is None or not hasattr(dev, "vmc_sweeps"):
+        return None
+    if not dev.has_slater or dev.has_j3 or dev.has_jastrow != (JastrowSpin in kinds):
+        return None
+    return dev
+
+
 LINEAR_JASTROW_KEYS = {"wf2acoeff", "wf2bcoeff"}  # the parameters the linear-Jastrow entry points vary
 
 

@@ -1,8 +1,8 @@
 """One-body density matrix timing, fused route against protocol route: one JSON line per configuration, appended to
 profiles/obdm_bench.jsonl with --record.
 
-    python tools/obdm_bench.py [--configs C2,M4096,M,MD50,K222] [--reps 7] [--routes fused,protocol] [--protocol-budget-s 90]
-                               [--driver 16384,65536] [--record]
+    python tools/obdm_bench.py [--configs C2,M4096,M,MD50,K222,C3,CX311] [--reps 7] [--routes fused,protocol] [--protocol-budget-s 90]
+                               [--driver 16384,65536] [--driver-complex 8192,16384] [--record]
 
 Per configuration and route: wall-clock milliseconds per ``OBDMAccumulator.avg`` and per ``OBDMAccumulator.__call__`` (nsweeps = 5,
 spin = 0, 32 orbitals) — the auxiliary walk, the orbitals at the electrons, the five sweeps and the fetch of the result, which ends
@@ -13,6 +13,9 @@ maximum and spread = (max - min) / median; the routes alternate call by call.  `
 otherwise the record says that it was left out for time.  ``--driver``: one 10-sweep ``vmc_worker`` block with {energy, rdm1_up,
 rdm1_down} of (H2O)8 on the resident and on the host driver path at those walker counts.  The library is used as built (no build on
 import); another checkout of the package (the parent commit's accumulator) is timed with OBDM_BENCH_TREE and --routes parent.
+C3 (the twisted 8-atom diamond cell of tools/config_bench.py, 16 + 16 electrons) and CX311 (the complex 3 x 1 x 1 cell) are complex
+handles with the evaluator's orbitals from the k-point mean field: their fused route is ``complex_device=True`` (``pqa_obdm_sweeps_c``),
+and ``--driver-complex`` runs the {energy, rdm1_up} block on C3.
 The kernel split comes from a ``rocprofv3 --kernel-trace --stats`` run of this tool with --routes fused --reps 3.
 """
 
@@ -61,6 +64,19 @@ def build(name):
         kpts = np.asarray(kmf.kpts)
         per_k = NORB // len(kpts)
         return sup, wf, 4096, dict(orb_coeff=[np.asarray(kmf.mo_coeff[0][k])[:, :per_k] for k in range(len(kpts))], kpts=kpts)
+    if name in ("C3", "CX311"):  # complex handles: eight orbitals of every k-point of the mean field (32 / 24 orbitals)
+        from pyqmc_amd import pbc
+
+        if name == "C3":
+            sup = pbc.get_supercell(systems.diamond_primitive(), np.array([[-1.0, 1, 1], [1, -1, 1], [1, 1, -1]]))
+            kmf = pbc.random_kmf(sup, complex_coeff=True, twist=(0.25, 0.1, -0.3), nvirt=4)
+        else:
+            sup = pbc.get_supercell(systems.diamond_primitive(), np.diag([3.0, 1.0, 1.0]))
+            kmf = pbc.random_kmf(sup, complex_coeff=True, nvirt=4)
+        sup, wf = helpers.gpu_pbc_wf(name, case=(sup, kmf))
+        kpts = np.asarray(kmf.kpts)
+        orb = [np.asarray(kmf.mo_coeff[0][k])[:, :8] for k in range(len(kpts))]
+        return sup, wf, 4096, dict(orb_coeff=orb, kpts=kpts, complex_device=True)
     raise KeyError(name)
 
 
@@ -90,6 +106,8 @@ def accumulator(pa, mol, kw, route):
     extra = {"route": "protocol"} if route == "protocol" else {} if route == "parent" else {"route": "fused"}
     if route == "fused_device":
         extra["rng"] = "device"
+    if route in ("protocol", "parent"):  # (the parent's accumulator does not know the keyword; the protocol route does not need it)
+        kw = {k: v for k, v in kw.items() if k != "complex_device"}
     return pa.OBDMAccumulator(mol, spin=0, nsweeps=NSWEEPS, warmup=20, **kw, **extra)
 
 
@@ -135,7 +153,10 @@ def run(name, reps, routes, budget_s, small_protocol_ms):
 
         configs = PeriodicConfigs(configs.configs, mol.lattice_vectors())
     wf.recompute(configs)
-    rec = {"config": name, "walkers": W, "nelec": list(dev.nelec), "ndet": dev.ndet, "nsweeps": NSWEEPS, "norb": NORB, "spin": 0}
+    cplx = bool(kw.get("complex_device"))
+    norb = sum(np.asarray(c).shape[1] for c in kw["orb_coeff"]) if "kpts" in kw else NORB
+    rec = {"config": name, "walkers": W, "nelec": list(dev.nelec), "ndet": dev.ndet, "nsweeps": NSWEEPS, "norb": norb, "spin": 0,
+           "complex": cplx, "twisted": bool(dev.twisted)}
     slow = [r for r in routes if r in ("protocol", "parent")]
     if W > 4096 and small_protocol_ms is not None and small_protocol_ms * (W / 4096) * 2 * (min(reps, 2) + 3) * 1e-3 > budget_s:
         for r in slow:
@@ -149,39 +170,46 @@ def run(name, reps, routes, budget_s, small_protocol_ms):
     for method in ("avg", "call"):
         for r, v in time_routes(pa, mol, wf, configs, kw, routes, reps, method).items():
             rec.setdefault(r, {})[method] = v
-    if any(r.startswith("fused") for r in routes):
+    if any(r.startswith("fused") for r in routes) and not cplx:  # (the model is that of the real kernels)
         rec["model_per_sweep"] = shapes_model(dev, W, dev.nelec[0], NORB)
     if "fused" in rec and "avg" in rec.get("protocol", {}):
         rec["speedup_avg"] = rec["protocol"]["avg"]["ms"] / rec["fused"]["avg"]["ms"]
         rec["speedup_call"] = rec["protocol"]["call"]["ms"] / rec["fused"]["call"]["ms"]
+        for m in ("avg", "call"):  # whether the two routes' [min, max] intervals are disjoint
+            f, p = rec["fused"][m], rec["protocol"][m]
+            rec["beyond_spread_" + m] = bool(f["max_ms"] < p["min_ms"] or p["max_ms"] < f["min_ms"])
     return rec
 
 
-def run_driver(W, reps):
+def run_driver(W, reps, cplx=False):
     """One 10-sweep vmc_worker block of (H2O)8 with {energy, rdm1_up, rdm1_down}: resident path (fused accumulators) against host
-    path (protocol accumulators), alternating; the first block of each (which holds the walk's warm-up) is timed on its own."""
+    path (protocol accumulators), alternating; the first block of each (which holds the walk's warm-up) is timed on its own.
+    ``cplx``: the block of the twisted cell C3 with {energy, rdm1_up}, the resident path through ``complex_device=True``."""
     import pyqmc_amd as pa
 
-    mol, wf, _, kw = build("M4096")
+    mol, wf, _, kw = build("C3" if cplx else "M4096")
     start = pa.initial_guess(mol, W, rng=np.random.default_rng(1))
-    rec = {"config": "driver", "walkers": W, "nsteps": 10, "nsweeps": NSWEEPS, "norb": NORB}
+    rec = {"config": "driver_C3" if cplx else "driver", "walkers": W, "nsteps": 10, "nsweeps": NSWEEPS,
+           "norb": sum(np.asarray(c).shape[1] for c in kw["orb_coeff"]) if cplx else NORB}
     accs = {}
     for path, route in (("resident", "fused"), ("resident_device_rng", "fused_device"), ("host", "protocol")):
-        accs[path] = {"energy": pa.EnergyAccumulator(mol), "rdm1_up": accumulator(pa, mol, kw, route),
-                      "rdm1_down": pa.OBDMAccumulator(mol, spin=1, nsweeps=NSWEEPS, warmup=20, **kw,
-                                                      **({"route": "protocol"} if route == "protocol" else
-                                                         {"route": "fused", "rng": "device"} if route == "fused_device" else {"route": "fused"}))}
+        accs[path] = {"energy": pa.EnergyAccumulator(mol), "rdm1_up": accumulator(pa, mol, kw, route)}
+        if not cplx:
+            accs[path]["rdm1_down"] = pa.OBDMAccumulator(mol, spin=1, nsweeps=NSWEEPS, warmup=20, **kw,
+                                                         **({"route": "protocol"} if route == "protocol" else
+                                                            {"route": "fused", "rng": "device"} if route == "fused_device" else {"route": "fused"}))
     ms = {p: [] for p in accs}
     np.random.seed(3)
     for rep in range(reps + 1):
         for path, a in accs.items():
-            cfg = pa.OpenConfigs(start.configs.copy())
+            cfg = type(start)(start.configs.copy(), mol.lattice_vectors()) if cplx else pa.OpenConfigs(start.configs.copy())
             t0 = time.perf_counter()
             pa.vmc_worker(wf, cfg, 0.3, 10, a, seed=5)
             ms[path].append((time.perf_counter() - t0) * 1e3)
     for path in accs:
         rec[path] = dict(_stats(ms[path][1:], reps), first_block_ms=ms[path][0])
     rec["speedup"] = rec["host"]["ms"] / rec["resident"]["ms"]
+    rec["beyond_spread"] = bool(rec["resident"]["max_ms"] < rec["host"]["min_ms"] or rec["host"]["max_ms"] < rec["resident"]["min_ms"])
     return rec
 
 
@@ -193,6 +221,7 @@ def main():
                     help="fused, fused_device, protocol, parent (a tree without the route keyword: OBDM_BENCH_TREE)")
     ap.add_argument("--protocol-budget-s", type=float, default=90.0)
     ap.add_argument("--driver", default="", help="walker counts of the vmc_worker block, e.g. 16384,65536")
+    ap.add_argument("--driver-complex", default="", help="walker counts of the twisted cell's vmc_worker block, e.g. 8192,16384")
     ap.add_argument("--record", action="store_true", help="append the lines to profiles/obdm_bench.jsonl")
     a = ap.parse_args()
 
@@ -211,6 +240,8 @@ def main():
         emit(rec)
     for W in [int(w) for w in a.driver.split(",") if w]:
         emit(run_driver(W, min(a.reps, 3)))
+    for W in [int(w) for w in a.driver_complex.split(",") if w]:
+        emit(run_driver(W, min(a.reps, 3), cplx=True))
 
 
 if __name__ == "__main__":
