@@ -457,6 +457,18 @@ int pqa_tbdm_accumulate(pqa_handle_t* h, int k, int64_t nconf, int nea, int neb,
    through the protocol route (pyqmc_amd.TBDMAccumulator: testvalue, updateinternals, testvalue_many). */
 int pqa_tbdm_sweep(pqa_handle_t* wf, pqa_handle_t* ev, int k, int spin_a, int spin_b, const int32_t* assign_a, const int32_t* assign_b,
                    const int32_t* ijkl, int ntuple, int first, int64_t walker_chunk, double* ratio);
+/* pqa_tbdm_sweep for complex and twisted wave-function handles and complex evaluators: the same steps, streams, events and chunks,
+   with ratio (W,nea,neb) interleaved complex,
+     v_D(q)[i] = sum_k phi_occ_D[k](q) T_D[i][k] (complex, no conjugation),   S_ab(D) = v_D(r1)[a] v_D(r2)[b] (- v_D(r2)[a] v_D(r1)[b]
+     for equal spins, S_aa an exact 0 + 0i),   R_ab = (sum_D w_D S_ab(D) / sum_D w_D) exp(dU_ab),
+   w_D the complex determinant weights relative to the largest |determinant| and dU_ab the real Jastrow difference of pqa_tbdm_sweep.
+   A twisted wf keeps its walkers unfolded; r1 / r2 are folded by its orbital kernel, which puts the wrap phase on the row.  ev ends
+   as pqa_tbdm_accumulate with complex ratios leaves it (a complex value, real norms; pqa_dm_fetch reads them).  Scope: wf a Slater
+   handle with a state (one or more determinants; real, complex or twisted; with or without the two-body Jastrow; no three-body
+   factor), both spin blocks non-empty, ev a second handle on the same device, real or complex; a twisted ev needs a twisted wf.
+   Everything else is refused (<0) and goes through the protocol route.  wf's state is not modified. */
+int pqa_tbdm_sweep_c(pqa_handle_t* wf, pqa_handle_t* ev, int k, int spin_a, int spin_b, const int32_t* assign_a, const int32_t* assign_b,
+                     const int32_t* ijkl, int ntuple, int first, int64_t walker_chunk, double* ratio);
 /* The whole one-body estimator of one evaluation (obdm.py:139-193) with the ratios formed on the device: wf holds the wave function
    with the configurations as its resident walkers (wf's W = nconf), ev the estimator's orbitals, whose `slot` holds the last
    nsweeps (or more) samples of a pqa_dm_walk.  es (ne) host: the listed electrons, any order, either spin, none twice.  Their
@@ -505,6 +517,10 @@ int pqa_obdm_sweeps_c(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_
    orbitals of the spin of the slot's walk (pqa_dm_walk comes first) are evaluated there into `slot`, rows (W, ne, norb) — the first
    stage of pqa_obdm_sweeps, with its scope checks.  wf's state is not modified. */
 int pqa_dm_points_resident(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_t* es, int ne);
+/* pqa_dm_points_resident with the scope of pqa_obdm_sweeps_c / pqa_tbdm_sweep_c: complex and twisted wf, complex ev (rows
+   (W, ne, 2 norb), real block | imaginary block); a twisted ev needs a twisted wf, whose unfolded walkers give phi_k(r_e) its wrap
+   phase. */
+int pqa_dm_points_resident_c(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_t* es, int ne);
 /* Device bytes ev holds for pqa_obdm_sweeps: scratch = the mean mode's panels, partial tiles and sums plus a walker chunk's ratios;
    per_walker = the per-walker accumulators (value, norms), which the mean mode never allocates.  These are the buffers' capacities,
    so after a pqa_obdm_sweeps_c call they are the complex sizes (five panels, 2 norb^2 + norb partials, interleaved ratios and values). */

@@ -129,6 +129,7 @@ _PROTOTYPES = {
     "pqa_tbdm_accumulate": (C.c_int, [_H, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                       C.c_int, C.c_int]),
     "pqa_tbdm_sweep": (C.c_int, [_H, _H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    "pqa_tbdm_sweep_c": (C.c_int, [_H, _H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "pqa_obdm_sweeps": (C.c_int, [_H, _H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "pqa_obdm_sweeps_w": (C.c_int, [_H, _H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p,
@@ -136,6 +137,7 @@ _PROTOTYPES = {
     "pqa_obdm_sweeps_c": (C.c_int, [_H, _H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pqa_dm_points_resident": (C.c_int, [_H, _H, C.c_int, C.c_void_p, C.c_int]),
+    "pqa_dm_points_resident_c": (C.c_int, [_H, _H, C.c_int, C.c_void_p, C.c_int]),
     "pqa_dm_fetch_w": (C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "pqa_sq_w": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pqa_obdm_bytes": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

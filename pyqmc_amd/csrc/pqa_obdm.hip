@@ -705,6 +705,16 @@ extern "C" int pqa_dm_points_resident(pqa_handle_t* h, pqa_handle_t* ev, int slo
   return resident_points(h, ev, slot, es, ne);
 }
 
+// pqa_dm_points_resident for complex and twisted handles and complex evaluators (pqa_obdm_sweeps_c's scope: a twisted evaluator needs
+// a twisted wf, whose walkers are unfolded, so that the evaluator's orbital kernel puts the wrap phase on phi_k(r_e))
+extern "C" int pqa_dm_points_resident_c(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne) {
+  int spins = 0;
+  TRY(resident_scope(h, ev, slot, es, ne, "pqa_dm_points_resident_c", &spins, true));
+  if (ev->dm[slot].n <= 0) FAIL("pqa_dm_points_resident_c: no auxiliary walkers in the slot (call pqa_dm_walk: it names the slot's spin)");
+  if (ev->nmo[ev->dm[slot].spin] <= 0) FAIL("pqa_dm_points_resident_c: the evaluator has no orbitals of the walk's spin");
+  return resident_points(h, ev, slot, es, ne);
+}
+
 // Weighted walker mean of one of ev's per-walker accumulators (pqa_dm_fetch's `which`), times scale
 extern "C" int pqa_dm_fetch_w(pqa_handle_t* h, int which, int ncol, double scale, const double* weights, double* out) {
   if (!h) return -2;

@@ -142,11 +142,12 @@ class OrbitalEvaluator:
         out = out.view(complex) if cplx else out
         return out.reshape(shape) if mean else out.reshape((nconf,) + tuple(shape))
 
-    def points_resident(self, slot, dev, electrons):
+    def points_resident(self, slot, dev, electrons, cplx=False):
         """``pqa_dm_points_resident``: what ``points`` leaves in ``slot``, for the listed ``electrons`` of the walkers resident
-        behind the wave-function handle ``dev``, gathered device to device (the slot's walk names the spin)."""
+        behind the wave-function handle ``dev``, gathered device to device (the slot's walk names the spin).  ``cplx``:
+        ``pqa_dm_points_resident_c``, which admits complex and twisted handles and complex evaluators."""
         es = np.ascontiguousarray(np.asarray(electrons).ravel(), dtype=np.int32)
-        dev.call("pqa_dm_points_resident", self.dev._h, int(slot), _ffi.ptr(es), len(es))
+        dev.call("pqa_dm_points_resident_c" if cplx else "pqa_dm_points_resident", self.dev._h, int(slot), _ffi.ptr(es), len(es))
 
     def fetch_w(self, which, nconf, shape, scale, weights, cplx=False):
         """``pqa_dm_fetch_w``: the walker mean of accumulator ``which`` with the walker ``weights`` (nconf,), times ``scale``."""

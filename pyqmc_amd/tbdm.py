@@ -17,6 +17,13 @@ Two routes give the pair ratios:
   Slater (one or more determinants), optionally times JastrowSpin, open or periodic at Gamma — with a real evaluator on the same
   device.  The ratios come in closed form from the resident state (pqa_tbdm.hip), which is not modified, for a walker chunk at a
   time, and ``k_tbdm_acc`` consumes them on the device: only the two assignments cross the bus.
+  With ``complex_device=True`` (opt-in) complex and twisted handles and complex evaluators take this route as well
+  (``pqa_tbdm_sweep_c``): the complex pair ratios come in closed form from the resident complex inverse (complex determinant
+  weights, a complex quotient, the real Jastrow difference) and ``k_tbdm_acc`` reads them as it reads the protocol route's.  The
+  entry is chosen per pair: anything complex or twisted on either side goes through ``pqa_tbdm_sweep_c``, two real handles through
+  ``pqa_tbdm_sweep`` bit for bit as before, and a twisted evaluator with an untwisted handle (whose folded walkers have lost the
+  wrap phase of the orbitals at the electrons) stays on the protocol route.  ``value`` is complex and the norms real, as on the
+  protocol route.
 * **protocol**: every other wave function.  ``testvalue`` + ``updateinternals`` move electron a to r1' (Sherman-Morrison on the
   device), ``testvalue_many`` gives the ratios of all partners b at once (``k_testvalue_many``), and a second ``updateinternals``
   moves a back.
@@ -29,24 +36,28 @@ import numpy as np
 
 from . import _ffi
 from .obdm import AuxiliaryWalkers, OrbitalEvaluator
-from .wf import readonly_device
+from .wf import readonly_device, readonly_device_c
 
 ROUTES = (None, "fused", "protocol")
+
+
+def _sweep(entry, dtype, dev, ev, k, spins, assign_a, assign_b, ijkl, first, walker_chunk, with_ratios):
+    a, b = (np.ascontiguousarray(x, dtype=np.int32) for x in (assign_a, assign_b))
+    if a.shape != (dev.W,) or b.shape != (dev.W,):
+        raise ValueError(f"assignments ({dev.W},) expected, got {a.shape} and {b.shape}")
+    R = np.empty((dev.W, dev.nelec[spins[0]], dev.nelec[spins[1]]), dtype=dtype) if with_ratios else None
+    if ijkl is not None:
+        ijkl = np.ascontiguousarray(ijkl, dtype=np.int32)
+    dev.call(entry, ev.dev._h, int(k), int(spins[0]), int(spins[1]), _ffi.ptr(a), _ffi.ptr(b), _ffi.ptr(ijkl),
+             0 if ijkl is None else ijkl.shape[1], int(first), int(walker_chunk), _ffi.ptr(R))
+    return R
 
 
 def device_tbdm_sweep(dev, ev, k, spins, assign_a, assign_b, ijkl=None, first=True, walker_chunk=0, with_ratios=False):
     """``pqa_tbdm_sweep``: the pair ratios of wave-function handle ``dev`` at kept sample ``k`` of the two resident walks of the
     evaluator ``ev`` (an ``OrbitalEvaluator``), contracted into ``ev``'s accumulators for the index tuples ``ijkl`` (4, M) (None:
     ratios only).  Returns the ratios (W, nea, neb) with ``with_ratios``, else None."""
-    a, b = (np.ascontiguousarray(x, dtype=np.int32) for x in (assign_a, assign_b))
-    if a.shape != (dev.W,) or b.shape != (dev.W,):
-        raise ValueError(f"assignments ({dev.W},) expected, got {a.shape} and {b.shape}")
-    R = np.empty((dev.W, dev.nelec[spins[0]], dev.nelec[spins[1]])) if with_ratios else None
-    if ijkl is not None:
-        ijkl = np.ascontiguousarray(ijkl, dtype=np.int32)
-    dev.call("pqa_tbdm_sweep", ev.dev._h, int(k), int(spins[0]), int(spins[1]), _ffi.ptr(a), _ffi.ptr(b), _ffi.ptr(ijkl),
-             0 if ijkl is None else ijkl.shape[1], int(first), int(walker_chunk), _ffi.ptr(R))
-    return R
+    return _sweep("pqa_tbdm_sweep", float, dev, ev, k, spins, assign_a, assign_b, ijkl, first, walker_chunk, with_ratios)
 
 
 def device_pair_ratios(dev, ev, k, spins, assign_a, assign_b, walker_chunk=0):
@@ -55,18 +66,34 @@ def device_pair_ratios(dev, ev, k, spins, assign_a, assign_b, walker_chunk=0):
     return device_tbdm_sweep(dev, ev, k, spins, assign_a, assign_b, walker_chunk=walker_chunk, with_ratios=True)
 
 
+def device_tbdm_sweep_c(dev, ev, k, spins, assign_a, assign_b, ijkl=None, first=True, walker_chunk=0, with_ratios=False):
+    """``pqa_tbdm_sweep_c``: ``device_tbdm_sweep`` for complex and twisted handles ``dev`` and complex evaluators ``ev`` (real ones are
+    taken too): complex ratios (W, nea, neb), and ``ev``'s value accumulator is complex (``ev.fetch(..., cplx=True)``)."""
+    return _sweep("pqa_tbdm_sweep_c", complex, dev, ev, k, spins, assign_a, assign_b, ijkl, first, walker_chunk, with_ratios)
+
+
+def device_pair_ratios_c(dev, ev, k, spins, assign_a, assign_b, walker_chunk=0):
+    """``device_pair_ratios`` through ``pqa_tbdm_sweep_c``: complex R (W, nea, neb); nothing is accumulated."""
+    return device_tbdm_sweep_c(dev, ev, k, spins, assign_a, assign_b, walker_chunk=walker_chunk, with_ratios=True)
+
+
 class TBDMAccumulator:
     """Keys ``value`` (M,), ``norm_a`` (norb_a,), ``norm_b`` (norb_b,) per configuration for the M index tuples ``ijkl``
     (default: the whole sector).  ``orb_coeff`` (2, nao, norb): orbital basis per spin; ``spin`` = (s1, s2).
 
     ``route``: None takes the fused route whenever the wave function and the evaluator are in its scope and the protocol route
     otherwise; "fused" raises outside the scope; "protocol" always moves the electrons.  ``walker_chunk``: walkers per scratch chunk
-    of the fused route (0: the library's bound)."""
+    of the fused route (0: the library's bound).  ``complex_device``: with True complex and twisted handles and complex evaluators
+    are in the fused scope too (``pqa_tbdm_sweep_c``), except a twisted evaluator with an untwisted handle; with False (the default)
+    they take the protocol route and ``route="fused"`` raises for them."""
 
     def __init__(self, mol, orb_coeff, spin, nsweeps=4, tstep=0.50, warmup=200, naux=None, ijkl=None, kpts=None,
-                 eval_gto_precision=None, device=0, route=None, walker_chunk=0):
+                 eval_gto_precision=None, device=0, route=None, walker_chunk=0, complex_device=False):
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}")
+        if not isinstance(complex_device, (bool, np.bool_)):
+            raise ValueError("complex_device must be True or False")
+        self.complex_device = bool(complex_device)
         self._route, self._walker_chunk, self.last_route = route, int(walker_chunk), None
         self.orbitals = OrbitalEvaluator(mol, orb_coeff, kpts=kpts, eval_gto_precision=eval_gto_precision, device=device)
         self._mol, self.dtype = self.orbitals.mol, self.orbitals.mo_dtype
@@ -95,15 +122,35 @@ class TBDMAccumulator:
             wf.updateinternals(a, configs.electron(a), configs)  # and back: the state ends where it started
         return R
 
+    def _device(self, wf):
+        """The handle the fused route reads ``wf`` from, or None."""
+        return readonly_device_c(wf) if self.complex_device else readonly_device(wf)
+
+    def _complex_entry(self, dev):
+        """Whether the evaluation of the handle ``dev`` goes through ``pqa_tbdm_sweep_c``."""
+        ev = self.orbitals.dev
+        return self.complex_device and bool(dev.cplx or dev.twisted or ev.cplx or ev.twisted)
+
+    def _evaluator_in_scope(self, dev):
+        ev = self.orbitals.dev
+        if self.complex_device:
+            return not (ev.twisted and not dev.twisted)
+        return not ev.cplx and not ev.twisted
+
     def _fused_device(self, configs, wf):
         """The handle the fused route evaluates ``wf`` on, or None: a read-only-scope wave function whose resident walkers are the
-        configurations, whole non-empty spin blocks, a real evaluator on the same device."""
+        configurations, whole non-empty spin blocks, an evaluator in scope (real; with ``complex_device`` also complex, and twisted
+        when the handle is) on the same device."""
         if self._route == "protocol":
             return None
-        dev, ev = readonly_device(wf), self.orbitals.dev
+        dev, ev = self._device(wf), self.orbitals.dev
         ok = (dev is not None and dev.W == configs.configs.shape[0] and tuple(dev.nelec) == tuple(self._mol.nelec)
-              and min(len(e) for e in self._electrons) > 0 and not ev.cplx and not ev.twisted and ev.device == dev.device)
+              and min(len(e) for e in self._electrons) > 0 and self._evaluator_in_scope(dev) and ev.device == dev.device)
         if not ok and self._route == "fused":
+            if self.complex_device:
+                raise ValueError("route='fused' needs a Slater (x two-body Jastrow) wave function on one device handle whose resident "
+                                 "walkers are the configurations, and an orbital evaluator on the same device that is twisted only if "
+                                 "the handle is: " + (self.resident_scope(wf) or "the handle holds other walkers than the configurations"))
             raise ValueError("route='fused' needs a real Slater (x two-body Jastrow) wave function on one device handle whose resident "
                              "walkers are the configurations, and a real orbital evaluator on the same device")
         return dev if ok else None
@@ -112,10 +159,15 @@ class TBDMAccumulator:
         """None when ``avg_resident`` can run for ``wf``, else the reason (the fused route's rules)."""
         if self._route == "protocol":
             return "the accumulator is bound to route='protocol'"
-        dev, ev = readonly_device(wf), self.orbitals.dev
+        dev, ev = self._device(wf), self.orbitals.dev
         if dev is None:
+            if self.complex_device:
+                return "the wave function is not a Slater (x two-body Jastrow) product on one device handle"
             return "the wave function is not a real Slater (x two-body Jastrow) product on one device handle"
-        if ev.cplx or ev.twisted:
+        if self.complex_device:
+            if ev.twisted and not dev.twisted:
+                return "the orbital evaluator is twisted and the wave function's handle is not (its folded walkers have lost the wrap phase)"
+        elif ev.cplx or ev.twisted:
             return "the orbital evaluator is complex"
         if ev.device != dev.device:
             return "the wave function and the evaluator are on different devices"
@@ -133,17 +185,19 @@ class TBDMAccumulator:
         why = self.resident_scope(wf)
         if why is not None:
             raise ValueError(f"TBDMAccumulator.avg_resident: {why}")
-        dev = readonly_device(wf)
+        dev = self._device(wf)
         nconf, scale = dev.W, 1.0 / self._nsweeps
         if weights is not None:
             weights = _ffi.walker_weights(weights, nconf)
-        self._sample(None, wf, resident=dev)
+        cplx = self._sample(None, wf, resident=dev)
+        if cplx and weights is None:  # (the complex entry's plain mean is the unit-weight instance of the weighted reduction: same bits)
+            weights = np.ones(nconf)
         na, nb = self.orbitals.nmo()
         shapes = ((self._ijkl.shape[1],), (na,), (nb,))
         if weights is None:
-            out = [self.orbitals.fetch(i, nconf, sh, scale, True) for i, sh in enumerate(shapes)]
+            out = [self.orbitals.fetch(i, nconf, sh, scale, True, cplx and i == 0) for i, sh in enumerate(shapes)]
         else:
-            out = [self.orbitals.fetch_w(i, nconf, sh, scale, weights) for i, sh in enumerate(shapes)]
+            out = [self.orbitals.fetch_w(i, nconf, sh, scale, weights, cplx and i == 0) for i, sh in enumerate(shapes)]
         return dict(zip(("value", "norm_a", "norm_b"), out))
 
     def _sample(self, configs, wf, resident=None):
@@ -169,10 +223,11 @@ class TBDMAccumulator:
                 ev.points(s, s, x[:, self._electrons[s]])
         else:
             for s in (0, 1):
-                ev.points_resident(s, dev, self._electrons[s])
-        cplx = False
+                ev.points_resident(s, dev, self._electrons[s], cplx=self._complex_entry(dev))
+        cplx = dev is not None and self._complex_entry(dev)
+        sweep = device_tbdm_sweep_c if cplx else device_tbdm_sweep
         for sw in range(self._nsweeps if dev is not None else 0):  # the ratios stay on the device
-            device_tbdm_sweep(dev, ev, sw, self._spin_sector, pick[0][sw], pick[1][sw], self._ijkl, sw == 0, self._walker_chunk)
+            sweep(dev, ev, sw, self._spin_sector, pick[0][sw], pick[1][sw], self._ijkl, sw == 0, self._walker_chunk)
         for sw in range(self._nsweeps if dev is None else 0):
             there = [ev.container(kept[s][sw][pick[s][sw]]).electron(0) for s in (0, 1)]
             R = np.ascontiguousarray(self._pair_ratios(configs, wf, *there))

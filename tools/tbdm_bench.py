@@ -1,13 +1,18 @@
 """Two-body density matrix timing, fused route against protocol route: one JSON line per configuration, appended to
 profiles/tbdm_bench.jsonl with --record.
 
-    python tools/tbdm_bench.py [--configs C2,M4096,M,MD50,K222] [--reps 7] [--routes fused,protocol] [--protocol-budget-s 90] [--record]
+    python tools/tbdm_bench.py [--configs C2,M4096,M,MD50,K222,C3,CX311] [--reps 7] [--routes fused,protocol] [--protocol-budget-s 90] [--record]
 
 Per configuration and route: wall-clock milliseconds per ``TBDMAccumulator.__call__`` (nsweeps = 4, 8 orbitals per spin, sector
 (up, down)) — the auxiliary walks, the orbitals at the electrons, the four sweeps and the fetch of the result, which ends with a
 stream synchronisation.  Two warm-up calls (the first also warms the walks up), then ``reps`` timed calls: median, minimum, maximum
 and spread = (max - min) / median.  The protocol route at more than 4 096 walkers runs only when 16 x its 4 096-walker time fits
 --protocol-budget-s; otherwise the record says that it was left out for time.  The library is used as built (no build on import).
+C3 (the twisted 8-atom diamond cell of tools/config_bench.py, 16 + 16 electrons) and CX311 (the complex 3 x 1 x 1 cell, 12 + 12), built
+as tools/obdm_bench.py builds them, are complex handles with the evaluator's orbitals from the k-point mean field (two of every k-point):
+their fused route is ``complex_device=True`` (``pqa_tbdm_sweep_c``).  For them ``__call__`` and ``avg`` are timed with the two routes
+alternating call by call in one process, after their results from equal seeds were found equal at the bound of
+tests/test_gpu_tbdm_complex.py; the rows carry ``"complex": true`` and say whether the routes' [min, max] intervals are disjoint.
 The kernel split comes from a ``rocprofv3 --kernel-trace --stats`` run of this tool with --routes fused --reps 3.
 """
 
@@ -52,6 +57,19 @@ def build(name):
         kpts = np.asarray(kmf.kpts)
         per_k = NORB // len(kpts)
         return sup, wf, 4096, dict(orb_coeff=[np.asarray(kmf.mo_coeff[0][k])[:, :per_k] for k in range(len(kpts))], kpts=kpts)
+    if name in ("C3", "CX311"):  # complex handles: two orbitals of every k-point of the mean field (8 / 6 orbitals)
+        from pyqmc_amd import pbc
+
+        if name == "C3":
+            sup = pbc.get_supercell(systems.diamond_primitive(), np.array([[-1.0, 1, 1], [1, -1, 1], [1, 1, -1]]))
+            kmf = pbc.random_kmf(sup, complex_coeff=True, twist=(0.25, 0.1, -0.3), nvirt=4)
+        else:
+            sup = pbc.get_supercell(systems.diamond_primitive(), np.diag([3.0, 1.0, 1.0]))
+            kmf = pbc.random_kmf(sup, complex_coeff=True, nvirt=4)
+        sup, wf = helpers.gpu_pbc_wf(name, case=(sup, kmf))
+        kpts = np.asarray(kmf.kpts)
+        per_k = max(1, NORB // len(kpts))
+        return sup, wf, 4096, dict(orb_coeff=[np.asarray(kmf.mo_coeff[0][k])[:, :per_k] for k in range(len(kpts))], kpts=kpts, complex_device=True)
     raise KeyError(name)
 
 
@@ -82,6 +100,58 @@ def time_route(pa, mol, wf, configs, kw, route, reps):
             "route_taken": getattr(acc, "last_route", "protocol")}
 
 
+def accumulator_c(pa, mol, kw, route):
+    """The complex configurations' accumulator: the fused route is complex_device=True, the protocol route does not need the keyword."""
+    if route == "protocol":
+        kw = dict({k: v for k, v in kw.items() if k != "complex_device"}, route="protocol")
+    else:
+        kw = dict(kw, route="fused")
+    return pa.TBDMAccumulator(mol, spin=(0, 1), nsweeps=NSWEEPS, warmup=20, **kw)
+
+
+def check_equal(pa, mol, wf, configs, kw):
+    """Worst deviations of the fused route from the protocol route at equal seeds; raises beyond the tests' bound."""
+    out = {}
+    for route in ("fused", "protocol"):  # (the protocol route last: its moves there and back leave round-off in the state)
+        acc = accumulator_c(pa, mol, kw, route)
+        np.random.seed(7)
+        out[route] = (acc(configs, wf), acc.avg(configs, wf))
+    err = lambda a, b: float(np.max(np.abs(a - b) / (1 + np.abs(b))))  # noqa: E731
+    worst = {f"{m}_{k}": err(out["fused"][i][k], out["protocol"][i][k]) for i, m in enumerate(("call", "avg")) for k in ("value", "norm_a", "norm_b")}
+    if max(worst.values()) >= 1e-10:
+        raise RuntimeError(f"the routes disagree: {worst}")
+    return worst
+
+
+def run_complex(pa, name, mol, wf, configs, W, kw, reps, routes):
+    """C3 / CX311: the routes alternate call by call in one process, ``__call__`` and ``avg``, after the seeded results were found equal."""
+    dev = wf.fused_device()
+    rec = {"config": name, "walkers": W, "nelec": list(dev.nelec), "ndet": dev.ndet, "nsweeps": NSWEEPS,
+           "norb": sum(np.asarray(c).shape[1] for c in kw["orb_coeff"]), "sector": [0, 1], "complex": True, "twisted": bool(dev.twisted)}
+    if "fused" in routes and "protocol" in routes:
+        rec["checked"] = check_equal(pa, mol, wf, configs, kw)
+    for method in ("call", "avg"):
+        accs = {r: accumulator_c(pa, mol, kw, r) for r in routes}
+        ms = {r: [] for r in routes}
+        np.random.seed(11)
+        for r_ in range(reps + 2):
+            for r, acc in accs.items():
+                t0 = time.perf_counter()
+                (acc.avg if method == "avg" else acc)(configs, wf)
+                if r_ >= 2:
+                    ms[r].append((time.perf_counter() - t0) * 1e3)
+        for r in routes:
+            med = float(np.median(ms[r]))
+            rec.setdefault(r, {})[method] = {"ms": med, "min_ms": float(min(ms[r])), "max_ms": float(max(ms[r])),
+                                             "spread": float((max(ms[r]) - min(ms[r])) / med), "reps": reps, "route_taken": accs[r].last_route}
+    if "fused" in rec and "protocol" in rec:
+        for m in ("call", "avg"):  # the ratio of medians, and whether the two routes' [min, max] intervals are disjoint
+            f, p = rec["fused"][m], rec["protocol"][m]
+            rec["speedup_" + m] = p["ms"] / f["ms"]
+            rec["beyond_spread_" + m] = bool(f["max_ms"] < p["min_ms"] or p["max_ms"] < f["min_ms"])
+    return rec
+
+
 def run(name, reps, routes, budget_s, small_protocol_ms):
     import pyqmc_amd as pa
 
@@ -93,6 +163,8 @@ def run(name, reps, routes, budget_s, small_protocol_ms):
 
         configs = PeriodicConfigs(configs.configs, mol.lattice_vectors())
     wf.recompute(configs)
+    if kw.get("complex_device"):
+        return run_complex(pa, name, mol, wf, configs, W, kw, reps, [r for r in routes if r in ("fused", "protocol")])
     rec = {"config": name, "walkers": W, "nelec": list(dev.nelec), "ndet": dev.ndet, "nsweeps": NSWEEPS, "norb": NORB, "sector": [0, 1]}
     if "fused" in routes:
         rec["fused"] = time_route(pa, mol, wf, configs, kw, "fused", reps)
