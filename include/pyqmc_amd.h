@@ -521,6 +521,27 @@ int pqa_dm_points_resident(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const i
    (W, ne, 2 norb), real block | imaginary block); a twisted ev needs a twisted wf, whose unfolded walkers give phi_k(r_e) its wrap
    phase. */
 int pqa_dm_points_resident_c(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_t* es, int ne);
+/* The fused density-matrix entries for wave functions with a THREE-BODY Jastrow factor.  pqa_obdm_sweeps_j3 has pqa_obdm_sweeps_c's
+   parameter list (weights NULL: unweighted) with real ratio (nsweeps, W, ne) and value_mean (norb, norb); pqa_tbdm_sweep_j3 has
+   pqa_tbdm_sweep's; pqa_dm_points_resident_j3 is pqa_dm_points_resident in their scope.  With C symmetrised in (k, l) the pair term
+     t(x, s; y, u) = sum_I sum_klm C[I][k][l][m][s + u] a_k(|x - R_I|) a_l(|y - R_I|) b_m(|x - y|)
+   is symmetric, U3 = sum_{i<j} t(i, j), P_e = sum_{j != e} t(e, j), and with one table G_s(q)[j] = t(q, s; r_j, s_j) per auxiliary
+   point and moving spin, SG its sum over j,
+     A3_e(r')  = SG_{s_e}(r') - G_{s_e}(r')[e] - P_e,                    R_e  = (Slater ratio) exp(A_e + A3_e)
+     dU3_ab    = SG_{s1}(r1) + SG_{s2}(r2) + t(r1, s1; r2, s2) - G_{s1}(r1)[a] - G_{s1}(r1)[b] - G_{s2}(r2)[a] - G_{s2}(r2)[b]
+                 - P_a - P_b + t(r_a, s1; r_b, s2),                      R_ab = S_ab exp(dU_ab + dU3_ab)
+   with the Slater and two-body parts of pqa_obdm_sweeps / pqa_tbdm_sweep.  One kernel (k_j3_moves, one wave per walker) forms the
+   three-body differences of a walker chunk ahead of the ratio kernel.  Scope: wf a real, untwisted Slater handle with a state (one
+   or more determinants; with or without the two-body factor; with or without the three-body factor — without one the launches and
+   the bits are those of pqa_obdm_sweeps / _w / pqa_tbdm_sweep), open or periodic at Gamma, whose three-body tables of one walker fit
+   160 KiB of LDS; ev a second, real handle on the same device.  Everything else is refused (<0) with a message that names the entry
+   and the protocol route.  Modes, chunks, assignments and weights follow the siblings.  wf's state is not modified. */
+int pqa_obdm_sweeps_j3(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
+                       uint64_t seed, int mean, int first, int64_t walker_chunk, const double* weights, double* ratio,
+                       int32_t* assign_out, double* value_mean, double* norm_mean);
+int pqa_tbdm_sweep_j3(pqa_handle_t* wf, pqa_handle_t* ev, int k, int spin_a, int spin_b, const int32_t* assign_a, const int32_t* assign_b,
+                      const int32_t* ijkl, int ntuple, int first, int64_t walker_chunk, double* ratio);
+int pqa_dm_points_resident_j3(pqa_handle_t* wf, pqa_handle_t* ev, int slot, const int32_t* es, int ne);
 /* Device bytes ev holds for pqa_obdm_sweeps: scratch = the mean mode's panels, partial tiles and sums plus a walker chunk's ratios;
    per_walker = the per-walker accumulators (value, norms), which the mean mode never allocates.  These are the buffers' capacities,
    so after a pqa_obdm_sweeps_c call they are the complex sizes (five panels, 2 norb^2 + norb partials, interleaved ratios and values). */

@@ -138,6 +138,10 @@ _PROTOTYPES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pqa_dm_points_resident": (C.c_int, [_H, _H, C.c_int, C.c_void_p, C.c_int]),
     "pqa_dm_points_resident_c": (C.c_int, [_H, _H, C.c_int, C.c_void_p, C.c_int]),
+    "pqa_obdm_sweeps_j3": (C.c_int, [_H, _H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pqa_tbdm_sweep_j3": (C.c_int, [_H, _H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    "pqa_dm_points_resident_j3": (C.c_int, [_H, _H, C.c_int, C.c_void_p, C.c_int]),
     "pqa_dm_fetch_w": (C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "pqa_sq_w": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pqa_obdm_bytes": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

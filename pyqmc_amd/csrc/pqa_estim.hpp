@@ -309,6 +309,13 @@ inline int readonly_scope(pqa_handle* h, const char* fn) {
   return 0;
 }
 
+// readonly_scope with a three-body factor admitted (pqa_obdm_sweeps_j3, pqa_tbdm_sweep_j3)
+inline int readonly_scope_j3(pqa_handle* h, const char* fn) {
+  const char* why = !h->has_slater ? "the handle has no Slater factor" : (h->cplx || h->twist) ? "complex orbitals / twisted cell" : nullptr;
+  if (why) FAIL(std::string(fn) + ": " + why + " (outside the fused scope: use the protocol route)");
+  return 0;
+}
+
 // Scope of the linear-Jastrow units (pqa_correlated, pqa_variance): a real single-determinant Slater x two-body Jastrow handle whose
 // row block R[4][P] fits the LDS.
 inline int linear_jastrow_scope(pqa_handle* h, const char* fn) {

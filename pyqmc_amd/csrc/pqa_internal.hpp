@@ -130,6 +130,7 @@ struct pqa_handle {
   DevBuf b_orbphi[2];
   DevBuf b_s2out;  // pqa_s2 (pqa_s2.hip): outputs
   DevBuf b_tbpts;  // pqa_tbdm_sweep (pqa_tbdm.hip): the auxiliary points of a walker chunk, gathered from the evaluator handle
+  DevBuf b_j3dm;   // k_j3_moves (pqa_j3dm.hpp): the three-body differences of a walker chunk
   // pqa_symmetry (pqa_symmetry.hip), per walker chunk: transformed coordinates, determinant ratios (sign, log) of each spin; the
   // ratios of every operator
   DevBuf b_symx, b_symdet[2], b_symout;

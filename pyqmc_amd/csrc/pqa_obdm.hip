@@ -38,6 +38,7 @@
 // phi_k(r_e); the wave function's own orbital launch folds r' and derives the phase there.  The per-walker mode hands the interleaved
 // ratios to k_obdm_acc with rc = 1.  Slices, chunks and the order of every sum are those of the real entries.
 #include "pqa_estim.hpp"
+#include "pqa_j3dm.hpp"
 
 namespace {
 
@@ -118,14 +119,15 @@ __device__ __forceinline__ double ion_u(const SysDev& S, double qx, double qy, d
 // [wc][norb] (t, b and the norm term of the walker).
 // Dynamic LDS (doubles): 3 N coordinates, 2 ne (Jastrow differences, ratios), ndet weights (several determinants), the v tables
 // ndet_up nup + ndet_dn ndn.
-template <bool PBC>
+// J3 (pqa_obdm_sweeps_j3 on a three-body handle): A3 [wc][ne], the three-body differences k_j3_moves left, join the exponent.
+template <bool PBC, bool J3 = false>
 __global__ __launch_bounds__(64) void k_obdm_rt(SysDev S, SlaterState st, JastrowState js, const double* __restrict__ phi_up,
                                                 const double* __restrict__ phi_dn, const double* __restrict__ pts,
                                                 const int* __restrict__ es, int ne, long w0, int jas, int spins,
                                                 const double* __restrict__ cfg, const double* __restrict__ rows,
                                                 const double* __restrict__ f, const int* __restrict__ assign, int norb,
                                                 double* __restrict__ R, double* __restrict__ T, double* __restrict__ B,
-                                                double* __restrict__ Nn) {
+                                                double* __restrict__ Nn, const double* __restrict__ A3) {
   extern __shared__ double lds[];
   const int N = S.nelec, lane = threadIdx.x, D = S.ndet;
   const long wl = blockIdx.x, w = w0 + wl;
@@ -180,7 +182,8 @@ __global__ __launch_bounds__(64) void k_obdm_rt(SysDev S, SlaterState st, Jastro
       for (int Dd = 0; Dd < D; ++Dd) ratio += wd[Dd] * v[(size_t)S.det_map[s * D + Dd] * n + i];
       ratio /= den;
     } else ratio = v[i];
-    if (jas) ratio *= exp(A[t]);
+    if (J3) ratio *= exp((jas ? A[t] : 0.0) + A3[(size_t)wl * ne + t]);
+    else if (jas) ratio *= exp(A[t]);
     Rl[t] = ratio;
     if (R) R[(size_t)wl * ne + t] = ratio;
   }
@@ -436,7 +439,9 @@ __global__ __launch_bounds__(256) void k_obdm_wscale(const double* __restrict__ 
 // spins: bit 0 / 1 set when an up / down electron is listed.  Leaves wf's walker-major arrays current.
 // cx (pqa_obdm_sweeps_c): complex and twisted handles and evaluators are admitted too; a twisted evaluator needs a twisted wf, whose
 // walkers are unfolded (an untwisted periodic handle holds folded walkers, and the wrap phase of phi_k(r_e) would be lost).
-int resident_scope(pqa_handle* h, pqa_handle* ev, int slot, const int32_t* es, int ne, const std::string& fn, int* spins_out, bool cx = false) {
+// j3 (pqa_obdm_sweeps_j3): readonly_scope with a three-body factor admitted.
+int resident_scope(pqa_handle* h, pqa_handle* ev, int slot, const int32_t* es, int ne, const std::string& fn, int* spins_out, bool cx = false,
+                   bool j3 = false) {
   if (!h) return -2;
   if (!ev) FAIL(fn + ": the orbital evaluator's handle is NULL");
   TRY(sync_aos(h));
@@ -445,7 +450,8 @@ int resident_scope(pqa_handle* h, pqa_handle* ev, int slot, const int32_t* es, i
   if (cx) {
     const char* why = !h->has_slater ? "the handle has no Slater factor" : h->has_j3 ? "three-body Jastrow factor" : nullptr;
     if (why) FAIL(fn + ": " + why + " (outside the fused scope: use the protocol route)");
-  } else TRY(readonly_scope(h, fn.c_str()));
+  } else if (j3) TRY(readonly_scope_j3(h, fn.c_str()));
+  else TRY(readonly_scope(h, fn.c_str()));
   if (ev == h) FAIL(fn + ": the wave function and the orbital evaluator must be two handles");
   if (cx) {
     if (ev->twist && !h->twist)
@@ -501,10 +507,12 @@ int resident_points(pqa_handle* h, pqa_handle* ev, int slot, const int32_t* es, 
 }
 
 // What an entry is: its name (in messages) and whether it is the complex one (complex / twisted handles and evaluators admitted, complex
-// ratios and value_mean, the kernels k_obdm_rt_c / k_obdm_mean_c; else the real kernels).
+// ratios and value_mean, the kernels k_obdm_rt_c / k_obdm_mean_c; else the real kernels), or the three-body one (real handles with a
+// three-body factor admitted: k_j3_moves ahead of k_obdm_rt<., true>; a handle without one runs exactly the real entry's launches).
 struct ObdmEntry {
   const char* name;
   bool cx;
+  bool j3 = false;
 };
 
 // pqa_obdm_sweeps (weights == NULL), pqa_obdm_sweeps_w (the mean mode with the walker weights `weights`) and pqa_obdm_sweeps_c (either)
@@ -514,7 +522,8 @@ int obdm_sweeps(pqa_handle* h, pqa_handle* ev, const ObdmEntry& en, int slot, co
   const std::string fn = en.name;
   const bool cx = en.cx;
   int spins = 0;
-  TRY(resident_scope(h, ev, slot, es, ne, fn, &spins, cx));
+  TRY(resident_scope(h, ev, slot, es, ne, fn, &spins, cx, en.j3));
+  const bool j3 = en.j3 && h->has_j3;  // (the three-body differences are formed and added)
   const long W = h->W;
   const int N = h->N;
   auto& d = ev->dm[slot];
@@ -535,15 +544,18 @@ int obdm_sweeps(pqa_handle* h, pqa_handle* ev, const ObdmEntry& en, int slot, co
   const size_t lds = ((size_t)3 * N + (1 + (size_t)cz) * ne + (D > 1 ? cz * D : 0) + cz * ((size_t)h->ndet_s[0] * h->nup + (size_t)h->ndet_s[1] * h->ndn)) * sizeof(double);
   if (lds > 160 * 1024) FAIL(fn + ": more determinants than one LDS block holds (use the protocol route)");
   if (lds > 64 * 1024)
-    TRY(raise_lds_limit(h, cx ? (h->S.pbc ? (const void*)k_obdm_rt_c<true> : (const void*)k_obdm_rt_c<false>)
-                              : (h->S.pbc ? (const void*)k_obdm_rt<true> : (const void*)k_obdm_rt<false>)));
+    TRY(raise_lds_limit(h, cx   ? (h->S.pbc ? (const void*)k_obdm_rt_c<true> : (const void*)k_obdm_rt_c<false>)
+                           : j3 ? (h->S.pbc ? (const void*)k_obdm_rt<true, true> : (const void*)k_obdm_rt<false, true>)
+                                : (h->S.pbc ? (const void*)k_obdm_rt<true> : (const void*)k_obdm_rt<false>)));
   // scratch per walker: the point, the orbital rows of the spins present, and the ratios (per-walker mode) or the three panels and
   // the walker's share of a slice's partial tile (mean mode)
   const int nm0 = (spins & 1) ? h->nmo[0] : 0, nm1 = (spins & 2) ? h->nmo[1] : 0;
   const size_t npart = (size_t)cz * norb * norb + norb;  // doubles of a slice's partials, and of the running sums
   const int npanel = cx ? 5 : 3;                           // T, B, Nn / Tr, Ti, Br, Bi, Nn
   const bool need_R = !mean || ratio;
-  const size_t per_walker = (3 + (size_t)nm0 + nm1 + (need_R ? cz * ne : 0) + (mean ? npanel * (size_t)norb + (npart + kSlice - 1) / kSlice : 0)) * sizeof(double);
+  size_t lds_j3 = 0;
+  if (j3) TRY(j3_moves_lds<false>(h, fn, ne, &lds_j3));
+  const size_t per_walker = (3 + (size_t)nm0 + nm1 + (j3 ? ne : 0) + (need_R ? cz * ne : 0) + (mean ? npanel * (size_t)norb + (npart + kSlice - 1) / kSlice : 0)) * sizeof(double);
   long Wc = chunk > 0 ? std::min<long>(W, chunk) : walker_chunk(W, per_walker);
   if (mean && Wc < W) Wc = std::max<long>(kSlice, Wc - Wc % kSlice);  // (whole slices: the slices do not depend on the chunk)
   const long nsl_max = (std::min(Wc, W) + kSlice - 1) / kSlice;
@@ -554,6 +566,7 @@ int obdm_sweeps(pqa_handle* h, pqa_handle* ev, const ObdmEntry& en, int slot, co
   if (mean) TRY(on_ev(h, ev, ensure(ev, ev->b_obdm, ((size_t)npanel * Wc * norb + (size_t)(nsl_max + 2) * npart + (weights ? (size_t)W + 1 : 0)) * sizeof(double))));
   else TRY(on_ev(h, ev, dm_prepare(ev, W, (long)norb * norb, cx ? 1 : 0, first, norb, 0)));
   TRY(ensure(h, h->b_tbpts, (size_t)3 * Wc * sizeof(double)));
+  if (j3) TRY(ensure(h, h->b_j3dm, (size_t)Wc * ne * sizeof(double)));
   if (nm0) TRY(ensure(h, h->b_orbphi[0], (size_t)Wc * nm0 * sizeof(double)));
   if (nm1) TRY(ensure(h, h->b_orbphi[1], (size_t)Wc * nm1 * sizeof(double)));
   TpTuneGuard tune(h), tune_ev(ev);
@@ -594,7 +607,17 @@ int obdm_sweeps(pqa_handle* h, pqa_handle* ev, const ObdmEntry& en, int slot, co
       TRY(check_launch(h, "k_obdm_gather"));
       if (nm0) TRY(launch_orb(h, 0, plain_points(d_pts, wc), wc, 1, (double*)h->b_orbphi[0].p));
       if (nm1) TRY(launch_orb(h, 1, plain_points(d_pts, wc), wc, 1, (double*)h->b_orbphi[1].p));
-      if (cx) {
+      if (j3) {
+        TRY(launch_j3_moves<false>(h, lds_j3, (const double*)d_pts, d_es, ne, w0, wc, 0, 0, spins, (double*)h->b_j3dm.p));
+        if (h->S.pbc)
+          hipLaunchKernelGGL((k_obdm_rt<true, true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
+                             (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, (const double*)d.cfg.p,
+                             keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_B, d_N, (const double*)h->b_j3dm.p);
+        else
+          hipLaunchKernelGGL((k_obdm_rt<false, true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
+                             (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, (const double*)d.cfg.p,
+                             keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_B, d_N, (const double*)h->b_j3dm.p);
+      } else if (cx) {
         if (h->S.pbc)
           hipLaunchKernelGGL((k_obdm_rt_c<true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
                              (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, hc, oc,
@@ -606,11 +629,11 @@ int obdm_sweeps(pqa_handle* h, pqa_handle* ev, const ObdmEntry& en, int slot, co
       } else if (h->S.pbc)
         hipLaunchKernelGGL((k_obdm_rt<true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
                            (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, (const double*)d.cfg.p,
-                           keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_B, d_N);
+                           keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_B, d_N, (const double*)nullptr);
       else
         hipLaunchKernelGGL((k_obdm_rt<false>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
                            (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, (const double*)d.cfg.p,
-                           keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_B, d_N);
+                           keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_B, d_N, (const double*)nullptr);
       TRY(check_launch(h, "k_obdm_rt"));
       if (ratio)
         HIPCHK(hipMemcpyAsync(ratio + ((size_t)s * W + w0) * ne * cz, d_R, (size_t)wc * ne * cz * sizeof(double), hipMemcpyDefault, h->stream));
@@ -696,6 +719,17 @@ extern "C" int pqa_obdm_sweeps_c(pqa_handle_t* h, pqa_handle_t* ev, int slot, co
                      value_mean, norm_mean, weights);
 }
 
+// pqa_obdm_sweeps_c's parameter list for real handles with a three-body Jastrow factor (handles without one are taken too and give the
+// bits of pqa_obdm_sweeps / pqa_obdm_sweeps_w): ratio and value_mean are real.  weights != NULL: the weighted mean (mean mode only).
+extern "C" int pqa_obdm_sweeps_j3(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
+                                  uint64_t seed, int mean, int first, int64_t chunk, const double* weights, double* ratio, int32_t* assign_out,
+                                  double* value_mean, double* norm_mean) {
+  if (!h) return -2;
+  if (weights && !mean) FAIL("pqa_obdm_sweeps_j3: walker weights need the mean mode");
+  return obdm_sweeps(h, ev, ObdmEntry{"pqa_obdm_sweeps_j3", false, true}, slot, es, ne, nsweeps, assign, seed, mean, first, chunk, ratio,
+                     assign_out, value_mean, norm_mean, weights);
+}
+
 // pqa_dm_points with the listed electrons' coordinates gathered from wf's resident walkers, device to device
 extern "C" int pqa_dm_points_resident(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne) {
   int spins = 0;
@@ -712,6 +746,15 @@ extern "C" int pqa_dm_points_resident_c(pqa_handle_t* h, pqa_handle_t* ev, int s
   TRY(resident_scope(h, ev, slot, es, ne, "pqa_dm_points_resident_c", &spins, true));
   if (ev->dm[slot].n <= 0) FAIL("pqa_dm_points_resident_c: no auxiliary walkers in the slot (call pqa_dm_walk: it names the slot's spin)");
   if (ev->nmo[ev->dm[slot].spin] <= 0) FAIL("pqa_dm_points_resident_c: the evaluator has no orbitals of the walk's spin");
+  return resident_points(h, ev, slot, es, ne);
+}
+
+// pqa_dm_points_resident in the scope of pqa_obdm_sweeps_j3 / pqa_tbdm_sweep_j3 (a three-body factor admitted)
+extern "C" int pqa_dm_points_resident_j3(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne) {
+  int spins = 0;
+  TRY(resident_scope(h, ev, slot, es, ne, "pqa_dm_points_resident_j3", &spins, false, true));
+  if (ev->dm[slot].n <= 0) FAIL("pqa_dm_points_resident_j3: no auxiliary walkers in the slot (call pqa_dm_walk: it names the slot's spin)");
+  if (ev->nmo[ev->dm[slot].spin] <= 0) FAIL("pqa_dm_points_resident_j3: the evaluator has no orbitals of the walk's spin");
   return resident_points(h, ev, slot, es, ne);
 }
 

@@ -30,6 +30,7 @@
 // orbital launch folds r1 / r2 and puts the wrap phase exp(i k_t . n . L) on the row, so a point moved by a lattice vector carries the
 // Bloch phase of the moved electron.  A real handle through this entry reads its real tables and leaves imaginary parts exactly 0.
 #include "pqa_estim.hpp"
+#include "pqa_j3dm.hpp"
 
 namespace {
 
@@ -103,10 +104,11 @@ __device__ __forceinline__ double ion_u(const SysDev& S, double qx, double qy, d
 // pts [2][wc][3]; jas: the handle has a two-body Jastrow factor; R [wc][nea][neb].
 // Dynamic LDS (doubles): 3 N coordinates, nea + neb Jastrow sums, ndet weights (several determinants), the v tables
 // ndet_s1 nea NP + (s1 != s2: ndet_s2 neb), NP = 2 for equal spins.
-template <bool PBC>
+// J3 (pqa_tbdm_sweep_j3 on a three-body handle): D3 [wc][nea][neb], the three-body differences k_j3_moves left, join the exponent.
+template <bool PBC, bool J3 = false>
 __global__ __launch_bounds__(64) void k_tbdm_pairs(SysDev S, SlaterState st, JastrowState js, const double* __restrict__ phi1,
                                                    const double* __restrict__ phi2, const double* __restrict__ pts, long w0, long wc, int s1,
-                                                   int s2, int jas, double* __restrict__ R) {
+                                                   int s2, int jas, double* __restrict__ R, const double* __restrict__ D3) {
   extern __shared__ double lds[];
   const int N = S.nelec, lane = threadIdx.x, D = S.ndet;
   const long wl = blockIdx.x, w = w0 + wl;
@@ -184,7 +186,15 @@ __global__ __launch_bounds__(64) void k_tbdm_pairs(SysDev S, SlaterState st, Jas
         ratio += D > 1 ? wd[Dd] * sab : sab;
       }
       if (D > 1) ratio /= den;
-      if (jas) {
+      if (J3) {
+        double dj = D3[(size_t)wl * nea * neb + idx];
+        if (jas) {
+          const int ia = ea0 + a, ib = eb0 + b;
+          dj += A1[a] + A2[b] + u12 +
+                pair_u<PBC>(S, xs[3 * ia] - xs[3 * ib], xs[3 * ia + 1] - xs[3 * ib + 1], xs[3 * ia + 2] - xs[3 * ib + 2], chan, irb);
+        }
+        ratio *= exp(dj);
+      } else if (jas) {
         const int ia = ea0 + a, ib = eb0 + b;
         const double dj = A1[a] + A2[b] + u12 +
                           pair_u<PBC>(S, xs[3 * ia] - xs[3 * ib], xs[3 * ia + 1] - xs[3 * ib + 1], xs[3 * ia + 2] - xs[3 * ib + 2], chan, irb);
@@ -347,10 +357,12 @@ __global__ __launch_bounds__(64) void k_tbdm_pairs_c(SysDev S, SlaterState st, J
 }
 
 // What an entry is: its name (in messages) and whether it is the complex one (complex / twisted handles and evaluators admitted,
-// interleaved complex ratios, the kernel k_tbdm_pairs_c; else k_tbdm_pairs on two real handles).
+// interleaved complex ratios, the kernel k_tbdm_pairs_c; else k_tbdm_pairs on two real handles), or the three-body one (real handles
+// with a three-body factor admitted: k_j3_moves ahead of k_tbdm_pairs<., true>; a handle without one runs the real entry's launches).
 struct TbdmEntry {
   const char* name;
   bool cx;
+  bool j3 = false;
 };
 
 // pqa_tbdm_sweep (cx = false) and pqa_tbdm_sweep_c
@@ -366,7 +378,9 @@ int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const TbdmEntry& en, int k, int sp
   if (cx) {
     const char* why = !h->has_slater ? "the handle has no Slater factor" : h->has_j3 ? "three-body Jastrow factor" : nullptr;
     if (why) FAIL(fn + ": " + why + " (outside the fused scope: use the protocol route)");
-  } else TRY(readonly_scope(h, en.name));
+  } else if (en.j3) TRY(readonly_scope_j3(h, en.name));
+  else TRY(readonly_scope(h, en.name));
+  const bool j3 = en.j3 && h->has_j3;  // (the three-body differences are formed and added)
   if (ev == h) FAIL(fn + ": the wave function and the orbital evaluator must be two handles");
   if (cx) {
     if (ev->twist && !h->twist)
@@ -409,7 +423,12 @@ int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const TbdmEntry& en, int k, int sp
   // scratch per walker: the ratios, the orbital rows at the two points, the points
   const bool same = spin_a == spin_b;
   const int nm1 = h->nmo[spin_a], nm2 = h->nmo[spin_b];
-  const long Wc = chunk > 0 ? std::min<long>(W, chunk) : walker_chunk(W, ((size_t)cz * nea * neb + nm1 + nm2 + 6) * sizeof(double));
+  const long Wc = chunk > 0 ? std::min<long>(W, chunk) : walker_chunk(W, ((size_t)(cz + (j3 ? 1 : 0)) * nea * neb + nm1 + nm2 + 6) * sizeof(double));
+  size_t lds_j3 = 0;
+  if (j3) {
+    TRY(j3_moves_lds<true>(h, fn, same ? nea : nea + neb, &lds_j3));
+    TRY(ensure(h, h->b_j3dm, (size_t)Wc * nea * neb * sizeof(double)));
+  }
   TRY(on_ev(ensure(ev, ev->dm_ratio, (size_t)Wc * nea * neb * cz * sizeof(double))));
   TRY(ensure(h, h->b_tbpts, (size_t)6 * Wc * sizeof(double)));
   TRY(ensure(h, h->b_orbphi[0], (size_t)Wc * (same ? 2 * nm1 : nm1) * sizeof(double)));
@@ -419,8 +438,9 @@ int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const TbdmEntry& en, int k, int sp
                       (same ? 0 : (size_t)h->ndet_s[spin_b] * neb))) * sizeof(double);
   if (lds > 160 * 1024) FAIL(fn + ": more determinants than one LDS block holds (use the protocol route)");
   if (lds > 64 * 1024)
-    TRY(raise_lds_limit(h, cx ? (h->S.pbc ? (const void*)k_tbdm_pairs_c<true> : (const void*)k_tbdm_pairs_c<false>)
-                              : (h->S.pbc ? (const void*)k_tbdm_pairs<true> : (const void*)k_tbdm_pairs<false>)));
+    TRY(raise_lds_limit(h, cx   ? (h->S.pbc ? (const void*)k_tbdm_pairs_c<true> : (const void*)k_tbdm_pairs_c<false>)
+                           : j3 ? (h->S.pbc ? (const void*)k_tbdm_pairs<true, true> : (const void*)k_tbdm_pairs<false, true>)
+                                : (h->S.pbc ? (const void*)k_tbdm_pairs<true> : (const void*)k_tbdm_pairs<false>)));
   if (!h->tb_ev[0])
     for (hipEvent_t& e : h->tb_ev) TRY(new_event(h, &e, hipEventDisableTiming));
   const hipEvent_t produced = h->tb_ev[0], consumed = h->tb_ev[1];
@@ -445,7 +465,15 @@ int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const TbdmEntry& en, int k, int sp
       TRY(launch_orb(h, spin_a, plain_points(d_pts, wc), wc, 1, phi1));
       TRY(launch_orb(h, spin_b, plain_points(d_pts + 3 * wc, wc), wc, 1, phi2));
     }
-    if (cx) {
+    if (j3) {
+      TRY(launch_j3_moves<true>(h, lds_j3, (const double*)d_pts, nullptr, 0, w0, wc, spin_a, spin_b, 3, (double*)h->b_j3dm.p));
+      if (h->S.pbc)
+        hipLaunchKernelGGL((k_tbdm_pairs<true, true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)phi1,
+                           (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, d_R, (const double*)h->b_j3dm.p);
+      else
+        hipLaunchKernelGGL((k_tbdm_pairs<false, true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)phi1,
+                           (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, d_R, (const double*)h->b_j3dm.p);
+    } else if (cx) {
       if (h->S.pbc)
         hipLaunchKernelGGL((k_tbdm_pairs_c<true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)phi1,
                            (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, hc, d_R);
@@ -454,10 +482,10 @@ int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const TbdmEntry& en, int k, int sp
                            (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, hc, d_R);
     } else if (h->S.pbc)
       hipLaunchKernelGGL((k_tbdm_pairs<true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)phi1,
-                         (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, d_R);
+                         (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, d_R, (const double*)nullptr);
     else
       hipLaunchKernelGGL((k_tbdm_pairs<false>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)phi1,
-                         (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, d_R);
+                         (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, d_R, (const double*)nullptr);
     TRY(check_launch(h, "k_tbdm_pairs"));
     if (ratio)
       HIPCHK(hipMemcpyAsync(ratio + (size_t)w0 * nea * neb * cz, d_R, (size_t)wc * nea * neb * cz * sizeof(double), hipMemcpyDefault, h->stream));
@@ -491,4 +519,11 @@ extern "C" int pqa_tbdm_sweep(pqa_handle_t* h, pqa_handle_t* ev, int k, int spin
 extern "C" int pqa_tbdm_sweep_c(pqa_handle_t* h, pqa_handle_t* ev, int k, int spin_a, int spin_b, const int32_t* assign_a,
                                 const int32_t* assign_b, const int32_t* ijkl, int ntuple, int first, int64_t chunk, double* ratio) {
   return tbdm_sweep(h, ev, TbdmEntry{"pqa_tbdm_sweep_c", true}, k, spin_a, spin_b, assign_a, assign_b, ijkl, ntuple, first, chunk, ratio);
+}
+
+// pqa_tbdm_sweep for real handles with a three-body Jastrow factor (handles without one are taken too and give pqa_tbdm_sweep's bits):
+// k_j3_moves forms the three-body difference of every pair of a walker chunk ahead of k_tbdm_pairs<., true>.
+extern "C" int pqa_tbdm_sweep_j3(pqa_handle_t* h, pqa_handle_t* ev, int k, int spin_a, int spin_b, const int32_t* assign_a,
+                                 const int32_t* assign_b, const int32_t* ijkl, int ntuple, int first, int64_t chunk, double* ratio) {
+  return tbdm_sweep(h, ev, TbdmEntry{"pqa_tbdm_sweep_j3", false, true}, k, spin_a, spin_b, assign_a, assign_b, ijkl, ntuple, first, chunk, ratio);
 }

@@ -32,6 +32,12 @@ imaginary panels (Re = Br^T Tr - Bi^T Ti, Im = Br^T Ti + Bi^T Tr).  ``value`` is
 A twisted evaluator needs a twisted wave-function handle (an untwisted periodic handle holds folded walkers, which have lost the wrap
 phase of the orbitals at the electrons): that pair stays on the protocol route.
 
+With ``three_body_device=True`` (opt-in) real wave functions with a three-body Jastrow factor take the fused route as well
+(``pqa_obdm_sweeps_j3``): U3 is a sum over electron pairs and every listed electron of a walker goes to the same point, so one table
+G_s(r')[j] = t(r', s; r_j, s_j) per moving spin gives A3_e = sum_j G[j] - G[e] - P_e for all of them (``k_j3_moves``,
+``csrc/pqa_j3dm.hpp``), added to the two-body difference in the exponent.  Complex or twisted three-body handles stay on the protocol
+route.
+
 ``avg_resident(wf, weights=w)`` is the weighted walker mean sum_w w_w res_w / sum_w w_w of DMC's mixed estimator
 (``pqa_obdm_sweeps_w``: the same product with the weight applied to B as it is loaded; unit weights give the bits of ``avg``).
 
@@ -44,7 +50,7 @@ from . import _ffi
 from . import pbc as _pbc
 from .configs import OpenConfigs, PeriodicConfigs
 from .systems import initial_guess
-from .wf import DeviceWF, readonly_device, readonly_device_c
+from .wf import DeviceWF, readonly_device, readonly_device_c, readonly_device_j3
 
 ROUTES = (None, "fused", "protocol")
 
@@ -142,12 +148,14 @@ class OrbitalEvaluator:
         out = out.view(complex) if cplx else out
         return out.reshape(shape) if mean else out.reshape((nconf,) + tuple(shape))
 
-    def points_resident(self, slot, dev, electrons, cplx=False):
+    def points_resident(self, slot, dev, electrons, cplx=False, j3=False):
         """``pqa_dm_points_resident``: what ``points`` leaves in ``slot``, for the listed ``electrons`` of the walkers resident
         behind the wave-function handle ``dev``, gathered device to device (the slot's walk names the spin).  ``cplx``:
-        ``pqa_dm_points_resident_c``, which admits complex and twisted handles and complex evaluators."""
+        ``pqa_dm_points_resident_c``, which admits complex and twisted handles and complex evaluators; ``j3``:
+        ``pqa_dm_points_resident_j3``, which admits real handles with a three-body Jastrow factor."""
         es = np.ascontiguousarray(np.asarray(electrons).ravel(), dtype=np.int32)
-        dev.call("pqa_dm_points_resident_c" if cplx else "pqa_dm_points_resident", self.dev._h, int(slot), _ffi.ptr(es), len(es))
+        entry = "pqa_dm_points_resident_j3" if j3 else "pqa_dm_points_resident_c" if cplx else "pqa_dm_points_resident"
+        dev.call(entry, self.dev._h, int(slot), _ffi.ptr(es), len(es))
 
     def fetch_w(self, which, nconf, shape, scale, weights, cplx=False):
         """``pqa_dm_fetch_w``: the walker mean of accumulator ``which`` with the walker ``weights`` (nconf,), times ``scale``."""
@@ -299,6 +307,35 @@ def device_obdm_sweeps_c(dev, ev, electrons, nsweeps, assign=None, seed=0, mean=
     return out
 
 
+def device_obdm_sweeps_j3(dev, ev, electrons, nsweeps, assign=None, seed=0, mean=False, first=True, walker_chunk=0, with_ratios=False,
+                          weights=None):
+    """``pqa_obdm_sweeps_j3``: ``device_obdm_sweeps`` for real handles ``dev`` with a three-body Jastrow factor (handles without one are
+    taken too and give the bits of ``device_obdm_sweeps`` / ``device_obdm_sweeps_w``).  The same dict, real; ``weights`` (W,): the
+    weighted mean of ``device_obdm_sweeps_w`` (``mean`` only)."""
+    es = np.ascontiguousarray(np.asarray(electrons).ravel(), dtype=np.int32)
+    W, norb = dev.W, ev.norb
+    if weights is not None:
+        if not mean:
+            raise ValueError("walker weights need the mean mode")
+        weights = _ffi.walker_weights(weights, W)
+    out = {}
+    if assign is not None:
+        assign = np.ascontiguousarray(assign, dtype=np.int32)
+        if assign.shape != (nsweeps, W):
+            raise ValueError(f"assignments ({nsweeps}, {W}) expected, got {assign.shape}")
+        out["assign"] = assign
+    else:
+        out["assign"] = np.empty((nsweeps, W), dtype=np.int32)
+    if with_ratios:
+        out["ratio"] = np.empty((nsweeps, W, len(es)))
+    if mean:
+        out["value"], out["norm"] = np.empty((norb, norb)), np.empty(norb)
+    dev.call("pqa_obdm_sweeps_j3", ev.dev._h, 0, _ffi.ptr(es), len(es), int(nsweeps), _ffi.ptr(assign), int(seed), int(mean), int(first),
+             int(walker_chunk), _ffi.ptr(weights), _ffi.ptr(out.get("ratio")), None if assign is not None else _ffi.ptr(out["assign"]),
+             _ffi.ptr(out.get("value")), _ffi.ptr(out.get("norm")))
+    return out
+
+
 class OBDMAccumulator:
     """Keys ``value`` (norb,norb), ``norm`` (norb,) per configuration (obdm.py:26-213).
 
@@ -313,10 +350,13 @@ class OBDMAccumulator:
     scratch chunk of the fused route (0: the library's bound).  ``last_route`` names the route of the last evaluation.
     ``complex_device``: with True complex and twisted handles and complex evaluators are in the fused scope too
     (``pqa_obdm_sweeps_c``), except a twisted evaluator with an untwisted handle; with False (the default) they take the protocol
-    route and ``route="fused"`` raises for them."""
+    route and ``route="fused"`` raises for them.  ``three_body_device``: with True real wave functions with a three-body Jastrow
+    factor are in the fused scope too (``pqa_obdm_sweeps_j3``, a real evaluator); complex or twisted three-body handles stay on the
+    protocol route.  With False (the default) three-body wave functions take the protocol route."""
 
     def __init__(self, mol, orb_coeff, nsweeps=5, tstep=0.50, warmup=10000, naux=None, spin=None, electrons=None, kpts=None,
-                 eval_gto_precision=None, device=0, route=None, rng="numpy", walker_chunk=0, complex_device=False):
+                 eval_gto_precision=None, device=0, route=None, rng="numpy", walker_chunk=0, complex_device=False,
+                 three_body_device=False):
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}")
         if rng not in ("numpy", "device"):
@@ -326,7 +366,9 @@ class OBDMAccumulator:
         if not isinstance(complex_device, (bool, np.bool_)):
             raise ValueError("complex_device must be True or False")
         self._route, self._rng, self._walker_chunk, self.last_route = route, rng, int(walker_chunk), None
-        self.complex_device = bool(complex_device)
+        if not isinstance(three_body_device, (bool, np.bool_)):
+            raise ValueError("three_body_device must be True or False")
+        self.complex_device, self.three_body_device = bool(complex_device), bool(three_body_device)
         self.last_assign = None  # (nsweeps, nconf) assignments of the last fused evaluation
         nup, ntot = mol.nelec[0], int(np.sum(mol.nelec))
         if spin is not None:
@@ -347,7 +389,14 @@ class OBDMAccumulator:
 
     def _device(self, wf):
         """The handle the fused route reads ``wf`` from, or None."""
-        return readonly_device_c(wf) if self.complex_device else readonly_device(wf)
+        dev = readonly_device_c(wf) if self.complex_device else readonly_device(wf)
+        if dev is None and self.three_body_device:
+            dev = readonly_device_j3(wf)
+        return dev
+
+    def _j3_entry(self, dev):
+        """Whether the evaluation of the handle ``dev`` goes through ``pqa_obdm_sweeps_j3``."""
+        return self.three_body_device and bool(dev.has_j3)
 
     def _complex_entry(self, dev):
         """Whether the evaluation of the handle ``dev`` goes through ``pqa_obdm_sweeps_c``."""
@@ -358,9 +407,18 @@ class OBDMAccumulator:
         dev, ev = self._device(wf), self.orbitals.dev
         es = np.asarray(self._electrons).ravel()
         if dev is None:
+            if self.three_body_device:
+                d3 = getattr(wf, "fused_device", lambda: None)()
+                if d3 is not None and getattr(d3, "has_j3", False) and (d3.cplx or d3.twisted):
+                    return "the three-body wave function is complex or twisted (pqa_obdm_sweeps_j3 takes real handles)"
+                if self.complex_device:
+                    return "the wave function is not a Slater (x two-body x three-body Jastrow) product on one device handle"
+                return "the wave function is not a real Slater (x two-body x three-body Jastrow) product on one device handle"
             if self.complex_device:
                 return "the wave function is not a Slater (x two-body Jastrow) product on one device handle"
             return "the wave function is not a real Slater (x two-body Jastrow) product on one device handle"
+        if self._j3_entry(dev) and (ev.cplx or ev.twisted):
+            return "the orbital evaluator is complex (a three-body wave function needs a real one)"
         if self.complex_device:
             if ev.twisted and not dev.twisted:
                 return "the orbital evaluator is twisted and the wave function's handle is not (its folded walkers have lost the wrap phase)"
@@ -427,7 +485,10 @@ class OBDMAccumulator:
         if seed is None:
             pick = np.random.randint(0, naux, size=(nsw, nconf)).astype(np.int32)  # drawn before the walk (obdm.py:150)
         _, kept = self._walkers.advance(0, nsw, self._tstep, keep=nsw, seed=seed)
-        if self._complex_entry(dev):
+        if self._j3_entry(dev):
+            out = device_obdm_sweeps_j3(dev, ev, self._electrons, nsw, assign=pick, seed=0 if seed is None else seed, mean=mean,
+                                        walker_chunk=self._walker_chunk, with_ratios=with_ratios, weights=weights)
+        elif self._complex_entry(dev):
             out = device_obdm_sweeps_c(dev, ev, self._electrons, nsw, assign=pick, seed=0 if seed is None else seed, mean=mean,
                                        walker_chunk=self._walker_chunk, with_ratios=with_ratios, weights=weights)
         elif weights is not None:

@@ -24,6 +24,10 @@ Two routes give the pair ratios:
   ``pqa_tbdm_sweep`` bit for bit as before, and a twisted evaluator with an untwisted handle (whose folded walkers have lost the
   wrap phase of the orbitals at the electrons) stays on the protocol route.  ``value`` is complex and the norms real, as on the
   protocol route.
+  With ``three_body_device=True`` (opt-in) real wave functions with a three-body Jastrow factor take it too (``pqa_tbdm_sweep_j3``):
+  both electrons of every pair go to the same two points, so two tables G_s(q)[j] = t(q, s; r_j, s_j), the listed electrons' P_e, the
+  cross term t(r1, r2) and the old pair terms give dU3_ab for all pairs of a walker (``k_j3_moves``, ``csrc/pqa_j3dm.hpp``).
+  Complex or twisted three-body handles stay on the protocol route.
 * **protocol**: every other wave function.  ``testvalue`` + ``updateinternals`` move electron a to r1' (Sherman-Morrison on the
   device), ``testvalue_many`` gives the ratios of all partners b at once (``k_testvalue_many``), and a second ``updateinternals``
   moves a back.
@@ -36,7 +40,7 @@ import numpy as np
 
 from . import _ffi
 from .obdm import AuxiliaryWalkers, OrbitalEvaluator
-from .wf import readonly_device, readonly_device_c
+from .wf import readonly_device, readonly_device_c, readonly_device_j3
 
 ROUTES = (None, "fused", "protocol")
 
@@ -77,6 +81,17 @@ def device_pair_ratios_c(dev, ev, k, spins, assign_a, assign_b, walker_chunk=0):
     return device_tbdm_sweep_c(dev, ev, k, spins, assign_a, assign_b, walker_chunk=walker_chunk, with_ratios=True)
 
 
+def device_tbdm_sweep_j3(dev, ev, k, spins, assign_a, assign_b, ijkl=None, first=True, walker_chunk=0, with_ratios=False):
+    """``pqa_tbdm_sweep_j3``: ``device_tbdm_sweep`` for real handles ``dev`` with a three-body Jastrow factor (handles without one are
+    taken too and give ``device_tbdm_sweep``'s bits)."""
+    return _sweep("pqa_tbdm_sweep_j3", float, dev, ev, k, spins, assign_a, assign_b, ijkl, first, walker_chunk, with_ratios)
+
+
+def device_pair_ratios_j3(dev, ev, k, spins, assign_a, assign_b, walker_chunk=0):
+    """``device_pair_ratios`` through ``pqa_tbdm_sweep_j3``: R (W, nea, neb); nothing is accumulated."""
+    return device_tbdm_sweep_j3(dev, ev, k, spins, assign_a, assign_b, walker_chunk=walker_chunk, with_ratios=True)
+
+
 class TBDMAccumulator:
     """Keys ``value`` (M,), ``norm_a`` (norb_a,), ``norm_b`` (norb_b,) per configuration for the M index tuples ``ijkl``
     (default: the whole sector).  ``orb_coeff`` (2, nao, norb): orbital basis per spin; ``spin`` = (s1, s2).
@@ -85,15 +100,19 @@ class TBDMAccumulator:
     otherwise; "fused" raises outside the scope; "protocol" always moves the electrons.  ``walker_chunk``: walkers per scratch chunk
     of the fused route (0: the library's bound).  ``complex_device``: with True complex and twisted handles and complex evaluators
     are in the fused scope too (``pqa_tbdm_sweep_c``), except a twisted evaluator with an untwisted handle; with False (the default)
-    they take the protocol route and ``route="fused"`` raises for them."""
+    they take the protocol route and ``route="fused"`` raises for them.  ``three_body_device``: with True real wave functions with a
+    three-body Jastrow factor are in the fused scope too (``pqa_tbdm_sweep_j3``, a real evaluator); complex or twisted three-body
+    handles stay on the protocol route.  With False (the default) three-body wave functions take the protocol route."""
 
     def __init__(self, mol, orb_coeff, spin, nsweeps=4, tstep=0.50, warmup=200, naux=None, ijkl=None, kpts=None,
-                 eval_gto_precision=None, device=0, route=None, walker_chunk=0, complex_device=False):
+                 eval_gto_precision=None, device=0, route=None, walker_chunk=0, complex_device=False, three_body_device=False):
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}")
         if not isinstance(complex_device, (bool, np.bool_)):
             raise ValueError("complex_device must be True or False")
-        self.complex_device = bool(complex_device)
+        if not isinstance(three_body_device, (bool, np.bool_)):
+            raise ValueError("three_body_device must be True or False")
+        self.complex_device, self.three_body_device = bool(complex_device), bool(three_body_device)
         self._route, self._walker_chunk, self.last_route = route, int(walker_chunk), None
         self.orbitals = OrbitalEvaluator(mol, orb_coeff, kpts=kpts, eval_gto_precision=eval_gto_precision, device=device)
         self._mol, self.dtype = self.orbitals.mol, self.orbitals.mo_dtype
@@ -124,7 +143,14 @@ class TBDMAccumulator:
 
     def _device(self, wf):
         """The handle the fused route reads ``wf`` from, or None."""
-        return readonly_device_c(wf) if self.complex_device else readonly_device(wf)
+        dev = readonly_device_c(wf) if self.complex_device else readonly_device(wf)
+        if dev is None and self.three_body_device:
+            dev = readonly_device_j3(wf)
+        return dev
+
+    def _j3_entry(self, dev):
+        """Whether the evaluation of the handle ``dev`` goes through ``pqa_tbdm_sweep_j3``."""
+        return self.three_body_device and bool(dev.has_j3)
 
     def _complex_entry(self, dev):
         """Whether the evaluation of the handle ``dev`` goes through ``pqa_tbdm_sweep_c``."""
@@ -133,6 +159,8 @@ class TBDMAccumulator:
 
     def _evaluator_in_scope(self, dev):
         ev = self.orbitals.dev
+        if self._j3_entry(dev):
+            return not ev.cplx and not ev.twisted
         if self.complex_device:
             return not (ev.twisted and not dev.twisted)
         return not ev.cplx and not ev.twisted
@@ -147,6 +175,10 @@ class TBDMAccumulator:
         ok = (dev is not None and dev.W == configs.configs.shape[0] and tuple(dev.nelec) == tuple(self._mol.nelec)
               and min(len(e) for e in self._electrons) > 0 and self._evaluator_in_scope(dev) and ev.device == dev.device)
         if not ok and self._route == "fused":
+            if self.three_body_device:
+                raise ValueError("route='fused' needs a Slater (x two-body x three-body Jastrow) wave function on one device handle whose "
+                                 "resident walkers are the configurations, and an orbital evaluator in scope on the same device: "
+                                 + (self.resident_scope(wf) or "the handle holds other walkers than the configurations"))
             if self.complex_device:
                 raise ValueError("route='fused' needs a Slater (x two-body Jastrow) wave function on one device handle whose resident "
                                  "walkers are the configurations, and an orbital evaluator on the same device that is twisted only if "
@@ -161,9 +193,18 @@ class TBDMAccumulator:
             return "the accumulator is bound to route='protocol'"
         dev, ev = self._device(wf), self.orbitals.dev
         if dev is None:
+            if self.three_body_device:
+                d3 = getattr(wf, "fused_device", lambda: None)()
+                if d3 is not None and getattr(d3, "has_j3", False) and (d3.cplx or d3.twisted):
+                    return "the three-body wave function is complex or twisted (pqa_tbdm_sweep_j3 takes real handles)"
+                if self.complex_device:
+                    return "the wave function is not a Slater (x two-body x three-body Jastrow) product on one device handle"
+                return "the wave function is not a real Slater (x two-body x three-body Jastrow) product on one device handle"
             if self.complex_device:
                 return "the wave function is not a Slater (x two-body Jastrow) product on one device handle"
             return "the wave function is not a real Slater (x two-body Jastrow) product on one device handle"
+        if self._j3_entry(dev) and (ev.cplx or ev.twisted):
+            return "the orbital evaluator is complex (a three-body wave function needs a real one)"
         if self.complex_device:
             if ev.twisted and not dev.twisted:
                 return "the orbital evaluator is twisted and the wave function's handle is not (its folded walkers have lost the wrap phase)"
@@ -223,9 +264,10 @@ class TBDMAccumulator:
                 ev.points(s, s, x[:, self._electrons[s]])
         else:
             for s in (0, 1):
-                ev.points_resident(s, dev, self._electrons[s], cplx=self._complex_entry(dev))
-        cplx = dev is not None and self._complex_entry(dev)
-        sweep = device_tbdm_sweep_c if cplx else device_tbdm_sweep
+                ev.points_resident(s, dev, self._electrons[s], cplx=self._complex_entry(dev), j3=self._j3_entry(dev))
+        j3 = dev is not None and self._j3_entry(dev)
+        cplx = dev is not None and not j3 and self._complex_entry(dev)
+        sweep = device_tbdm_sweep_j3 if j3 else device_tbdm_sweep_c if cplx else device_tbdm_sweep
         for sw in range(self._nsweeps if dev is not None else 0):  # the ratios stay on the device
             sweep(dev, ev, sw, self._spin_sector, pick[0][sw], pick[1][sw], self._ijkl, sw == 0, self._walker_chunk)
         for sw in range(self._nsweeps if dev is None else 0):

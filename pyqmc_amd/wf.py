@@ -1226,6 +1226,24 @@ def readonly_device_c(wf):
     return dev
 
 
+def readonly_device_j3(wf):
+    """``readonly_device`` with ``ThreeBodyJastrow`` admitted as a third factor (``pqa_obdm_sweeps_j3``, ``pqa_tbdm_sweep_j3``): ``wf``
+    must be exactly the handle's factors — a Slater factor, plus the two-body and the three-body Jastrow when the handle has them —
+    real and not twisted."""
+    factors = wf.wf_factors if isinstance(wf, MultiplyWF) else [wf]
+    kinds = [type(f) for f in factors]
+    if any(k not in (Slater, JastrowSpin, ThreeBodyJastrow) for k in kinds) or len(set(kinds)) != len(kinds) or Slater not in kinds:
+        return None
+    dev = wf.fused_device() if isinstance(wf, MultiplyWF) else getattr(wf, "_dev", None)
+    if dev is None or not hasattr(dev, "vmc_sweeps"):
+        return None
+    if not dev.has_slater or dev.cplx or dev.twisted:
+        return None
+    if bool(dev.has_j3) != (ThreeBodyJastrow in kinds) or bool(dev.has_jastrow) != (JastrowSpin in kinds):
+        return None
+    return dev
+
+
 LINEAR_JASTROW_KEYS = {"wf2acoeff", "wf2bcoeff"}  # the parameters the linear-Jastrow entry points vary
 
 

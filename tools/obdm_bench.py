@@ -1,7 +1,7 @@
 """One-body density matrix timing, fused route against protocol route: one JSON line per configuration, appended to
 profiles/obdm_bench.jsonl with --record.
 
-    python tools/obdm_bench.py [--configs C2,M4096,M,MD50,K222,C3,CX311] [--reps 7] [--routes fused,protocol] [--protocol-budget-s 90]
+    python tools/obdm_bench.py [--configs C2,M4096,M,MD50,K222,C3,CX311,C4,M4096J3] [--reps 7] [--routes fused,protocol] [--protocol-budget-s 90]
                                [--driver 16384,65536] [--driver-complex 8192,16384] [--record]
 
 Per configuration and route: wall-clock milliseconds per ``OBDMAccumulator.avg`` and per ``OBDMAccumulator.__call__`` (nsweeps = 5,
@@ -16,6 +16,8 @@ import); another checkout of the package (the parent commit's accumulator) is ti
 C3 (the twisted 8-atom diamond cell of tools/config_bench.py, 16 + 16 electrons) and CX311 (the complex 3 x 1 x 1 cell) are complex
 handles with the evaluator's orbitals from the k-point mean field: their fused route is ``complex_device=True`` (``pqa_obdm_sweeps_c``),
 and ``--driver-complex`` runs the {energy, rdm1_up} block on C3.
+C4 (BASELINE's 50 determinants x two-body x three-body water molecule, 2 048 walkers) and M4096J3 ((H2O)8 with ``jastrow3=True``, 4 096
+walkers) are three-body handles: their fused route is ``three_body_device=True`` (``pqa_obdm_sweeps_j3``).
 The kernel split comes from a ``rocprofv3 --kernel-trace --stats`` run of this tool with --routes fused --reps 3.
 """
 
@@ -58,6 +60,13 @@ def build(name):
         mol = systems.water()
         mf = systems.random_mf(mol, nvirt=6)
         return mol, helpers.gpu_wf(mol, mf, systems.random_determinants(mol, mf, 50)), 2048, open_orbitals(mol)
+    if name == "C4":
+        mol = systems.water()
+        mf = systems.random_mf(mol, nvirt=6)
+        return mol, helpers.gpu_wf3(mol, mf, systems.random_determinants(mol, mf, 50)), 2048, dict(open_orbitals(mol), three_body_device=True)
+    if name == "M4096J3":
+        mol = systems.water_cluster()
+        return mol, helpers.gpu_wf3(mol, systems.random_mf(mol)), 4096, dict(open_orbitals(mol), three_body_device=True)
     if name == "K222":  # diamond, 2 x 2 x 2 primitive cells: 8 k-points, four orbitals of each
         sup, wf = helpers.gpu_pbc_wf("k222")
         _, kmf = helpers.pbc_slater_case("k222")
@@ -107,7 +116,7 @@ def accumulator(pa, mol, kw, route):
     if route == "fused_device":
         extra["rng"] = "device"
     if route in ("protocol", "parent"):  # (the parent's accumulator does not know the keyword; the protocol route does not need it)
-        kw = {k: v for k, v in kw.items() if k != "complex_device"}
+        kw = {k: v for k, v in kw.items() if k not in ("complex_device", "three_body_device")}
     return pa.OBDMAccumulator(mol, spin=0, nsweeps=NSWEEPS, warmup=20, **kw, **extra)
 
 
@@ -156,7 +165,7 @@ def run(name, reps, routes, budget_s, small_protocol_ms):
     cplx = bool(kw.get("complex_device"))
     norb = sum(np.asarray(c).shape[1] for c in kw["orb_coeff"]) if "kpts" in kw else NORB
     rec = {"config": name, "walkers": W, "nelec": list(dev.nelec), "ndet": dev.ndet, "nsweeps": NSWEEPS, "norb": norb, "spin": 0,
-           "complex": cplx, "twisted": bool(dev.twisted)}
+           "complex": cplx, "twisted": bool(dev.twisted), "three_body": bool(dev.has_j3)}
     slow = [r for r in routes if r in ("protocol", "parent")]
     if W > 4096 and small_protocol_ms is not None and small_protocol_ms * (W / 4096) * 2 * (min(reps, 2) + 3) * 1e-3 > budget_s:
         for r in slow:
@@ -170,7 +179,7 @@ def run(name, reps, routes, budget_s, small_protocol_ms):
     for method in ("avg", "call"):
         for r, v in time_routes(pa, mol, wf, configs, kw, routes, reps, method).items():
             rec.setdefault(r, {})[method] = v
-    if any(r.startswith("fused") for r in routes) and not cplx:  # (the model is that of the real kernels)
+    if any(r.startswith("fused") for r in routes) and not cplx and not dev.has_j3:  # (the model is that of the real two-body kernels)
         rec["model_per_sweep"] = shapes_model(dev, W, dev.nelec[0], NORB)
     if "fused" in rec and "avg" in rec.get("protocol", {}):
         rec["speedup_avg"] = rec["protocol"]["avg"]["ms"] / rec["fused"]["avg"]["ms"]
