@@ -299,21 +299,52 @@ struct TpTuneGuard {
   ~TpTuneGuard() { memcpy(h->tp_tune, saved, sizeof(h->tp_tune)); }
 };
 
-// Scope of the read-only estimators (pqa_s2, pqa_symmetry, pqa_tbdm_sweep): a real, untwisted Slater handle without a three-body factor.
-inline int readonly_scope(pqa_handle* h, const char* fn) {
-  const char* why = !h->has_slater             ? "the handle has no Slater factor"
-                    : (h->cplx || h->twist)     ? "complex orbitals / twisted cell"
-                    : h->has_j3                 ? "three-body Jastrow factor"
-                                                : nullptr;
+// Scope of the read-only estimators (pqa_s2, pqa_symmetry, the density matrices): a real, untwisted Slater handle without a three-body
+// factor.  complex_ok admits complex and twisted handles, three_body_ok a three-body factor (the density matrices' _c / _j3 entries).
+inline int readonly_scope(pqa_handle* h, const char* fn, bool complex_ok = false, bool three_body_ok = false) {
+  const char* why = !h->has_slater                           ? "the handle has no Slater factor"
+                    : (!complex_ok && (h->cplx || h->twist)) ? "complex orbitals / twisted cell"
+                    : (!three_body_ok && h->has_j3)          ? "three-body Jastrow factor"
+                                                             : nullptr;
   if (why) FAIL(std::string(fn) + ": " + why + " (outside the fused scope: use the protocol route)");
   return 0;
 }
 
-// readonly_scope with a three-body factor admitted (pqa_obdm_sweeps_j3, pqa_tbdm_sweep_j3)
-inline int readonly_scope_j3(pqa_handle* h, const char* fn) {
-  const char* why = !h->has_slater ? "the handle has no Slater factor" : (h->cplx || h->twist) ? "complex orbitals / twisted cell" : nullptr;
-  if (why) FAIL(std::string(fn) + ": " + why + " (outside the fused scope: use the protocol route)");
+// What an entry of the density-matrix units (pqa_obdm, pqa_tbdm) is: its name (in messages) and whether it is the complex one (complex
+// / twisted handles and evaluators admitted, complex ratios and values, the _c kernels; else the real kernels), or the three-body one
+// (real handles with a three-body factor admitted: k_j3_moves ahead of the <., true> kernels; a handle without one runs exactly the
+// real entry's launches).
+struct DmEntry {
+  const char* name;
+  bool cx;
+  bool j3 = false;
+};
+
+// Scope of the entries that read wf's resident walkers for the evaluator ev: two handles on one device, wf in the read-only scope of
+// the entry with a state.  Real entries take real handles and evaluators.  The complex one takes complex and twisted ones too; a
+// twisted evaluator needs a twisted wf, whose walkers are unfolded (an untwisted periodic handle holds folded walkers, and the wrap
+// phase of phi_k(r_e) would be lost).  Leaves wf's walker-major arrays current.
+inline int dm_pair_scope(pqa_handle* h, pqa_handle* ev, const DmEntry& en) {
+  const std::string fn = en.name;
+  if (!h) return -2;
+  if (!ev) FAIL(fn + ": the orbital evaluator's handle is NULL");
+  TRY(sync_aos(h));
+  HIPCHK(hipSetDevice(h->device));
+  if (h->W == 0) FAIL(fn + ": state not initialised (call recompute)");
+  TRY(readonly_scope(h, en.name, en.cx, en.j3));
+  if (ev == h) FAIL(fn + ": the wave function and the orbital evaluator must be two handles");
+  if (en.cx) {
+    if (ev->twist && !h->twist)
+      FAIL(fn + ": twisted orbital evaluator on an untwisted handle, whose folded walkers have lost the wrap phase (use the protocol route)");
+  } else if (ev->cplx || ev->twist) FAIL(fn + ": complex orbital evaluator (outside the fused scope: use the protocol route)");
+  if (ev->device != h->device) FAIL(fn + ": the two handles are on different devices (use the protocol route)");
   return 0;
+}
+
+// The return code of a call on the evaluator's handle, with its error reported on the wave function's
+inline int on_ev(pqa_handle* h, pqa_handle* ev, int rc) {
+  if (rc) h->err = ev->err;
+  return rc;
 }
 
 // Scope of the linear-Jastrow units (pqa_correlated, pqa_variance): a real single-determinant Slater x two-body Jastrow handle whose

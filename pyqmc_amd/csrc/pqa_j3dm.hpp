@@ -34,6 +34,27 @@
 #pragma once
 #include "pqa_estim.hpp"
 
+// The two-body Jastrow terms of the density-matrix kernels (k_obdm_rt, k_tbdm_pairs and their complex variants).
+// sum_l bcoeff[l][col] b_l(|d|) of one electron pair (minimal image in a periodic cell)
+template <bool PBC>
+__device__ __forceinline__ double pair_u(const SysDev& S, double dx, double dy, double dz, int col, double irb) {
+  if (PBC) min_image_j(S, dx, dy, dz);
+  double u = 0.0;
+  jas_basis<true>(S, sqrt(dx * dx + dy * dy + dz * dz), irb, [&](int l, double v) { u += S.bcoeff[l * 3 + col] * v; });
+  return u;
+}
+// sum_I sum_k acoeff[I][k][spin] a_k(|q - R_I|)
+template <bool PBC>
+__device__ __forceinline__ double ion_u(const SysDev& S, double qx, double qy, double qz, int spin, double ira) {
+  double u = 0.0;
+  for (int I = 0; I < S.natom; ++I) {
+    double dx = qx - S.atom_xyz[3 * I], dy = qy - S.atom_xyz[3 * I + 1], dz = qz - S.atom_xyz[3 * I + 2];
+    if (PBC) min_image_j(S, dx, dy, dz);
+    jas_basis<false>(S, sqrt(dx * dx + dy * dy + dz * dz), ira, [&](int k, double v) { u += S.acoeff[(I * S.na + k) * 2 + spin] * v; });
+  }
+  return u;
+}
+
 struct J3dmLayout {
   int as, Ns, nrow, R, es;  // stride of an a-value row, of a row of M; rows of M; rows per group; entries of a row's E
   size_t o_al, o_E, o_M, o_P, ndbl, bytes;

@@ -21,7 +21,7 @@
 // counted from walker 0 (chunks hold whole slices), a slice's partial tile is one MFMA chain, and k_obdm_reduce adds the partial tiles
 // to the running sums one after the other in slice order, sweep after sweep.
 //
-// Complex and twisted handles, complex evaluators (pqa_obdm_sweeps_c; the same host driver, obdm_sweeps, with ObdmEntry::cx set):
+// Complex and twisted handles, complex evaluators (pqa_obdm_sweeps_c; the same host driver, obdm_sweeps, with DmEntry::cx set):
 //
 //   b[w][j]  = phi_j(r') / F,  F = sum_i |phi_i(r')|^2 / norb                     (complex / real)
 //   R[w][e]  = (sum_D w_D v_D(r')[e] / sum_D w_D) exp(A_e(r'))                     (complex; A_e real)
@@ -93,24 +93,6 @@ __device__ __forceinline__ void inverse_rows(const SysDev& S, const SlaterState&
     for (int off = 1; off < GS; off <<= 1) p += __shfl_xor(p, off, 64);
     if (act && j == 0) v[r] = p;
   }
-}
-
-template <bool PBC>
-__device__ __forceinline__ double pair_u(const SysDev& S, double dx, double dy, double dz, int col, double irb) {
-  if (PBC) min_image_j(S, dx, dy, dz);
-  double u = 0.0;
-  jas_basis<true>(S, sqrt(dx * dx + dy * dy + dz * dz), irb, [&](int l, double v) { u += S.bcoeff[l * 3 + col] * v; });
-  return u;
-}
-template <bool PBC>
-__device__ __forceinline__ double ion_u(const SysDev& S, double qx, double qy, double qz, int spin, double ira) {
-  double u = 0.0;
-  for (int I = 0; I < S.natom; ++I) {
-    double dx = qx - S.atom_xyz[3 * I], dy = qy - S.atom_xyz[3 * I + 1], dz = qz - S.atom_xyz[3 * I + 2];
-    if (PBC) min_image_j(S, dx, dy, dz);
-    jas_basis<false>(S, sqrt(dx * dx + dy * dy + dz * dz), ira, [&](int k, double v) { u += S.acoeff[(I * S.na + k) * 2 + spin] * v; });
-  }
-  return u;
 }
 
 // One wave per walker of the chunk.  phi_up / phi_dn [wc][nmo_s]: the wave function's orbitals at the walkers' r' (a spin without a
@@ -434,30 +416,11 @@ __global__ __launch_bounds__(256) void k_obdm_wscale(const double* __restrict__ 
 }
 
 
-// Scope of the entries that read wf's resident walkers for the evaluator ev (pqa_obdm_sweeps, pqa_obdm_sweeps_w,
-// pqa_dm_points_resident): two real handles on one device, wf in the read-only scope with a state, the listed electrons distinct.
-// spins: bit 0 / 1 set when an up / down electron is listed.  Leaves wf's walker-major arrays current.
-// cx (pqa_obdm_sweeps_c): complex and twisted handles and evaluators are admitted too; a twisted evaluator needs a twisted wf, whose
-// walkers are unfolded (an untwisted periodic handle holds folded walkers, and the wrap phase of phi_k(r_e) would be lost).
-// j3 (pqa_obdm_sweeps_j3): readonly_scope with a three-body factor admitted.
-int resident_scope(pqa_handle* h, pqa_handle* ev, int slot, const int32_t* es, int ne, const std::string& fn, int* spins_out, bool cx = false,
-                   bool j3 = false) {
-  if (!h) return -2;
-  if (!ev) FAIL(fn + ": the orbital evaluator's handle is NULL");
-  TRY(sync_aos(h));
-  HIPCHK(hipSetDevice(h->device));
-  if (h->W == 0) FAIL(fn + ": state not initialised (call recompute)");
-  if (cx) {
-    const char* why = !h->has_slater ? "the handle has no Slater factor" : h->has_j3 ? "three-body Jastrow factor" : nullptr;
-    if (why) FAIL(fn + ": " + why + " (outside the fused scope: use the protocol route)");
-  } else if (j3) TRY(readonly_scope_j3(h, fn.c_str()));
-  else TRY(readonly_scope(h, fn.c_str()));
-  if (ev == h) FAIL(fn + ": the wave function and the orbital evaluator must be two handles");
-  if (cx) {
-    if (ev->twist && !h->twist)
-      FAIL(fn + ": twisted orbital evaluator on an untwisted handle, whose folded walkers have lost the wrap phase (use the protocol route)");
-  } else if (ev->cplx || ev->twist) FAIL(fn + ": complex orbital evaluator (outside the fused scope: use the protocol route)");
-  if (ev->device != h->device) FAIL(fn + ": the two handles are on different devices (use the protocol route)");
+// Scope of the entries that read wf's resident walkers for the evaluator ev (the pqa_obdm_sweeps and pqa_dm_points_resident entries):
+// dm_pair_scope, a slot, the listed electrons distinct.  spins: bit 0 / 1 set when an up / down electron is listed.
+int resident_scope(pqa_handle* h, pqa_handle* ev, const DmEntry& en, int slot, const int32_t* es, int ne, int* spins_out) {
+  TRY(dm_pair_scope(h, ev, en));
+  const std::string fn = en.name;
   if (slot < 0 || slot > 1) FAIL(fn + ": slot must be 0 or 1");
   if (!es || ne < 1) FAIL(fn + ": no electron listed (use the protocol route)");
   int spins = 0;
@@ -470,11 +433,6 @@ int resident_scope(pqa_handle* h, pqa_handle* ev, int slot, const int32_t* es, i
   }
   *spins_out = spins;
   return 0;
-}
-
-int on_ev(pqa_handle* h, pqa_handle* ev, int rc) {  // (errors are reported on the wave function's handle)
-  if (rc) h->err = ev->err;
-  return rc;
 }
 
 // ev's orbitals of the slot's spin at the listed electrons of wf's resident walkers, into the slot's rows (what pqa_dm_points leaves
@@ -506,23 +464,25 @@ int resident_points(pqa_handle* h, pqa_handle* ev, int slot, const int32_t* es, 
   return 0;
 }
 
-// What an entry is: its name (in messages) and whether it is the complex one (complex / twisted handles and evaluators admitted, complex
-// ratios and value_mean, the kernels k_obdm_rt_c / k_obdm_mean_c; else the real kernels), or the three-body one (real handles with a
-// three-body factor admitted: k_j3_moves ahead of k_obdm_rt<., true>; a handle without one runs exactly the real entry's launches).
-struct ObdmEntry {
-  const char* name;
-  bool cx;
-  bool j3 = false;
-};
+// The kernel variants of a call: the real ones of a kind share a signature, the complex ones have their own.
+decltype(&k_obdm_rt<false, false>) obdm_rt_kernel(bool pbc, bool j3) {
+  return pbc ? (j3 ? k_obdm_rt<true, true> : k_obdm_rt<true, false>) : (j3 ? k_obdm_rt<false, true> : k_obdm_rt<false, false>);
+}
+decltype(&k_obdm_rt_c<false>) obdm_rt_c_kernel(bool pbc) { return pbc ? k_obdm_rt_c<true> : k_obdm_rt_c<false>; }
+decltype(&k_obdm_mean<false>) obdm_mean_kernel(bool wt) { return wt ? k_obdm_mean<true> : k_obdm_mean<false>; }
+decltype(&k_obdm_mean_c<false, false>) obdm_mean_c_kernel(bool wt, bool bi) {
+  return wt ? (bi ? k_obdm_mean_c<true, true> : k_obdm_mean_c<true, false>) : (bi ? k_obdm_mean_c<false, true> : k_obdm_mean_c<false, false>);
+}
 
-// pqa_obdm_sweeps (weights == NULL), pqa_obdm_sweeps_w (the mean mode with the walker weights `weights`) and pqa_obdm_sweeps_c (either)
-int obdm_sweeps(pqa_handle* h, pqa_handle* ev, const ObdmEntry& en, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
+// pqa_obdm_sweeps (weights == NULL), pqa_obdm_sweeps_w (the mean mode with the walker weights `weights`), pqa_obdm_sweeps_c and
+// pqa_obdm_sweeps_j3 (either)
+int obdm_sweeps(pqa_handle* h, pqa_handle* ev, const DmEntry& en, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
                 uint64_t seed, int mean, int first, int64_t chunk, double* ratio, int32_t* assign_out, double* value_mean, double* norm_mean,
                 const double* weights) {
   const std::string fn = en.name;
   const bool cx = en.cx;
   int spins = 0;
-  TRY(resident_scope(h, ev, slot, es, ne, fn, &spins, cx, en.j3));
+  TRY(resident_scope(h, ev, en, slot, es, ne, &spins));
   const bool j3 = en.j3 && h->has_j3;  // (the three-body differences are formed and added)
   const long W = h->W;
   const int N = h->N;
@@ -543,10 +503,11 @@ int obdm_sweeps(pqa_handle* h, pqa_handle* ev, const ObdmEntry& en, int slot, co
   const int D = h->ndet, cz = cx ? 2 : 1;  // (cz: doubles per ratio, weight and inverse-row entry)
   const size_t lds = ((size_t)3 * N + (1 + (size_t)cz) * ne + (D > 1 ? cz * D : 0) + cz * ((size_t)h->ndet_s[0] * h->nup + (size_t)h->ndet_s[1] * h->ndn)) * sizeof(double);
   if (lds > 160 * 1024) FAIL(fn + ": more determinants than one LDS block holds (use the protocol route)");
-  if (lds > 64 * 1024)
-    TRY(raise_lds_limit(h, cx   ? (h->S.pbc ? (const void*)k_obdm_rt_c<true> : (const void*)k_obdm_rt_c<false>)
-                           : j3 ? (h->S.pbc ? (const void*)k_obdm_rt<true, true> : (const void*)k_obdm_rt<false, true>)
-                                : (h->S.pbc ? (const void*)k_obdm_rt<true> : (const void*)k_obdm_rt<false>)));
+  const auto rt = obdm_rt_kernel(h->S.pbc, j3);
+  const auto rt_c = obdm_rt_c_kernel(h->S.pbc);
+  const auto mean_r = obdm_mean_kernel(weights != nullptr);
+  const auto mean_c = obdm_mean_c_kernel(weights != nullptr, oc != 0);
+  if (lds > 64 * 1024) TRY(raise_lds_limit(h, cx ? (const void*)rt_c : (const void*)rt));
   // scratch per walker: the point, the orbital rows of the spins present, and the ratios (per-walker mode) or the three panels and
   // the walker's share of a slice's partial tile (mean mode)
   const int nm0 = (spins & 1) ? h->nmo[0] : 0, nm1 = (spins & 2) ? h->nmo[1] : 0;
@@ -607,33 +568,15 @@ int obdm_sweeps(pqa_handle* h, pqa_handle* ev, const ObdmEntry& en, int slot, co
       TRY(check_launch(h, "k_obdm_gather"));
       if (nm0) TRY(launch_orb(h, 0, plain_points(d_pts, wc), wc, 1, (double*)h->b_orbphi[0].p));
       if (nm1) TRY(launch_orb(h, 1, plain_points(d_pts, wc), wc, 1, (double*)h->b_orbphi[1].p));
-      if (j3) {
-        TRY(launch_j3_moves<false>(h, lds_j3, (const double*)d_pts, d_es, ne, w0, wc, 0, 0, spins, (double*)h->b_j3dm.p));
-        if (h->S.pbc)
-          hipLaunchKernelGGL((k_obdm_rt<true, true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
-                             (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, (const double*)d.cfg.p,
-                             keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_B, d_N, (const double*)h->b_j3dm.p);
-        else
-          hipLaunchKernelGGL((k_obdm_rt<false, true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
-                             (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, (const double*)d.cfg.p,
-                             keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_B, d_N, (const double*)h->b_j3dm.p);
-      } else if (cx) {
-        if (h->S.pbc)
-          hipLaunchKernelGGL((k_obdm_rt_c<true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
-                             (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, hc, oc,
-                             (const double*)d.cfg.p, keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_Ti, d_B, d_Bi, d_N);
-        else
-          hipLaunchKernelGGL((k_obdm_rt_c<false>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
-                             (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, hc, oc,
-                             (const double*)d.cfg.p, keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_Ti, d_B, d_Bi, d_N);
-      } else if (h->S.pbc)
-        hipLaunchKernelGGL((k_obdm_rt<true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
-                           (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, (const double*)d.cfg.p,
-                           keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_B, d_N, (const double*)nullptr);
+      if (j3) TRY(launch_j3_moves<false>(h, lds_j3, (const double*)d_pts, d_es, ne, w0, wc, 0, 0, spins, (double*)h->b_j3dm.p));
+      if (cx)
+        hipLaunchKernelGGL(rt_c, dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
+                           (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, hc, oc,
+                           (const double*)d.cfg.p, keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_Ti, d_B, d_Bi, d_N);
       else
-        hipLaunchKernelGGL((k_obdm_rt<false>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
+        hipLaunchKernelGGL(rt, dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)h->b_orbphi[0].p,
                            (const double*)h->b_orbphi[1].p, (const double*)d_pts, d_es, ne, w0, (int)h->has_j2, spins, (const double*)d.cfg.p,
-                           keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_B, d_N, (const double*)nullptr);
+                           keep_row, keep_f, (const int*)asg, norb, d_R, d_T, d_B, d_N, j3 ? (const double*)h->b_j3dm.p : (const double*)nullptr);
       TRY(check_launch(h, "k_obdm_rt"));
       if (ratio)
         HIPCHK(hipMemcpyAsync(ratio + ((size_t)s * W + w0) * ne * cz, d_R, (size_t)wc * ne * cz * sizeof(double), hipMemcpyDefault, h->stream));
@@ -642,21 +585,13 @@ int obdm_sweeps(pqa_handle* h, pqa_handle* ev, const ObdmEntry& en, int slot, co
       if (mean) {
         const long nsl = (wc + kSlice - 1) / kSlice;
         const unsigned tiles = (unsigned)((norb + 15) / 16);
-        if (cx) {
-          const dim3 grid(tiles, tiles, (unsigned)nsl);
-          const double* wts = weights ? (const double*)d_wts + w0 : (const double*)nullptr;
-#define PQA_OBDM_MEAN_C(WT, BI) \
-  hipLaunchKernelGGL((k_obdm_mean_c<WT, BI>), grid, dim3(64), 0, ev->stream, (const double*)d_B, (const double*)d_Bi, (const double*)d_T, \
-                     (const double*)d_Ti, (const double*)d_N, wts, wc, norb, d_part)
-          if (weights) { if (oc) PQA_OBDM_MEAN_C(true, true); else PQA_OBDM_MEAN_C(true, false); }
-          else { if (oc) PQA_OBDM_MEAN_C(false, true); else PQA_OBDM_MEAN_C(false, false); }
-#undef PQA_OBDM_MEAN_C
-        } else if (weights)
-          hipLaunchKernelGGL(k_obdm_mean<true>, dim3(tiles, tiles, (unsigned)nsl), dim3(64), 0, ev->stream, (const double*)d_B, (const double*)d_T,
-                             (const double*)d_N, (const double*)d_wts + w0, wc, norb, d_part);
+        const dim3 grid(tiles, tiles, (unsigned)nsl);
+        const double* wts = weights ? (const double*)d_wts + w0 : (const double*)nullptr;
+        if (cx)
+          hipLaunchKernelGGL(mean_c, grid, dim3(64), 0, ev->stream, (const double*)d_B, (const double*)d_Bi, (const double*)d_T, (const double*)d_Ti,
+                             (const double*)d_N, wts, wc, norb, d_part);
         else
-          hipLaunchKernelGGL(k_obdm_mean<false>, dim3(tiles, tiles, (unsigned)nsl), dim3(64), 0, ev->stream, (const double*)d_B, (const double*)d_T,
-                             (const double*)d_N, (const double*)nullptr, wc, norb, d_part);
+          hipLaunchKernelGGL(mean_r, grid, dim3(64), 0, ev->stream, (const double*)d_B, (const double*)d_T, (const double*)d_N, wts, wc, norb, d_part);
         hipLaunchKernelGGL(k_obdm_reduce, dim3((unsigned)((npart + 255) / 256)), dim3(256), 0, ev->stream, (const double*)d_part, (long)npart,
                            nsl, (int)(s == 0 && w0 == 0), d_sums);
         TRY(on_ev(h, ev, check_launch(ev, "k_obdm_mean")));
@@ -694,7 +629,7 @@ int obdm_sweeps(pqa_handle* h, pqa_handle* ev, const ObdmEntry& en, int slot, co
 extern "C" int pqa_obdm_sweeps(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne, int nsweeps, const int32_t* assign,
                                uint64_t seed, int mean, int first, int64_t chunk, double* ratio, int32_t* assign_out, double* value_mean,
                                double* norm_mean) {
-  return obdm_sweeps(h, ev, ObdmEntry{"pqa_obdm_sweeps", false}, slot, es, ne, nsweeps, assign, seed, mean, first, chunk, ratio, assign_out,
+  return obdm_sweeps(h, ev, DmEntry{"pqa_obdm_sweeps", false}, slot, es, ne, nsweeps, assign, seed, mean, first, chunk, ratio, assign_out,
                      value_mean, norm_mean, nullptr);
 }
 
@@ -704,7 +639,7 @@ extern "C" int pqa_obdm_sweeps_w(pqa_handle_t* h, pqa_handle_t* ev, int slot, co
                                  double* norm_mean) {
   if (!h) return -2;
   if (!weights) FAIL("pqa_obdm_sweeps_w: weights is NULL");
-  return obdm_sweeps(h, ev, ObdmEntry{"pqa_obdm_sweeps_w", false}, slot, es, ne, nsweeps, assign, seed, 1, 1, chunk, nullptr, assign_out,
+  return obdm_sweeps(h, ev, DmEntry{"pqa_obdm_sweeps_w", false}, slot, es, ne, nsweeps, assign, seed, 1, 1, chunk, nullptr, assign_out,
                      value_mean, norm_mean, weights);
 }
 
@@ -715,7 +650,7 @@ extern "C" int pqa_obdm_sweeps_c(pqa_handle_t* h, pqa_handle_t* ev, int slot, co
                                  double* value_mean, double* norm_mean) {
   if (!h) return -2;
   if (weights && !mean) FAIL("pqa_obdm_sweeps_c: walker weights need the mean mode");
-  return obdm_sweeps(h, ev, ObdmEntry{"pqa_obdm_sweeps_c", true}, slot, es, ne, nsweeps, assign, seed, mean, first, chunk, ratio, assign_out,
+  return obdm_sweeps(h, ev, DmEntry{"pqa_obdm_sweeps_c", true}, slot, es, ne, nsweeps, assign, seed, mean, first, chunk, ratio, assign_out,
                      value_mean, norm_mean, weights);
 }
 
@@ -726,36 +661,33 @@ extern "C" int pqa_obdm_sweeps_j3(pqa_handle_t* h, pqa_handle_t* ev, int slot, c
                                   double* value_mean, double* norm_mean) {
   if (!h) return -2;
   if (weights && !mean) FAIL("pqa_obdm_sweeps_j3: walker weights need the mean mode");
-  return obdm_sweeps(h, ev, ObdmEntry{"pqa_obdm_sweeps_j3", false, true}, slot, es, ne, nsweeps, assign, seed, mean, first, chunk, ratio,
+  return obdm_sweeps(h, ev, DmEntry{"pqa_obdm_sweeps_j3", false, true}, slot, es, ne, nsweeps, assign, seed, mean, first, chunk, ratio,
                      assign_out, value_mean, norm_mean, weights);
 }
 
-// pqa_dm_points with the listed electrons' coordinates gathered from wf's resident walkers, device to device
-extern "C" int pqa_dm_points_resident(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne) {
+// pqa_dm_points with the listed electrons' coordinates gathered from wf's resident walkers, device to device, in the scope of the entry
+static int dm_points_resident(pqa_handle* h, pqa_handle* ev, const DmEntry& en, int slot, const int32_t* es, int ne) {
+  const std::string fn = en.name;
   int spins = 0;
-  TRY(resident_scope(h, ev, slot, es, ne, "pqa_dm_points_resident", &spins));
-  if (ev->dm[slot].n <= 0) FAIL("pqa_dm_points_resident: no auxiliary walkers in the slot (call pqa_dm_walk: it names the slot's spin)");
-  if (ev->nmo[ev->dm[slot].spin] <= 0) FAIL("pqa_dm_points_resident: the evaluator has no orbitals of the walk's spin");
+  TRY(resident_scope(h, ev, en, slot, es, ne, &spins));
+  if (ev->dm[slot].n <= 0) FAIL(fn + ": no auxiliary walkers in the slot (call pqa_dm_walk: it names the slot's spin)");
+  if (ev->nmo[ev->dm[slot].spin] <= 0) FAIL(fn + ": the evaluator has no orbitals of the walk's spin");
   return resident_points(h, ev, slot, es, ne);
+}
+
+extern "C" int pqa_dm_points_resident(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne) {
+  return dm_points_resident(h, ev, DmEntry{"pqa_dm_points_resident", false}, slot, es, ne);
 }
 
 // pqa_dm_points_resident for complex and twisted handles and complex evaluators (pqa_obdm_sweeps_c's scope: a twisted evaluator needs
 // a twisted wf, whose walkers are unfolded, so that the evaluator's orbital kernel puts the wrap phase on phi_k(r_e))
 extern "C" int pqa_dm_points_resident_c(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne) {
-  int spins = 0;
-  TRY(resident_scope(h, ev, slot, es, ne, "pqa_dm_points_resident_c", &spins, true));
-  if (ev->dm[slot].n <= 0) FAIL("pqa_dm_points_resident_c: no auxiliary walkers in the slot (call pqa_dm_walk: it names the slot's spin)");
-  if (ev->nmo[ev->dm[slot].spin] <= 0) FAIL("pqa_dm_points_resident_c: the evaluator has no orbitals of the walk's spin");
-  return resident_points(h, ev, slot, es, ne);
+  return dm_points_resident(h, ev, DmEntry{"pqa_dm_points_resident_c", true}, slot, es, ne);
 }
 
 // pqa_dm_points_resident in the scope of pqa_obdm_sweeps_j3 / pqa_tbdm_sweep_j3 (a three-body factor admitted)
 extern "C" int pqa_dm_points_resident_j3(pqa_handle_t* h, pqa_handle_t* ev, int slot, const int32_t* es, int ne) {
-  int spins = 0;
-  TRY(resident_scope(h, ev, slot, es, ne, "pqa_dm_points_resident_j3", &spins, false, true));
-  if (ev->dm[slot].n <= 0) FAIL("pqa_dm_points_resident_j3: no auxiliary walkers in the slot (call pqa_dm_walk: it names the slot's spin)");
-  if (ev->nmo[ev->dm[slot].spin] <= 0) FAIL("pqa_dm_points_resident_j3: the evaluator has no orbitals of the walk's spin");
-  return resident_points(h, ev, slot, es, ne);
+  return dm_points_resident(h, ev, DmEntry{"pqa_dm_points_resident_j3", false, true}, slot, es, ne);
 }
 
 // Weighted walker mean of one of ev's per-walker accumulators (pqa_dm_fetch's `which`), times scale

@@ -21,7 +21,7 @@
 // do here (a 16-column tile would carry 2 live columns); lanes run over the inverse's rows with a butterfly per row instead.
 // The ratios of a walker chunk stay on the device: k_tbdm_acc (pqa_dm.hpp) consumes them on the evaluator's stream, ordered by events.
 //
-// Complex and twisted handles, complex evaluators (pqa_tbdm_sweep_c; the same host driver, tbdm_sweep, with TbdmEntry::cx set): the
+// Complex and twisted handles, complex evaluators (pqa_tbdm_sweep_c; the same host driver, tbdm_sweep, with DmEntry::cx set): the
 // same formulas with everything complex except the Jastrow part,
 //   v_s,D(q)[i] = sum_k phi^s_{occ_D[k]}(q) T^s_D[i][k]                      (complex x complex, no conjugation; T interleaved)
 //   S_ab = sum_D w_D S_ab(D) / sum_D w_D,   w_D = det_weight_c               (complex quotient; S_aa an exact 0 + 0i)
@@ -78,26 +78,6 @@ __device__ __forceinline__ void inverse_products(const SysDev& S, const SlaterSt
       if (NP == 2) v[(size_t)r * NP + 1] = p1;
     }
   }
-}
-
-// sum_l bcoeff[l][col] b_l(|d|) of one electron pair (minimal image in a periodic cell)
-template <bool PBC>
-__device__ __forceinline__ double pair_u(const SysDev& S, double dx, double dy, double dz, int col, double irb) {
-  if (PBC) min_image_j(S, dx, dy, dz);
-  double u = 0.0;
-  jas_basis<true>(S, sqrt(dx * dx + dy * dy + dz * dz), irb, [&](int l, double v) { u += S.bcoeff[l * 3 + col] * v; });
-  return u;
-}
-// sum_I sum_k acoeff[I][k][spin] a_k(|q - R_I|)
-template <bool PBC>
-__device__ __forceinline__ double ion_u(const SysDev& S, double qx, double qy, double qz, int spin, double ira) {
-  double u = 0.0;
-  for (int I = 0; I < S.natom; ++I) {
-    double dx = qx - S.atom_xyz[3 * I], dy = qy - S.atom_xyz[3 * I + 1], dz = qz - S.atom_xyz[3 * I + 2];
-    if (PBC) min_image_j(S, dx, dy, dz);
-    jas_basis<false>(S, sqrt(dx * dx + dy * dy + dz * dz), ira, [&](int k, double v) { u += S.acoeff[(I * S.na + k) * 2 + spin] * v; });
-  }
-  return u;
 }
 
 // One wave per walker of the chunk.  phi1 [wc][nmo_s1]: spin-s1 orbitals at r1, phi2 [wc][nmo_s2]: spin-s2 orbitals at r2;
@@ -356,37 +336,19 @@ __global__ __launch_bounds__(64) void k_tbdm_pairs_c(SysDev S, SlaterState st, J
   }
 }
 
-// What an entry is: its name (in messages) and whether it is the complex one (complex / twisted handles and evaluators admitted,
-// interleaved complex ratios, the kernel k_tbdm_pairs_c; else k_tbdm_pairs on two real handles), or the three-body one (real handles
-// with a three-body factor admitted: k_j3_moves ahead of k_tbdm_pairs<., true>; a handle without one runs the real entry's launches).
-struct TbdmEntry {
-  const char* name;
-  bool cx;
-  bool j3 = false;
-};
+// The kernel variant of a call: the real ones share a signature, the complex ones have their own.
+decltype(&k_tbdm_pairs<false, false>) tbdm_pairs_kernel(bool pbc, bool j3) {
+  return pbc ? (j3 ? k_tbdm_pairs<true, true> : k_tbdm_pairs<true, false>) : (j3 ? k_tbdm_pairs<false, true> : k_tbdm_pairs<false, false>);
+}
+decltype(&k_tbdm_pairs_c<false>) tbdm_pairs_c_kernel(bool pbc) { return pbc ? k_tbdm_pairs_c<true> : k_tbdm_pairs_c<false>; }
 
-// pqa_tbdm_sweep (cx = false) and pqa_tbdm_sweep_c
-int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const TbdmEntry& en, int k, int spin_a, int spin_b, const int32_t* assign_a,
+// pqa_tbdm_sweep, pqa_tbdm_sweep_c and pqa_tbdm_sweep_j3
+int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const DmEntry& en, int k, int spin_a, int spin_b, const int32_t* assign_a,
                const int32_t* assign_b, const int32_t* ijkl, int ntuple, int first, int64_t chunk, double* ratio) {
+  TRY(dm_pair_scope(h, ev, en));
   const std::string fn = en.name;
   const bool cx = en.cx;
-  if (!h) return -2;
-  if (!ev) FAIL(fn + ": the orbital evaluator's handle is NULL");
-  TRY(sync_aos(h));
-  HIPCHK(hipSetDevice(h->device));
-  if (h->W == 0) FAIL(fn + ": state not initialised (call recompute)");
-  if (cx) {
-    const char* why = !h->has_slater ? "the handle has no Slater factor" : h->has_j3 ? "three-body Jastrow factor" : nullptr;
-    if (why) FAIL(fn + ": " + why + " (outside the fused scope: use the protocol route)");
-  } else if (en.j3) TRY(readonly_scope_j3(h, en.name));
-  else TRY(readonly_scope(h, en.name));
   const bool j3 = en.j3 && h->has_j3;  // (the three-body differences are formed and added)
-  if (ev == h) FAIL(fn + ": the wave function and the orbital evaluator must be two handles");
-  if (cx) {
-    if (ev->twist && !h->twist)
-      FAIL(fn + ": twisted orbital evaluator on an untwisted handle, whose folded walkers have lost the wrap phase (use the protocol route)");
-  } else if (ev->cplx || ev->twist) FAIL(fn + ": complex orbital evaluator (outside the fused scope: use the protocol route)");
-  if (ev->device != h->device) FAIL(fn + ": the two handles are on different devices (use the protocol route)");
   if (spin_a < 0 || spin_a > 1 || spin_b < 0 || spin_b > 1) FAIL(fn + ": spins must be 0 or 1");
   if (!assign_a || !assign_b) FAIL(fn + ": assign_a / assign_b is NULL");
   const bool accumulate = ijkl != nullptr || ntuple != 0;
@@ -400,10 +362,6 @@ int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const TbdmEntry& en, int k, int sp
   if (k < 0 || k >= da.nkeep || k >= db.nkeep) FAIL(fn + ": sample was not kept by pqa_dm_walk");
   for (long w = 0; w < W; ++w)
     if (assign_a[w] < 0 || assign_a[w] >= da.n || assign_b[w] < 0 || assign_b[w] >= db.n) FAIL(fn + ": assignment outside the auxiliary walkers");
-  auto on_ev = [&](int rc) {  // (errors are reported on the wave function's handle)
-    if (rc) h->err = ev->err;
-    return rc;
-  };
   // na2 / nb2: the doubles of an orbital row of the evaluator ([re block | im block] when it is complex), na / nb: its orbitals;
   // cz: doubles per ratio
   const int hc = h->cplx ? 1 : 0, oc = ev->cplx ? 1 : 0, cz = cx ? 2 : 1;
@@ -412,14 +370,14 @@ int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const TbdmEntry& en, int k, int sp
   if (accumulate) {
     if (da.ncfg != W * nea || db.ncfg != W * neb) FAIL(fn + ": pqa_dm_points was called with other numbers of points (the handle's walkers must be the configurations)");
     if (lds_acc > 64 * 1024) FAIL(fn + ": orbital basis too large for the per-walker LDS tiles");
-    TRY(on_ev(dm_prepare(ev, W, ntuple, cx ? 1 : 0, first, na, nb)));
-    TRY(on_ev(ensure(ev, ev->dm_ijkl, (size_t)4 * ntuple * sizeof(int))));
-    TRY(on_ev(copy_in(ev, ev->dm_ijkl.p, ijkl, (size_t)4 * ntuple * sizeof(int))));
+    TRY(on_ev(h, ev, dm_prepare(ev, W, ntuple, cx ? 1 : 0, first, na, nb)));
+    TRY(on_ev(h, ev, ensure(ev, ev->dm_ijkl, (size_t)4 * ntuple * sizeof(int))));
+    TRY(on_ev(h, ev, copy_in(ev, ev->dm_ijkl.p, ijkl, (size_t)4 * ntuple * sizeof(int))));
   }
-  TRY(on_ev(ensure(ev, ev->dm_assign[0], (size_t)W * sizeof(int))));
-  TRY(on_ev(ensure(ev, ev->dm_assign[1], (size_t)W * sizeof(int))));
-  TRY(on_ev(copy_in(ev, ev->dm_assign[0].p, assign_a, (size_t)W * sizeof(int))));
-  TRY(on_ev(copy_in(ev, ev->dm_assign[1].p, assign_b, (size_t)W * sizeof(int))));
+  TRY(on_ev(h, ev, ensure(ev, ev->dm_assign[0], (size_t)W * sizeof(int))));
+  TRY(on_ev(h, ev, ensure(ev, ev->dm_assign[1], (size_t)W * sizeof(int))));
+  TRY(on_ev(h, ev, copy_in(ev, ev->dm_assign[0].p, assign_a, (size_t)W * sizeof(int))));
+  TRY(on_ev(h, ev, copy_in(ev, ev->dm_assign[1].p, assign_b, (size_t)W * sizeof(int))));
   // scratch per walker: the ratios, the orbital rows at the two points, the points
   const bool same = spin_a == spin_b;
   const int nm1 = h->nmo[spin_a], nm2 = h->nmo[spin_b];
@@ -429,7 +387,7 @@ int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const TbdmEntry& en, int k, int sp
     TRY(j3_moves_lds<true>(h, fn, same ? nea : nea + neb, &lds_j3));
     TRY(ensure(h, h->b_j3dm, (size_t)Wc * nea * neb * sizeof(double)));
   }
-  TRY(on_ev(ensure(ev, ev->dm_ratio, (size_t)Wc * nea * neb * cz * sizeof(double))));
+  TRY(on_ev(h, ev, ensure(ev, ev->dm_ratio, (size_t)Wc * nea * neb * cz * sizeof(double))));
   TRY(ensure(h, h->b_tbpts, (size_t)6 * Wc * sizeof(double)));
   TRY(ensure(h, h->b_orbphi[0], (size_t)Wc * (same ? 2 * nm1 : nm1) * sizeof(double)));
   if (!same) TRY(ensure(h, h->b_orbphi[1], (size_t)Wc * nm2 * sizeof(double)));
@@ -437,10 +395,9 @@ int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const TbdmEntry& en, int k, int sp
   const size_t lds = ((size_t)3 * N + nea + neb + (D > 1 ? cz * D : 0) + cz * ((size_t)h->ndet_s[spin_a] * nea * (same ? 2 : 1) +
                       (same ? 0 : (size_t)h->ndet_s[spin_b] * neb))) * sizeof(double);
   if (lds > 160 * 1024) FAIL(fn + ": more determinants than one LDS block holds (use the protocol route)");
-  if (lds > 64 * 1024)
-    TRY(raise_lds_limit(h, cx   ? (h->S.pbc ? (const void*)k_tbdm_pairs_c<true> : (const void*)k_tbdm_pairs_c<false>)
-                           : j3 ? (h->S.pbc ? (const void*)k_tbdm_pairs<true, true> : (const void*)k_tbdm_pairs<false, true>)
-                                : (h->S.pbc ? (const void*)k_tbdm_pairs<true> : (const void*)k_tbdm_pairs<false>)));
+  const auto pairs = tbdm_pairs_kernel(h->S.pbc, j3);
+  const auto pairs_c = tbdm_pairs_c_kernel(h->S.pbc);
+  if (lds > 64 * 1024) TRY(raise_lds_limit(h, cx ? (const void*)pairs_c : (const void*)pairs));
   if (!h->tb_ev[0])
     for (hipEvent_t& e : h->tb_ev) TRY(new_event(h, &e, hipEventDisableTiming));
   const hipEvent_t produced = h->tb_ev[0], consumed = h->tb_ev[1];
@@ -465,27 +422,14 @@ int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const TbdmEntry& en, int k, int sp
       TRY(launch_orb(h, spin_a, plain_points(d_pts, wc), wc, 1, phi1));
       TRY(launch_orb(h, spin_b, plain_points(d_pts + 3 * wc, wc), wc, 1, phi2));
     }
-    if (j3) {
-      TRY(launch_j3_moves<true>(h, lds_j3, (const double*)d_pts, nullptr, 0, w0, wc, spin_a, spin_b, 3, (double*)h->b_j3dm.p));
-      if (h->S.pbc)
-        hipLaunchKernelGGL((k_tbdm_pairs<true, true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)phi1,
-                           (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, d_R, (const double*)h->b_j3dm.p);
-      else
-        hipLaunchKernelGGL((k_tbdm_pairs<false, true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)phi1,
-                           (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, d_R, (const double*)h->b_j3dm.p);
-    } else if (cx) {
-      if (h->S.pbc)
-        hipLaunchKernelGGL((k_tbdm_pairs_c<true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)phi1,
-                           (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, hc, d_R);
-      else
-        hipLaunchKernelGGL((k_tbdm_pairs_c<false>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)phi1,
-                           (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, hc, d_R);
-    } else if (h->S.pbc)
-      hipLaunchKernelGGL((k_tbdm_pairs<true>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)phi1,
-                         (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, d_R, (const double*)nullptr);
+    if (j3) TRY(launch_j3_moves<true>(h, lds_j3, (const double*)d_pts, nullptr, 0, w0, wc, spin_a, spin_b, 3, (double*)h->b_j3dm.p));
+    if (cx)
+      hipLaunchKernelGGL(pairs_c, dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)phi1, (const double*)phi2,
+                         (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, hc, d_R);
     else
-      hipLaunchKernelGGL((k_tbdm_pairs<false>), dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)phi1,
-                         (const double*)phi2, (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, d_R, (const double*)nullptr);
+      hipLaunchKernelGGL(pairs, dim3((unsigned)wc), dim3(64), lds, h->stream, h->S, h->st, h->js, (const double*)phi1, (const double*)phi2,
+                         (const double*)d_pts, w0, wc, spin_a, spin_b, (int)h->has_j2, d_R,
+                         j3 ? (const double*)h->b_j3dm.p : (const double*)nullptr);
     TRY(check_launch(h, "k_tbdm_pairs"));
     if (ratio)
       HIPCHK(hipMemcpyAsync(ratio + (size_t)w0 * nea * neb * cz, d_R, (size_t)wc * nea * neb * cz * sizeof(double), hipMemcpyDefault, h->stream));
@@ -499,7 +443,7 @@ int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const TbdmEntry& en, int k, int sp
                          cx ? 1 : 0, oc, nea, neb, na, nb, (const int*)ev->dm_ijkl.p, ntuple, first,
                          (double*)ev->dm_val.p + (size_t)w0 * ntuple * cz, (double*)ev->dm_norm[0].p + (size_t)w0 * na,
                          (double*)ev->dm_norm[1].p + (size_t)w0 * nb);
-      TRY(on_ev(check_launch(ev, "k_tbdm_acc")));
+      TRY(on_ev(h, ev, check_launch(ev, "k_tbdm_acc")));
     }
     HIPCHK(hipEventRecord(consumed, ev->stream));
   }
@@ -511,19 +455,19 @@ int tbdm_sweep(pqa_handle* h, pqa_handle* ev, const TbdmEntry& en, int k, int sp
 
 extern "C" int pqa_tbdm_sweep(pqa_handle_t* h, pqa_handle_t* ev, int k, int spin_a, int spin_b, const int32_t* assign_a,
                               const int32_t* assign_b, const int32_t* ijkl, int ntuple, int first, int64_t chunk, double* ratio) {
-  return tbdm_sweep(h, ev, TbdmEntry{"pqa_tbdm_sweep", false}, k, spin_a, spin_b, assign_a, assign_b, ijkl, ntuple, first, chunk, ratio);
+  return tbdm_sweep(h, ev, DmEntry{"pqa_tbdm_sweep", false}, k, spin_a, spin_b, assign_a, assign_b, ijkl, ntuple, first, chunk, ratio);
 }
 
 // pqa_tbdm_sweep for complex and twisted wave-function handles and complex evaluators (real ones are taken too): ratio (W, nea, neb) is
 // interleaved complex, and the evaluator's value accumulator is complex (pqa_dm_fetch as after pqa_tbdm_accumulate with complex ratios).
 extern "C" int pqa_tbdm_sweep_c(pqa_handle_t* h, pqa_handle_t* ev, int k, int spin_a, int spin_b, const int32_t* assign_a,
                                 const int32_t* assign_b, const int32_t* ijkl, int ntuple, int first, int64_t chunk, double* ratio) {
-  return tbdm_sweep(h, ev, TbdmEntry{"pqa_tbdm_sweep_c", true}, k, spin_a, spin_b, assign_a, assign_b, ijkl, ntuple, first, chunk, ratio);
+  return tbdm_sweep(h, ev, DmEntry{"pqa_tbdm_sweep_c", true}, k, spin_a, spin_b, assign_a, assign_b, ijkl, ntuple, first, chunk, ratio);
 }
 
 // pqa_tbdm_sweep for real handles with a three-body Jastrow factor (handles without one are taken too and give pqa_tbdm_sweep's bits):
 // k_j3_moves forms the three-body difference of every pair of a walker chunk ahead of k_tbdm_pairs<., true>.
 extern "C" int pqa_tbdm_sweep_j3(pqa_handle_t* h, pqa_handle_t* ev, int k, int spin_a, int spin_b, const int32_t* assign_a,
                                  const int32_t* assign_b, const int32_t* ijkl, int ntuple, int first, int64_t chunk, double* ratio) {
-  return tbdm_sweep(h, ev, TbdmEntry{"pqa_tbdm_sweep_j3", false, true}, k, spin_a, spin_b, assign_a, assign_b, ijkl, ntuple, first, chunk, ratio);
+  return tbdm_sweep(h, ev, DmEntry{"pqa_tbdm_sweep_j3", false, true}, k, spin_a, spin_b, assign_a, assign_b, ijkl, ntuple, first, chunk, ratio);
 }

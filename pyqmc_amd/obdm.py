@@ -50,7 +50,7 @@ from . import _ffi
 from . import pbc as _pbc
 from .configs import OpenConfigs, PeriodicConfigs
 from .systems import initial_guess
-from .wf import DeviceWF, readonly_device, readonly_device_c, readonly_device_j3
+from .wf import DeviceWF, readonly_device
 
 ROUTES = (None, "fused", "protocol")
 
@@ -232,14 +232,17 @@ def sample_onebody(configs, orbitals, nsamples=1, tstep=0.5, spin=0):
     return acc, snaps, [orbitals.mos(k, spin) for k in kept]
 
 
-def device_obdm_sweeps(dev, ev, electrons, nsweeps, assign=None, seed=0, mean=False, first=True, walker_chunk=0, with_ratios=False):
-    """``pqa_obdm_sweeps``: the one-body estimator of wave-function handle ``dev`` over the first ``nsweeps`` kept samples of slot 0
-    of the evaluator ``ev`` (an ``OrbitalEvaluator``) for the listed ``electrons``.  ``assign`` (nsweeps, W): the auxiliary walker of
-    every configuration, or None: drawn on the device from ``seed``.  Returns a dict: ``assign`` (the assignments used), ``ratio``
-    (nsweeps, W, nelec) with ``with_ratios``, and with ``mean`` the walker means ``value`` (norb, norb) and ``norm`` (norb,) already
-    divided by ``nsweeps``; without ``mean`` the evaluator's per-configuration accumulators hold the sums (``ev.fetch``)."""
+def _sweeps(entry, dev, ev, electrons, nsweeps, assign, seed, mean, first, walker_chunk, with_ratios, weights):
+    """One call of the library entry ``entry`` (``pqa_obdm_sweeps``, ``_w``, ``_c`` or ``_j3``) behind the ``device_obdm_sweeps*``
+    helpers: the electron list, the checked weights and assignments and the outputs (complex for ``_c``) are prepared once, and the
+    argument list is the named entry's (``_c`` and ``_j3`` share one; ``_w`` is the mean mode alone and has no ratio output)."""
     es = np.ascontiguousarray(np.asarray(electrons).ravel(), dtype=np.int32)
     W, norb = dev.W, ev.norb
+    dtype = complex if entry == "pqa_obdm_sweeps_c" else float
+    if weights is not None or entry == "pqa_obdm_sweeps_w":  # (the weighted entry refuses None)
+        if not mean:
+            raise ValueError("walker weights need the mean mode")
+        weights = _ffi.walker_weights(weights, W)
     out = {}
     if assign is not None:
         assign = np.ascontiguousarray(assign, dtype=np.int32)
@@ -248,33 +251,35 @@ def device_obdm_sweeps(dev, ev, electrons, nsweeps, assign=None, seed=0, mean=Fa
         out["assign"] = assign
     else:
         out["assign"] = np.empty((nsweeps, W), dtype=np.int32)
-    if with_ratios:
-        out["ratio"] = np.empty((nsweeps, W, len(es)))
+    if with_ratios and entry != "pqa_obdm_sweeps_w":
+        out["ratio"] = np.empty((nsweeps, W, len(es)), dtype=dtype)
     if mean:
-        out["value"], out["norm"] = np.empty((norb, norb)), np.empty(norb)
-    dev.call("pqa_obdm_sweeps", ev.dev._h, 0, _ffi.ptr(es), len(es), int(nsweeps), _ffi.ptr(assign), int(seed), int(mean), int(first),
-             int(walker_chunk), _ffi.ptr(out.get("ratio")), None if assign is not None else _ffi.ptr(out["assign"]), _ffi.ptr(out.get("value")),
-             _ffi.ptr(out.get("norm")))
+        out["value"], out["norm"] = np.empty((norb, norb), dtype=dtype), np.empty(norb)
+    head = (ev.dev._h, 0, _ffi.ptr(es), len(es), int(nsweeps), _ffi.ptr(assign), int(seed))
+    tail = (None if assign is not None else _ffi.ptr(out["assign"]), _ffi.ptr(out.get("value")), _ffi.ptr(out.get("norm")))
+    if entry == "pqa_obdm_sweeps":
+        args = head + (int(mean), int(first), int(walker_chunk), _ffi.ptr(out.get("ratio"))) + tail
+    elif entry == "pqa_obdm_sweeps_w":
+        args = head + (int(walker_chunk), _ffi.ptr(weights)) + tail
+    else:
+        args = head + (int(mean), int(first), int(walker_chunk), _ffi.ptr(weights), _ffi.ptr(out.get("ratio"))) + tail
+    dev.call(entry, *args)
     return out
+
+
+def device_obdm_sweeps(dev, ev, electrons, nsweeps, assign=None, seed=0, mean=False, first=True, walker_chunk=0, with_ratios=False):
+    """``pqa_obdm_sweeps``: the one-body estimator of wave-function handle ``dev`` over the first ``nsweeps`` kept samples of slot 0
+    of the evaluator ``ev`` (an ``OrbitalEvaluator``) for the listed ``electrons``.  ``assign`` (nsweeps, W): the auxiliary walker of
+    every configuration, or None: drawn on the device from ``seed``.  Returns a dict: ``assign`` (the assignments used), ``ratio``
+    (nsweeps, W, nelec) with ``with_ratios``, and with ``mean`` the walker means ``value`` (norb, norb) and ``norm`` (norb,) already
+    divided by ``nsweeps``; without ``mean`` the evaluator's per-configuration accumulators hold the sums (``ev.fetch``)."""
+    return _sweeps("pqa_obdm_sweeps", dev, ev, electrons, nsweeps, assign, seed, mean, first, walker_chunk, with_ratios, None)
 
 
 def device_obdm_sweeps_w(dev, ev, electrons, nsweeps, weights, assign=None, seed=0, walker_chunk=0):
     """``pqa_obdm_sweeps_w``: the mean mode of ``device_obdm_sweeps`` with the walker ``weights`` (W,): ``value`` and ``norm`` are
     sum_s sum_w w_w (...) / (nsweeps sum_w w_w).  Returns a dict with ``assign``, ``value`` and ``norm``."""
-    es = np.ascontiguousarray(np.asarray(electrons).ravel(), dtype=np.int32)
-    W, norb = dev.W, ev.norb
-    w = _ffi.walker_weights(weights, W)
-    out = {"value": np.empty((norb, norb)), "norm": np.empty(norb)}
-    if assign is not None:
-        assign = np.ascontiguousarray(assign, dtype=np.int32)
-        if assign.shape != (nsweeps, W):
-            raise ValueError(f"assignments ({nsweeps}, {W}) expected, got {assign.shape}")
-        out["assign"] = assign
-    else:
-        out["assign"] = np.empty((nsweeps, W), dtype=np.int32)
-    dev.call("pqa_obdm_sweeps_w", ev.dev._h, 0, _ffi.ptr(es), len(es), int(nsweeps), _ffi.ptr(assign), int(seed), int(walker_chunk),
-             _ffi.ptr(w), None if assign is not None else _ffi.ptr(out["assign"]), _ffi.ptr(out["value"]), _ffi.ptr(out["norm"]))
-    return out
+    return _sweeps("pqa_obdm_sweeps_w", dev, ev, electrons, nsweeps, assign, seed, True, True, walker_chunk, False, weights)
 
 
 def device_obdm_sweeps_c(dev, ev, electrons, nsweeps, assign=None, seed=0, mean=False, first=True, walker_chunk=0, with_ratios=False,
@@ -283,28 +288,7 @@ def device_obdm_sweeps_c(dev, ev, electrons, nsweeps, assign=None, seed=0, mean=
     taken too).  The same dict, with complex ``ratio`` (nsweeps, W, nelec) and ``value`` (norb, norb) and a real ``norm``; ``weights``
     (W,): the weighted mean of ``device_obdm_sweeps_w`` (``mean`` only).  Without ``mean`` the evaluator's per-configuration accumulators
     hold complex sums (``ev.fetch(..., cplx=True)``)."""
-    es = np.ascontiguousarray(np.asarray(electrons).ravel(), dtype=np.int32)
-    W, norb = dev.W, ev.norb
-    if weights is not None:
-        if not mean:
-            raise ValueError("walker weights need the mean mode")
-        weights = _ffi.walker_weights(weights, W)
-    out = {}
-    if assign is not None:
-        assign = np.ascontiguousarray(assign, dtype=np.int32)
-        if assign.shape != (nsweeps, W):
-            raise ValueError(f"assignments ({nsweeps}, {W}) expected, got {assign.shape}")
-        out["assign"] = assign
-    else:
-        out["assign"] = np.empty((nsweeps, W), dtype=np.int32)
-    if with_ratios:
-        out["ratio"] = np.empty((nsweeps, W, len(es)), dtype=complex)
-    if mean:
-        out["value"], out["norm"] = np.empty((norb, norb), dtype=complex), np.empty(norb)
-    dev.call("pqa_obdm_sweeps_c", ev.dev._h, 0, _ffi.ptr(es), len(es), int(nsweeps), _ffi.ptr(assign), int(seed), int(mean), int(first),
-             int(walker_chunk), _ffi.ptr(weights), _ffi.ptr(out.get("ratio")), None if assign is not None else _ffi.ptr(out["assign"]),
-             _ffi.ptr(out.get("value")), _ffi.ptr(out.get("norm")))
-    return out
+    return _sweeps("pqa_obdm_sweeps_c", dev, ev, electrons, nsweeps, assign, seed, mean, first, walker_chunk, with_ratios, weights)
 
 
 def device_obdm_sweeps_j3(dev, ev, electrons, nsweeps, assign=None, seed=0, mean=False, first=True, walker_chunk=0, with_ratios=False,
@@ -312,31 +296,70 @@ def device_obdm_sweeps_j3(dev, ev, electrons, nsweeps, assign=None, seed=0, mean
     """``pqa_obdm_sweeps_j3``: ``device_obdm_sweeps`` for real handles ``dev`` with a three-body Jastrow factor (handles without one are
     taken too and give the bits of ``device_obdm_sweeps`` / ``device_obdm_sweeps_w``).  The same dict, real; ``weights`` (W,): the
     weighted mean of ``device_obdm_sweeps_w`` (``mean`` only)."""
-    es = np.ascontiguousarray(np.asarray(electrons).ravel(), dtype=np.int32)
-    W, norb = dev.W, ev.norb
-    if weights is not None:
-        if not mean:
-            raise ValueError("walker weights need the mean mode")
-        weights = _ffi.walker_weights(weights, W)
-    out = {}
-    if assign is not None:
-        assign = np.ascontiguousarray(assign, dtype=np.int32)
-        if assign.shape != (nsweeps, W):
-            raise ValueError(f"assignments ({nsweeps}, {W}) expected, got {assign.shape}")
-        out["assign"] = assign
-    else:
-        out["assign"] = np.empty((nsweeps, W), dtype=np.int32)
-    if with_ratios:
-        out["ratio"] = np.empty((nsweeps, W, len(es)))
-    if mean:
-        out["value"], out["norm"] = np.empty((norb, norb)), np.empty(norb)
-    dev.call("pqa_obdm_sweeps_j3", ev.dev._h, 0, _ffi.ptr(es), len(es), int(nsweeps), _ffi.ptr(assign), int(seed), int(mean), int(first),
-             int(walker_chunk), _ffi.ptr(weights), _ffi.ptr(out.get("ratio")), None if assign is not None else _ffi.ptr(out["assign"]),
-             _ffi.ptr(out.get("value")), _ffi.ptr(out.get("norm")))
-    return out
+    return _sweeps("pqa_obdm_sweeps_j3", dev, ev, electrons, nsweeps, assign, seed, mean, first, walker_chunk, with_ratios, weights)
 
 
-class OBDMAccumulator:
+class _FusedScope:
+    """What ``OBDMAccumulator`` and ``TBDMAccumulator`` share of the fused route's scope: the two opt-in flags, the handle lookup, the
+    choice of the library entry and the common part of the reason ladder.  A subclass names its three entries in ``ENTRIES`` (real,
+    complex, three-body), holds ``orbitals`` and ``_mol``, and adds the estimator's own tail to ``_common_scope``."""
+
+    ENTRIES = (None, None, None)
+
+    @staticmethod
+    def _flag(name, value):
+        """The opt-in flag ``name`` (``complex_device`` / ``three_body_device``) as a bool; anything but True or False is refused."""
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{name} must be True or False")
+        return bool(value)
+
+    def _device(self, wf):
+        """The handle the fused route reads ``wf`` from, or None."""
+        return readonly_device(wf, complex_ok=self.complex_device, three_body_ok=self.three_body_device)
+
+    def _j3_entry(self, dev):
+        """Whether the evaluation of the handle ``dev`` goes through the three-body entry."""
+        return self.three_body_device and bool(dev.has_j3)
+
+    def _complex_entry(self, dev):
+        """Whether the evaluation of the handle ``dev`` goes through the complex entry."""
+        ev = self.orbitals.dev
+        return self.complex_device and bool(dev.cplx or dev.twisted or ev.cplx or ev.twisted)
+
+    def _entry(self, dev):
+        """The library entry that evaluates the handle ``dev``: the three-body one before the complex one before the real one."""
+        return self.ENTRIES[2 if self._j3_entry(dev) else 1 if self._complex_entry(dev) else 0]
+
+    def _common_scope(self, wf):
+        """(handle, reason): why the fused route cannot take ``wf`` as far as both estimators agree — wave-function kind, evaluator
+        kind, devices, electron numbers — or None; the handle is None when the wave function has none in scope."""
+        dev, ev = self._device(wf), self.orbitals.dev
+        if dev is None:
+            if self.three_body_device:
+                d3 = getattr(wf, "fused_device", lambda: None)()
+                if d3 is not None and getattr(d3, "has_j3", False) and (d3.cplx or d3.twisted):
+                    return None, f"the three-body wave function is complex or twisted ({self.ENTRIES[2]} takes real handles)"
+                if self.complex_device:
+                    return None, "the wave function is not a Slater (x two-body x three-body Jastrow) product on one device handle"
+                return None, "the wave function is not a real Slater (x two-body x three-body Jastrow) product on one device handle"
+            if self.complex_device:
+                return None, "the wave function is not a Slater (x two-body Jastrow) product on one device handle"
+            return None, "the wave function is not a real Slater (x two-body Jastrow) product on one device handle"
+        if self._j3_entry(dev) and (ev.cplx or ev.twisted):
+            return dev, "the orbital evaluator is complex (a three-body wave function needs a real one)"
+        if self.complex_device:
+            if ev.twisted and not dev.twisted:
+                return dev, "the orbital evaluator is twisted and the wave function's handle is not (its folded walkers have lost the wrap phase)"
+        elif ev.cplx or ev.twisted:
+            return dev, "the orbital evaluator is complex"
+        if ev.device != dev.device:
+            return dev, "the wave function and the evaluator are on different devices"
+        if tuple(dev.nelec) != tuple(self._mol.nelec):
+            return dev, "the wave function has other electron numbers than the accumulator's system"
+        return dev, None
+
+
+class OBDMAccumulator(_FusedScope):
     """Keys ``value`` (norb,norb), ``norm`` (norb,) per configuration (obdm.py:26-213).
 
     ``spin`` 0/1 restricts the moved electrons to the up/down ones, ``electrons`` to an explicit list; ``naux`` auxiliary
@@ -354,6 +377,8 @@ class OBDMAccumulator:
     factor are in the fused scope too (``pqa_obdm_sweeps_j3``, a real evaluator); complex or twisted three-body handles stay on the
     protocol route.  With False (the default) three-body wave functions take the protocol route."""
 
+    ENTRIES = ("pqa_obdm_sweeps", "pqa_obdm_sweeps_c", "pqa_obdm_sweeps_j3")
+
     def __init__(self, mol, orb_coeff, nsweeps=5, tstep=0.50, warmup=10000, naux=None, spin=None, electrons=None, kpts=None,
                  eval_gto_precision=None, device=0, route=None, rng="numpy", walker_chunk=0, complex_device=False,
                  three_body_device=False):
@@ -363,12 +388,9 @@ class OBDMAccumulator:
             raise ValueError("rng must be 'numpy' or 'device'")
         if rng == "device" and route == "protocol":
             raise ValueError("rng='device' draws inside pqa_obdm_sweeps: it needs the fused route")
-        if not isinstance(complex_device, (bool, np.bool_)):
-            raise ValueError("complex_device must be True or False")
+        self.complex_device = self._flag("complex_device", complex_device)
         self._route, self._rng, self._walker_chunk, self.last_route = route, rng, int(walker_chunk), None
-        if not isinstance(three_body_device, (bool, np.bool_)):
-            raise ValueError("three_body_device must be True or False")
-        self.complex_device, self.three_body_device = bool(complex_device), bool(three_body_device)
+        self.three_body_device = self._flag("three_body_device", three_body_device)
         self.last_assign = None  # (nsweeps, nconf) assignments of the last fused evaluation
         nup, ntot = mol.nelec[0], int(np.sum(mol.nelec))
         if spin is not None:
@@ -387,47 +409,12 @@ class OBDMAccumulator:
     def _extra_config(self):
         return None if self._walkers is None else self._walkers.configs
 
-    def _device(self, wf):
-        """The handle the fused route reads ``wf`` from, or None."""
-        dev = readonly_device_c(wf) if self.complex_device else readonly_device(wf)
-        if dev is None and self.three_body_device:
-            dev = readonly_device_j3(wf)
-        return dev
-
-    def _j3_entry(self, dev):
-        """Whether the evaluation of the handle ``dev`` goes through ``pqa_obdm_sweeps_j3``."""
-        return self.three_body_device and bool(dev.has_j3)
-
-    def _complex_entry(self, dev):
-        """Whether the evaluation of the handle ``dev`` goes through ``pqa_obdm_sweeps_c``."""
-        return self.complex_device and bool(dev.cplx or dev.twisted or self.orbitals.dev.cplx or self.orbitals.dev.twisted)
-
     def _out_of_scope(self, wf, nconf=None):
         """Why the fused route cannot take ``wf`` (and ``nconf`` configurations), or None when it can."""
-        dev, ev = self._device(wf), self.orbitals.dev
+        dev, why = self._common_scope(wf)
+        if why is not None:
+            return why
         es = np.asarray(self._electrons).ravel()
-        if dev is None:
-            if self.three_body_device:
-                d3 = getattr(wf, "fused_device", lambda: None)()
-                if d3 is not None and getattr(d3, "has_j3", False) and (d3.cplx or d3.twisted):
-                    return "the three-body wave function is complex or twisted (pqa_obdm_sweeps_j3 takes real handles)"
-                if self.complex_device:
-                    return "the wave function is not a Slater (x two-body x three-body Jastrow) product on one device handle"
-                return "the wave function is not a real Slater (x two-body x three-body Jastrow) product on one device handle"
-            if self.complex_device:
-                return "the wave function is not a Slater (x two-body Jastrow) product on one device handle"
-            return "the wave function is not a real Slater (x two-body Jastrow) product on one device handle"
-        if self._j3_entry(dev) and (ev.cplx or ev.twisted):
-            return "the orbital evaluator is complex (a three-body wave function needs a real one)"
-        if self.complex_device:
-            if ev.twisted and not dev.twisted:
-                return "the orbital evaluator is twisted and the wave function's handle is not (its folded walkers have lost the wrap phase)"
-        elif ev.cplx or ev.twisted:
-            return "the orbital evaluator is complex"
-        if ev.device != dev.device:
-            return "the wave function and the evaluator are on different devices"
-        if tuple(dev.nelec) != tuple(self._mol.nelec):
-            return "the wave function has other electron numbers than the accumulator's system"
         if len(es) < 1:
             return "no electron is listed"
         if es.min() < 0 or es.max() >= dev.N or len(np.unique(es)) != len(es):
@@ -485,18 +472,11 @@ class OBDMAccumulator:
         if seed is None:
             pick = np.random.randint(0, naux, size=(nsw, nconf)).astype(np.int32)  # drawn before the walk (obdm.py:150)
         _, kept = self._walkers.advance(0, nsw, self._tstep, keep=nsw, seed=seed)
-        if self._j3_entry(dev):
-            out = device_obdm_sweeps_j3(dev, ev, self._electrons, nsw, assign=pick, seed=0 if seed is None else seed, mean=mean,
-                                        walker_chunk=self._walker_chunk, with_ratios=with_ratios, weights=weights)
-        elif self._complex_entry(dev):
-            out = device_obdm_sweeps_c(dev, ev, self._electrons, nsw, assign=pick, seed=0 if seed is None else seed, mean=mean,
-                                       walker_chunk=self._walker_chunk, with_ratios=with_ratios, weights=weights)
-        elif weights is not None:
-            out = device_obdm_sweeps_w(dev, ev, self._electrons, nsw, weights, assign=pick, seed=0 if seed is None else seed,
-                                       walker_chunk=self._walker_chunk)
-        else:
-            out = device_obdm_sweeps(dev, ev, self._electrons, nsw, assign=pick, seed=0 if seed is None else seed, mean=mean,
-                                     walker_chunk=self._walker_chunk, with_ratios=with_ratios)
+        entry = self._entry(dev)
+        if entry == "pqa_obdm_sweeps" and weights is not None:  # (the real entry's weighted mean is an entry of its own)
+            entry = "pqa_obdm_sweeps_w"
+        out = _sweeps(entry, dev, ev, self._electrons, nsw, pick, 0 if seed is None else seed, mean, True, self._walker_chunk, with_ratios,
+                      weights)
         vm, nm, ratio, used = out.get("value"), out.get("norm"), out.get("ratio"), out["assign"]
         self.last_assign = used
         self._walkers.x = np.ascontiguousarray(kept[-1][self.last_assign[-1]])  # the reference's resampling step, as in _sample

@@ -39,8 +39,7 @@ ratios draw nothing).
 import numpy as np
 
 from . import _ffi
-from .obdm import AuxiliaryWalkers, OrbitalEvaluator
-from .wf import readonly_device, readonly_device_c, readonly_device_j3
+from .obdm import AuxiliaryWalkers, OrbitalEvaluator, _FusedScope
 
 ROUTES = (None, "fused", "protocol")
 
@@ -92,7 +91,7 @@ def device_pair_ratios_j3(dev, ev, k, spins, assign_a, assign_b, walker_chunk=0)
     return device_tbdm_sweep_j3(dev, ev, k, spins, assign_a, assign_b, walker_chunk=walker_chunk, with_ratios=True)
 
 
-class TBDMAccumulator:
+class TBDMAccumulator(_FusedScope):
     """Keys ``value`` (M,), ``norm_a`` (norb_a,), ``norm_b`` (norb_b,) per configuration for the M index tuples ``ijkl``
     (default: the whole sector).  ``orb_coeff`` (2, nao, norb): orbital basis per spin; ``spin`` = (s1, s2).
 
@@ -104,15 +103,14 @@ class TBDMAccumulator:
     three-body Jastrow factor are in the fused scope too (``pqa_tbdm_sweep_j3``, a real evaluator); complex or twisted three-body
     handles stay on the protocol route.  With False (the default) three-body wave functions take the protocol route."""
 
+    ENTRIES = ("pqa_tbdm_sweep", "pqa_tbdm_sweep_c", "pqa_tbdm_sweep_j3")
+
     def __init__(self, mol, orb_coeff, spin, nsweeps=4, tstep=0.50, warmup=200, naux=None, ijkl=None, kpts=None,
                  eval_gto_precision=None, device=0, route=None, walker_chunk=0, complex_device=False, three_body_device=False):
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}")
-        if not isinstance(complex_device, (bool, np.bool_)):
-            raise ValueError("complex_device must be True or False")
-        if not isinstance(three_body_device, (bool, np.bool_)):
-            raise ValueError("three_body_device must be True or False")
-        self.complex_device, self.three_body_device = bool(complex_device), bool(three_body_device)
+        self.complex_device = self._flag("complex_device", complex_device)
+        self.three_body_device = self._flag("three_body_device", three_body_device)
         self._route, self._walker_chunk, self.last_route = route, int(walker_chunk), None
         self.orbitals = OrbitalEvaluator(mol, orb_coeff, kpts=kpts, eval_gto_precision=eval_gto_precision, device=device)
         self._mol, self.dtype = self.orbitals.mol, self.orbitals.mo_dtype
@@ -141,29 +139,12 @@ class TBDMAccumulator:
             wf.updateinternals(a, configs.electron(a), configs)  # and back: the state ends where it started
         return R
 
-    def _device(self, wf):
-        """The handle the fused route reads ``wf`` from, or None."""
-        dev = readonly_device_c(wf) if self.complex_device else readonly_device(wf)
-        if dev is None and self.three_body_device:
-            dev = readonly_device_j3(wf)
-        return dev
-
-    def _j3_entry(self, dev):
-        """Whether the evaluation of the handle ``dev`` goes through ``pqa_tbdm_sweep_j3``."""
-        return self.three_body_device and bool(dev.has_j3)
-
-    def _complex_entry(self, dev):
-        """Whether the evaluation of the handle ``dev`` goes through ``pqa_tbdm_sweep_c``."""
-        ev = self.orbitals.dev
-        return self.complex_device and bool(dev.cplx or dev.twisted or ev.cplx or ev.twisted)
-
-    def _evaluator_in_scope(self, dev):
-        ev = self.orbitals.dev
-        if self._j3_entry(dev):
-            return not ev.cplx and not ev.twisted
-        if self.complex_device:
-            return not (ev.twisted and not dev.twisted)
-        return not ev.cplx and not ev.twisted
+    def _scope(self, wf):
+        """(handle, reason): the handle the fused route reads ``wf`` from, and why it cannot take it, or None when it can."""
+        dev, why = self._common_scope(wf)
+        if why is None and min(len(e) for e in self._electrons) < 1:
+            why = "a spin block of the sector is empty"
+        return dev, why
 
     def _fused_device(self, configs, wf):
         """The handle the fused route evaluates ``wf`` on, or None: a read-only-scope wave function whose resident walkers are the
@@ -171,18 +152,17 @@ class TBDMAccumulator:
         when the handle is) on the same device."""
         if self._route == "protocol":
             return None
-        dev, ev = self._device(wf), self.orbitals.dev
-        ok = (dev is not None and dev.W == configs.configs.shape[0] and tuple(dev.nelec) == tuple(self._mol.nelec)
-              and min(len(e) for e in self._electrons) > 0 and self._evaluator_in_scope(dev) and ev.device == dev.device)
+        dev, why = self._scope(wf)
+        ok = why is None and dev.W == configs.configs.shape[0]
         if not ok and self._route == "fused":
             if self.three_body_device:
                 raise ValueError("route='fused' needs a Slater (x two-body x three-body Jastrow) wave function on one device handle whose "
                                  "resident walkers are the configurations, and an orbital evaluator in scope on the same device: "
-                                 + (self.resident_scope(wf) or "the handle holds other walkers than the configurations"))
+                                 + (why or "the handle holds other walkers than the configurations"))
             if self.complex_device:
                 raise ValueError("route='fused' needs a Slater (x two-body Jastrow) wave function on one device handle whose resident "
                                  "walkers are the configurations, and an orbital evaluator on the same device that is twisted only if "
-                                 "the handle is: " + (self.resident_scope(wf) or "the handle holds other walkers than the configurations"))
+                                 "the handle is: " + (why or "the handle holds other walkers than the configurations"))
             raise ValueError("route='fused' needs a real Slater (x two-body Jastrow) wave function on one device handle whose resident "
                              "walkers are the configurations, and a real orbital evaluator on the same device")
         return dev if ok else None
@@ -191,32 +171,7 @@ class TBDMAccumulator:
         """None when ``avg_resident`` can run for ``wf``, else the reason (the fused route's rules)."""
         if self._route == "protocol":
             return "the accumulator is bound to route='protocol'"
-        dev, ev = self._device(wf), self.orbitals.dev
-        if dev is None:
-            if self.three_body_device:
-                d3 = getattr(wf, "fused_device", lambda: None)()
-                if d3 is not None and getattr(d3, "has_j3", False) and (d3.cplx or d3.twisted):
-                    return "the three-body wave function is complex or twisted (pqa_tbdm_sweep_j3 takes real handles)"
-                if self.complex_device:
-                    return "the wave function is not a Slater (x two-body x three-body Jastrow) product on one device handle"
-                return "the wave function is not a real Slater (x two-body x three-body Jastrow) product on one device handle"
-            if self.complex_device:
-                return "the wave function is not a Slater (x two-body Jastrow) product on one device handle"
-            return "the wave function is not a real Slater (x two-body Jastrow) product on one device handle"
-        if self._j3_entry(dev) and (ev.cplx or ev.twisted):
-            return "the orbital evaluator is complex (a three-body wave function needs a real one)"
-        if self.complex_device:
-            if ev.twisted and not dev.twisted:
-                return "the orbital evaluator is twisted and the wave function's handle is not (its folded walkers have lost the wrap phase)"
-        elif ev.cplx or ev.twisted:
-            return "the orbital evaluator is complex"
-        if ev.device != dev.device:
-            return "the wave function and the evaluator are on different devices"
-        if tuple(dev.nelec) != tuple(self._mol.nelec):
-            return "the wave function has other electron numbers than the accumulator's system"
-        if min(len(e) for e in self._electrons) < 1:
-            return "a spin block of the sector is empty"
-        return None
+        return self._scope(wf)[1]
 
     def avg_resident(self, wf, weights=None):
         """The walker mean for the walkers resident behind ``wf``, without a host container: the electrons' coordinates are gathered

@@ -1196,52 +1196,36 @@ class MultiplyWF:
         return np.sum(g, axis=0), np.sum(l, axis=0) + 2 * cross
 
 
-def readonly_device(wf):
-    """The device handle the read-only fused estimators (``pqa_s2``, ``pqa_symmetry``) can evaluate ``wf`` on, or None: ``wf`` must
-    be exactly the handle's factors (a Slater factor, plus the two-body Jastrow when the handle has one), real, not twisted, without
-    a three-body factor."""
+def readonly_device(wf, complex_ok=False, three_body_ok=False):
+    """The device handle the read-only fused estimators (``pqa_s2``, ``pqa_symmetry``, the density matrices) can evaluate ``wf`` on, or
+    None: ``wf`` must be exactly the handle's factors (a Slater factor, plus the two-body Jastrow when the handle has one), real, not
+    twisted, without a three-body factor.  ``complex_ok`` admits complex and twisted handles, ``three_body_ok`` a ``ThreeBodyJastrow``
+    as a third factor when the handle has one; a complex or twisted three-body handle is refused with both (no entry serves it)."""
     factors = wf.wf_factors if isinstance(wf, MultiplyWF) else [wf]
     kinds = [type(f) for f in factors]
-    if any(k not in (Slater, JastrowSpin) for k in kinds) or len(set(kinds)) != len(kinds) or Slater not in kinds:
+    allowed = (Slater, JastrowSpin, ThreeBodyJastrow) if three_body_ok else (Slater, JastrowSpin)
+    if any(k not in allowed for k in kinds) or len(set(kinds)) != len(kinds) or Slater not in kinds:
         return None
     dev = wf.fused_device() if isinstance(wf, MultiplyWF) else getattr(wf, "_dev", None)
-    if dev is None or not hasattr(dev, "vmc_sweeps"):
+    if dev is None or not hasattr(dev, "vmc_sweeps") or not dev.has_slater:
         return None
-    if not dev.has_slater or dev.cplx or dev.twisted or dev.has_j3 or dev.has_jastrow != (JastrowSpin in kinds):
+    if (dev.cplx or dev.twisted) and (not complex_ok or dev.has_j3):
+        return None
+    if bool(dev.has_j3) != (ThreeBodyJastrow in kinds) or bool(dev.has_jastrow) != (JastrowSpin in kinds):
         return None
     return dev
 
 
 def readonly_device_c(wf):
     """``readonly_device`` with complex and twisted handles admitted (``pqa_obdm_sweeps_c``): the same rules otherwise."""
-    factors = wf.wf_factors if isinstance(wf, MultiplyWF) else [wf]
-    kinds = [type(f) for f in factors]
-    if any(k not in (Slater, JastrowSpin) for k in kinds) or len(set(kinds)) != len(kinds) or Slater not in kinds:
-        return None
-    dev = wf.fused_device() if isinstance(wf, MultiplyWF) else getattr(wf, "_dev", None)
-    if dev is None or not hasattr(dev, "vmc_sweeps"):
-        return None
-    if not dev.has_slater or dev.has_j3 or dev.has_jastrow != (JastrowSpin in kinds):
-        return None
-    return dev
+    return readonly_device(wf, complex_ok=True)
 
 
 def readonly_device_j3(wf):
     """``readonly_device`` with ``ThreeBodyJastrow`` admitted as a third factor (``pqa_obdm_sweeps_j3``, ``pqa_tbdm_sweep_j3``): ``wf``
     must be exactly the handle's factors — a Slater factor, plus the two-body and the three-body Jastrow when the handle has them —
     real and not twisted."""
-    factors = wf.wf_factors if isinstance(wf, MultiplyWF) else [wf]
-    kinds = [type(f) for f in factors]
-    if any(k not in (Slater, JastrowSpin, ThreeBodyJastrow) for k in kinds) or len(set(kinds)) != len(kinds) or Slater not in kinds:
-        return None
-    dev = wf.fused_device() if isinstance(wf, MultiplyWF) else getattr(wf, "_dev", None)
-    if dev is None or not hasattr(dev, "vmc_sweeps"):
-        return None
-    if not dev.has_slater or dev.cplx or dev.twisted:
-        return None
-    if bool(dev.has_j3) != (ThreeBodyJastrow in kinds) or bool(dev.has_jastrow) != (JastrowSpin in kinds):
-        return None
-    return dev
+    return readonly_device(wf, three_body_ok=True)
 
 
 LINEAR_JASTROW_KEYS = {"wf2acoeff", "wf2bcoeff"}  # the parameters the linear-Jastrow entry points vary
