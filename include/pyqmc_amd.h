@@ -682,6 +682,21 @@ int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, const double* b
 int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff, const double* acoeff, const double* bcoeff, double threshold,
                       const double* rot, const double* unif, uint64_t seed, long walker_chunk, double* logpsi, double* en);
 
+/* The same evaluation for handles with a three-body Jastrow factor (three_body_jastrow.py:19-655), whose coefficients vary between
+   the sets as well: pqa_correlated_md's arguments with ccoeff (K, natom, na3, na3, nb3, 3) after bcoeff; NULL for an array means
+   that every set uses the handle's own.  Each set's ccoeff is symmetrised as the handle's is, C = (c + c^T_kl) / 2.  U3 is linear
+   in C, and C enters only through its contraction with the a-functions of the moving electron: per electron (and per ECP point,
+   values only) the wave builds the C-independent tables M_c[I][l][m][s'] = sum_{j != e, spin s'} a_l(r_jI) {b_m, grad b_m, lap b_m}
+   (r_e - r_j) once, and every set contracts them and the a-triples of r_eI with its own coefficients to P_e, grad P_e, lap P_e (the
+   J3 instantiations of k_corr_md); grad U3 and lap U3 join the two-body terms of the set, an ECP point's exponent gains
+   P_e(q) - P_e(r_e), and logpsi[k] gains U3_k - U3_0 with U3 = 1/2 sum_e P_e(r_e), both from the same kernel.  Fixed summation
+   orders: two calls give the same bits, whatever walker_chunk.  Writes as pqa_correlated_md: none to the walkers, inverses,
+   determinants, coefficients or the three-body value.  Real, untwisted Slater x two-body x three-body Jastrow handles with one or
+   more determinants, open or periodic at Gamma, the semi-local ECP integrator or no ECP; anything else, and an LDS plan that does
+   not fit, is refused. */
+int pqa_correlated_j3(pqa_handle_t* h, int K, const double* det_coeff, const double* acoeff, const double* bcoeff, const double* ccoeff,
+                      double threshold, const double* rot, const double* unif, uint64_t seed, long walker_chunk, double* logpsi, double* en);
+
 /* ---- stochastic-reconfiguration moments from the resident state ----------------------------------- */
 /* StochasticReconfiguration.avg (stochastic_reconfiguration.py:49-118) on the resident walkers, without the walkers or the
    derivative arrays crossing the bus.  Column i of the serialised derivative matrix dp (W, P) is entry pos[i] (flat C-order index)

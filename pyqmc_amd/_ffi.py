@@ -155,6 +155,8 @@ _PROTOTYPES = {
                                  C.c_void_p]),
     "pqa_correlated_md": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_uint64, C.c_long,
                                     C.c_void_p, C.c_void_p]),
+    "pqa_correlated_j3": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_uint64,
+                                    C.c_long, C.c_void_p, C.c_void_p]),
     "pqa_sr_moments": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_uint64,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "pqa_sr_moments_orb": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_uint64,

@@ -12,7 +12,8 @@
 //                   ke_k = -1/2 sum_e [lap D/D + 2 grad D/D . grad U_k + lap U_k + |grad U_k|^2],  grad2_k = sum_e |grad D/D + grad U_k|^2,
 //                   ecp_k = local + sum_q s_q exp(dU_k(q)),  total_k = ke_k + ee + ei + ecp_k + ii.
 // The handle's coefficients are never changed.  Outputs are written per walker chunk of at most 256 MiB.
-// Several determinants, with det_coeff varying between the sets too: pqa_correlated_md / k_corr_md, further down.
+// Several determinants, with det_coeff varying between the sets too: pqa_correlated_md / k_corr_md, further down; with a three-body
+// factor whose ccoeff varies as well: pqa_correlated_j3, the J3 instantiations of k_corr_md.
 #include "pqa_estim.hpp"
 
 namespace {
@@ -146,6 +147,9 @@ struct CorrMdArgs {
   int nseg, has_ecp;
   double ii;
   double* out;              // [K][6][Wc]
+  // three-body instantiations (J3) only
+  const double* c3t;        // [P3][K1] symmetrised three-body coefficient matrix (column K: the handle's own)
+  double* u3;               // [K1][W] three-body log value U3_k = 1/2 sum_e P_e^k(r_e)
 };
 
 __device__ __forceinline__ double md_omega(const SysDev& S, const SlaterState& st, long w, int d, double ref) {
@@ -174,7 +178,206 @@ __global__ __launch_bounds__(64) void k_corr_md_s(SysDev S, SlaterState st, cons
 // LDS of k_corr_md in doubles: omega [ndet (even)], rho [16][RS], num [5][16][GS], R [4][P]
 inline size_t corr_md_lds(int ndet, int RS, int GS, int P) { return (size_t)((ndet + 1) & ~1) + (size_t)16 * RS + (size_t)80 * GS + (size_t)4 * P; }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Three-body factor (pqa_correlated_j3): ccoeff varies between the sets too.  U3 is linear in C (symmetrised in (k, l) by the host as
+// set_c3 does), and C enters jas3_eval only through its contraction with the moving electron's a-functions (pqa_jastrow.hpp).  For
+// electron e of spin s_e at r (its own position, or an ECP point q), with d_eI = r - R_I and partner spin s':
+//   M_c[I][l][m][s'] = sum_{j != e, spin s'} a_l(r_jI) {b_m, (b_m'/r) d_x, d_y, d_z, lap b_m}(r - r_j)        c = 0 .. 4, C-independent
+//   t_c[I][k]        = sum_{l m s'} C_k[I][k][l][m][s_e + s'] M_c[I][l][m][s']                                 per set (lane)
+//   P_e      = sum_{I k} a_k t_0,     grad P_e = sum_{I k} (a_k'/r) d_eI t_0 + a_k t_{1..3},
+//   lap P_e  = sum_{I k} (lap a_k) t_0 + 2 (a_k'/r) d_eI . t_{1..3} + a_k t_4                                  a_k = a_k(r_eI)
+// the sums of jas3_eval_n regrouped.  grad U3 = grad P_e and lap U3 = lap P_e join the two-body rows' sums of the set, an ECP point
+// adds P_e(q) - P_e(r_e) to the exponent, and U3_k = 1/2 sum_e P_e(r_e) goes to u3 for the log value (column K, the handle's own
+// coefficients, through the same code: the difference U3_k - U3_0 cancels what the regrouping rounds differently from the handle's
+// value).  The whole wave builds the tables once per electron or point; each lane then walks its own set's column of c3t, a read
+// coalesced over the lanes as ct's.  An ECP point needs the value table alone, so the five table slots hold up to five positions of
+// one electron at a time (consecutive points of the list, and r_e itself when the electron is new): the lane reads each coefficient
+// once for all of them (c3t lives in L2: P3 K1 doubles, 189 KB for water at K = 40; measured 10 - 20 % of a call: DESIGN section 47).
+// Sums run over partners, ions, k, l, m, s' ascending, whatever the grouping.  No per-lane arrays beyond t_c: nothing depends on an
+// unrolled length, so there is one instantiation for every na3, nb3 <= PQA_MAXBAS3.
+// LDS (doubles): aj [N][natom][na3] a_l(r_jI) of every electron, once per walker; M [5][natom][na3][nb3][2]; at [5][natom][na3] the
+// a-triples (slots 0 .. 2) or the a-values of five positions; de [natom][3]; bj [N][5][nb3] the partners' b-functions.
+struct J3Lds { double *aj, *M, *at, *de, *bj; };
+
+inline size_t corr_j3_lds(int N, int natom, int na3, int nb3) {
+  return (size_t)N * natom * na3 + (size_t)5 * natom * na3 * nb3 * 2 + (size_t)5 * natom * na3 + (size_t)3 * natom + (size_t)5 * N * nb3;
+}
+
+__device__ __forceinline__ J3Lds j3_lds(const SysDev& S, double* p) {
+  J3Lds L;
+  L.aj = p;
+  L.M = L.aj + (size_t)S.nelec * S.natom * S.na3;
+  L.at = L.M + (size_t)5 * S.natom * S.na3 * S.nb3 * 2;
+  L.de = L.at + (size_t)5 * S.natom * S.na3;
+  L.bj = L.de + (size_t)3 * S.natom;
+  return L;
+}
+
+// aj of the walker whose coordinates are xw (one wave; complete for every lane on return)
 template <bool PBC>
+__device__ __forceinline__ void j3_partner_a(const SysDev& S, const double* xw, const J3Lds& L) {
+  const int lane = threadIdx.x, A = S.natom, na = S.na3;
+  const double ira = 1.0 / S.rcut_a3;
+  for (int q = lane; q < S.nelec * A; q += 64) {
+    const int j = q / A, I = q - j * A;
+    double d[3];
+    const double r = jrow_dist<PBC>(S, xw[3 * j] - S.atom_xyz[3 * I], xw[3 * j + 1] - S.atom_xyz[3 * I + 1], xw[3 * j + 2] - S.atom_xyz[3 * I + 2], d);
+    const bool in = r < S.rcut_a3;
+    const RadShared sh = rad_shared<0>(in ? r : 0.5 * S.rcut_a3, ira);
+    for (int l = 0; l < na; ++l) {
+      double v = 0.0, g, lp;
+      if (in) rad_fn<0>(S.a3_kind[l], S.a3_param[l], S.a3_aux[l], S.rcut_a3, sh, v, g, lp);
+      L.aj[(size_t)q * na + l] = v;
+    }
+  }
+  __syncthreads();
+}
+
+// M[c][I][l][m][s'] = sum_{j of spin s'} aj[j][I][l] bj[j][c][m] for the slots c < nc (partners ascending; bj is zero for j = e and
+// outside the cutoff).  Lanes over the table entries; starts and ends with a barrier.
+__device__ __forceinline__ void j3_table_sums(const SysDev& S, int nc, const J3Lds& L) {
+  const int lane = threadIdx.x, N = S.nelec, A = S.natom, na = S.na3, nb = S.nb3, nlm = na * nb * 2, TS = A * nlm;
+  __syncthreads();
+  for (int t = lane; t < nc * TS; t += 64) {
+    const int c = t / TS, rem = t - c * TS, I = rem / nlm, r2 = rem - I * nlm;
+    const int l = r2 / (2 * nb), m = (r2 >> 1) % nb, sp = r2 & 1;
+    const int j0 = sp ? S.nup : 0, j1 = sp ? N : S.nup;
+    double acc = 0.0;
+    for (int j = j0; j < j1; ++j) acc += L.aj[((size_t)j * A + I) * na + l] * L.bj[((size_t)j * 5 + c) * nb + m];
+    L.M[t] = acc;
+  }
+  __syncthreads();
+}
+
+// The tables of electron e placed at (rx, ry, rz): M_0 .. M_4, the a-triples and d_eI.  One wave; complete for every lane on return.
+template <bool PBC>
+__device__ __forceinline__ void j3_tables(const SysDev& S, const double* xw, int e, double rx, double ry, double rz, const J3Lds& L) {
+  constexpr int NC = 5;
+  const int lane = threadIdx.x, N = S.nelec, A = S.natom, na = S.na3, nb = S.nb3;
+  const double ira = 1.0 / S.rcut_a3, irb = 1.0 / S.rcut_b3;
+  __syncthreads();  // (the lanes' contractions with the previous tables are over)
+  for (int I = lane; I < A; I += 64) {
+    double d[3];
+    const double r = jrow_dist<PBC>(S, rx - S.atom_xyz[3 * I], ry - S.atom_xyz[3 * I + 1], rz - S.atom_xyz[3 * I + 2], d);
+    const bool in = r < S.rcut_a3;
+    const RadShared sh = rad_shared<2>(in ? r : 0.5 * S.rcut_a3, ira);
+    L.de[3 * I] = d[0]; L.de[3 * I + 1] = d[1]; L.de[3 * I + 2] = d[2];
+    for (int k = 0; k < na; ++k) {
+      double v = 0.0, g = 0.0, lp = 0.0;
+      if (in) rad_fn<2>(S.a3_kind[k], S.a3_param[k], S.a3_aux[k], S.rcut_a3, sh, v, g, lp);
+      L.at[I * na + k] = v; L.at[(A + I) * na + k] = g; L.at[(2 * A + I) * na + k] = lp;
+    }
+  }
+  for (int j = lane; j < N; j += 64) {
+    double d[3];
+    const double r = jrow_dist<PBC>(S, rx - xw[3 * j], ry - xw[3 * j + 1], rz - xw[3 * j + 2], d);
+    const bool in = j != e && r < S.rcut_b3;
+    const RadShared sh = rad_shared<2>(in ? r : 0.5 * S.rcut_b3, irb);
+    double* row = L.bj + (size_t)j * NC * nb;
+    for (int m = 0; m < nb; ++m) {
+      double v = 0.0, g = 0.0, lp = 0.0;
+      if (in) rad_fn<2>(S.b3_kind[m], S.b3_param[m], S.b3_aux[m], S.rcut_b3, sh, v, g, lp);
+      row[m] = v; row[nb + m] = g * d[0]; row[2 * nb + m] = g * d[1]; row[3 * nb + m] = g * d[2]; row[4 * nb + m] = lp;
+    }
+  }
+  j3_table_sums(S, NC, L);
+}
+
+// Value tables of np <= 5 positions pos(c) (pointers to x, y, z) of electron e: slot c of M and of at as above.
+template <bool PBC, class F>
+__device__ __forceinline__ void j3_point_tables(const SysDev& S, const double* xw, int e, int np, F&& pos, const J3Lds& L) {
+  const int lane = threadIdx.x, N = S.nelec, A = S.natom, na = S.na3, nb = S.nb3;
+  const double ira = 1.0 / S.rcut_a3, irb = 1.0 / S.rcut_b3;
+  __syncthreads();  // (the lanes' contractions with the previous tables are over)
+  for (int q = lane; q < np * A; q += 64) {
+    const int c = q / A, I = q - c * A;
+    const double* p = pos(c);
+    double d[3];
+    const double r = jrow_dist<PBC>(S, p[0] - S.atom_xyz[3 * I], p[1] - S.atom_xyz[3 * I + 1], p[2] - S.atom_xyz[3 * I + 2], d);
+    const bool in = r < S.rcut_a3;
+    const RadShared sh = rad_shared<0>(in ? r : 0.5 * S.rcut_a3, ira);
+    for (int k = 0; k < na; ++k) {
+      double v = 0.0, g, lp;
+      if (in) rad_fn<0>(S.a3_kind[k], S.a3_param[k], S.a3_aux[k], S.rcut_a3, sh, v, g, lp);
+      L.at[(c * A + I) * na + k] = v;
+    }
+  }
+  for (int q = lane; q < np * N; q += 64) {
+    const int c = q / N, j = q - c * N;
+    const double* p = pos(c);
+    double d[3];
+    const double r = jrow_dist<PBC>(S, p[0] - xw[3 * j], p[1] - xw[3 * j + 1], p[2] - xw[3 * j + 2], d);
+    const bool in = j != e && r < S.rcut_b3;
+    const RadShared sh = rad_shared<0>(in ? r : 0.5 * S.rcut_b3, irb);
+    for (int m = 0; m < nb; ++m) {
+      double v = 0.0, g, lp;
+      if (in) rad_fn<0>(S.b3_kind[m], S.b3_param[m], S.b3_aux[m], S.rcut_b3, sh, v, g, lp);
+      L.bj[((size_t)j * 5 + c) * nb + m] = v;
+    }
+  }
+  j3_table_sums(S, np, L);
+}
+
+// Column kcol of c3t against the value tables of np <= 5 positions: out[c] = P_e(position c); one read of each coefficient serves
+// them all (slots beyond np hold leftovers, and so do their out[c]).
+__device__ __forceinline__ void j3_contract_points(const SysDev& S, int edown, const J3Lds& L, const double* __restrict__ c3t, int K1, int kcol,
+                                                   double (&out)[5]) {
+  const int A = S.natom, na = S.na3, nb = S.nb3, nlm = na * nb * 2, TS = A * nlm;
+#pragma unroll
+  for (int c = 0; c < 5; ++c) out[c] = 0.0;
+  for (int I = 0; I < A; ++I) {
+    const double* Mp = L.M + (size_t)I * nlm;
+    for (int k = 0; k < na; ++k) {
+      const double* cp = c3t + ((size_t)(I * na + k) * na * nb * 3 + edown) * K1 + kcol;
+      double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+      for (int lm = 0; lm < na * nb; ++lm)
+#pragma unroll
+        for (int sp = 0; sp < 2; ++sp) {
+          const double cc = cp[(size_t)(lm * 3 + sp) * K1];
+#pragma unroll
+          for (int c = 0; c < 5; ++c) t[c] += cc * Mp[(size_t)c * TS + lm * 2 + sp];
+        }
+#pragma unroll
+      for (int c = 0; c < 5; ++c) out[c] += L.at[(c * A + I) * na + k] * t[c];
+    }
+  }
+}
+
+// Column kcol of c3t against the tables of j3_tables: out[0] = P_e, out[1 .. 3] = grad P_e, out[4] = lap P_e.
+__device__ __forceinline__ void j3_contract(const SysDev& S, int edown, const J3Lds& L, const double* __restrict__ c3t, int K1, int kcol,
+                                            double (&out)[5]) {
+  constexpr int NC = 5;
+  const int A = S.natom, na = S.na3, nb = S.nb3, nlm = na * nb * 2, TS = A * nlm;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) out[c] = 0.0;
+  for (int I = 0; I < A; ++I) {
+    const double* Mp = L.M + (size_t)I * nlm;
+    for (int k = 0; k < na; ++k) {
+      const double* cp = c3t + ((size_t)(I * na + k) * na * nb * 3 + edown) * K1 + kcol;
+      double t[NC];
+#pragma unroll
+      for (int c = 0; c < NC; ++c) t[c] = 0.0;
+      for (int lm = 0; lm < na * nb; ++lm)
+#pragma unroll
+        for (int sp = 0; sp < 2; ++sp) {
+          const double cc = cp[(size_t)(lm * 3 + sp) * K1];
+#pragma unroll
+          for (int c = 0; c < NC; ++c) t[c] += cc * Mp[(size_t)c * TS + lm * 2 + sp];
+        }
+      const double a = L.at[I * na + k], ag = L.at[(A + I) * na + k], al = L.at[(2 * A + I) * na + k];
+      const double dx = L.de[3 * I], dy = L.de[3 * I + 1], dz = L.de[3 * I + 2];
+      out[0] += a * t[0];
+      out[1] += ag * dx * t[0] + a * t[1];
+      out[2] += ag * dy * t[0] + a * t[2];
+      out[3] += ag * dz * t[0] + a * t[3];
+      out[4] += al * t[0] + 2.0 * ag * (dx * t[1] + dy * t[2] + dz * t[3]) + a * t[4];
+    }
+  }
+}
+
+// J3: the three-body instantiations (pqa_correlated_j3).  Block column blockIdx.y covers the K1 = K + 1 columns of c3t: the lane of
+// column K (the handle's own coefficients) takes part in the three-body value alone.
+template <bool PBC, bool J3>
 __global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, JastrowState js, CorrMdArgs A) {
   extern __shared__ double sm[];
   const int lane = threadIdx.x, i16 = lane & 15, kq = lane >> 4;
@@ -189,6 +392,13 @@ __global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, Jastro
   double* R = G + (size_t)80 * GS;
   const double* xw = js.x + (size_t)w * N * 3;
   const double irb = 1.0 / S.rcut_b, ira = 1.0 / S.rcut_a;
+  const bool act3 = J3 && k < A.K1;  // (three-body value: the sets and the handle's own column)
+  J3Lds L3{};
+  double u3 = 0.0;
+  if constexpr (J3) {
+    L3 = j3_lds(S, R + (size_t)4 * P);
+    j3_partner_a<PBC>(S, xw, L3);
+  }
   // phase 0
   const double ref = det_ref(S, st, w);
   for (int d = lane; d < ndet; d += 64) om[d] = md_omega(S, st, w, d, ref);
@@ -243,6 +453,14 @@ __global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, Jastro
     for (int row = 0; row < rows; ++row) {  // phase 3
       const int e = e0 + row, s = e >= S.nup;
       jas_rows<PBC>(S, xw, e, s, xw[3 * e], xw[3 * e + 1], xw[3 * e + 2], P, Pa, ira, irb, R);
+      double p3[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+      if constexpr (J3) {
+        j3_tables<PBC>(S, xw, e, xw[3 * e], xw[3 * e + 1], xw[3 * e + 2], L3);
+        if (act3) {
+          j3_contract(S, s, L3, A.c3t, A.K1, k, p3);
+          u3 += 0.5 * p3[0];
+        }
+      }
       if (act) {
         const double v = G[row * GS + lane];
         const double G0 = G[(16 + row) * GS + lane] / v, G1 = G[(32 + row) * GS + lane] / v, G2 = G[(48 + row) * GS + lane] / v;
@@ -258,6 +476,7 @@ __global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, Jastro
           const double c = A.ct[(size_t)p * A.K + k];
           gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
         }
+        if constexpr (J3) { gx += p3[1]; gy += p3[2]; gz += p3[3]; lp += p3[4]; }
         const double lj = lp + gx * gx + gy * gy + gz * gz;
         const double lap = L + lj + 2.0 * (G0 * gx + G1 * gy + G2 * gz);
         const double tx = G0 + gx, ty = G1 + gy, tz = G2 + gz;
@@ -269,7 +488,9 @@ __global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, Jastro
   }
   // ECP: tiles of 16 points of one list segment
   double tot = 0.0;
-  if (A.has_ecp) {
+  int last_e = -1;      // (J3: the electron whose P_e(r_e) the lane holds in p_old, reused while consecutive points share it)
+  double p_old = 0.0;
+  if (A.has_ecp && (!J3 || kb < A.K)) {  // (a block with the handle's own column alone has no set to evaluate)
     const size_t SS = (size_t)A.nseg * A.W + 1;
     for (int sp = 0; sp < 2; ++sp) {
       const int n = sp ? S.ndn : S.nup, nmo = S.nmo[sp], D = S.ndet_s[sp];
@@ -302,14 +523,34 @@ __global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, Jastro
             }
           }
           __syncthreads();
+          // (J3) groups of consecutive points of one electron share the five table slots, the first slot for r_e when the electron is new
+          double pv[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+          int gnext = 0, gslot = 0;  // first row behind the current group; the slot of the row at hand
           for (int row = 0; row < rows; ++row) {  // phase 3
             const long pt = pb + row;
             const int e = A.pte[sp][pt];
+            double dp3 = 0.0;
+            if constexpr (J3) {
+              if (row == gnext) {
+                const int o = e != last_e;
+                int g = 1;
+                while (g + o < 5 && row + g < rows && A.pte[sp][pt + g] == e) ++g;
+                j3_point_tables<PBC>(S, xw, e, g + o, [&](int c) { return c < o ? xw + 3 * e : A.pts[sp] + 3 * (pt + c - o); }, L3);
+                if (act) {
+                  j3_contract_points(S, sp, L3, A.c3t, A.K1, k, pv);
+                  if (o) p_old = pv[0];
+                }
+                last_e = e; gnext = row + g; gslot = o;
+              }
+              dp3 = (gslot == 0 ? pv[0] : gslot == 1 ? pv[1] : gslot == 2 ? pv[2] : gslot == 3 ? pv[3] : pv[4]) - p_old;
+              ++gslot;
+            }
             jas_diff_rows<PBC>(S, xw, e, sp, A.pts[sp][3 * pt], A.pts[sp][3 * pt + 1], A.pts[sp][3 * pt + 2], P, Pa, ira, irb, R);
             if (act) {
               double du = 0.0;
               for (int q = 0; q < S.natom * S.na; ++q) { const int p = 2 * q + sp; du += A.ct[(size_t)p * A.K + k] * R[p]; }
               for (int q = 0; q < 2 * S.nb; ++q) { const int p = Pa + (q >> 1) * 3 + sp + (q & 1); du += A.ct[(size_t)p * A.K + k] * R[p]; }
+              if constexpr (J3) du += dp3;
               tot += A.wgt[sp][pt] * (G[row * GS + lane] * invS) * exp(du);
             }
             __syncthreads();
@@ -318,6 +559,8 @@ __global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, Jastro
       }
     }
   }
+  if constexpr (J3)
+    if (act3) A.u3[(size_t)k * A.W + w] = u3;
   if (!act) return;
   const double ee = A.kc[A.W + w], ei = A.kc[2 * A.W + w], ec = A.has_ecp ? A.local[w] + tot : 0.0;
   double* o = A.out + (size_t)k * 6 * A.Wc + bw;
@@ -326,15 +569,21 @@ __global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, Jastro
 
 // Scope of pqa_correlated_md: a real, untwisted Slater x two-body Jastrow handle, one or more determinants, no three-body factor, the
 // semi-local ECP integrator or no ECP.
-int linear_det_jastrow_scope(pqa_handle* h, const char* fn) {
-  const char* why = (!h->has_slater || !h->has_j2) ? "needs a Slater x two-body Jastrow handle"
+// j3 (pqa_correlated_j3): the same with a three-body factor, which the handle must then have.
+int linear_det_jastrow_scope(pqa_handle* h, const char* fn, bool j3 = false) {
+  const char* why = (!h->has_slater || !h->has_j2) ? (j3 ? "needs a Slater x two-body x three-body Jastrow handle" : "needs a Slater x two-body Jastrow handle")
                     : (h->cplx || h->twist)        ? "complex orbitals / twisted cell"
-                    : h->has_j3                    ? "three-body Jastrow factor"
+                    : (!j3 && h->has_j3)           ? "three-body Jastrow factor"
+                    : (j3 && !h->has_j3)           ? "needs a Slater x two-body x three-body Jastrow handle"
                     : (h->necp > 0 && h->ecpb_on)  ? "batched ECP integrator"
                                                    : nullptr;
   if (why) FAIL(std::string(fn) + ": " + why + " (others: set, recompute and evaluate per set)");
   return 0;
 }
+
+using CorrMdKernel = void (*)(SysDev, SlaterState, JastrowState, CorrMdArgs);
+const CorrMdKernel corr_md_kernels[2][2] = {  // [J3][PBC]
+    {k_corr_md<true, true>, k_corr_md<false, true>}, {k_corr_md<true, false>, k_corr_md<false, false>}};
 
 }  // namespace
 
@@ -410,23 +659,29 @@ extern "C" int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, cons
   return 0;
 }
 
-extern "C" int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff, const double* acoeff, const double* bcoeff, double threshold,
-                                 const double* rot, const double* unif, uint64_t seed, long walker_chunk_arg, double* logpsi, double* en) {
+// The host driver of pqa_correlated_md (j3 = false: ccoeff unused, the J3 = false kernels) and pqa_correlated_j3 (fn: the entry's name).
+static int correlated_md_run(pqa_handle_t* h, const char* fn_, bool j3, int K, const double* det_coeff, const double* acoeff, const double* bcoeff,
+                             const double* ccoeff, double threshold, const double* rot, const double* unif, uint64_t seed, long walker_chunk_arg,
+                             double* logpsi, double* en) {
+  const std::string fn = fn_;
   HIPCHK(hipSetDevice(h->device));
   if (h->W == 0) FAIL("state not initialised (call pqa_wf_recompute)");
-  if (K < 1) FAIL("pqa_correlated_md: K must be at least 1");
-  if (!logpsi || !en) FAIL("pqa_correlated_md: logpsi and en must not be NULL");
-  if (walker_chunk_arg < 0) FAIL("pqa_correlated_md: walker_chunk must be 0 (the 256 MiB rule) or positive");
-  TRY(linear_det_jastrow_scope(h, "pqa_correlated_md"));
+  if (K < 1) FAIL(fn + ": K must be at least 1");
+  if (!logpsi || !en) FAIL(fn + ": logpsi and en must not be NULL");
+  if (walker_chunk_arg < 0) FAIL(fn + ": walker_chunk must be 0 (the 256 MiB rule) or positive");
+  TRY(linear_det_jastrow_scope(h, fn_, j3));
   const long W = h->W;
   const int ndet = h->ndet, Pa = h->natom * h->na * 2, Pb = h->nb * 3, P = Pa + Pb, K1 = K + 1;
+  const int P3 = j3 ? h->natom * h->na3 * h->na3 * h->nb3 * 3 : 0;
   // the LDS plan: refused where it does not fit, never truncated
   const int DP = std::max(h->ndet_s[0], h->ndet_s[1]), RS = ((5 * DP + 29) / 32) * 32 + 2;
   const int ncol = ((std::min(K, 64) + 15) / 16) * 16, GS = ncol + ((ncol % 32 == 0) ? 16 : 0);
-  const size_t lds = corr_md_lds(ndet, RS, GS, P) * sizeof(double);
+  const size_t lds = (corr_md_lds(ndet, RS, GS, P) + (j3 ? corr_j3_lds(h->N, h->natom, h->na3, h->nb3) : 0)) * sizeof(double);
   if (lds > 160 * 1024)
-    FAIL("pqa_correlated_md: the determinant rows and Jastrow rows of a 16-row tile exceed the LDS of a CU (others: set, recompute and evaluate per set)");
-  if (lds > 64 * 1024) TRY(raise_lds_limit(h, h->S.pbc ? (const void*)k_corr_md<true> : (const void*)k_corr_md<false>));
+    FAIL(fn + (j3 ? ": the determinant rows, Jastrow rows and three-body tables of a 16-row tile exceed the LDS of a CU (others: set, recompute and evaluate per set)"
+                  : ": the determinant rows and Jastrow rows of a 16-row tile exceed the LDS of a CU (others: set, recompute and evaluate per set)"));
+  const CorrMdKernel kernel = corr_md_kernels[j3 ? 0 : 1][h->S.pbc ? 0 : 1];
+  if (lds > 64 * 1024) TRY(raise_lds_limit(h, (const void*)kernel));
   // log|Psi| at the handle's own coefficients (as pqa_wf_value: refreshes the basis sums a fused sweep left stale)
   std::vector<double> lg0((size_t)W);
   TRY(pqa_wf_value(h, nullptr, lg0.data()));
@@ -450,6 +705,25 @@ extern "C" int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff
   std::vector<double> cd((size_t)ndet * K1);  // [ndet][K1]
   for (int k = 0; k < K1; ++k)
     for (int d = 0; d < ndet; ++d) cd[(size_t)d * K1 + k] = cdr[(size_t)k * ndet + d];
+  // three-body sets, symmetrised in (k, l) as set_c3 does (the handle's own, d_c3, already is): [P3][K1], column K the handle's own
+  std::vector<double> c3t((size_t)P3 * K1);
+  if (j3) {
+    std::vector<double> c3((size_t)K1 * P3);
+    HIPCHK(hipMemcpy(c3.data() + (size_t)K * P3, h->d_c3, (size_t)P3 * sizeof(double), hipMemcpyDeviceToHost));
+    TRY(rows_in(c3, ccoeff, P3));
+    const int na3 = h->na3, m3 = h->nb3 * 3;
+    for (int k = 0; k < K1; ++k) {
+      const double* c = c3.data() + (size_t)k * P3;
+      const bool sym = k < K && ccoeff;
+      for (int I = 0; I < h->natom; ++I)
+        for (int a = 0; a < na3; ++a)
+          for (int l = 0; l < na3; ++l)
+            for (int m = 0; m < m3; ++m) {
+              const size_t p = (((size_t)I * na3 + a) * na3 + l) * m3 + m, q = (((size_t)I * na3 + l) * na3 + a) * m3 + m;
+              c3t[p * K1 + k] = sym ? 0.5 * (c[p] + c[q]) : c[p];
+            }
+    }
+  }
   // the Slater-only energy pass, once, with the ECP totals read on the host
   TRY(sync_aos(h));
   h->saved_valid = false;  // (as pqa_energy: the saved orbital rows of a gradient_value call are overwritten)
@@ -457,12 +731,14 @@ extern "C" int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff
   eo.slater_only = true; eo.host_totals = true;
   TRY(energy_dev(h, threshold, rot, unif, seed, 0u, eo));
   const bool has_ecp = h->necp > 0;
-  if (has_ecp && (h->en.last_tot[0] < 0 || h->en.last_tot[1] < 0)) FAIL("pqa_correlated_md: ECP point totals were left on the device");
-  // device scratch (b_out is sized by every user on entry): coefficient rows for k_corr_u, U, the two matrices, S, a chunk of outputs
+  if (has_ecp && (h->en.last_tot[0] < 0 || h->en.last_tot[1] < 0)) FAIL(fn + ": ECP point totals were left on the device");
+  // device scratch (b_out is sized by every user on entry): coefficient rows for k_corr_u, U, the two matrices, S, a chunk of outputs;
+  // behind them the three-body matrix and U3
   const size_t nca = (size_t)K1 * std::max(Pa, 1), ncb = (size_t)K1 * std::max(Pb, 1), nu = (size_t)K1 * W, nct = (size_t)P * K;
   const size_t ncd = (size_t)ndet * K1;
   const long Wc = walker_chunk_arg > 0 ? std::min(W, walker_chunk_arg) : walker_chunk(W, (size_t)K * 6 * sizeof(double));
-  TRY(ensure(h, h->b_out, (nca + ncb + 2 * nu + nct + ncd + (size_t)K * 6 * Wc) * sizeof(double)));
+  const size_t nc3 = (size_t)P3 * K1, nout = (size_t)K * 6 * Wc;
+  TRY(ensure(h, h->b_out, (nca + ncb + 2 * nu + nct + ncd + nout + nc3 + (j3 ? nu : 0)) * sizeof(double)));
   double* d_ca = (double*)h->b_out.p;
   double* d_cb = d_ca + nca;
   double* d_u = d_cb + ncb;
@@ -470,10 +746,13 @@ extern "C" int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff
   double* d_ct = d_s + nu;
   double* d_cd = d_ct + nct;
   double* d_o = d_cd + ncd;
+  double* d_c3t = d_o + nout;
+  double* d_u3 = d_c3t + nc3;
   if (Pa) TRY(copy_in(h, d_ca, ca.data(), (size_t)K1 * Pa * sizeof(double)));
   if (Pb) TRY(copy_in(h, d_cb, cb.data(), (size_t)K1 * Pb * sizeof(double)));
   TRY(copy_in(h, d_ct, ct.data(), nct * sizeof(double)));
   TRY(copy_in(h, d_cd, cd.data(), ncd * sizeof(double)));
+  if (j3) TRY(copy_in(h, d_c3t, c3t.data(), nc3 * sizeof(double)));
   hipLaunchKernelGGL(k_corr_u, dim3((unsigned)W), dim3(64), 0, h->stream, (const double*)h->js.avalues, (const double*)h->js.bvalues,
                      (const double*)d_ca, (const double*)d_cb, Pa, Pb, K1, W, d_u);
   TRY(check_launch(h, "k_corr_u"));
@@ -482,6 +761,7 @@ extern "C" int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff
   CorrMdArgs A{};
   A.W = W; A.K = K; A.K1 = K1; A.P = P; A.Pa = Pa; A.DP = DP; A.RS = RS; A.GS = GS; A.ct = d_ct; A.cd = d_cd;
   A.kc = (const double*)h->b_kc.p; A.ii = h->ii_energy; A.out = d_o; A.has_ecp = has_ecp;
+  if (j3) { A.c3t = d_c3t; A.u3 = d_u3; }
   if (has_ecp) {
     A.local = (const double*)h->b_elocal.p; A.off = (const long*)h->b_eoff.p; A.nseg = h->en.last_nseg;
     for (int s = 0; s < 2; ++s) {
@@ -491,9 +771,8 @@ extern "C" int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff
   }
   for (long w0 = 0; w0 < W; w0 += Wc) {
     A.w0 = w0; A.Wc = std::min(Wc, W - w0);
-    const dim3 g((unsigned)A.Wc, (unsigned)((K + 63) / 64));
-    if (h->S.pbc) hipLaunchKernelGGL(k_corr_md<true>, g, dim3(64), lds, h->stream, h->S, h->st, h->js, A);
-    else hipLaunchKernelGGL(k_corr_md<false>, g, dim3(64), lds, h->stream, h->S, h->st, h->js, A);
+    const dim3 g((unsigned)A.Wc, (unsigned)(((j3 ? K1 : K) + 63) / 64));  // (J3: the handle's own column rides along for U3)
+    hipLaunchKernelGGL(kernel, g, dim3(64), lds, h->stream, h->S, h->st, h->js, A);
     TRY(check_launch(h, "k_corr_md"));
     // [K][6][Wc] -> en [K][6][W] columns w0 ..
     HIPCHK(hipMemcpy2DAsync(en + w0, (size_t)W * sizeof(double), d_o, (size_t)A.Wc * sizeof(double), (size_t)A.Wc * sizeof(double),
@@ -502,12 +781,29 @@ extern "C" int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff
   std::vector<double> u((size_t)K1 * W), sv((size_t)K1 * W);
   TRY(copy_out(h, u.data(), d_u, u.size() * sizeof(double)));
   TRY(copy_out(h, sv.data(), d_s, sv.size() * sizeof(double)));
+  std::vector<double> v3;
+  if (j3) {
+    v3.resize((size_t)K1 * W);
+    TRY(copy_out(h, v3.data(), d_u3, v3.size() * sizeof(double)));
+  }
   std::vector<double> lp((size_t)K * W);
   for (int k = 0; k < K; ++k)
     for (long w = 0; w < W; ++w) {
       const size_t i = (size_t)k * W + w, i0 = (size_t)K * W + w;
       lp[i] = lg0[w] + (std::log(std::fabs(sv[i])) - std::log(std::fabs(sv[i0]))) + (u[i] - u[i0]);
+      if (j3) lp[i] += v3[i] - v3[i0];
     }
   HIPCHK(hipMemcpy(logpsi, lp.data(), lp.size() * sizeof(double), hipMemcpyDefault));
   return 0;
+}
+
+extern "C" int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff, const double* acoeff, const double* bcoeff, double threshold,
+                                 const double* rot, const double* unif, uint64_t seed, long walker_chunk_arg, double* logpsi, double* en) {
+  return correlated_md_run(h, "pqa_correlated_md", false, K, det_coeff, acoeff, bcoeff, nullptr, threshold, rot, unif, seed, walker_chunk_arg, logpsi, en);
+}
+
+extern "C" int pqa_correlated_j3(pqa_handle_t* h, int K, const double* det_coeff, const double* acoeff, const double* bcoeff, const double* ccoeff,
+                                 double threshold, const double* rot, const double* unif, uint64_t seed, long walker_chunk_arg, double* logpsi,
+                                 double* en) {
+  return correlated_md_run(h, "pqa_correlated_j3", true, K, det_coeff, acoeff, bcoeff, ccoeff, threshold, rot, unif, seed, walker_chunk_arg, logpsi, en);
 }

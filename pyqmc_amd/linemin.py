@@ -14,6 +14,9 @@ step along it by correlated sampling: the walkers are drawn from the mixture of 
   with ``evaluation_route="fused"`` also several determinants and ``wf1det_coeff`` among the parameters (real, untwisted, no
   three-body factor): ONE C call, ``pqa_correlated_md``, which adds the determinant sums of all sets as one matrix-core product
   per walker (``data["entry"]`` names the call that ran);
+  with ``three_body_device=True`` (opt-in) also a real, untwisted Slater x two-body x three-body Jastrow wave function with any
+  number of determinants and ``wf3ccoeff`` among the parameters: ONE C call, ``pqa_correlated_j3``, which builds the
+  coefficient-independent three-body tables once per electron and ECP point and contracts them with every set's ``ccoeff``;
 * ``"protocol"`` — anything else: per set, the parameters are set, the wave function recomputed and the energy accumulator
   run, as the reference does.  It is the default for several determinants; ``evaluation_route`` (``line_minimization``,
   ``correlated_sampling_minimum``, ``correlated_compute``, ``correlated_compute_worker``) selects a route by name.
@@ -33,7 +36,7 @@ import numpy as np
 
 from . import sample_many as sm
 from .energy import EnergyAccumulator
-from .wf import linear_det_jastrow_device, linear_jastrow_device
+from .wf import ThreeBodyJastrow, linear_det_jastrow_device, linear_j3_device, linear_jastrow_device
 
 
 def opt_hdf(hdf_file, data, attr, configs, parameters):
@@ -97,12 +100,15 @@ def _no_client(client, npartitions):
 
 def line_minimization(wf, coords, pgrad_acc, steprange=0.2, max_iterations=30, warmup_options=None, correlated_reference_wfs=None,
                       stderr_weight=3.0, vmcoptions=None, lmoptions=None, correlatedoptions=None, update_kws=None, verbose=False, npts=40,
-                      hdf_file=None, client=None, npartitions=None, correlated_sampling=True, evaluation_route=None):
+                      hdf_file=None, client=None, npartitions=None, correlated_sampling=True, evaluation_route=None,
+                      three_body_device=False):
     """Optimise the energy by stochastic-reconfiguration directions and correlated-sampling line searches (linemin.py:103-260).
     ``pgrad_acc``: a ``StochasticReconfiguration`` (e.g. ``accumulators.gradient_generator``) or a list of them (sub-iterations).
     ``evaluation_route``: the route of the line points' evaluation (``correlated_route``; None: the default choice).
+    ``three_body_device``: with True wave functions with a three-body Jastrow factor take the fused route (``correlated_route``).
     Returns (wf, list of per-step dictionaries)."""
     _no_client(client, npartitions)
+    three_body_device = _flag("three_body_device", three_body_device)
     from .blockfile import BlockFile
 
     vmcoptions = {} if vmcoptions is None else vmcoptions
@@ -166,7 +172,7 @@ def line_minimization(wf, coords, pgrad_acc, steprange=0.2, max_iterations=30, w
             if correlated_sampling:
                 x0, min_data = correlated_sampling_minimum(steprange, npts, stderr_weight, correlated_reference_wfs, pgrad, wf, data, x0,
                                                            coords, client, npartitions, evaluation_route=evaluation_route,
-                                                           **correlatedoptions)
+                                                           three_body_device=three_body_device, **correlatedoptions)
                 step_data.update(min_data)
                 if verbose:
                     print("Moved", step_data["est_min"])
@@ -187,16 +193,17 @@ def sr_step(steprange, pgrad, data, x0):
 
 
 def correlated_sampling_minimum(steprange, npts, stderr_weight, correlated_reference_wfs, pgrad, wf, data, x0, coords, client, npartitions,
-                                evaluation_route=None, **correlatedoptions):
+                                evaluation_route=None, three_body_device=False, **correlatedoptions):
     """Step along the SR direction that minimises ``mean energy + stderr_weight * spread`` over ``npts`` points of
     ``np.linspace(-steprange / (npts - 2), steprange, npts)`` (linemin.py:280-328).  ``correlatedoptions``: ``nsteps`` / ``nblocks``
     / ``tstep`` of the mixture sampling (the reference accepts them and drops them, sampling 10 blocks x 10 sweeps);
-    ``evaluation_route`` goes to ``correlated_compute_worker``, not into the sampling's options."""
+    ``evaluation_route`` and ``three_body_device`` go to ``correlated_compute_worker``, not into the sampling's options."""
+    three_body_device = _flag("three_body_device", three_body_device)
     steps = np.linspace(-steprange / (npts - 2), steprange, npts)
     dps, update_report = pgrad.delta_p(steps, data, verbose=False)
     params = [x0 + dp for dp in dps]
     correlated_data = correlated_compute(wf, coords, params, pgrad, client=client, npartitions=npartitions, ref_wfs=correlated_reference_wfs,
-                                         evaluation_route=evaluation_route, **correlatedoptions)
+                                         evaluation_route=evaluation_route, three_body_device=three_body_device, **correlatedoptions)
     w = correlated_data["weight"].copy()
     w = w / np.mean(w, axis=1, keepdims=True)
     en = np.real(np.mean(correlated_data["total"] * w, axis=1))
@@ -212,10 +219,12 @@ def correlated_sampling_minimum(steprange, npts, stderr_weight, correlated_refer
     return x0, update_report
 
 
-def correlated_compute(wf, configs, params, pgrad_acc, client=None, npartitions=None, ref_wfs=None, evaluation_route=None, **kws):
+def correlated_compute(wf, configs, params, pgrad_acc, client=None, npartitions=None, ref_wfs=None, evaluation_route=None,
+                       three_body_device=False, **kws):
     """Walkers drawn from the mixture of the ``ref_wfs`` parameter sets (deep copies of ``wf``), then every set of ``params``
     evaluated on them (linemin.py:331-375).  ``kws``: ``nsteps`` / ``nblocks`` / ``tstep`` of ``sample_many.sample_overlap``."""
     _no_client(client, npartitions)
+    three_body_device = _flag("three_body_device", three_body_device)
     if ref_wfs is None:
         ref_wfs = [0, 1]
     wfs = [copy.deepcopy(wf) for i in ref_wfs]
@@ -223,20 +232,46 @@ def correlated_compute(wf, configs, params, pgrad_acc, client=None, npartitions=
         set_wf_params(wfs[i], params[i], pgrad_acc)
     _, _, configs = sm.sample_overlap(wfs, configs, None, **kws)
     del wfs  # (their device handles)
-    return correlated_compute_worker(wf, configs, params, pgrad_acc, ref_wfs, evaluation_route=evaluation_route)
+    return correlated_compute_worker(wf, configs, params, pgrad_acc, ref_wfs, evaluation_route=evaluation_route,
+                                     three_body_device=three_body_device)
 
 
-def correlated_route(wf, pgrad_acc, route=None):
+def _flag(name, value):
+    """The opt-in flag ``name`` as a bool; anything but True or False is refused (as the density-matrix accumulators' flags)."""
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"{name} must be True or False")
+    return bool(value)
+
+
+def _has_three_body(wf):
+    dev = wf.fused_device() if hasattr(wf, "fused_device") else None
+    return any(type(f) is ThreeBodyJastrow for f in getattr(wf, "wf_factors", ())) or bool(getattr(dev, "has_j3", False))
+
+
+def correlated_route(wf, pgrad_acc, route=None, three_body_device=False):
     """The route ``correlated_compute_worker`` takes.  ``route=None``: ``"fused"`` when ``pqa_correlated`` covers this wave function,
     accumulator and parameter selection, else ``"protocol"``.  ``route="fused"``: ``"fused"`` also where only ``pqa_correlated_md``
     covers them (several determinants, ``wf1det_coeff`` among the parameters); ``NotImplementedError`` with the reason where neither
-    does.  ``route="protocol"``: ``"protocol"``."""
+    does.  ``route="protocol"``: ``"protocol"``.  ``three_body_device=True`` (opt-in) changes the outcome for wave functions with
+    a three-body Jastrow factor alone: where ``pqa_correlated_j3`` covers them (``wf.linear_j3_device``, a plain
+    ``EnergyAccumulator`` with the semi-local ECP integrator) ``"fused"`` for ``route=None`` and ``route="fused"``, whatever the
+    determinant count; elsewhere ``"protocol"`` for ``route=None`` and ``NotImplementedError`` with the reason for ``"fused"``."""
     if route not in (None, "fused", "protocol"):
         raise ValueError(f"evaluation route {route!r}: None, 'fused' or 'protocol' expected")
+    three_body_device = _flag("three_body_device", three_body_device)
     if route == "protocol":
         return "protocol"
     enacc = getattr(pgrad_acc, "enacc", None)
     plain = type(enacc) is EnergyAccumulator and enacc.use_old_ecp
+    if three_body_device and _has_three_body(wf):
+        why = []
+        if not plain:
+            why.append("the energy accumulator is not an EnergyAccumulator with the semi-local ECP integrator (use_old_ecp=True)")
+        elif linear_j3_device(wf, _opt_keys(pgrad_acc), why) is not None:
+            return "fused"
+        if route is None:
+            return "protocol"
+        raise NotImplementedError(f"evaluation_route='fused': {why[0]}; use the set-recompute-energy route (evaluation_route='protocol')")
     if route is None:
         if not plain:
             return "protocol"
@@ -261,12 +296,12 @@ def _weights(psi, ref_wfs):
     return psirel / rho
 
 
-def correlated_compute_worker(wf, configs, params, pgrad_acc, ref_wfs, evaluation_route=None):
+def correlated_compute_worker(wf, configs, params, pgrad_acc, ref_wfs, evaluation_route=None, three_body_device=False):
     """Energies and log values of ``wf`` at every parameter set of ``params`` on the same walkers, with the same random draws for
     every set (linemin.py:378-409).  Returns ``{energy key: (nsets, nconf)}``, ``weight`` (nsets, nconf) relative to the mixture
     of the ``ref_wfs`` sets, ``route`` and, on the fused route, ``entry`` (the C call).  ``wf`` keeps its parameters; its device
-    state is that of ``configs``.  ``evaluation_route``: see ``correlated_route``."""
-    route = correlated_route(wf, pgrad_acc, evaluation_route)
+    state is that of ``configs``.  ``evaluation_route``, ``three_body_device``: see ``correlated_route``."""
+    route = correlated_route(wf, pgrad_acc, evaluation_route, three_body_device)
     if route == "fused":
         return _correlated_fused(wf, configs, params, pgrad_acc, ref_wfs)
     x_orig = pgrad_acc.transform.serialize_parameters(wf.parameters)
@@ -305,7 +340,13 @@ def _correlated_fused(wf, configs, params, pgrad_acc, ref_wfs):
     enacc._calls += 1
     # the draws one accumulator call makes (EnergyAccumulator.__call__), shared by every set as the reference's reset gives them
     key = int(np.random.randint(0, 2**31 - 1)) if enacc.seed is None else enacc.seed + enacc._calls
-    if dev.ndet > 1 or "wf1det_coeff" in _opt_keys(pgrad_acc):
+    if dev.has_j3:  # (correlated_route admits a three-body handle with three_body_device=True alone)
+        dc, cc = wf.wf_factors[0].parameters["det_coeff"], wf.wf_factors[2].parameters["ccoeff"]
+        det_coeff = np.stack([s.get("wf1det_coeff", dc) for s in sets])
+        ccoeff = np.stack([s.get("wf3ccoeff", cc) for s in sets])
+        psi, en = dev.correlated_j3(det_coeff, acoeff, bcoeff, ccoeff, enacc.threshold, seed=key)
+        entry = "pqa_correlated_j3"
+    elif dev.ndet > 1 or "wf1det_coeff" in _opt_keys(pgrad_acc):
         dc = wf.wf_factors[0].parameters["det_coeff"]
         det_coeff = np.stack([s.get("wf1det_coeff", dc) for s in sets])
         psi, en = dev.correlated_md(det_coeff, acoeff, bcoeff, enacc.threshold, seed=key)

@@ -303,18 +303,38 @@ class DeviceWF:
         coefficients acoeff (K, natom, na, 2), bcoeff (K, nb, 3), every set with the same energy draws -> (logpsi (K, W), energy
         rows (K, 6, W)).  None for an array: every set uses the handle's own (K from the arrays given; 1 when none is).  The handle
         keeps its own coefficients and state; the result does not depend on ``walker_chunk`` (0: output chunks of 256 MiB)."""
-        shapes = {"det_coeff": (self.ndet,), "acoeff": (self.natom, self.na, 2), "bcoeff": (self.nb, 3)}
-        arrs = {k: None if v is None else _ffi.f64(v) for k, v in (("det_coeff", det_coeff), ("acoeff", acoeff), ("bcoeff", bcoeff))}
-        Ks = {v.shape[0] for v in arrs.values() if v is not None and v.ndim >= 1}
-        K = Ks.pop() if len(Ks) == 1 else (1 if not Ks and all(v is None for v in arrs.values()) else None)
-        for name, v in arrs.items():
-            if K is None or (v is not None and v.shape != (K,) + shapes[name]):
-                raise ValueError(f"{name}: (K,) + {shapes[name]} expected with one K for all arrays, got {None if v is None else v.shape}")
+        arrs, K = self._coef_set_arrays(det_coeff=det_coeff, acoeff=acoeff, bcoeff=bcoeff)
         logpsi, en = np.empty((K, self.W)), np.empty((K, 6, self.W))
         rot = None if rot is None else _ffi.f64(rot)
         unif = None if unif is None else _ffi.f64(unif)
         self.call("pqa_correlated_md", int(K), _ffi.ptr(arrs["det_coeff"]), _ffi.ptr(arrs["acoeff"]), _ffi.ptr(arrs["bcoeff"]), float(threshold),
                   _ffi.ptr(rot), _ffi.ptr(unif), int(seed), int(walker_chunk), _ffi.ptr(logpsi), _ffi.ptr(en))
+        return logpsi, en
+
+    def _coef_set_arrays(self, **given):
+        """The coefficient arrays of ``correlated_md`` / ``correlated_j3`` (name -> array or None) as float64 with their shapes
+        checked -> ({name: array or None}, K): K from the arrays given, 1 when none is."""
+        shapes = {"det_coeff": (self.ndet,), "acoeff": (self.natom, self.na, 2), "bcoeff": (self.nb, 3),
+                  "ccoeff": (self.natom, self.na3, self.na3, self.nb3, 3)}
+        arrs = {k: None if v is None else _ffi.f64(v) for k, v in given.items()}
+        Ks = {v.shape[0] for v in arrs.values() if v is not None and v.ndim >= 1}
+        K = Ks.pop() if len(Ks) == 1 else (1 if not Ks and all(v is None for v in arrs.values()) else None)
+        for name, v in arrs.items():
+            if K is None or (v is not None and v.shape != (K,) + shapes[name]):
+                raise ValueError(f"{name}: (K,) + {shapes[name]} expected with one K for all arrays, got {None if v is None else v.shape}")
+        return arrs, K
+
+    def correlated_j3(self, det_coeff=None, acoeff=None, bcoeff=None, ccoeff=None, threshold=10.0, rot=None, unif=None, seed=0, walker_chunk=0):
+        """``pqa_correlated_j3``: ``correlated_md`` for a handle with a three-body Jastrow factor, with K sets of its coefficients
+        ccoeff (K, natom, na3, na3, nb3, 3) as well (symmetrised per set as the handle's own are).  None for an array: every set
+        uses the handle's own.  The handle keeps its own coefficients and state; the result does not depend on ``walker_chunk``."""
+        arrs, K = self._coef_set_arrays(det_coeff=det_coeff, acoeff=acoeff, bcoeff=bcoeff, ccoeff=ccoeff)
+        logpsi, en = np.empty((K, self.W)), np.empty((K, 6, self.W))
+        rot = None if rot is None else _ffi.f64(rot)
+        unif = None if unif is None else _ffi.f64(unif)
+        self.call("pqa_correlated_j3", int(K), _ffi.ptr(arrs["det_coeff"]), _ffi.ptr(arrs["acoeff"]), _ffi.ptr(arrs["bcoeff"]),
+                  _ffi.ptr(arrs["ccoeff"]), float(threshold), _ffi.ptr(rot), _ffi.ptr(unif), int(seed), int(walker_chunk), _ffi.ptr(logpsi),
+                  _ffi.ptr(en))
         return logpsi, en
 
     def _sr_call(self, entry, src, pos, nodal_cutoff, weights, threshold, rot, unif, seed, per_walker, tail=None, chunk=None, dp_walker=False,
@@ -1265,6 +1285,34 @@ def linear_det_jastrow_device(wf, keys, why=None):
             reason = "three-body Jastrow factor"
         elif not set(keys) <= LINEAR_DET_KEYS:
             reason = f"parameters outside {sorted(LINEAR_DET_KEYS)}: {sorted(set(keys) - LINEAR_DET_KEYS)}"
+    if reason is not None:
+        if why is not None:
+            why.append(reason)
+        return None
+    return dev
+
+
+LINEAR_J3_KEYS = LINEAR_DET_KEYS | {"wf3ccoeff"}  # the parameters ``pqa_correlated_j3`` varies
+
+
+def linear_j3_device(wf, keys, why=None):
+    """The device handle ``pqa_correlated_j3`` can evaluate ``wf`` on while the parameters ``keys`` vary, or None: ``wf`` must be
+    exactly Slater x JastrowSpin x ThreeBodyJastrow on one handle, real and untwisted, with one or more determinants, and ``keys``
+    within ``LINEAR_J3_KEYS``.  ``why``: a list that receives the reason for a None."""
+    f = getattr(wf, "wf_factors", None)
+    reason, dev = None, None
+    if f is None or len(f) != 3 or type(f[0]) is not Slater or type(f[1]) is not JastrowSpin or type(f[2]) is not ThreeBodyJastrow:
+        reason = "the wave function is not Slater x two-body Jastrow (JastrowSpin) x three-body Jastrow (ThreeBodyJastrow) on one device handle"
+    else:
+        dev = wf.fused_device()
+        if dev is None:
+            reason = "the wave function has no fused device handle"
+        elif dev.cplx or dev.twisted:
+            reason = "complex orbitals / twisted cell"
+        elif not dev.has_j3:
+            reason = "the device handle has no three-body Jastrow factor"
+        elif not set(keys) <= LINEAR_J3_KEYS:
+            reason = f"parameters outside {sorted(LINEAR_J3_KEYS)}: {sorted(set(keys) - LINEAR_J3_KEYS)}"
     if reason is not None:
         if why is not None:
             why.append(reason)

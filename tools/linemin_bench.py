@@ -14,6 +14,12 @@
 systems.random_determinants over random_mf(nvirt=6) orbitals; --system water | cluster), det_coeff, acoeff and bcoeff varying:
 evaluation_route="fused" (pqa_correlated_md) against "protocol" on the same handle in one process, alternately, each after a
 warm-up, --repeats timed calls of each; the rows are appended to --out.
+
+    python tools/linemin_bench.py --three-body [--ndet 50] [--walkers 2048 16384]
+
+--three-body: the same comparison for a Slater x two-body x three-body Jastrow wave function (config C4 with --ndet 50; --ndet 0 or 1:
+single-determinant water), ccoeff varying as well: three_body_device=True (pqa_correlated_j3) against evaluation_route="protocol",
+the per-set loop it replaces; default walker counts 2048 and 16384; the rows are appended to --out.
 """
 
 import argparse
@@ -73,29 +79,32 @@ def correlated(W, npts, fused_only):
     return rows
 
 
-def correlated_md(W, npts, ndet, system, fused_only, repeats):
+def correlated_md(W, npts, ndet, system, fused_only, repeats, three_body=False):
     mol = systems.water() if system == "water" else systems.water_cluster()
     mf = systems.random_mf(mol, nvirt=6)
-    wf = pa.generate_wf(mol, mf, determinants=systems.random_determinants(mol, mf, ndet))
+    wf = pa.generate_wf(mol, mf, determinants=systems.random_determinants(mol, mf, ndet) if ndet > 0 else None, jastrow3=three_body)
     rng = np.random.default_rng(11)
     ja = wf.wf_factors[1].parameters
     wf.parameters["wf2acoeff"] = 0.05 * rng.standard_normal(np.shape(ja["acoeff"]))
     wf.parameters["wf2bcoeff"] = np.concatenate([np.asarray(ja["bcoeff"])[:1], 0.05 * rng.standard_normal((np.shape(ja["bcoeff"])[0] - 1, 3))])
+    if three_body:
+        wf.parameters["wf3ccoeff"] = 0.1 * rng.standard_normal(np.shape(wf.wf_factors[2].parameters["ccoeff"]))
     configs = OpenConfigs(systems.initial_guess(mol, W, rng=np.random.default_rng(1)).configs.copy())
     pgrad = gradient_generator(mol, wf, pwf.default_to_opt(wf))
     params = _params(wf, pgrad, npts)
     wf.recompute(configs)
     routes = ["fused"] if fused_only else ["fused", "protocol"]
     for route in routes:  # (warm-up)
-        linemin.correlated_compute_worker(wf, configs, params[:3], pgrad, [0, 1], evaluation_route=route)
+        linemin.correlated_compute_worker(wf, configs, params[:3], pgrad, [0, 1], evaluation_route=route, three_body_device=three_body)
     rows = []
     for rep in range(repeats):
         for route in routes:
             t0 = time.perf_counter()
-            res = linemin.correlated_compute_worker(wf, configs, params, pgrad, [0, 1], evaluation_route=route)
+            res = linemin.correlated_compute_worker(wf, configs, params, pgrad, [0, 1], evaluation_route=route, three_body_device=three_body)
             dt = time.perf_counter() - t0
             assert res["route"] == route
-            rows.append({"what": "correlated_compute_worker", "system": "H2O" if system == "water" else "(H2O)8", "ndet": ndet,
+            rows.append({"what": "correlated_compute_worker", "system": "H2O" if system == "water" else "(H2O)8", "ndet": max(ndet, 1),
+                         "three_body": bool(three_body),
                          "ndet_unique": list(wf.fused_device().ndet_s), "walkers": W, "npts": npts, "route": route, "entry": res.get("entry"),
                          "repeat": rep, "seconds": dt, "ms_per_set": 1e3 * dt / npts,
                          "mean_total_first_last": [float(res["total"][0].mean()), float(res["total"][-1].mean())]})
@@ -149,18 +158,21 @@ def one_iteration(W, npts, correlatedoptions):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--walkers", type=int, nargs="+", default=[16384, 65536])
+    ap.add_argument("--walkers", type=int, nargs="+", default=None)
     ap.add_argument("--npts", type=int, default=40)
     ap.add_argument("--fused-only", action="store_true")
     ap.add_argument("--ndet", type=int, default=0)
     ap.add_argument("--system", choices=["water", "cluster"], default="water")
     ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--three-body", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "linemin_bench.jsonl"))
     a = ap.parse_args()
+    if a.walkers is None:
+        a.walkers = [2048, 16384] if a.three_body else [16384, 65536]
     rows = []
-    if a.ndet > 0:
+    if a.ndet > 0 or a.three_body:
         for W in a.walkers:
-            rows += correlated_md(W, a.npts, a.ndet, a.system, a.fused_only, a.repeats)
+            rows += correlated_md(W, a.npts, a.ndet, a.system, a.fused_only, a.repeats, a.three_body)
         if a.out:
             with open(a.out, "a") as f:
                 for r in rows:
