@@ -328,8 +328,10 @@ int pqa_set_ecp_naip(pqa_handle_t* h, int32_t naip);
    rest with weight 1 / (nselect_random p) (downselect_move_info, jax_ecp.py:225-290); nothing is dropped when the two add up
    to the table size.  enable = 1 switches the ECP part of pqa_energy and of the energy passes of pqa_vmc_sweeps /
    pqa_dmc_steps to it, 0 back to the semi-local integrator (eval_ecp.py).  In this mode pqa_energy's `unif` is the
-   (N, W, nselect_random) table of selection uniforms (jax_ecp.py:255) and `rot` (N, necp, 3, 3) as before; pqa_vmc_sweeps /
-   pqa_dmc_steps draw both from the device streams (their tapes keep the semi-local layout and are refused).
+   (N, W, nselect_random) table of selection uniforms (jax_ecp.py:255) and `rot` (N, necp, 3, 3) as before; pqa_vmc_sweeps
+   draws both from the device streams (its tapes keep the semi-local layout and are refused); pqa_dmc_steps also takes its
+   T-MOVE candidates from this integrator (nonlocal_tmoves, jax_ecp.py:110-135: every electron's selected points whose weight is
+   not exactly 0) and takes or draws the tapes in the batched layout (pqa_dmc_tapes_t).
    pqa_ecp_batched_nselected: slots per electron (the P of the outputs below).
    pqa_ecp_batched_moves: ECPAccumulator.nonlocal_tmoves (jax_ecp.py:110-135) for electron e — the selected points' positions
    pos (W, P, 3) and T-move weights weight (W, P) = sum_l [P_l > 0] (exp(-tau v_l / P_l) - 1) P_l; rot (necp, 3, 3),
@@ -401,7 +403,14 @@ int pqa_branch_exchange(pqa_handle_t* h, const int32_t* keep_src, int64_t nkeep,
    needs must be set (the ECP ones only when the system has ECP atoms):
      gauss (nsteps,N,W,3) standard normals, unif (nsteps,N,W)                      drift-diffusion moves
      tm_rot (nsteps,N,necp,3,3), tm_unif (nsteps,N,necp,W), tm_u1, tm_u2 (nsteps,N,W)  T-move grid, mask, selection, acceptance
-     ecp_rot (nsteps+1,N,necp,3,3), ecp_unif (nsteps+1,N,necp,W)                  energy draws; index 0 = starting energy */
+     ecp_rot (nsteps+1,N,necp,3,3), ecp_unif (nsteps+1,N,necp,W)                  energy draws; index 0 = starting energy
+   With pqa_set_ecp_batched on, the members keep their names and the uniforms of the ECP integrator take its layout — what
+   pqa_energy's `unif` has in that mode: ecp_unif (nsteps+1,N,W,nselect_random) and tm_unif (nsteps,N,W,nselect_random) are the
+   selection uniforms of downselect_move_info (jax_ecp.py:255), one rotation per (electron, ECP atom) as before (atoms without
+   points ignore theirs); both may be NULL where nothing is dropped (nselect_deterministic + nselect_random >= the table size)
+   or nselect_random = 0.  gauss, unif, tm_u1 and tm_u2 are unchanged.  Without tapes the T-move selection uniforms come from
+   a Philox stream of their own, not the energy evaluations': the evaluation that closes step i and the T-moves of step i + 1
+   are keyed by the same (seed, step, walker, electron nselect_random + j). */
 typedef struct {
   const double* gauss;
   const double* unif;
@@ -568,6 +577,9 @@ int pqa_philox_tapes(pqa_handle_t* h, uint64_t seed, int step, int64_t W, double
    0..W-1, in the tape layouts above (the members of `out` point to caller-allocated HOST arrays of those shapes; tm_* may be
    NULL for systems without ECPs) — T-move grid rotations, mask uniforms, selection / acceptance uniforms, drift-diffusion
    normals and uniforms, and the energy evaluations' quadrature rotations and mask uniforms (index 0 = starting energy).
+   With pqa_set_ecp_batched on it writes the batched layouts: ecp_unif / tm_unif are the selection uniforms of the energy
+   evaluations and of the T-move tables (two different streams), written only where the selection drops points (NULL allowed
+   otherwise).
    Test entry: the CPU oracle's dmc_propagate (pyqmc/method/dmc.py:123-221) replays a device-RNG block walker by walker. */
 int pqa_philox_dmc_tapes(pqa_handle_t* h, uint64_t seed, int nsteps, int64_t W, pqa_dmc_tapes_t* out);
 

@@ -1009,21 +1009,39 @@ static __global__ __launch_bounds__(256) void k_uniform_plane(uint64_t seed, uin
   const Philox p = philox(seed, (uint32_t)w, (uint32_t)c, stream, step);
   out[idx] = u01(p.c[0], p.c[1]);
 }
+// out[e][w][j] = the uniform of Philox(seed; walker w, counter e nsr + j, stream, step) — the selection draws of k_ecpb_fill
+static __global__ __launch_bounds__(256) void k_uniform_sel(uint64_t seed, uint32_t stream, uint32_t step, int nelec, long W, int nsr, double* __restrict__ out) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)nelec * W * nsr) return;
+  const int j = (int)(idx % nsr);
+  const long ew = idx / nsr, e = ew / W, w = ew - e * W;
+  const Philox p = philox(seed, (uint32_t)w, (uint32_t)(e * nsr + j), stream, step);
+  out[idx] = u01(p.c[0], p.c[1]);
+}
 extern "C" int pqa_philox_dmc_tapes(pqa_handle_t* h, uint64_t seed, int nsteps, int64_t W, pqa_dmc_tapes_t* out) {
   HIPCHK(hipSetDevice(h->device));
   if (W <= 0 || nsteps <= 0 || !out || !out->gauss || !out->unif) FAIL("pqa_philox_dmc_tapes: bad arguments");
   const int N = h->N, necp = h->necp;
   const size_t NW = (size_t)N * W, nrot = (size_t)N * std::max(necp, 1);
-  if (necp > 0 && (!out->ecp_rot || !out->ecp_unif)) FAIL("pqa_philox_dmc_tapes: ECP systems need ecp_rot and ecp_unif");
-  const bool tm = necp > 0 && out->tm_rot && out->tm_unif && out->tm_u1 && out->tm_u2;
+  // batched ECP integrator: ecp_unif / tm_unif are its selection uniforms, (N, W, nsr) per evaluation, and exist only where points are dropped
+  const bool batched = necp > 0 && h->ecpb_on;
+  const int nsr = batched ? h->ecpb_nsr : 0;
+  const bool selu = batched && h->ecpb_nsel < h->ecpb_npoints && nsr > 0;
+  if (necp > 0 && (!out->ecp_rot || (batched ? selu && !out->ecp_unif : !out->ecp_unif))) FAIL("pqa_philox_dmc_tapes: ECP systems need ecp_rot and ecp_unif");
+  const bool tm = necp > 0 && out->tm_rot && (batched ? !selu || out->tm_unif : out->tm_unif != nullptr) && out->tm_u1 && out->tm_u2;
   TRY(ensure(h, h->b_gauss, NW * 3 * sizeof(double)));
-  TRY(ensure(h, h->b_unif, std::max(NW, nrot * (size_t)W) * sizeof(double)));
+  TRY(ensure(h, h->b_unif, std::max(std::max(NW, nrot * (size_t)W), NW * (size_t)nsr) * sizeof(double)));
   TRY(ensure(h, h->b_rot, nrot * 9 * sizeof(double)));
   auto plane = [&](uint32_t stream, uint32_t step, size_t ncount, const double* dst) -> int {
     hipLaunchKernelGGL(k_uniform_plane, dim3((unsigned)((ncount * W + 255) / 256)), dim3(256), 0, h->stream, seed, stream, step, (long)ncount, (long)W,
                        (double*)h->b_unif.p);
     TRY(check_launch(h, "k_uniform_plane"));
     return copy_out(h, const_cast<double*>(dst), h->b_unif.p, ncount * W * sizeof(double));
+  };
+  auto sel = [&](uint32_t stream, uint32_t step, const double* dst) -> int {
+    hipLaunchKernelGGL(k_uniform_sel, dim3((unsigned)((NW * nsr + 255) / 256)), dim3(256), 0, h->stream, seed, stream, step, N, (long)W, nsr, (double*)h->b_unif.p);
+    TRY(check_launch(h, "k_uniform_sel"));
+    return copy_out(h, const_cast<double*>(dst), h->b_unif.p, NW * nsr * sizeof(double));
   };
   auto rots = [&](uint64_t sd, uint32_t step, const double* dst) -> int {
     hipLaunchKernelGGL((k_gen_rot<>), dim3((unsigned)((nrot + 63) / 64)), dim3(64), 0, h->stream, (int)nrot, sd, step, (double*)h->b_rot.p);
@@ -1033,12 +1051,14 @@ extern "C" int pqa_philox_dmc_tapes(pqa_handle_t* h, uint64_t seed, int nsteps, 
   for (int i = 0; i <= nsteps; ++i) {
     if (necp > 0) {  // energy evaluation i (0: the starting configuration; energy_dev's draws)
       TRY(rots(seed, (uint32_t)i, out->ecp_rot + (size_t)i * nrot * 9));
-      TRY(plane(PQA_STREAM_ECPMASK, (uint32_t)i, nrot, out->ecp_unif + (size_t)i * nrot * W));
+      if (!batched) TRY(plane(PQA_STREAM_ECPMASK, (uint32_t)i, nrot, out->ecp_unif + (size_t)i * nrot * W));
+      else if (selu) TRY(sel(PQA_STREAM_ECPSEL, (uint32_t)i, out->ecp_unif + (size_t)i * NW * nsr));
     }
     if (i == nsteps) break;
     if (tm) {
       TRY(rots(seed ^ 0x9E3779B97F4A7C15ull, (uint32_t)i, out->tm_rot + (size_t)i * nrot * 9));
-      TRY(plane(PQA_STREAM_TMMASK, (uint32_t)i, nrot, out->tm_unif + (size_t)i * nrot * W));
+      if (!batched) TRY(plane(PQA_STREAM_TMMASK, (uint32_t)i, nrot, out->tm_unif + (size_t)i * nrot * W));
+      else if (selu) TRY(sel(PQA_STREAM_TMSEL, (uint32_t)i, out->tm_unif + (size_t)i * NW * nsr));
       TRY(plane(PQA_STREAM_TM_U1, (uint32_t)i, (size_t)N, out->tm_u1 + (size_t)i * NW));
       TRY(plane(PQA_STREAM_TM_U2, (uint32_t)i, (size_t)N, out->tm_u2 + (size_t)i * NW));
     }

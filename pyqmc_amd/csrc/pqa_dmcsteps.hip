@@ -1,6 +1,7 @@
 // pyqmc_amd C ABI implementation (host side): the fused DMC step loop (pqa_dmc_steps) and the T-move entry (pqa_tmoves).
 // See include/pyqmc_amd.h for the contract and pqa_internal.hpp for what the units share.
 #include "pqa_internal.hpp"
+#include "pqa_tmb.hpp"
 int scan_ints(pqa_handle* h, const int* c, long* o, long n, long Wm, long* marks) {
   const long nt = (n + 1023) / 1024;
   TRY(ensure(h, h->b_tmtile, (size_t)(nt + 1) * sizeof(long)));
@@ -24,11 +25,16 @@ extern "C" int pqa_dmc_steps(pqa_handle_t* h, double tstep, int nsteps, double b
   const int navg = h->cplx ? 8 : 7;  // numbers per step in step_avg (complex: + the weighted mean of Im ecp = Im total)
   const long W = h->W;
   const int N = h->N, necp = h->necp, P = h->tm_P;
-  const bool tmoves = necp > 0 && P > 0;
+  // batched ECP integrator (pqa_set_ecp_batched): the energy passes and the T-move tables come from it, nsel slots per electron; its
+  // selection uniforms — nsr per (electron, walker) — exist only where the selection drops points
+  const bool batched = necp > 0 && h->ecpb_on;
+  const int nsel = batched ? h->ecpb_nsel : 0, nsr = batched ? h->ecpb_nsr : 0;
+  const bool selu = batched && nsel < h->ecpb_npoints && nsr > 0;
+  const bool tmoves = necp > 0 && (batched ? nsel > 0 : P > 0);
   if (tp && (!tp->gauss || !tp->unif)) FAIL("pqa_dmc_steps: a tape set needs gauss and unif");
-  if (tp && h->ecpb_on) FAIL("pqa_dmc_steps: the tapes have the semi-local ECP integrator's layout (pqa_set_ecp_batched is on)");
-  if (tp && necp > 0 && (!tp->ecp_rot || !tp->ecp_unif)) FAIL("pqa_dmc_steps: a tape set needs ecp_rot and ecp_unif for ECP systems");
-  if (tp && tmoves && (!tp->tm_rot || !tp->tm_unif || !tp->tm_u1 || !tp->tm_u2)) FAIL("pqa_dmc_steps: a tape set needs the four T-move tapes");
+  if (tp && necp > 0 && (!tp->ecp_rot || (batched ? selu && !tp->ecp_unif : !tp->ecp_unif))) FAIL("pqa_dmc_steps: a tape set needs ecp_rot and ecp_unif for ECP systems");
+  if (tp && tmoves && (!tp->tm_rot || (batched ? selu && !tp->tm_unif : !tp->tm_unif) || !tp->tm_u1 || !tp->tm_u2))
+    FAIL("pqa_dmc_steps: a tape set needs the four T-move tapes");
   h->saved_valid = false;
   const int nmo_max = std::max(std::max(h->nmo[0], h->nmo[1]), 1);
   TRY(ensure(h, h->b_newpos, (size_t)W * 3 * sizeof(double)));
@@ -61,13 +67,17 @@ extern "C" int pqa_dmc_steps(pqa_handle_t* h, double tstep, int nsteps, double b
     const size_t NW = (size_t)N * W;
     TRY(ensure(h, h->b_tmcnt, NW * sizeof(int)));
     TRY(ensure(h, h->b_tmoff, (NW + 1) * sizeof(long)));
-    TRY(ensure(h, h->b_tmpass, NW * nkw * sizeof(unsigned long long)));
+    if (!batched) TRY(ensure(h, h->b_tmpass, NW * nkw * sizeof(unsigned long long)));
+    else {  // the dense table of a step: three coordinates and a weight per slot
+      TRY(ensure(h, h->b_tmbpos, NW * nsel * 3 * sizeof(double)));
+      TRY(ensure(h, h->b_tmbwgt, NW * nsel * sizeof(double)));
+    }
     TRY(ensure(h, h->b_tmacc, NW * sizeof(int)));
     TRY(ensure(h, h->b_tmaoff, (NW + 1) * sizeof(long)));
     TRY(ensure(h, h->b_tmmarks, (size_t)(N + 1) * sizeof(long)));
     TRY(ensure(h, h->b_tmidx, NW * sizeof(int)));
     TRY(ensure(h, h->b_tmapos, NW * 3 * sizeof(double)));
-    if (tp) TRY(ensure(h, h->b_tmu, (size_t)(2 + necp) * NW * sizeof(double)));
+    if (tp) TRY(ensure(h, h->b_tmu, (size_t)(2 + (batched ? nsr : necp)) * NW * sizeof(double)));
     TRY(ensure(h, h->b_rot, nrot * 9 * sizeof(double)));
   }
   const bool lw = lw_eligible(h);
@@ -77,13 +87,16 @@ extern "C" int pqa_dmc_steps(pqa_handle_t* h, double tstep, int nsteps, double b
   double* eold = (double*)h->b_dmcold.p;
   double* r2 = (double*)h->b_dmcr2.p;
   std::vector<long> tm_accepted((size_t)nsteps, 0);
+  // the uniforms of one energy evaluation: mask uniforms (N, necp, W), or the batched integrator's selection uniforms (N, W, nsr)
+  const size_t eu_stride = batched ? (size_t)N * W * nsr : nrot * W;
+  const double* eu_tape = (tp && necp && (!batched || selu)) ? tp->ecp_unif : nullptr;
   // energy of the starting configuration (dmc.py:146-149) — or, after pqa_dmc_continue, the energies the previous call's last step
   // left in eold / v2old: what the reference itself carries from step to step (dmc.py:148-149, :199-200)
   const bool cont = h->dmc_continue;
   h->dmc_continue = false;
   if (cont && !(h->dmc_old_valid && h->dmc_old_W == W)) FAIL("pqa_dmc_continue: no previous pqa_dmc_steps call on the resident walkers' state");
   if (!cont) {
-    TRY(energy_dev(h, threshold, (tp && necp) ? tp->ecp_rot : nullptr, (tp && necp) ? tp->ecp_unif : nullptr, seed, 0u));
+    TRY(energy_dev(h, threshold, (tp && necp) ? tp->ecp_rot : nullptr, eu_tape, seed, 0u));
     hipLaunchKernelGGL((k_dmc_keep<>), gw256, dim3(256), 0, h->stream, (const double*)h->b_en.p, eold, eold + W, W);
   }
   for (int step = 0; step < nsteps; ++step) {
@@ -105,7 +118,8 @@ extern "C" int pqa_dmc_steps(pqa_handle_t* h, double tstep, int nsteps, double b
         TRY(copy_in(h, h->b_rot.p, tp->tm_rot + (size_t)step * nrot * 9, nrot * 9 * sizeof(double)));
         TRY(copy_in(h, u, tp->tm_u1 + (size_t)step * NW, NW * sizeof(double)));
         TRY(copy_in(h, u + NW, tp->tm_u2 + (size_t)step * NW, NW * sizeof(double)));
-        TRY(copy_in(h, u + 2 * NW, tp->tm_unif + (size_t)step * NW * necp, NW * necp * sizeof(double)));
+        if (!batched) TRY(copy_in(h, u + 2 * NW, tp->tm_unif + (size_t)step * NW * necp, NW * necp * sizeof(double)));
+        else if (selu) TRY(copy_in(h, u + 2 * NW, tp->tm_unif + (size_t)step * NW * nsr, NW * nsr * sizeof(double)));
         B.u1 = u; B.u2 = u + NW; B.unif = u + 2 * NW;
       } else {
         hipLaunchKernelGGL((k_gen_rot<>), dim3((unsigned)((nrot + 63) / 64)), dim3(64), 0, h->stream, (int)nrot, seed ^ 0x9E3779B97F4A7C15ull,
@@ -114,8 +128,15 @@ extern "C" int pqa_dmc_steps(pqa_handle_t* h, double tstep, int nsteps, double b
       }
       B.rot = (const double*)h->b_rot.p;
       HIPCHK(hipMemsetAsync(B.acc, 0, NW * sizeof(int), h->stream));
-      hipLaunchKernelGGL((k_tm_count<>), dim3(gw256.x, (unsigned)N), dim3(256), 0, h->stream, h->S, h->js, B, W);
-      TRY(check_launch(h, "k_tm_count"));
+      const dim3 gtmb((unsigned)((W + PQA_TMB_WB - 1) / PQA_TMB_WB));
+      if (batched) {  // every electron's selected points (k_ecpb_fill, T-move mode), then the slots that carry a weight (pqa_tmb.hpp)
+        launch_tmb_table(h, B.rot, (tp && selu) ? B.unif : nullptr, seed, (uint32_t)step, tstep, (double*)h->b_tmbpos.p, (double*)h->b_tmbwgt.p);
+        hipLaunchKernelGGL((k_tmb_count<>), gtmb, dim3(64 * PQA_TMB_WB), 0, h->stream, (const double*)h->b_tmbwgt.p, N, nsel, W, B.cnt);
+        TRY(check_launch(h, "k_ecpb_fill/k_tmb_count"));
+      } else {
+        hipLaunchKernelGGL((k_tm_count<>), dim3(gw256.x, (unsigned)N), dim3(256), 0, h->stream, h->S, h->js, B, W);
+        TRY(check_launch(h, "k_tm_count"));
+      }
       TRY(scan_ints(h, (const int*)B.cnt, B.off, (long)NW, W, d_marks));
       std::vector<long> eoff((size_t)N + 1);  // first candidate of every electron
       TRY(copy_out(h, eoff.data(), d_marks, eoff.size() * sizeof(long)));
@@ -127,8 +148,14 @@ extern "C" int pqa_dmc_steps(pqa_handle_t* h, double tstep, int nsteps, double b
         TRY(ensure(h, h->b_tmptw, (size_t)tot * sizeof(int)));
         B.pts = (double*)h->b_tpos.p; B.wgt = (double*)h->b_twgt.p; B.amp = (double*)h->b_tmamp.p; B.rat = B.amp + tot;
         B.ptw = (int*)h->b_tmptw.p;
-        hipLaunchKernelGGL((k_tm_fill<>), dim3((unsigned)W, (unsigned)N), dim3(64), 0, h->stream, h->S, h->js, B, W);
-        TRY(check_launch(h, "k_tm_fill"));
+        if (batched) {
+          hipLaunchKernelGGL((k_tmb_compact<>), gtmb, dim3(64 * PQA_TMB_WB), 0, h->stream, (const double*)h->b_tmbpos.p, (const double*)h->b_tmbwgt.p, N,
+                             nsel, W, (const long*)B.off, B.pts, B.wgt, B.ptw);
+          TRY(check_launch(h, "k_tmb_compact"));
+        } else {
+          hipLaunchKernelGGL((k_tm_fill<>), dim3((unsigned)W, (unsigned)N), dim3(64), 0, h->stream, h->S, h->js, B, W);
+          TRY(check_launch(h, "k_tm_fill"));
+        }
         const long cnt_s[2] = {tot_up, tot - tot_up}, base_s[2] = {0, tot_up};
         if (h->has_slater)
           for (int s = 0; s < 2; ++s) {
@@ -193,7 +220,7 @@ extern "C" int pqa_dmc_steps(pqa_handle_t* h, double tstep, int nsteps, double b
     EnergyOpts eo;
     eo.soa_current = lw;  // (aos_T_needed: the next step's T-moves)
     TRY(energy_dev(h, threshold, (tp && necp) ? tp->ecp_rot + (size_t)(step + 1) * nrot * 9 : nullptr,
-                   (tp && necp) ? tp->ecp_unif + (size_t)(step + 1) * nrot * W : nullptr, seed, (uint32_t)(step + 1), eo));
+                   eu_tape ? eu_tape + (size_t)(step + 1) * eu_stride : nullptr, seed, (uint32_t)(step + 1), eo));
     hipLaunchKernelGGL((k_dmc_weights<>), gw256, dim3(256), 0, h->stream, (const double*)h->b_en.p, eold, eold + W, r2, r2 + W,
                        (double*)h->b_dmcw.p, tstep, branchcut, e_trial, e_est, N, W);
     hipLaunchKernelGGL((k_dmc_averages<>), dim3(1), dim3(1024), 0, h->stream, (const double*)h->b_en.p, (const double*)h->b_dmcw.p, W,

@@ -22,6 +22,8 @@
 #include "pqa_energy.hpp"
 
 #define PQA_STREAM_ECPSEL 9u
+#define PQA_STREAM_TMSEL 10u  // the T-move tables of pqa_dmc_steps (pqa_tmb.hpp): the energy evaluation that closes step i and the T-moves of
+                              // step i + 1 share (seed, step, walker, electron nsr + j) — one stream for both would hand them the same uniforms
 
 struct EcpbArgs {
   const int* naip;     // [necp] points of atom k (0: the atom has no non-local channel to integrate)
@@ -30,9 +32,10 @@ struct EcpbArgs {
   int npoints, nsd, nsr, nsel;  // table size, deterministic / random selections, slots per electron (npoints when nothing is dropped)
   const double* selu;  // [N][W][nsr] selection uniforms, or NULL -> Philox
   int e0, e1;
-  double tau;          // > 0: T-move weights of electron e0 into out_pos / out_w (nothing goes to the EcpBuf lists)
-  double* out_pos;     // [W][nsel][3]
-  double* out_w;       // [W][nsel]
+  double tau;          // > 0: T-move weights of the electrons [e0, e1) into out_pos / out_w (nothing goes to the EcpBuf lists)
+  double* out_pos;     // [W][e1 - e0][nsel][3]
+  double* out_w;       // [W][e1 - e0][nsel]
+  uint32_t stream;     // Philox stream of the selection uniforms (0: PQA_STREAM_ECPSEL)
 };
 
 #define PQA_ECPB_WB 4
@@ -56,6 +59,7 @@ static __global__ __launch_bounds__(64 * PQA_ECPB_WB) void k_ecpb_fill(SysDev S,
   const double ax = S.atom_xyz[3 * ia], ay = S.atom_xyz[3 * ia + 1], az = S.atom_xyz[3 * ia + 2];
   const int naip = atom ? A.naip[kk] : 0, qoff = A.qoff[kk], pstart = A.pstart[kk];
   const bool down = A.nsel < A.npoints;
+  const uint32_t stream = A.stream ? A.stream : PQA_STREAM_ECPSEL;
   double loc = 0.0;
   for (int e = A.e0; e < A.e1; ++e) {
     const int s = e >= S.nup, i_s = e - s * S.nup, n_s = s ? S.ndn : S.nup;
@@ -116,7 +120,7 @@ static __global__ __launch_bounds__(64 * PQA_ECPB_WB) void k_ecpb_fill(SysDev S,
           double u;
           if (A.selu) u = A.selu[((size_t)e * W + w) * A.nsr + j];
           else {
-            const Philox p = philox(B.seed, (uint32_t)w, (uint32_t)(e * A.nsr + j), PQA_STREAM_ECPSEL, B.step);
+            const Philox p = philox(B.seed, (uint32_t)w, (uint32_t)(e * A.nsr + j), stream, B.step);
             u = u01(p.c[0], p.c[1]);
           }
           int c = 0;  // this atom's points whose cumulative probability lies below u (jax_ecp.py:254-257)
@@ -164,7 +168,7 @@ static __global__ __launch_bounds__(64 * PQA_ECPB_WB) void k_ecpb_fill(SysDev S,
               const double pl = (2 * c + 1) * legendre_l(c, cosv) * qw;
               if (pl > 0.0) wsum += (exp(-A.tau * (kv[c] * sc)) - 1.0) * pl;  // jax_ecp.py:124-131
             }
-            const size_t o = (size_t)w * A.nsel + base + sl;
+            const size_t o = ((size_t)w * (A.e1 - A.e0) + (e - A.e0)) * A.nsel + base + sl;
             A.out_pos[3 * o] = px; A.out_pos[3 * o + 1] = py; A.out_pos[3 * o + 2] = pz;
             A.out_w[o] = wsum;
           } else {

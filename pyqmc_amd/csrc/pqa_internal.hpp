@@ -171,7 +171,7 @@ struct pqa_handle {
   hipEvent_t tb_ev[2] = {nullptr, nullptr};     // pqa_tbdm_sweep / pqa_obdm_sweeps: a chunk's ratios produced / consumed
   hipEvent_t tune_ev[2] = {nullptr, nullptr};   // periodic k_orb: timing of the tile-size trials (tp_tune)
   DevBuf b_tpos, b_twgt, b_tlive, b_trat;
-  DevBuf b_tmcnt, b_tmoff, b_tmpass, b_tmamp, b_tmacc, b_tmidx, b_tmapos, b_tmu, b_tmtile, b_tmaoff, b_tmptw, b_tmmarks, b_dmcw, b_dmcold, b_dmcr2, b_dmcout;
+  DevBuf b_tmcnt, b_tmoff, b_tmpass, b_tmamp, b_tmacc, b_tmidx, b_tmapos, b_tmu, b_tmtile, b_tmaoff, b_tmptw, b_tmmarks, b_tmbpos, b_tmbwgt, b_dmcw, b_dmcold, b_dmcr2, b_dmcout;
   int tm_P = 0;
   int *d_ptk = nullptr, *d_pti = nullptr;
   DevBuf b_xt, b_Tt[2], b_rc[2], b_sel[2], b_auxt, b_kpart, b_rbuf, b_vbuf, b_act;  // lane-per-walker SoA mirrors (pqa_lw.hpp)

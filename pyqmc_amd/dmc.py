@@ -11,6 +11,9 @@ Accumulators besides the energy (density matrices, S^2, S(q), symmetry ratios) e
 walkers (``avg_resident(wf, weights=w)``), nothing but the means crosses the bus — or "host", the per-walker results of the fetched
 walkers weighted in NumPy.
 
+An energy accumulator with ``use_old_ecp=False`` (the batched ECP integrator, jax_ecp.py) runs on every route: the device then takes the
+energy and the T-move candidates from that integrator (csrc/pqa_tmb.hpp) and the replay tapes have its layout (``_record_tapes_batched``).
+
 ``rng`` (optional, tests) supplies the random draws to replay the reference's:
 ``normal(W)->(W,3)``, ``rand(W)->(W,)``, ``rand1()->float``, ``rot()->(3,3)``, ``random(W)->(W,)``.
 """
@@ -18,9 +21,62 @@ walkers weighted in NumPy.
 import numpy as np
 
 
-def _record_tapes(rng, nsteps, N, necp, W, tmoves):
+def _batched_selection(acc):
+    """(naip, nselect_deterministic, nselect_random) of an accumulator bound to the batched ECP integrator (``use_old_ecp=False``), else None."""
+    if getattr(acc, "use_old_ecp", True):
+        return None
+    return np.asarray(acc.ecp.naip), int(acc.ecp.nselect_deterministic), int(acc.ecp.nselect_random)
+
+
+def _record_tapes_batched(rng, nsteps, N, necp, W, tmoves, batched):
+    """``_record_tapes`` for the batched ECP integrator (jax_ecp.py).  Per evaluation and electron the reference draws one rotation for
+    every ECP atom that has points, in atom order (``evaluate_vl`` :160-222; the others get the identity here, nothing reads it), and then,
+    only when the selection drops points, ``nselect_random`` uniform vectors (``downselect_move_info`` :225-290, draw j = 0..nsr-1).
+    ``ecp_unif`` / ``tm_unif`` (..., N, W, nsr) are left out when no selection draw is made."""
+    naip, nsd, nsr = batched
+    select = nsd + nsr < int(np.sum(naip)) and nsr > 0
+    t = {"gauss": np.empty((nsteps, N, W, 3)), "unif": np.empty((nsteps, N, W))}
+    t["ecp_rot"] = np.tile(np.eye(3), (nsteps + 1, N, necp, 1, 1))
+    if select:
+        t["ecp_unif"] = np.empty((nsteps + 1, N, W, nsr))
+    if tmoves:
+        t["tm_rot"] = np.tile(np.eye(3), (nsteps, N, necp, 1, 1))
+        t["tm_u1"], t["tm_u2"] = np.empty((nsteps, N, W)), np.empty((nsteps, N, W))
+        if select:
+            t["tm_unif"] = np.empty((nsteps, N, W, nsr))
+
+    def table_draws(rot, unif, i, e):
+        for k in range(necp):
+            if naip[k] > 0:
+                t[rot][i, e, k] = rng.rot()
+        if select:
+            for j in range(nsr):
+                t[unif][i, e, :, j] = rng.random(W)
+
+    def energy_draws(i):
+        for e in range(N):
+            table_draws("ecp_rot", "ecp_unif", i, e)
+
+    energy_draws(0)
+    for i in range(nsteps):
+        if tmoves:
+            for e in range(N):
+                table_draws("tm_rot", "tm_unif", i, e)
+                t["tm_u1"][i, e] = [rng.rand1() for _ in range(W)]
+                t["tm_u2"][i, e] = rng.rand(W)
+        for e in range(N):
+            t["gauss"][i, e] = rng.normal(W)
+            t["unif"][i, e] = rng.rand(W)
+        energy_draws(i + 1)
+    return t
+
+
+def _record_tapes(rng, nsteps, N, necp, W, tmoves, batched=None):
     """Draw everything ``nsteps`` steps consume from ``rng`` in the reference's order (dmc.py:146-196) and lay it out as
-    the replay tapes of ``pqa_dmc_steps``."""
+    the replay tapes of ``pqa_dmc_steps``.  ``batched``: ``_batched_selection`` of the energy accumulator — the batched ECP
+    integrator's draws and layout (``_record_tapes_batched``)."""
+    if batched is not None and necp:
+        return _record_tapes_batched(rng, nsteps, N, necp, W, tmoves, batched)
     t = {"gauss": np.empty((nsteps, N, W, 3)), "unif": np.empty((nsteps, N, W))}
     if necp:
         t["ecp_rot"], t["ecp_unif"] = np.empty((nsteps + 1, N, necp, 3, 3)), np.empty((nsteps + 1, N, necp, W))
@@ -50,16 +106,6 @@ def _record_tapes(rng, nsteps, N, necp, W, tmoves):
     return t
 
 
-def _refuse_batched_tmoves(acc, necp):
-    """Both device step loops (all-device and one step per call) draw their T-move candidates inside ``pqa_dmc_steps`` from the semi-local
-    integrator's table (eval_ecp.compute_tmoves); an accumulator bound with ``use_old_ecp=False`` would have its ENERGY from the batched
-    integrator and its T-MOVES from the other one — refused in both, not mixed silently."""
-    if acc.has_nonlocal_moves() and necp > 0 and not getattr(acc, "use_old_ecp", True):
-        raise NotImplementedError("the device DMC driver draws its T-move candidates from the semi-local integrator's table (eval_ecp.compute_tmoves); "
-                                  "with use_old_ecp=False run the reference's pyqmc.method.dmc over the protocol objects: "
-                                  "EnergyAccumulator.nonlocal_tmoves then serves the batched candidates (INTEGRATION.md)")
-
-
 def _propagate_fused(dev, wf, configs, weights, tstep, branchcut, e_trial, e_est, nsteps, acc, name, rng, state_current=False):
     """``dmc_propagate`` through ``pqa_dmc_steps``: the whole step loop stays on the device."""
     from .energy import KEYS
@@ -67,11 +113,10 @@ def _propagate_fused(dev, wf, configs, weights, tstep, branchcut, e_trial, e_est
     W, N = configs.configs.shape[:2]
     necp = getattr(dev, "necp", 0)
     tmoves = acc.has_nonlocal_moves() and necp > 0
-    _refuse_batched_tmoves(acc, necp)
     if not state_current:  # the reference recomputes at the start of every block (dmc.py:155)
         wf.recompute(configs)
     acc.bind(dev)
-    tapes = None if rng is None else _record_tapes(rng, nsteps, N, necp, W, tmoves)
+    tapes = None if rng is None else _record_tapes(rng, nsteps, N, necp, W, tmoves, batched=_batched_selection(acc))
     w = np.ascontiguousarray(weights, dtype=np.float64)
     # like vmc_worker: the device Philox streams are keyed by a seed drawn from numpy's global generator, so
     # numpy.random.seed() controls reproducibility and ranks that seed numpy differently get independent streams
@@ -107,7 +152,6 @@ def _propagate_host_accumulators(dev, wf, configs, weights, tstep, branchcut, e_
 
     acc, name = accumulators[ekey[0]], ekey[0]
     W = configs.configs.shape[0]
-    _refuse_batched_tmoves(acc, getattr(dev, "necp", 0))
     if not state_current:
         wf.recompute(configs)
     acc.bind(dev)
@@ -116,7 +160,7 @@ def _propagate_host_accumulators(dev, wf, configs, weights, tstep, branchcut, e_
     tapes = None
     if rng is not None:
         N, necp = configs.configs.shape[1], getattr(dev, "necp", 0)
-        tapes = _record_tapes(rng, nsteps, N, necp, W, acc.has_nonlocal_moves() and necp > 0)
+        tapes = _record_tapes(rng, nsteps, N, necp, W, acc.has_nonlocal_moves() and necp > 0, batched=_batched_selection(acc))
     for i in range(nsteps):
         step_tapes = None
         if tapes is not None:  # this step's slice; the energy draws: [starting configuration (used by the first call only), this step]
@@ -164,7 +208,6 @@ def _propagate_resident_accumulators(dev, wf, configs, weights, tstep, branchcut
 
     acc, name = accumulators[ekey[0]], ekey[0]
     W = configs.configs.shape[0]
-    _refuse_batched_tmoves(acc, getattr(dev, "necp", 0))
     if not state_current:
         wf.recompute(configs)
     acc.bind(dev)
@@ -173,7 +216,7 @@ def _propagate_resident_accumulators(dev, wf, configs, weights, tstep, branchcut
     tapes = None
     if rng is not None:
         N, necp = configs.configs.shape[1], getattr(dev, "necp", 0)
-        tapes = _record_tapes(rng, nsteps, N, necp, W, acc.has_nonlocal_moves() and necp > 0)
+        tapes = _record_tapes(rng, nsteps, N, necp, W, acc.has_nonlocal_moves() and necp > 0, batched=_batched_selection(acc))
     per_step_fetch = bool(getattr(dev, "pbc", False))
     for i in range(nsteps):
         step_tapes = None

@@ -443,10 +443,24 @@ class DeviceWF:
 
     def philox_dmc_tapes(self, seed, nsteps, W, tmoves=True):
         """The draws ``dmc_steps(..., tapes=None, seed=seed)`` makes for walkers 0..W-1, as the tape dictionary ``dmc_steps`` takes
-        (``pqa_philox_dmc_tapes``): lets the CPU oracle replay a device-RNG DMC block."""
+        (``pqa_philox_dmc_tapes``): lets the CPU oracle replay a device-RNG DMC block.  A handle in batched ECP mode
+        (``set_ecp_batched``) gets that integrator's layout: ``ecp_unif`` (nsteps + 1, N, W, nsr) / ``tm_unif`` (nsteps, N, W, nsr), and
+        neither where the selection drops nothing."""
         N, necp = self.N, getattr(self, "necp", 0)
         t = {"gauss": np.empty((nsteps, N, W, 3)), "unif": np.empty((nsteps, N, W))}
-        if necp:
+        batched = getattr(self, "_ecpb", None) if necp else None
+        if batched is not None:
+            naip, nsd, nsr = batched
+            select = nsd + nsr < int(np.sum(naip)) and nsr > 0
+            t["ecp_rot"] = np.empty((nsteps + 1, N, necp, 3, 3))
+            if select:
+                t["ecp_unif"] = np.empty((nsteps + 1, N, W, nsr))
+            if tmoves:
+                t["tm_rot"] = np.empty((nsteps, N, necp, 3, 3))
+                t["tm_u1"], t["tm_u2"] = np.empty((nsteps, N, W)), np.empty((nsteps, N, W))
+                if select:
+                    t["tm_unif"] = np.empty((nsteps, N, W, nsr))
+        elif necp:
             t["ecp_rot"], t["ecp_unif"] = np.empty((nsteps + 1, N, necp, 3, 3)), np.empty((nsteps + 1, N, necp, W))
             if tmoves:
                 t["tm_rot"], t["tm_unif"] = np.empty((nsteps, N, necp, 3, 3)), np.empty((nsteps, N, necp, W))
@@ -550,11 +564,13 @@ class DeviceWF:
         """Switch the energy pass's ECP part to the batched integrator (pqa_set_ecp_batched; naip per ECP atom) or, with None, back."""
         if naip is None:
             self.call("pqa_set_ecp_batched", 0, None, 0, 0)
+            self._ecpb = None
             return
         a = np.ascontiguousarray(naip, dtype=np.int32)
         if a.shape != (self.necp,):
             raise ValueError(f"naip: one entry per ECP atom ({self.necp})")
         self.call("pqa_set_ecp_batched", 1, _ffi.ptr(a), int(nsd), int(nsr))
+        self._ecpb = (a.copy(), int(nsd), int(nsr)) if self.necp else None  # (what the tape layouts of the DMC loop follow)
 
     def ecp_batched_moves(self, e, tau, rot, unif=None, seed=0):
         """(weight (W, P), pos (W, P, 3)) of pqa_ecp_batched_moves for electron e."""
