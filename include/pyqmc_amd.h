@@ -11,6 +11,8 @@
  *  - every buffer is caller-owned, C-contiguous fp64 unless typed otherwise, and may be a
  *    host pointer OR a device pointer (copies use hipMemcpyDefault).  No pointer is
  *    retained after the call returns.
+ *  - walker indices (widx) are checked against the walker count by every entry that takes
+ *    them, host or device pointer, before anything is launched; an index outside is an error.
  *  - one handle = one walker shard on one device, one HIP stream, not re-entrant
  *    (same as the reference objects, which hold mutable per-walker state).
  *  - electrons are ordered all spin-up then all spin-down (slater.py:236-239).

@@ -1,6 +1,7 @@
 // pyqmc_amd C ABI implementation (host side): parameters, the walker state and the protocol entry points.  See
 // include/pyqmc_amd.h for the contract; pqa_create.hip builds and destroys the handle.
 #include "pqa_internal.hpp"
+#include "pqa_stage.hpp"
 
 // ---------------------------------------------------------------- parameters
 extern "C" int pqa_set_param(pqa_handle_t* h, const char* name, const double* data, int64_t n) {
@@ -255,25 +256,18 @@ extern "C" int pqa_slater_eval(pqa_handle_t* h, int e, const double* pts, int64_
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_slater || h->W == 0) FAIL("Slater state not initialised (call recompute)");
-  if (e < 0 || e >= h->N) FAIL("electron index out of range");
   if (ncomp != 1 && ncomp != 5) FAIL("ncomp must be 1 or 5");
-  if (nrow <= 0 || npt <= 0) return 0;
-  if (!widx && nrow != h->W) FAIL("nrow must equal the number of walkers when widx is NULL");
+  StagedPoints in;
+  TRY(stage_eval(h, "pqa_slater_eval", h->W, e, pts, nrow, npt, widx, 0, &in));
+  if (!in.P) return 0;
   const int s = e >= h->nup, nmo = h->nmo[s];
-  const long P = nrow * npt;
+  const long P = in.P;
+  const int* dw = in.widx;
   h->saved_valid = false;
-  TRY(ensure(h, h->b_pts, (size_t)P * 3 * sizeof(double)));
   TRY(ensure(h, h->b_motmp, (size_t)P * ncomp * nmo * sizeof(double)));
   const size_t cf = h->cplx ? 2 : 1;
   TRY(ensure(h, h->b_out, cf * (size_t)P * ncomp * sizeof(double)));
-  TRY(copy_in(h, h->b_pts.p, pts, (size_t)P * 3 * sizeof(double)));
-  const int* dw = nullptr;
-  if (widx) {
-    TRY(ensure(h, h->b_widx, (size_t)nrow * sizeof(int)));
-    TRY(copy_in(h, h->b_widx.p, widx, (size_t)nrow * sizeof(int)));
-    dw = (const int*)h->b_widx.p;
-  }
-  TRY(launch_orb(h, s, plain_points((const double*)h->b_pts.p, P), P, ncomp, (double*)h->b_motmp.p));
+  TRY(launch_orb(h, s, plain_points(in.pts, P), P, ncomp, (double*)h->b_motmp.p));
   const dim3 grid((unsigned)nrow), block(64);
   if (h->cplx) {
     if (ncomp == 1)
@@ -301,40 +295,30 @@ extern "C" int pqa_testvalue_many(pqa_handle_t* h, const int32_t* es, int ne, co
   HIPCHK(hipSetDevice(h->device));
   if (h->W == 0) FAIL("state not initialised (call recompute)");
   if (nrow <= 0 || ne <= 0) return 0;
-  if (!widx && nrow != h->W) FAIL("nrow must equal the number of walkers when widx is NULL");
   if ((factors & 1) && !h->has_slater) FAIL("handle has no Slater factor");
   if ((factors & 2) && !h->has_j2) FAIL("handle has no two-body Jastrow factor");
   if ((factors & 4) && !h->has_j3) FAIL("handle has no three-body Jastrow factor");
   if (!(factors & 7)) FAIL("no factor selected");
-  std::vector<int> he((size_t)ne);
-  HIPCHK(hipMemcpy(he.data(), es, (size_t)ne * sizeof(int), hipMemcpyDefault));
-  for (int e : he)
-    if (e < 0 || e >= h->N) FAIL("electron index out of range");
+  const int* des;
+  StagedPoints in;
+  TRY(stage_points(h, "pqa_testvalue_many", h->W, pts, nrow, 1, widx, &in));
+  TRY(stage_electrons(h, "pqa_testvalue_many", es, ne, &des));
+  const int* dw = in.widx;
   h->saved_valid = false;
-  TRY(ensure(h, h->b_pts, (size_t)nrow * 3 * sizeof(double)));
   const size_t cf = h->cplx ? 2 : 1;  // complex handles return (re, im) pairs
   TRY(ensure(h, h->b_out, cf * nrow * ne * sizeof(double)));
-  TRY(ensure(h, h->b_tves, (size_t)ne * sizeof(int)));
-  TRY(copy_in(h, h->b_pts.p, pts, (size_t)nrow * 3 * sizeof(double)));
-  TRY(copy_in(h, h->b_tves.p, he.data(), (size_t)ne * sizeof(int)));
-  const int* dw = nullptr;
-  if (widx) {
-    TRY(ensure(h, h->b_widx, (size_t)nrow * sizeof(int)));
-    TRY(copy_in(h, h->b_widx.p, widx, (size_t)nrow * sizeof(int)));
-    dw = (const int*)h->b_widx.p;
-  }
   if (factors & 1)
     for (int s = 0; s < 2; ++s) {
       TRY(ensure(h, h->b_emo[s], (size_t)nrow * std::max(h->nmo[s], 1) * sizeof(double)));
-      TRY(launch_orb(h, s, plain_points((const double*)h->b_pts.p, nrow), nrow, 1, (double*)h->b_emo[s].p));
+      TRY(launch_orb(h, s, plain_points(in.pts, nrow), nrow, 1, (double*)h->b_emo[s].p));
     }
   if (h->cplx)
     hipLaunchKernelGGL(k_testvalue_many<true>, dim3((unsigned)nrow), dim3(64), 2 * lds_det(h, 1), h->stream, h->S, h->st, h->js,
-                       (const int*)h->b_tves.p, ne, (const double*)h->b_pts.p, (const double*)h->b_emo[0].p,
+                       des, ne, in.pts, (const double*)h->b_emo[0].p,
                        (const double*)h->b_emo[1].p, (long)nrow, dw, factors, (double*)h->b_out.p);
   else
     hipLaunchKernelGGL(k_testvalue_many<false>, dim3((unsigned)nrow), dim3(64), lds_det(h, 1), h->stream, h->S, h->st, h->js,
-                       (const int*)h->b_tves.p, ne, (const double*)h->b_pts.p, (const double*)h->b_emo[0].p,
+                       des, ne, in.pts, (const double*)h->b_emo[0].p,
                        (const double*)h->b_emo[1].p, (long)nrow, dw, factors, (double*)h->b_out.p);
   TRY(check_launch(h, "k_testvalue_many"));
   return copy_out(h, out, h->b_out.p, cf * nrow * ne * sizeof(double));
@@ -395,21 +379,17 @@ extern "C" int pqa_slater_update(pqa_handle_t* h, int e, const double* epos, con
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_slater || h->W == 0) FAIL("Slater state not initialised (call recompute)");
-  if (e < 0 || e >= h->N) FAIL("electron index out of range");
-  const int s = e >= h->nup, nmo = h->nmo[s];
   const long W = h->W;
-  if (!(use_saved && h->saved_valid && h->saved_e == e)) {
-    TRY(ensure(h, h->b_pts, (size_t)W * 3 * sizeof(double)));
+  const bool saved = use_saved && h->saved_valid && h->saved_e == e;  // the orbital rows are in b_motmp: the positions are not needed
+  const double* dx = nullptr;
+  const uint8_t* dm;
+  TRY(stage_move(h, "pqa_slater_update", W, e, epos, mask, saved ? nullptr : &dx, &dm));
+  const int s = e >= h->nup, nmo = h->nmo[s];
+  if (!saved) {
     TRY(ensure(h, h->b_motmp, (size_t)W * 5 * nmo * sizeof(double)));
-    TRY(copy_in(h, h->b_pts.p, epos, (size_t)W * 3 * sizeof(double)));
-    TRY(launch_orb(h, s, plain_points((const double*)h->b_pts.p, W), W, 5, (double*)h->b_motmp.p));
+    TRY(launch_orb(h, s, plain_points(dx, W), W, 5, (double*)h->b_motmp.p));
   }
   h->saved_valid = false;
-  const uint8_t* dm = nullptr;
-  if (mask) {
-    TRY(copy_in(h, h->b_mask.p, mask, (size_t)W));
-    dm = (const uint8_t*)h->b_mask.p;
-  }
   if (h->cplx) hipLaunchKernelGGL((k_sm_update_c<>), dim3((unsigned)W), dim3(64), 2 * lds_sm(h), h->stream, h->S, h->st, e,
                                   (const double*)h->b_motmp.p, 5 * nmo, dm, 1);
   else hipLaunchKernelGGL((k_sm_update<>), dim3((unsigned)W), dim3(64), lds_sm(h), h->stream, h->S, h->st, e, (const double*)h->b_motmp.p,
@@ -472,23 +452,13 @@ static int jastrow_eval_parts(pqa_handle_t* h, int parts, int e, const double* p
                               int mode, double* out) {
   HIPCHK(hipSetDevice(h->device));
   if (!((parts & 1) ? h->has_j2 : h->has_j3) || h->W == 0) FAIL("Jastrow state not initialised (call recompute)");
-  if (e < 0 || e >= h->N) FAIL("electron index out of range");
-  if (mode < 0 || mode > 2 || (mode > 0 && npt != 1)) FAIL("bad mode / npt combination");
-  if (nrow <= 0 || npt <= 0) return 0;
-  if (!widx && nrow != h->W) FAIL("nrow must equal the number of walkers when widx is NULL");
-  const long P = nrow * npt;
-  const size_t nout = mode == 0 ? (size_t)P : (size_t)4 * nrow;
-  TRY(ensure(h, h->b_pts, (size_t)P * 3 * sizeof(double)));
+  StagedPoints in;
+  TRY(stage_eval(h, (parts & 1) ? "pqa_jastrow_eval" : "pqa_j3_eval", h->W, e, pts, nrow, npt, widx, mode, &in));
+  if (!in.P) return 0;
+  const size_t nout = mode == 0 ? (size_t)in.P : (size_t)4 * nrow;
   TRY(ensure(h, h->b_out, nout * sizeof(double)));
-  TRY(copy_in(h, h->b_pts.p, pts, (size_t)P * 3 * sizeof(double)));
-  const int* dw = nullptr;
-  if (widx) {
-    TRY(ensure(h, h->b_widx, (size_t)nrow * sizeof(int)));
-    TRY(copy_in(h, h->b_widx.p, widx, (size_t)nrow * sizeof(int)));
-    dw = (const int*)h->b_widx.p;
-  }
-  hipLaunchKernelGGL((k_jastrow_eval<>), dim3((unsigned)nrow), dim3(64), lds_j3(h), h->stream, h->S, h->js, e, (const double*)h->b_pts.p,
-                     (long)nrow, npt, dw, mode, parts, (double*)h->b_out.p);
+  hipLaunchKernelGGL((k_jastrow_eval<>), dim3((unsigned)nrow), dim3(64), lds_j3(h), h->stream, h->S, h->js, e, in.pts,
+                     (long)nrow, npt, in.widx, mode, parts, (double*)h->b_out.p);
   TRY(check_launch(h, "k_jastrow_eval"));
   return copy_out(h, out, h->b_out.p, nout * sizeof(double));
 }
@@ -551,17 +521,15 @@ extern "C" int pqa_j3_update(pqa_handle_t* h, int e, const double* epos, const u
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_j3 || h->W == 0) FAIL("three-body Jastrow state not initialised (call recompute)");
-  if (e < 0 || e >= h->N) FAIL("electron index out of range");
-  if (h->has_j2) return 0;  // coordinates are moved by the two-body factor's update
-  const long W = h->W;
-  TRY(ensure(h, h->b_newpos, (size_t)W * 3 * sizeof(double)));
-  TRY(copy_in(h, h->b_newpos.p, epos, (size_t)W * 3 * sizeof(double)));
-  const uint8_t* dm = nullptr;
-  if (mask) {
-    TRY(copy_in(h, h->b_mask.p, mask, (size_t)W));
-    dm = (const uint8_t*)h->b_mask.p;
+  if (h->has_j2) {  // coordinates are moved by the two-body factor's update: nothing to stage, a bad index is an error all the same
+    if (e < 0 || e >= h->N) FAIL("pqa_j3_update: electron index out of range");
+    return 0;
   }
-  hipLaunchKernelGGL((k_move_x<>), dim3((unsigned)((W + 255) / 256)), dim3(256), 0, h->stream, h->js, h->N, e, (const double*)h->b_newpos.p, dm, W);
+  const long W = h->W;
+  const double* dx;
+  const uint8_t* dm;
+  TRY(stage_move(h, "pqa_j3_update", W, e, epos, mask, &dx, &dm));
+  hipLaunchKernelGGL((k_move_x<>), dim3((unsigned)((W + 255) / 256)), dim3(256), 0, h->stream, h->js, h->N, e, dx, dm, W);
   TRY(check_launch(h, "k_move_x"));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
@@ -572,17 +540,12 @@ extern "C" int pqa_jastrow_update(pqa_handle_t* h, int e, const double* epos, co
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_j2 || h->W == 0) FAIL("Jastrow state not initialised (call recompute)");
-  if (e < 0 || e >= h->N) FAIL("electron index out of range");
   const long W = h->W;
+  const double* dx;
+  const uint8_t* dm;
+  TRY(stage_move(h, "pqa_jastrow_update", W, e, epos, mask, &dx, &dm));
   TRY(jas_refresh(h));
-  TRY(ensure(h, h->b_newpos, (size_t)W * 3 * sizeof(double)));
-  TRY(copy_in(h, h->b_newpos.p, epos, (size_t)W * 3 * sizeof(double)));
-  const uint8_t* dm = nullptr;
-  if (mask) {
-    TRY(copy_in(h, h->b_mask.p, mask, (size_t)W));
-    dm = (const uint8_t*)h->b_mask.p;
-  }
-  hipLaunchKernelGGL((k_jastrow_update<>), dim3((unsigned)W), dim3(64), 0, h->stream, h->S, h->js, e, (const double*)h->b_newpos.p, dm);
+  hipLaunchKernelGGL((k_jastrow_update<>), dim3((unsigned)W), dim3(64), 0, h->stream, h->S, h->js, e, dx, dm);
   TRY(check_launch(h, "k_jastrow_update"));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
@@ -597,19 +560,18 @@ extern "C" int pqa_wf_eval(pqa_handle_t* h, int e, const double* pts, int jmode,
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_slater || !h->has_j2 || h->has_j3 || h->cplx || h->W == 0) FAIL("pqa_wf_eval: a real Slater x two-body-Jastrow product with resident walkers");
-  if (e < 0 || e >= h->N) FAIL("electron index out of range");
   if (jmode != 1 && jmode != 2) FAIL("jmode: 1 (Jastrow gradient + value) or 2 (gradient + laplacian)");
-  const int s = e >= h->nup, nmo = h->nmo[s];
   const long W = h->W;
+  StagedPoints in;  // one point per resident walker
+  TRY(stage_eval(h, "pqa_wf_eval", W, e, pts, W, 1, nullptr, jmode, &in));
+  const int s = e >= h->nup, nmo = h->nmo[s];
   h->saved_valid = false;
-  TRY(ensure(h, h->b_pts, (size_t)W * 3 * sizeof(double)));
   TRY(ensure(h, h->b_motmp, (size_t)W * 5 * nmo * sizeof(double)));
   TRY(ensure(h, h->b_out, (size_t)9 * W * sizeof(double)));
-  TRY(copy_in(h, h->b_pts.p, pts, (size_t)W * 3 * sizeof(double)));
-  TRY(launch_orb(h, s, plain_points((const double*)h->b_pts.p, W), W, 5, (double*)h->b_motmp.p));
+  TRY(launch_orb(h, s, plain_points(in.pts, W), W, 5, (double*)h->b_motmp.p));
   hipLaunchKernelGGL(k_slater_eval<5>, dim3((unsigned)W), dim3(64), lds_det(h, 5), h->stream, h->S, h->st, e, (const double*)h->b_motmp.p, W, 1,
                      (const int*)nullptr, (double*)h->b_out.p);
-  hipLaunchKernelGGL((k_jastrow_eval<>), dim3((unsigned)W), dim3(64), lds_j3(h), h->stream, h->S, h->js, e, (const double*)h->b_pts.p, W, 1,
+  hipLaunchKernelGGL((k_jastrow_eval<>), dim3((unsigned)W), dim3(64), lds_j3(h), h->stream, h->S, h->js, e, in.pts, W, 1,
                      (const int*)nullptr, jmode, 1, (double*)h->b_out.p + (size_t)5 * W);
   TRY(check_launch(h, "k_slater_eval / k_jastrow_eval"));
   TRY(copy_out(h, out, h->b_out.p, (size_t)9 * W * sizeof(double)));
@@ -622,24 +584,19 @@ extern "C" int pqa_wf_update(pqa_handle_t* h, int e, const double* epos, const u
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_slater || !h->has_j2 || h->has_j3 || h->cplx || h->W == 0) FAIL("pqa_wf_update: a real Slater x two-body-Jastrow product with resident walkers");
-  if (e < 0 || e >= h->N) FAIL("electron index out of range");
-  const int s = e >= h->nup, nmo = h->nmo[s];
   const long W = h->W;
+  const double* dx;
+  const uint8_t* dm;
+  TRY(stage_move(h, "pqa_wf_update", W, e, epos, mask, &dx, &dm));
+  const int s = e >= h->nup, nmo = h->nmo[s];
   TRY(jas_refresh(h));
-  TRY(ensure(h, h->b_newpos, (size_t)W * 3 * sizeof(double)));
-  TRY(copy_in(h, h->b_newpos.p, epos, (size_t)W * 3 * sizeof(double)));
   if (!(use_saved && h->saved_valid && h->saved_e == e)) {
     TRY(ensure(h, h->b_motmp, (size_t)W * 5 * nmo * sizeof(double)));
-    TRY(launch_orb(h, s, plain_points((const double*)h->b_newpos.p, W), W, 5, (double*)h->b_motmp.p));
+    TRY(launch_orb(h, s, plain_points(dx, W), W, 5, (double*)h->b_motmp.p));
   }
   h->saved_valid = false;
-  const uint8_t* dm = nullptr;
-  if (mask) {
-    TRY(copy_in(h, h->b_mask.p, mask, (size_t)W));
-    dm = (const uint8_t*)h->b_mask.p;
-  }
   hipLaunchKernelGGL((k_sm_update<>), dim3((unsigned)W), dim3(64), lds_sm(h), h->stream, h->S, h->st, e, (const double*)h->b_motmp.p, 5 * nmo, dm, 1);
-  hipLaunchKernelGGL((k_jastrow_update<>), dim3((unsigned)W), dim3(64), 0, h->stream, h->S, h->js, e, (const double*)h->b_newpos.p, dm);
+  hipLaunchKernelGGL((k_jastrow_update<>), dim3((unsigned)W), dim3(64), 0, h->stream, h->S, h->js, e, dx, dm);
   // slater.py:269-275 looks for a vanished determinant BEFORE an update; the flag of the state this call leaves is what the next
   // update of this spin needs (the caller keeps it), and it travels with the synchronisation the call ends with anyway
   TRY(ensure(h, h->b_flag, sizeof(int)));

@@ -21,6 +21,7 @@
 // row and position and rebuilds T of the touched walkers by a fresh ascending sum: no running corrections, so a chain of moves
 // agrees with a recompute of the moved walkers.
 #include "pqa_internal.hpp"
+#include "pqa_stage.hpp"
 
 namespace {
 
@@ -283,37 +284,22 @@ int gem_gemm(pqa_handle* h, const GemRows& R, long nrow, double* H) {
   return check_launch(h, "k_gem_gemm");
 }
 
-// walker indices of a call: range-checked on the host, then staged after `lead` ints of b_gem_idx
-int gem_widx(pqa_handle* h, const char* fn, const int32_t* widx, int64_t nrow, size_t lead, const int** dw) {
-  *dw = nullptr;
-  if (!widx) {
-    if (nrow != h->gem_W) FAIL(std::string(fn) + ": nrow must equal the number of walkers when widx is NULL");
-    return 0;
-  }
-  for (int64_t r = 0; r < nrow; ++r)
-    if (widx[r] < 0 || widx[r] >= h->gem_W) FAIL(std::string(fn) + ": walker index out of range");
-  TRY(ensure(h, h->b_gem_idx, (lead + (size_t)nrow) * sizeof(int)));
-  TRY(copy_in(h, (int*)h->b_gem_idx.p + lead, widx, (size_t)nrow * sizeof(int)));
-  *dw = (const int*)h->b_gem_idx.p + lead;
-  return 0;
-}
-
 // log Psi of every walker, in walker chunks that keep the rows of H below 256 MiB
 int gem_value(pqa_handle* h, double* logval) {
   const long W = h->gem_W, N = h->N, nao = h->nao;
   const long Wc = std::max<long>(1, std::min<long>(W, ((long)1 << 25) / ((N + 1) * nao)));
   TRY(ensure(h, h->b_gem_h, (size_t)Wc * (N + 1) * nao * sizeof(double)));
-  TRY(ensure(h, h->b_gem_out, (size_t)W * sizeof(double)));
+  TRY(ensure(h, h->b_out, (size_t)W * sizeof(double)));
   for (long w0 = 0; w0 < W; w0 += Wc) {
     const long n = std::min(Wc, W - w0);
     GemRows R = gem_rows(h, 2);
     R.A += (size_t)w0 * N * nao; R.T += (size_t)w0 * nao; R.nA = n * N;
     TRY(gem_gemm(h, R, n * (N + 1), (double*)h->b_gem_h.p));
     hipLaunchKernelGGL(k_gem_value, gem_grid1(n, kGemWaves), dim3(kGemThreads), 0, h->stream, R.A, R.T, (const double*)h->b_gem_h.p, n, (int)N,
-                       (int)nao, (double*)h->b_gem_out.p + w0);
+                       (int)nao, (double*)h->b_out.p + w0);
     TRY(check_launch(h, "k_gem_value"));
   }
-  return copy_out(h, logval, h->b_gem_out.p, (size_t)W * sizeof(double));
+  return copy_out(h, logval, h->b_out.p, (size_t)W * sizeof(double));
 }
 
 }  // namespace
@@ -328,10 +314,10 @@ extern "C" int pqa_geminal_set(pqa_handle_t* h, const double* gcoeff, int64_t n)
          std::to_string(h->nao));
   if (!gcoeff) FAIL("pqa_geminal_set: gcoeff is NULL");
   const size_t nn = (size_t)h->nao * h->nao;
-  TRY(ensure(h, h->b_gem_in, (size_t)n * sizeof(double)));
+  TRY(ensure(h, h->b_pts, (size_t)n * sizeof(double)));
   TRY(ensure(h, h->b_gem_g, nn * sizeof(double)));
-  TRY(copy_in(h, h->b_gem_in.p, gcoeff, (size_t)n * sizeof(double)));
-  hipLaunchKernelGGL(k_gem_sym, gem_grid1((long)nn, kGemThreads), dim3(kGemThreads), 0, h->stream, (const double*)h->b_gem_in.p, h->nao,
+  TRY(copy_in(h, h->b_pts.p, gcoeff, (size_t)n * sizeof(double)));
+  hipLaunchKernelGGL(k_gem_sym, gem_grid1((long)nn, kGemThreads), dim3(kGemThreads), 0, h->stream, (const double*)h->b_pts.p, h->nao,
                      (double*)h->b_gem_g.p);
   TRY(check_launch(h, "k_gem_sym"));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -370,26 +356,22 @@ extern "C" int pqa_geminal_eval(pqa_handle_t* h, int e, const double* pts, int64
                                 double* out) {
   HIPCHK(hipSetDevice(h->device));
   TRY(gem_ready(h, "pqa_geminal_eval", true));
-  if (e < 0 || e >= h->N) FAIL("pqa_geminal_eval: electron index out of range");
-  if (mode < 0 || mode > 2 || (mode > 0 && npt != 1)) FAIL("pqa_geminal_eval: bad mode / npt combination");
-  if (nrow <= 0 || npt <= 0) return 0;
-  if (!pts || !out) FAIL("pqa_geminal_eval: pts / out is NULL");
-  const int* dw;
-  TRY(gem_widx(h, "pqa_geminal_eval", widx, nrow, 0, &dw));
+  StagedPoints in;
+  TRY(stage_eval(h, "pqa_geminal_eval", h->gem_W, e, pts, nrow, npt, widx, mode, &in));
+  if (!in.P) return 0;
+  if (!out) FAIL("pqa_geminal_eval: out is NULL");
   h->gem_saved_valid = false;
-  const size_t nao = h->nao, P = (size_t)nrow * npt, nout = mode == 0 ? P : (size_t)4 * nrow;
+  const size_t nao = h->nao, P = (size_t)in.P, nout = mode == 0 ? P : (size_t)4 * nrow;
   const int ncomp = mode == 0 ? 1 : mode == 1 ? 4 : 5;
-  TRY(ensure(h, h->b_gem_in, P * 3 * sizeof(double)));
   TRY(ensure(h, h->b_gem_ao, (size_t)ncomp * P * nao * sizeof(double)));
   TRY(ensure(h, h->b_gem_h, (size_t)nrow * nao * sizeof(double)));
-  TRY(ensure(h, h->b_gem_out, nout * sizeof(double)));
-  TRY(copy_in(h, h->b_gem_in.p, pts, P * 3 * sizeof(double)));
-  TRY(launch_ao(h, plain_points((const double*)h->b_gem_in.p, (long)P), (long)P, ncomp, (double*)h->b_gem_ao.p));
+  TRY(ensure(h, h->b_out, nout * sizeof(double)));
+  TRY(launch_ao(h, plain_points(in.pts, (long)P), (long)P, ncomp, (double*)h->b_gem_ao.p));
   GemRows R = gem_rows(h, 0);
-  R.e = e; R.widx = dw;
+  R.e = e; R.widx = in.widx;
   TRY(gem_gemm(h, R, nrow, (double*)h->b_gem_h.p));
   hipLaunchKernelGGL(k_gem_dots, gem_grid1(nrow, kGemWaves), dim3(kGemThreads), 0, h->stream, R, (const double*)h->b_gem_h.p,
-                     (const double*)h->b_gem_ao.p, (long)nrow, (long)P, (int)nao, npt, mode, (double*)h->b_gem_out.p);
+                     (const double*)h->b_gem_ao.p, (long)nrow, (long)P, (int)nao, npt, mode, (double*)h->b_out.p);
   TRY(check_launch(h, "k_gem_dots"));
   if (keep_saved && mode == 1 && !widx) {  // the value plane, one row per walker
     TRY(ensure(h, h->b_gem_saved, (size_t)nrow * nao * sizeof(double)));
@@ -397,7 +379,7 @@ extern "C" int pqa_geminal_eval(pqa_handle_t* h, int e, const double* pts, int64
     h->gem_saved_valid = true;
     h->gem_saved_e = e;
   }
-  return copy_out(h, out, h->b_gem_out.p, nout * sizeof(double));
+  return copy_out(h, out, h->b_out.p, nout * sizeof(double));
 }
 
 extern "C" int pqa_geminal_testvalue_many(pqa_handle_t* h, const int32_t* es, int ne, const double* pts, int64_t nrow, const int32_t* widx,
@@ -405,56 +387,45 @@ extern "C" int pqa_geminal_testvalue_many(pqa_handle_t* h, const int32_t* es, in
   HIPCHK(hipSetDevice(h->device));
   TRY(gem_ready(h, "pqa_geminal_testvalue_many", true));
   if (nrow <= 0 || ne <= 0) return 0;
-  if (!es || !pts || !out) FAIL("pqa_geminal_testvalue_many: es / pts / out is NULL");
-  for (int k = 0; k < ne; ++k)
-    if (es[k] < 0 || es[k] >= h->N) FAIL("pqa_geminal_testvalue_many: electron index out of range");
-  const int* dw;
-  TRY(gem_widx(h, "pqa_geminal_testvalue_many", widx, nrow, (size_t)ne, &dw));
+  if (!out) FAIL("pqa_geminal_testvalue_many: out is NULL");
+  const int* des;
+  StagedPoints in;
+  TRY(stage_electrons(h, "pqa_geminal_testvalue_many", es, ne, &des));
+  TRY(stage_points(h, "pqa_geminal_testvalue_many", h->gem_W, pts, nrow, 1, widx, &in));
   h->gem_saved_valid = false;
   const size_t nao = h->nao, rows = (size_t)nrow * ne;
-  TRY(ensure(h, h->b_gem_idx, (size_t)ne * sizeof(int)));  // (gem_widx sized it for both when widx is given)
-  TRY(copy_in(h, h->b_gem_idx.p, es, (size_t)ne * sizeof(int)));
-  TRY(ensure(h, h->b_gem_in, (size_t)nrow * 3 * sizeof(double)));
   TRY(ensure(h, h->b_gem_ao, (size_t)nrow * nao * sizeof(double)));
   TRY(ensure(h, h->b_gem_h, rows * nao * sizeof(double)));
-  TRY(ensure(h, h->b_gem_out, rows * sizeof(double)));
-  TRY(copy_in(h, h->b_gem_in.p, pts, (size_t)nrow * 3 * sizeof(double)));
-  TRY(launch_ao(h, plain_points((const double*)h->b_gem_in.p, (long)nrow), (long)nrow, 1, (double*)h->b_gem_ao.p));
+  TRY(ensure(h, h->b_out, rows * sizeof(double)));
+  TRY(launch_ao(h, plain_points(in.pts, (long)nrow), (long)nrow, 1, (double*)h->b_gem_ao.p));
   GemRows R = gem_rows(h, 1);
-  R.es = (const int*)h->b_gem_idx.p; R.ne = ne; R.widx = dw;
+  R.es = des; R.ne = ne; R.widx = in.widx;
   TRY(gem_gemm(h, R, (long)rows, (double*)h->b_gem_h.p));
   hipLaunchKernelGGL(k_gem_dots, gem_grid1((long)rows, kGemWaves), dim3(kGemThreads), 0, h->stream, R, (const double*)h->b_gem_h.p,
-                     (const double*)h->b_gem_ao.p, (long)rows, (long)nrow, (int)nao, 1, 0, (double*)h->b_gem_out.p);
+                     (const double*)h->b_gem_ao.p, (long)rows, (long)nrow, (int)nao, 1, 0, (double*)h->b_out.p);
   TRY(check_launch(h, "k_gem_dots"));
-  return copy_out(h, out, h->b_gem_out.p, rows * sizeof(double));
+  return copy_out(h, out, h->b_out.p, rows * sizeof(double));
 }
 
 extern "C" int pqa_geminal_update(pqa_handle_t* h, int e, const double* epos, const uint8_t* mask, int use_saved) {
   HIPCHK(hipSetDevice(h->device));
   TRY(gem_ready(h, "pqa_geminal_update", true));
-  if (e < 0 || e >= h->N) FAIL("pqa_geminal_update: electron index out of range");
-  if (!epos) FAIL("pqa_geminal_update: epos is NULL");
   const long W = h->gem_W;
   const size_t nao = h->nao;
-  TRY(ensure(h, h->b_gem_in, (size_t)W * 3 * sizeof(double)));
-  TRY(copy_in(h, h->b_gem_in.p, epos, (size_t)W * 3 * sizeof(double)));
+  const double* dx;
+  const uint8_t* dm;
+  TRY(stage_move(h, "pqa_geminal_update", W, e, epos, mask, &dx, &dm));
   const double* row = (const double*)h->b_gem_saved.p;
   if (!(use_saved && h->gem_saved_valid && h->gem_saved_e == e)) {
     // value and gradient planes, as the mode-1 evaluation whose value plane the other route keeps: the same instantiation of the
     // AO kernel on the same points, so both routes write bitwise the same row
     TRY(ensure(h, h->b_gem_ao, (size_t)4 * W * nao * sizeof(double)));
-    TRY(launch_ao(h, plain_points((const double*)h->b_gem_in.p, W), W, 4, (double*)h->b_gem_ao.p));
+    TRY(launch_ao(h, plain_points(dx, W), W, 4, (double*)h->b_gem_ao.p));
     row = (const double*)h->b_gem_ao.p;
   }
   h->gem_saved_valid = false;
-  const uint8_t* dm = nullptr;
-  if (mask) {
-    TRY(ensure(h, h->b_gem_idx, (size_t)W));
-    TRY(copy_in(h, h->b_gem_idx.p, mask, (size_t)W));
-    dm = (const uint8_t*)h->b_gem_idx.p;
-  }
   hipLaunchKernelGGL(k_gem_update, gem_grid1(W * (long)nao, kGemThreads), dim3(kGemThreads), 0, h->stream, (double*)h->b_gem_a.p,
-                     (double*)h->b_gem_t.p, (double*)h->b_gem_x.p, e, row, (const double*)h->b_gem_in.p, dm, W, h->N, (int)nao);
+                     (double*)h->b_gem_t.p, (double*)h->b_gem_x.p, e, row, dx, dm, W, h->N, (int)nao);
   TRY(check_launch(h, "k_gem_update"));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
@@ -467,14 +438,14 @@ extern "C" int pqa_geminal_pgradient(pqa_handle_t* h, double* d_gcoeff) {
   const long W = h->gem_W, N = h->N, nao = h->nao, npair = nao * (nao + 1) / 2;
   // walker chunks: at most 256 MiB of derivatives on the device, and a grid z extent below 65536
   const long Wc = std::max<long>(1, std::min<long>(std::min<long>(W, 65535), ((long)1 << 25) / npair));
-  TRY(ensure(h, h->b_gem_out, (size_t)Wc * npair * sizeof(double)));
+  TRY(ensure(h, h->b_out, (size_t)Wc * npair * sizeof(double)));
   for (long w0 = 0; w0 < W; w0 += Wc) {
     const long n = std::min(Wc, W - w0);
     const dim3 grid((unsigned)((nao + 63) / 64), (unsigned)((nao + kGemPgRows - 1) / kGemPgRows), (unsigned)n);
     hipLaunchKernelGGL(k_gem_pgrad, grid, dim3(64), 0, h->stream, (const double*)h->b_gem_a.p + (size_t)w0 * N * nao,
-                       (const double*)h->b_gem_t.p + (size_t)w0 * nao, (int)N, (int)nao, npair, (double*)h->b_gem_out.p);
+                       (const double*)h->b_gem_t.p + (size_t)w0 * nao, (int)N, (int)nao, npair, (double*)h->b_out.p);
     TRY(check_launch(h, "k_gem_pgrad"));
-    TRY(copy_out(h, d_gcoeff + (size_t)w0 * npair, h->b_gem_out.p, (size_t)n * npair * sizeof(double)));
+    TRY(copy_out(h, d_gcoeff + (size_t)w0 * npair, h->b_out.p, (size_t)n * npair * sizeof(double)));
   }
   return 0;
 }

@@ -25,6 +25,7 @@
 // The masked update writes the electron's column and position and rebuilds S of the touched walkers by a fresh ascending sum: no
 // running corrections, so a chain of moves agrees with a recompute of the moved walkers.
 #include "pqa_internal.hpp"
+#include "pqa_stage.hpp"
 
 namespace {
 
@@ -201,10 +202,10 @@ int gps_ready(pqa_handle* h, const char* fn, bool state) {
 
 int gps_value(pqa_handle* h, double* logval) {
   const long W = h->gps_W;
-  TRY(ensure(h, h->b_gps_out, (size_t)W * sizeof(double)));
-  hipLaunchKernelGGL(k_gps_value, gps_grid(W), dim3(kGpsThreads), 0, h->stream, gps_dev(h), W, (double*)h->b_gps_out.p);
+  TRY(ensure(h, h->b_out, (size_t)W * sizeof(double)));
+  hipLaunchKernelGGL(k_gps_value, gps_grid(W), dim3(kGpsThreads), 0, h->stream, gps_dev(h), W, (double*)h->b_out.p);
   TRY(check_launch(h, "k_gps_value"));
-  return copy_out(h, logval, h->b_gps_out.p, (size_t)W * sizeof(double));
+  return copy_out(h, logval, h->b_out.p, (size_t)W * sizeof(double));
 }
 
 }  // namespace
@@ -250,45 +251,26 @@ extern "C" int pqa_gps_value(pqa_handle_t* h, double* logval) {
 extern "C" int pqa_gps_eval(pqa_handle_t* h, int e, const double* pts, int64_t nrow, int npt, const int32_t* widx, int mode, double* out) {
   HIPCHK(hipSetDevice(h->device));
   TRY(gps_ready(h, "pqa_gps_eval", true));
-  if (e < 0 || e >= h->N) FAIL("pqa_gps_eval: electron index out of range");
-  if (mode < 0 || mode > 2 || (mode > 0 && npt != 1)) FAIL("pqa_gps_eval: bad mode / npt combination");
-  if (nrow <= 0 || npt <= 0) return 0;
-  if (!pts || !out) FAIL("pqa_gps_eval: pts / out is NULL");
-  if (!widx && nrow != h->gps_W) FAIL("pqa_gps_eval: nrow must equal the number of walkers when widx is NULL");
-  if (widx)
-    for (int64_t r = 0; r < nrow; ++r)
-      if (widx[r] < 0 || widx[r] >= h->gps_W) FAIL("pqa_gps_eval: walker index out of range");
-  const size_t P = (size_t)nrow * npt, nout = mode == 0 ? P : (size_t)4 * nrow;
-  TRY(ensure(h, h->b_gps_in, P * 3 * sizeof(double)));
-  TRY(ensure(h, h->b_gps_out, nout * sizeof(double)));
-  TRY(copy_in(h, h->b_gps_in.p, pts, P * 3 * sizeof(double)));
-  const int* dw = nullptr;
-  if (widx) {
-    TRY(ensure(h, h->b_gps_idx, (size_t)nrow * sizeof(int)));
-    TRY(copy_in(h, h->b_gps_idx.p, widx, (size_t)nrow * sizeof(int)));
-    dw = (const int*)h->b_gps_idx.p;
-  }
-  hipLaunchKernelGGL(k_gps_eval, gps_grid(nrow), dim3(kGpsThreads), 0, h->stream, h->S, gps_dev(h), e, (const double*)h->b_gps_in.p, (long)nrow,
-                     npt, dw, mode, (double*)h->b_gps_out.p);
+  StagedPoints in;
+  TRY(stage_eval(h, "pqa_gps_eval", h->gps_W, e, pts, nrow, npt, widx, mode, &in));
+  if (!in.P) return 0;
+  if (!out) FAIL("pqa_gps_eval: out is NULL");
+  const size_t nout = mode == 0 ? (size_t)in.P : (size_t)4 * nrow;
+  TRY(ensure(h, h->b_out, nout * sizeof(double)));
+  hipLaunchKernelGGL(k_gps_eval, gps_grid(nrow), dim3(kGpsThreads), 0, h->stream, h->S, gps_dev(h), e, in.pts, (long)nrow, npt, in.widx, mode,
+                     (double*)h->b_out.p);
   TRY(check_launch(h, "k_gps_eval"));
-  return copy_out(h, out, h->b_gps_out.p, nout * sizeof(double));
+  return copy_out(h, out, h->b_out.p, nout * sizeof(double));
 }
 
 extern "C" int pqa_gps_update(pqa_handle_t* h, int e, const double* epos, const uint8_t* mask) {
   HIPCHK(hipSetDevice(h->device));
   TRY(gps_ready(h, "pqa_gps_update", true));
-  if (e < 0 || e >= h->N) FAIL("pqa_gps_update: electron index out of range");
-  if (!epos) FAIL("pqa_gps_update: epos is NULL");
   const long W = h->gps_W;
-  TRY(ensure(h, h->b_gps_in, (size_t)W * 3 * sizeof(double)));
-  TRY(copy_in(h, h->b_gps_in.p, epos, (size_t)W * 3 * sizeof(double)));
-  const uint8_t* dm = nullptr;
-  if (mask) {
-    TRY(ensure(h, h->b_gps_idx, (size_t)W));
-    TRY(copy_in(h, h->b_gps_idx.p, mask, (size_t)W));
-    dm = (const uint8_t*)h->b_gps_idx.p;
-  }
-  hipLaunchKernelGGL(k_gps_update, gps_grid(W), dim3(kGpsThreads), 0, h->stream, h->S, gps_dev(h), e, (const double*)h->b_gps_in.p, dm, W);
+  const double* dx;
+  const uint8_t* dm;
+  TRY(stage_move(h, "pqa_gps_update", W, e, epos, mask, &dx, &dm));
+  hipLaunchKernelGGL(k_gps_update, gps_grid(W), dim3(kGpsThreads), 0, h->stream, h->S, gps_dev(h), e, dx, dm, W);
   TRY(check_launch(h, "k_gps_update"));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
@@ -299,8 +281,8 @@ extern "C" int pqa_gps_pgradient(pqa_handle_t* h, double* d_alpha, double* d_xsu
   TRY(gps_ready(h, "pqa_gps_pgradient", true));
   if (!d_alpha || !d_xsupport || !d_f) FAIL("pqa_gps_pgradient: d_alpha / d_xsupport / d_f is NULL");
   const size_t W = h->gps_W, ns = h->gps_nsup;
-  TRY(ensure(h, h->b_gps_out, W * (7 * ns + 1) * sizeof(double)));
-  double* da = (double*)h->b_gps_out.p;
+  TRY(ensure(h, h->b_out, W * (7 * ns + 1) * sizeof(double)));
+  double* da = (double*)h->b_out.p;
   double *dx = da + W * ns, *df = dx + W * 6 * ns;
   hipLaunchKernelGGL(k_gps_pgrad, gps_grid((long)W), dim3(kGpsThreads), 0, h->stream, h->S, gps_dev(h), (long)W, da, dx, df);
   TRY(check_launch(h, "k_gps_pgrad"));

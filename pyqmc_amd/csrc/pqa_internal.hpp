@@ -140,17 +140,17 @@ struct pqa_handle {
   // pqa_ewald2d (pqa_ewald2d.hip): the call's tables, per-walker values of a walker chunk, the mean mode's partial sums
   DevBuf b_e2tab, b_e2out, b_e2acc;
   // Gaussian-process Jastrow factor (pqa_gps.hip), a state of its own beside the walker state above: support points (nsup, 2, 3)
-  // followed by alpha (nsup); the unit's own walkers (gps_W, N, 3), e [gps_W][N][2 nsup] and S [gps_W][2 nsup]; per-call inputs
-  // (points / new positions; walker indices / mask) and outputs.  gps_nsup == 0: pqa_gps_set has not run; gps_W == 0: no recompute yet
-  DevBuf b_gps_par, b_gps_x, b_gps_e, b_gps_s, b_gps_in, b_gps_idx, b_gps_out;
+  // followed by alpha (nsup); the unit's own walkers (gps_W, N, 3), e [gps_W][N][2 nsup] and S [gps_W][2 nsup].  Per-call inputs and
+  // outputs go through the common scratch above (pqa_stage.hpp, b_out).  gps_nsup == 0: pqa_gps_set has not run; gps_W == 0: no recompute yet
+  DevBuf b_gps_par, b_gps_x, b_gps_e, b_gps_s;
   int gps_nsup = 0;
   double gps_f = 0.0;
   long gps_W = 0;
   // AO-pair (geminal) Jastrow factor (pqa_geminal.hip), a state of its own as the one above: the symmetric G (nao, nao); the unit's
   // own walkers (gem_W, N, 3), their AO values A [gem_W][N][nao] and sums T [gem_W][nao]; the value plane a mode-1 evaluation kept
-  // for the update that follows it; per-call scratch: AO planes, the rows h = (T - a_e) G, inputs (points / positions / gcoeff),
-  // walker and electron indices or the mask, outputs.  gem_set: pqa_geminal_set has run; gem_W == 0: no recompute yet
-  DevBuf b_gem_g, b_gem_x, b_gem_a, b_gem_t, b_gem_saved, b_gem_ao, b_gem_h, b_gem_in, b_gem_idx, b_gem_out;
+  // for the update that follows it; per-call scratch of its own: AO planes, the rows h = (T - a_e) G (inputs and outputs go through the
+  // common scratch above: pqa_stage.hpp, b_pts for gcoeff, b_out).  gem_set: pqa_geminal_set has run; gem_W == 0: no recompute yet
+  DevBuf b_gem_g, b_gem_x, b_gem_a, b_gem_t, b_gem_saved, b_gem_ao, b_gem_h;
   bool gem_set = false, gem_saved_valid = false;
   int gem_saved_e = -1;
   long gem_W = 0;

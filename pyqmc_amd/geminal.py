@@ -22,23 +22,15 @@ import itertools
 import numpy as np
 
 from . import _ffi, tables
-from .wf import DeviceWF, _DeviceFactor, _DeviceParams, _mask_args, _points, _xyz
+from .wf import DeviceWF, _OwnHandle, _ScalarFactor, _mask_args, _xyz
 
 _serial = itertools.count()
 
 
-class _Push:
-    """What ``_DeviceParams`` sends an assignment to (``pqa_geminal_set``)."""
-
-    def __init__(self, owner):
-        self._owner = owner
-
-    def set_param(self, key, value):
-        self._owner._push()
-
-
-class GeminalJastrow(_DeviceFactor):
+class GeminalJastrow(_OwnHandle, _ScalarFactor):
     """``GeminalJastrow(mol)`` of geminaljastrow.py:49-68 on device ``device``; ``parameters["gcoeff"]``: nao (nao + 1) / 2 zeros."""
+
+    _entry, _handle_attr = "pqa_geminal", "_gem"
 
     def __init__(self, mol, device=0, _gem=None):
         if _gem is None:
@@ -58,60 +50,23 @@ class GeminalJastrow(_DeviceFactor):
         self._bind_parameters({"gcoeff": np.zeros(self.nao * (self.nao + 1) // 2)})
         self._push()
 
-    # ---- parameters / copies
-    def _bind_parameters(self, items):
-        self.parameters = _DeviceParams(_Push(self), items)
-
     def _push(self):
         p = _ffi.f64(self.parameters["gcoeff"]).ravel()
         self._gem.call("pqa_geminal_set", _ffi.ptr(p), p.size)
 
     def __getstate__(self):
         d = super().__getstate__()
-        d["_resident"] = self._get_state()[1] if self._W else None
         d["_saved"] = None
         return d
 
-    def __setstate__(self, d):
-        x = d.pop("_resident")
-        super().__setstate__(d)
-        self._W = 0
-        self._push()
-        if x is not None:
-            self._recompute(x)
-
-    # ---- protocol
+    # ---- protocol: the base class's, with the saved AO row (invalidated by every evaluation) threaded through
     def _recompute(self, x):
-        x = _ffi.f64(x)
-        W = x.shape[0]
-        u = np.empty(W)
-        self._gem.call("pqa_geminal_recompute", _ffi.ptr(x), W, _ffi.ptr(u))
-        self._W = W
         self._saved = None
-        return np.ones(W), u
-
-    def recompute(self, configs):
-        self._push()
-        return self._recompute(_xyz(self._gem, configs))
-
-    def value(self):
-        u = np.empty(self._W)
-        self._gem.call("pqa_geminal_value", _ffi.ptr(u))
-        return np.ones(self._W), u
+        return super()._recompute(x)
 
     def _eval(self, e, epos, mask, mode, keep=False):
-        m, _ = _mask_args(mask, self._W)
-        pts, widx, aux = _points(epos, m, self._gem)
-        nrow, npt = pts.shape[0], pts.shape[1]
-        out = np.empty(nrow * npt) if mode == 0 else np.empty((4, nrow))
         self._saved = None
-        if nrow:
-            self._gem.call("pqa_geminal_eval", int(e), _ffi.ptr(pts), nrow, npt, _ffi.ptr(widx), mode, int(keep), _ffi.ptr(out))
-        return out, nrow, npt, aux
-
-    def testvalue(self, e, epos, mask=None):
-        r, nrow, npt, aux = self._eval(e, epos, mask, 0)
-        return (r.reshape(nrow, npt) if aux else r), None
+        return super()._eval(e, epos, mask, mode, int(keep))
 
     def testvalue_many(self, e, epos, mask=None):
         """geminaljastrow.py:238-256: ratios for moving each electron of ``e`` to ``epos`` -> (nconf[mask], len(e))."""
@@ -136,21 +91,10 @@ class GeminalJastrow(_DeviceFactor):
         self._saved = ("pqa-geminal-saved", int(e), next(_serial))  # names the AO row the device kept
         return r[:3], r[3], self._saved
 
-    def gradient(self, e, epos):
-        return self._eval(e, epos, None, 1)[0][:3]
-
-    def gradient_laplacian(self, e, epos):
-        r, *_ = self._eval(e, epos, None, 2)
-        return r[:3], r[3]
-
-    def updateinternals(self, e, epos, configs, mask=None, saved_values=None):
-        _, m8 = _mask_args(mask, self._W)
-        x = _ffi.f64(_xyz(self._gem, epos))
-        if x.shape != (self._W, 3):
-            raise ValueError(f"updateinternals takes one position per walker ({self._W}, 3), got {x.shape}")
+    def _update_extra(self, e, saved_values):
         use_saved = saved_values is not None and saved_values is self._saved and saved_values[1] == int(e)
-        self._gem.call("pqa_geminal_update", int(e), _ffi.ptr(x), _ffi.ptr(m8), int(use_saved))
-        self._saved = None
+        self._saved = None  # (the update consumes the kept row)
+        return (int(use_saved),)
 
     def pgradient(self):
         out = np.empty((self._W, self.nao * (self.nao + 1) // 2))

@@ -17,21 +17,13 @@ from the resident walkers.
 import numpy as np
 
 from . import _ffi
-from .wf import DeviceWF, _DeviceFactor, _DeviceParams, _mask_args, _points, _xyz
+from .wf import DeviceWF, _OwnHandle, _ScalarFactor
 
 
-class _Push:
-    """What ``_DeviceParams`` sends an assignment to: the three parameters travel together (``pqa_gps_set``)."""
-
-    def __init__(self, owner):
-        self._owner = owner
-
-    def set_param(self, key, value):
-        self._owner._push()
-
-
-class GPSJastrow(_DeviceFactor):
+class GPSJastrow(_OwnHandle, _ScalarFactor):
     """``GPSJastrow(mol, X_support, f=100)`` of gps2.py:4-19 on device ``device``.  ``X_support``: (nsupport, 2, 3)."""
+
+    _entry, _handle_attr = "pqa_gps", "_gps"
 
     def __init__(self, mol, X_support, f=100, device=0):
         X_support = np.array(X_support, dtype=float)
@@ -44,76 +36,13 @@ class GPSJastrow(_DeviceFactor):
         self._bind_parameters({"Xsupport": X_support, "alpha": np.zeros(self.n_support), "f": np.array([f], dtype=float)})
         self._push()
 
-    # ---- parameters / copies
-    def _bind_parameters(self, items):
-        self.parameters = _DeviceParams(_Push(self), items)
-
     def _push(self):
         p = self.parameters
         X, a = _ffi.f64(p["Xsupport"]), _ffi.f64(p["alpha"])
         self._gps.call("pqa_gps_set", self.n_support, _ffi.ptr(X), _ffi.ptr(a), float(np.asarray(p["f"]).ravel()[0]))
 
-    def __getstate__(self):
-        d = super().__getstate__()
-        d["_resident"] = self._get_state()[1] if self._W else None
-        return d
-
-    def __setstate__(self, d):
-        x = d.pop("_resident")
-        super().__setstate__(d)
-        self._W = 0
-        self._push()
-        if x is not None:
-            self._recompute(x)
-
-    # ---- protocol
-    def _recompute(self, x):
-        x = _ffi.f64(x)
-        W = x.shape[0]
-        u = np.empty(W)
-        self._gps.call("pqa_gps_recompute", _ffi.ptr(x), W, _ffi.ptr(u))
-        self._W = W
-        return np.ones(W), u
-
-    def recompute(self, configs):
-        self._push()
-        return self._recompute(_xyz(self._gps, configs))
-
-    def value(self):
-        u = np.empty(self._W)
-        self._gps.call("pqa_gps_value", _ffi.ptr(u))
-        return np.ones(self._W), u
-
-    def _eval(self, e, epos, mask, mode):
-        m, _ = _mask_args(mask, self._W)
-        pts, widx, aux = _points(epos, m, self._gps)
-        nrow, npt = pts.shape[0], pts.shape[1]
-        out = np.empty(nrow * npt) if mode == 0 else np.empty((4, nrow))
-        if nrow:
-            self._gps.call("pqa_gps_eval", int(e), _ffi.ptr(pts), nrow, npt, _ffi.ptr(widx), mode, _ffi.ptr(out))
-        return out, nrow, npt, aux
-
-    def testvalue(self, e, epos, mask=None):
-        r, nrow, npt, aux = self._eval(e, epos, mask, 0)
-        return (r.reshape(nrow, npt) if aux else r), np.array([1])
-
-    def gradient_value(self, e, epos):
-        r, *_ = self._eval(e, epos, None, 1)
-        return r[:3], r[3], np.array([1])
-
-    def gradient(self, e, epos):
-        return self._eval(e, epos, None, 1)[0][:3]
-
-    def gradient_laplacian(self, e, epos):
-        r, *_ = self._eval(e, epos, None, 2)
-        return r[:3], r[3]
-
-    def updateinternals(self, e, epos, configs, mask=None, saved_values=None):
-        _, m8 = _mask_args(mask, self._W)
-        x = _ffi.f64(_xyz(self._gps, epos))
-        if x.shape != (self._W, 3):
-            raise ValueError(f"updateinternals takes one position per walker ({self._W}, 3), got {x.shape}")
-        self._gps.call("pqa_gps_update", int(e), _ffi.ptr(x), _ffi.ptr(m8))
+    def _saved_values(self):
+        return np.array([1])
 
     def pgradient(self):
         W, ns = self._W, self.n_support

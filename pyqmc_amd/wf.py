@@ -722,6 +722,132 @@ def _testvalue_many(dev, factors, e, epos, mask):
     return out if cplx else np.real(out)
 
 
+def _walker_rows(dev, epos, W):
+    """The new positions of an ``updateinternals`` call as the device takes them: float64 (W, 3), one per resident walker."""
+    x = _ffi.f64(_xyz(dev, epos))
+    if x.shape != (W, 3):
+        raise ValueError(f"updateinternals takes one position per walker ({W}, 3), got {x.shape}")
+    return x
+
+
+class _ScalarFactor(_DeviceFactor):
+    """The per-electron protocol of a real, positive factor exp(u) whose entries are ``{_entry}_recompute / _value / _eval / _update``
+    (``pqa_jastrow``, ``pqa_j3``, ``pqa_gps``, ``pqa_geminal``).  A subclass names the entry prefix and the attribute its handle
+    lives under; the walker count is the handle's unless the subclass keeps its own (``_OwnHandle``).  ``_eval``'s ``extra`` and
+    ``_update_extra`` carry an entry's further arguments (the geminal's ``keep_saved`` / ``use_saved``)."""
+
+    _entry = None
+    _handle_attr = "_dev"
+
+    @property
+    def _handle(self):
+        return getattr(self, self._handle_attr)
+
+    @property
+    def _nwalk(self):
+        return self._handle.W
+
+    @_nwalk.setter
+    def _nwalk(self, W):
+        self._handle.W = W
+
+    def _push(self):
+        self.parameters.push()
+
+    def _saved_values(self):
+        """The saved-values slot of ``testvalue`` and ``gradient_value``."""
+        return None
+
+    def _recompute(self, x):
+        x = _ffi.f64(x)
+        W = x.shape[0]
+        u = np.empty(W)
+        self._handle.call(self._entry + "_recompute", _ffi.ptr(x), W, _ffi.ptr(u))
+        self._nwalk = W
+        return np.ones(W), u
+
+    def recompute(self, configs):
+        self._push()
+        return self._recompute(_xyz(self._handle, configs))
+
+    def value(self):
+        u = np.empty(self._nwalk)
+        self._handle.call(self._entry + "_value", _ffi.ptr(u))
+        return np.ones(len(u)), u
+
+    def _eval(self, e, epos, mask, mode, *extra):
+        m, _ = _mask_args(mask, self._nwalk)
+        pts, widx, aux = _points(epos, m, self._handle)
+        nrow, npt = pts.shape[0], pts.shape[1]
+        out = np.empty(nrow * npt) if mode == 0 else np.empty((4, nrow))
+        if nrow:
+            self._handle.call(self._entry + "_eval", int(e), _ffi.ptr(pts), nrow, npt, _ffi.ptr(widx), mode, *extra, _ffi.ptr(out))
+        return out, nrow, npt, aux
+
+    def testvalue(self, e, epos, mask=None):
+        r, nrow, npt, aux = self._eval(e, epos, mask, 0)
+        return (r.reshape(nrow, npt) if aux else r), self._saved_values()
+
+    def gradient_value(self, e, epos):
+        r, *_ = self._eval(e, epos, None, 1)
+        return r[:3], r[3], self._saved_values()
+
+    def gradient(self, e, epos):
+        return self._eval(e, epos, None, 1)[0][:3]
+
+    def gradient_laplacian(self, e, epos):
+        r, *_ = self._eval(e, epos, None, 2)
+        return r[:3], r[3]
+
+    def _update_extra(self, e, saved_values):
+        """Arguments of the update entry after the mask."""
+        return ()
+
+    def updateinternals(self, e, epos, configs, mask=None, saved_values=None):
+        _, m8 = _mask_args(mask, self._nwalk)
+        x = _walker_rows(self._handle, epos, self._nwalk)
+        self._handle.call(self._entry + "_update", int(e), _ffi.ptr(x), _ffi.ptr(m8), *self._update_extra(e, saved_values))
+
+
+class _Push:
+    """What ``_DeviceParams`` sends an assignment to when a factor's parameters travel together (``pqa_gps_set``, ``pqa_geminal_set``)."""
+
+    def __init__(self, owner):
+        self._owner = owner
+
+    def set_param(self, key, value):
+        self._owner._push()
+
+
+class _OwnHandle:
+    """Mixin of a ``_ScalarFactor`` on a handle of its own (``_push()`` sends all its parameters): the factor keeps its walker count
+    in ``_W``, and a copy or pickle carries the resident walkers (``_get_state()[1]``) and recomputes from them on a fresh handle."""
+
+    @property
+    def _nwalk(self):
+        return self._W
+
+    @_nwalk.setter
+    def _nwalk(self, W):
+        self._W = W
+
+    def _bind_parameters(self, items):
+        self.parameters = _DeviceParams(_Push(self), items)
+
+    def __getstate__(self):
+        d = super().__getstate__()
+        d["_resident"] = self._get_state()[1] if self._W else None
+        return d
+
+    def __setstate__(self, d):
+        x = d.pop("_resident")
+        super().__setstate__(d)
+        self._W = 0
+        self._push()
+        if x is not None:
+            self._recompute(x)
+
+
 def orbital_sr_scope(dev):
     """None when the handle ``dev`` can form orbital-coefficient columns on the device (``pqa_sr_moments_orb``), else the reason."""
     if dev.cplx or dev.twisted:
@@ -910,7 +1036,7 @@ class Slater(_DeviceFactor):
             self.recompute(configs)
             return
         _, m8 = _mask_args(mask, self._dev.W)
-        x = _ffi.f64(_xyz(self._dev, epos))
+        x = _walker_rows(self._dev, epos, self._dev.W)
         use_saved = saved_values is not None and saved_values is self._saved and saved_values[1] == int(e)
         self._dev.call("pqa_slater_update", int(e), _ffi.ptr(x), _ffi.ptr(m8), int(use_saved))
         self._saved = None
@@ -928,9 +1054,11 @@ class Slater(_DeviceFactor):
         return inv, dets
 
 
-class JastrowSpin(_DeviceFactor):
+class JastrowSpin(_ScalarFactor):
     """One- and two-body Jastrow factor (protocol of ``pyqmc/wf/jastrowspin.py:20-419``).
     ``a_basis``/``b_basis``: lists of ``pyqmc_amd.func3d`` descriptors."""
+
+    _entry = "pqa_jastrow"
 
     def __init__(self, mol, a_basis, b_basis, device=0, _dev=None):
         self._mol = mol
@@ -941,52 +1069,9 @@ class JastrowSpin(_DeviceFactor):
         self._bind_parameters({"bcoeff": np.zeros((_dev.nb, 3)), "acoeff": np.zeros((_dev.natom, _dev.na, 2))})
         self.dtype = float
 
-    def recompute(self, configs):
-        self.parameters.push()
-        x = _ffi.f64(_xyz(self._dev, configs))
-        W = x.shape[0]
-        u = np.empty(W)
-        self._dev.call("pqa_jastrow_recompute", _ffi.ptr(x), W, _ffi.ptr(u))
-        self._dev.W = W
-        return np.ones(W), u
-
-    def value(self):
-        u = np.empty(self._dev.W)
-        self._dev.call("pqa_jastrow_value", _ffi.ptr(u))
-        return np.ones(len(u)), u
-
-    def _eval(self, e, epos, mask, mode):
-        m, _ = _mask_args(mask, self._dev.W)
-        pts, widx, aux = _points(epos, m, self._dev)
-        nrow, npt = pts.shape[0], pts.shape[1]
-        out = np.empty(nrow * npt) if mode == 0 else np.empty((4, nrow))
-        if nrow:
-            self._dev.call("pqa_jastrow_eval", int(e), _ffi.ptr(pts), nrow, npt, _ffi.ptr(widx), mode, _ffi.ptr(out))
-        return out, nrow, npt, aux
-
-    def testvalue(self, e, epos, mask=None):
-        r, nrow, npt, aux = self._eval(e, epos, mask, 0)
-        return (r.reshape(nrow, npt) if aux else r), None
-
     def testvalue_many(self, e, epos, mask=None):
         """jastrowspin.py:421-455 -> (nconf[mask], len(e))."""
         return _testvalue_many(self._dev, 2, e, epos, mask)
-
-    def gradient_value(self, e, epos):
-        r, *_ = self._eval(e, epos, None, 1)
-        return r[:3], r[3], None
-
-    def gradient(self, e, epos):
-        return self._eval(e, epos, None, 1)[0][:3]
-
-    def gradient_laplacian(self, e, epos):
-        r, *_ = self._eval(e, epos, None, 2)
-        return r[:3], r[3]
-
-    def updateinternals(self, e, epos, configs, mask=None, saved_values=None):
-        _, m8 = _mask_args(mask, self._dev.W)
-        x = _ffi.f64(_xyz(self._dev, epos))
-        self._dev.call("pqa_jastrow_update", int(e), _ffi.ptr(x), _ffi.ptr(m8))
 
     def pgradient(self):
         """jastrowspin.py:457-464: the stored sums."""
@@ -1000,12 +1085,14 @@ class JastrowSpin(_DeviceFactor):
         return a, b, x
 
 
-class ThreeBodyJastrow(_DeviceFactor):
+class ThreeBodyJastrow(_ScalarFactor):
     """Electron-electron-ion Jastrow factor (protocol of ``pyqmc/wf/three_body_jastrow.py:19-655``).
     ``a_basis``/``b_basis``: lists of ``pyqmc_amd.func3d`` descriptors; parameter ``ccoeff``
     (natom, na, na, nb, 3).  The device keeps no per-electron partial sums for this factor: the one-electron sum
     P_e is re-evaluated from the stored walker coordinates, so the result does not depend on whether the driver
     moves ``configs`` before or after ``updateinternals`` (the reference's does, see tests/golden/make_golden.py)."""
+
+    _entry = "pqa_j3"
 
     def __init__(self, mol, a_basis, b_basis, device=0, _dev=None):
         self._mol = mol
@@ -1015,33 +1102,6 @@ class ThreeBodyJastrow(_DeviceFactor):
         self._dev = _dev
         self._bind_parameters({"ccoeff": np.zeros((_dev.natom, _dev.na3, _dev.na3, _dev.nb3, 3))})
         self.dtype = float
-
-    def recompute(self, configs):
-        self.parameters.push()
-        x = _ffi.f64(_xyz(self._dev, configs))
-        W = x.shape[0]
-        u = np.empty(W)
-        self._dev.call("pqa_j3_recompute", _ffi.ptr(x), W, _ffi.ptr(u))
-        self._dev.W = W
-        return np.ones(W), u
-
-    def value(self):
-        u = np.empty(self._dev.W)
-        self._dev.call("pqa_j3_value", _ffi.ptr(u))
-        return np.ones(len(u)), u
-
-    def _eval(self, e, epos, mask, mode):
-        m, _ = _mask_args(mask, self._dev.W)
-        pts, widx, aux = _points(epos, m, self._dev)
-        nrow, npt = pts.shape[0], pts.shape[1]
-        out = np.empty(nrow * npt) if mode == 0 else np.empty((4, nrow))
-        if nrow:
-            self._dev.call("pqa_j3_eval", int(e), _ffi.ptr(pts), nrow, npt, _ffi.ptr(widx), mode, _ffi.ptr(out))
-        return out, nrow, npt, aux
-
-    def testvalue(self, e, epos, mask=None):
-        r, nrow, npt, aux = self._eval(e, epos, mask, 0)
-        return (r.reshape(nrow, npt) if aux else r), None
 
     def testvalue_many(self, e, epos, mask=None):
         """three_body_jastrow.py:343-372 -> (nconf[mask], len(e))."""
@@ -1053,22 +1113,6 @@ class ThreeBodyJastrow(_DeviceFactor):
         out = np.empty((d.W, d.natom, d.na3, d.na3, d.nb3, 3))
         d.call("pqa_j3_pgradient", _ffi.ptr(out))
         return {"ccoeff": out}
-
-    def gradient_value(self, e, epos):
-        r, *_ = self._eval(e, epos, None, 1)
-        return r[:3], r[3], None
-
-    def gradient(self, e, epos):
-        return self._eval(e, epos, None, 1)[0][:3]
-
-    def gradient_laplacian(self, e, epos):
-        r, *_ = self._eval(e, epos, None, 2)
-        return r[:3], r[3]
-
-    def updateinternals(self, e, epos, configs, mask=None, saved_values=None):
-        _, m8 = _mask_args(mask, self._dev.W)
-        x = _ffi.f64(_xyz(self._dev, epos))
-        self._dev.call("pqa_j3_update", int(e), _ffi.ptr(x), _ffi.ptr(m8))
 
 
 class Parameters:
@@ -1169,7 +1213,7 @@ class MultiplyWF:
                 _, m8 = _mask_args(mask, d.W)
                 sv = None if saved_values is None else saved_values[0]
                 use_saved = sv is not None and sv is sl._saved and sv[1] == int(e)
-                d.wf_update(e, _ffi.f64(_xyz(d, epos)), m8, use_saved, s)
+                d.wf_update(e, _walker_rows(d, epos, d.W), m8, use_saved, s)
                 sl._saved = None
                 return
         saved_values = [None] * len(self.wf_factors) if saved_values is None else saved_values
