@@ -14,6 +14,11 @@
 // The handle's coefficients are never changed.  Outputs are written per walker chunk of at most 256 MiB.
 // Several determinants, with det_coeff varying between the sets too: pqa_correlated_md / k_corr_md, further down; with a three-body
 // factor whose ccoeff varies as well: pqa_correlated_j3, the J3 instantiations of k_corr_md.
+// The three entries are one-line calls into one host driver, correlated_run, which an entry descriptor (CorrEntry) steers: one scope
+// table, one staging of the coefficient sets, one argument struct (CorrArgs) and one plan of the scratch.  The kernels stay two:
+// k_corr_energy is the default route, and its single-determinant ratios (slater_ratios) are not the bits of k_corr_md with one
+// determinant.  What they share is factored once: the contractions of the Jastrow rows (jas_contract4 / jas_contract1,
+// pqa_estim.hpp), the energy rows (corr_write_rows) and, between the two three-body contractions, the column walk (j3_column).
 #include "pqa_estim.hpp"
 
 namespace {
@@ -36,20 +41,36 @@ __global__ __launch_bounds__(64) void k_corr_u(const double* __restrict__ aval, 
   }
 }
 
+// The arguments of k_corr_energy and of k_corr_md (further down), filled by corr_args and the driver.
 struct CorrArgs {
   long w0, Wc, W;           // first walker of the chunk, walkers in it, resident walkers
-  int K, P, Pa;             // sets, coefficients per set (acoeff then bcoeff), of which acoeff
-  const double* ct;         // [P][K] coefficient matrix
+  int K, K1, P, Pa;         // sets, columns of cd and c3t (K + 1), Jastrow coefficients per set (acoeff then bcoeff), of which acoeff
+  const double* ct;         // [P][K] Jastrow coefficient matrix
   const double* kc;         // [4][W] rows ke, ee, ei, grad2 of the Slater-only pass (ee, ei used)
   const double* local;      // [W] local ECP channel
-  const double* econ[2];    // per spin: Slater-weighted point values
+  const double* econ[2];    // per spin: Slater-weighted point values (k_corr_energy)
+  const double* wgt[2];     // per spin: point weights (k_corr_md)
+  const double* emo[2];     // per spin: orbital rows of the points [n][nmo_s] (k_corr_md)
   const double* pts[2];     // per spin: point positions [n][3]
   const int* pte[2];        // per spin: electron of the point
   const long* off;          // [2][nseg W + 1] list offsets (k_ecp_sum's order)
   int nseg, has_ecp;
   double ii;
   double* out;              // [K][6][Wc]
+  // k_corr_md only
+  int DP, RS, GS;           // LDS strides: unique determinants of a component, a row of rho (= 2 mod 32), a row of num
+  const double* cd;         // [ndet][K1] determinant coefficient matrix (column K: the handle's own)
+  // its three-body instantiations (J3) only
+  const double* c3t;        // [P3][K1] symmetrised three-body coefficient matrix (column K: the handle's own)
+  double* u3;               // [K1][W] three-body log value U3_k = 1/2 sum_e P_e^k(r_e)
 };
+
+// The six energy rows of set k, walker w (column bw of the chunk): ke, ee, ei, ecp = local + tot, grad2, total.
+__device__ __forceinline__ void corr_write_rows(const CorrArgs& A, long w, long bw, int k, double ke, double g2, double tot) {
+  const double ee = A.kc[A.W + w], ei = A.kc[2 * A.W + w], ec = A.has_ecp ? A.local[w] + tot : 0.0;
+  double* o = A.out + (size_t)k * 6 * A.Wc + bw;
+  o[0] = ke; o[A.Wc] = ee; o[2 * A.Wc] = ei; o[3 * A.Wc] = ec; o[4 * A.Wc] = g2; o[5 * A.Wc] = ke + ee + ei + ec + A.ii;
+}
 
 // One wave per walker (grid.x), lanes = parameter sets kb + lane (grid.y: chunks of 64 sets).  LDS: rows R[4][P] (ke_electron).
 template <bool PBC>
@@ -79,20 +100,12 @@ __global__ __launch_bounds__(64) void k_corr_energy(SysDev S, SlaterState st, Ja
           const int e = A.pte[sp][pt], s = e >= S.nup;
           const double qx = A.pts[sp][3 * pt], qy = A.pts[sp][3 * pt + 1], qz = A.pts[sp][3 * pt + 2];
           jas_diff_rows<PBC>(S, xw, e, s, qx, qy, qz, P, Pa, ira, irb, R);
-          if (act) {
-            double du = 0.0;
-            for (int q = 0; q < S.natom * S.na; ++q) { const int p = 2 * q + s; du += A.ct[(size_t)p * A.K + k] * R[p]; }
-            for (int q = 0; q < 2 * S.nb; ++q) { const int p = Pa + (q >> 1) * 3 + s + (q & 1); du += A.ct[(size_t)p * A.K + k] * R[p]; }
-            tot += A.econ[sp][pt] * exp(du);
-          }
+          if (act) tot += A.econ[sp][pt] * exp(jas_contract1(S, R, A.ct, A.K, k, s, Pa));
           __syncthreads();
         }
       }
   }
-  if (!act) return;
-  const double ee = A.kc[A.W + w], ei = A.kc[2 * A.W + w], ec = A.has_ecp ? A.local[w] + tot : 0.0;
-  double* o = A.out + (size_t)k * 6 * A.Wc + bw;
-  o[0] = ke; o[A.Wc] = ee; o[2 * A.Wc] = ei; o[3 * A.Wc] = ec; o[4 * A.Wc] = g2; o[5 * A.Wc] = ke + ee + ei + ec + A.ii;
+  if (act) corr_write_rows(A, w, bw, k, ke, g2, tot);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -131,27 +144,6 @@ __global__ __launch_bounds__(64) void k_corr_energy(SysDev S, SlaterState st, Ja
 //            electron) or num / S_k (a point) as above; the ECP
 //            points in k_ecp_sum's order (spin up then down, segment by segment, points ascending).
 // Every sum has a fixed order (k-steps, determinants, electrons, points ascending): two calls give the same bits, whatever the chunk.
-struct CorrMdArgs {
-  long w0, Wc, W;           // first walker of the chunk, walkers in it, resident walkers
-  int K, K1, P, Pa;         // sets, columns of cd (K + 1), Jastrow coefficients per set, of which acoeff
-  int DP, RS, GS;           // LDS strides: unique determinants of a component, a row of rho (= 2 mod 32), a row of num
-  const double* ct;         // [P][K] Jastrow coefficient matrix
-  const double* cd;         // [ndet][K1] determinant coefficient matrix (column K: the handle's own)
-  const double* kc;         // [4][W] rows ke, ee, ei, grad2 of the Slater-only pass (ee, ei used)
-  const double* local;      // [W] local ECP channel
-  const double* wgt[2];     // per spin: point weights
-  const double* emo[2];     // per spin: orbital rows of the points [n][nmo_s]
-  const double* pts[2];     // per spin: point positions [n][3]
-  const int* pte[2];        // per spin: electron of the point
-  const long* off;          // [2][nseg W + 1] list offsets
-  int nseg, has_ecp;
-  double ii;
-  double* out;              // [K][6][Wc]
-  // three-body instantiations (J3) only
-  const double* c3t;        // [P3][K1] symmetrised three-body coefficient matrix (column K: the handle's own)
-  double* u3;               // [K1][W] three-body log value U3_k = 1/2 sum_e P_e^k(r_e)
-};
-
 __device__ __forceinline__ double md_omega(const SysDev& S, const SlaterState& st, long w, int d, double ref) {
   const double su = st.dsign[0][w * S.ndet_s[0] + S.det_map[d]];
   const double sd = st.dsign[1][w * S.ndet_s[1] + S.det_map[S.ndet + d]];
@@ -318,52 +310,50 @@ __device__ __forceinline__ void j3_point_tables(const SysDev& S, const double* x
   j3_table_sums(S, np, L);
 }
 
+// t[c] = sum_{l m s'} c3t[(I, k, l, m, edown + s')][kcol] M_c[I][l][m][s'] for the five table slots c: the walk down column kcol of c3t
+// that both contractions make for ion I and function k (l m, then s', ascending).
+__device__ __forceinline__ void j3_column(const SysDev& S, int edown, const J3Lds& L, const double* __restrict__ c3t, int K1, int kcol, int I,
+                                          int k, double (&t)[5]) {
+  const int A = S.natom, na = S.na3, nb = S.nb3, nlm = na * nb * 2, TS = A * nlm;
+  const double* Mp = L.M + (size_t)I * nlm;
+  const double* cp = c3t + ((size_t)(I * na + k) * na * nb * 3 + edown) * K1 + kcol;
+#pragma unroll
+  for (int c = 0; c < 5; ++c) t[c] = 0.0;
+  for (int lm = 0; lm < na * nb; ++lm)
+#pragma unroll
+    for (int sp = 0; sp < 2; ++sp) {
+      const double cc = cp[(size_t)(lm * 3 + sp) * K1];
+#pragma unroll
+      for (int c = 0; c < 5; ++c) t[c] += cc * Mp[(size_t)c * TS + lm * 2 + sp];
+    }
+}
+
 // Column kcol of c3t against the value tables of np <= 5 positions: out[c] = P_e(position c); one read of each coefficient serves
 // them all (slots beyond np hold leftovers, and so do their out[c]).
 __device__ __forceinline__ void j3_contract_points(const SysDev& S, int edown, const J3Lds& L, const double* __restrict__ c3t, int K1, int kcol,
                                                    double (&out)[5]) {
-  const int A = S.natom, na = S.na3, nb = S.nb3, nlm = na * nb * 2, TS = A * nlm;
+  const int A = S.natom, na = S.na3;
 #pragma unroll
   for (int c = 0; c < 5; ++c) out[c] = 0.0;
-  for (int I = 0; I < A; ++I) {
-    const double* Mp = L.M + (size_t)I * nlm;
+  for (int I = 0; I < A; ++I)
     for (int k = 0; k < na; ++k) {
-      const double* cp = c3t + ((size_t)(I * na + k) * na * nb * 3 + edown) * K1 + kcol;
-      double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-      for (int lm = 0; lm < na * nb; ++lm)
-#pragma unroll
-        for (int sp = 0; sp < 2; ++sp) {
-          const double cc = cp[(size_t)(lm * 3 + sp) * K1];
-#pragma unroll
-          for (int c = 0; c < 5; ++c) t[c] += cc * Mp[(size_t)c * TS + lm * 2 + sp];
-        }
+      double t[5];
+      j3_column(S, edown, L, c3t, K1, kcol, I, k, t);
 #pragma unroll
       for (int c = 0; c < 5; ++c) out[c] += L.at[(c * A + I) * na + k] * t[c];
     }
-  }
 }
 
 // Column kcol of c3t against the tables of j3_tables: out[0] = P_e, out[1 .. 3] = grad P_e, out[4] = lap P_e.
 __device__ __forceinline__ void j3_contract(const SysDev& S, int edown, const J3Lds& L, const double* __restrict__ c3t, int K1, int kcol,
                                             double (&out)[5]) {
-  constexpr int NC = 5;
-  const int A = S.natom, na = S.na3, nb = S.nb3, nlm = na * nb * 2, TS = A * nlm;
+  const int A = S.natom, na = S.na3;
 #pragma unroll
-  for (int c = 0; c < NC; ++c) out[c] = 0.0;
+  for (int c = 0; c < 5; ++c) out[c] = 0.0;
   for (int I = 0; I < A; ++I) {
-    const double* Mp = L.M + (size_t)I * nlm;
     for (int k = 0; k < na; ++k) {
-      const double* cp = c3t + ((size_t)(I * na + k) * na * nb * 3 + edown) * K1 + kcol;
-      double t[NC];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) t[c] = 0.0;
-      for (int lm = 0; lm < na * nb; ++lm)
-#pragma unroll
-        for (int sp = 0; sp < 2; ++sp) {
-          const double cc = cp[(size_t)(lm * 3 + sp) * K1];
-#pragma unroll
-          for (int c = 0; c < NC; ++c) t[c] += cc * Mp[(size_t)c * TS + lm * 2 + sp];
-        }
+      double t[5];
+      j3_column(S, edown, L, c3t, K1, kcol, I, k, t);
       const double a = L.at[I * na + k], ag = L.at[(A + I) * na + k], al = L.at[(2 * A + I) * na + k];
       const double dx = L.de[3 * I], dy = L.de[3 * I + 1], dz = L.de[3 * I + 2];
       out[0] += a * t[0];
@@ -378,7 +368,7 @@ __device__ __forceinline__ void j3_contract(const SysDev& S, int edown, const J3
 // J3: the three-body instantiations (pqa_correlated_j3).  Block column blockIdx.y covers the K1 = K + 1 columns of c3t: the lane of
 // column K (the handle's own coefficients) takes part in the three-body value alone.
 template <bool PBC, bool J3>
-__global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, JastrowState js, CorrMdArgs A) {
+__global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, JastrowState js, CorrArgs A) {
   extern __shared__ double sm[];
   const int lane = threadIdx.x, i16 = lane & 15, kq = lane >> 4;
   const long bw = blockIdx.x, w = A.w0 + bw;
@@ -465,23 +455,14 @@ __global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, Jastro
         const double v = G[row * GS + lane];
         const double G0 = G[(16 + row) * GS + lane] / v, G1 = G[(32 + row) * GS + lane] / v, G2 = G[(48 + row) * GS + lane] / v;
         const double L = G[(64 + row) * GS + lane] / v;
-        double gx = 0.0, gy = 0.0, gz = 0.0, lp = 0.0;
-        for (int q = 0; q < S.natom * S.na; ++q) {
-          const int p = 2 * q + s;
-          const double c = A.ct[(size_t)p * A.K + k];
-          gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
-        }
-        for (int q = 0; q < 2 * S.nb; ++q) {
-          const int p = Pa + (q >> 1) * 3 + s + (q & 1);
-          const double c = A.ct[(size_t)p * A.K + k];
-          gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
-        }
-        if constexpr (J3) { gx += p3[1]; gy += p3[2]; gz += p3[3]; lp += p3[4]; }
-        const double lj = lp + gx * gx + gy * gy + gz * gz;
-        const double lap = L + lj + 2.0 * (G0 * gx + G1 * gy + G2 * gz);
-        const double tx = G0 + gx, ty = G1 + gy, tz = G2 + gz;
-        ke += -0.5 * lap;
-        g2 += tx * tx + ty * ty + tz * tz;
+        jas_contract4(S, R, A.ct, A.K, k, s, P, Pa, [&](double gx, double gy, double gz, double lp) {
+          if constexpr (J3) { gx += p3[1]; gy += p3[2]; gz += p3[3]; lp += p3[4]; }
+          const double lj = lp + gx * gx + gy * gy + gz * gz;
+          const double lap = L + lj + 2.0 * (G0 * gx + G1 * gy + G2 * gz);
+          const double tx = G0 + gx, ty = G1 + gy, tz = G2 + gz;
+          ke += -0.5 * lap;
+          g2 += tx * tx + ty * ty + tz * tz;
+        });
       }
       __syncthreads();
     }
@@ -547,9 +528,7 @@ __global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, Jastro
             }
             jas_diff_rows<PBC>(S, xw, e, sp, A.pts[sp][3 * pt], A.pts[sp][3 * pt + 1], A.pts[sp][3 * pt + 2], P, Pa, ira, irb, R);
             if (act) {
-              double du = 0.0;
-              for (int q = 0; q < S.natom * S.na; ++q) { const int p = 2 * q + sp; du += A.ct[(size_t)p * A.K + k] * R[p]; }
-              for (int q = 0; q < 2 * S.nb; ++q) { const int p = Pa + (q >> 1) * 3 + sp + (q & 1); du += A.ct[(size_t)p * A.K + k] * R[p]; }
+              double du = jas_contract1(S, R, A.ct, A.K, k, sp, Pa);
               if constexpr (J3) du += dp3;
               tot += A.wgt[sp][pt] * (G[row * GS + lane] * invS) * exp(du);
             }
@@ -561,156 +540,112 @@ __global__ __launch_bounds__(64) void k_corr_md(SysDev S, SlaterState st, Jastro
   }
   if constexpr (J3)
     if (act3) A.u3[(size_t)k * A.W + w] = u3;
-  if (!act) return;
-  const double ee = A.kc[A.W + w], ei = A.kc[2 * A.W + w], ec = A.has_ecp ? A.local[w] + tot : 0.0;
-  double* o = A.out + (size_t)k * 6 * A.Wc + bw;
-  o[0] = ke; o[A.Wc] = ee; o[2 * A.Wc] = ei; o[3 * A.Wc] = ec; o[4 * A.Wc] = g2; o[5 * A.Wc] = ke + ee + ei + ec + A.ii;
+  if (act) corr_write_rows(A, w, bw, k, ke, g2, tot);
 }
 
-// Scope of pqa_correlated_md: a real, untwisted Slater x two-body Jastrow handle, one or more determinants, no three-body factor, the
-// semi-local ECP integrator or no ECP.
-// j3 (pqa_correlated_j3): the same with a three-body factor, which the handle must then have.
-int linear_det_jastrow_scope(pqa_handle* h, const char* fn, bool j3 = false) {
-  const char* why = (!h->has_slater || !h->has_j2) ? (j3 ? "needs a Slater x two-body x three-body Jastrow handle" : "needs a Slater x two-body Jastrow handle")
-                    : (h->cplx || h->twist)        ? "complex orbitals / twisted cell"
-                    : (!j3 && h->has_j3)           ? "three-body Jastrow factor"
-                    : (j3 && !h->has_j3)           ? "needs a Slater x two-body x three-body Jastrow handle"
-                    : (h->necp > 0 && h->ecpb_on)  ? "batched ECP integrator"
-                                                   : nullptr;
-  if (why) FAIL(std::string(fn) + ": " + why + " (others: set, recompute and evaluate per set)");
+// ---------------------------------------------------------------------------------------------------------------------------------
+// host: one driver for the three entries
+
+// What an entry is: its name (in messages), whether det_coeff is read (k_corr_md with k_corr_md_s and the determinant term of the log
+// value; else k_corr_energy), whether ccoeff is read (the J3 instantiations; implies det), and whether a NULL coefficient array
+// means the handle's own (else acoeff and bcoeff are required).
+struct CorrEntry {
+  const char* name;
+  bool det, j3, own;
+};
+
+// Scope: a real Slater x two-body Jastrow handle with the semi-local ECP integrator or no ECP.  !det: one determinant, possibly
+// twisted; det: one or more determinants, untwisted, no three-body factor; j3: the same with a three-body factor, which the handle
+// must then have.  The first row that applies is the reason.
+int correlated_scope(pqa_handle* h, const CorrEntry& en) {
+  if (!en.det) TRY(linear_jastrow_scope(h, en.name));  // (the single-determinant handle and its LDS row block: pqa_variance's rule)
+  const char* const needs = en.j3 ? "needs a Slater x two-body x three-body Jastrow handle" : "needs a Slater x two-body Jastrow handle";
+  const char* const per_set = " (others: set, recompute and evaluate per set)";
+  const struct { bool refuse; const char *why, *hint; } rows[] = {
+      {en.det && (!h->has_slater || !h->has_j2), needs, per_set},
+      {en.det && (h->cplx || h->twist), "complex orbitals / twisted cell", per_set},
+      {en.det && !en.j3 && h->has_j3, "three-body Jastrow factor", per_set},
+      {en.j3 && !h->has_j3, needs, per_set},
+      {en.det && h->necp > 0 && h->ecpb_on, "batched ECP integrator", per_set},
+      // the single-determinant entry alone also refuses the ECP pass with a wave per point (en.ecp_wave), and the batched integrator
+      // whether or not there is an ECP: the other two take both, and the difference stands as it is
+      {!en.det && (h->ecpb_on || h->en.ecp_wave), "needs the semi-local ECP integrator's thread-per-point pass", " (evaluate per set)"},
+  };
+  for (const auto& r : rows)
+    if (r.refuse) FAIL(std::string(en.name) + ": " + r.why + r.hint);
   return 0;
 }
 
-using CorrMdKernel = void (*)(SysDev, SlaterState, JastrowState, CorrMdArgs);
-const CorrMdKernel corr_md_kernels[2][2] = {  // [J3][PBC]
-    {k_corr_md<true, true>, k_corr_md<false, true>}, {k_corr_md<true, false>, k_corr_md<false, false>}};
+using CorrKernel = void (*)(SysDev, SlaterState, JastrowState, CorrArgs);
+const CorrKernel corr_kernels[3][2] = {  // [k_corr_energy, k_corr_md, its J3 instantiation][open, periodic]
+    {k_corr_energy<false>, k_corr_energy<true>}, {k_corr_md<false, false>, k_corr_md<true, false>}, {k_corr_md<false, true>, k_corr_md<true, true>}};
 
-}  // namespace
-
-extern "C" int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, const double* bcoeff, double threshold, const double* rot,
-                              const double* unif, uint64_t seed, double* logpsi, double* en) {
-  HIPCHK(hipSetDevice(h->device));
-  if (h->W == 0) FAIL("state not initialised (call pqa_wf_recompute)");
-  if (K < 1) FAIL("pqa_correlated: K must be at least 1");
-  if (!acoeff || !bcoeff || !logpsi || !en) FAIL("pqa_correlated: acoeff, bcoeff, logpsi and en must not be NULL");
-  TRY(linear_jastrow_scope(h, "pqa_correlated"));
-  if (h->ecpb_on || h->en.ecp_wave) FAIL("pqa_correlated: needs the semi-local ECP integrator's thread-per-point pass (evaluate per set)");
-  const long W = h->W;
-  const int Pa = h->natom * h->na * 2, Pb = h->nb * 3, P = Pa + Pb, K1 = K + 1;
-  // log|Psi| at the handle's own coefficients (as pqa_wf_value: refreshes the basis sums a fused sweep left stale)
-  std::vector<double> lg0((size_t)W);
-  TRY(pqa_wf_value(h, nullptr, lg0.data()));
-  std::vector<double> ca((size_t)K1 * Pa), cb((size_t)K1 * Pb);
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (Pa) HIPCHK(hipMemcpy(ca.data(), acoeff, (size_t)K * Pa * sizeof(double), hipMemcpyDefault));
-  if (Pb) HIPCHK(hipMemcpy(cb.data(), bcoeff, (size_t)K * Pb * sizeof(double), hipMemcpyDefault));
-  if (Pa) HIPCHK(hipMemcpy(ca.data() + (size_t)K * Pa, h->d_acoeff, Pa * sizeof(double), hipMemcpyDeviceToHost));
-  if (Pb) HIPCHK(hipMemcpy(cb.data() + (size_t)K * Pb, h->d_bcoeff, Pb * sizeof(double), hipMemcpyDeviceToHost));
-  const std::vector<double> ct = pack_coef_sets(ca.data(), cb.data(), K, Pa, Pb);
-  // the Slater-only energy pass, once, with the ECP totals read on the host
-  TRY(sync_aos(h));
-  h->saved_valid = false;  // (as pqa_energy: the saved orbital rows of a gradient_value call are overwritten)
-  EnergyOpts eo;
-  eo.slater_only = true; eo.host_totals = true;
-  TRY(energy_dev(h, threshold, rot, unif, seed, 0u, eo));
-  const bool has_ecp = h->necp > 0;
-  if (has_ecp && (h->en.last_tot[0] < 0 || h->en.last_tot[1] < 0)) FAIL("pqa_correlated: ECP point totals were left on the device");
-  // device scratch (b_out is sized by every user on entry): coefficient rows for k_corr_u, U, the [P][K] matrix, a chunk of outputs
-  const size_t nca = (size_t)K1 * std::max(Pa, 1), ncb = (size_t)K1 * std::max(Pb, 1), nu = (size_t)K1 * W, nct = (size_t)P * K;
-  const long Wc = walker_chunk(W, (size_t)K * 6 * sizeof(double));
-  TRY(ensure(h, h->b_out, (nca + ncb + nu + nct + (size_t)K * 6 * Wc) * sizeof(double)));
-  double* d_ca = (double*)h->b_out.p;
-  double* d_cb = d_ca + nca;
-  double* d_u = d_cb + ncb;
-  double* d_ct = d_u + nu;
-  double* d_o = d_ct + nct;
-  if (Pa) TRY(copy_in(h, d_ca, ca.data(), (size_t)K1 * Pa * sizeof(double)));
-  if (Pb) TRY(copy_in(h, d_cb, cb.data(), (size_t)K1 * Pb * sizeof(double)));
-  TRY(copy_in(h, d_ct, ct.data(), nct * sizeof(double)));
-  hipLaunchKernelGGL(k_corr_u, dim3((unsigned)W), dim3(64), 0, h->stream, (const double*)h->js.avalues, (const double*)h->js.bvalues,
-                     (const double*)d_ca, (const double*)d_cb, Pa, Pb, K1, W, d_u);
-  TRY(check_launch(h, "k_corr_u"));
+// The fields every entry's kernel reads, after the Slater-only energy pass: the shapes, the pass's rows and its ECP point lists.
+CorrArgs corr_args(pqa_handle* h, int K, int P, int Pa) {
   CorrArgs A{};
-  A.W = W; A.K = K; A.P = P; A.Pa = Pa; A.ct = d_ct; A.kc = (const double*)h->b_kc.p; A.ii = h->ii_energy; A.out = d_o;
-  A.has_ecp = has_ecp;
-  if (has_ecp) {
+  A.W = h->W; A.K = K; A.K1 = K + 1; A.P = P; A.Pa = Pa; A.kc = (const double*)h->b_kc.p; A.ii = h->ii_energy; A.has_ecp = h->necp > 0;
+  if (A.has_ecp) {
     A.local = (const double*)h->b_elocal.p; A.off = (const long*)h->b_eoff.p; A.nseg = h->en.last_nseg;
     for (int s = 0; s < 2; ++s) {
-      A.econ[s] = (const double*)h->b_econ[s].p; A.pts[s] = (const double*)h->b_epts[s].p; A.pte[s] = (const int*)h->b_epte[s].p;
+      A.econ[s] = (const double*)h->b_econ[s].p; A.wgt[s] = (const double*)h->b_ewgt[s].p; A.emo[s] = (const double*)h->b_emo[s].p;
+      A.pts[s] = (const double*)h->b_epts[s].p; A.pte[s] = (const int*)h->b_epte[s].p;
     }
   }
-  const size_t lds = (size_t)4 * P * sizeof(double);
-  for (long w0 = 0; w0 < W; w0 += Wc) {
-    A.w0 = w0; A.Wc = std::min(Wc, W - w0);
-    const dim3 g((unsigned)A.Wc, (unsigned)((K + 63) / 64));
-    if (h->S.pbc) hipLaunchKernelGGL(k_corr_energy<true>, g, dim3(64), lds, h->stream, h->S, h->st, h->js, A);
-    else hipLaunchKernelGGL(k_corr_energy<false>, g, dim3(64), lds, h->stream, h->S, h->st, h->js, A);
-    TRY(check_launch(h, "k_corr_energy"));
-    // [K][6][Wc] -> en [K][6][W] columns w0 ..
-    HIPCHK(hipMemcpy2DAsync(en + w0, (size_t)W * sizeof(double), d_o, (size_t)A.Wc * sizeof(double), (size_t)A.Wc * sizeof(double),
-                            (size_t)K * 6, hipMemcpyDefault, h->stream));
-  }
-  std::vector<double> u((size_t)K1 * W);
-  TRY(copy_out(h, u.data(), d_u, u.size() * sizeof(double)));
-  std::vector<double> lp((size_t)K * W);
-  for (int k = 0; k < K; ++k)
-    for (long w = 0; w < W; ++w) lp[(size_t)k * W + w] = lg0[w] - u[(size_t)K * W + w] + u[(size_t)k * W + w];
-  HIPCHK(hipMemcpy(logpsi, lp.data(), lp.size() * sizeof(double), hipMemcpyDefault));
-  return 0;
+  return A;
 }
 
-// The host driver of pqa_correlated_md (j3 = false: ccoeff unused, the J3 = false kernels) and pqa_correlated_j3 (fn: the entry's name).
-static int correlated_md_run(pqa_handle_t* h, const char* fn_, bool j3, int K, const double* det_coeff, const double* acoeff, const double* bcoeff,
-                             const double* ccoeff, double threshold, const double* rot, const double* unif, uint64_t seed, long walker_chunk_arg,
-                             double* logpsi, double* en) {
-  const std::string fn = fn_;
+// The host driver of the three entries (en: which).  det_coeff and ccoeff are read where the entry says so; walker_chunk_arg is 0 for
+// the entry without that argument.
+int correlated_run(pqa_handle_t* h, const CorrEntry& en, int K, const double* det_coeff, const double* acoeff, const double* bcoeff,
+                   const double* ccoeff, double threshold, const double* rot, const double* unif, uint64_t seed, long walker_chunk_arg,
+                   double* logpsi, double* energy) {
+  const std::string fn = en.name;
   HIPCHK(hipSetDevice(h->device));
   if (h->W == 0) FAIL("state not initialised (call pqa_wf_recompute)");
   if (K < 1) FAIL(fn + ": K must be at least 1");
-  if (!logpsi || !en) FAIL(fn + ": logpsi and en must not be NULL");
+  if (!logpsi || !energy || (!en.own && (!acoeff || !bcoeff)))
+    FAIL(fn + (en.own ? ": logpsi and en must not be NULL" : ": acoeff, bcoeff, logpsi and en must not be NULL"));
   if (walker_chunk_arg < 0) FAIL(fn + ": walker_chunk must be 0 (the 256 MiB rule) or positive");
-  TRY(linear_det_jastrow_scope(h, fn_, j3));
+  TRY(correlated_scope(h, en));
   const long W = h->W;
-  const int ndet = h->ndet, Pa = h->natom * h->na * 2, Pb = h->nb * 3, P = Pa + Pb, K1 = K + 1;
-  const int P3 = j3 ? h->natom * h->na3 * h->na3 * h->nb3 * 3 : 0;
-  // the LDS plan: refused where it does not fit, never truncated
+  const int ndet = en.det ? h->ndet : 0, Pa = h->natom * h->na * 2, Pb = h->nb * 3, P = Pa + Pb, K1 = K + 1;
+  const int P3 = en.j3 ? h->natom * h->na3 * h->na3 * h->nb3 * 3 : 0;
+  // the LDS plan: refused where it does not fit, never truncated (k_corr_energy: the rows R[4][P] alone, which the scope has checked)
   const int DP = std::max(h->ndet_s[0], h->ndet_s[1]), RS = ((5 * DP + 29) / 32) * 32 + 2;
   const int ncol = ((std::min(K, 64) + 15) / 16) * 16, GS = ncol + ((ncol % 32 == 0) ? 16 : 0);
-  const size_t lds = (corr_md_lds(ndet, RS, GS, P) + (j3 ? corr_j3_lds(h->N, h->natom, h->na3, h->nb3) : 0)) * sizeof(double);
+  const size_t lds = (en.det ? corr_md_lds(ndet, RS, GS, P) + (en.j3 ? corr_j3_lds(h->N, h->natom, h->na3, h->nb3) : 0) : (size_t)4 * P) * sizeof(double);
   if (lds > 160 * 1024)
-    FAIL(fn + (j3 ? ": the determinant rows, Jastrow rows and three-body tables of a 16-row tile exceed the LDS of a CU (others: set, recompute and evaluate per set)"
-                  : ": the determinant rows and Jastrow rows of a 16-row tile exceed the LDS of a CU (others: set, recompute and evaluate per set)"));
-  const CorrMdKernel kernel = corr_md_kernels[j3 ? 0 : 1][h->S.pbc ? 0 : 1];
+    FAIL(fn + (en.j3 ? ": the determinant rows, Jastrow rows and three-body tables of a 16-row tile exceed the LDS of a CU (others: set, recompute and evaluate per set)"
+                     : ": the determinant rows and Jastrow rows of a 16-row tile exceed the LDS of a CU (others: set, recompute and evaluate per set)"));
+  const CorrKernel kernel = corr_kernels[en.j3 ? 2 : en.det ? 1 : 0][h->S.pbc ? 1 : 0];
+  const char* const kname = en.det ? "k_corr_md" : "k_corr_energy";
   if (lds > 64 * 1024) TRY(raise_lds_limit(h, (const void*)kernel));
   // log|Psi| at the handle's own coefficients (as pqa_wf_value: refreshes the basis sums a fused sweep left stale)
   std::vector<double> lg0((size_t)W);
   TRY(pqa_wf_value(h, nullptr, lg0.data()));
-  // rows 0 .. K-1: the sets (NULL: the handle's own); row K: the handle's own
-  std::vector<double> ca((size_t)K1 * Pa), cb((size_t)K1 * Pb), cdr((size_t)K1 * ndet);
+  // [K1][n] rows of each coefficient array: rows 0 .. K-1 the sets (host or device memory; NULL: the handle's own), row K the handle's own
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (Pa) HIPCHK(hipMemcpy(ca.data() + (size_t)K * Pa, h->d_acoeff, Pa * sizeof(double), hipMemcpyDeviceToHost));
-  if (Pb) HIPCHK(hipMemcpy(cb.data() + (size_t)K * Pb, h->d_bcoeff, Pb * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(cdr.data() + (size_t)K * ndet, h->d_detcoeff, ndet * sizeof(double), hipMemcpyDeviceToHost));
-  auto rows_in = [&](std::vector<double>& dst, const double* src, int n) -> int {
+  auto rows_in = [&](std::vector<double>& dst, const double* src, const double* own, int n) -> int {
+    dst.resize((size_t)K1 * n);
     if (!n) return 0;
+    HIPCHK(hipMemcpy(dst.data() + (size_t)K * n, own, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     if (src) HIPCHK(hipMemcpy(dst.data(), src, (size_t)K * n * sizeof(double), hipMemcpyDefault));
     else
-      for (int k = 0; k < K; ++k) std::copy(dst.begin() + (size_t)K * n, dst.begin() + (size_t)K1 * n, dst.begin() + (size_t)k * n);
+      for (int k = 0; k < K; ++k) std::copy(dst.begin() + (size_t)K * n, dst.end(), dst.begin() + (size_t)k * n);
     return 0;
   };
-  TRY(rows_in(ca, acoeff, Pa));
-  TRY(rows_in(cb, bcoeff, Pb));
-  TRY(rows_in(cdr, det_coeff, ndet));
+  std::vector<double> ca, cb, cdr, c3;
+  TRY(rows_in(ca, acoeff, h->d_acoeff, Pa));
+  TRY(rows_in(cb, bcoeff, h->d_bcoeff, Pb));
+  TRY(rows_in(cdr, det_coeff, h->d_detcoeff, ndet));
+  TRY(rows_in(c3, ccoeff, h->d_c3, P3));
   const std::vector<double> ct = pack_coef_sets(ca.data(), cb.data(), K, Pa, Pb);
   std::vector<double> cd((size_t)ndet * K1);  // [ndet][K1]
   for (int k = 0; k < K1; ++k)
     for (int d = 0; d < ndet; ++d) cd[(size_t)d * K1 + k] = cdr[(size_t)k * ndet + d];
   // three-body sets, symmetrised in (k, l) as set_c3 does (the handle's own, d_c3, already is): [P3][K1], column K the handle's own
   std::vector<double> c3t((size_t)P3 * K1);
-  if (j3) {
-    std::vector<double> c3((size_t)K1 * P3);
-    HIPCHK(hipMemcpy(c3.data() + (size_t)K * P3, h->d_c3, (size_t)P3 * sizeof(double), hipMemcpyDeviceToHost));
-    TRY(rows_in(c3, ccoeff, P3));
+  if (en.j3) {
     const int na3 = h->na3, m3 = h->nb3 * 3;
     for (int k = 0; k < K1; ++k) {
       const double* c = c3.data() + (size_t)k * P3;
@@ -730,80 +665,75 @@ static int correlated_md_run(pqa_handle_t* h, const char* fn_, bool j3, int K, c
   EnergyOpts eo;
   eo.slater_only = true; eo.host_totals = true;
   TRY(energy_dev(h, threshold, rot, unif, seed, 0u, eo));
-  const bool has_ecp = h->necp > 0;
-  if (has_ecp && (h->en.last_tot[0] < 0 || h->en.last_tot[1] < 0)) FAIL(fn + ": ECP point totals were left on the device");
-  // device scratch (b_out is sized by every user on entry): coefficient rows for k_corr_u, U, the two matrices, S, a chunk of outputs;
-  // behind them the three-body matrix and U3
-  const size_t nca = (size_t)K1 * std::max(Pa, 1), ncb = (size_t)K1 * std::max(Pb, 1), nu = (size_t)K1 * W, nct = (size_t)P * K;
-  const size_t ncd = (size_t)ndet * K1;
+  CorrArgs A = corr_args(h, K, P, Pa);
+  if (A.has_ecp && (h->en.last_tot[0] < 0 || h->en.last_tot[1] < 0)) FAIL(fn + ": ECP point totals were left on the device");
+  // device scratch (b_out is sized by every user on entry), one plan for its size and its pieces: the coefficient rows for k_corr_u, U,
+  // the Jastrow matrix and a chunk of outputs; with det the determinant matrix and S; with j3 the three-body matrix and U3
   const long Wc = walker_chunk_arg > 0 ? std::min(W, walker_chunk_arg) : walker_chunk(W, (size_t)K * 6 * sizeof(double));
-  const size_t nc3 = (size_t)P3 * K1, nout = (size_t)K * 6 * Wc;
-  TRY(ensure(h, h->b_out, (nca + ncb + 2 * nu + nct + ncd + nout + nc3 + (j3 ? nu : 0)) * sizeof(double)));
-  double* d_ca = (double*)h->b_out.p;
-  double* d_cb = d_ca + nca;
-  double* d_u = d_cb + ncb;
-  double* d_s = d_u + nu;
-  double* d_ct = d_s + nu;
-  double* d_cd = d_ct + nct;
-  double* d_o = d_cd + ncd;
-  double* d_c3t = d_o + nout;
-  double* d_u3 = d_c3t + nc3;
-  if (Pa) TRY(copy_in(h, d_ca, ca.data(), (size_t)K1 * Pa * sizeof(double)));
-  if (Pb) TRY(copy_in(h, d_cb, cb.data(), (size_t)K1 * Pb * sizeof(double)));
-  TRY(copy_in(h, d_ct, ct.data(), nct * sizeof(double)));
-  TRY(copy_in(h, d_cd, cd.data(), ncd * sizeof(double)));
-  if (j3) TRY(copy_in(h, d_c3t, c3t.data(), nc3 * sizeof(double)));
+  const size_t nu = (size_t)K1 * W;
+  double *d_ca, *d_cb, *d_u, *d_ct, *d_o, *d_cd, *d_s, *d_c3t, *d_u3;
+  const std::pair<double**, size_t> plan[] = {{&d_ca, (size_t)K1 * std::max(Pa, 1)}, {&d_cb, (size_t)K1 * std::max(Pb, 1)}, {&d_u, nu},
+                                              {&d_ct, ct.size()}, {&d_o, (size_t)K * 6 * Wc}, {&d_cd, cd.size()}, {&d_s, en.det ? nu : 0},
+                                              {&d_c3t, c3t.size()}, {&d_u3, en.j3 ? nu : 0}};
+  size_t total = 0;
+  for (const auto& pc : plan) total += pc.second;
+  TRY(ensure(h, h->b_out, total * sizeof(double)));
+  double* next = (double*)h->b_out.p;
+  for (const auto& pc : plan) { *pc.first = next; next += pc.second; }
+  TRY(copy_in(h, d_ca, ca.data(), ca.size() * sizeof(double)));
+  TRY(copy_in(h, d_cb, cb.data(), cb.size() * sizeof(double)));
+  TRY(copy_in(h, d_ct, ct.data(), ct.size() * sizeof(double)));
+  TRY(copy_in(h, d_cd, cd.data(), cd.size() * sizeof(double)));
+  TRY(copy_in(h, d_c3t, c3t.data(), c3t.size() * sizeof(double)));
   hipLaunchKernelGGL(k_corr_u, dim3((unsigned)W), dim3(64), 0, h->stream, (const double*)h->js.avalues, (const double*)h->js.bvalues,
                      (const double*)d_ca, (const double*)d_cb, Pa, Pb, K1, W, d_u);
   TRY(check_launch(h, "k_corr_u"));
-  hipLaunchKernelGGL(k_corr_md_s, dim3((unsigned)W), dim3(64), (size_t)ndet * sizeof(double), h->stream, h->S, h->st, (const double*)d_cd, K1, W, d_s);
-  TRY(check_launch(h, "k_corr_md_s"));
-  CorrMdArgs A{};
-  A.W = W; A.K = K; A.K1 = K1; A.P = P; A.Pa = Pa; A.DP = DP; A.RS = RS; A.GS = GS; A.ct = d_ct; A.cd = d_cd;
-  A.kc = (const double*)h->b_kc.p; A.ii = h->ii_energy; A.out = d_o; A.has_ecp = has_ecp;
-  if (j3) { A.c3t = d_c3t; A.u3 = d_u3; }
-  if (has_ecp) {
-    A.local = (const double*)h->b_elocal.p; A.off = (const long*)h->b_eoff.p; A.nseg = h->en.last_nseg;
-    for (int s = 0; s < 2; ++s) {
-      A.wgt[s] = (const double*)h->b_ewgt[s].p; A.emo[s] = (const double*)h->b_emo[s].p;
-      A.pts[s] = (const double*)h->b_epts[s].p; A.pte[s] = (const int*)h->b_epte[s].p;
-    }
+  if (en.det) {
+    hipLaunchKernelGGL(k_corr_md_s, dim3((unsigned)W), dim3(64), (size_t)ndet * sizeof(double), h->stream, h->S, h->st, (const double*)d_cd, K1, W, d_s);
+    TRY(check_launch(h, "k_corr_md_s"));
   }
+  A.ct = d_ct; A.out = d_o; A.DP = DP; A.RS = RS; A.GS = GS; A.cd = d_cd; A.c3t = d_c3t; A.u3 = d_u3;
   for (long w0 = 0; w0 < W; w0 += Wc) {
     A.w0 = w0; A.Wc = std::min(Wc, W - w0);
-    const dim3 g((unsigned)A.Wc, (unsigned)(((j3 ? K1 : K) + 63) / 64));  // (J3: the handle's own column rides along for U3)
+    const dim3 g((unsigned)A.Wc, (unsigned)(((en.j3 ? K1 : K) + 63) / 64));  // (J3: the handle's own column rides along for U3)
     hipLaunchKernelGGL(kernel, g, dim3(64), lds, h->stream, h->S, h->st, h->js, A);
-    TRY(check_launch(h, "k_corr_md"));
-    // [K][6][Wc] -> en [K][6][W] columns w0 ..
-    HIPCHK(hipMemcpy2DAsync(en + w0, (size_t)W * sizeof(double), d_o, (size_t)A.Wc * sizeof(double), (size_t)A.Wc * sizeof(double),
+    TRY(check_launch(h, kname));
+    // [K][6][Wc] -> energy [K][6][W] columns w0 ..
+    HIPCHK(hipMemcpy2DAsync(energy + w0, (size_t)W * sizeof(double), d_o, (size_t)A.Wc * sizeof(double), (size_t)A.Wc * sizeof(double),
                             (size_t)K * 6, hipMemcpyDefault, h->stream));
   }
-  std::vector<double> u((size_t)K1 * W), sv((size_t)K1 * W);
+  // log|Psi_k| = log|Psi| - U_0 + U_k, with det also - log|S_0| + log|S_k|, with j3 also - U3_0 + U3_k (0: the handle's own, row K)
+  std::vector<double> u(nu), sv(en.det ? nu : 0), v3(en.j3 ? nu : 0);
   TRY(copy_out(h, u.data(), d_u, u.size() * sizeof(double)));
-  TRY(copy_out(h, sv.data(), d_s, sv.size() * sizeof(double)));
-  std::vector<double> v3;
-  if (j3) {
-    v3.resize((size_t)K1 * W);
-    TRY(copy_out(h, v3.data(), d_u3, v3.size() * sizeof(double)));
-  }
+  if (en.det) TRY(copy_out(h, sv.data(), d_s, sv.size() * sizeof(double)));
+  if (en.j3) TRY(copy_out(h, v3.data(), d_u3, v3.size() * sizeof(double)));
   std::vector<double> lp((size_t)K * W);
   for (int k = 0; k < K; ++k)
     for (long w = 0; w < W; ++w) {
       const size_t i = (size_t)k * W + w, i0 = (size_t)K * W + w;
-      lp[i] = lg0[w] + (std::log(std::fabs(sv[i])) - std::log(std::fabs(sv[i0]))) + (u[i] - u[i0]);
-      if (j3) lp[i] += v3[i] - v3[i0];
+      lp[i] = en.det ? lg0[w] + (std::log(std::fabs(sv[i])) - std::log(std::fabs(sv[i0]))) + (u[i] - u[i0]) : lg0[w] - u[i0] + u[i];
+      if (en.j3) lp[i] += v3[i] - v3[i0];
     }
   HIPCHK(hipMemcpy(logpsi, lp.data(), lp.size() * sizeof(double), hipMemcpyDefault));
   return 0;
 }
 
+}  // namespace
+
+extern "C" int pqa_correlated(pqa_handle_t* h, int K, const double* acoeff, const double* bcoeff, double threshold, const double* rot,
+                              const double* unif, uint64_t seed, double* logpsi, double* en) {
+  return correlated_run(h, {"pqa_correlated", false, false, false}, K, nullptr, acoeff, bcoeff, nullptr, threshold, rot, unif, seed, 0, logpsi, en);
+}
+
 extern "C" int pqa_correlated_md(pqa_handle_t* h, int K, const double* det_coeff, const double* acoeff, const double* bcoeff, double threshold,
                                  const double* rot, const double* unif, uint64_t seed, long walker_chunk_arg, double* logpsi, double* en) {
-  return correlated_md_run(h, "pqa_correlated_md", false, K, det_coeff, acoeff, bcoeff, nullptr, threshold, rot, unif, seed, walker_chunk_arg, logpsi, en);
+  return correlated_run(h, {"pqa_correlated_md", true, false, true}, K, det_coeff, acoeff, bcoeff, nullptr, threshold, rot, unif, seed, walker_chunk_arg,
+                        logpsi, en);
 }
 
 extern "C" int pqa_correlated_j3(pqa_handle_t* h, int K, const double* det_coeff, const double* acoeff, const double* bcoeff, const double* ccoeff,
                                  double threshold, const double* rot, const double* unif, uint64_t seed, long walker_chunk_arg, double* logpsi,
                                  double* en) {
-  return correlated_md_run(h, "pqa_correlated_j3", true, K, det_coeff, acoeff, bcoeff, ccoeff, threshold, rot, unif, seed, walker_chunk_arg, logpsi, en);
+  return correlated_run(h, {"pqa_correlated_j3", true, true, true}, K, det_coeff, acoeff, bcoeff, ccoeff, threshold, rot, unif, seed, walker_chunk_arg,
+                        logpsi, en);
 }

@@ -4,7 +4,8 @@
 // Basis-resolved two-body Jastrow rows: U = sum_p c_p B_p(R) is linear in the coefficients (acoeff entries (atom, k, spin), then
 // bcoeff entries (k, pair)), and so are grad_e U, lap_e U and U(e -> q) - U(e).  jas_rows writes R[m * P + p] = grad_e B_p
 // (m = 0, 1, 2) and lap_e B_p (m = 3) for electron e, jas_diff_rows R[p] = B_p(e -> q) - B_p(e), and a caller contracts them with
-// whichever coefficient set it needs.
+// whichever coefficient set it needs: jas_contract4 (gradient and Laplacian: ke_electron for k_corr_energy and k_var_ke, and
+// k_corr_md) and jas_contract1 (the value at an ECP point: k_corr_energy and k_corr_md).
 //
 // Weighted walker means (pqa_obdm, pqa_sq): the weight sum k_wsum (pqa_sr's too) and the column reduction k_wcol_means / k_wcol_fold.
 #pragma once
@@ -124,6 +125,37 @@ __device__ __forceinline__ void jas_diff_rows(const SysDev& S, const double* xw,
   __syncthreads();
 }
 
+// The rows jas_rows left for an electron of spin s, contracted with set k of ct [P][K] (a lane's own set): g = grad_e U_k and
+// lp = lap_e U_k.  Only the entries of spin s are non-zero: the one-body entries p = 2 q + s, then the two-body entries
+// p = Pa + (q >> 1) * 3 + s + (q & 1), ascending.  Every kernel that contracts these rows does it here, so they hold the same bits.
+// The four sums are handed to f(gx, gy, gz, lp) and not returned: the callers combine them with G = grad D / D as G . g, which the
+// compiler contracts into fused multiply-adds, and which product it fuses depends on where G's divisions stand.  With the sums
+// returned into the caller the divisions are sunk next to their use before this function is inlined, and the contraction rounds
+// differently from the loops written in place; with the use inside f it is formed as it always was.
+template <class F>
+__device__ __forceinline__ void jas_contract4(const SysDev& S, const double* R, const double* ct, int K, int k, int s, int P, int Pa, F&& f) {
+  double gx = 0.0, gy = 0.0, gz = 0.0, lp = 0.0;
+  for (int q = 0; q < S.natom * S.na; ++q) {
+    const int p = 2 * q + s;
+    const double c = ct[(size_t)p * K + k];
+    gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
+  }
+  for (int q = 0; q < 2 * S.nb; ++q) {
+    const int p = Pa + (q >> 1) * 3 + s + (q & 1);
+    const double c = ct[(size_t)p * K + k];
+    gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
+  }
+  f(gx, gy, gz, lp);
+}
+
+// The value-only form, for the row jas_diff_rows left: dU_k = U_k(e -> q) - U_k(e), the same entries in the same order.
+__device__ __forceinline__ double jas_contract1(const SysDev& S, const double* R, const double* ct, int K, int k, int s, int Pa) {
+  double du = 0.0;
+  for (int q = 0; q < S.natom * S.na; ++q) { const int p = 2 * q + s; du += ct[(size_t)p * K + k] * R[p]; }
+  for (int q = 0; q < 2 * S.nb; ++q) { const int p = Pa + (q >> 1) * 3 + s + (q & 1); du += ct[(size_t)p * K + k] * R[p]; }
+  return du;
+}
+
 // Kinetic terms of electron e of walker w (one wave per walker; LDS R[4][P] for jas_rows).  G = grad D / D and L = lap D / D come
 // from the orbital-row cache; on the lanes with act the rows are contracted with set k of ct [P][K] to g = grad_e U_k,
 // lp = lap_e U_k, and f(lap, tx, ty, tz) receives lap = L + lp + |g|^2 + 2 G . g (the electron's lap Psi / Psi) and t = G + g.
@@ -136,22 +168,12 @@ __device__ __forceinline__ void ke_electron(const SysDev& S, const SlaterState& 
   slater_ratios<5>(S, st, s, i, w, st.cache[s] + ((size_t)w * n + i) * 5 * nmo, r, nullptr);
   const double G0 = r[1] / r[0], G1 = r[2] / r[0], G2 = r[3] / r[0], L = r[4] / r[0];
   jas_rows<PBC>(S, xw, e, s, xw[3 * e], xw[3 * e + 1], xw[3 * e + 2], P, Pa, ira, irb, R);
-  if (act) {
-    double gx = 0.0, gy = 0.0, gz = 0.0, lp = 0.0;
-    for (int q = 0; q < S.natom * S.na; ++q) {
-      const int p = 2 * q + s;
-      const double c = ct[(size_t)p * K + k];
-      gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
-    }
-    for (int q = 0; q < 2 * S.nb; ++q) {
-      const int p = Pa + (q >> 1) * 3 + s + (q & 1);
-      const double c = ct[(size_t)p * K + k];
-      gx += c * R[p]; gy += c * R[P + p]; gz += c * R[2 * P + p]; lp += c * R[3 * P + p];
-    }
-    const double lj = lp + gx * gx + gy * gy + gz * gz;
-    const double lap = L + lj + 2.0 * (G0 * gx + G1 * gy + G2 * gz);
-    f(lap, G0 + gx, G1 + gy, G2 + gz);
-  }
+  if (act)
+    jas_contract4(S, R, ct, K, k, s, P, Pa, [&](double gx, double gy, double gz, double lp) {
+      const double lj = lp + gx * gx + gy * gy + gz * gz;
+      const double lap = L + lj + 2.0 * (G0 * gx + G1 * gy + G2 * gz);
+      f(lap, G0 + gx, G1 + gy, G2 + gz);
+    });
   __syncthreads();
 }
 
@@ -347,8 +369,8 @@ inline int on_ev(pqa_handle* h, pqa_handle* ev, int rc) {
   return rc;
 }
 
-// Scope of the linear-Jastrow units (pqa_correlated, pqa_variance): a real single-determinant Slater x two-body Jastrow handle whose
-// row block R[4][P] fits the LDS.
+// Scope of the single-determinant linear-Jastrow entries (pqa_variance; pqa_correlated through correlated_scope): a real
+// single-determinant Slater x two-body Jastrow handle whose row block R[4][P] fits the LDS.
 inline int linear_jastrow_scope(pqa_handle* h, const char* fn) {
   if (!h->has_slater || !h->has_j2 || h->has_j3 || h->cplx || h->ndet != 1)
     FAIL(std::string(fn) + ": needs a real single-determinant Slater x two-body Jastrow handle (others: set, recompute and evaluate per set)");

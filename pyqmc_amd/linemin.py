@@ -263,24 +263,20 @@ def correlated_route(wf, pgrad_acc, route=None, three_body_device=False):
         return "protocol"
     enacc = getattr(pgrad_acc, "enacc", None)
     plain = type(enacc) is EnergyAccumulator and enacc.use_old_ecp
+    # the entry asked of, and the parameters it has to cover (the default route asks pqa_correlated about every parameter listed)
     if three_body_device and _has_three_body(wf):
-        why = []
-        if not plain:
-            why.append("the energy accumulator is not an EnergyAccumulator with the semi-local ECP integrator (use_old_ecp=True)")
-        elif linear_j3_device(wf, _opt_keys(pgrad_acc), why) is not None:
-            return "fused"
-        if route is None:
-            return "protocol"
-        raise NotImplementedError(f"evaluation_route='fused': {why[0]}; use the set-recompute-energy route (evaluation_route='protocol')")
-    if route is None:
-        if not plain:
-            return "protocol"
-        return "protocol" if linear_jastrow_device(wf, pgrad_acc.transform.to_opt) is None else "fused"
+        device, keys = linear_j3_device, _opt_keys
+    elif route is None:
+        device, keys = (lambda wf, keys, why: linear_jastrow_device(wf, keys)), (lambda pgrad_acc: pgrad_acc.transform.to_opt)
+    else:
+        device, keys = linear_det_jastrow_device, _opt_keys
     why = []
     if not plain:
         why.append("the energy accumulator is not an EnergyAccumulator with the semi-local ECP integrator (use_old_ecp=True)")
-    elif linear_det_jastrow_device(wf, _opt_keys(pgrad_acc), why) is not None:
+    elif device(wf, keys(pgrad_acc), why) is not None:
         return "fused"
+    if route is None:
+        return "protocol"
     raise NotImplementedError(f"evaluation_route='fused': {why[0]}; use the set-recompute-energy route (evaluation_route='protocol')")
 
 
@@ -326,6 +322,12 @@ def correlated_compute_worker(wf, configs, params, pgrad_acc, ref_wfs, evaluatio
     return data_ret
 
 
+# The coefficient arrays of the fused entries: (parameter key, factor index, parameter name, argument name of DeviceWF.correlated*).
+# pqa_correlated takes the two-body rows, pqa_correlated_md those and det_coeff, pqa_correlated_j3 all four.
+_CORRELATED_SETS = (("wf1det_coeff", 0, "det_coeff", "det_coeff"), ("wf2acoeff", 1, "acoeff", "acoeff"), ("wf2bcoeff", 1, "bcoeff", "bcoeff"),
+                    ("wf3ccoeff", 2, "ccoeff", "ccoeff"))
+
+
 def _correlated_fused(wf, configs, params, pgrad_acc, ref_wfs):
     from .energy import KEYS
 
@@ -333,27 +335,18 @@ def _correlated_fused(wf, configs, params, pgrad_acc, ref_wfs):
     dev = wf.fused_device()
     wf.recompute(configs)  # (at the current parameters: the state every set shares)
     sets = [tr.deserialize(wf, p) for p in params]
-    ja = wf.wf_factors[1].parameters
-    acoeff = np.stack([s.get("wf2acoeff", ja["acoeff"]) for s in sets])
-    bcoeff = np.stack([s.get("wf2bcoeff", ja["bcoeff"]) for s in sets])
     enacc.bind(dev)
     enacc._calls += 1
     # the draws one accumulator call makes (EnergyAccumulator.__call__), shared by every set as the reference's reset gives them
     key = int(np.random.randint(0, 2**31 - 1)) if enacc.seed is None else enacc.seed + enacc._calls
     if dev.has_j3:  # (correlated_route admits a three-body handle with three_body_device=True alone)
-        dc, cc = wf.wf_factors[0].parameters["det_coeff"], wf.wf_factors[2].parameters["ccoeff"]
-        det_coeff = np.stack([s.get("wf1det_coeff", dc) for s in sets])
-        ccoeff = np.stack([s.get("wf3ccoeff", cc) for s in sets])
-        psi, en = dev.correlated_j3(det_coeff, acoeff, bcoeff, ccoeff, enacc.threshold, seed=key)
-        entry = "pqa_correlated_j3"
+        entry, rows = "pqa_correlated_j3", _CORRELATED_SETS
     elif dev.ndet > 1 or "wf1det_coeff" in _opt_keys(pgrad_acc):
-        dc = wf.wf_factors[0].parameters["det_coeff"]
-        det_coeff = np.stack([s.get("wf1det_coeff", dc) for s in sets])
-        psi, en = dev.correlated_md(det_coeff, acoeff, bcoeff, enacc.threshold, seed=key)
-        entry = "pqa_correlated_md"
+        entry, rows = "pqa_correlated_md", _CORRELATED_SETS[:3]
     else:
-        psi, en = dev.correlated(acoeff, bcoeff, enacc.threshold, seed=key)
-        entry = "pqa_correlated"
+        entry, rows = "pqa_correlated", _CORRELATED_SETS[1:3]
+    arrays = {arg: np.stack([s.get(pkey, wf.wf_factors[i].parameters[name]) for s in sets]) for pkey, i, name, arg in rows}
+    psi, en = getattr(dev, entry[len("pqa_"):])(**arrays, threshold=enacc.threshold, seed=key)
     data_ret = {k: en[:, i, :] for i, k in enumerate(KEYS)}
     data_ret["weight"] = _weights(psi, ref_wfs)
     data_ret["route"] = "fused"

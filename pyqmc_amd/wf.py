@@ -291,11 +291,16 @@ class DeviceWF:
         bcoeff (K, nb, 3), every set with the same energy draws -> (logpsi (K, W), energy rows (K, 6, W)).  The handle keeps its
         own coefficients and state."""
         a, b, K = self._coef_sets(acoeff, bcoeff)
+        return self._correlated_call("pqa_correlated", (a, b), K, threshold, rot, unif, seed)
+
+    def _correlated_call(self, entry, arrs, K, threshold, rot, unif, seed, walker_chunk=None):
+        """The ``pqa_correlated*`` call ``entry`` for K sets: ``arrs`` are its coefficient arrays in the order of its arguments
+        (None: the handle's own), ``walker_chunk`` None for the entry without that argument -> (logpsi (K, W), energy rows (K, 6, W))."""
         logpsi, en = np.empty((K, self.W)), np.empty((K, 6, self.W))
         rot = None if rot is None else _ffi.f64(rot)
         unif = None if unif is None else _ffi.f64(unif)
-        self.call("pqa_correlated", int(K), _ffi.ptr(a), _ffi.ptr(b), float(threshold), _ffi.ptr(rot), _ffi.ptr(unif), int(seed),
-                  _ffi.ptr(logpsi), _ffi.ptr(en))
+        self.call(entry, int(K), *map(_ffi.ptr, arrs), float(threshold), _ffi.ptr(rot), _ffi.ptr(unif), int(seed),
+                  *(() if walker_chunk is None else (int(walker_chunk),)), _ffi.ptr(logpsi), _ffi.ptr(en))
         return logpsi, en
 
     def correlated_md(self, det_coeff=None, acoeff=None, bcoeff=None, threshold=10.0, rot=None, unif=None, seed=0, walker_chunk=0):
@@ -304,16 +309,11 @@ class DeviceWF:
         rows (K, 6, W)).  None for an array: every set uses the handle's own (K from the arrays given; 1 when none is).  The handle
         keeps its own coefficients and state; the result does not depend on ``walker_chunk`` (0: output chunks of 256 MiB)."""
         arrs, K = self._coef_set_arrays(det_coeff=det_coeff, acoeff=acoeff, bcoeff=bcoeff)
-        logpsi, en = np.empty((K, self.W)), np.empty((K, 6, self.W))
-        rot = None if rot is None else _ffi.f64(rot)
-        unif = None if unif is None else _ffi.f64(unif)
-        self.call("pqa_correlated_md", int(K), _ffi.ptr(arrs["det_coeff"]), _ffi.ptr(arrs["acoeff"]), _ffi.ptr(arrs["bcoeff"]), float(threshold),
-                  _ffi.ptr(rot), _ffi.ptr(unif), int(seed), int(walker_chunk), _ffi.ptr(logpsi), _ffi.ptr(en))
-        return logpsi, en
+        return self._correlated_call("pqa_correlated_md", arrs.values(), K, threshold, rot, unif, seed, walker_chunk)
 
     def _coef_set_arrays(self, **given):
         """The coefficient arrays of ``correlated_md`` / ``correlated_j3`` (name -> array or None) as float64 with their shapes
-        checked -> ({name: array or None}, K): K from the arrays given, 1 when none is."""
+        checked -> ({name: array or None} in the order given, K): K from the arrays given, 1 when none is."""
         shapes = {"det_coeff": (self.ndet,), "acoeff": (self.natom, self.na, 2), "bcoeff": (self.nb, 3),
                   "ccoeff": (self.natom, self.na3, self.na3, self.nb3, 3)}
         arrs = {k: None if v is None else _ffi.f64(v) for k, v in given.items()}
@@ -329,13 +329,7 @@ class DeviceWF:
         ccoeff (K, natom, na3, na3, nb3, 3) as well (symmetrised per set as the handle's own are).  None for an array: every set
         uses the handle's own.  The handle keeps its own coefficients and state; the result does not depend on ``walker_chunk``."""
         arrs, K = self._coef_set_arrays(det_coeff=det_coeff, acoeff=acoeff, bcoeff=bcoeff, ccoeff=ccoeff)
-        logpsi, en = np.empty((K, self.W)), np.empty((K, 6, self.W))
-        rot = None if rot is None else _ffi.f64(rot)
-        unif = None if unif is None else _ffi.f64(unif)
-        self.call("pqa_correlated_j3", int(K), _ffi.ptr(arrs["det_coeff"]), _ffi.ptr(arrs["acoeff"]), _ffi.ptr(arrs["bcoeff"]),
-                  _ffi.ptr(arrs["ccoeff"]), float(threshold), _ffi.ptr(rot), _ffi.ptr(unif), int(seed), int(walker_chunk), _ffi.ptr(logpsi),
-                  _ffi.ptr(en))
-        return logpsi, en
+        return self._correlated_call("pqa_correlated_j3", arrs.values(), K, threshold, rot, unif, seed, walker_chunk)
 
     def _sr_call(self, entry, src, pos, nodal_cutoff, weights, threshold, rot, unif, seed, per_walker, tail=None, chunk=None, dp_walker=False,
                  scope=None):
@@ -1309,75 +1303,62 @@ def readonly_device_j3(wf):
 
 
 LINEAR_JASTROW_KEYS = {"wf2acoeff", "wf2bcoeff"}  # the parameters the linear-Jastrow entry points vary
+LINEAR_DET_KEYS = LINEAR_JASTROW_KEYS | {"wf1det_coeff"}  # the parameters ``pqa_correlated_md`` varies
+LINEAR_J3_KEYS = LINEAR_DET_KEYS | {"wf3ccoeff"}  # the parameters ``pqa_correlated_j3`` varies
+
+_FACTOR_NAMES = {Slater: "Slater", JastrowSpin: "two-body Jastrow (JastrowSpin)", ThreeBodyJastrow: "three-body Jastrow (ThreeBodyJastrow)"}
+# The scope of the linear entry points, a row each: the factor types, the parameters that may vary, whether one determinant is required,
+# whether twisted handles are refused, and the three-body factor (True: required, False: refused).
+_LINEAR_SCOPES = {
+    "jastrow": ((Slater, JastrowSpin), LINEAR_JASTROW_KEYS, True, False, False),
+    "det": ((Slater, JastrowSpin), LINEAR_DET_KEYS, False, True, False),
+    "j3": ((Slater, JastrowSpin, ThreeBodyJastrow), LINEAR_J3_KEYS, False, True, True),
+}
+
+
+def _linear_device(row, wf, keys, why=None):
+    """The device handle the linear entry points of scope ``row`` (``_LINEAR_SCOPES``) can evaluate ``wf`` on while the parameters
+    ``keys`` vary, or None, with the reason appended to the list ``why`` when one is given."""
+    kinds, allowed, one_det, untwisted, three_body = _LINEAR_SCOPES[row]
+    f = getattr(wf, "wf_factors", None)
+    dev = None
+    if f is None or tuple(type(x) for x in f) != kinds:
+        reason = "the wave function is not " + " x ".join(_FACTOR_NAMES[k] for k in kinds) + " on one device handle"
+    else:
+        dev = wf.fused_device()
+        reason = ("the wave function has no fused device handle" if dev is None
+                  else "complex orbitals / twisted cell" if dev.cplx or (untwisted and dev.twisted)
+                  else "more than one determinant" if one_det and dev.ndet != 1
+                  else "three-body Jastrow factor" if dev.has_j3 and not three_body
+                  else "the device handle has no three-body Jastrow factor" if three_body and not dev.has_j3
+                  else f"parameters outside {sorted(allowed)}: {sorted(set(keys) - allowed)}" if not set(keys) <= allowed
+                  else None)
+    if reason is None:
+        return dev
+    if why is not None:
+        why.append(reason)
+    return None
 
 
 def linear_jastrow_device(wf, keys):
     """The device handle the linear-Jastrow entry points (``pqa_correlated``, ``pqa_variance``) can evaluate ``wf`` on while the
     parameters ``keys`` vary, or None: ``wf`` must be Slater x JastrowSpin on one handle, real, with one determinant and no three-body
     factor, and ``keys`` within ``LINEAR_JASTROW_KEYS``."""
-    f = getattr(wf, "wf_factors", None)
-    if f is None or len(f) != 2 or type(f[0]) is not Slater or type(f[1]) is not JastrowSpin:
-        return None
-    dev = wf.fused_device()
-    if dev is None or dev.cplx or dev.ndet != 1 or dev.has_j3:
-        return None
-    return dev if set(keys) <= LINEAR_JASTROW_KEYS else None
-
-
-LINEAR_DET_KEYS = LINEAR_JASTROW_KEYS | {"wf1det_coeff"}  # the parameters ``pqa_correlated_md`` varies
+    return _linear_device("jastrow", wf, keys)
 
 
 def linear_det_jastrow_device(wf, keys, why=None):
     """The device handle ``pqa_correlated_md`` can evaluate ``wf`` on while the parameters ``keys`` vary, or None: ``wf`` must be
     Slater x JastrowSpin on one handle, real and untwisted, with one or more determinants and no three-body factor, and ``keys``
     within ``LINEAR_DET_KEYS``.  ``why``: a list that receives the reason for a None."""
-    f = getattr(wf, "wf_factors", None)
-    reason, dev = None, None
-    if f is None or len(f) != 2 or type(f[0]) is not Slater or type(f[1]) is not JastrowSpin:
-        reason = "the wave function is not Slater x two-body Jastrow (JastrowSpin) on one device handle"
-    else:
-        dev = wf.fused_device()
-        if dev is None:
-            reason = "the wave function has no fused device handle"
-        elif dev.cplx or dev.twisted:
-            reason = "complex orbitals / twisted cell"
-        elif dev.has_j3:
-            reason = "three-body Jastrow factor"
-        elif not set(keys) <= LINEAR_DET_KEYS:
-            reason = f"parameters outside {sorted(LINEAR_DET_KEYS)}: {sorted(set(keys) - LINEAR_DET_KEYS)}"
-    if reason is not None:
-        if why is not None:
-            why.append(reason)
-        return None
-    return dev
-
-
-LINEAR_J3_KEYS = LINEAR_DET_KEYS | {"wf3ccoeff"}  # the parameters ``pqa_correlated_j3`` varies
+    return _linear_device("det", wf, keys, why)
 
 
 def linear_j3_device(wf, keys, why=None):
     """The device handle ``pqa_correlated_j3`` can evaluate ``wf`` on while the parameters ``keys`` vary, or None: ``wf`` must be
     exactly Slater x JastrowSpin x ThreeBodyJastrow on one handle, real and untwisted, with one or more determinants, and ``keys``
     within ``LINEAR_J3_KEYS``.  ``why``: a list that receives the reason for a None."""
-    f = getattr(wf, "wf_factors", None)
-    reason, dev = None, None
-    if f is None or len(f) != 3 or type(f[0]) is not Slater or type(f[1]) is not JastrowSpin or type(f[2]) is not ThreeBodyJastrow:
-        reason = "the wave function is not Slater x two-body Jastrow (JastrowSpin) x three-body Jastrow (ThreeBodyJastrow) on one device handle"
-    else:
-        dev = wf.fused_device()
-        if dev is None:
-            reason = "the wave function has no fused device handle"
-        elif dev.cplx or dev.twisted:
-            reason = "complex orbitals / twisted cell"
-        elif not dev.has_j3:
-            reason = "the device handle has no three-body Jastrow factor"
-        elif not set(keys) <= LINEAR_J3_KEYS:
-            reason = f"parameters outside {sorted(LINEAR_J3_KEYS)}: {sorted(set(keys) - LINEAR_J3_KEYS)}"
-    if reason is not None:
-        if why is not None:
-            why.append(reason)
-        return None
-    return dev
+    return _linear_device("j3", wf, keys, why)
 
 
 def _ion_cusp_list(mol, ion_cusp):
