@@ -30,11 +30,10 @@ Deliberate differences from the reference:
 * ``updateinternals(saved_values=None)`` works; the reference reads a missing ``self.wf_factors`` (addwf.py:55).
 """
 
-import ctypes as C
-
 import numpy as np
 
 from . import _ffi
+from .sample_many import component_devices, finish, handle_array
 from .wf import Parameters
 
 MAX_FUSED = 8
@@ -49,10 +48,6 @@ def _handles(wf):
     return set() if d is None else {id(d)}
 
 
-def _hs(devs):
-    return (C.c_void_p * len(devs))(*[d._h.value for d in devs])
-
-
 def add_weights(devs, coeffs, sign=True, logabs=True, w=True):
     """``pqa_add_weights`` -> (sign (W), log|Psi| (W), w (K, W)); None where not asked for."""
     K, W = len(devs), devs[0].W
@@ -60,7 +55,7 @@ def add_weights(devs, coeffs, sign=True, logabs=True, w=True):
     s = np.empty(W) if sign else None
     l = np.empty(W) if logabs else None
     wk = np.empty((K, W)) if w else None
-    _ffi.check(devs[0]._h, _ffi.lib().pqa_add_weights(_hs(devs), K, _ffi.ptr(c), _ffi.ptr(s), _ffi.ptr(l), _ffi.ptr(wk)))
+    finish(devs, _ffi.lib().pqa_add_weights(handle_array(devs), K, _ffi.ptr(c), _ffi.ptr(s), _ffi.ptr(l), _ffi.ptr(wk)))
     return s, l, wk
 
 
@@ -70,10 +65,8 @@ def add_sweeps(devs, coeffs, tstep, gauss, unif):
     nsteps = gauss.shape[0] // N
     c, gauss, unif = _ffi.f64(coeffs), _ffi.f64(gauss), _ffi.f64(unif)
     acc = np.empty(nsteps)
-    rc = _ffi.lib().pqa_add_sweeps(_hs(devs), K, _ffi.ptr(c), float(tstep), int(nsteps), _ffi.ptr(gauss), _ffi.ptr(unif), _ffi.ptr(acc))
-    for d in devs:
-        d._zero = [None, None]  # (the determinants changed)
-    _ffi.check(devs[0]._h, rc)
+    rc = _ffi.lib().pqa_add_sweeps(handle_array(devs), K, _ffi.ptr(c), float(tstep), int(nsteps), _ffi.ptr(gauss), _ffi.ptr(unif), _ffi.ptr(acc))
+    finish(devs, rc, moved=True)
     return acc
 
 
@@ -84,10 +77,8 @@ def add_energy(devs, coeffs, threshold=10.0, rot=None, unif=None, seed=0):
     rot = None if rot is None else _ffi.f64(rot)
     unif = None if unif is None else _ffi.f64(unif)
     out = np.empty((6, W))
-    rc = _ffi.lib().pqa_add_energy(_hs(devs), K, _ffi.ptr(c), float(threshold), _ffi.ptr(rot), _ffi.ptr(unif), int(seed), _ffi.ptr(out))
-    for d in devs:
-        d._zero = [None, None]
-    _ffi.check(devs[0]._h, rc)
+    rc = _ffi.lib().pqa_add_energy(handle_array(devs), K, _ffi.ptr(c), float(threshold), _ffi.ptr(rot), _ffi.ptr(unif), int(seed), _ffi.ptr(out))
+    finish(devs, rc, moved=True)
     return out
 
 
@@ -135,14 +126,9 @@ class AddWF:
             return None, f"more than {MAX_FUSED} components"
         if any(np.iscomplexobj(c) and np.imag(c) != 0 for c in self.coeffs):
             return None, "complex coeffs"
-        devs = []
-        for k, wf in enumerate(self.wf_components):
-            d = wf._product_device() if hasattr(wf, "_product_device") else None
-            if d is None:
-                return None, f"component {k} is not a real Slater x two-body Jastrow product on one device handle"
-            if d.pbc or getattr(d, "twisted", False):
-                return None, f"component {k} is periodic"
-            devs.append(d)
+        devs, why = component_devices(self.wf_components, "component")
+        if devs is None:
+            return None, why
         if len({d.device for d in devs}) != 1:
             return None, "the components live on different devices"
         if len({(d.nelec, d.N) for d in devs}) != 1:

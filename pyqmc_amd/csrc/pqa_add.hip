@@ -6,16 +6,10 @@
 //   grad_e Psi / Psi at R'   = sum_k rho_k grad_e Psi_k / Psi_k
 //   E_L                      = sum_k w_k E_L,k                                (H is linear)
 //
-// pqa_add_sweeps, per electron e (spin s), all K handles' work ordered on the first handle's stream (pqa_multi.hpp):
-//   has-zero   multi_flags; e's current position gathered (k_ovl_gather); every handle's value (values_dev)
-//   old rows   per handle: rows_at the current position
-//   proposal   k_add_propose: w_k from the values, the drift sum_k rho_k g_k with AddWF.gradient_value's rules, limdrift,
-//              x + gauss + tstep grad into every handle's b_newpos
-//   new rows   per handle: rows_at the proposed position (the saved rows of the update)
-//   decision   k_add_decide: the new drift likewise, val = sum_k w_k val_k, t_prob |val|^2 against the uniform draw; the mask into
-//              every handle's b_mask, the walker's accepted moves of the sweep counted
-//   update     multi_update
-// After each sweep k_add_mean turns the counts into the accepted fraction (a fixed-order tree) and clears them.
+// pqa_add_sweeps is multi_sweeps of pqa_multi.hpp with
+//   proposal   k_add_propose: w_k from the values, the drift sum_k rho_k g_k with AddWF.gradient_value's rules, limdrift
+//   decision   k_add_decide: the new drift likewise, val = sum_k w_k val_k, t_prob |val|^2 against the uniform draw
+//   after      k_ovl_fraction: the sweep's accepted fraction, the counts cleared
 #include "pqa_multi.hpp"
 
 #pragma clang fp contract(off)  // (as pqa_multi.hpp: this unit's own kernels too)
@@ -99,11 +93,7 @@ __global__ __launch_bounds__(256) void k_add_propose(OvlPtrs P, AddCoef C, int K
   }
   add_gradient_value(P, K, W, w, wk, g, val);
   limdrift1(g);
-  for (int d = 0; d < 3; ++d) {
-    grad[3 * w + d] = g[d];
-    const double x = (P.pts[0][3 * w + d] + gauss[3 * w + d]) + g[d] * tstep;
-    for (int k = 0; k < K; ++k) P.newpos[k][3 * w + d] = x;
-  }
+  multi_propose(P, K, w, tstep, gauss, g, grad);
 }
 
 __global__ __launch_bounds__(256) void k_add_decide(OvlPtrs P, int K, long W, double tstep, const double* __restrict__ gauss,
@@ -115,29 +105,8 @@ __global__ __launch_bounds__(256) void k_add_decide(OvlPtrs P, int K, long W, do
   for (int k = 0; k < K; ++k) wk[k] = wts[(size_t)k * W + w];
   add_gradient_value(P, K, W, w, wk, ng, val);
   limdrift1(ng);
-  double gs[3], bs[3];
-  for (int d = 0; d < 3; ++d) {
-    gs[d] = gauss[3 * w + d];
-    bs[d] = gs[d] + tstep * (grad[3 * w + d] + ng[d]);
-  }
-  const double forward = gs[0] * gs[0] + gs[1] * gs[1] + gs[2] * gs[2];
-  const double backward = bs[0] * bs[0] + bs[1] * bs[1] + bs[2] * bs[2];
-  const double t_prob = exp(1.0 / (2.0 * tstep) * (forward - backward));
-  const bool acc = fabs(val) * fabs(val) * t_prob > unif[w];
-  for (int k = 0; k < K; ++k) P.mask[k][w] = acc;
-  nacc[w] += acc ? 1.0 : 0.0;
-}
-
-// out[0] = sum_w nacc[w] / denom in a fixed order (one block); the counts cleared for the next sweep
-__global__ __launch_bounds__(256) void k_add_mean(double* __restrict__ nacc, long W, double denom, double* __restrict__ out) {
-  __shared__ double part[256];
-  double a = 0.0;
-  for (long w = threadIdx.x; w < W; w += 256) {
-    a += nacc[w];
-    nacc[w] = 0.0;
-  }
-  a = block_sum256(a, part);
-  if (threadIdx.x == 0) out[0] = a / denom;
+  const double t_prob = multi_tprob(w, tstep, gauss, grad, ng);
+  multi_accept(P, K, w, fabs(val) * fabs(val) * t_prob > unif[w], nacc);
 }
 
 // grad2[w] (+)= |sum_k w_k g_k|^2 of the electron whose rows are in b_out (g_k = grad D_k / D_k + grad U_k at the current position)
@@ -180,49 +149,30 @@ __global__ __launch_bounds__(256) void k_add_combine(AddRows E, int K, long W, c
   out[5 * W + w] = ke + ee + ei + ec + ii;
 }
 
-// what the three entry points do first: the handles checked, their states current, their streams shared from here on by the caller
-int add_begin(pqa_handle* const* hs, int K, const double* coeffs, const char* fn, AddCoef& C) {
-  pqa_handle* h = hs[0];
-  if (!coeffs) FAIL(std::string(fn) + ": coeffs must not be NULL");
-  TRY(multi_validate(hs, K, fn));
-  HIPCHK(hipSetDevice(h->device));
-  for (int k = 0; k < K; ++k) C.c[k] = coeffs[k];
-  return multi_begin(hs, K, fn);
-}
-
-int all_values(pqa_handle* const* hs, int K) {
-  for (int k = 0; k < K; ++k) {
-    int rc = values_dev(hs[k]);
-    if (rc) { hs[0]->err = hs[k]->err; return rc; }
-  }
-  return 0;
-}
-
-int all_rows(pqa_handle* const* hs, int K, int e, double* const* pts) {
-  for (int k = 0; k < K; ++k) {
-    int rc = rows_at(hs[k], e, pts[k]);
-    if (rc) { hs[0]->err = hs[k]->err; return rc; }
-  }
+// what the three entry points do after their own argument checks: the coefficients checked, the shared opening, the coefficients kept
+int add_open(MultiCall& mc, const double* coeffs, AddCoef& C) {
+  pqa_handle* h = mc.h;
+  if (!coeffs) FAIL(std::string(mc.fn) + ": coeffs must not be NULL");
+  TRY(mc.open());
+  for (int k = 0; k < mc.K; ++k) C.c[k] = coeffs[k];
   return 0;
 }
 
 }  // namespace
 
 extern "C" int pqa_add_weights(pqa_handle_t* const* hs, int K, const double* coeffs, double* sign, double* logabs, double* w) {
-  if (!hs || K < 1 || !hs[0]) return -2;
-  pqa_handle* h = hs[0];  // (errors are reported on the first handle)
+  MultiCall mc(hs, K, "pqa_add_weights", true);  // (it sizes the per-move scratch and clears dmc_old_valid, as it always has)
+  pqa_handle* h = mc.h;
+  if (!h) return -2;
   AddCoef C{};
-  TRY(add_begin(hs, K, coeffs, "pqa_add_weights", C));
+  TRY(add_open(mc, coeffs, C));
   const long W = h->W;
-  StreamShare share(hs, K);
-  OvlPtrs P{};
-  TRY(multi_buffers(hs, K, P));
   TRY(ensure(h, h->b_add, (size_t)(K + 2) * W * sizeof(double)));
   double* d_s = (double*)h->b_add.p;
   double* d_l = d_s + W;
   double* d_w = d_l + W;
-  TRY(all_values(hs, K));
-  hipLaunchKernelGGL(k_add_weights, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, h->stream, P, C, K, W, sign ? d_s : nullptr,
+  TRY(multi_values(hs, K));
+  hipLaunchKernelGGL(k_add_weights, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, h->stream, mc.P, C, K, W, sign ? d_s : nullptr,
                      logabs ? d_l : nullptr, w ? d_w : nullptr);
   TRY(check_launch(h, "k_add_weights"));
   if (sign) TRY(copy_in(h, sign, d_s, (size_t)W * sizeof(double)));
@@ -232,68 +182,50 @@ extern "C" int pqa_add_weights(pqa_handle_t* const* hs, int K, const double* coe
 
 extern "C" int pqa_add_sweeps(pqa_handle_t* const* hs, int K, const double* coeffs, double tstep, int nsteps, const double* gauss,
                               const double* unif, double* acc) {
-  if (!hs || K < 1 || !hs[0]) return -2;
-  pqa_handle* h = hs[0];  // (errors are reported on the first handle)
+  MultiCall mc(hs, K, "pqa_add_sweeps", true);
+  pqa_handle* h = mc.h;
+  if (!h) return -2;
   if (nsteps < 0) FAIL("pqa_add_sweeps: nsteps must not be negative");
   if (!gauss || !unif) FAIL("pqa_add_sweeps: gauss and unif must not be NULL");
   AddCoef C{};
-  TRY(add_begin(hs, K, coeffs, "pqa_add_sweeps", C));
+  TRY(add_open(mc, coeffs, C));
   const long W = h->W;
-  const int N = h->N;
-  StreamShare share(hs, K);
-  OvlPtrs P{};
-  TRY(multi_buffers(hs, K, P));
-  // scratch on the first handle: one sweep's tapes (N W 3 + N W), the weights (K W), the old drift (3 W), acceptance counts (W),
-  // per-sweep accepted fractions (nsteps)
-  const size_t ng = (size_t)N * W * 3, nu = (size_t)N * W, nw = (size_t)K * W;
-  TRY(ensure(h, h->b_add, (ng + nu + nw + 3 * (size_t)W + W + (size_t)std::max(nsteps, 1)) * sizeof(double)));
-  double* d_g = (double*)h->b_add.p;
-  double* d_u = d_g + ng;
-  double* d_w = d_u + nu;
-  double* d_grad = d_w + nw;
-  double* d_acc = d_grad + 3 * (size_t)W;
-  double* d_o = d_acc + W;
+  const OvlPtrs& P = mc.P;
+  const dim3 gb((unsigned)((W + 255) / 256)), tb(256);
   hipStream_t st = h->stream;
-  HIPCHK(hipMemsetAsync(d_acc, 0, (size_t)W * sizeof(double), st));
-  const unsigned gb = (unsigned)((W + 255) / 256);
-  for (int n = 0; n < nsteps; ++n) {
-    TRY(copy_in(h, d_g, gauss + (size_t)n * ng, ng * sizeof(double)));
-    TRY(copy_in(h, d_u, unif + (size_t)n * nu, nu * sizeof(double)));
-    for (int e = 0; e < N; ++e) {
-      const int s = e >= h->nup;
-      TRY(multi_flags(hs, K, s));
-      hipLaunchKernelGGL(k_ovl_gather, dim3(gb), dim3(256), 0, st, P, K, N, e, W);
-      TRY(check_launch(h, "k_has_zero / k_ovl_gather"));
-      TRY(all_values(hs, K));
-      TRY(all_rows(hs, K, e, P.pts));
-      hipLaunchKernelGGL(k_add_propose, dim3(gb), dim3(256), 0, st, P, C, K, W, tstep, (const double*)(d_g + (size_t)e * W * 3), d_w, d_grad);
-      TRY(check_launch(h, "k_add_propose"));
-      TRY(all_rows(hs, K, e, P.newpos));
-      hipLaunchKernelGGL(k_add_decide, dim3(gb), dim3(256), 0, st, P, K, W, tstep, (const double*)(d_g + (size_t)e * W * 3),
-                         (const double*)(d_u + (size_t)e * W), (const double*)d_w, (const double*)d_grad, d_acc);
-      TRY(check_launch(h, "k_add_decide"));
-      TRY(multi_update(hs, K, e, s));
-    }
-    hipLaunchKernelGGL(k_add_mean, dim3(1), dim3(256), 0, st, d_acc, W, (double)W * N, d_o + n);
-    TRY(check_launch(h, "k_add_mean"));
-  }
-  return copy_out(h, acc, d_o, acc ? (size_t)nsteps * sizeof(double) : 0);
+  // scratch of its own: the weights (K W), the per-sweep accepted fractions (nsteps)
+  const size_t nw = (size_t)K * W;
+  SweepScratch sc{};
+  TRY(multi_sweeps(
+      mc, h->b_add, nw + nsteps, nsteps, gauss, unif, sc,
+      [&](const double* g) {
+        hipLaunchKernelGGL(k_add_propose, gb, tb, 0, st, P, C, K, W, tstep, g, sc.own, sc.grad);
+        return check_launch(h, "k_add_propose");
+      },
+      [&](const double* g, const double* u) {
+        hipLaunchKernelGGL(k_add_decide, gb, tb, 0, st, P, K, W, tstep, g, u, (const double*)sc.own, (const double*)sc.grad, sc.acc);
+        return check_launch(h, "k_add_decide");
+      },
+      [&](int n) {
+        hipLaunchKernelGGL((k_ovl_fraction<>), dim3(1), tb, 0, st, sc.acc, W, (double)W * h->N, sc.own + nw + n);
+        return check_launch(h, "k_ovl_fraction");
+      }));
+  return copy_out(h, acc, sc.own + nw, acc ? (size_t)nsteps * sizeof(double) : 0);
 }
 
 extern "C" int pqa_add_energy(pqa_handle_t* const* hs, int K, const double* coeffs, double threshold, const double* rot,
                               const double* unif, uint64_t seed, double* out) {
-  if (!hs || K < 1 || !hs[0]) return -2;
-  pqa_handle* h = hs[0];  // (errors are reported on the first handle)
+  MultiCall mc(hs, K, "pqa_add_energy", true);
+  pqa_handle* h = mc.h;
+  if (!h) return -2;
   if (!out) FAIL("pqa_add_energy: out must not be NULL");
   AddCoef C{};
-  TRY(add_begin(hs, K, coeffs, "pqa_add_energy", C));
+  TRY(add_open(mc, coeffs, C));
   for (int k = 0; k < K; ++k)
     if (hs[k]->ecpb_on) FAIL("pqa_add_energy: the semi-local ECP integrator only (pqa_set_ecp_batched is on)");
   const long W = h->W;
   const int N = h->N;
-  StreamShare share(hs, K);
-  OvlPtrs P{};
-  TRY(multi_buffers(hs, K, P));
+  const OvlPtrs& P = mc.P;
   TRY(ensure(h, h->b_add, (size_t)(K + 6) * W * sizeof(double)));
   double* d_w = (double*)h->b_add.p;
   double* d_out = d_w + (size_t)K * W;
@@ -301,18 +233,18 @@ extern "C" int pqa_add_energy(pqa_handle_t* const* hs, int K, const double* coef
   const unsigned gb = (unsigned)((W + 255) / 256);
   // every handle's own energy pass with the same draws: its six rows stay in its b_en
   AddRows E{};
-  for (int k = 0; k < K; ++k) {
-    int rc = energy_dev(hs[k], threshold, rot, unif, seed, 0u);
-    if (rc) { h->err = hs[k]->err; return rc; }
-    E.en[k] = (const double*)hs[k]->b_en.p;
-  }
-  TRY(all_values(hs, K));
+  TRY(multi_each(hs, K, [&](pqa_handle* g, int k) {
+    TRY(energy_dev(g, threshold, rot, unif, seed, 0u));
+    E.en[k] = (const double*)g->b_en.p;
+    return 0;
+  }));
+  TRY(multi_values(hs, K));
   hipLaunchKernelGGL(k_add_weights, dim3(gb), dim3(256), 0, st, P, C, K, W, (double*)nullptr, (double*)nullptr, d_w);
   TRY(check_launch(h, "k_add_weights"));
   for (int e = 0; e < N; ++e) {
     hipLaunchKernelGGL(k_ovl_gather, dim3(gb), dim3(256), 0, st, P, K, N, e, W);
     TRY(check_launch(h, "k_ovl_gather"));
-    TRY(all_rows(hs, K, e, P.pts));
+    TRY(multi_rows(hs, K, e, P.pts));
     hipLaunchKernelGGL(k_add_grad2, dim3(gb), dim3(256), 0, st, P, K, W, (const double*)d_w, (int)(e == 0), d_out + 4 * (size_t)W);
     TRY(check_launch(h, "k_add_grad2"));
   }

@@ -104,39 +104,13 @@ __global__ __launch_bounds__(256) void k_mix_gather_wt(SrSources S, const int* _
   A[idx] = v;
 }
 
-// The handles of a mixture estimator: pqa_overlap_sweeps' scope; then, as pqa_sr_moments, every handle's walker-major state current,
-// its saved gradient_value rows dropped and its queued work done before its stream is shared.
-int mix_begin(pqa_handle* const* hs, int K, const char* fn) {
-  pqa_handle* h = hs[0];
-  TRY(multi_validate(hs, K, fn));
-  HIPCHK(hipSetDevice(h->device));
-  for (int k = 0; k < K; ++k) {
-    pqa_handle* g = hs[k];
-    int rc = sync_aos(g);
-    if (!rc) rc = jas_refresh(g);
-    if (rc) { h->err = g->err; return rc; }
-    g->saved_valid = false;
-  }
-  for (int k = 1; k < K; ++k) {
-    hipError_t e = hipStreamSynchronize(hs[k]->stream);
-    if (e != hipSuccess) FAIL(std::string(fn) + ": " + hipGetErrorString(e));
-  }
-  return 0;
-}
-
 // values of every handle, then the weights (K, K, W) and their walker means (K, K) on the first handle's stream
-int mix_weights(pqa_handle* const* hs, int K, OvlPtrs& P, double* d_w, double* d_ovl) {
-  pqa_handle* h = hs[0];
+int mix_weights(const MultiCall& mc, double* d_w, double* d_ovl) {
+  pqa_handle* h = mc.h;
   const long W = h->W;
-  for (int k = 0; k < K; ++k) {
-    int rc = values_dev(hs[k]);
-    if (rc) { h->err = hs[k]->err; return rc; }
-    P.sign[k] = (const double*)hs[k]->b_sign.p;
-    P.lg[k] = (const double*)hs[k]->b_log.p;
-    P.ju[k] = (const double*)hs[k]->b_ju.p;
-  }
-  hipLaunchKernelGGL((k_ovl_weights<>), dim3((unsigned)((W + 255) / 256)), dim3(256), 0, h->stream, P, K, W, d_w);
-  hipLaunchKernelGGL((k_ovl_mean<>), dim3((unsigned)(K * K)), dim3(256), 0, h->stream, (const double*)d_w, W, d_ovl);
+  TRY(multi_values(mc.hs, mc.K));
+  hipLaunchKernelGGL((k_ovl_weights<>), dim3((unsigned)((W + 255) / 256)), dim3(256), 0, h->stream, mc.P, mc.K, W, d_w);
+  hipLaunchKernelGGL((k_ovl_mean<>), dim3((unsigned)(mc.K * mc.K)), dim3(256), 0, h->stream, (const double*)d_w, W, d_ovl);
   return check_launch(h, "k_ovl_weights / k_ovl_mean");
 }
 
@@ -185,15 +159,15 @@ int mix_product(pqa_handle* h, const MixPlan& p, int P, int nx, int sym, long wc
 extern "C" int pqa_mix_moments(pqa_handle_t* const* hs, int K, const int32_t* P, const int32_t* src, const int32_t* pos, double offset,
                                double threshold, const double* rot, const double* unif, const uint64_t* seeds, int64_t walker_chunk_arg,
                                double* overlap, double* en, double* moments, double* u_walker, double* en_walker) {
-  if (!hs || K < 1 || !hs[0]) return -2;
-  pqa_handle* h = hs[0];  // (errors are reported on the first handle)
-  const std::string fn = "pqa_mix_moments";
+  MultiCall mc(hs, K, "pqa_mix_moments", false);  // (as pqa_sr_moments: nothing moves)
+  pqa_handle* h = mc.h;
+  if (!h) return -2;
+  const std::string fn = mc.fn;
   // argument checks first: they need nothing but the handles' host-side sizes
   if (!P || !overlap || !en) FAIL(fn + ": P, overlap and en must not be NULL");
   if ((rot == nullptr) != (unif == nullptr)) FAIL(fn + ": rot and unif come together");
   if (!rot && !seeds) FAIL(fn + ": seeds must not be NULL without rot / unif");
   if (walker_chunk_arg < 0) FAIL(fn + ": walker_chunk must not be negative");
-  if (K > kMaxK) FAIL(fn + ": at most 8 wave functions");
   long ptot = 0;
   int pmax = 0;
   for (int k = 0; k < K; ++k) {
@@ -204,24 +178,22 @@ extern "C" int pqa_mix_moments(pqa_handle_t* const* hs, int K, const int32_t* P,
       FAIL(fn + ": the (P + 2K) x P moments of a state exceed the 256 MiB scratch limit (use the protocol route)");
   }
   if (ptot > 0 && (!src || !pos || !moments)) FAIL(fn + ": src, pos and moments must not be NULL when a state has columns");
-  TRY(mix_begin(hs, K, "pqa_mix_moments"));
+  TRY(mc.open());
   bool need[kMaxK][4] = {};
   for (int k = 0, off = 0; k < K; off += P[k], ++k) TRY(sr_check_columns(h, hs[k], fn, P[k], src + off, pos + off, 2, need[k]));
   const long W = h->W;
-  StreamShare share(hs, K);
   // every handle's energy pass (its own draws) and derivative sources
   MixEn E{};
   SrSources S[kMaxK] = {};
   size_t orot = 0, ounif = 0;
-  for (int k = 0; k < K; ++k) {
-    pqa_handle* g = hs[k];
-    int rc = energy_dev(g, threshold, rot ? rot + orot : nullptr, unif ? unif + ounif : nullptr, seeds ? seeds[k] : 0, 0u);
-    if (!rc) rc = sr_sources(g, need[k], S[k]);
-    if (rc) { h->err = g->err; return rc; }
+  TRY(multi_each(hs, K, [&](pqa_handle* g, int k) {
+    TRY(energy_dev(g, threshold, rot ? rot + orot : nullptr, unif ? unif + ounif : nullptr, seeds ? seeds[k] : 0, 0u));
+    TRY(sr_sources(g, need[k], S[k]));
     E.en[k] = (const double*)g->b_en.p;
     orot += (size_t)g->N * g->necp * 9;
     ounif += (size_t)g->N * g->necp * W;
-  }
+    return 0;
+  }));
   // plans of the states' products
   MixPlan plan[kMaxK];
   size_t amax = 0, pamax = 0, mmax = 0;
@@ -252,10 +224,9 @@ extern "C" int pqa_mix_moments(pqa_handle_t* const* hs, int K, const int32_t* P,
   };
   TRY(ensure(h, h->b_sr, layout(Carver())));
   layout(Carver(h->b_sr.p));
-  OvlPtrs O{};
-  TRY(mix_weights(hs, K, O, d_w, d_ovl));
+  TRY(mix_weights(mc, d_w, d_ovl));
   const unsigned gb = (unsigned)((W + 255) / 256);
-  hipLaunchKernelGGL(k_mix_scale, dim3(gb), dim3(256), 0, h->stream, O, K, W, d_a, d_s, u_walker ? d_u : nullptr);
+  hipLaunchKernelGGL(k_mix_scale, dim3(gb), dim3(256), 0, h->stream, mc.P, K, W, d_a, d_s, u_walker ? d_u : nullptr);
   hipLaunchKernelGGL(k_mix_en, dim3((unsigned)(6 * K * K)), dim3(256), 0, h->stream, E, (const double*)d_w, K, W, offset, d_en);
   TRY(check_launch(h, "k_mix_scale / k_mix_en"));
   size_t moff = 0;
@@ -287,26 +258,25 @@ extern "C" int pqa_mix_moments(pqa_handle_t* const* hs, int K, const int32_t* P,
 
 extern "C" int pqa_mix_wtdp(pqa_handle_t* const* hs, int K, int P, const int32_t* src, const int32_t* pos, int64_t walker_chunk_arg,
                             double* overlap, double* wtdp) {
-  if (!hs || K < 1 || !hs[0]) return -2;
-  pqa_handle* h = hs[0];  // (errors are reported on the first handle)
-  const std::string fn = "pqa_mix_wtdp";
+  MultiCall mc(hs, K, "pqa_mix_wtdp", false);
+  pqa_handle* h = mc.h;
+  if (!h) return -2;
+  const std::string fn = mc.fn;
   if (P < 1) FAIL(fn + ": P must be at least 1");
   if (!src || !pos || !overlap || !wtdp) FAIL(fn + ": src, pos, overlap and wtdp must not be NULL");
   if (walker_chunk_arg < 0) FAIL(fn + ": walker_chunk must not be negative");
-  if (K > kMaxK) FAIL(fn + ": at most 8 wave functions");
   const int npair = K * (K + 1) / 2;
   if ((size_t)(P + npair) * P * sizeof(double) > kChunkScratchBytes)
     FAIL(fn + ": the (P + K (K + 1) / 2) x P partial moments exceed the 256 MiB scratch limit (use the protocol route)");
-  TRY(mix_begin(hs, K, "pqa_mix_wtdp"));
+  TRY(mc.open());
   pqa_handle* g = hs[K - 1];  // the derivatives are the last state's
   bool need[4] = {false, false, false, false};
   TRY(sr_check_columns(h, g, fn, P, src, pos, 2, need));
   const long W = h->W;
-  StreamShare share(hs, K);
   SrSources S{};
-  {
-    int rc = sr_sources(g, need, S);
-    if (rc) { h->err = g->err; return rc; }
+  if (int rc = sr_sources(g, need, S)) {
+    h->err = g->err;
+    return rc;
   }
   const MixPlan p = mix_plan(W, P, npair, (long)walker_chunk_arg);
   // scratch on the first handle
@@ -327,8 +297,7 @@ extern "C" int pqa_mix_wtdp(pqa_handle_t* const* hs, int K, int P, const int32_t
   layout(Carver(h->b_sr.p));
   TRY(copy_in(h, d_src, src, (size_t)P * sizeof(int)));
   TRY(copy_in(h, d_pos, pos, (size_t)P * sizeof(int)));
-  OvlPtrs O{};
-  TRY(mix_weights(hs, K, O, d_w, d_ovl));
+  TRY(mix_weights(mc, d_w, d_ovl));
   hipLaunchKernelGGL(k_mix_fill, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, h->stream, W, d_s);
   TRY(check_launch(h, "k_mix_fill"));
   for (long w0 = 0; w0 < W; w0 += p.Wc) {

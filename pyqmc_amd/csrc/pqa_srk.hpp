@@ -13,7 +13,6 @@
 //   k_sr_reduce      the slices' partial tiles summed in slice order (the same bits on every call), the lower triangle mirrored from
 //                    the upper one (the P x P block is exactly symmetric), added to the running moments of the chunks before (pqa_sr:
 //                    as one term; pqa_mix: slice by slice, so that the chunking does not show in the result);
-//   Carver           the scratch layout of a host function, stated once.
 #pragma once
 #include "pqa_estim.hpp"
 
@@ -99,22 +98,6 @@ inline long sr_slices(long Wc, int nbi, int nbj, size_t nmom) {
   const long nslice = std::min<long>(std::max<long>(1, 1024 / ((long)nbi * nbj)), std::max<long>(1, Wc / 64));
   return std::max<long>(1, std::min<long>(nslice, (long)(kChunkScratchBytes / (nmom * sizeof(double)))));
 }
-
-// Bump carver of a scratch buffer.  A host function states its layout once, as a function that takes its pieces from a Carver; run over
-// a null base it only adds up the bytes (size()), run over the buffer it hands out the pointers, so the two cannot disagree.  Every piece
-// starts on an 8-byte boundary.
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b = nullptr) : base((char*)b) {}
-  template <class T>
-  T* take(size_t n) {
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += (n * sizeof(T) + 7) & ~(size_t)7;
-    return p;
-  }
-  size_t size() const { return off; }
-};
 
 }  // namespace
 

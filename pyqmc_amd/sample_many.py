@@ -64,6 +64,31 @@ def rolling_average(block, data, nsteps):
         block[k] += it / nsteps
 
 
+def component_devices(wfs, noun):
+    """``(handles, None)``, or ``(None, reason)`` at the first member of ``wfs`` that is not a real Slater x two-body Jastrow product on
+    one handle with open boundaries; ``noun`` is the caller's word for a member ("wave function", ``AddWF.scope``: "component")."""
+    devs = []
+    for i, wf in enumerate(wfs):
+        d = wf._product_device() if hasattr(wf, "_product_device") else None
+        if d is None:
+            return None, f"{noun} {i} is not a real Slater x two-body Jastrow product on one device handle"
+        if d.pbc or getattr(d, "twisted", False):
+            return None, f"{noun} {i} is periodic"
+        devs.append(d)
+    return devs, None
+
+
+def handle_array(devs):
+    return (C.c_void_p * len(devs))(*[d._h.value for d in devs])
+
+
+def finish(devs, rc, moved=False):
+    """The tail of a multi-handle wrapper; ``moved``: the call moved walkers or ran the handles' energy passes."""
+    for d in devs if moved else ():
+        d._zero = [None, None]  # (the determinants changed)
+    _ffi.check(devs[0]._h, rc)
+
+
 def fused_scope(wfs, configs=None):
     """``(handles, None)`` when the multi-handle device calls (``pqa_overlap_sweeps``, ``pqa_mix_moments``) can take ``wfs``, else
     ``(None, reason)``; see the module docstring.  ``configs`` None: the walkers are the resident ones, only the handles are looked at."""
@@ -71,14 +96,9 @@ def fused_scope(wfs, configs=None):
         return None, f"{len(wfs)} wave functions (the device calls take 1 to 8)"
     if configs is not None and (hasattr(configs, "wrap") or np.ndim(configs.configs) != 3):
         return None, "periodic walkers"
-    devs = []
-    for i, wf in enumerate(wfs):
-        d = wf._product_device() if hasattr(wf, "_product_device") else None
-        if d is None:
-            return None, f"wave function {i} is not a real Slater x two-body Jastrow product on one device handle"
-        if d.pbc or getattr(d, "twisted", False):
-            return None, f"wave function {i} is periodic"
-        devs.append(d)
+    devs, why = component_devices(wfs, "wave function")
+    if devs is None:
+        return None, why
     if len({id(d) for d in devs}) != len(devs):
         return None, "two wave functions share a device handle"
     if len({d.device for d in devs}) != 1:
@@ -110,17 +130,10 @@ def overlap_sweeps(devs, tstep, gauss, unif, weights=False):
     ovl = np.empty((nsteps, K, K))
     wts = np.empty((K, K, W)) if weights else None
     acc = C.c_double()
-    hs = (C.c_void_p * K)(*[d._h.value for d in devs])
-    rc = _ffi.lib().pqa_overlap_sweeps(hs, K, float(tstep), int(nsteps), _ffi.ptr(gauss), _ffi.ptr(unif), _ffi.ptr(ovl),
+    rc = _ffi.lib().pqa_overlap_sweeps(handle_array(devs), K, float(tstep), int(nsteps), _ffi.ptr(gauss), _ffi.ptr(unif), _ffi.ptr(ovl),
                                        None if wts is None else _ffi.ptr(wts), C.byref(acc))
-    for d in devs:
-        d._zero = [None, None]  # (the determinants changed)
-    _ffi.check(devs[0]._h, rc)
+    finish(devs, rc, moved=True)
     return ovl, wts, acc.value
-
-
-def _handles(devs):
-    return (C.c_void_p * len(devs))(*[d._h.value for d in devs])
 
 
 def mix_moments(devs, columns, offset=0.0, threshold=10.0, rot=None, unif=None, seeds=None, walker_chunk=0, per_walker=False):
@@ -147,10 +160,10 @@ def mix_moments(devs, columns, offset=0.0, threshold=10.0, rot=None, unif=None, 
     moments = np.empty(max(sum(sizes), 1))
     u = np.empty((K, W)) if per_walker else None
     enw = np.empty((K, W, 6)) if per_walker else None
-    rc = _ffi.lib().pqa_mix_moments(_handles(devs), K, _ffi.ptr(P), _ffi.ptr(src), _ffi.ptr(pos), float(offset), float(threshold),
+    rc = _ffi.lib().pqa_mix_moments(handle_array(devs), K, _ffi.ptr(P), _ffi.ptr(src), _ffi.ptr(pos), float(offset), float(threshold),
                                     _ffi.ptr(rot), _ffi.ptr(unif), _ffi.ptr(seeds), int(walker_chunk), _ffi.ptr(overlap), _ffi.ptr(en),
                                     _ffi.ptr(moments), _ffi.ptr(u), _ffi.ptr(enw))
-    _ffi.check(devs[0]._h, rc)
+    finish(devs, rc)
     offs = np.concatenate(([0], np.cumsum(sizes)))
     mom = [moments[offs[i]:offs[i + 1]].reshape(int(P[i]) + 2 * K, int(P[i])) if P[i] else None for i in range(K)]
     return (overlap, en, mom, u, enw) if per_walker else (overlap, en, mom)
@@ -164,9 +177,9 @@ def mix_wtdp(devs, src, pos, walker_chunk=0):
     if len(src) != len(pos):
         raise ValueError("src and pos must be equally long")
     overlap, wtdp = np.empty((K, K)), np.empty((K, K, len(src)))
-    rc = _ffi.lib().pqa_mix_wtdp(_handles(devs), K, len(src), _ffi.ptr(src), _ffi.ptr(pos), int(walker_chunk), _ffi.ptr(overlap),
+    rc = _ffi.lib().pqa_mix_wtdp(handle_array(devs), K, len(src), _ffi.ptr(src), _ffi.ptr(pos), int(walker_chunk), _ffi.ptr(overlap),
                                  _ffi.ptr(wtdp))
-    _ffi.check(devs[0]._h, rc)
+    finish(devs, rc)
     return overlap, wtdp
 
 
