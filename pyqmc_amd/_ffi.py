@@ -25,6 +25,17 @@ class DmcTapes(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("gauss", "unif", "tm_rot", "tm_unif", "tm_u1", "tm_u2", "ecp_rot", "ecp_unif")]
 
 
+def dmc_tapes(tapes):
+    """(``DmcTapes`` of a tape dictionary, the float64 arrays it points into: keep them alive across the call).  An array that already is
+    contiguous float64 is pointed into itself, so the device's own draws (``pqa_philox_dmc_tapes``) land in the dictionary."""
+    tp, keep = DmcTapes(), []
+    for name, _ in DmcTapes._fields_:
+        if tapes.get(name) is not None:
+            keep.append(f64(tapes[name]))
+            setattr(tp, name, keep[-1].ctypes.data)
+    return tp, keep
+
+
 class SystemStruct(C.Structure):
     """Mirror of ``pqa_system_t``."""
 

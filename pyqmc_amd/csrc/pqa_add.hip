@@ -161,7 +161,7 @@ int add_open(MultiCall& mc, const double* coeffs, AddCoef& C) {
 }  // namespace
 
 extern "C" int pqa_add_weights(pqa_handle_t* const* hs, int K, const double* coeffs, double* sign, double* logabs, double* w) {
-  MultiCall mc(hs, K, "pqa_add_weights", true);  // (it sizes the per-move scratch and clears dmc_old_valid, as it always has)
+  MultiCall mc(hs, K, "pqa_add_weights", true);  // (it sizes the per-move scratch and clears dmc.old_valid, as it always has)
   pqa_handle* h = mc.h;
   if (!h) return -2;
   AddCoef C{};

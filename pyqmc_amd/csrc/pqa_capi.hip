@@ -5,7 +5,7 @@
 
 // ---------------------------------------------------------------- parameters
 extern "C" int pqa_set_param(pqa_handle_t* h, const char* name, const double* data, int64_t n) {
-  h->dmc_old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
+  h->dmc.old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
   const std::string k(name);
@@ -220,7 +220,7 @@ int slater_value_dev(pqa_handle* h) {
 }
 
 extern "C" int pqa_slater_recompute(pqa_handle_t* h, const double* configs, int64_t W, double* sign, double* logabs) {
-  h->dmc_old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
+  h->dmc.old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_slater) FAIL("handle has no Slater factor");
@@ -375,7 +375,7 @@ extern "C" int pqa_slater_has_zero(pqa_handle_t* h, int spin, int* flag) {
 }
 
 extern "C" int pqa_slater_update(pqa_handle_t* h, int e, const double* epos, const uint8_t* mask, int use_saved) {
-  h->dmc_old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
+  h->dmc.old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_slater || h->W == 0) FAIL("Slater state not initialised (call recompute)");
@@ -426,7 +426,7 @@ extern "C" int pqa_slater_get_state(pqa_handle_t* h, int spin, double* inverse, 
 
 // ---------------------------------------------------------------- Jastrow
 extern "C" int pqa_jastrow_recompute(pqa_handle_t* h, const double* configs, int64_t W, double* logval) {
-  h->dmc_old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
+  h->dmc.old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_j2) FAIL("handle has no two-body Jastrow factor");
@@ -497,7 +497,7 @@ extern "C" int pqa_j3_pgradient(pqa_handle_t* h, double* d_ccoeff) {
 }
 
 extern "C" int pqa_j3_recompute(pqa_handle_t* h, const double* configs, int64_t W, double* logval) {
-  h->dmc_old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
+  h->dmc.old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_j3) FAIL("handle has no three-body Jastrow factor");
@@ -517,7 +517,7 @@ extern "C" int pqa_j3_recompute(pqa_handle_t* h, const double* configs, int64_t 
 }
 
 extern "C" int pqa_j3_update(pqa_handle_t* h, int e, const double* epos, const uint8_t* mask) {
-  h->dmc_old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
+  h->dmc.old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_j3 || h->W == 0) FAIL("three-body Jastrow state not initialised (call recompute)");
@@ -536,7 +536,7 @@ extern "C" int pqa_j3_update(pqa_handle_t* h, int e, const double* epos, const u
 }
 
 extern "C" int pqa_jastrow_update(pqa_handle_t* h, int e, const double* epos, const uint8_t* mask) {
-  h->dmc_old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
+  h->dmc.old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_j2 || h->W == 0) FAIL("Jastrow state not initialised (call recompute)");
@@ -580,7 +580,7 @@ extern "C" int pqa_wf_eval(pqa_handle_t* h, int e, const double* pts, int jmode,
 }
 
 extern "C" int pqa_wf_update(pqa_handle_t* h, int e, const double* epos, const uint8_t* mask, int use_saved, int* has_zero) {
-  h->dmc_old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
+  h->dmc.old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (!h->has_slater || !h->has_j2 || h->has_j3 || h->cplx || h->W == 0) FAIL("pqa_wf_update: a real Slater x two-body-Jastrow product with resident walkers");
@@ -648,7 +648,7 @@ static int wf_value_host(pqa_handle* h, double* sign, double* logabs) {
 }
 
 extern "C" int pqa_wf_recompute(pqa_handle_t* h, const double* configs, int64_t W, double* sign, double* logabs) {
-  h->dmc_old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
+  h->dmc.old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   TRY(ensure_walkers(h, W));
@@ -689,7 +689,7 @@ static int gather_swap(pqa_handle* h, DevBuf& cur, DevBuf& alt, const int* d_idx
   return 0;
 }
 extern "C" int pqa_resample(pqa_handle_t* h, const int32_t* newinds) {
-  h->dmc_old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
+  h->dmc.old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (h->W == 0) FAIL("state not initialised (call recompute)");
@@ -754,7 +754,7 @@ static int recompute_range(pqa_handle* h, long w0, long n) {
 }
 
 extern "C" int pqa_branch_exchange(pqa_handle_t* h, const int32_t* keep_src, int64_t nkeep, const double* recv_x, int64_t nrecv) {
-  h->dmc_old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
+  h->dmc.old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
   TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (h->W == 0) FAIL("state not initialised (call recompute)");
@@ -979,15 +979,12 @@ extern "C" int pqa_philox_dmc_tapes(pqa_handle_t* h, uint64_t seed, int nsteps, 
   HIPCHK(hipSetDevice(h->device));
   if (W <= 0 || nsteps <= 0 || !out || !out->gauss || !out->unif) FAIL("pqa_philox_dmc_tapes: bad arguments");
   const int N = h->N, necp = h->necp;
-  const size_t NW = (size_t)N * W, nrot = (size_t)N * std::max(necp, 1);
-  // batched ECP integrator: ecp_unif / tm_unif are its selection uniforms, (N, W, nsr) per evaluation, and exist only where points are dropped
-  const bool batched = necp > 0 && h->ecpb_on;
-  const int nsr = batched ? h->ecpb_nsr : 0;
-  const bool selu = batched && h->ecpb_nsel < h->ecpb_npoints && nsr > 0;
-  if (necp > 0 && (!out->ecp_rot || (batched ? selu && !out->ecp_unif : !out->ecp_unif))) FAIL("pqa_philox_dmc_tapes: ECP systems need ecp_rot and ecp_unif");
-  const bool tm = necp > 0 && out->tm_rot && (batched ? !selu || out->tm_unif : out->tm_unif != nullptr) && out->tm_u1 && out->tm_u2;
+  const DmcDraws d = dmc_draws(h);  // (the layout of ecp_unif / tm_unif, and whether they exist)
+  const size_t NW = (size_t)N * W, nrot = d.nrot;
+  if (necp > 0 && (!out->ecp_rot || (d.nu > 0 && !out->ecp_unif))) FAIL("pqa_philox_dmc_tapes: ECP systems need ecp_rot and ecp_unif");
+  const bool tm = necp > 0 && out->tm_rot && (d.nu == 0 || out->tm_unif) && out->tm_u1 && out->tm_u2;
   TRY(ensure(h, h->b_gauss, NW * 3 * sizeof(double)));
-  TRY(ensure(h, h->b_unif, std::max(std::max(NW, nrot * (size_t)W), NW * (size_t)nsr) * sizeof(double)));
+  TRY(ensure(h, h->b_unif, NW * std::max(d.nu, 1) * sizeof(double)));
   TRY(ensure(h, h->b_rot, nrot * 9 * sizeof(double)));
   auto plane = [&](uint32_t stream, uint32_t step, size_t ncount, const double* dst) -> int {
     hipLaunchKernelGGL(k_uniform_plane, dim3((unsigned)((ncount * W + 255) / 256)), dim3(256), 0, h->stream, seed, stream, step, (long)ncount, (long)W,
@@ -996,9 +993,9 @@ extern "C" int pqa_philox_dmc_tapes(pqa_handle_t* h, uint64_t seed, int nsteps, 
     return copy_out(h, const_cast<double*>(dst), h->b_unif.p, ncount * W * sizeof(double));
   };
   auto sel = [&](uint32_t stream, uint32_t step, const double* dst) -> int {
-    hipLaunchKernelGGL(k_uniform_sel, dim3((unsigned)((NW * nsr + 255) / 256)), dim3(256), 0, h->stream, seed, stream, step, N, (long)W, nsr, (double*)h->b_unif.p);
+    hipLaunchKernelGGL(k_uniform_sel, dim3((unsigned)((NW * d.nsr + 255) / 256)), dim3(256), 0, h->stream, seed, stream, step, N, (long)W, d.nsr, (double*)h->b_unif.p);
     TRY(check_launch(h, "k_uniform_sel"));
-    return copy_out(h, const_cast<double*>(dst), h->b_unif.p, NW * nsr * sizeof(double));
+    return copy_out(h, const_cast<double*>(dst), h->b_unif.p, NW * d.nsr * sizeof(double));
   };
   auto rots = [&](uint64_t sd, uint32_t step, const double* dst) -> int {
     hipLaunchKernelGGL((k_gen_rot<>), dim3((unsigned)((nrot + 63) / 64)), dim3(64), 0, h->stream, (int)nrot, sd, step, (double*)h->b_rot.p);
@@ -1008,14 +1005,14 @@ extern "C" int pqa_philox_dmc_tapes(pqa_handle_t* h, uint64_t seed, int nsteps, 
   for (int i = 0; i <= nsteps; ++i) {
     if (necp > 0) {  // energy evaluation i (0: the starting configuration; energy_dev's draws)
       TRY(rots(seed, (uint32_t)i, out->ecp_rot + (size_t)i * nrot * 9));
-      if (!batched) TRY(plane(PQA_STREAM_ECPMASK, (uint32_t)i, nrot, out->ecp_unif + (size_t)i * nrot * W));
-      else if (selu) TRY(sel(PQA_STREAM_ECPSEL, (uint32_t)i, out->ecp_unif + (size_t)i * NW * nsr));
+      if (!d.batched) TRY(plane(PQA_STREAM_ECPMASK, (uint32_t)i, nrot, out->ecp_unif + (size_t)i * NW * d.nu));
+      else if (d.selu) TRY(sel(PQA_STREAM_ECPSEL, (uint32_t)i, out->ecp_unif + (size_t)i * NW * d.nu));
     }
     if (i == nsteps) break;
     if (tm) {
       TRY(rots(seed ^ 0x9E3779B97F4A7C15ull, (uint32_t)i, out->tm_rot + (size_t)i * nrot * 9));
-      if (!batched) TRY(plane(PQA_STREAM_TMMASK, (uint32_t)i, nrot, out->tm_unif + (size_t)i * nrot * W));
-      else if (selu) TRY(sel(PQA_STREAM_TMSEL, (uint32_t)i, out->tm_unif + (size_t)i * NW * nsr));
+      if (!d.batched) TRY(plane(PQA_STREAM_TMMASK, (uint32_t)i, nrot, out->tm_unif + (size_t)i * NW * d.nu));
+      else if (d.selu) TRY(sel(PQA_STREAM_TMSEL, (uint32_t)i, out->tm_unif + (size_t)i * NW * d.nu));
       TRY(plane(PQA_STREAM_TM_U1, (uint32_t)i, (size_t)N, out->tm_u1 + (size_t)i * NW));
       TRY(plane(PQA_STREAM_TM_U2, (uint32_t)i, (size_t)N, out->tm_u2 + (size_t)i * NW));
     }
@@ -1078,11 +1075,7 @@ extern "C" int pqa_profile_query_part(pqa_handle_t* h, int64_t* launches, double
   TRY(prof_drain(h, h->prof_part));
   if (launches) *launches = h->prof_part.launches;
   if (total_ms) *total_ms = h->prof_part.ms;
-  if (groups) {
-    LwCtx lc;
-    TRY(lw_setup(h, false, lc));
-    *groups = lc.Gm;
-  }
+  if (groups) *groups = lw_geometry(h, h->W).Gm;
   return 0;
 }
 extern "C" int pqa_set_ecp_naip(pqa_handle_t* h, int32_t naip) {

@@ -850,9 +850,9 @@ static int create_ecp(pqa_handle* h, const pqa_system_t* sys) {
       const int naip = nch <= 2 ? 6 : 12;
       for (int i = 0; i < naip; ++i) { ptk.push_back(k); pti.push_back(i); }
     }
-    h->tm_P = (int)ptk.size();
-    TRY(upload_table(h, ptk.data(), ptk.size(), &h->d_ptk));
-    TRY(upload_table(h, pti.data(), pti.size(), &h->d_pti));
+    h->dmc.tm_P = (int)ptk.size();
+    TRY(upload_table(h, ptk.data(), ptk.size(), &h->dmc.d_ptk));
+    TRY(upload_table(h, pti.data(), pti.size(), &h->dmc.d_pti));
   }
   return 0;
 }

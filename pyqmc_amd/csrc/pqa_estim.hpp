@@ -9,6 +9,7 @@
 //
 // Weighted walker means (pqa_obdm, pqa_sq): the weight sum k_wsum (pqa_sr's too) and the column reduction k_wcol_means / k_wcol_fold.
 #pragma once
+#include "pqa_carver.hpp"
 #include "pqa_internal.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -311,22 +312,6 @@ constexpr size_t kChunkScratchBytes = size_t(256) << 20;
 inline long walker_chunk(long W, size_t bytes_per_walker) {  // walkers per chunk
   return std::max<long>(1, std::min<long>(W, (long)(kChunkScratchBytes / std::max<size_t>(bytes_per_walker, 1))));
 }
-
-// Bump carver of a scratch buffer.  A host function states its layout once, as a function that takes its pieces from a Carver; run over
-// a null base it only adds up the bytes (size()), run over the buffer it hands out the pointers, so the two cannot disagree.  Every piece
-// starts on an 8-byte boundary.
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b = nullptr) : base((char*)b) {}
-  template <class T>
-  T* take(size_t n) {
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += (n * sizeof(T) + 7) & ~(size_t)7;
-    return p;
-  }
-  size_t size() const { return off; }
-};
 
 // The periodic orbital launcher times its tile sizes on large launches and keeps the choice; an estimator's launches are not to
 // change the choices the handle's sweeps made themselves, so the tuning is restored on every exit.

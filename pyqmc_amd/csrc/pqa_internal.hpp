@@ -74,9 +74,6 @@ struct pqa_handle {
   int pbc_maxcls = PQA_PRE_NCUT;  // most distinct shell cut-offs any atom has (picks the pre-pass instantiation)
   int pbc_nw = 2;  // words per (atom, point) of the sorted image lists k_pbc_prepass writes (4 entries each)
   bool orb_general = false;  // PQA_ORB_GENERAL=1: big open handles evaluate orbitals by k_ao + k_mo_rows instead of the windowed k_orb (A/B, tests)
-  // pqa_dmc_continue: the next pqa_dmc_steps call takes the energies its predecessor ended with as its starting energies
-  bool dmc_continue = false, dmc_old_valid = false;
-  long dmc_old_W = 0;
   bool invert_attr = false;  // k_build_invert's dynamic-LDS limit raised (n > 90)
   bool big = false;         // more than 64 electrons or orbitals of a spin: general orbital path, wave-per-walker kernels (pqa_create)
   bool pbc_high_l = false;  // a periodic cell with g / h shells: orbitals through k_ao<.., 5> + k_mo_rows (pqa_orb_pbc.hip)
@@ -119,7 +116,7 @@ struct pqa_handle {
   DevBuf b_x, b_T[2], b_dsign[2], b_dlog[2], b_cache[2], b_aval, b_bval;
   DevBuf b_alt_x, b_alt_T[2], b_alt_dsign[2], b_alt_dlog[2], b_alt_cache[2], b_alt_aval, b_alt_bval, b_alt_j3u, b_rsidx;  // pqa_resample's other halves
   // scratch
-  DevBuf b_pts, b_motmp, b_out, b_widx, b_mask, b_ao, b_flag, b_newpos, b_aux, b_accept, b_accrec, b_acccnt, b_accw, b_dwrap, b_wrap, b_epass, b_eptw[2], b_econ[2], b_eu0[2], b_tves, b_pgdet, b_pbcd0, b_pbcmask, b_pbcth, b_tmuold;
+  DevBuf b_pts, b_motmp, b_out, b_widx, b_mask, b_ao, b_flag, b_newpos, b_aux, b_accept, b_accrec, b_acccnt, b_accw, b_dwrap, b_wrap, b_epass, b_eptw[2], b_econ[2], b_eu0[2], b_tves, b_pgdet, b_pbcd0, b_pbcmask, b_pbcth;
   int* d_colmap[2] = {nullptr, nullptr};  // [ndet_s][nmo_s] column of an orbital in a unique determinant, or -1
   int jas_fold_allowed = 1;  // PQA_JAS_FOLD=0: Voronoi reduction in every periodic Jastrow pair (A/B, bitwise check)
   int ecp_nchan = 0, ecp_nterm = 0;
@@ -170,10 +167,20 @@ struct pqa_handle {
   DevBuf b_obdm;
   hipEvent_t tb_ev[2] = {nullptr, nullptr};     // pqa_tbdm_sweep / pqa_obdm_sweeps: a chunk's ratios produced / consumed
   hipEvent_t tune_ev[2] = {nullptr, nullptr};   // periodic k_orb: timing of the tile-size trials (tp_tune)
-  DevBuf b_tpos, b_twgt, b_tlive, b_trat;
-  DevBuf b_tmcnt, b_tmoff, b_tmpass, b_tmamp, b_tmacc, b_tmidx, b_tmapos, b_tmu, b_tmtile, b_tmaoff, b_tmptw, b_tmmarks, b_tmbpos, b_tmbwgt, b_dmcw, b_dmcold, b_dmcr2, b_dmcout;
-  int tm_P = 0;
-  int *d_ptk = nullptr, *d_pti = nullptr;
+  DevBuf b_tpos, b_twgt, b_tlive, b_trat;  // pqa_tmoves: candidates of one electron; the first two also the candidate lists of a DMC step
+  DevBuf b_tmtile, b_tmmarks;  // scan_ints: tile sums; the marks of the energy pass's scans
+  // DMC (pqa_dmc_steps, pqa_dmcsteps.hip).  cont (pqa_dmc_continue): the next call starts from the energies its predecessor's last step left in
+  // b_old [2][W] (local energy, |v|^2), which therefore outlives the call; old_valid / old_W: the resident state is still the one that call
+  // ended with.  tm_P, d_ptk, d_pti: T-move points of the semi-local integrator over all ECP atoms, their atom and index in the atom's rule.
+  // b_call: every piece whose size the call's W, N, nsteps, necp and nsel fix, laid out by dmc_scratch (pqa_dmcsteps.hip).  Sized by a step's
+  // candidate count, with ensure's regrowth headroom: b_amp [2][ncand] ratio x weight and ratio, b_ptw [ncand] walker of a candidate (positions
+  // and weights: b_tpos, b_twgt; orbital rows: b_emo).
+  struct {
+    bool cont = false, old_valid = false;
+    long old_W = 0;
+    int tm_P = 0, *d_ptk = nullptr, *d_pti = nullptr;
+    DevBuf b_old, b_call, b_amp, b_ptw;
+  } dmc;
   DevBuf b_xt, b_Tt[2], b_rc[2], b_sel[2], b_auxt, b_kpart, b_rbuf, b_vbuf, b_act;  // lane-per-walker SoA mirrors (pqa_lw.hpp)
   // launch-per-move sweep on those planes (k_step_lw / k_step_pre, pqa_lw.hpp).  mode (PQA_LW): 1 lane-per-walker fused sweeps for
   // single-determinant handles, 0 the wave-per-walker kernels.  kb (PQA_LW_KB), electrons per Sherman-Morrison block: -1 automatic (4 for
@@ -417,7 +424,25 @@ LwState lw_state(pqa_handle* h);
 int lw_from_aos(pqa_handle* h, bool with_cache = true);
 int lw_to_aos(pqa_handle* h, bool with_cache);
 int sync_aos(pqa_handle* h);
-int lw_setup(pqa_handle* h, bool lw, LwCtx& c);
+LwCtx lw_geometry(const pqa_handle* h, long W);  // launch geometry of the lane-per-walker kernels: pure
+int lw_setup(pqa_handle* h, bool lw, LwCtx& c);  // the geometry, the state in the layout the sweep works on, and (lw) its scratch
+// One call of a propagation entry (pqa_vmc_sweeps, pqa_dmc_steps).  The entry fills in what it was called with: nsteps, tstep, seed, the sweep
+// tapes it brought (host, [nsteps][N][W][3] / [nsteps][N][W]; NULL: device draws) and nacc, the acceptance counts it keeps per step (DMC: 2).
+// step_call_open does what both do before their first step: the walker-major state first if from_aos (DMC: the starting energy and the first
+// T-moves read it), the device, the W check, the entry's own refusal (raised where the entries raised it: after the W check, and not for
+// nsteps <= 0, where the caller returns 0), saved_valid, the per-move scratch, the zeroed counts and wrap counters, the tape buffers, lw_setup.
+// step_moves fills one step's MoveBuf and copies that step's tapes in; it holds the rule that twisted handles get no wrap pointers.
+struct StepCall {
+  int nsteps = 0, nacc = 1, N = 0;
+  long W = 0;
+  double tstep = 0.0;
+  uint64_t seed = 0;
+  const double *gauss = nullptr, *unif = nullptr;
+  bool lw = false;  // lw_eligible; lc: lw_setup's geometry
+  LwCtx lc;
+};
+int step_call_open(pqa_handle* h, StepCall& c, bool from_aos, const char* refused);
+int step_moves(pqa_handle* h, const StepCall& c, int step, MoveBuf& mb);
 int sweep_electrons(pqa_handle* h, const MoveBuf& mb, const LwCtx& lc);
 void launch_step_real(pqa_handle* h, const LwState& L, const MoveBuf& mb, const StepArgs& a, int rowlen);
 void launch_flush_real(pqa_handle* h, const LwState& L, int s, long W, long w0, long w1, int j_lo, int j_hi, int nq, int rowlen, int n_s);
@@ -448,6 +473,14 @@ int sweep_ww(pqa_handle* h, const MoveBuf& mb);
 struct EnergyOpts { bool soa_current = false, aos_T_needed = true, assemble = true, slater_only = false, host_totals = false; };
 int energy_dev(pqa_handle* h, double threshold, const double* rot, const double* unif, uint64_t seed, uint32_t step, const EnergyOpts& o = {});
 // pqa_dmcsteps.hip
+// What a DMC call draws besides its sweeps' normals and uniforms (pqa_dmc_tapes_t), by the handle's ECP integrator; read by the tape
+// check and scratch of pqa_dmc_steps, its per-step staging and pqa_philox_dmc_tapes.  batched (pqa_set_ecp_batched): the energy passes and
+// the T-move tables come from that integrator, nsel slots per electron; selu: its selection drops points, so its nsr selection uniforms
+// per (electron, walker) exist.  tmoves: a step makes T-moves.  nrot: rotations of one energy evaluation or one step's T-moves, N x
+// max(necp, 1).  nu: uniforms per (electron, walker) of one evaluation or one step's T-moves — the necp mask uniforms, layout (N, necp, W),
+// or the batched integrator's nsr where selu, layout (N, W, nsr): ecp_unif / tm_unif advance by N W nu doubles, and neither exists where nu = 0.
+struct DmcDraws { bool batched, selu, tmoves; int nsel, nsr, nu; size_t nrot; };
+DmcDraws dmc_draws(const pqa_handle* h);
 int scan_ints(pqa_handle* h, const int* c, long* o, long n, long Wm, long* marks);
 // pqa_create.hip
 int set_mo(pqa_handle* h, int s, const double* mo_host);  // orbital coefficients of a spin: d_mo, the padded copies, the resident sweep's

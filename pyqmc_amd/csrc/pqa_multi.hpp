@@ -196,7 +196,7 @@ int multi_validate(pqa_handle* const* hs, int K, const char* fn) {
 
 // The opening of an entry.  The entry returns -2 when h is NULL (hs, K or the first handle missing), runs the argument checks that
 // come before the handles' own, then open().  moves: the call moves walkers or evaluates rows (every entry but pqa_mix's two, which
-// keep dmc_old_valid and grow no per-move scratch).
+// keep dmc.old_valid and grow no per-move scratch).
 struct MultiCall {
   pqa_handle* const* hs;
   const int K;
@@ -217,7 +217,7 @@ struct MultiCall {
     HIPCHK(hipSetDevice(h->device));
     // every handle's walker-major state current, its saved gradient_value rows dropped and its queued work done ...
     TRY(multi_each(hs, K, [&](pqa_handle* g, int) {
-      if (moves) g->dmc_old_valid = false;  // (as pqa_wf_update)
+      if (moves) g->dmc.old_valid = false;  // (as pqa_wf_update)
       TRY(sync_aos(g));
       TRY(jas_refresh(g));
       g->saved_valid = false;

@@ -1,4 +1,5 @@
-// pyqmc_amd C ABI implementation (host side): layout conversions, the fused VMC sweep (pqa_vmc_sweeps).
+// pyqmc_amd C ABI implementation (host side): layout conversions, the sweep routes, what the two propagation entries share (step_call_open,
+// step_moves) and the fused VMC sweep (pqa_vmc_sweeps).
 // See include/pyqmc_amd.h for the contract and pqa_internal.hpp for what the units share.
 #include "pqa_sweep_launch.hpp"
 
@@ -78,9 +79,9 @@ int sync_aos(pqa_handle* h) {
 
 
 // ---------------------------------------------------------------- one sweep over the electrons (shared by VMC and DMC)
-// Geometry of the lane-per-walker kernels and, when `lw`, the SoA copy of the state and its scratch.
-int lw_setup(pqa_handle* h, bool lw, LwCtx& c) {
-  const long W = h->W;
+// Geometry of the lane-per-walker kernels for W walkers.
+LwCtx lw_geometry(const pqa_handle* h, long W) {
+  LwCtx c;
   // thread groups per walker in k_step_lw.  Measured (tools/scratch/r3_step_abl*.sh, (H2O)8 step in ms at 4 / 8 / 16 groups):
   // 4096 walkers 6.38 / 5.15 / 4.67, 8192: 7.71 / 6.54 / 6.39, 16384: 10.7 / 9.8 / 11.1, 32768: 16.5 / 17.3 / 18.8, 65536: 30.8 / 32.7 / 37.3
   // 4 groups (a wave per group, k_step_lw's wide form) from 26624 walkers, 8 below, 16 below 16384 (re-measured at the end of round 4:
@@ -96,6 +97,12 @@ int lw_setup(pqa_handle* h, bool lw, LwCtx& c) {
   // ((H2O)8 at 4096 walkers: 4.08 ms per step with 5, 3.97 with 8, 3.94 with 11, 4.01 with 16; 8192: 5.97 / 5.80 / 5.90 / 6.00)
   const int kb = h->lw.kb < 0 ? (c.nmax >= 24 ? (W <= 8192 ? 8 : 5) : (c.nmax >= 16 ? 4 : 0)) : h->lw.kb;
   c.KB = (kb > 0) ? std::min(kb, std::max(c.nmax, 1)) : std::max(c.nmax, 1);  // KB = n: plain per-move update
+  return c;
+}
+// ... and the state where the sweep works on it: walker-major, or (`lw`) the SoA planes with the sweep's scratch.
+int lw_setup(pqa_handle* h, bool lw, LwCtx& c) {
+  const long W = h->W;
+  c = lw_geometry(h, W);
   if (!lw) TRY(sync_aos(h));
   if (lw) {
     if (!h->aos_stale) TRY(lw_from_aos(h));  // (stale walker-major arrays: the planes ARE the state)
@@ -277,27 +284,23 @@ int sweep_electrons(pqa_handle* h, const MoveBuf& mb, const LwCtx& lc) {
   }
 }
 
-extern "C" int pqa_vmc_sweeps(pqa_handle_t* h, double tstep, int nsteps, const double* gauss, const double* unif, double threshold,
-                              const double* ecp_rot, const double* ecp_unif, uint64_t seed, double* acceptance,
-                              double* energy_mean, uint8_t* accept_rec) {
-  h->dmc_old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
+int step_call_open(pqa_handle* h, StepCall& c, bool from_aos, const char* refused) {
+  if (from_aos) TRY(sync_aos(h));
   HIPCHK(hipSetDevice(h->device));
   if (h->W == 0) FAIL("state not initialised (call pqa_wf_recompute)");
-  if (nsteps <= 0) return 0;
-  if (h->ecpb_on && (ecp_rot || ecp_unif)) FAIL("the ECP tapes of pqa_vmc_sweeps have the semi-local integrator's layout: with pqa_set_ecp_batched the draws come from the device streams (replay through pqa_energy)");
-  const long W = h->W;
-  const int N = h->N;
+  if (c.nsteps <= 0) return 0;
+  if (refused) FAIL(refused);
+  const long W = c.W = h->W;
+  const int N = c.N = h->N;
   h->saved_valid = false;
-  const int nmo_max = std::max(h->nmo[0], h->nmo[1]);
+  const int nmo_max = std::max(std::max(h->nmo[0], h->nmo[1]), 1);
   TRY(ensure(h, h->b_newpos, (size_t)W * 3 * sizeof(double)));
   TRY(ensure(h, h->b_aux, (size_t)W * 8 * sizeof(double)));
   TRY(ensure(h, h->b_accept, (size_t)W));
-  TRY(ensure(h, h->b_acccnt, (size_t)nsteps * sizeof(int)));
-  TRY(ensure(h, h->b_motmp, (size_t)W * 5 * std::max(nmo_max, 1) * sizeof(double)));
-  const int nen = h->cplx ? 7 : 6;  // energy rows: complex determinants add Im(ecp) = Im(total)
-  TRY(ensure(h, h->b_means, (size_t)nsteps * nen * sizeof(double)));
+  TRY(ensure(h, h->b_acccnt, (size_t)c.nsteps * c.nacc * sizeof(int)));
+  TRY(ensure(h, h->b_motmp, (size_t)W * 5 * nmo_max * sizeof(double)));
   TRY(ensure(h, h->b_accw, (size_t)W * sizeof(int)));
-  HIPCHK(hipMemsetAsync(h->b_acccnt.p, 0, (size_t)nsteps * sizeof(int), h->stream));
+  HIPCHK(hipMemsetAsync(h->b_acccnt.p, 0, (size_t)c.nsteps * c.nacc * sizeof(int), h->stream));
   HIPCHK(hipMemsetAsync(h->b_accw.p, 0, (size_t)W * sizeof(int), h->stream));
   if (h->S.pbc) {  // wrap counters of this call's accepted moves (pqa_get_wrap)
     TRY(ensure(h, h->b_dwrap, (size_t)W * 3 * sizeof(int)));
@@ -305,32 +308,48 @@ extern "C" int pqa_vmc_sweeps(pqa_handle_t* h, double tstep, int nsteps, const d
     HIPCHK(hipMemsetAsync(h->b_wrap.p, 0, (size_t)W * N * 3 * sizeof(int), h->stream));
     h->wrap_W = W;
   }
-  if (gauss) TRY(ensure(h, h->b_gauss, (size_t)N * W * 3 * sizeof(double)));
-  if (unif) TRY(ensure(h, h->b_unif, (size_t)N * W * sizeof(double)));
+  if (c.gauss) TRY(ensure(h, h->b_gauss, (size_t)N * W * 3 * sizeof(double)));
+  if (c.unif) TRY(ensure(h, h->b_unif, (size_t)N * W * sizeof(double)));
+  c.lw = lw_eligible(h);
+  return lw_setup(h, c.lw, c.lc);
+}
+int step_moves(pqa_handle* h, const StepCall& c, int step, MoveBuf& mb) {
+  const size_t NW = (size_t)c.N * c.W;
+  mb = MoveBuf{};
+  mb.newpos = (double*)h->b_newpos.p; mb.aux = (double*)h->b_aux.p; mb.accept = (uint8_t*)h->b_accept.p;
+  mb.acc_w = (int*)h->b_accw.p; mb.seed = c.seed; mb.step = (uint32_t)step; mb.tstep = c.tstep;
+  if (h->S.pbc && !h->twist) { mb.dwrap = (int*)h->b_dwrap.p; mb.wrap = (int*)h->b_wrap.p; }  // twisted handles keep the walkers unfolded
+  if (c.gauss) TRY(copy_in(h, h->b_gauss.p, c.gauss + (size_t)step * NW * 3, NW * 3 * sizeof(double)));
+  if (c.unif) TRY(copy_in(h, h->b_unif.p, c.unif + (size_t)step * NW, NW * sizeof(double)));
+  mb.gauss = c.gauss ? (const double*)h->b_gauss.p : nullptr;
+  mb.unif = c.unif ? (const double*)h->b_unif.p : nullptr;
+  return 0;
+}
+
+extern "C" int pqa_vmc_sweeps(pqa_handle_t* h, double tstep, int nsteps, const double* gauss, const double* unif, double threshold,
+                              const double* ecp_rot, const double* ecp_unif, uint64_t seed, double* acceptance,
+                              double* energy_mean, uint8_t* accept_rec) {
+  h->dmc.old_valid = false;  // (the state pqa_dmc_continue refers to is gone)
+  StepCall call;
+  call.nsteps = nsteps; call.tstep = tstep; call.seed = seed; call.gauss = gauss; call.unif = unif;
+  const char* refused = "the ECP tapes of pqa_vmc_sweeps have the semi-local integrator's layout: with pqa_set_ecp_batched the draws come from the device streams (replay through pqa_energy)";
+  TRY(step_call_open(h, call, false, h->ecpb_on && (ecp_rot || ecp_unif) ? refused : nullptr));
+  if (nsteps <= 0) return 0;
+  const long W = call.W;
+  const bool lw = call.lw;
+  const int N = call.N, nen = h->cplx ? 7 : 6;  // energy rows: complex determinants add Im(ecp) = Im(total)
+  TRY(ensure(h, h->b_means, (size_t)nsteps * nen * sizeof(double)));
   if (accept_rec) TRY(ensure(h, h->b_accrec, (size_t)N * W));
   const size_t nrot = (size_t)N * std::max(h->necp, 1);
-  const bool lw = lw_eligible(h);
-  LwCtx lc;
-  TRY(lw_setup(h, lw, lc));
   h->draw.ahead_valid = false;
   for (int step = 0; step < nsteps; ++step) {
-    MoveBuf mb{};
-    mb.newpos = (double*)h->b_newpos.p; mb.aux = (double*)h->b_aux.p; mb.accept = (uint8_t*)h->b_accept.p;
-    mb.acc_w = (int*)h->b_accw.p; mb.seed = seed; mb.step = (uint32_t)step; mb.tstep = tstep;
-    if (h->S.pbc && !h->twist) { mb.dwrap = (int*)h->b_dwrap.p; mb.wrap = (int*)h->b_wrap.p; }  // twisted handles keep the walkers unfolded
-    if (gauss) {
-      TRY(copy_in(h, h->b_gauss.p, gauss + (size_t)step * N * W * 3, (size_t)N * W * 3 * sizeof(double)));
-      mb.gauss = (const double*)h->b_gauss.p;
-    }
-    if (unif) {
-      TRY(copy_in(h, h->b_unif.p, unif + (size_t)step * N * W, (size_t)N * W * sizeof(double)));
-      mb.unif = (const double*)h->b_unif.p;
-    }
+    MoveBuf mb;
+    TRY(step_moves(h, call, step, mb));
     if (accept_rec) mb.accept_rec = (uint8_t*)h->b_accrec.p;
     h->r8.jsx_current = false;
     h->r8.xaos_next = energy_mean != nullptr && h->necp > 0;  // (consumed by sweep_r8 only)
     h->draw.on_device = false;
-    TRY(sweep_electrons(h, mb, lc));
+    TRY(sweep_electrons(h, mb, call.lc));
     h->r8.xaos_next = false;
     if (h->draw.on_device && energy_mean && step + 1 < nsteps && W >= 16384) TRY(draws_ahead(h, seed, (uint32_t)(step + 1)));
     // small shards: the accepted-move count, the energy rows and their means in one launch at the end of the step (three launches of ~5 us

@@ -12,7 +12,7 @@ walkers (``avg_resident(wf, weights=w)``), nothing but the means crosses the bus
 walkers weighted in NumPy.
 
 An energy accumulator with ``use_old_ecp=False`` (the batched ECP integrator, jax_ecp.py) runs on every route: the device then takes the
-energy and the T-move candidates from that integrator (csrc/pqa_tmb.hpp) and the replay tapes have its layout (``_record_tapes_batched``).
+energy and the T-move candidates from that integrator (csrc/pqa_tmb.hpp) and the replay tapes have its layout (``tape_shapes``).
 
 ``rng`` (optional, tests) supplies the random draws to replay the reference's:
 ``normal(W)->(W,3)``, ``rand(W)->(W,)``, ``rand1()->float``, ``rot()->(3,3)``, ``random(W)->(W,)``.
@@ -28,30 +28,51 @@ def _batched_selection(acc):
     return np.asarray(acc.ecp.naip), int(acc.ecp.nselect_deterministic), int(acc.ecp.nselect_random)
 
 
-def _record_tapes_batched(rng, nsteps, N, necp, W, tmoves, batched):
-    """``_record_tapes`` for the batched ECP integrator (jax_ecp.py).  Per evaluation and electron the reference draws one rotation for
-    every ECP atom that has points, in atom order (``evaluate_vl`` :160-222; the others get the identity here, nothing reads it), and then,
-    only when the selection drops points, ``nselect_random`` uniform vectors (``downselect_move_info`` :225-290, draw j = 0..nsr-1).
-    ``ecp_unif`` / ``tm_unif`` (..., N, W, nsr) are left out when no selection draw is made."""
-    naip, nsd, nsr = batched
-    select = nsd + nsr < int(np.sum(naip)) and nsr > 0
-    t = {"gauss": np.empty((nsteps, N, W, 3)), "unif": np.empty((nsteps, N, W))}
-    t["ecp_rot"] = np.tile(np.eye(3), (nsteps + 1, N, necp, 1, 1))
-    if select:
-        t["ecp_unif"] = np.empty((nsteps + 1, N, W, nsr))
+def tape_shapes(nsteps, N, necp, W, tmoves, batched=None):
+    """{name: shape} of the replay tapes of ``pqa_dmc_steps`` (``pqa_dmc_tapes_t``) for ``nsteps`` steps: the sweeps' ``gauss`` / ``unif``,
+    per energy evaluation (``nsteps + 1``: the starting configuration first) ``ecp_rot`` / ``ecp_unif`` and, with ``tmoves``, per step the
+    four T-move tapes.  ``batched``: ``_batched_selection`` of the energy accumulator — ``ecp_unif`` / ``tm_unif`` are then that
+    integrator's selection uniforms (..., N, W, nsr), and left out when the selection drops no point (no such draw is made)."""
+    unif = (N, necp, W)
+    if batched is not None and necp:
+        naip, nsd, nsr = batched
+        unif = (N, W, nsr) if nsd + nsr < int(np.sum(naip)) and nsr > 0 else None
+    t = {"gauss": (nsteps, N, W, 3), "unif": (nsteps, N, W)}
+    for on, key, n in ((necp, "ecp", nsteps + 1), (tmoves, "tm", nsteps)):
+        if on:
+            t[key + "_rot"] = (n, N, necp, 3, 3)
+            if unif is not None:
+                t[key + "_unif"] = (n,) + unif
     if tmoves:
-        t["tm_rot"] = np.tile(np.eye(3), (nsteps, N, necp, 1, 1))
-        t["tm_u1"], t["tm_u2"] = np.empty((nsteps, N, W)), np.empty((nsteps, N, W))
-        if select:
-            t["tm_unif"] = np.empty((nsteps, N, W, nsr))
+        t["tm_u1"], t["tm_u2"] = (nsteps, N, W), (nsteps, N, W)
+    return t
 
-    def table_draws(rot, unif, i, e):
+
+def _record_tapes(rng, nsteps, N, necp, W, tmoves, batched=None):
+    """Draw everything ``nsteps`` steps consume from ``rng`` in the reference's order (dmc.py:146-196) and lay it out as
+    the replay tapes of ``pqa_dmc_steps`` (``tape_shapes``).  ``batched``: ``_batched_selection`` of the energy accumulator — the batched
+    ECP integrator's draws and layout."""
+    batched = batched if necp else None
+    t = {k: np.empty(shape) for k, shape in tape_shapes(nsteps, N, necp, W, tmoves, batched).items()}
+
+    def semilocal_draws(rot, unif, i, e):  # one electron's grids (eval_ecp.py): per ECP atom the mask uniforms, then the rotation
         for k in range(necp):
-            if naip[k] > 0:
+            t[unif][i, e, k] = rng.random(W)
+            t[rot][i, e, k] = rng.rot()
+
+    def batched_draws(rot, unif, i, e):
+        # one electron's table (jax_ecp.py): a rotation for every ECP atom that has points, in atom order (``evaluate_vl`` :160-222; the others
+        # get the identity, nothing reads it); then, only when the selection drops points, ``nselect_random`` uniform vectors
+        # (``downselect_move_info`` :225-290, draw j = 0..nsr-1)
+        t[rot][i, e] = np.eye(3)
+        for k in range(necp):
+            if batched[0][k] > 0:
                 t[rot][i, e, k] = rng.rot()
-        if select:
-            for j in range(nsr):
+        if unif in t:
+            for j in range(batched[2]):
                 t[unif][i, e, :, j] = rng.random(W)
+
+    table_draws = semilocal_draws if batched is None else batched_draws
 
     def energy_draws(i):
         for e in range(N):
@@ -71,60 +92,28 @@ def _record_tapes_batched(rng, nsteps, N, necp, W, tmoves, batched):
     return t
 
 
-def _record_tapes(rng, nsteps, N, necp, W, tmoves, batched=None):
-    """Draw everything ``nsteps`` steps consume from ``rng`` in the reference's order (dmc.py:146-196) and lay it out as
-    the replay tapes of ``pqa_dmc_steps``.  ``batched``: ``_batched_selection`` of the energy accumulator — the batched ECP
-    integrator's draws and layout (``_record_tapes_batched``)."""
-    if batched is not None and necp:
-        return _record_tapes_batched(rng, nsteps, N, necp, W, tmoves, batched)
-    t = {"gauss": np.empty((nsteps, N, W, 3)), "unif": np.empty((nsteps, N, W))}
-    if necp:
-        t["ecp_rot"], t["ecp_unif"] = np.empty((nsteps + 1, N, necp, 3, 3)), np.empty((nsteps + 1, N, necp, W))
-    if tmoves:
-        t["tm_rot"], t["tm_unif"] = np.empty((nsteps, N, necp, 3, 3)), np.empty((nsteps, N, necp, W))
-        t["tm_u1"], t["tm_u2"] = np.empty((nsteps, N, W)), np.empty((nsteps, N, W))
-
-    def energy_draws(i):
-        for e in range(N):
-            for k in range(necp):
-                t["ecp_unif"][i, e, k] = rng.random(W)
-                t["ecp_rot"][i, e, k] = rng.rot()
-
-    energy_draws(0)
-    for i in range(nsteps):
-        if tmoves:
-            for e in range(N):
-                for k in range(necp):
-                    t["tm_unif"][i, e, k] = rng.random(W)
-                    t["tm_rot"][i, e, k] = rng.rot()
-                t["tm_u1"][i, e] = [rng.rand1() for _ in range(W)]
-                t["tm_u2"][i, e] = rng.rand(W)
-        for e in range(N):
-            t["gauss"][i, e] = rng.normal(W)
-            t["unif"][i, e] = rng.rand(W)
-        energy_draws(i + 1)
-    return t
+def _replay_tapes(rng, dev, acc, nsteps, W, N):
+    """The replay tapes of ``nsteps`` steps drawn from ``rng`` (None: none, the device draws)."""
+    necp = getattr(dev, "necp", 0)
+    return None if rng is None else _record_tapes(rng, nsteps, N, necp, W, acc.has_nonlocal_moves() and necp > 0, batched=_batched_selection(acc))
 
 
 def _propagate_fused(dev, wf, configs, weights, tstep, branchcut, e_trial, e_est, nsteps, acc, name, rng, state_current=False):
     """``dmc_propagate`` through ``pqa_dmc_steps``: the whole step loop stays on the device."""
     from .energy import KEYS
+    from .vmc import _fetch
 
     W, N = configs.configs.shape[:2]
-    necp = getattr(dev, "necp", 0)
-    tmoves = acc.has_nonlocal_moves() and necp > 0
     if not state_current:  # the reference recomputes at the start of every block (dmc.py:155)
         wf.recompute(configs)
     acc.bind(dev)
-    tapes = None if rng is None else _record_tapes(rng, nsteps, N, necp, W, tmoves, batched=_batched_selection(acc))
+    tapes = _replay_tapes(rng, dev, acc, nsteps, W, N)
     w = np.ascontiguousarray(weights, dtype=np.float64)
     # like vmc_worker: the device Philox streams are keyed by a seed drawn from numpy's global generator, so
     # numpy.random.seed() controls reproducibility and ranks that seed numpy differently get independent streams
     avg, stat = dev.dmc_steps(tstep, nsteps, w, branchcut, e_trial, e_est, threshold=acc.threshold, tapes=tapes,
                               seed=int(np.random.randint(0, 2**31 - 1)))
     weights[:] = w
-    from .vmc import _fetch
-
     _fetch(dev, configs)  # (periodic: folded positions + wrap counters; twisted handles keep true coordinates on the device)
     wts = avg[:, 6]
     rel = wts / wts.mean()
@@ -139,28 +128,25 @@ def _propagate_fused(dev, wf, configs, weights, tstep, branchcut, e_trial, e_est
     return out, configs, weights
 
 
-def _propagate_host_accumulators(dev, wf, configs, weights, tstep, branchcut, e_trial, e_est, nsteps, accumulators, ekey, state_current=False,
-                                 rng=None):
+def _propagate_stepwise(dev, wf, configs, weights, tstep, branchcut, e_trial, e_est, nsteps, accumulators, ekey, state_current, rng, others, fetch):
     """``dmc_propagate`` with further accumulators (density matrices, ...) next to the energy: every step is one device call
-    (``pqa_dmc_steps`` with ``nsteps = 1``), after which the walkers come back and the other accumulators run on the host over
-    the protocol entry points, weight-averaged as in dmc.py:205-221.  From the second step on the device starts from the
-    energies its previous step ended with (``pqa_dmc_continue``), as the reference carries ``eloc`` / ``v2`` from step to step
-    (dmc.py:148-149, :199-200): same trajectory as the all-device loop, one energy evaluation per step.  ``rng`` replays the
-    reference's draws (tests)."""
+    (``pqa_dmc_steps`` with ``nsteps = 1``), after which ``others(accumulator, w, mean weight)`` gives each other accumulator's weighted
+    walker means of the step (dmc.py:205-221).  From the second step on the device starts from the energies its previous step ended with
+    (``pqa_dmc_continue``), as the reference carries ``eloc`` / ``v2`` from step to step (dmc.py:148-149, :199-200): same trajectory as
+    the all-device loop, one energy evaluation per step.  ``fetch``: the walkers come back after every step; else once, after the last.
+    ``rng`` replays the reference's draws (tests).  (The complex ``ecp`` / ``total`` branch is the host route's: the resident route admits
+    real handles only, ``dmc_accumulator_route``, and never takes it.)"""
     from .energy import KEYS
     from .vmc import _fetch
 
     acc, name = accumulators[ekey[0]], ekey[0]
-    W = configs.configs.shape[0]
+    W, N = configs.configs.shape[:2]
     if not state_current:
         wf.recompute(configs)
     acc.bind(dev)
     w = np.ascontiguousarray(weights, dtype=np.float64)
     df = []
-    tapes = None
-    if rng is not None:
-        N, necp = configs.configs.shape[1], getattr(dev, "necp", 0)
-        tapes = _record_tapes(rng, nsteps, N, necp, W, acc.has_nonlocal_moves() and necp > 0, batched=_batched_selection(acc))
+    tapes = _replay_tapes(rng, dev, acc, nsteps, W, N)
     for i in range(nsteps):
         step_tapes = None
         if tapes is not None:  # this step's slice; the energy draws: [starting configuration (used by the first call only), this step]
@@ -169,21 +155,31 @@ def _propagate_host_accumulators(dev, wf, configs, weights, tstep, branchcut, e_
         # device kept are then gone and the step starts from a fresh evaluation, as the first one does
         avg, stat = dev.dmc_steps(tstep, 1, w, branchcut, e_trial, e_est, threshold=acc.threshold, tapes=step_tapes,
                                   seed=int(np.random.randint(0, 2**31 - 1)), cont=i > 0 and dev.dmc_can_continue())
-        _fetch(dev, configs)
+        if fetch:
+            _fetch(dev, configs)
         wavg = float(avg[0, 6])
         d = {name + k: avg[0, i] for i, k in enumerate(KEYS[:6])}
         if avg.shape[1] > 7:
             for k in ("ecp", "total"):
                 d[name + k] = complex(d[name + k], avg[0, 7])
         for k, other in accumulators.items():
-            if k == name:
-                continue
-            for m, res in other(configs, wf).items():
-                d[k + m] = np.einsum("...i,i...->...", w, res) / (W * wavg)
+            if k != name:
+                d.update({k + m: res for m, res in others(other, w, wavg).items()})
         d["weight"], d["acceptance"], d["tmove_acceptance"] = wavg, stat[0, 0], stat[0, 1]
         df.append(d)
+    if not fetch:
+        _fetch(dev, configs)
     weights[:] = w
     return combine_steps(df), configs, weights
+
+
+def _propagate_host_accumulators(dev, wf, configs, weights, tstep, branchcut, e_trial, e_est, nsteps, accumulators, ekey, state_current=False,
+                                 rng=None):
+    """``_propagate_stepwise`` with the walkers fetched after every step and the other accumulators run on the host over the protocol
+    entry points, their per-walker results weighted in NumPy."""
+    W = configs.configs.shape[0]
+    others = lambda other, w, wavg: {m: np.einsum("...i,i...->...", w, res) / (W * wavg) for m, res in other(configs, wf).items()}  # noqa: E731
+    return _propagate_stepwise(dev, wf, configs, weights, tstep, branchcut, e_trial, e_est, nsteps, accumulators, ekey, state_current, rng, others, True)
 
 
 def combine_steps(df):
@@ -198,47 +194,12 @@ def combine_steps(df):
 
 def _propagate_resident_accumulators(dev, wf, configs, weights, tstep, branchcut, e_trial, e_est, nsteps, accumulators, ekey, state_current=False,
                                      rng=None):
-    """``dmc_propagate`` with further accumulators, all of them evaluated from the resident state: every step is the device call of
-    ``_propagate_host_accumulators`` (same seed draws, same continuation), after which each other accumulator's
-    ``avg_resident(wf, weights=w)`` gives the step's weighted walker mean sum_w w_w res_w / sum_w w_w (dmc.py:205-207) on the device.
-    Neither the walkers nor a per-walker array cross the bus during the block: the walkers are fetched once after the last step
-    (periodic containers: after every step, for the wrap counters, which ``pqa_get_wrap`` hands out as increments)."""
-    from .energy import KEYS
-    from .vmc import _fetch
-
-    acc, name = accumulators[ekey[0]], ekey[0]
-    W = configs.configs.shape[0]
-    if not state_current:
-        wf.recompute(configs)
-    acc.bind(dev)
-    w = np.ascontiguousarray(weights, dtype=np.float64)
-    df = []
-    tapes = None
-    if rng is not None:
-        N, necp = configs.configs.shape[1], getattr(dev, "necp", 0)
-        tapes = _record_tapes(rng, nsteps, N, necp, W, acc.has_nonlocal_moves() and necp > 0, batched=_batched_selection(acc))
-    per_step_fetch = bool(getattr(dev, "pbc", False))
-    for i in range(nsteps):
-        step_tapes = None
-        if tapes is not None:  # (sliced as on the host route)
-            step_tapes = {k: (np.stack([v[0 if i == 0 else i], v[i + 1]]) if k.startswith("ecp_") else v[i:i + 1]) for k, v in tapes.items()}
-        avg, stat = dev.dmc_steps(tstep, 1, w, branchcut, e_trial, e_est, threshold=acc.threshold, tapes=step_tapes,
-                                  seed=int(np.random.randint(0, 2**31 - 1)), cont=i > 0 and dev.dmc_can_continue())
-        if per_step_fetch:
-            _fetch(dev, configs)
-        wavg = float(avg[0, 6])
-        d = {name + k: avg[0, i] for i, k in enumerate(KEYS[:6])}
-        for k, other in accumulators.items():
-            if k == name:
-                continue
-            for m, res in other.avg_resident(wf, weights=w).items():
-                d[k + m] = res
-        d["weight"], d["acceptance"], d["tmove_acceptance"] = wavg, stat[0, 0], stat[0, 1]
-        df.append(d)
-    if not per_step_fetch:
-        _fetch(dev, configs)
-    weights[:] = w
-    return combine_steps(df), configs, weights
+    """``_propagate_stepwise`` with every other accumulator evaluated from the resident state: ``avg_resident(wf, weights=w)`` gives the
+    step's weighted walker mean sum_w w_w res_w / sum_w w_w (dmc.py:205-207) on the device.  Neither the walkers nor a per-walker array
+    cross the bus during the block: the walkers are fetched once after the last step (periodic containers: after every step, for the
+    wrap counters, which ``pqa_get_wrap`` hands out as increments)."""
+    return _propagate_stepwise(dev, wf, configs, weights, tstep, branchcut, e_trial, e_est, nsteps, accumulators, ekey, state_current, rng,
+                               lambda other, w, wavg: other.avg_resident(wf, weights=w), bool(getattr(dev, "pbc", False)))
 
 
 ACCUMULATOR_ROUTES = (None, "resident", "host")

@@ -418,10 +418,7 @@ class DeviceWF:
         acc = np.empty(nsteps)
         en = np.empty((nsteps, 7 if self.cplx else 6)) if energy else None
         rec = np.empty((nsteps, self.N, self.W), dtype=np.uint8) if record else None
-        g = None if gauss is None else _ffi.f64(gauss)
-        u = None if unif is None else _ffi.f64(unif)
-        er = None if ecp_rot is None else _ffi.f64(ecp_rot)
-        eu = None if ecp_unif is None else _ffi.f64(ecp_unif)
+        g, u, er, eu = (None if a is None else _ffi.f64(a) for a in (gauss, unif, ecp_rot, ecp_unif))
         self.call("pqa_vmc_sweeps", float(tstep), int(nsteps), _ffi.ptr(g), _ffi.ptr(u), float(threshold), _ffi.ptr(er),
                   _ffi.ptr(eu), int(seed), _ffi.ptr(acc), _ffi.ptr(en), _ffi.ptr(rec))
         if energy and self.cplx:
@@ -437,32 +434,13 @@ class DeviceWF:
 
     def philox_dmc_tapes(self, seed, nsteps, W, tmoves=True):
         """The draws ``dmc_steps(..., tapes=None, seed=seed)`` makes for walkers 0..W-1, as the tape dictionary ``dmc_steps`` takes
-        (``pqa_philox_dmc_tapes``): lets the CPU oracle replay a device-RNG DMC block.  A handle in batched ECP mode
-        (``set_ecp_batched``) gets that integrator's layout: ``ecp_unif`` (nsteps + 1, N, W, nsr) / ``tm_unif`` (nsteps, N, W, nsr), and
-        neither where the selection drops nothing."""
-        N, necp = self.N, getattr(self, "necp", 0)
-        t = {"gauss": np.empty((nsteps, N, W, 3)), "unif": np.empty((nsteps, N, W))}
-        batched = getattr(self, "_ecpb", None) if necp else None
-        if batched is not None:
-            naip, nsd, nsr = batched
-            select = nsd + nsr < int(np.sum(naip)) and nsr > 0
-            t["ecp_rot"] = np.empty((nsteps + 1, N, necp, 3, 3))
-            if select:
-                t["ecp_unif"] = np.empty((nsteps + 1, N, W, nsr))
-            if tmoves:
-                t["tm_rot"] = np.empty((nsteps, N, necp, 3, 3))
-                t["tm_u1"], t["tm_u2"] = np.empty((nsteps, N, W)), np.empty((nsteps, N, W))
-                if select:
-                    t["tm_unif"] = np.empty((nsteps, N, W, nsr))
-        elif necp:
-            t["ecp_rot"], t["ecp_unif"] = np.empty((nsteps + 1, N, necp, 3, 3)), np.empty((nsteps + 1, N, necp, W))
-            if tmoves:
-                t["tm_rot"], t["tm_unif"] = np.empty((nsteps, N, necp, 3, 3)), np.empty((nsteps, N, necp, W))
-                t["tm_u1"], t["tm_u2"] = np.empty((nsteps, N, W)), np.empty((nsteps, N, W))
-        tp = _ffi.DmcTapes()
-        for name, _ in _ffi.DmcTapes._fields_:
-            if name in t:
-                setattr(tp, name, t[name].ctypes.data)
+        (``pqa_philox_dmc_tapes``; shapes: ``dmc.tape_shapes``, a handle in batched ECP mode gets that integrator's layout): lets the CPU
+        oracle replay a device-RNG DMC block."""
+        from .dmc import tape_shapes
+
+        necp = getattr(self, "necp", 0)
+        t = {k: np.empty(shape) for k, shape in tape_shapes(nsteps, self.N, necp, W, tmoves and necp > 0, getattr(self, "_ecpb", None)).items()}
+        tp, _ = _ffi.dmc_tapes(t)
         self.call("pqa_philox_dmc_tapes", int(seed), int(nsteps), int(W), C.addressof(tp))
         return t
 
@@ -496,15 +474,7 @@ class DeviceWF:
         Returns (step_avg (nsteps,7) — (nsteps,8) for complex wave functions —, step_acc (nsteps,2))."""
         assert weights.dtype == np.float64 and weights.flags.c_contiguous and weights.shape == (self.W,)
         avg, acc = np.empty((nsteps, 8 if self.cplx else 7)), np.empty((nsteps, 2))  # complex: + the weighted mean of Im ecp
-        tp, keep = None, []
-        if tapes is not None:
-            tp = _ffi.DmcTapes()
-            for name, _ in _ffi.DmcTapes._fields_:
-                a = tapes.get(name)
-                if a is not None:
-                    a = _ffi.f64(a)
-                    keep.append(a)
-                    setattr(tp, name, a.ctypes.data)
+        tp, keep = (None, []) if tapes is None else _ffi.dmc_tapes(tapes)
         if cont:  # start from the energies the previous call ended with (pqa_dmc_continue)
             self.call("pqa_dmc_continue", 1)
         self.call("pqa_dmc_steps", float(tstep), int(nsteps), float(branchcut), float(e_trial), float(e_est), float(threshold),
