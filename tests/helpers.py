@@ -67,6 +67,15 @@ def case(name):
     raise KeyError(name)
 
 
+def rotations(rng, *shape):
+    """(*shape, 3, 3) rotation matrices from ``rng``'s normalised quaternions: the ECP quadrature's rotations on a tape."""
+    q = rng.standard_normal(shape + (4,))
+    w, x, y, z = np.moveaxis(q / np.linalg.norm(q, axis=-1, keepdims=True), -1, 0)
+    return np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], -1),
+                     np.stack([2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)], -1),
+                     np.stack([2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1)], -2)
+
+
 def relerr(a, b):
     a, b = np.asarray(a), np.asarray(b)
     scale = max(np.max(np.abs(b)), 1e-300) if b.size else 1.0

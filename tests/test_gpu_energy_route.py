@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import helpers
-from helpers import pbc_jastrow_coeffs
+from helpers import pbc_jastrow_coeffs, rotations
 from pyqmc_amd import systems
 
 pytestmark = pytest.mark.gpu
@@ -53,14 +53,6 @@ def case(name, *routes, **env):
 
 def route(kinetic, lists, orbitals, points):
     return f"kinetic={kinetic} lists={lists} orbitals={orbitals} points={points}"
-
-
-def rotations(rng, *shape):
-    q = rng.standard_normal(shape + (4,))
-    w, x, y, z = np.moveaxis(q / np.linalg.norm(q, axis=-1, keepdims=True), -1, 0)
-    return np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], -1),
-                     np.stack([2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)], -1),
-                     np.stack([2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1)], -2)
 
 
 def ecp_tapes(dev, nsteps, seed=21):

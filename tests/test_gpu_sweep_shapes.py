@@ -250,7 +250,7 @@ def test_walkers_that_share_a_block_are_independent(monkeypatch, capfd):
         _, _, rec = dev.vmc_sweeps(tstep, c.ns, gauss=gauss[:, :, order].copy(), unif=unif[:, :, order].copy(), energy=False, record=True)
         inv, _, logpsi = _state(c, wf, dev)
         got = {"rec": np.moveaxis(rec, 2, 0), "x": dev.configs(), "logpsi": logpsi, "inv_up": inv[0][:, 0], "inv_dn": inv[1][:, 0],
-               "rows": np.real(dev.energy(10.0, seed=9))[[0, 1, 2, 4]].T}  # ke, ee, ei, grad2 (the ECP row draws its grid per walker index)
+               "rows": np.real(dev.energy(10.0, seed=9))[[0, 1, 2, 4]].T}  # ke, ee, ei, grad2 (the ECP row draws its grid per walker index: test_gpu_ecp_shapes.py)
         back = np.argsort(order)
         outs.append({k: v[back] for k, v in got.items()})
         errs += capfd.readouterr()[1]
